@@ -57,6 +57,12 @@ def parse(argv=None):
                          "summed in chunk order: the same bits on any number of ranks (adrates_amd/distributed.py)")
     ap.add_argument("--print-spawn-command", action="store_true",
                     help="with --gpus N > 1 and no WORLD_SIZE: print the launcher command instead of running it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all): agg = the portfolio ladder [pv, delta[P], gamma[P*P]] as the "
+                         "step left it (all-reduced over the ranks; the XCCY ladders follow the OIS one), and pv / delta "
+                         "/ gamma of a fixed, seeded sample of each per-trade book (<book>trade_index holds the sampled "
+                         "trade indices); the inputs are seeded, so two builds can be compared file for file")
     return ap.parse_args(argv)
 
 
@@ -223,6 +229,39 @@ def profile_is_stale(summary):
     if have != now:
         return f"was taken on sources {have[:12]}, the running library is built from {now[:12]}"
     return ""
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # array data; with the .npy headers the files stay under 64 MB
+DUMP_SAMPLE_TRADES = 4096        # per book; fewer when the books' rows would not fit the limit
+DUMP_SEED = 20240501
+
+
+def dump_outputs(out_dir, agg, books):
+    """--dump-outputs: `agg` is the step's aggregate buffer, `books` [(name prefix, pv, delta, gamma)] the per-trade device
+    outputs (None where not computed).  The full per-trade outputs are n x (1 + P + P*P) doubles (8 GB at the headline
+    size), so each book contributes the rows of a seeded sample of its trades, the same rows in every run."""
+    import numpy as np
+    import torch
+    arrays = {"agg": agg.detach().cpu().numpy()}
+    books = [(prefix, [(k, t) for k, t in (("pv", pv), ("delta", delta), ("gamma", gamma)) if t is not None])
+             for prefix, pv, delta, gamma in books]
+    books = [(prefix, outs) for prefix, outs in books if outs]
+    row_bytes = sum(8 + sum(8 * t[0].numel() for _, t in outs) for _, outs in books)
+    k = min(DUMP_SAMPLE_TRADES, (DUMP_LIMIT_BYTES - arrays["agg"].nbytes) // max(row_bytes, 1))
+    for prefix, outs in books:
+        n = outs[0][1].shape[0]
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, k), replace=False))
+        sel = torch.from_numpy(idx).to(outs[0][1].device)
+        arrays[prefix + "trade_index"] = idx.astype(np.float64)
+        for name, t in outs:
+            arrays[prefix + name] = t.index_select(0, sel).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "files": sorted(arrays), "bytes": total, "sampled_trades_per_book": int(k)}
 
 
 def measured_traffic(n, want_gamma, kind, interp):
@@ -489,6 +528,10 @@ def main(argv=None):
         kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     else:
         kern_ms = ev[0][0].elapsed_time(ev[0][1]) / args.steps
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, aggs[(step_no[0] - 1) & 1],
+                              [("", pv, delta, gamma)] + [(f"xccy{i}_", x[2], x[3], x[4]) for i, x in enumerate(xccy)])
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if use_dist:
         reduce_small(t, dist.ReduceOp.MAX)
@@ -588,6 +631,8 @@ def main(argv=None):
         line["upload_ms"] = {"trades": upload_ms, "what": "adr_trades_upload of rank 0's batch: host-side construction of "
                              "the row tables + H2D copies, blocking, once per portfolio; outside `value`",
                              "input_bytes": in_bytes}
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if allreduce_check is not None:
             line["allreduce_check"] = allreduce_check
             spot_ok = spot_ok and allreduce_check["status"] == "ok"
