@@ -427,7 +427,7 @@ def curve_layout_host(times, dfs, jac, hess=None):
            "adr_curve_layout_host")
     keys = ("packed_ok", "core_pillars", "core_pairs", "packed_entries", "entries_per_lane", "core_rows",
             "mini_knots", "lds_bytes", "general_lds_bytes", "general_lds_rows", "core_slots_per_lane", "hub_layout",
-            "wide_chunks", "wide_lds_bytes", "wide_max_knot_chunks", "reserved")
+            "wide_chunks", "wide_lds_bytes", "wide_max_knot_chunks", "upload_lds_bytes")
     return dict(zip(keys, (int(v) for v in info)))
 
 

@@ -300,7 +300,7 @@ int adr_curve_layout_host(int K, int P, const double* times, const double* dfs, 
     info[13] = t.wide_nch > 0 ? static_cast<int64_t>(adr::wide_kernel_lds_bytes(t.K, t.Kc, t.wide_nch, t.has_hess)) : 0;
     info[14] = 0;
     for (uint32_t m : t.wide_knot_chunks) info[14] = std::max<int64_t>(info[14], __builtin_popcount(m));
-    info[15] = 0;
+    info[15] = static_cast<int64_t>(adr::general_kernel_lds_bytes(t.K, t.Kc, t.T > 1));   // what adr_curve_upload checks
     return ADR_OK;
 }
 

@@ -13,7 +13,10 @@
 // leave pair BANDS P_d[k] = sum w u_k u_{k+d}, d = 1 .. kKnotBand, and - for pairs farther apart - a dense overflow matrix.
 //
 // Here: (1) the block records are summed in a fixed order (one wavefront per number, lanes stride over the blocks, fixed
-// butterfly - no atomics, the result does not depend on scheduling), (2) one projection per launch
+// butterfly - no atomics, the result does not depend on scheduling; the one exception is the ratio nodes' overflow matrix,
+// which the knot-lag pass's waves fill with atomic adds (kernels_lite.hip, unsafeAtomicAdd): with GAMMA, a book whose
+// payment-lag coupons couple knots farther apart than the pair bands gets a gamma ladder whose last bits depend on the
+// order of those adds), (2) one projection per launch
 //
 //   delta_p  += 1e-4 sum_k w_k LJ[k][p]
 //   gamma_pq += 1e-8 sum_k ( D_k LJ[k][p] LJ[k][q] + O_k (LJ[k][p] LJ[k+1][q] + LJ[k+1][p] LJ[k][q]) + w_k LC[k][p][q] )

@@ -60,7 +60,9 @@ def allgather_sum_fixed_order(agg, group=None):
 # near-equal cash-flow count, whatever the world size (which must divide the chunk count: 1, 2, 3, 4, 6, 8, 12, 24) - every
 # rank prices its run of chunks one by one (one aggregate ladder per chunk: a chunk's ladder is the same numbers on whichever
 # rank prices it), the chunk ladders are all-gathered and every rank adds them in chunk order: one result, bit for bit, on
-# 1, 2, 3 ... ranks.
+# 1, 2, 3 ... ranks.  One exception: an aggregate-only GAMMA request on a chunk with payment-lag or weighted coupons whose
+# ratio nodes couple knots farther apart than the knot-lag pass's pair bands.  Those pairs go to an overflow matrix summed
+# with atomic adds (csrc/kernels_lite.hip), so the last bits of that chunk's gamma ladder vary from run to run (to ~1e-13).
 CANONICAL_CHUNKS = 24
 
 

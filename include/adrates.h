@@ -62,7 +62,10 @@ typedef enum adr_status {
  * curves are refused with ADR_ERR_UNSUPPORTED, and so is one whose knot tables do not fit the 160 KiB LDS of a CU next to two
  * 32-pillar tiles of its Jacobian.  Up to 32 pillars: the fast / lite kernels; 33-64: one launch for the whole ladder (wide
  * layout); 65-256: 32-pillar tiles, one launch per tile pair.  Results do not depend on the pillar count's parity or on which
- * kernel family a curve is routed to (DESIGN.md section 5 describes the routes and their measured rates).
+ * kernel family a curve is routed to (DESIGN.md section 5 describes the routes and their measured rates).  The LDS check binds
+ * long before 256 pillars on realistic curves (about 12 bytes per knot and 536 per reachable knot): validated against the C
+ * oracle are a curve of 155 pillars with a weekly short end (K = 2 021 knots, the largest such curve accepted) and one of 256
+ * single-period pillars (K = 257).
  * adr_curve_plan_create (the device curve builder) takes up to ADR_MAX_PLAN_PILLARS. */
 #define ADR_MAX_PILLARS 256
 #define ADR_MAX_PLAN_PILLARS 64
@@ -123,7 +126,8 @@ int adr_curve_tables_host(int K, int P, const double* times, const double* dfs,
  *              LDS bytes of the general kernel's variant with resident convexity rows (0: none), that variant fits (0/1),
  *              core slots per lane, hub layout found (0/1: the exact kernel variants; 0 = the universal ones),
  *              wide layout (33-64 pillars): 128-entry chunks per row of the packed triangle (7 / 10 / 17; 0: none),
- *              LDS bytes of the wide gamma kernel, the most chunks any knot's convexity row is read in, reserved }.
+ *              LDS bytes of the wide gamma kernel, the most chunks any knot's convexity row is read in,
+ *              LDS bytes of the general kernel's tables that adr_curve_upload checks against the 160 KiB of a CU }.
  * Returns 0 or a negative status.  No GPU needed.
  */
 int adr_curve_layout_host(int K, int P, const double* times, const double* dfs,
@@ -266,7 +270,11 @@ int64_t adr_trades_input_bytes(const adr_trades* trades);
  * (x1e-4), gamma per bp^2 (x1e-8).  Any output may be NULL; req_mask says what
  * to compute.  agg (optional) receives the portfolio sums laid out as
  * [pv, delta[P], gamma[P*P]] = 1 + P + P*P doubles - what Portfolio.compute
- * returns.  Blocks until the results are in the (host) buffers.
+ * returns.  Whatever req_mask says, agg[0] holds the book's PV; the delta block
+ * holds the book's delta when DELTA or GAMMA is requested, the gamma block its
+ * gamma with GAMMA; a block not computed is zeros.  Per-trade outputs the mask
+ * does not ask for are not written.  Blocks until the results are in the
+ * (host) buffers.
  */
 int adr_price(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades,
               uint32_t req_mask,

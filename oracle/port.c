@@ -24,8 +24,6 @@
 #include <omp.h>
 #endif
 
-#define MAXLOC 1024 /* distinct knots one trade may touch */
-
 typedef struct {
     int K, P, method;
     const double *x, *d, *jac, *hess;
@@ -104,9 +102,10 @@ static void interpolate(const curve_t* c, double t, df_t* r) {
 
 typedef struct {
     int n;               /* local knots in use */
-    int glob[MAXLOC];    /* local -> global knot */
-    double g[MAXLOC];
-    double* H;           /* [MAXLOC*MAXLOC], row stride MAXLOC */
+    int cap;             /* local knots one trade of the batch may touch: the row stride of H */
+    int* glob;           /* [cap] local -> global knot */
+    double* g;           /* [cap] */
+    double* H;           /* [cap*cap] */
     int* loc_of;         /* [K] global -> local, -1 */
 } work_t;
 
@@ -117,7 +116,7 @@ static int local_of(work_t* w, int k) {
         w->loc_of[k] = l;
         w->glob[l] = k;
         w->g[l] = 0.0;
-        for (int i = 0; i <= l; ++i) { w->H[i * MAXLOC + l] = 0.0; w->H[l * MAXLOC + i] = 0.0; }
+        for (int i = 0; i <= l; ++i) { w->H[(size_t)i * w->cap + l] = 0.0; w->H[(size_t)l * w->cap + i] = 0.0; }
     }
     return l;
 }
@@ -130,12 +129,12 @@ static void add_term(work_t* w, int m, const df_t* X, const double* fX, const do
     for (int a = 0; a < m; ++a)
         for (int i = 0; i < X[a].n; ++i) {
             w->g[loc[a][i]] += fX[a] * X[a].d1[i];
-            for (int jx = 0; jx < X[a].n; ++jx) w->H[loc[a][i] * MAXLOC + loc[a][jx]] += fX[a] * X[a].d2[i][jx];
+            for (int jx = 0; jx < X[a].n; ++jx) w->H[(size_t)loc[a][i] * w->cap + loc[a][jx]] += fX[a] * X[a].d2[i][jx];
             for (int b = 0; b < m; ++b) {
                 const double h = fXY[a * m + b];
                 if (h == 0.0) continue;
                 for (int jx = 0; jx < X[b].n; ++jx)
-                    w->H[loc[a][i] * MAXLOC + loc[b][jx]] += h * X[a].d1[i] * X[b].d1[jx];
+                    w->H[(size_t)loc[a][i] * w->cap + loc[b][jx]] += h * X[a].d1[i] * X[b].d1[jx];
             }
         }
 }
@@ -143,7 +142,7 @@ static void add_term(work_t* w, int m, const df_t* X, const double* fX, const do
 static double price_one(const curve_t* c, work_t* w, int mf, const double* ftp, const double* fpay, int ml,
                         const double* ltp, const double* lts, const double* lte, const double* lal,
                         const double* lw /* per-coupon weights or NULL */, double N,
-                        double spread, double sf, double sl, double* delta, double* gamma, double* tmp /* MAXLOC*P */) {
+                        double spread, double sf, double sl, double* delta, double* gamma, double* tmp /* cap*P */) {
     const int P = c->P;
     const double tv = 0.0;
     double pv = 0.0;
@@ -215,7 +214,7 @@ static double price_one(const curve_t* c, work_t* w, int mf, const double* ftp, 
             double* ta = tmp + (size_t)a * P;
             for (int q = 0; q < P; ++q) ta[q] = 0.0;
             for (int b = 0; b < m; ++b) {
-                const double h = w->H[a * MAXLOC + b];
+                const double h = w->H[(size_t)a * w->cap + b];
                 if (h == 0.0) continue;
                 const double* J = c->jac + (size_t)w->glob[b] * P;
                 for (int q = 0; q < P; ++q) ta[q] += h * J[q];
@@ -246,8 +245,8 @@ int adr_port_price_weighted(int K, int P, int method, const double* times, const
                             const double* notional, const double* spread, const double* fix_sign,
                             const double* flt_sign, double* pv, double* delta, double* gamma, int n_threads);
 
-/* Returns 0, or -1 on bad arguments / a trade touching more than MAXLOC knots cannot occur silently:
- * the number of knots per trade is bounded by 2 + 6 * flows, checked up front. */
+/* Returns 0, or -1 on bad arguments or a failed allocation.  Each thread's local-knot scratch is sized from the batch:
+ * a trade touches at most min(K, 2 + 2 * fixed flows + 6 * float flows) distinct knots. */
 int adr_port_price(int K, int P, int method, const double* times, const double* dfs, const double* jac,
                    const double* hess, int64_t n, const int64_t* fix_off, const int64_t* flt_off,
                    const double* fix_tp, const double* fix_pay, const double* flt_tp, const double* flt_ts,
@@ -268,9 +267,13 @@ int adr_port_price_weighted(int K, int P, int method, const double* times, const
                             const double* notional, const double* spread, const double* fix_sign,
                             const double* flt_sign, double* pv, double* delta, double* gamma, int n_threads) {
     if (K < 2 || P < 1 || (method != 1 && method != 2 && method != 4) || (gamma && !hess)) return -1;
-    for (int64_t t = 0; t < n; ++t)
-        if (2 + 2 * (fix_off[t + 1] - fix_off[t]) + 6 * (flt_off[t + 1] - flt_off[t]) > MAXLOC && K > MAXLOC)
-            return -1;
+    int64_t cap = 1;
+    for (int64_t t = 0; t < n; ++t) {
+        const int64_t nf = fix_off[t + 1] - fix_off[t], nl = flt_off[t + 1] - flt_off[t];
+        if (nf < 0 || nl < 0) return -1;
+        const int64_t m = 2 + 2 * nf + 6 * nl;
+        if (m > cap) cap = m < K ? m : K;
+    }
     curve_t c = {K, P, method, times, dfs, jac, hess};
     int rc = 0;
 #ifdef _OPENMP
@@ -279,10 +282,13 @@ int adr_port_price_weighted(int K, int P, int method, const double* times, const
 #pragma omp parallel
     {
         work_t w;
-        w.H = (double*)malloc(sizeof(double) * MAXLOC * MAXLOC);
+        w.cap = (int)cap;
+        w.glob = (int*)malloc(sizeof(int) * (size_t)cap);
+        w.g = (double*)malloc(sizeof(double) * (size_t)cap);
+        w.H = (double*)malloc(sizeof(double) * (size_t)cap * (size_t)cap);
         w.loc_of = (int*)malloc(sizeof(int) * K);
-        double* tmp = (double*)malloc(sizeof(double) * MAXLOC * P);
-        if (!w.H || !w.loc_of || !tmp) {
+        double* tmp = (double*)malloc(sizeof(double) * (size_t)cap * P);
+        if (!w.glob || !w.g || !w.H || !w.loc_of || !tmp) {
 #pragma omp atomic write
             rc = -1;
         } else {
@@ -299,7 +305,7 @@ int adr_port_price_weighted(int K, int P, int method, const double* times, const
                 if (pv) pv[t] = v;
             }
         }
-        free(w.H); free(w.loc_of); free(tmp);
+        free(w.glob); free(w.g); free(w.H); free(w.loc_of); free(tmp);
     }
     return rc;
 }

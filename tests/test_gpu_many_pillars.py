@@ -49,6 +49,33 @@ def many_pillar_quotes(P):
     return px, tenors
 
 
+def weekly_pillar_quotes(P):
+    """A realistic curve of more than 64 pillars whose knot tables still fit the upload's LDS: the 32 README quotes, weekly
+    pillars 3W-51W (not 13W, 26W, 39W: the 3M, 6M, 9M maturities), annual ones to 49Y, then monthly / half-year ones as in
+    `many_pillar_quotes`; quoted off the neighbours.  Up to 155 pillars fit (tests/_route_cases.py, REALISTIC_MAX)."""
+    base_t = np.array([_years(t) for t in F.TENORS])
+    weeks = [f"{w}W" for w in range(3, 52) if w not in (13, 26, 39)]
+    years = [f"{y}Y" for y in range(11, 50) if f"{y}Y" not in F.TENORS]
+    months = [f"{m}M" for m in range(13, 24) if m != 18] + [f"{m}M" for m in range(30, 600, 12)]
+    tenors = sorted(list(F.TENORS) + (weeks + years + months)[:P - len(F.TENORS)], key=_years)
+    assert len(tenors) == P
+    px = [float(np.interp(_years(t), base_t, F.GBP_PX)) if t not in F.TENORS else F.GBP_PX[F.TENORS.index(t)] for t in tenors]
+    return px, tenors
+
+
+def short_dated_quotes(P):
+    """A curve of single-period pillars: one per business day from 1D (README_VALUE_DT is a Tuesday; weekend maturities would
+    roll onto the next pillar's), quoted off the README curve - about one knot per pillar (K = Kc = P + 1), the only shape of
+    curve whose tables fit the upload's LDS at 256 pillars."""
+    import datetime
+    vd = datetime.date(2024, 4, 30)
+    assert vd == datetime.date(F.README_VALUE_DT._y, F.README_VALUE_DT._m, F.README_VALUE_DT._d)
+    days = [d for d in range(1, 366) if (vd + datetime.timedelta(days=d)).weekday() < 5][:P]
+    assert len(days) == P
+    base_t = np.array([_years(t) for t in F.TENORS])
+    return [float(np.interp(d / 365.0, base_t, F.GBP_PX)) for d in days], [f"{d}D" for d in days]
+
+
 def _mixed_batch(vd, n, seed):
     rng = np.random.default_rng(seed)
     terms = OISTerms(effective_dt=vd, tenor=[f"{int(m)}M" for m in rng.integers(1, 481, n)],

@@ -41,3 +41,25 @@ def test_port_threads_agree():
     many = port.price(4, cache["times"], cache["dfs"], cache["jac"], cache["hess"], b, n_threads=4)
     for k in ("pv", "delta", "gamma"):
         assert np.array_equal(one[k], many[k])
+
+
+def test_port_prices_long_legs_on_curves_of_more_than_1024_knots():
+    """Monthly legs of 400 / 480 coupons touch up to 2 + 6 x 480 knots; on the 96-pillar curve (K = 1 585) each thread's
+    local-knot scratch is sized from the batch (every such trade used to be refused).  Against the autodiff restatement."""
+    from ._route_cases import batch, engine_curve
+    vd = F.README_VALUE_DT
+    host = engine_curve(vd, 96)
+    assert host.times.shape[0] > 1024
+    b, labels = batch(vd, ("very_long", "plain"))
+    assert labels[:2] == ["very_long", "very_long"] and 2 + 6 * int(np.diff(b.flt_off).max()) > 1024
+    got = port.price(4, host.times, host.dfs, host.jac, host.hess, b)
+    cache = dict(times=host.times, dfs=host.dfs, jac=host.jac, hess=host.hess)
+    for t in (0, 1, 3):
+        f0, f1, l0, l1 = int(b.fix_off[t]), int(b.fix_off[t + 1]), int(b.flt_off[t]), int(b.flt_off[t + 1])
+        fixed = dict(payment_times=b.fix_tp[f0:f1], payments=b.fix_pay[f0:f1], principal=0.0, leg_sign=float(b.fix_sign[t]))
+        floating = dict(payment_times=b.flt_tp[l0:l1], start_times=b.flt_ts[l0:l1], end_times=b.flt_te[l0:l1],
+                        pay_alphas=b.flt_alpha[l0:l1], spread=float(b.spread[t]), notional=float(b.notional[t]), principal=0.0,
+                        leg_sign=float(b.flt_sign[t]))
+        r = O.ois_analytics(cache, 4, fixed, floating)
+        e = trade_errors(got["pv"][t], got["delta"][t], got["gamma"][t], r["value"], r["delta"], r["gamma"], b.notional[t])
+        assert e < 1e-12, (labels[t], e)
