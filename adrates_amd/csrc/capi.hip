@@ -8,11 +8,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <functional>
+#include <memory>
 #include <mutex>
-#include <queue>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/adrates.h"
@@ -70,14 +68,14 @@ struct adr_ctx {
 };
 
 namespace {
-constexpr int kKnotMaxKc = 640;             // reachable knots a curve can have (its dense 32-wide Jacobian must fit the LDS)
-constexpr int kKnotLagMaxKc = 256;          // ... for the knot pass over payment-lag rows (16 pair bands per knot, a dense overflow matrix)
-constexpr int kKnotStrideMax = std::max(1 + 3 * kKnotMaxKc, 1 + (2 + adr::kKnotBand) * kKnotLagMaxKc);
+namespace R = adr::route;
+constexpr int kKnotStrideMax = std::max(1 + 3 * R::kKnotMaxKc, 1 + (2 + adr::kKnotBand) * R::kKnotLagMaxKc);
 }
 
 struct adr_curve {
     adr_ctx* ctx = nullptr;
     adr::CurveDev dev{};
+    R::CurveClass cls{};                 // what the launch plan reads (route.hpp)
     std::vector<void*> allocations;
 };
 
@@ -89,6 +87,7 @@ struct adr_curve_plan {
     adr::CurveTables base;               // host tables of the base curve (structure + base values)
     adr::CurveBuildPlanDev dev{};
     adr::CurveDev shared{};              // the structural device arrays every built curve points at
+    R::CurveClass cls{};                 // ... and the class of every built curve
     std::vector<void*> allocations;
 };
 
@@ -104,67 +103,34 @@ struct adr_curve_set {
 
 struct adr_trades {
     adr_ctx* ctx = nullptr;
-    adr::TradesDev dev{};
+    adr::TradesDev dev{};            // the batch: headers and cash flows, the identity list, the plain row table
     int64_t n_fix_flows = 0, n_flt_flows = 0;
-    // Trades with a coupon whose accrual end differs from its payment time (payment lag) need the general
-    // kernel (list_general, null when there are none), and so do legs of more than kMaxChain * 32 coupons.
-    // list_fast holds the trades of at most 32 coupons per leg sorted by coupon
-    // count, so that the trades sharing a wavefront in the fast kernel have similar lengths.
-    int64_t n_fast = 0, n_long = 0, n_general = 0;
-    const int32_t* list_general = nullptr;
-    adr::TradesDev chained{};        // row table of the longer trades as chains of 32-coupon rows (fast kernel, LONG)
-    int chained_blocks = 0;          // the grid the chains were laid out for
-    // delta / PV-only requests: the trades without payment lag and at most 32 coupons per leg as 16-slot rows of the
-    // lite kernel (the trades of the 32-slot row table); list_nonlite = every other trade (for curves without a packed layout)
-    // gamma requests on curves with the packed layout: trades with payment lag or per-coupon notionals and at most 32
-    // coupons per leg as rows of the payment-lag variant of the fast kernel; list_rest = the general list without them
-    adr::TradesDev lagged{};
-    adr::TradesDev lagged_chained{};   // ... those of 33-128 coupons per leg as chains of rows (LONG + LAG), laid out for
-    int lagged_chained_blocks = 0;     // this grid
-    int64_t n_lagged = 0, n_lagged_long = 0, n_rest = 0;
-    // per-wave stash of the payment-lag variant (kernels.hpp, OutputsDev::lag_scratch), sized for a grid of lag_blocks
+    // What each trade set of the launch plan (route.hpp, Set) hands its kernel: set[s] for the row tables (S_ROWS ..
+    // S_LAGGED_CHAINED) and the trade lists (S_GENERAL .. S_ALL), lite[s] for the lite tables (S_LITE, S_LITE_LAG).
+    adr::TradesDev set[R::kSets] = {};
+    adr::LiteRowsDev lite[2] = {};
+    R::TradeCounts counts;           // what the launch plan needs to know about the batch
+    // per-wave stash of the payment-lag variant (kernels.hpp, OutputsDev::lag_scratch), sized for a grid of counts.lag_blocks
     // blocks.  It belongs to the BATCH (not to the ctx): two batches priced on two streams never share it.
     double* lag_scratch = nullptr;
-    int lag_blocks = 0;
-    const int32_t* list_rest = nullptr;
-    adr::LiteRowsDev lite{};
-    int64_t n_lite = 0, n_nonlite = 0;
-    const int32_t* list_nonlite = nullptr;
-    // ... and the trades with payment lag or per-coupon notionals and at most 135 coupons per leg as rows of the lite
-    // kernel's payment-lag variant; list_general_b / list_nonlite_b = list_general / list_nonlite without them
-    adr::LiteRowsDev lite_lag{};
-    int64_t n_lite_lag = 0, n_general_b = 0, n_nonlite_b = 0;
-    const int32_t* list_general_b = nullptr;
-    const int32_t* list_nonlite_b = nullptr;
     std::vector<void*> allocations;
 
-    // what the launch plan needs to know about the batch (route.hpp)
-    adr::route::TradeCounts counts() const {
-        adr::route::TradeCounts c;
-        c.n = dev.n;
-        c.rows = dev.n_rows; c.chained_rows = chained.n_rows; c.lagged_rows = lagged.n_rows; c.lagged_chained_rows = lagged_chained.n_rows;
-        c.lite_units = lite.n_units; c.lite_lag_units = lite_lag.n_units;
-        c.n_general = n_general; c.n_general_b = n_general_b; c.n_rest = n_rest; c.n_nonlite = n_nonlite; c.n_nonlite_b = n_nonlite_b;
-        c.chained_blocks = chained_blocks; c.lagged_chained_blocks = lagged_chained_blocks; c.lag_blocks = lag_blocks;
-        c.lag_scratch = lag_scratch != nullptr;
-        return c;
-    }
-    // the plan of the last (curve class, request) this batch was priced with: built on first use, replayed afterwards
-    struct PlanKey { int v[20]; };
+    // The plan of the last (curve class, request) this batch was priced with: built on first use, replayed afterwards.  A
+    // caller gets a reference-counted immutable plan, taken under the lock: a concurrent call with another request replaces
+    // the cached pointer, never the plan the caller is walking.
+    struct PlanKey { R::CurveClass cls; int req[4]; };
     mutable std::mutex plan_mutex;
     mutable PlanKey plan_key{};
-    mutable bool plan_valid = false;
-    mutable adr::route::Plan plan;
-    const adr::route::Plan& plan_for(const adr::CurveDev& cv, bool want_delta, bool want_gamma, bool per_trade, bool has_agg,
-                                     const adr_ctx& c) const {
-        const PlanKey key{{cv.K, cv.Kc, cv.P, cv.T, cv.wide_nch, cv.packed_ok, cv.method, cv.epg, cv.cpg, cv.Ec, cv.Kcore, cv.n_mini,
-                           cv.n_lut, cv.n_fringe, cv.pc_pad, cv.Eu, want_delta ? 1 : 0, want_gamma ? 1 : 0, per_trade ? 1 : 0, has_agg ? 1 : 0}};
+    mutable std::shared_ptr<const R::Plan> plan;
+    std::shared_ptr<const R::Plan> plan_for(const R::CurveClass& cls, bool want_delta, bool want_gamma, bool per_trade, bool has_agg,
+                                            int n_cu) const {
+        PlanKey key{};
+        key.cls = cls;
+        key.req[0] = want_delta; key.req[1] = want_gamma; key.req[2] = per_trade; key.req[3] = has_agg;
         std::lock_guard<std::mutex> lock(plan_mutex);
-        if (!plan_valid || std::memcmp(&key, &plan_key, sizeof key) != 0) {
-            plan = adr::route::make_plan(cv, counts(), want_delta, want_gamma, per_trade, has_agg, c.n_cu, c.max_blocks, c.knot_blocks,
-                                         kKnotMaxKc, kKnotLagMaxKc);
+        if (!plan || std::memcmp(&key, &plan_key, sizeof key) != 0) {
+            plan = std::make_shared<const R::Plan>(R::make_plan(cls, counts, want_delta, want_gamma, per_trade, has_agg, n_cu));
             plan_key = key;
-            plan_valid = true;
         }
         return plan;
     }
@@ -204,7 +170,8 @@ int adr_init(int device_ordinal, adr_ctx** out) {
                                                            : prop.sharedMemPerBlock;
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete ctx; return fail_hip(e, "hipStreamCreate"); }
-    ctx->max_blocks = std::max(1, ctx->n_cu) * 16;
+    const R::Grid grid = R::grid_for(ctx->n_cu);
+    ctx->max_blocks = grid.max_blocks;
     e = hipMalloc(reinterpret_cast<void**>(&ctx->partials),
                   sizeof(double) * static_cast<size_t>(ctx->max_blocks) * adr::kAggStride);
     if (e != hipSuccess) { hipStreamDestroy(ctx->stream); delete ctx; return fail_hip(e, "hipMalloc(partials)"); }
@@ -213,9 +180,9 @@ int adr_init(int device_ordinal, adr_ctx** out) {
         hipFree(ctx->partials); hipStreamDestroy(ctx->stream); delete ctx;
         return fail_hip(e, "hipMalloc(dump)");
     }
-    ctx->knot_blocks = std::max(1, ctx->n_cu) * adr::kLiteWavesPerSimd * 4 * 64 / adr::kLiteThreads;   // blocks resident at once
+    ctx->knot_blocks = grid.knot_blocks;
     e = hipMalloc(reinterpret_cast<void**>(&ctx->knot_partials),
-                  sizeof(double) * (static_cast<size_t>(ctx->knot_blocks + 1) * kKnotStrideMax + static_cast<size_t>(kKnotLagMaxKc) * kKnotLagMaxKc + 1));
+                  sizeof(double) * (static_cast<size_t>(ctx->knot_blocks + 1) * kKnotStrideMax + static_cast<size_t>(R::kKnotLagMaxKc) * R::kKnotLagMaxKc + 1));
     if (e != hipSuccess) {
         hipFree(ctx->dump); hipFree(ctx->partials); hipStreamDestroy(ctx->stream); delete ctx;
         return fail_hip(e, "hipMalloc(knot partials)");
@@ -283,17 +250,14 @@ int adr_curve_layout_host(int K, int P, const double* times, const double* dfs, 
     adr::CurveTables t;
     const std::string err = adr::build_curve_tables(K, P, times, dfs, jac, hess, t);
     if (!err.empty()) return fail(ADR_ERR_INVALID, "adr_curve_layout_host: " + err);
-    adr::CurveDev d{};
-    d.K = t.K; d.Kc = t.Kc; d.Kcore = t.Kcore; d.pc_pad = t.pc_pad; d.Ec = t.Ec; d.Eu = t.Eu; d.epg = t.epg; d.cpg = t.cpg; d.hub = t.hub ? 1 : 0; d.n_lut = static_cast<int>(t.lut.size() / 2); d.n_mini = t.n_mini;
+    const R::CurveClass cls = R::curve_class(t, 0, false);
     info[0] = t.packed_ok ? 1 : 0; info[1] = t.Pc; info[2] = t.Ec; info[3] = t.Eu; info[4] = t.epg;
     info[5] = t.Kcore; info[6] = t.n_mini;
-    info[7] = t.packed_ok ? static_cast<int64_t>(adr::fast_kernel_lds_bytes(d, t.has_hess)) : 0;
-    {   // the general kernel's variant with LDS-resident convexity rows (it serves what the fast kernels do not take)
-        const size_t g = (t.packed_ok && t.has_hess && t.T == 1)
-            ? adr::general_lds_kernel_lds_bytes_for(t.K, t.Kc, t.Kcore, t.Ec, t.n_mini, static_cast<int>(t.lut.size() / 2), true) : 0;
-        info[8] = static_cast<int64_t>(g);
-        info[9] = adr::general_lds_rows_fit(g, t.Ec, t.n_fringe) ? 1 : 0;
-    }
+    info[7] = t.packed_ok ? static_cast<int64_t>(adr::fast_kernel_lds_bytes(cls.sizes(), t.has_hess)) : 0;
+    // the general kernel's variant with LDS-resident convexity rows (it serves what the fast kernels do not take)
+    info[8] = (t.packed_ok && t.has_hess && t.T == 1)
+        ? static_cast<int64_t>(adr::general_lds_kernel_lds_bytes_for(t.K, t.Kc, t.Kcore, t.Ec, t.n_mini, cls.n_lut, true)) : 0;
+    info[9] = cls.lds_rows;
     info[10] = t.cpg;
     info[11] = t.hub ? 1 : 0;
     info[12] = t.wide_nch;
@@ -371,8 +335,8 @@ int adr_curve_upload_ex(adr_ctx* ctx, int interp_method, int K, int P, const dou
     double *d_lj64 = nullptr, *d_lcflat = nullptr;
     uint32_t *d_went = nullptr, *d_wchunks = nullptr, *d_wsmap = nullptr;
     int32_t *d_wpos = nullptr, *d_worder = nullptr;
-    const bool wide = t.wide_nch > 0 && t.wide_nch <= adr::kWideMaxChunks && !(flags & ADR_CURVE_PILLAR_TILES) &&
-                      adr::wide_kernel_lds_bytes(t.K, t.Kc, t.wide_nch, t.has_hess) <= kLdsBudget;
+    c->cls = R::curve_class(t, interp_method, (flags & ADR_CURVE_PILLAR_TILES) != 0);
+    const bool wide = c->cls.wide_nch > 0;
     if (wide) {
         track(upload(t.lj64, &d_lj64), d_lj64);
         track(upload(t.wide_ent, &d_went), d_went);
@@ -401,23 +365,17 @@ int adr_curve_upload_ex(adr_ctx* ctx, int interp_method, int K, int P, const dou
     c->dev.T = t.T; c->dev.tile_i = c->dev.tile_j = 0;
     c->dev.x = d_x; c->dev.log_df = d_log; c->dev.inv_x = d_invx; c->dev.lj = d_lj; c->dev.lc_lanes = d_lc; c->dev.lc_block_mask = d_lcmask;
     c->dev.first_of = d_first; c->dev.compact_of = d_comp; c->dev.lut = d_lut; c->dev.n_lut = static_cast<int>(t.lut.size() / 2);
-    c->dev.wide_nch = wide ? t.wide_nch : 0;
+    c->dev.wide_nch = c->cls.wide_nch;
     c->dev.lj64 = d_lj64; c->dev.wide_ent = d_went; c->dev.lcflat = d_lcflat; c->dev.wide_knot_chunks = d_wchunks; c->dev.wide_store_map = d_wsmap; c->dev.wide_pos = d_wpos; c->dev.wide_order = d_worder;
     // the fast kernels store the [P][P] matrices as 16-byte pairs of the flat array: P must be even
     // LINEAR_FWD_RATES is linear in the knot DFs, not in their logs: only the general kernel carries the extra
     // Hessian term (kernels_general.hip, `Lookup`)
-    c->dev.packed_ok = t.packed_ok ? 1 : 0;
+    c->dev.packed_ok = c->cls.packed_ok;
     c->dev.odd_last = t.odd_last;
     c->dev.Pc = t.Pc; c->dev.pc_pad = t.pc_pad; c->dev.Ec = t.Ec; c->dev.Eu = t.Eu; c->dev.epg = t.epg; c->dev.cpg = t.cpg; c->dev.hub = t.hub ? 1 : 0;
     c->dev.Kcore = t.Kcore; c->dev.n_mini = t.n_mini; c->dev.fringe_start = t.fringe_start; c->dev.n_fringe = t.n_fringe; c->dev.fringe_own = t.fringe_own ? 1 : 0;
     c->dev.ljc = d_ljc; c->dev.lcc = d_lcc; c->dev.mini = d_mini; c->dev.knot_class = d_class;
     c->dev.pillar_to_core = d_p2c; c->dev.out_map = d_omap; c->dev.store_map = d_smap; c->dev.ent_pq = d_pq; c->dev.core_pos = d_cpos; c->dev.lcc_pos = d_lpos;
-    // the packed tables must fit the LDS of a CU next to the search arrays, else the general kernel serves all
-    size_t fast_lds = 0;
-    if (c->dev.packed_ok) {
-        fast_lds = adr::fast_kernel_lds_bytes(c->dev, t.has_hess);
-        if (fast_lds > kLdsBudget) { c->dev.packed_ok = 0; fast_lds = 0; }
-    }
     *out = c;
     return ADR_OK;
 }
@@ -487,7 +445,8 @@ int adr_curve_plan_create(adr_ctx* ctx, int interp_method, int K, int P, const d
     adr::CurveTables& t = plan->base;
     const std::string err = adr::build_curve_tables(K, P, times, base_dfs, base_jac, base_hess, t);
     if (!err.empty()) { delete plan; return fail(ADR_ERR_INVALID, "adr_curve_plan_create: " + err); }
-    // more than 32 pillars: the built curves carry the wide layout's tables only (no tiled route for them)
+    // more than 32 pillars: the built curves carry the wide layout's tables only (no tiled route for them).  (Every curve this
+    // accepts - at most 64 pillars, wide tables that fit the LDS - is one curve_class puts on the wide route.)
     const bool wide = t.T > 1;
     const size_t lds = wide ? adr::wide_kernel_lds_bytes(t.K, t.Kc, t.wide_nch, plan->has_hess) : adr::general_kernel_lds_bytes(t.K, t.Kc);
     // the PV01 gradients of the scan ([K][P] doubles) stay in LDS when they fit, else they go through a scratch buffer
@@ -553,10 +512,13 @@ int adr_curve_plan_create(adr_ctx* ctx, int interp_method, int K, int P, const d
 
     adr::CurveBuildPlanDev& d = plan->dev;
     d.K = K; d.P = P; d.Kc = t.Kc; d.acc = d_acc; d.pillar = d_pil; d.prev_idx = d_prev; d.knot_index = d_kidx;
-    d.packed_ok = t.packed_ok ? 1 : 0;   // as in adr_curve_upload
+    R::CurveClass& cls = plan->cls;
+    cls = R::curve_class(t, interp_method, false);
+    if (!cls.packed_ok) cls.lds_rows = 0;   // (the built curves carry the convexity rows only with the packed layout)
+    d.packed_ok = cls.packed_ok;
     d.Pc = t.Pc; d.pc_pad = t.pc_pad; d.Ec = t.Ec; d.Kcore = t.Kcore; d.n_mini = t.n_mini;
     d.knot_class = d_class; d.core_pillars = d_core; d.lcc_pq = d_lccpq;
-    d.wide_nch = wide ? t.wide_nch : 0; d.wide_pq = d_wpq; d.dpv_global = dpv_global ? 1 : 0;
+    d.wide_nch = cls.wide_nch; d.wide_pq = d_wpq; d.dpv_global = dpv_global ? 1 : 0;
 
     adr::CurveDev& c = plan->shared;
     c.K = t.K; c.Kc = t.Kc; c.P = t.P; c.method = interp_method; c.T = t.T; c.tile_i = c.tile_j = 0;
@@ -568,11 +530,6 @@ int adr_curve_plan_create(adr_ctx* ctx, int interp_method, int K, int P, const d
     c.odd_last = t.odd_last;
     c.Pc = t.Pc; c.pc_pad = t.pc_pad; c.Ec = t.Ec; c.Eu = t.Eu; c.epg = t.epg; c.cpg = t.cpg; c.hub = t.hub ? 1 : 0; c.Kcore = t.Kcore; c.n_mini = t.n_mini; c.fringe_start = t.fringe_start; c.n_fringe = t.n_fringe; c.fringe_own = t.fringe_own ? 1 : 0;
     c.knot_class = d_class; c.pillar_to_core = d_p2c; c.out_map = d_omap; c.store_map = d_smap; c.ent_pq = d_pq; c.core_pos = d_cpos; c.lcc_pos = d_lpos;
-    size_t fast_lds = 0;
-    if (c.packed_ok) {
-        fast_lds = adr::fast_kernel_lds_bytes(c, plan->has_hess);
-        if (fast_lds > kLdsBudget) { c.packed_ok = 0; d.packed_ok = 0; fast_lds = 0; }
-    }
     *out = plan;
     return ADR_OK;
 }
@@ -659,6 +616,7 @@ int adr_curve_set_build(adr_ctx* ctx, const adr_curve_plan* plan, int n_scen, co
         adr_curve& c = set->curves[s];
         c.ctx = ctx;
         c.dev = plan->shared;
+        c.cls = plan->cls;
         c.dev.log_df = po.log_df + s * Kc;
         if (wide) {
             c.dev.lj64 = po.lj64 + s * Kc * adr::kWidePad;
@@ -728,9 +686,7 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
     if (n > 0 && (fix_off[0] != 0 || flt_off[0] != 0))
         return fail(ADR_ERR_INVALID, "adr_trades_upload: offsets must start at 0");
 
-    // Host side of the upload: validation, the routing class of every trade and the row orders.  All of it is a
-    // single pass over the caller's arrays, cut into contiguous trade ranges for a pool of threads; the tables
-    // themselves are gathered on the device (trades_build.hip).
+    // Validation: a single pass over the caller's arrays, cut into contiguous trade ranges for a pool of threads.
     const int n_threads = adr::pool_threads(n, 4096);
     auto parallel_ranges = [&](auto&& body) {          // body(range, first trade, one past the last trade); host_pool.hpp
         adr::parallel_ranges(n, n_threads, body);
@@ -753,11 +709,8 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
         return fail(ADR_ERR_INVALID, "adr_trades_upload: null cash-flow array");
 
     // NaN / infinite inputs would only produce NaN outputs (every table index in the kernels is clamped), but a
-    // batch that contains them is a caller error: say so here instead of returning a ladder of NaNs.
-    // Class of a trade: bit 0 = a coupon accrues to a date other than its payment date (payment lag: ratio terms) or
-    // carries a notional multiplier != 1.
-    // (rows per trade in the chained tables - route.hpp, kMaxChain / kMaxChainLag: plain legs of up to 384 coupons (a 30Y
-    // monthly leg is 360, cavour/utils/frequency.py:46); payment-lag legs of up to 128 (the variant's per-trade stash))
+    // batch that contains them is a caller error: say so here instead of returning a ladder of NaNs.  The same pass flags
+    // the trades with payment lag or per-coupon notionals (route.hpp, flag_lagged).
     std::vector<uint8_t> lagged_of(static_cast<size_t>(n), 0);
     {
         std::vector<char> bad(static_cast<size_t>(n_threads), 0);       // 1: not finite, 2: bad sign
@@ -775,13 +728,9 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
                     !finite(notional, t0, t1) || !finite(spread, t0, t1))
                     err = 1;
             }
-            for (int64_t t = t0; t < t1 && !err; ++t) {
-                if (!(fix_sign[t] == 1.0 || fix_sign[t] == -1.0) || !(flt_sign[t] == 1.0 || flt_sign[t] == -1.0)) { err = 2; break; }
-                bool lag = false;
-                for (int64_t j = flt_off[t]; j < flt_off[t + 1] && !lag; ++j)
-                    lag = (flt_alpha[j] > 0.0 && flt_te[j] != flt_tp[j]) || (flt_weight && flt_weight[j] != 1.0);
-                lagged_of[static_cast<size_t>(t)] = lag ? 1 : 0;
-            }
+            for (int64_t t = t0; t < t1 && !err; ++t)
+                if (!(fix_sign[t] == 1.0 || fix_sign[t] == -1.0) || !(flt_sign[t] == 1.0 || flt_sign[t] == -1.0)) err = 2;
+            if (!err) R::flag_lagged(t0, t1, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, lagged_of.data());
             bad[static_cast<size_t>(k)] = err;
         });
         for (char b : bad)
@@ -790,32 +739,11 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
             if (b == 2) return fail(ADR_ERR_INVALID, "adr_trades_upload: leg signs must be +1 or -1");
     }
 
-    auto coupons_of = [&](int64_t t) { return flt_off[t + 1] - flt_off[t]; };
-    auto rows_of = [&](int64_t t) {
-        const int64_t m = std::max(flt_off[t + 1] - flt_off[t], fix_off[t + 1] - fix_off[t]);
-        return std::max<int64_t>(1, (m + adr::kRowSlots - 1) / adr::kRowSlots);
-    };
-    // stable order by float-coupon count, longest first (the trades sharing a wavefront then have similar lengths):
-    // a counting sort for the one-row tables (at most 32 coupons), std::stable_sort for the short lists of longer trades
-    auto sort_by_coupons = [&](std::vector<int32_t>& list) {
-        bool small = true;
-        for (int32_t t : list) small &= coupons_of(t) <= 64;
-        if (!small) {
-            std::stable_sort(list.begin(), list.end(), [&](int32_t a, int32_t b) { return coupons_of(a) > coupons_of(b); });
-            return;
-        }
-        size_t count[66] = {0};
-        for (int32_t t : list) ++count[64 - coupons_of(t) + 1];
-        for (int b = 1; b < 66; ++b) count[b] += count[b - 1];
-        std::vector<int32_t> sorted(list.size());
-        for (int32_t t : list) sorted[count[64 - coupons_of(t)]++] = t;
-        list.swap(sorted);
-    };
-    // which table or list every trade lands in (route.hpp: the same classification the launch plan's test walks)
-    adr::route::TradeClasses cls;
-    adr::route::classify_trades(n, fix_off, flt_off, lagged_of.data(), cls);
-    std::vector<int32_t>&list_fast = cls.list_fast, &list_long = cls.list_long, &list_general = cls.list_general,
-                        &list_lagged = cls.list_lagged, &list_lagged_long = cls.list_lagged_long, &list_rest = cls.list_rest;
+    // which table or list every trade lands in, and the host side of those tables (route.cpp); they are gathered on the
+    // device (trades_build.hip)
+    R::TradeLayout L = R::trade_layout(n, fix_off, flt_off, lagged_of.data(), ctx->n_cu);
+    if (L.too_many_rows)
+        return fail(ADR_ERR_UNSUPPORTED, "adr_trades_upload: more than 2^28 rows in the delta-only table; shard the portfolio");
 
     ADR_HIP(hipSetDevice(ctx->device));
     adr_trades* tr = new (std::nothrow) adr_trades();
@@ -823,6 +751,7 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
     tr->ctx = ctx;
     tr->n_fix_flows = n_fix;
     tr->n_flt_flows = n_flt;
+    tr->counts = L.counts;
     hipError_t e = hipSuccess;
     hipStream_t stream = ctx->stream;
     auto alloc = [&](size_t bytes) -> void* {
@@ -834,22 +763,15 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
         tr->allocations.push_back(p);
         return p;
     };
+    // (the host vectors handed to `put` - the caller's arrays and the layout - outlive the asynchronous copies: they are
+    // kept until the final synchronisation)
     auto put = [&](const void* src, size_t bytes) -> void* {
         void* p = alloc(bytes);
         if (p && e == hipSuccess) e = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream);
         return p;
     };
-    // (host vectors handed to `put` must outlive the asynchronous copies: they are kept until the final synchronisation)
-    std::vector<std::vector<int32_t>> keep32;
-    std::vector<std::vector<uint8_t>> keep8;
-    auto put32 = [&](std::vector<int32_t>&& v) -> const int32_t* {
-        keep32.push_back(std::move(v));
-        return static_cast<const int32_t*>(put(keep32.back().data(), keep32.back().size() * sizeof(int32_t)));
-    };
-    auto put8 = [&](std::vector<uint8_t>&& v) -> const uint8_t* {
-        keep8.push_back(std::move(v));
-        return static_cast<const uint8_t*>(put(keep8.back().data(), keep8.back().size()));
-    };
+    auto put32 = [&](const std::vector<int32_t>& v) { return static_cast<const int32_t*>(put(v.data(), v.size() * sizeof(int32_t))); };
+    auto put8 = [&](const std::vector<uint8_t>& v) { return static_cast<const uint8_t*>(put(v.data(), v.size())); };
 
     // the caller's arrays, once
     adr::CsrDev csr{};
@@ -869,8 +791,7 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
     csr.flt_sign = static_cast<const double*>(put(flt_sign, n * sizeof(double)));
 
     tr->dev.n = n;
-    tr->dev.any_ratio = 0;
-    for (uint8_t lg : lagged_of) if (lg) { tr->dev.any_ratio = 1; break; }
+    tr->dev.any_ratio = L.any_lagged ? 1 : 0;
     {
         adr::TradeHeader* hdr = static_cast<adr::TradeHeader*>(alloc(static_cast<size_t>(n) * sizeof(adr::TradeHeader)));
         if (e == hipSuccess && n > 0) e = adr::launch_build_headers(csr, hdr, stream);
@@ -880,24 +801,20 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
     tr->dev.flt_te = csr.flt_te; tr->dev.flt_alpha = csr.flt_alpha; tr->dev.flt_weight = csr.flt_weight;
     tr->dev.list = nullptr;
     tr->dev.n_list = n;
-    tr->n_fast = static_cast<int64_t>(list_fast.size());
-    tr->n_long = static_cast<int64_t>(list_long.size());
-    tr->n_general = static_cast<int64_t>(list_general.size());
-    sort_by_coupons(list_fast);
-    tr->list_general = static_cast<const int32_t*>(put(list_general.data(), list_general.size() * sizeof(int32_t)));
 
-    // Row tables of the fast kernel (kernels.hpp): 32 zero-padded slots per row and array, gathered on the device
-    // from the work list (trade or -1 for an empty row, first coupon of the piece, "the trade continues" flag).
-    struct Piece { int64_t trade; int64_t first; bool more; };
-    auto build_rows = [&](std::vector<int32_t>&& piece_trade, std::vector<int32_t>&& piece_first, std::vector<uint8_t>&& piece_more,
-                          adr::TradesDev& dst, bool lagged = false) {
+    // Row tables of the fast kernel (kernels.hpp): 32 zero-padded slots per row and array, gathered on the device from the
+    // work list (trade or -1 for an empty row; chained tables: first coupon of the piece, "the trade continues" flag).
+    auto build_rows = [&](int set, bool chained, bool lagged) {
+        const std::vector<int32_t>& piece_trade = chained ? L.chain_trade[set] : L.trades[set];
+        adr::TradesDev& dst = set == R::S_ROWS ? tr->dev : tr->set[set];
+        if (set != R::S_ROWS) { dst = tr->dev; dst.n_rows = 0; }
+        if (piece_trade.empty()) return;
         const size_t rows = piece_trade.size(), S = adr::kRowSlots;
-        const bool chained = !piece_first.empty();
         adr::RowBuildDev rb{};
         rb.rows = static_cast<int64_t>(rows);
-        rb.piece_trade = put32(std::move(piece_trade));
-        rb.piece_first = chained ? put32(std::move(piece_first)) : nullptr;
-        rb.piece_more = chained ? put8(std::move(piece_more)) : nullptr;
+        rb.piece_trade = put32(piece_trade);
+        rb.piece_first = chained ? put32(L.chain_first[set]) : nullptr;
+        rb.piece_more = chained ? put8(L.chain_more[set]) : nullptr;
         rb.row_tp = static_cast<double*>(alloc(rows * S * sizeof(double)));
         rb.row_ts = static_cast<double*>(alloc(rows * S * sizeof(double)));
         rb.row_alpha = static_cast<double*>(alloc(rows * S * sizeof(double)));
@@ -913,180 +830,52 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
         dst.n_rows = static_cast<int64_t>(rows);
         dst.row_tp = rb.row_tp; dst.row_ts = rb.row_ts; dst.row_alpha = rb.row_alpha; dst.row_xtp = rb.row_xtp; dst.row_xpay = rb.row_xpay;
         dst.row_notional = rb.row_notional; dst.row_spread = rb.row_spread; dst.row_meta = rb.row_meta; dst.row_trade = rb.row_trade;
+        dst.rows_chained = chained ? 1 : 0;
         dst.rows_lagged = lagged ? 1 : 0;
         dst.row_te = rb.row_te; dst.row_w = rb.row_w;
     };
-    {   // plain table: one row per trade, sorted by coupon count
-        tr->dev.rows_chained = 0;
-        build_rows(std::vector<int32_t>(list_fast), {}, {}, tr->dev);
+    build_rows(R::S_ROWS, false, false);                // plain table: one row per trade, sorted by coupon count
+    build_rows(R::S_CHAINED, true, false);              // longer trades as chains of 32-coupon rows
+    build_rows(R::S_LAGGED, false, true);               // payment-lag rows, one per trade (GAMMA on the packed layout)
+    build_rows(R::S_LAGGED_CHAINED, true, true);        // ... chains of them (33-128 coupons)
+    tr->set[R::S_ROWS] = tr->dev;
+    // the trade lists of the general / wide / tiled kernels; S_ALL: the identity
+    for (int s = R::S_GENERAL; s <= R::S_ALL; ++s) {
+        tr->set[s] = tr->dev;
+        if (s != R::S_ALL) { tr->set[s].list = put32(L.trades[s]); tr->set[s].n_list = static_cast<int64_t>(L.trades[s].size()); }
     }
-    // Chained tables.  The kernel's wave w walks units w, w + W, w + 2W, ... (W = waves of the launch), so the
-    // rows of a pair of trades (one per group of a wave) go to consecutive "rounds" of one wave column;
-    // pairs are dealt to the columns longest first, always to the shortest column.
-    auto build_chained = [&](std::vector<int32_t>& list, adr::TradesDev& dst, int blocks, int waves_per_block, bool lagged) {
-        std::stable_sort(list.begin(), list.end(), [&](int32_t a, int32_t b) { return rows_of(a) > rows_of(b); });
-        const int G = adr::fast_kernel_groups();
-        const int64_t W = static_cast<int64_t>(blocks) * waves_per_block;
-        // pass 1: the wave column and first round of every pair - always the shortest column, the lowest-numbered one among
-        // equals (a heap of (height, column): with tens of thousands of pairs and thousands of columns a linear search
-        // per pair was most of the upload's host time for books of long legs)
-        const size_t n_pairs = (list.size() + static_cast<size_t>(G) - 1) / static_cast<size_t>(G);
-        std::vector<int64_t> pair_col(n_pairs), pair_round(n_pairs);
-        typedef std::pair<int64_t, int64_t> HW;                                  // (height, column)
-        std::priority_queue<HW, std::vector<HW>, std::greater<HW>> heap;
-        for (int64_t w = 0; w < W; ++w) heap.push(HW(0, w));
-        int64_t rounds = 0;
-        for (size_t pi = 0; pi < n_pairs; ++pi) {
-            const HW top = heap.top();
-            heap.pop();
-            const int64_t len = rows_of(list[pi * static_cast<size_t>(G)]);     // the longest of the pair (sorted)
-            pair_col[pi] = top.second; pair_round[pi] = top.first;
-            heap.push(HW(top.first + len, top.second));
-            rounds = std::max(rounds, top.first + len);
-        }
-        // pass 2: the rows
-        const size_t total = static_cast<size_t>(rounds * W * G);
-        std::vector<int32_t> p_trade(total, -1), p_first(total, 0);
-        std::vector<uint8_t> p_more(total, 0);
-        for (size_t pi = 0; pi < n_pairs; ++pi) {
-            const size_t i = pi * static_cast<size_t>(G);
-            const int64_t len = rows_of(list[i]);
-            for (int64_t j = 0; j < len; ++j)
-                for (int g = 0; g < G; ++g) {
-                    const size_t at = static_cast<size_t>(((pair_round[pi] + j) * W + pair_col[pi]) * G + g);
-                    p_more[at] = j + 1 < len ? 1 : 0;
-                    if (i + static_cast<size_t>(g) >= list.size()) continue;          // an odd trade out: the slot stays empty
-                    const int64_t t = list[i + static_cast<size_t>(g)];
-                    p_first[at] = static_cast<int32_t>(j * adr::kRowSlots);
-                    // results are written after the chain's last row, by the row's trade index: an empty padding row of
-                    // the shorter trade still has to carry that index
-                    if (j < rows_of(t) || j + 1 == len) p_trade[at] = static_cast<int32_t>(t);
-                }
-        }
-        build_rows(std::move(p_trade), std::move(p_first), std::move(p_more), dst, lagged);
-        dst.rows_chained = 1;
-    };
-    tr->chained = tr->dev;
-    tr->chained.n_rows = 0;
-    if (!list_long.empty()) {
-        tr->chained_blocks = std::max(1, ctx->n_cu);
-        build_chained(list_long, tr->chained, tr->chained_blocks, adr::kFastThreads / 64, false);
+    if (tr->counts.lag_scratch && e == hipSuccess) {
+        // per-wave scratch of the payment-lag variant: its special nodes' stash
+        void* p = nullptr;
+        const size_t bytes = adr::fast_kernel_lag_scratch_bytes(tr->counts.lag_blocks);
+        e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) { tr->allocations.push_back(p); tr->lag_scratch = static_cast<double*>(p); }
+        if (e == hipSuccess) e = hipMemsetAsync(p, 0, bytes, stream);
     }
-    tr->lagged = tr->dev;
-    tr->lagged.n_rows = 0;
-    tr->lagged_chained = tr->dev;
-    tr->lagged_chained.n_rows = 0;
-    tr->n_lagged_long = static_cast<int64_t>(list_lagged_long.size());
-    tr->n_lagged = static_cast<int64_t>(list_lagged.size());
-    tr->n_rest = static_cast<int64_t>(list_rest.size());
-    tr->list_rest = static_cast<const int32_t*>(put(list_rest.data(), list_rest.size() * sizeof(int32_t)));
-    if (!list_lagged_long.empty()) {   // payment-lag legs of 33-128 coupons: chains of rows for the grid of the variant
-        tr->lagged_chained_blocks = std::max(1, ctx->n_cu);
-        build_chained(list_lagged_long, tr->lagged_chained, tr->lagged_chained_blocks,
-                      adr::fast_kernel_threads(true) / 64, true);
-    }
-    if (!list_lagged.empty() || !list_lagged_long.empty()) {
-        // sized for the grids these rows can be launched on: the chained rows' fixed grid, or as many blocks as the
-        // one-row trades fill (557 KB per block: a batch with a handful of such trades must not pin 143 MB)
-        const int waves = adr::fast_kernel_threads(true) / 64, G = adr::fast_kernel_groups();
-        const int64_t units = (static_cast<int64_t>(list_lagged.size()) + G - 1) / G;
-        const int need = static_cast<int>(std::min<int64_t>(std::max(1, ctx->n_cu), (units + waves - 1) / waves));
-        const int blocks = std::max({1, need, list_lagged_long.empty() ? 0 : tr->lagged_chained_blocks});
-        if (e == hipSuccess) {
-            // per-wave scratch of the payment-lag variant: its special nodes' stash
-            void* p = nullptr;
-            const size_t bytes = adr::fast_kernel_lag_scratch_bytes(blocks);
-            e = hipMalloc(&p, bytes);
-            if (e == hipSuccess) { tr->allocations.push_back(p); tr->lag_scratch = static_cast<double*>(p); tr->lag_blocks = blocks; }
-            if (e == hipSuccess) e = hipMemsetAsync(p, 0, bytes, stream);
-        }
-    }
-    if (!list_lagged.empty()) {   // payment-lag rows: one row per trade, sorted by coupon count like the plain table
-        sort_by_coupons(list_lagged);
-        tr->lagged.rows_chained = 0;
-        build_rows(std::vector<int32_t>(list_lagged), {}, {}, tr->lagged, true);
-    }
-    bool too_many_rows = false;
-    {   // lite tables (kernels.hpp, LiteRowsDev): segments of equal row count, longest coupon counts first -
-        // one for the trades of the 32-slot row table, one (with accrual ends and notional multipliers) for trades with
-        // payment lag or per-coupon notionals of at most 390 coupons per leg (26 rows)
-        constexpr int S = adr::kLiteSlots, G = 64 / adr::kLiteSlots;
-        // rows per trade, rounded up to one of kLiteSegments row counts (the kernel keeps one segment per distinct count):
-        // 1, 2, 3, 4, 6, 8, 12, 16, 26 rows = up to 390 coupons per leg; kLiteSegments = too long for the table
-        const int64_t (&kRowBuckets)[adr::kLiteSegments] = adr::route::kLiteRowBuckets;
-        // plain: the same trades as the 32-slot row table holds (at most 32 coupons per leg, i.e. up to 3 lite rows); longer
-        // ones keep their chained rows.  (seg_*[k] holds bucket kLiteSegments - 1 - k: longest first; route.hpp)
-        std::vector<int32_t> (&seg_plain)[adr::kLiteSegments] = cls.seg_plain, (&seg_lag)[adr::kLiteSegments] = cls.seg_lag;
-        std::vector<int32_t>&nonlite = cls.nonlite, &nonlite_b = cls.nonlite_b, &general_b = cls.general_b;
-        tr->n_nonlite = static_cast<int64_t>(nonlite.size());
-        tr->list_nonlite = put32(std::move(nonlite));
-        tr->n_nonlite_b = static_cast<int64_t>(nonlite_b.size());
-        tr->list_nonlite_b = put32(std::move(nonlite_b));
-        tr->n_general_b = static_cast<int64_t>(general_b.size());
-        tr->list_general_b = put32(std::move(general_b));
-        auto build_lite = [&](std::vector<int32_t> (&seg_trades)[adr::kLiteSegments], adr::LiteRowsDev& lt, int64_t& n_out,
-                              bool with_te) {
-            int64_t units = 0, rows = 0;
-            int used[adr::kLiteSegments];                 // the non-empty row counts, longest first, packed to the front
-            lt.n_seg = 0;
-            for (int k = 0; k < adr::kLiteSegments; ++k) {
-                lt.seg_rows[k] = 1; lt.seg_unit0[k] = 0; lt.seg_row0[k] = 0;
-                if (seg_trades[k].empty()) continue;
-                used[lt.n_seg++] = k;
-            }
-            for (int j = 0; j < lt.n_seg; ++j) {
-                const int k = used[j];
-                sort_by_coupons(seg_trades[k]);
-                n_out += static_cast<int64_t>(seg_trades[k].size());
-                lt.seg_rows[j] = static_cast<int>(kRowBuckets[adr::kLiteSegments - 1 - k]);
-                lt.seg_unit0[j] = units;
-                lt.seg_row0[j] = rows;
-                const int64_t seg_units = (static_cast<int64_t>(seg_trades[k].size()) + G - 1) / G;
-                units += seg_units;
-                rows += seg_units * G * lt.seg_rows[j];
-            }
-            for (int j = lt.n_seg; j < adr::kLiteSegments; ++j) { lt.seg_unit0[j] = units; lt.seg_row0[j] = rows; }   // (never reached)
-            lt.n_units = units;
-            if (rows * S > static_cast<int64_t>(UINT32_MAX)) { too_many_rows = true; return; }   // the kernel indexes with 32 bits
-            const size_t n_slots = static_cast<size_t>(units) * G, n_rows = static_cast<size_t>(rows);
-            std::vector<int32_t> slot_trade(n_slots, -1), row_slot(n_rows, -1);
-            std::vector<uint8_t> row_piece(n_rows, 0);
-            for (int j = 0; j < lt.n_seg; ++j) {
-                const int k = used[j];
-                const int R = lt.seg_rows[j];
-                const size_t slot0 = static_cast<size_t>(lt.seg_unit0[j]) * G, row0 = static_cast<size_t>(lt.seg_row0[j]);
-                for (size_t i = 0; i < seg_trades[k].size(); ++i) slot_trade[slot0 + i] = seg_trades[k][i];
-                const size_t slots_here = ((seg_trades[k].size() + G - 1) / G) * G;
-                for (size_t i = 0; i < slots_here; ++i)
-                    for (int r = 0; r < R; ++r) {
-                        row_slot[row0 + i * static_cast<size_t>(R) + static_cast<size_t>(r)] = static_cast<int32_t>(slot0 + i);
-                        row_piece[row0 + i * static_cast<size_t>(R) + static_cast<size_t>(r)] = static_cast<uint8_t>(r);
-                    }
-            }
-            adr::LiteBuildDev lb{};
-            lb.rows = static_cast<int64_t>(n_rows); lb.n_slots = static_cast<int64_t>(n_slots);
-            lb.slot_trade = put32(std::move(slot_trade));
-            lb.row_slot = put32(std::move(row_slot));
-            lb.row_piece = put8(std::move(row_piece));
-            lb.tp_ts = static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double)));
-            lb.al_xtp = static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double)));
-            lb.xpay = static_cast<double*>(alloc(n_rows * S * sizeof(double)));
-            lb.te_w = with_te ? static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double))) : nullptr;
-            lb.slot = static_cast<adr::LiteTrade*>(alloc(n_slots * sizeof(adr::LiteTrade)));
-            if (e == hipSuccess) e = adr::launch_build_lite(csr, lb, stream);
-            lt.tp_ts = lb.tp_ts; lt.al_xtp = lb.al_xtp; lt.xpay = lb.xpay; lt.te_w = lb.te_w; lt.slot = lb.slot;
-        };
-        build_lite(seg_plain, tr->lite, tr->n_lite, false);
-        if (!too_many_rows && tr->n_nonlite > tr->n_nonlite_b) build_lite(seg_lag, tr->lite_lag, tr->n_lite_lag, true);
+    // lite tables (kernels.hpp, LiteRowsDev): gathered on the device from their slots' trades and their rows' slot and piece
+    for (int s : {R::S_LITE, R::S_LITE_LAG}) {
+        constexpr int S = adr::kLiteSlots;
+        adr::LiteRowsDev& lt = tr->lite[s];
+        lt = L.lite[s];
+        if (L.trades[s].empty()) continue;
+        adr::LiteBuildDev lb{};
+        const size_t n_rows = L.lite_row_slot[s].size(), n_slots = L.trades[s].size();
+        lb.rows = static_cast<int64_t>(n_rows); lb.n_slots = static_cast<int64_t>(n_slots);
+        lb.slot_trade = put32(L.trades[s]);
+        lb.row_slot = put32(L.lite_row_slot[s]);
+        lb.row_piece = put8(L.lite_row_piece[s]);
+        lb.tp_ts = static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double)));
+        lb.al_xtp = static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double)));
+        lb.xpay = static_cast<double*>(alloc(n_rows * S * sizeof(double)));
+        lb.te_w = s == R::S_LITE_LAG ? static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double))) : nullptr;
+        lb.slot = static_cast<adr::LiteTrade*>(alloc(n_slots * sizeof(adr::LiteTrade)));
+        if (e == hipSuccess) e = adr::launch_build_lite(csr, lb, stream);
+        lt.tp_ts = lb.tp_ts; lt.al_xtp = lb.al_xtp; lt.xpay = lb.xpay; lt.te_w = lb.te_w; lt.slot = lb.slot;
     }
     // the copies and the table builders run on the ctx's stream: the batch is usable once they are done
     {
         const hipError_t es = hipStreamSynchronize(stream);        // (also on errors: the copies read this function's vectors)
         if (e == hipSuccess) e = es;
-    }
-    if (too_many_rows) {
-        adr_free_trades(tr);
-        return fail(ADR_ERR_UNSUPPORTED, "adr_trades_upload: more than 2^28 rows in the delta-only table; shard the portfolio");
     }
     if (e != hipSuccess) { adr_free_trades(tr); return fail_hip(e, "adr_trades_upload: copying trades"); }
     *out = tr;
@@ -1128,38 +917,25 @@ int adr_price_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades
     // class, the batch's table sizes and the request only; the batch keeps the last one (a book is priced again and again on
     // scenario curves of one class).
     const bool per_trade = o.pv || o.delta || o.gamma;
-    const adr::route::Plan& plan = trades->plan_for(curve->dev, want_delta, want_gamma, per_trade, agg_dev != nullptr, *ctx);
+    const std::shared_ptr<const R::Plan> held = trades->plan_for(curve->cls, want_delta, want_gamma, per_trade, agg_dev != nullptr, ctx->n_cu);
+    const R::Plan& plan = *held;
     if (plan.error) return fail(ADR_ERR_INVALID, std::string("adr_price: ") + plan.error);
 
-    namespace R = adr::route;
     const int stride = plan.wide ? adr::wide_partial_doubles(curve->dev.wide_nch) : adr::kAggStride;
-    auto list_view = [&](int set) {              // the general / wide / tiled kernels walk a trade list
-        adr::TradesDev v = trades->dev;
-        v.list = nullptr; v.n_list = n;
-        switch (set) {
-            case R::S_GENERAL: v.list = trades->list_general; v.n_list = trades->n_general; break;
-            case R::S_GENERAL_B: v.list = trades->list_general_b; v.n_list = trades->n_general_b; break;
-            case R::S_REST: v.list = trades->list_rest; v.n_list = trades->n_rest; break;
-            case R::S_NONLITE: v.list = trades->list_nonlite; v.n_list = trades->n_nonlite; break;
-            case R::S_NONLITE_B: v.list = trades->list_nonlite_b; v.n_list = trades->n_nonlite_b; break;
-            default: break;                      // S_ALL: the identity list
-        }
-        return v;
-    };
     if (plan.tiled && agg_dev)   // tiles no launch covers (no GAMMA: the off-diagonal ones; PV alone: every delta tile) stay zero
         ADR_HIP(hipMemsetAsync(agg_dev, 0, agg_bytes, stream));
     const R::Launch *knot = nullptr, *knot_lag = nullptr;
     for (const R::Launch& L : plan.launches) {
         o.block_partials = agg_dev ? ctx->partials + static_cast<size_t>(L.first_block) * stride : nullptr;
         switch (L.family) {
-            case R::F_LITE: ADR_HIP(adr::launch_price_lite(curve->dev, trades->lite, o, want_delta, L.blocks, stream)); break;
-            case R::F_LITE_LAG: ADR_HIP(adr::launch_price_lite(curve->dev, trades->lite_lag, o, want_delta, L.blocks, stream)); break;
-            case R::F_FAST: ADR_HIP(adr::launch_price_fast(curve->dev, trades->dev, o, want_delta, want_gamma, L.blocks, stream)); break;
-            case R::F_FAST_CHAINED: ADR_HIP(adr::launch_price_fast(curve->dev, trades->chained, o, want_delta, want_gamma, L.blocks, stream)); break;
-            case R::F_FAST_LAG: ADR_HIP(adr::launch_price_fast(curve->dev, trades->lagged, o, want_delta, want_gamma, L.blocks, stream)); break;
-            case R::F_FAST_LAG_CHAINED: ADR_HIP(adr::launch_price_fast(curve->dev, trades->lagged_chained, o, want_delta, want_gamma, L.blocks, stream)); break;
-            case R::F_GENERAL: ADR_HIP(adr::launch_price_general(curve->dev, list_view(L.set), o, want_delta, want_gamma, L.blocks, stream)); break;
-            case R::F_WIDE: ADR_HIP(adr::launch_price_wide(curve->dev, list_view(L.set), o, want_delta, want_gamma, L.blocks, stream)); break;
+            case R::F_LITE:
+            case R::F_LITE_LAG: ADR_HIP(adr::launch_price_lite(curve->dev, trades->lite[L.set], o, want_delta, L.blocks, stream)); break;
+            case R::F_FAST:
+            case R::F_FAST_CHAINED:
+            case R::F_FAST_LAG:
+            case R::F_FAST_LAG_CHAINED: ADR_HIP(adr::launch_price_fast(curve->dev, trades->set[L.set], o, want_delta, want_gamma, L.blocks, stream)); break;
+            case R::F_GENERAL: ADR_HIP(adr::launch_price_general(curve->dev, trades->set[L.set], o, want_delta, want_gamma, L.blocks, stream)); break;
+            case R::F_WIDE: ADR_HIP(adr::launch_price_wide(curve->dev, trades->set[L.set], o, want_delta, want_gamma, L.blocks, stream)); break;
             case R::F_TILED: {
                 // each launch writes its tile of the ladders; its partials are reduced into its tile of the aggregate
                 adr::CurveDev cv = curve->dev;
@@ -1167,7 +943,7 @@ int adr_price_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades
                 const size_t pair_tile = static_cast<size_t>(curve->dev.Kc) * 64 * adr::kGammaPerLane;
                 if (cv.lc_lanes) cv.lc_lanes += static_cast<size_t>(adr::tile_pair(L.tile_i, L.tile_j)) * pair_tile;
                 if (cv.lc_block_mask) cv.lc_block_mask += static_cast<size_t>(adr::tile_pair(L.tile_i, L.tile_j)) * curve->dev.Kc;
-                ADR_HIP(adr::launch_price_general(cv, list_view(L.set), o, want_delta, want_gamma, L.blocks, stream));
+                ADR_HIP(adr::launch_price_general(cv, trades->set[L.set], o, want_delta, want_gamma, L.blocks, stream));
                 if (agg_dev)
                     ADR_HIP(adr::launch_reduce_partials(o.block_partials, L.blocks, P, want_gamma, agg_dev, stream, L.tile_i, L.tile_j));
                 break;
@@ -1186,14 +962,14 @@ int adr_price_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades
         // aggregate-only request (agg and no per-trade output - Portfolio.compute's single ladder): the lite table's trades
         // are summed in KNOT space and projected once (kernels_lite.hip KNOT instantiations, kernels_knot.hip); the
         // projection ADDS to what the other families' reduction wrote above
-        ADR_HIP(adr::launch_price_knot(curve->dev, trades->lite, o, want_gamma, knot->blocks, stream));
+        ADR_HIP(adr::launch_price_knot(curve->dev, trades->lite[knot->set], o, want_gamma, knot->blocks, stream));
         ADR_HIP(adr::launch_knot_project(curve->dev, ctx->knot_partials, knot->blocks, ctx->knot_reduced, want_delta, want_gamma, 1, nullptr, agg_dev, stream));
     }
     if (knot_lag) {
         // ... and the payment-lag rows' ratio nodes: pair bands per wave, pairs farther apart in the launch's overflow matrix
         const size_t kc = static_cast<size_t>(curve->dev.Kc);
         if (want_gamma) ADR_HIP(hipMemsetAsync(ctx->knot_overflow, 0, sizeof(double) * (kc * kc + 1), stream));   // (+ the "in use" flag)
-        ADR_HIP(adr::launch_price_knot(curve->dev, trades->lite_lag, o, want_gamma, knot_lag->blocks, stream));
+        ADR_HIP(adr::launch_price_knot(curve->dev, trades->lite[knot_lag->set], o, want_gamma, knot_lag->blocks, stream));
         ADR_HIP(adr::launch_knot_project(curve->dev, ctx->knot_partials, knot_lag->blocks, ctx->knot_reduced, want_delta, want_gamma,
                                          adr::kKnotBand, ctx->knot_overflow, agg_dev, stream));
     }
@@ -1256,11 +1032,12 @@ int adr_price_xccy_foreign_dev(adr_ctx* ctx, const adr_curve* foreign_curve, con
         return ADR_OK;
     }
     // every leg must sit in the lite kernel's payment-lag rows (accrual end != payment time on some coupon, <= 390 coupons)
-    if (legs->lite.n_units > 0 || legs->n_nonlite_b > 0 || legs->lite_lag.n_units == 0)
+    const adr::LiteRowsDev& rows = legs->lite[R::S_LITE_LAG];
+    if (legs->lite[R::S_LITE].n_units > 0 || legs->counts.n_nonlite_b > 0 || rows.n_units == 0)
         return fail(ADR_ERR_UNSUPPORTED, "adr_price_xccy_foreign: a leg is outside the payment-lag row table (more than 390 coupons, "
                                          "or no coupon whose accrual end differs from its payment time)");
     // one block per CU: its registers leave room for the block's own three waves per SIMD
-    const int blocks = adr::route::blocks_for(legs->lite_lag.n_units, adr::lite_xc_kernel_threads() / 64, static_cast<int64_t>(ctx->n_cu));
+    const int blocks = R::blocks_for(rows.n_units, adr::lite_xc_kernel_threads() / 64, static_cast<int64_t>(ctx->n_cu));
     if (2 * blocks > ctx->max_blocks) return fail(ADR_ERR_INVALID, "adr_price_xccy_foreign: grid exceeds scratch");
     const bool want_agg = agg_foreign_dev || agg_basis_dev;
     adr::OutputsDev o{};
@@ -1269,7 +1046,7 @@ int adr_price_xccy_foreign_dev(adr_ctx* ctx, const adr_curve* foreign_curve, con
     o.delta2 = (req_mask & ADR_REQ_DELTA) ? delta_basis_dev : nullptr;
     o.block_partials = want_agg ? ctx->partials : nullptr;
     o.block_partials2 = want_agg ? ctx->partials + static_cast<size_t>(blocks) * adr::kAggStride : nullptr;
-    ADR_HIP(adr::launch_price_lite_xc(cf, cx, legs->lite_lag, o, blocks, stream));
+    ADR_HIP(adr::launch_price_lite_xc(cf, cx, rows, o, blocks, stream));
     if (agg_foreign_dev) ADR_HIP(adr::launch_reduce_partials(o.block_partials, blocks, Pf, false, agg_foreign_dev, stream));
     if (agg_basis_dev) ADR_HIP(adr::launch_reduce_partials(o.block_partials2, blocks, Px, false, agg_basis_dev, stream));
     return ADR_OK;
@@ -1312,70 +1089,28 @@ int adr_route_host(int interp_method, int K, int P, const double* times, const d
     adr::CurveTables t;
     const std::string err = adr::build_curve_tables(K, P, times, dfs, jac, hess, t);
     if (!err.empty()) return fail(ADR_ERR_INVALID, "adr_route_host: " + err);
-    // the curve's class, as adr_curve_upload_ex decides it (integer fields only: no table is read by the plan)
-    adr::CurveDev cv{};
-    cv.K = t.K; cv.Kc = t.Kc; cv.P = t.P; cv.method = interp_method; cv.T = t.T;
-    cv.Pc = t.Pc; cv.pc_pad = t.pc_pad; cv.Ec = t.Ec; cv.Eu = t.Eu; cv.epg = t.epg; cv.cpg = t.cpg; cv.hub = t.hub ? 1 : 0;
-    cv.Kcore = t.Kcore; cv.n_mini = t.n_mini; cv.n_fringe = t.n_fringe; cv.n_lut = static_cast<int>(t.lut.size() / 2);
-    const bool wide = t.wide_nch > 0 && t.wide_nch <= adr::kWideMaxChunks && !(curve_flags & ADR_CURVE_PILLAR_TILES) &&
-                      adr::wide_kernel_lds_bytes(t.K, t.Kc, t.wide_nch, t.has_hess) <= kLdsBudget;
-    cv.wide_nch = wide ? t.wide_nch : 0;
-    cv.packed_ok = (t.packed_ok && adr::fast_kernel_lds_bytes(cv, t.has_hess) <= kLdsBudget) ? 1 : 0;
+    const R::CurveClass cls = R::curve_class(t, interp_method, (curve_flags & ADR_CURVE_PILLAR_TILES) != 0);
     if ((req_mask & ADR_REQ_GAMMA) && !t.has_hess) return fail(ADR_ERR_INVALID, "adr_route_host: GAMMA requested but hess is null");
-    // the trades' classes, as adr_trades_upload decides them
     std::vector<uint8_t> lagged_of(static_cast<size_t>(n), 0);
-    for (int64_t tr = 0; tr < n; ++tr) {
-        bool lag = false;
-        for (int64_t j = flt_off[tr]; j < flt_off[tr + 1] && !lag; ++j)
-            lag = (flt_alpha[j] > 0.0 && flt_te[j] != flt_tp[j]) || (flt_weight && flt_weight[j] != 1.0);
-        lagged_of[static_cast<size_t>(tr)] = lag ? 1 : 0;
-    }
-    namespace R = adr::route;
-    R::TradeClasses cls;
-    R::classify_trades(n, fix_off, flt_off, lagged_of.data(), cls);
-    R::TradeCounts tc;
-    tc.n = n;
-    tc.rows = static_cast<int64_t>(cls.list_fast.size());
-    tc.chained_rows = static_cast<int64_t>(cls.list_long.size());               // (non-zero is all the plan asks of the chained tables)
-    tc.lagged_rows = static_cast<int64_t>(cls.list_lagged.size());
-    tc.lagged_chained_rows = static_cast<int64_t>(cls.list_lagged_long.size());
-    tc.lite_units = cls.lite_units; tc.lite_lag_units = cls.lite_lag_units;
-    tc.n_general = static_cast<int64_t>(cls.list_general.size()); tc.n_general_b = static_cast<int64_t>(cls.general_b.size());
-    tc.n_rest = static_cast<int64_t>(cls.list_rest.size());
-    tc.n_nonlite = static_cast<int64_t>(cls.nonlite.size()); tc.n_nonlite_b = static_cast<int64_t>(cls.nonlite_b.size());
-    tc.chained_blocks = cls.list_long.empty() ? 0 : n_cu;
-    tc.lagged_chained_blocks = cls.list_lagged_long.empty() ? 0 : n_cu;
-    tc.lag_scratch = !cls.list_lagged.empty() || !cls.list_lagged_long.empty();
-    tc.lag_blocks = tc.lag_scratch ? n_cu : 0;
+    R::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, lagged_of.data());
+    const R::TradeLayout L = R::trade_layout(n, fix_off, flt_off, lagged_of.data(), n_cu);
+    if (L.too_many_rows)
+        return fail(ADR_ERR_UNSUPPORTED, "adr_route_host: more than 2^28 rows in the delta-only table; shard the portfolio");
     const bool want_gamma = (req_mask & ADR_REQ_GAMMA) != 0, want_delta = want_gamma || (req_mask & ADR_REQ_DELTA) != 0;
-    const R::Plan plan = R::make_plan(cv, tc, want_delta, want_gamma, per_trade != 0, aggregate != 0, n_cu, n_cu * 16,
-                                      n_cu * adr::kLiteWavesPerSimd * 4 * 64 / adr::kLiteThreads, kKnotMaxKc, kKnotLagMaxKc);
+    const R::Plan plan = R::make_plan(cls, L.counts, want_delta, want_gamma, per_trade != 0, aggregate != 0, n_cu);
     if (plan.error) return fail(ADR_ERR_INVALID, std::string("adr_route_host: ") + plan.error);
     // who is covered how often: the tile launches of one pass count once
     for (int64_t i = 0; i < n; ++i) cover[i] = 0;
-    auto add = [&](const std::vector<int32_t>& list) { for (int32_t tr : list) ++cover[tr]; };
     int n_out = 0;
-    for (const R::Launch& L : plan.launches) {
+    for (const R::Launch& Ln : plan.launches) {
         if (n_out < max_launches) {
             int32_t* row = launches + 4 * n_out;
-            row[0] = L.family; row[1] = L.set; row[2] = static_cast<int32_t>(std::min<int64_t>(L.items, INT32_MAX)); row[3] = L.blocks;
+            row[0] = Ln.family; row[1] = Ln.set; row[2] = static_cast<int32_t>(std::min<int64_t>(Ln.items, INT32_MAX)); row[3] = Ln.blocks;
         }
         ++n_out;
-        if (L.family == R::F_TILED && !(L.tile_i == 0 && L.tile_j == 0)) continue;
-        switch (L.set) {
-            case R::S_LITE: for (auto& v : cls.seg_plain) add(v); break;
-            case R::S_LITE_LAG: for (auto& v : cls.seg_lag) add(v); break;
-            case R::S_ROWS: add(cls.list_fast); break;
-            case R::S_CHAINED: add(cls.list_long); break;
-            case R::S_LAGGED: add(cls.list_lagged); break;
-            case R::S_LAGGED_CHAINED: add(cls.list_lagged_long); break;
-            case R::S_GENERAL: add(cls.list_general); break;
-            case R::S_GENERAL_B: add(cls.general_b); break;
-            case R::S_REST: add(cls.list_rest); break;
-            case R::S_NONLITE: add(cls.nonlite); break;
-            case R::S_NONLITE_B: add(cls.nonlite_b); break;
-            default: for (int64_t i = 0; i < n; ++i) ++cover[i]; break;
-        }
+        if (Ln.family == R::F_TILED && !(Ln.tile_i == 0 && Ln.tile_j == 0)) continue;
+        if (Ln.set == R::S_ALL) for (int64_t i = 0; i < n; ++i) ++cover[i];
+        for (int32_t tr : L.trades[Ln.set]) if (tr >= 0) ++cover[tr];        // (-1: an empty slot of a lite table)
     }
     return n_out;
 }

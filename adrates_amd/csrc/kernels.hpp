@@ -47,7 +47,7 @@ constexpr int kLiteSlots = 16;
 constexpr int kLiteCoupons = 15;
 constexpr int kKnotBand = 16;                                        // aggregate-only mode, payment-lag rows: pair bands kept per wave (knots up to 16 apart)
 constexpr int kLiteSegments = 9;                                     // distinct row counts per table: 1, 2, 3, 4, 6, 8, 12, 16, 26 rows
-                                                                     // (route.hpp) = up to 390 coupons per leg
+                                                                     // (route.cpp) = up to 390 coupons per leg
 
 // Per-trade header, 32 bytes, read once per trade with scalar loads.
 struct TradeHeader {

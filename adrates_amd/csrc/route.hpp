@@ -1,7 +1,8 @@
 // Launch plan of a pricing call: which kernel family takes which set of trades, on what grid, and where its block partials
 // go.  Pure host logic (no HIP call): adr_price_dev builds the plan from the curve's class and the batch's table sizes and
-// replays it; adr_route_host exposes the same function for a CPU test that checks, over the cross product of trade
-// classes, curve classes, schemes and requests, that every trade is priced exactly once (tests/test_route_table.py).
+// replays it; adr_route_host runs the same three functions (curve_class, trade_layout, make_plan) for a CPU test that
+// checks, over the cross product of trade classes, curve classes, schemes and requests, that every trade is priced
+// exactly once (tests/test_route_table.py).
 //
 // The reference has one route - Engine._compute_ois_natural walks a trade's legs whatever they look like
 // (cavour/market/position/engine.py:153-215); everything here is about which specialised kernel gives the same numbers fastest.
@@ -39,6 +40,7 @@ enum Set : int {
     S_NONLITE_B = 10,     // ... and outside the lite kernel's payment-lag rows
     S_ALL = 11
 };
+constexpr int kSets = S_ALL + 1;
 
 struct Launch {
     int family, set;
@@ -68,26 +70,70 @@ struct Plan {
 };
 
 constexpr size_t kLds = 160 * 1024;
+constexpr int kKnotMaxKc = 640;             // reachable knots a curve can have for the knot pass (its dense 32-wide Jacobian must fit the LDS)
+constexpr int kKnotLagMaxKc = 256;          // ... for the knot pass over payment-lag rows (16 pair bands per knot, a dense overflow matrix)
+
+// The scratch grids of a device of n_cu CUs (adr_ctx): block partials for max_blocks blocks, knot-pass records for knot_blocks
+struct Grid { int max_blocks, knot_blocks; };
+inline Grid grid_for(int n_cu) {
+    const int cu = std::max(1, n_cu);
+    return Grid{cu * 16, cu * kLiteWavesPerSimd * 4 * 64 / kLiteThreads};     // (knot pass: the blocks resident at once)
+}
+
+// The class of a curve: everything about it the plan reads.  Two curves of one class get the same plan, so the class plus
+// the request is the key of the plan a batch caches.
+struct CurveClass {
+    int K, Kc, P, T, method;
+    int wide_nch;       // chunks of the wide layout's tables when the curve takes the wide route, else 0
+    int packed_ok;      // the packed layout exists and the fast kernel's tables fit the LDS
+    int lds_rows;       // GAMMA: the general kernel's variant with LDS-resident convexity rows serves the curve
+    int n_lut, Kcore, pc_pad, Ec, epg, cpg, n_mini;    // what the kernels' LDS sizes read besides (kernels.hpp)
+    CurveDev sizes() const {                           // a CurveDev without tables, for those size functions
+        CurveDev d{};
+        d.K = K; d.Kc = Kc; d.P = P; d.T = T; d.method = method; d.wide_nch = wide_nch; d.packed_ok = packed_ok;
+        d.n_lut = n_lut; d.Kcore = Kcore; d.pc_pad = pc_pad; d.Ec = Ec; d.epg = epg; d.cpg = cpg; d.n_mini = n_mini;
+        return d;
+    }
+};
+
+// The class of the curve of tables t under interpolation scheme `method`; pillar_tiles: ADR_CURVE_PILLAR_TILES.
+// 33-64 pillars take the wide route when its tables fit the LDS, else the tiles; the packed layout of up to 32 pillars serves
+// the fast kernels only when their tables fit the LDS next to the search arrays, else the general kernel serves all.
+inline CurveClass curve_class(const CurveTables& t, int method, bool pillar_tiles) {
+    CurveClass c{};
+    c.K = t.K; c.Kc = t.Kc; c.P = t.P; c.T = t.T; c.method = method;
+    c.n_lut = static_cast<int>(t.lut.size() / 2); c.Kcore = t.Kcore; c.pc_pad = t.pc_pad; c.Ec = t.Ec; c.epg = t.epg; c.cpg = t.cpg;
+    c.n_mini = t.n_mini;
+    const bool wide = t.wide_nch > 0 && t.wide_nch <= kWideMaxChunks && !pillar_tiles &&
+                      wide_kernel_lds_bytes(t.K, t.Kc, t.wide_nch, t.has_hess) <= kLds;
+    c.wide_nch = wide ? t.wide_nch : 0;
+    c.packed_ok = t.packed_ok && fast_kernel_lds_bytes(c.sizes(), t.has_hess) <= kLds ? 1 : 0;
+    // (the convexity rows are uploaded with the packed layout, whether or not the fast kernel's tables fit)
+    c.lds_rows = t.has_hess && t.packed_ok && t.T == 1 &&
+                 general_lds_rows_fit(general_lds_kernel_lds_bytes_for(t.K, t.Kc, t.Kcore, t.Ec, t.n_mini, c.n_lut, true), t.Ec, t.n_fringe);
+    return c;
+}
 
 inline int blocks_for(int64_t units, int waves, int64_t cap) {
     const int64_t need = (units + waves - 1) / waves;
     return static_cast<int>(std::min<int64_t>(need, cap));
 }
 
-// cv: only its integer fields are read (a CurveDev built from CurveTables on the host serves as well); has_hess: the curve
-// carries second derivatives.  per_trade: some per-trade output pointer is non-null; has_agg: agg is requested.
-inline Plan make_plan(const CurveDev& cv, const TradeCounts& tc, bool want_delta, bool want_gamma, bool per_trade, bool has_agg,
-                      int n_cu, int max_blocks, int knot_blocks, int knot_kc_max, int knot_lag_kc_max) {
+// per_trade: some per-trade output pointer is non-null; has_agg: agg is requested.
+inline Plan make_plan(const CurveClass& cc, const TradeCounts& tc, bool want_delta, bool want_gamma, bool per_trade, bool has_agg,
+                      int n_cu) {
     Plan plan;
     const int64_t n = tc.n;
     if (n == 0) return plan;
+    const CurveDev cv = cc.sizes();
+    const int max_blocks = grid_for(n_cu).max_blocks, knot_blocks = grid_for(n_cu).knot_blocks;
     const bool lite_fits = lite_kernel_lds_bytes(cv, want_delta, true) <= kLds;
     const bool log_linear = cv.method != 2;
     // aggregate-only request: the lite table's trades in knot space
-    plan.knot = has_agg && !per_trade && want_delta && tc.lite_units > 0 && cv.Kc <= knot_kc_max &&
+    plan.knot = has_agg && !per_trade && want_delta && tc.lite_units > 0 && cv.Kc <= kKnotMaxKc &&
                 knot_kernel_lds_bytes(cv, want_gamma) <= kLds;
     // ... and the payment-lag rows' (ratio nodes, any scheme; the pair bands of 16 want more LDS and scratch per knot)
-    plan.knot_lag = has_agg && !per_trade && want_delta && tc.lite_lag_units > 0 && cv.Kc <= knot_lag_kc_max &&
+    plan.knot_lag = has_agg && !per_trade && want_delta && tc.lite_lag_units > 0 && cv.Kc <= kKnotLagMaxKc &&
                     (plan.knot || tc.lite_units == 0) && knot_kernel_lds_bytes(cv, want_gamma, true) <= kLds;
     // the trades no knot pass takes: everything / outside the lite table / and outside its payment-lag rows
     const int rest_of_knot = plan.knot_lag ? S_NONLITE_B : (plan.knot ? S_NONLITE : S_ALL);
@@ -200,7 +246,7 @@ inline Plan make_plan(const CurveDev& cv, const TradeCounts& tc, bool want_delta
     }
     if (chained > 0) push(F_FAST_CHAINED, S_CHAINED, chained, tc.chained_blocks);        // the chains are laid out for this grid
     if (general_n > 0) {
-        const int threads = general_kernel_threads(cv, want_gamma);     // 512: LDS-resident convexity rows
+        const int threads = want_gamma && cc.lds_rows ? kGeneralLdsThreads : kGeneralThreads;    // (general_kernel_threads)
         push(F_GENERAL, general_set, general_n,
              blocks_for(general_n, threads / 64, static_cast<int64_t>(n_cu) * (threads == kGeneralThreads ? 4 : 2)));
     }
@@ -216,57 +262,44 @@ inline Plan make_plan(const CurveDev& cv, const TradeCounts& tc, bool want_delta
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Classes of the trades of a batch: which table or list each trade lands in (host side of adr_trades_upload).
+// Trade layout: which table or list every trade of a batch lands in, and the host side of those tables (route.cpp).
+// adr_trades_upload copies it to the device and gathers the tables there (trades_build.hip); adr_route_host reads it.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int64_t kMaxChain = 12;                                       // rows per trade in the chained table: legs of up to 384 coupons
 constexpr int64_t kMaxChainLag = kLagScratchNodes / kRowSlots;          // ... payment-lag legs: 128 (the variant's per-trade stash)
-static const int64_t kLiteRowBuckets[kLiteSegments] = {1, 2, 3, 4, 6, 8, 12, 16, 26};   // lite rows per trade, rounded up (26 x 15 >= 384)
 
-struct TradeClasses {
-    std::vector<int32_t> list_fast, list_long, list_general, list_lagged, list_lagged_long, list_rest;
-    std::vector<int32_t> seg_plain[kLiteSegments], seg_lag[kLiteSegments], nonlite, nonlite_b, general_b;
-    int64_t lite_units = 0, lite_lag_units = 0;
+struct TradeLayout {
+    // The trades of each set, in table order: a list set's list; a row table's trades (one row each, sorted by coupon count;
+    // the chained tables: in the order their chains were dealt); a lite table's slots (-1: an empty slot).  S_ALL: empty.
+    std::vector<int32_t> trades[kSets];
+    // chained tables (S_CHAINED, S_LAGGED_CHAINED): the rows dealt to the wave columns - the row's trade (-1: empty), the
+    // first coupon of its piece and "the trade continues in the group's next row"
+    std::vector<int32_t> chain_trade[kSets], chain_first[kSets];
+    std::vector<uint8_t> chain_more[kSets];
+    // lite tables (S_LITE, S_LITE_LAG): the segment header (device pointers null) and every row's slot and piece
+    LiteRowsDev lite[2] = {};
+    std::vector<int32_t> lite_row_slot[2];
+    std::vector<uint8_t> lite_row_piece[2];
+    TradeCounts counts;
+    bool any_lagged = false;      // some trade has payment lag or per-coupon notionals (TradesDev::any_ratio)
+    bool too_many_rows = false;   // a lite table has more than 2^32 slots: its work lists are not built
 };
 
-// lagged_of[t] != 0: a coupon of trade t accrues to a date other than its payment date, or carries a weight != 1
-inline void classify_trades(int64_t n, const int64_t* fix_off, const int64_t* flt_off, const uint8_t* lagged_of, TradeClasses& out) {
-    auto rows_of = [&](int64_t t) {
-        const int64_t m = std::max(flt_off[t + 1] - flt_off[t], fix_off[t + 1] - fix_off[t]);
-        return std::max<int64_t>(1, (m + kRowSlots - 1) / kRowSlots);
-    };
-    auto lite_bucket = [&](int64_t t) {
-        const int64_t m = std::max(flt_off[t + 1] - flt_off[t], fix_off[t + 1] - fix_off[t]);
-        const int64_t rows = std::max<int64_t>(1, (m + kLiteCoupons - 1) / kLiteCoupons);
-        int b = 0;
-        while (b < kLiteSegments && kLiteRowBuckets[b] < rows) ++b;
-        return b;
-    };
-    std::vector<char> lite_lag(static_cast<size_t>(n), 0);
-    for (int64_t t = 0; t < n; ++t) {
-        const int64_t rows = rows_of(t);
-        const bool lagged = lagged_of[static_cast<size_t>(t)] != 0;
-        const bool general = rows > kMaxChain || lagged;
-        (general ? out.list_general : rows > 1 ? out.list_long : out.list_fast).push_back(static_cast<int32_t>(t));
-        if (general) (rows == 1 ? out.list_lagged : rows <= kMaxChainLag ? out.list_lagged_long : out.list_rest).push_back(static_cast<int32_t>(t));
-        // lite tables: plain = the trades of the 32-slot row tables, one-row and chained (legs of up to 384 coupons = 26 lite
-        // rows of 15); with payment lag / weights: as many rows as the buckets allow
-        const int bucket = lite_bucket(t);
-        if (!general) { out.seg_plain[kLiteSegments - 1 - bucket].push_back(static_cast<int32_t>(t)); continue; }
-        out.nonlite.push_back(static_cast<int32_t>(t));
-        if (lagged && bucket < kLiteSegments) {
-            out.seg_lag[kLiteSegments - 1 - bucket].push_back(static_cast<int32_t>(t));
-            lite_lag[static_cast<size_t>(t)] = 1;
-        } else {
-            out.nonlite_b.push_back(static_cast<int32_t>(t));
-        }
-    }
-    for (int32_t t : out.list_general) if (!lite_lag[static_cast<size_t>(t)]) out.general_b.push_back(t);
-    constexpr int G = 64 / kLiteSlots;
-    for (int k = 0; k < kLiteSegments; ++k) {
-        out.lite_units += (static_cast<int64_t>(out.seg_plain[k].size()) + G - 1) / G;
-        out.lite_lag_units += (static_cast<int64_t>(out.seg_lag[k].size()) + G - 1) / G;
+// lagged_of[t] for the trades t0 <= t < t1: a float coupon of trade t accrues to a date other than its payment date (payment
+// lag: ratio terms), or carries a weight != 1.  (adr_trades_upload runs it inside its validation pass, one range per thread.)
+inline void flag_lagged(int64_t t0, int64_t t1, const int64_t* flt_off, const double* flt_tp, const double* flt_te,
+                        const double* flt_alpha, const double* flt_weight, uint8_t* lagged_of) {
+    for (int64_t t = t0; t < t1; ++t) {
+        bool lag = false;
+        for (int64_t j = flt_off[t]; j < flt_off[t + 1] && !lag; ++j)
+            lag = (flt_alpha[j] > 0.0 && flt_te[j] != flt_tp[j]) || (flt_weight && flt_weight[j] != 1.0);
+        lagged_of[t] = lag ? 1 : 0;
     }
 }
+
+// The trades' classes and tables (the offsets have been validated; lagged_of: flag_lagged).  n_cu: the grid the chained
+// tables are dealt for.
+TradeLayout trade_layout(int64_t n, const int64_t* fix_off, const int64_t* flt_off, const uint8_t* lagged_of, int n_cu);
 
 }  // namespace route
 }  // namespace adr

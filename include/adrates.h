@@ -227,8 +227,8 @@ void adr_free_curve_set(adr_curve_set* set);
  *   fix_sign, flt_sign     +1 receive / -1 pay, per trade
  * Value time is 0 and both principals are 0, as for every OIS the reference builds
  * (cavour/trades/rates/ois.py:149, swap_float_leg.py:106).
- * The arrays are validated and classified on the host (a thread per contiguous trade range), copied to the
- * device once, and the kernels' padded row tables are gathered from them ON THE DEVICE (trades_build.hip):
+ * The arrays are validated on the host (a thread per contiguous trade range) and classified there (route.cpp,
+ * trade_layout), copied to the device once, and the kernels' padded row tables are gathered from them ON THE DEVICE (trades_build.hip):
  * about 40 ms per million benchmark trades.  Blocks until the batch is usable; may be called from several
  * host threads on one ctx (it touches no shared state of the ctx but its stream).
  */
@@ -284,9 +284,11 @@ int adr_price(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades,
  * Same, with device-resident outputs and no host synchronisation: the kernels
  * are enqueued on `stream` (a hipStream_t; NULL = the ctx's own stream) and the
  * call returns immediately.  Output pointers are device memory owned by the
- * caller.  This is the entry the throughput benchmark times.  The call neither
- * allocates nor synchronises, so a sequence of them (a scenario ladder, the pieces
+ * caller.  This is the entry the throughput benchmark times.  The call does no device
+ * allocation and no synchronisation, so a sequence of them (a scenario ladder, the pieces
  * of a cross-currency book) can be captured on `stream` into a HIP graph and replayed.
+ * (The first call for a (curve class, request) on a batch builds the batch's host-side
+ * launch plan; later calls replay it.  Concurrent calls each hold the plan they walk.)
  * Stream rules: (1) a call with agg_dev != NULL stages its per-block partial sums in scratch
  * owned by the ctx, so all aggregate-producing calls of one ctx must be ordered on ONE
  * stream (or separated by a synchronisation); use one ctx per stream for concurrent aggregates.
@@ -322,7 +324,7 @@ int adr_price_xccy_foreign_dev(adr_ctx* ctx, const adr_curve* foreign_curve, con
 
 /*
  * Host-side half of adr_price_dev's routing, exposed so that it can be checked without a GPU (like adr_curve_layout_host):
- * the launch plan for a curve (arguments as adr_curve_upload_ex) and a batch (the arrays of adr_trades_upload_weighted the
+ * the curve class, trade layout and launch plan the upload and adr_price_dev compute (route.hpp), for a curve (arguments as adr_curve_upload_ex) and a batch (the arrays of adr_trades_upload_weighted the
  * classification reads) under a request - req_mask, per_trade != 0: some per-trade output is wanted, aggregate != 0: agg is
  * wanted - on a device of n_cu compute units.  launches [max_launches][4] receives {kernel family, trade set, items,
  * blocks} per launch (enums of adrates_amd/csrc/route.hpp), cover [n] how many launches price each trade (the tile
