@@ -73,6 +73,12 @@ _SIGNATURES = {
     "adr_exchange_flows_host": (C.c_int, [C.c_int64, _dp, _dp, C.POINTER(C.c_uint8), _dp, C.c_double, _i64p, _dp, _dp, _dp]),
     "adr_xccy_assemble_host": (C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp,
                                          C.POINTER(C.c_uint8), _i64p, _dp, _dp, _dp, _dp, _i64p, _dp, _dp, _dp]),
+    "adr_bond_measures": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int64, _i64p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                    _dp, C.c_int, _dp, _i32p]),
+    "adr_bond_measures_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "adr_bond_measures_host": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.c_int64, _i64p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                         _dp, C.c_int, _dp, _i32p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -493,6 +499,67 @@ def xccy_assemble_host(for_off, tp_x, ts, te, alpha, disc, growth, for_n, for_sp
         r_off[:] = 0; f_off[:] = 0
     kr, kf = int(r_off[-1]), int(f_off[-1])
     return r_off, r_ts[:kr], r_te[:kr], r_al[:kr], r_w[:kr], f_off, f_tp[:kf], f_pay[:kf], pv
+
+
+BOND_OUTPUTS = ("z", "dirty", "clean", "ytm", "duration", "convexity", "dv01")     # rows of adr_bond_measures' out
+BOND_FLOW_FIELDS = ("flow_T", "flow_tau", "flow_cpn", "flow_prin")
+BOND_FIELDS = ("bond_Ts", "bond_tauM", "bond_face", "bond_acc100", "bond_quote")
+
+
+def _bond_arrays(node_t, node_df, book):
+    """Contiguous copies of a bond book's arrays (keys: ``flow_off``, BOND_FLOW_FIELDS, BOND_FIELDS)."""
+    node_t, node_df = _f64(node_t), _f64(node_df)
+    if node_t.ndim != 1 or node_t.shape != node_df.shape:
+        raise LibError("node_t and node_df must be 1-D arrays of one length")
+    arr = {"flow_off": np.ascontiguousarray(book["flow_off"], dtype=np.int64)}
+    n = arr["flow_off"].shape[0] - 1
+    if n < 0:
+        raise LibError("flow_off needs n_bonds + 1 entries")
+    for k in BOND_FLOW_FIELDS + BOND_FIELDS:
+        arr[k] = _f64(book[k]).reshape(-1)
+    m = int(arr["flow_off"][-1]) if n > 0 else 0
+    if any(arr[k].shape != (m,) for k in BOND_FLOW_FIELDS) or any(arr[k].shape != (n,) for k in BOND_FIELDS):
+        raise LibError("bond arrays have inconsistent lengths")
+    return node_t, node_df, arr, n
+
+
+def _bond_result(out, status):
+    res = {k: out[i] for i, k in enumerate(BOND_OUTPUTS)}
+    res["status"] = status
+    return res
+
+
+def bond_measures(ctx: Context, interp_method: int, node_t, node_df, book, quote_is_z: bool):
+    """Spread and yield measures of a bond book on the GPU (adr_bond_measures, blocking).  ``book``: a mapping with
+    ``flow_off`` and the fields BOND_FLOW_FIELDS + BOND_FIELDS.  Returns a dict of arrays, keys BOND_OUTPUTS + ``status``."""
+    node_t, node_df, a, n = _bond_arrays(node_t, node_df, book)
+    out, status = np.empty((len(BOND_OUTPUTS), n)), np.empty(n, dtype=np.int32)
+    _check(load().adr_bond_measures(ctx._h, int(interp_method), node_t.size, _ptr(node_t), _ptr(node_df), n,
+                                    _ptr(a["flow_off"], _i64p), *(_ptr(a[k]) for k in BOND_FLOW_FIELDS + BOND_FIELDS),
+                                    1 if quote_is_z else 0, _ptr(out), _ptr(status, _i32p)), "adr_bond_measures")
+    return _bond_result(out, status)
+
+
+def bond_measures_host(interp_method: int, node_t, node_df, book, quote_is_z: bool):
+    """The same per-bond code on the CPU (adr_bond_measures_host; no GPU needed)."""
+    node_t, node_df, a, n = _bond_arrays(node_t, node_df, book)
+    out, status = np.empty((len(BOND_OUTPUTS), n)), np.empty(n, dtype=np.int32)
+    _check(load().adr_bond_measures_host(int(interp_method), node_t.size, _ptr(node_t), _ptr(node_df), n,
+                                         _ptr(a["flow_off"], _i64p), *(_ptr(a[k]) for k in BOND_FLOW_FIELDS + BOND_FIELDS),
+                                         1 if quote_is_z else 0, _ptr(out), _ptr(status, _i32p)), "adr_bond_measures_host")
+    return _bond_result(out, status)
+
+
+def bond_measures_dev(ctx: Context, interp_method: int, n_nodes: int, n_bonds: int, ptrs, quote_is_z: bool, out_ptr: int,
+                      status_ptr: int, stream=0):
+    """Non-blocking form (adr_bond_measures_dev): ``ptrs`` maps ``node_t``, ``node_df``, ``flow_off`` and the fields of
+    BOND_FLOW_FIELDS + BOND_FIELDS to device pointers (integers, e.g. ``tensor.data_ptr()``); ``out_ptr``: float64
+    [len(BOND_OUTPUTS), n_bonds], ``status_ptr``: int32 [n_bonds]."""
+    keys = ("node_t", "node_df", "flow_off") + BOND_FLOW_FIELDS + BOND_FIELDS
+    p = [_vp(int(ptrs[k]) or None) for k in keys]
+    _check(load().adr_bond_measures_dev(ctx._h, int(interp_method), int(n_nodes), p[0], p[1], int(n_bonds), *p[2:],
+                                        1 if quote_is_z else 0, _vp(out_ptr or None), _vp(status_ptr or None),
+                                        _vp(stream or None)), "adr_bond_measures_dev")
 
 
 _default_ctx = {}

@@ -1,0 +1,484 @@
+// Batched spread and yield measures of fixed-rate bonds (adr_bond_measures*; declarations: include/adrates.h).
+//
+// Per bond, the host methods of adrates_amd/trades/credit/bond.py (cavour/trades/credit/bond.py:262-783):
+//   1. z from the target dirty value when a clean price is given (`z_spread`),
+//   2. the price at z and dv01 = cs01 from z -/+ 1bp (`value`, `dv01`, `cs01`),
+//   3. the yield whose yield-PV equals that dirty value (`yield_to_maturity`),
+//   4. Macaulay duration and convexity at that yield (`duration`, `convexity`).
+// Discount factors come from the curve's OWN node set, interpolated like market/curves/interpolator.py::_point
+// (not curve_lookup.hpp's engine interpolation, which snaps knots and treats the ends differently).
+//
+// Layout: kGroup lanes per bond, flows dealt across the lanes (flow i on lane i % kGroup); the first kRegFlows flows of
+// each lane stay in VGPRs across the solver's iterations, later ones (long bonds) are re-derived from global memory on
+// every pass.  Each pass over the flows ends in one fixed-order butterfly over the group's lanes, so every lane holds the
+// same bits and a bond's results do not depend on the launch shape.  The host entry point runs the same per-bond code
+// with the same per-lane order and the same reduction tree.  No atomics.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/adrates.h"
+#include "host_pool.hpp"
+
+int adr_set_error(int status, const std::string& msg);                          // capi.hip
+int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
+
+// The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
+// exp / log implementations.
+#pragma clang fp contract(off)
+
+namespace adr {
+namespace bond {
+
+constexpr int kGroup = 16;                  // lanes per bond
+constexpr int kRegFlows = 8;                // flows per lane held in registers (kGroup * kRegFlows = 128 per bond)
+constexpr int kBlock = 256;
+constexpr int kBondsPerBlock = kBlock / kGroup;
+constexpr int kMaxIter = 100;
+constexpr double kBump = 0.0001;            // 1bp, bond.py dv01 / cs01
+
+enum Kind { Z_NEWTON = 0, Z_PRICES = 1, Y_NEWTON = 2, Y_MOMENTS = 3 };
+
+struct V3 {
+    double a, b, c;
+};
+
+struct Args {
+    int method, n_nodes;
+    const double* node_t;
+    const double* node_df;
+    int64_t n;
+    const int64_t* flow_off;
+    const double* flow_T;
+    const double* flow_tau;
+    const double* flow_cpn;
+    const double* flow_prin;
+    const double* bond_Ts;
+    const double* bond_tauM;
+    const double* bond_face;
+    const double* bond_acc100;
+    const double* bond_quote;
+    int quote_is_z;
+    double* out;                            // [ADR_BOND_OUTPUTS][n]
+    int32_t* status;
+};
+
+// interpolator.py::_point: ``i`` is the first node with x[i] >= t (the reference's linear scan stops at n - 1), n when t
+// lies beyond the last node.  A time before the first node has no formula there; it gives NaN.
+__host__ __device__ inline double node_df(double t, const double* x, const double* d, int n, int method) {
+    if (t == x[0]) return d[0];
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (x[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    int i = lo;
+    if (t > x[i]) i = n;
+    if (i == 0) return NAN;
+    if (method == ADR_INTERP_LINEAR_ZERO_RATES) {
+        double r1, r2, a, b;
+        if (i == 1) {                       // first segment: the first node's zero rate held flat
+            r1 = r2 = -log(d[1]) / x[1];
+            a = x[0]; b = x[1];
+        } else if (i < n) {
+            r1 = -log(d[i - 1]) / x[i - 1];
+            r2 = -log(d[i]) / x[i];
+            a = x[i - 1]; b = x[i];
+        } else {                            // extrapolation: the last node's zero rate held flat
+            r1 = r2 = -log(d[n - 1]) / x[n - 1];
+            a = x[n - 2]; b = x[n - 1];
+        }
+        const double rate = ((b - t) * r1 + (t - a) * r2) / (b - a);
+        return exp(-rate * t);
+    }
+    if (method == ADR_INTERP_FLAT_FWD_RATES) {   // -ln(df) linear; the last segment's slope beyond the last node
+        const int a = i < n ? i - 1 : n - 2, b = i < n ? i : n - 1;
+        const double rt1 = -log(d[a]), rt2 = -log(d[b]);
+        const double rt = ((x[b] - t) * rt1 + (t - x[a]) * rt2) / (x[b] - x[a]);
+        return exp(-rt);
+    }
+    // LINEAR_FWD_RATES: forwards of the segments interpolated; `small` regularises the first segment as the reference does
+    const double small = 1e-10;
+    if (i == 1) return exp(-(t * -log(d[1] + small) / (x[1] + small)));
+    const double fwd1 = -log(d[i - 1] / d[i - 2]) / (x[i - 1] - x[i - 2]);
+    double fwd = fwd1;
+    if (i < n) {
+        const double fwd2 = -log(d[i] / d[i - 1]) / (x[i] - x[i - 1]);
+        fwd = ((x[i] - t) * fwd1 + (t - x[i - 1]) * fwd2) / (x[i] - x[i - 1]);
+    }
+    return d[i - 1] * exp(-fwd * (t - x[i - 1]));
+}
+
+// What one flow adds to a pass.  A = (coupon + principal if > 0) * D(T) / D(T_s) is the flow on the curve (`value`
+// discounts relative to the settlement date); c is the coupon alone (the yield measures price coupons plus the FULL face at
+// the unadjusted maturity, whatever the amortization).
+__host__ __device__ inline V3 term(int kind, double x, double A, double tau, double c) {
+    switch (kind) {
+    case Z_NEWTON: {
+        const double e = A * exp(-x * tau);
+        return {e, -(e * tau), 0.0};
+    }
+    case Z_PRICES:
+        return {A * exp(-x * tau), A * exp(-(x - kBump) * tau), A * exp(-(x + kBump) * tau)};
+    case Y_NEWTON: {
+        const double e = c * exp(-x * tau);
+        return {e, -(e * tau), 0.0};
+    }
+    default: {
+        const double e = c * exp(-x * tau);
+        return {e, e * tau, e * (tau * tau)};
+    }
+    }
+}
+
+__host__ __device__ inline bool finite(double x) { return x - x == 0.0; }    // false for NaN and +-inf
+
+__host__ __device__ inline V3 add(V3 p, V3 q) { return {p.a + q.a, p.b + q.b, p.c + q.c}; }
+
+// The face at the unadjusted maturity, added after the pass (bond.py:488-503, 648-750); tau_M <= 0: matured.
+template <class Group>
+__host__ __device__ inline V3 pass(Group& g, int kind, double x, double face, double tauM) {
+    V3 s = g.sum(kind, x);
+    if (kind >= Y_NEWTON && tauM > 0.0) {
+        const V3 p = term(kind, x, 0.0, tauM, face);
+        s = add(s, p);
+    }
+    return s;
+}
+
+// Root of pass(x).a - target.  The bracket [lo, hi] first (brentq's test: no sign change -> fall back); inside it a
+// safeguarded Newton whose steps are clipped into the shrinking sign-change bracket (bisection when a step leaves it).
+// Without a bracket an unbracketed Newton from x0.  Stop when |step| <= 1e-15 max(1, |x|) or after kMaxIter steps.
+// Returns 0 (bracketed), 1 (fallback converged) or 2 (no root).
+template <class Group>
+__host__ __device__ inline int solve(Group& g, int kind, double face, double tauM, double target, double lo, double hi,
+                                     double x0, double* root) {
+    V3 pa = pass(g, kind, lo, face, tauM), pb = pass(g, kind, hi, face, tauM);
+    double fa = pa.a - target, fb = pb.a - target;
+    if (fa == 0.0) { *root = lo; return 0; }
+    if (fb == 0.0) { *root = hi; return 0; }
+    if (fa * fb < 0.0) {
+        double a = lo, b = hi;
+        double x = a - fa / pa.b;
+        if (!(x > a && x < b)) x = 0.5 * (a + b);
+        for (int it = 0; it < kMaxIter; ++it) {
+            const V3 p = pass(g, kind, x, face, tauM);
+            const double f = p.a - target;
+            if (f == 0.0) break;
+            if ((f < 0.0) == (fa < 0.0)) { a = x; fa = f; } else { b = x; }
+            double xn = x - f / p.b;
+            if (!(xn > fmin(a, b) && xn < fmax(a, b))) xn = 0.5 * (a + b);
+            const double step = xn - x;
+            x = xn;
+            if (fabs(step) <= 1e-15 * fmax(1.0, fabs(x))) break;
+        }
+        *root = x;
+        return 0;
+    }
+    double x = x0;
+    for (int it = 0; it < kMaxIter; ++it) {
+        const V3 p = pass(g, kind, x, face, tauM);
+        const double f = p.a - target;
+        if (!finite(f) || !finite(p.b)) break;
+        if (f == 0.0) { *root = x; return 1; }
+        if (p.b == 0.0) break;
+        const double xn = x - f / p.b;
+        if (!finite(xn)) break;
+        const double step = xn - x;
+        x = xn;
+        if (fabs(step) <= 1e-15 * fmax(1.0, fabs(x))) { *root = x; return 1; }
+    }
+    *root = NAN;
+    return 2;
+}
+
+struct Result {
+    double v[ADR_BOND_OUTPUTS];
+    int32_t status;
+};
+
+template <class Group>
+__host__ __device__ inline Result measures(Group& g, double face, double tauM, double acc100, double quote, int quote_is_z) {
+    Result r;
+    double z = quote;
+    int sz = 0;
+    if (!quote_is_z) {
+        const double target = ((quote + acc100) / 100.0) * face;
+        sz = solve(g, Z_NEWTON, face, tauM, target, -0.1, 0.5, 0.01, &z);
+    }
+    if (sz == 2) {
+        for (int k = 0; k < ADR_BOND_OUTPUTS; ++k) r.v[k] = NAN;
+        r.status = 2;
+        return r;
+    }
+    const V3 p = pass(g, Z_PRICES, z, face, tauM);
+    const double dirty = (p.a / face) * 100.0;
+    const double clean = dirty - acc100;
+    r.v[ADR_BOND_Z] = z;
+    r.v[ADR_BOND_DIRTY] = dirty;
+    r.v[ADR_BOND_CLEAN] = clean;
+    r.v[ADR_BOND_DV01] = (p.b - p.c) / 2.0;
+    double y = NAN;
+    const int sy = solve(g, Y_NEWTON, face, tauM, ((clean + acc100) / 100.0) * face, -0.5, 0.5, 0.05, &y);
+    r.v[ADR_BOND_YTM] = y;
+    r.v[ADR_BOND_DURATION] = r.v[ADR_BOND_CONVEXITY] = NAN;
+    if (sy != 2) {
+        const V3 m = pass(g, Y_MOMENTS, y, face, tauM);
+        r.v[ADR_BOND_DURATION] = m.b / m.a;
+        r.v[ADR_BOND_CONVEXITY] = m.c / m.a;
+    }
+    r.status = sz > sy ? sz : sy;
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------------------ device
+struct DeviceGroup {
+    const Args* a;
+    const double* st;
+    const double* sd;
+    int lane;
+    int64_t f0;
+    int nf;
+    double Ds;
+    double A[kRegFlows], tau[kRegFlows], c[kRegFlows];
+
+    __device__ void flow(int64_t i, double& Ai, double& ti, double& ci) const {
+        const double T = a->flow_T[i], p = a->flow_prin[i];
+        ci = a->flow_cpn[i];
+        ti = a->flow_tau[i];
+        Ai = (ci + (p > 0.0 ? p : 0.0)) * (node_df(T, st, sd, a->n_nodes, a->method) / Ds);
+    }
+
+    __device__ void load() {
+#pragma unroll
+        for (int k = 0; k < kRegFlows; ++k) {
+            const int i = lane + k * kGroup;
+            A[k] = tau[k] = c[k] = 0.0;
+            if (i < nf) flow(f0 + i, A[k], tau[k], c[k]);
+        }
+    }
+
+    __device__ V3 sum(int kind, double x) const {
+        V3 s = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < kRegFlows; ++k)
+            if (lane + k * kGroup < nf) s = add(s, term(kind, x, A[k], tau[k], c[k]));
+        for (int i = lane + kRegFlows * kGroup; i < nf; i += kGroup) {
+            double Ai, ti, ci;
+            flow(f0 + i, Ai, ti, ci);
+            s = add(s, term(kind, x, Ai, ti, ci));
+        }
+#pragma unroll
+        for (int m = kGroup / 2; m >= 1; m >>= 1) {
+            s.a = s.a + __shfl_xor(s.a, m);
+            s.b = s.b + __shfl_xor(s.b, m);
+            s.c = s.c + __shfl_xor(s.c, m);
+        }
+        return s;
+    }
+};
+
+__global__ __launch_bounds__(kBlock) void bond_measures_kernel(Args a) {
+    __shared__ double s_t[ADR_BOND_MAX_NODES], s_d[ADR_BOND_MAX_NODES];
+    for (int k = threadIdx.x; k < a.n_nodes; k += kBlock) {
+        s_t[k] = a.node_t[k];
+        s_d[k] = a.node_df[k];
+    }
+    __syncthreads();
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * kBondsPerBlock + threadIdx.x / kGroup;
+    if (b >= a.n) return;
+    const int lane = threadIdx.x % kGroup;
+    const int64_t f0 = a.flow_off[b], f1 = a.flow_off[b + 1];
+    Result r;
+    if (f1 < f0 || f1 - f0 > (int64_t(1) << 30)) {          // malformed offsets: no reads, NaN and status 2
+        for (int k = 0; k < ADR_BOND_OUTPUTS; ++k) r.v[k] = NAN;
+        r.status = 2;
+    } else {
+        DeviceGroup g;
+        g.a = &a; g.st = s_t; g.sd = s_d; g.lane = lane; g.f0 = f0; g.nf = static_cast<int>(f1 - f0);
+        g.Ds = node_df(a.bond_Ts[b], s_t, s_d, a.n_nodes, a.method);
+        g.load();
+        r = measures(g, a.bond_face[b], a.bond_tauM[b], a.bond_acc100[b], a.bond_quote[b], a.quote_is_z);
+    }
+    // lanes 0 .. 6 store one output each, lane 7 the status
+    for (int k = 0; k < ADR_BOND_OUTPUTS; ++k)
+        if (lane == k) a.out[static_cast<int64_t>(k) * a.n + b] = r.v[k];
+    if (lane == ADR_BOND_OUTPUTS) a.status[b] = r.status;
+}
+
+// -------------------------------------------------------------------------------------------------------------- host
+// The device's lanes in sequence: lane l sums flows l, l + kGroup, ... in order, then the butterfly's tree (lane 0's view).
+struct HostGroup {
+    const double* A;
+    const double* tau;
+    const double* c;
+    int nf;
+
+    V3 sum(int kind, double x) const {
+        V3 p[kGroup];
+        for (int l = 0; l < kGroup; ++l) {
+            p[l] = {0.0, 0.0, 0.0};
+            for (int i = l; i < nf; i += kGroup) p[l] = add(p[l], term(kind, x, A[i], tau[i], c[i]));
+        }
+        for (int m = kGroup / 2; m >= 1; m >>= 1)
+            for (int l = 0; l < m; ++l) p[l] = add(p[l], p[l + m]);
+        return p[0];
+    }
+};
+
+int validate(const char* who, int method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
+             const void* off, const void* T, const void* tau, const void* cpn, const void* prin, const void* Ts,
+             const void* tauM, const void* face, const void* acc, const void* quote, const void* out, const void* status) {
+    const std::string w(who);
+    if (method != ADR_INTERP_FLAT_FWD_RATES && method != ADR_INTERP_LINEAR_FWD_RATES && method != ADR_INTERP_LINEAR_ZERO_RATES)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and LINEAR_ZERO_RATES (4)");
+    if (n_nodes < 2 || n_nodes > ADR_BOND_MAX_NODES)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": the curve needs 2 .. ADR_BOND_MAX_NODES (1024) nodes");
+    if (!node_t || !node_df) return adr_set_error(ADR_ERR_INVALID, w + ": null node arrays");
+    if (n < 0 || (n > 0 && (!off || !Ts || !tauM || !face || !acc || !quote || !out || !status)))
+        return adr_set_error(ADR_ERR_INVALID, w + ": bad count / null array");
+    (void)T; (void)tau; (void)cpn; (void)prin;
+    return ADR_OK;
+}
+
+int check_host_arrays(const char* who, int n_nodes, const double* node_t, int64_t n, const int64_t* off, const double* T,
+                      const double* tau, const double* cpn, const double* prin, const double* Ts) {
+    const std::string w(who);
+    for (int k = 0; k < n_nodes; ++k)
+        if (!std::isfinite(node_t[k]) || (k > 0 && !(node_t[k] > node_t[k - 1])))
+            return adr_set_error(ADR_ERR_INVALID, w + ": node times must be finite and increasing");
+    if (n == 0) return ADR_OK;
+    if (off[0] != 0) return adr_set_error(ADR_ERR_INVALID, w + ": flow_off[0] must be 0");
+    for (int64_t b = 0; b < n; ++b)
+        if (off[b + 1] < off[b] || off[b + 1] - off[b] > (int64_t(1) << 30))
+            return adr_set_error(ADR_ERR_INVALID, w + ": flow offsets must be non-decreasing");
+    const int64_t m = off[n];
+    if (m > 0 && (!T || !tau || !cpn || !prin)) return adr_set_error(ADR_ERR_INVALID, w + ": null flow arrays");
+    for (int64_t i = 0; i < m; ++i)
+        if (!(T[i] >= node_t[0]) || !std::isfinite(T[i]) || !std::isfinite(tau[i]) || !std::isfinite(cpn[i]) ||
+            !std::isfinite(prin[i]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": flow times must be finite and not before the curve's first node");
+    for (int64_t b = 0; b < n; ++b)
+        if (!(Ts[b] >= node_t[0]) || !std::isfinite(Ts[b]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": settlement times must be finite and not before the curve's first node");
+    return ADR_OK;
+}
+
+}  // namespace bond
+}  // namespace adr
+
+namespace B = adr::bond;
+
+extern "C" {
+
+int adr_bond_measures_dev(adr_ctx* ctx, int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
+                          const int64_t* flow_off, const double* flow_T, const double* flow_tau, const double* flow_cpn,
+                          const double* flow_prin, const double* bond_Ts, const double* bond_tauM, const double* bond_face,
+                          const double* bond_acc100, const double* bond_quote, int quote_is_z, double* out, int32_t* status,
+                          void* stream_v) {
+    int rc = B::validate("adr_bond_measures_dev", interp_method, n_nodes, node_t, node_df, n, flow_off, flow_T, flow_tau,
+                         flow_cpn, flow_prin, bond_Ts, bond_tauM, bond_face, bond_acc100, bond_quote, out, status);
+    if (rc != ADR_OK) return rc;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    rc = adr_ctx_target(ctx, &device, &stream);
+    if (rc != ADR_OK) return rc;
+    if (n == 0) return ADR_OK;
+    if (stream_v) stream = static_cast<hipStream_t>(stream_v);
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures_dev: ") + hipGetErrorString(e));
+    B::Args a{interp_method, n_nodes, node_t, node_df, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin, bond_Ts, bond_tauM,
+              bond_face, bond_acc100, bond_quote, quote_is_z ? 1 : 0, out, status};
+    const int64_t blocks = (n + B::kBondsPerBlock - 1) / B::kBondsPerBlock;
+    if (blocks > 0x7fffffff) return adr_set_error(ADR_ERR_UNSUPPORTED, "adr_bond_measures_dev: too many bonds for one launch");
+    hipLaunchKernelGGL(B::bond_measures_kernel, dim3(static_cast<unsigned>(blocks)), dim3(B::kBlock), 0, stream, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures_dev: ") + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+int adr_bond_measures(adr_ctx* ctx, int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
+                      const int64_t* flow_off, const double* flow_T, const double* flow_tau, const double* flow_cpn,
+                      const double* flow_prin, const double* bond_Ts, const double* bond_tauM, const double* bond_face,
+                      const double* bond_acc100, const double* bond_quote, int quote_is_z, double* out, int32_t* status) {
+    const char* who = "adr_bond_measures";
+    int rc = B::validate(who, interp_method, n_nodes, node_t, node_df, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin,
+                         bond_Ts, bond_tauM, bond_face, bond_acc100, bond_quote, out, status);
+    if (rc == ADR_OK) rc = B::check_host_arrays(who, n_nodes, node_t, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin, bond_Ts);
+    if (rc != ADR_OK) return rc;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    rc = adr_ctx_target(ctx, &device, &stream);
+    if (rc != ADR_OK || n == 0) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures: ") + hipGetErrorString(e));
+    const int64_t m = flow_off[n];
+    const size_t d = sizeof(double);
+    // one allocation: nodes, flows, bonds, outputs, then the offsets and the status words
+    const size_t n_dbl = 2 * static_cast<size_t>(n_nodes) + 4 * static_cast<size_t>(m) + 5 * static_cast<size_t>(n) +
+                         ADR_BOND_OUTPUTS * static_cast<size_t>(n);
+    const size_t bytes = n_dbl * d + static_cast<size_t>(n + 1) * sizeof(int64_t) + static_cast<size_t>(n) * sizeof(int32_t);
+    char* base = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures: hipMalloc: ") + hipGetErrorString(e));
+    double* p = reinterpret_cast<double*>(base);
+    struct Piece { const void* src; size_t bytes; };
+    double *dt = p, *dd = dt + n_nodes, *dT = dd + n_nodes, *dtau = dT + m, *dcpn = dtau + m, *dprin = dcpn + m;
+    double *dTs = dprin + m, *dtauM = dTs + n, *dface = dtauM + n, *dacc = dface + n, *dquote = dacc + n, *dout = dquote + n;
+    int64_t* doff = reinterpret_cast<int64_t*>(dout + ADR_BOND_OUTPUTS * n);
+    int32_t* dstatus = reinterpret_cast<int32_t*>(doff + n + 1);
+    const Piece pieces[] = {{node_t, n_nodes * d}, {node_df, n_nodes * d}, {flow_T, m * d}, {flow_tau, m * d},
+                            {flow_cpn, m * d},     {flow_prin, m * d},     {bond_Ts, n * d}, {bond_tauM, n * d},
+                            {bond_face, n * d},    {bond_acc100, n * d},   {bond_quote, n * d}};
+    char* dst = base;
+    for (const Piece& pc : pieces) {
+        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
+        dst += pc.bytes;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(doff, flow_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess)
+        rc = adr_bond_measures_dev(ctx, interp_method, n_nodes, dt, dd, n, doff, dT, dtau, dcpn, dprin, dTs, dtauM, dface, dacc,
+                                   dquote, quote_is_z, dout, dstatus, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, ADR_BOND_OUTPUTS * n * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(status, dstatus, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipStreamSynchronize(stream);
+    hipFree(base);
+    if (rc != ADR_OK) return rc;
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures: ") + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+int adr_bond_measures_host(int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
+                           const int64_t* flow_off, const double* flow_T, const double* flow_tau, const double* flow_cpn,
+                           const double* flow_prin, const double* bond_Ts, const double* bond_tauM, const double* bond_face,
+                           const double* bond_acc100, const double* bond_quote, int quote_is_z, double* out, int32_t* status) {
+    const char* who = "adr_bond_measures_host";
+    int rc = B::validate(who, interp_method, n_nodes, node_t, node_df, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin,
+                         bond_Ts, bond_tauM, bond_face, bond_acc100, bond_quote, out, status);
+    if (rc == ADR_OK) rc = B::check_host_arrays(who, n_nodes, node_t, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin, bond_Ts);
+    if (rc != ADR_OK || n == 0) return rc;
+    adr::parallel_ranges(n, adr::pool_threads(n, 256), [&](int, int64_t lo, int64_t hi) {
+        std::vector<double> A;
+        for (int64_t b = lo; b < hi; ++b) {
+            const int64_t f0 = flow_off[b];
+            const int nf = static_cast<int>(flow_off[b + 1] - f0);
+            const double Ds = B::node_df(bond_Ts[b], node_t, node_df, n_nodes, interp_method);
+            A.resize(static_cast<size_t>(nf));
+            for (int i = 0; i < nf; ++i) {
+                const double p = flow_prin[f0 + i];
+                A[i] = (flow_cpn[f0 + i] + (p > 0.0 ? p : 0.0)) *
+                       (B::node_df(flow_T[f0 + i], node_t, node_df, n_nodes, interp_method) / Ds);
+            }
+            B::HostGroup g{A.data(), flow_tau + f0, flow_cpn + f0, nf};
+            const B::Result r = B::measures(g, bond_face[b], bond_tauM[b], bond_acc100[b], bond_quote[b], quote_is_z ? 1 : 0);
+            for (int k = 0; k < ADR_BOND_OUTPUTS; ++k) out[static_cast<int64_t>(k) * n + b] = r.v[k];
+            status[b] = r.status;
+        }
+    });
+    return ADR_OK;
+}
+
+}  // extern "C"

@@ -10,7 +10,7 @@ from typing import Iterable, List
 
 from ...requests.results import AnalyticsResult
 from ...utils.global_types import InstrumentTypes, RequestTypes
-from ..position.engine import Engine, price_batch, wrap_result
+from ..position.engine import Engine, bond_curve_type, is_bond, price_batch, price_bonds, wrap_result
 from ..position.position import Position
 
 
@@ -27,14 +27,19 @@ class Portfolio:
     def compute(self, request_list: Iterable[RequestTypes]) -> AnalyticsResult:
         """Aggregate VALUE / DELTA / GAMMA over all positions."""
         reqs = set(request_list)
-        groups = {}   # (model id, curve name, currency) -> positions, in first-seen order
-        singles = []  # everything that is not an OIS: priced one by one and added with `+`, as the reference does
+        groups = {}   # (model id, curve, currency, OIS_SWAP or BOND) -> positions, in first-seen order
+        singles = []  # everything that is not an OIS or a bond: priced one by one and added with `+`, as the reference does
         for pos in self._positions:
             d = pos.derivative
+            if d.derivative_type == InstrumentTypes.BOND and is_bond(d):
+                # bonds of one model and currency: one fixed-flows-only launch on that currency's OIS curve
+                key = (id(pos.model), bond_curve_type(d), d._currency, InstrumentTypes.BOND)
+                groups.setdefault(key, []).append(pos)
+                continue
             if d.derivative_type != InstrumentTypes.OIS_SWAP:
                 singles.append(pos)
                 continue
-            key = (id(pos.model), d._floating_index, d._currency)
+            key = (id(pos.model), d._floating_index, d._currency, InstrumentTypes.OIS_SWAP)
             groups.setdefault(key, []).append(pos)
 
         total_val = total_delta = total_gamma = None
@@ -49,12 +54,12 @@ class Portfolio:
                 total_delta = res.risk if total_delta is None else total_delta + res.risk
             if RequestTypes.GAMMA in reqs:
                 total_gamma = res.gamma if total_gamma is None else total_gamma + res.gamma
-        for (_, curve_type, currency), members in groups.items():
+        for (_, curve_type, currency, kind), members in groups.items():
             model = members[0].model
             ir_model = getattr(model.curves, curve_type.name)
             engine = members[0]._engine
-            res = price_batch(engine, ir_model, [p.derivative for p in members], reqs,
-                              per_trade=False, aggregate=True)
+            pricer = price_bonds if kind == InstrumentTypes.BOND else price_batch
+            res = pricer(engine, ir_model, [p.derivative for p in members], reqs, per_trade=False, aggregate=True)
             part = wrap_result(res, 0, reqs, res["tenors"], currency, curve_type, aggregate=True)
             if RequestTypes.VALUE in reqs:
                 total_val = part.value if total_val is None else total_val + part.value

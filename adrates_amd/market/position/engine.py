@@ -22,13 +22,31 @@ import numpy as np
 
 from ... import _native
 from ...requests.results import AnalyticsResult, CashflowItem, Cashflows, Delta, Gamma, Valuation
-from ...trades.compiler import compile_ois
+from ...trades.compiler import compile_bonds, compile_ois
 from ...utils.error import LibError
-from ...utils.global_types import InstrumentTypes, InterpTypes, RequestTypes, SwapTypes, collateral_to_currency
+from ...utils.currency import CurrencyTypes
+from ...utils.global_types import (CurveTypes, InstrumentTypes, InterpTypes, RequestTypes, SwapTypes,
+                                   collateral_to_currency)
 from ...utils.helpers import to_tenor
 from ..curves.curve_tables import build_engine_curve
 
 _SUPPORTED_INTERP = (InterpTypes.FLAT_FWD_RATES.value, InterpTypes.LINEAR_FWD_RATES.value, InterpTypes.LINEAR_ZERO_RATES.value)
+
+# the OIS curve a bond discounts on, by currency (engine.py:517-525)
+BOND_CURVES = {CurrencyTypes.GBP: CurveTypes.GBP_OIS_SONIA, CurrencyTypes.USD: CurveTypes.USD_OIS_SOFR,
+               CurrencyTypes.EUR: CurveTypes.EUR_OIS_ESTR}
+
+
+def bond_curve_type(bond):
+    curve_type = BOND_CURVES.get(bond._currency)
+    if curve_type is None:
+        raise LibError(f"No default OIS curve for currency {bond._currency}")
+    return curve_type
+
+
+def is_bond(derivative) -> bool:
+    from ...trades.credit.bond import Bond
+    return isinstance(derivative, Bond)
 
 
 class Engine:
@@ -74,6 +92,8 @@ class Engine:
         if dtype == InstrumentTypes.XCCY_SWAP:
             from .xccy_engine import compute_xccy
             return compute_xccy(self, derivative, reqs)
+        if dtype == InstrumentTypes.BOND and is_bond(derivative):
+            return self._compute_bond(derivative, reqs)
         raise LibError(f"{dtype} not yet implemented")
 
     def _compute_ois(self, derivative, reqs, collateral_type=None):
@@ -95,6 +115,43 @@ class Engine:
             out = AnalyticsResult(value=out.value, risk=out.risk, gamma=out.gamma,
                                   cashflows=self._ois_cashflows(derivative, ir_model))
         return out
+
+    def _compute_bond(self, bond, reqs):
+        """A bond's curve Greeks (engine.py:505-698): its coupons and the face on the last flow, sign +1, priced as a
+        fixed-flows-only trade on its currency's OIS curve."""
+        curve_type = bond_curve_type(bond)
+        ir_model = getattr(self.model.curves, curve_type.name)
+        out = AnalyticsResult()
+        if reqs & {RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}:
+            res = price_bonds(self, ir_model, [bond], reqs, per_trade=True, aggregate=False)
+            out = wrap_result(res, 0, reqs, ir_model_tenors=res["tenors"], currency=bond._currency, curve_type=curve_type)
+        if RequestTypes.CASHFLOWS in reqs:
+            out = AnalyticsResult(value=out.value, risk=out.risk, gamma=out.gamma,
+                                  cashflows=self._bond_cashflows(bond, ir_model))
+        return out
+
+    @staticmethod
+    def _bond_cashflows(bond, ir_model):
+        """Coupon and principal items (engine.py:652-697), from `Bond.value` on the curve's own nodes at its value
+        date."""
+        bond.value(ir_model._value_dt, ir_model)
+        items = []
+        for i, pay_dt in enumerate(bond._payment_dts):
+            coupon = bond._coupon_payments[i]
+            principal = bond._principal_payments[i]
+            if abs(coupon) > 1e-10:
+                notional = bond._principal_schedule[i]
+                items.append(CashflowItem(payment_date=pay_dt, notional=notional,
+                                          payment_fraction=coupon / notional if notional != 0 else 0.0,
+                                          accrual_period=float(bond._year_fracs[i]), amount=float(coupon),
+                                          discount_factor=float(bond._payment_dfs[i]),
+                                          discounted_amount=float(bond._coupon_pvs[i]), leg_type="Coupon"))
+            if abs(principal) > 1e-10:
+                items.append(CashflowItem(payment_date=pay_dt, notional=principal, payment_fraction=1.0,
+                                          accrual_period=0.0, amount=float(principal),
+                                          discount_factor=float(bond._payment_dfs[i]),
+                                          discounted_amount=float(bond._principal_pvs[i]), leg_type="Principal"))
+        return Cashflows(items, bond._currency)
 
     # --------------------------------------------------------------- cash flows
     @staticmethod
@@ -132,6 +189,22 @@ def price_batch(engine: Engine, ir_model, derivatives, reqs, per_trade=True, agg
     cur = engine._device_curve(ir_model)
     batch = compile_ois(derivatives, ir_model._value_dt)
     dev_trades = _native.DeviceTrades(cur["ctx"], batch)
+    try:
+        out = _native.price(cur["ctx"], cur["dev"], dev_trades,
+                            want_value=RequestTypes.VALUE in reqs,
+                            want_delta=RequestTypes.DELTA in reqs,
+                            want_gamma=RequestTypes.GAMMA in reqs,
+                            per_trade=per_trade, aggregate=aggregate)
+    finally:
+        dev_trades.close()
+    out["tenors"] = cur["tenors"]
+    return out
+
+
+def price_bonds(engine: Engine, ir_model, bonds, reqs, per_trade=True, aggregate=False):
+    """Compile, upload and price bonds on ``ir_model``'s curve through the OIS route (fixed flows only)."""
+    cur = engine._device_curve(ir_model)
+    dev_trades = _native.DeviceTrades(cur["ctx"], compile_bonds(bonds, ir_model._value_dt))
     try:
         out = _native.price(cur["ctx"], cur["dev"], dev_trades,
                             want_value=RequestTypes.VALUE in reqs,

@@ -84,6 +84,30 @@ def compile_ois(swaps: Iterable, value_dt) -> TradeBatch:
                       f64(notional), f64(spread), f64(fix_sign), f64(flt_sign))
 
 
+def compile_bonds(bonds: Iterable, value_dt) -> TradeBatch:
+    """Fixed-flows-only batch of bonds: the reference prices a bond's curve Greeks as `_price_fixed_leg_jax`
+    with ``principal = face`` (cavour/market/position/engine.py:505-560, 2414-2448).  Times are year fractions
+    from ``value_dt`` in the bond's day count; the face is folded into the LAST flow's amount, which is the one
+    flow the reference pays it on (under the same ``time > value time`` mask) - also for amortizing bonds, whose
+    repayment schedule the engine ignores.  No float coupons; ``notional`` is the face."""
+    fix_off = [0]
+    fix_tp, fix_pay, notional = [], [], []
+    for b in bonds:
+        if getattr(b, "derivative_type", None) != InstrumentTypes.BOND:
+            raise LibError(f"{getattr(b, 'derivative_type', type(b))} is not a bond")
+        pays = [float(c) for c in b._coupon_payments]
+        pays[-1] += float(b._face_value)
+        fix_tp += _times(b._payment_dts, value_dt, b._dc_type)
+        fix_pay += pays
+        fix_off.append(len(fix_tp))
+        notional.append(float(b._face_value))
+    n = len(notional)
+    f64 = lambda a: np.array(a, dtype=np.float64)
+    empty = np.zeros(0, dtype=np.float64)
+    return TradeBatch(np.array(fix_off, dtype=np.int64), np.zeros(n + 1, dtype=np.int64), f64(fix_tp), f64(fix_pay),
+                      empty, empty.copy(), empty.copy(), empty.copy(), f64(notional), np.zeros(n), np.ones(n), np.ones(n))
+
+
 # --------------------------------------------------------------------------------------------------------
 # Vectorised path: trades given by their economic terms, no per-trade objects
 # (SURVEY.md section 8(f) row 4).  Every Python `Date` / `Schedule` / `DayCount` call of the object path

@@ -61,3 +61,32 @@ def make_swap(effective_dt, tenor, coupon, notional=1e6, pay=True, dc=DayCountTy
                notional=notional, payment_lag=payment_lag, float_spread=spread,
                bd_type=BusDayAdjustTypes.MODIFIED_FOLLOWING, float_freq_type=float_freq,
                float_dc_type=float_dc or dc)
+
+
+def random_bond_book(value_dt, n, seed=7, currency=CurrencyTypes.GBP):
+    """``n`` fixed-rate bonds: bullet, zero-coupon (10%) and equal-principal amortizers (20% of the coupon bonds), issued
+    up to five years before ``value_dt`` on 1Y-30Y tenors, with payment lags of 0-2 days and none maturing within a month;
+    and a z-spread per bond between -2% and 6%."""
+    import numpy as np
+    from .credit.bond import Bond
+    tenors = ["1Y", "2Y", "3Y", "5Y", "7Y", "10Y", "15Y", "20Y", "30Y"]
+    freqs = [FrequencyTypes.ANNUAL, FrequencyTypes.SEMI_ANNUAL, FrequencyTypes.QUARTERLY]
+    dcs = [DayCountTypes.ACT_365F, DayCountTypes.ACT_360, DayCountTypes.THIRTY_360_BOND]
+    rng = np.random.default_rng(seed)
+    bonds = []
+    while len(bonds) < n:
+        issue = value_dt.add_days(-int(rng.integers(0, 5 * 365)))
+        tenor, freq, dc = (tenors[int(rng.integers(len(tenors)))], freqs[int(rng.integers(len(freqs)))],
+                           dcs[int(rng.integers(len(dcs)))])
+        kind = rng.random()
+        coupon = 0.0 if kind < 0.1 else round(float(rng.uniform(0.005, 0.08)), 4)
+        face = float(rng.choice([100.0, 1000.0, 1e6]))
+        lag = int(rng.integers(0, 3))
+        b = Bond(issue, tenor, coupon, freq, dc, currency, face_value=face, payment_lag=lag)
+        if b._payment_dts[-1] <= value_dt.add_days(30):
+            continue
+        if kind > 0.8 and coupon > 0.0:
+            b = Bond(issue, tenor, coupon, freq, dc, currency, face_value=face, payment_lag=lag,
+                     amortization_schedule=Bond.generate_equal_principal_schedule(face, b._num_coupons))
+        bonds.append(b)
+    return bonds, rng.uniform(-0.02, 0.06, size=n)

@@ -346,6 +346,48 @@ int adr_route_host(int interp_method, int K, int P, const double* times, const d
 int adr_curve_df(adr_ctx* ctx, const adr_curve* curve, int64_t n, const double* t, double* df);
 int adr_curve_df_dev(adr_ctx* ctx, const adr_curve* curve, int64_t n, const double* t_dev, double* df_dev, void* stream);
 
+/*
+ * Spread and yield measures of fixed-rate bonds, one root-find pair per bond (cavour/trades/credit/bond.py:262-783, the
+ * host methods of adrates_amd/trades/credit/bond.py).  Discount factors come from the curve's OWN nodes (node_t ascending,
+ * node_df; interpolator.py::_point), not from an uploaded engine curve.
+ *
+ * Flows (CSR over bonds, flow_off [n + 1]; only flows paid after settlement): flow_T the curve time of the payment date
+ * (ACT/ACT ISDA from the curve's value date, as DiscountCurve.df), flow_tau = (payment - settlement) days / 365.25, the
+ * coupon and the principal amount (a principal <= 0 is not paid, as in Bond.value).  Per bond: bond_Ts the curve time of
+ * settlement, bond_tauM = (unadjusted maturity - settlement) / 365.25 (<= 0: matured; the yield measures price the FULL
+ * face there, ignoring amortization), the face, the accrued interest per 100 face, and the quote: a clean price per 100
+ * (quote_is_z = 0; z is solved) or a z-spread (quote_is_z = 1).
+ *
+ * out [ADR_BOND_OUTPUTS][n], row k = ADR_BOND_* below.  status [n]: 0 = the bracket ([-0.1, 0.5] for z, [-0.5, 0.5] for
+ * the yield) held a sign change and a bracketed safeguarded Newton solved it; 1 = no sign change and the unbracketed Newton
+ * fallback (from 0.01 / 0.05) converged; 2 = no root: the outputs depending on it are NaN.  Duration is Macaulay; dv01 is
+ * the central 1bp difference in z, which is also cs01.  Results are bit-identical from run to run and do not depend on
+ * the launch shape; adr_bond_measures_host runs the same per-bond code and reduction order on the CPU (no GPU needed).
+ */
+#define ADR_BOND_OUTPUTS 7
+#define ADR_BOND_Z 0
+#define ADR_BOND_DIRTY 1
+#define ADR_BOND_CLEAN 2
+#define ADR_BOND_YTM 3
+#define ADR_BOND_DURATION 4
+#define ADR_BOND_CONVEXITY 5
+#define ADR_BOND_DV01 6
+#define ADR_BOND_MAX_NODES 1024
+int adr_bond_measures(adr_ctx* ctx, int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
+                      const int64_t* flow_off, const double* flow_T, const double* flow_tau, const double* flow_cpn,
+                      const double* flow_prin, const double* bond_Ts, const double* bond_tauM, const double* bond_face,
+                      const double* bond_acc100, const double* bond_quote, int quote_is_z, double* out, int32_t* status);
+/* The same with every array in device memory, enqueued on `stream` (NULL: the ctx's stream); only the scalars are checked. */
+int adr_bond_measures_dev(adr_ctx* ctx, int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
+                          const int64_t* flow_off, const double* flow_T, const double* flow_tau, const double* flow_cpn,
+                          const double* flow_prin, const double* bond_Ts, const double* bond_tauM, const double* bond_face,
+                          const double* bond_acc100, const double* bond_quote, int quote_is_z, double* out, int32_t* status,
+                          void* stream);
+int adr_bond_measures_host(int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
+                           const int64_t* flow_off, const double* flow_T, const double* flow_tau, const double* flow_cpn,
+                           const double* flow_prin, const double* bond_Ts, const double* bond_tauM, const double* bond_face,
+                           const double* bond_acc100, const double* bond_quote, int quote_is_z, double* out, int32_t* status);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
