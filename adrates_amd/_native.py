@@ -79,6 +79,12 @@ _SIGNATURES = {
                                         _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "adr_bond_measures_host": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.c_int64, _i64p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                          _dp, C.c_int, _dp, _i32p]),
+    "adr_frn_measures": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int64, _i64p,
+                                   _dp, _dp, C.c_int, _dp, _i32p]),
+    "adr_frn_measures_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int64, C.c_int64, _vp,
+                                       _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "adr_frn_measures_host": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int64, _i64p,
+                                        _dp, _dp, C.c_int, _dp, _i32p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -560,6 +566,83 @@ def bond_measures_dev(ctx: Context, interp_method: int, n_nodes: int, n_bonds: i
     _check(load().adr_bond_measures_dev(ctx._h, int(interp_method), int(n_nodes), p[0], p[1], int(n_bonds), *p[2:],
                                         1 if quote_is_z else 0, _vp(out_ptr or None), _vp(status_ptr or None),
                                         _vp(stream or None)), "adr_bond_measures_dev")
+
+
+FRN_OUTPUTS = ("dm", "dirty", "clean", "pv", "mod_duration", "dv01")          # rows of adr_frn_measures' out
+FRN_FLOW_FIELDS = ("cpn_T", "cpn_ts", "cpn_te", "cpn_ialpha", "cpn_alpha", "cpn_tau", "cpn_fix")   # rows of its cpn
+FRN_FIELDS = ("frn_Ts", "frn_TM", "frn_tauM", "frn_face", "frn_margin", "frn_cap", "frn_floor", "frn_ffr", "frn_acc100",
+              "frn_quote", "frn_guess")                                        # rows of its frn
+
+
+def _frn_nodes(curve):
+    method, node_t, node_df = curve
+    node_t, node_df = _f64(node_t), _f64(node_df)
+    if node_t.ndim != 1 or node_t.shape != node_df.shape:
+        raise LibError("node_t and node_df must be 1-D arrays of one length")
+    return int(method), node_t, node_df
+
+
+def frn_pack(book):
+    """``(cpn_off, cpn [len(FRN_FLOW_FIELDS), m], frn [len(FRN_FIELDS), n])``: the field-major arrays adr_frn_measures
+    reads, from a mapping with ``cpn_off`` and the fields FRN_FLOW_FIELDS + FRN_FIELDS."""
+    off = np.ascontiguousarray(book["cpn_off"], dtype=np.int64)
+    n = off.shape[0] - 1
+    if n < 0:
+        raise LibError("cpn_off needs n_frns + 1 entries")
+    m = int(off[-1]) if n > 0 else 0
+    cpn = np.empty((len(FRN_FLOW_FIELDS), m))
+    frn = np.empty((len(FRN_FIELDS), n))
+    for rows, fields, size in ((cpn, FRN_FLOW_FIELDS, m), (frn, FRN_FIELDS, n)):
+        for k, name in enumerate(fields):
+            v = np.asarray(book[name], dtype=np.float64).reshape(-1)
+            if v.shape != (size,):
+                raise LibError(f"FRN array {name} has {v.size} entries, not {size}")
+            rows[k] = v
+    return off, cpn, frn
+
+
+def _frn_result(out, status):
+    res = {k: out[i] for i, k in enumerate(FRN_OUTPUTS)}
+    res["status"] = status
+    return res
+
+
+def frn_measures(ctx: Context, disc, index, book, quote_is_dm: bool):
+    """Discount margins and prices of an FRN book on the GPU (adr_frn_measures, blocking).  ``disc`` / ``index``:
+    ``(interp method, node times, node dfs)`` of the two curves; ``book``: a mapping with ``cpn_off`` and the fields
+    FRN_FLOW_FIELDS + FRN_FIELDS.  Returns a dict of arrays, keys FRN_OUTPUTS + ``status``."""
+    (dm, dt, dd), (im, it, idf) = _frn_nodes(disc), _frn_nodes(index)
+    off, cpn, frn = frn_pack(book)
+    n, m = frn.shape[1], cpn.shape[1]
+    out, status = np.empty((len(FRN_OUTPUTS), n)), np.empty(n, dtype=np.int32)
+    _check(load().adr_frn_measures(ctx._h, dm, dt.size, _ptr(dt), _ptr(dd), im, it.size, _ptr(it), _ptr(idf), n, m,
+                                   _ptr(off, _i64p), _ptr(cpn), _ptr(frn), 1 if quote_is_dm else 0, _ptr(out),
+                                   _ptr(status, _i32p)), "adr_frn_measures")
+    return _frn_result(out, status)
+
+
+def frn_measures_host(disc, index, book, quote_is_dm: bool):
+    """The same per-FRN code on the CPU (adr_frn_measures_host; no GPU needed)."""
+    (dm, dt, dd), (im, it, idf) = _frn_nodes(disc), _frn_nodes(index)
+    off, cpn, frn = frn_pack(book)
+    n, m = frn.shape[1], cpn.shape[1]
+    out, status = np.empty((len(FRN_OUTPUTS), n)), np.empty(n, dtype=np.int32)
+    _check(load().adr_frn_measures_host(dm, dt.size, _ptr(dt), _ptr(dd), im, it.size, _ptr(it), _ptr(idf), n, m,
+                                        _ptr(off, _i64p), _ptr(cpn), _ptr(frn), 1 if quote_is_dm else 0, _ptr(out),
+                                        _ptr(status, _i32p)), "adr_frn_measures_host")
+    return _frn_result(out, status)
+
+
+def frn_measures_dev(ctx: Context, disc_method: int, disc_n: int, index_method: int, index_n: int, n_frns: int,
+                     n_coupons: int, ptrs, quote_is_dm: bool, out_ptr: int, status_ptr: int, stream=0):
+    """Non-blocking form (adr_frn_measures_dev): ``ptrs`` maps ``disc_t``, ``disc_df``, ``index_t``, ``index_df``,
+    ``cpn_off``, ``cpn`` and ``frn`` (the arrays of `frn_pack`) to device pointers (integers, e.g. ``tensor.data_ptr()``);
+    ``out_ptr``: float64 [len(FRN_OUTPUTS), n_frns], ``status_ptr``: int32 [n_frns]."""
+    p = {k: _vp(int(ptrs[k]) or None) for k in ("disc_t", "disc_df", "index_t", "index_df", "cpn_off", "cpn", "frn")}
+    _check(load().adr_frn_measures_dev(ctx._h, int(disc_method), int(disc_n), p["disc_t"], p["disc_df"], int(index_method),
+                                       int(index_n), p["index_t"], p["index_df"], int(n_frns), int(n_coupons),
+                                       p["cpn_off"], p["cpn"], p["frn"], 1 if quote_is_dm else 0, _vp(out_ptr or None),
+                                       _vp(status_ptr or None), _vp(stream or None)), "adr_frn_measures_dev")
 
 
 _default_ctx = {}

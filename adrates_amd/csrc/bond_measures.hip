@@ -22,6 +22,7 @@
 
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
+#include "node_df.hpp"
 
 int adr_set_error(int status, const std::string& msg);                          // capi.hip
 int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
@@ -65,52 +66,6 @@ struct Args {
     double* out;                            // [ADR_BOND_OUTPUTS][n]
     int32_t* status;
 };
-
-// interpolator.py::_point: ``i`` is the first node with x[i] >= t (the reference's linear scan stops at n - 1), n when t
-// lies beyond the last node.  A time before the first node has no formula there; it gives NaN.
-__host__ __device__ inline double node_df(double t, const double* x, const double* d, int n, int method) {
-    if (t == x[0]) return d[0];
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (x[mid] < t) lo = mid + 1; else hi = mid;
-    }
-    int i = lo;
-    if (t > x[i]) i = n;
-    if (i == 0) return NAN;
-    if (method == ADR_INTERP_LINEAR_ZERO_RATES) {
-        double r1, r2, a, b;
-        if (i == 1) {                       // first segment: the first node's zero rate held flat
-            r1 = r2 = -log(d[1]) / x[1];
-            a = x[0]; b = x[1];
-        } else if (i < n) {
-            r1 = -log(d[i - 1]) / x[i - 1];
-            r2 = -log(d[i]) / x[i];
-            a = x[i - 1]; b = x[i];
-        } else {                            // extrapolation: the last node's zero rate held flat
-            r1 = r2 = -log(d[n - 1]) / x[n - 1];
-            a = x[n - 2]; b = x[n - 1];
-        }
-        const double rate = ((b - t) * r1 + (t - a) * r2) / (b - a);
-        return exp(-rate * t);
-    }
-    if (method == ADR_INTERP_FLAT_FWD_RATES) {   // -ln(df) linear; the last segment's slope beyond the last node
-        const int a = i < n ? i - 1 : n - 2, b = i < n ? i : n - 1;
-        const double rt1 = -log(d[a]), rt2 = -log(d[b]);
-        const double rt = ((x[b] - t) * rt1 + (t - x[a]) * rt2) / (x[b] - x[a]);
-        return exp(-rt);
-    }
-    // LINEAR_FWD_RATES: forwards of the segments interpolated; `small` regularises the first segment as the reference does
-    const double small = 1e-10;
-    if (i == 1) return exp(-(t * -log(d[1] + small) / (x[1] + small)));
-    const double fwd1 = -log(d[i - 1] / d[i - 2]) / (x[i - 1] - x[i - 2]);
-    double fwd = fwd1;
-    if (i < n) {
-        const double fwd2 = -log(d[i] / d[i - 1]) / (x[i] - x[i - 1]);
-        fwd = ((x[i] - t) * fwd1 + (t - x[i - 1]) * fwd2) / (x[i] - x[i - 1]);
-    }
-    return d[i - 1] * exp(-fwd * (t - x[i - 1]));
-}
 
 // What one flow adds to a pass.  A = (coupon + principal if > 0) * D(T) / D(T_s) is the flow on the curve (`value`
 // discounts relative to the settlement date); c is the coupon alone (the yield measures price coupons plus the FULL face at
@@ -465,12 +420,12 @@ int adr_bond_measures_host(int interp_method, int n_nodes, const double* node_t,
         for (int64_t b = lo; b < hi; ++b) {
             const int64_t f0 = flow_off[b];
             const int nf = static_cast<int>(flow_off[b + 1] - f0);
-            const double Ds = B::node_df(bond_Ts[b], node_t, node_df, n_nodes, interp_method);
+            const double Ds = adr::node_df(bond_Ts[b], node_t, node_df, n_nodes, interp_method);
             A.resize(static_cast<size_t>(nf));
             for (int i = 0; i < nf; ++i) {
                 const double p = flow_prin[f0 + i];
                 A[i] = (flow_cpn[f0 + i] + (p > 0.0 ? p : 0.0)) *
-                       (B::node_df(flow_T[f0 + i], node_t, node_df, n_nodes, interp_method) / Ds);
+                       (adr::node_df(flow_T[f0 + i], node_t, node_df, n_nodes, interp_method) / Ds);
             }
             B::HostGroup g{A.data(), flow_tau + f0, flow_cpn + f0, nf};
             const B::Result r = B::measures(g, bond_face[b], bond_tauM[b], bond_acc100[b], bond_quote[b], quote_is_z ? 1 : 0);

@@ -139,7 +139,7 @@ struct adr_trades {
 // the host-only translation units (book_host.cpp) report errors through the same per-thread message
 int adr_set_error(int status, const std::string& msg) { return fail(status, msg); }
 
-// the GPU and stream of a ctx, for the launch code of other translation units (bond_measures.hip)
+// the GPU and stream of a ctx, for the launch code of other translation units (bond_measures.hip, frn_measures.hip)
 int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream) {
     if (!ctx) return fail(ADR_ERR_INVALID, "null ctx");
     *device = ctx->device;

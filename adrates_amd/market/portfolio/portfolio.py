@@ -10,7 +10,8 @@ from typing import Iterable, List
 
 from ...requests.results import AnalyticsResult
 from ...utils.global_types import InstrumentTypes, RequestTypes
-from ..position.engine import Engine, bond_curve_type, is_bond, price_batch, price_bonds, wrap_result
+from ..position.engine import (Engine, bond_curve_type, frn_is_single_curve, is_bond, is_frn, price_batch, price_bonds,
+                               price_frns, wrap_result)
 from ..position.position import Position
 
 
@@ -27,13 +28,18 @@ class Portfolio:
     def compute(self, request_list: Iterable[RequestTypes]) -> AnalyticsResult:
         """Aggregate VALUE / DELTA / GAMMA over all positions."""
         reqs = set(request_list)
-        groups = {}   # (model id, curve, currency, OIS_SWAP or BOND) -> positions, in first-seen order
-        singles = []  # everything that is not an OIS or a bond: priced one by one and added with `+`, as the reference does
+        groups = {}   # (model id, curve, currency, OIS_SWAP, BOND or FRN) -> positions, in first-seen order
+        singles = []  # everything else (dual-curve FRNs among them): priced one by one and added with `+`, as the reference does
         for pos in self._positions:
             d = pos.derivative
             if d.derivative_type == InstrumentTypes.BOND and is_bond(d):
                 # bonds of one model and currency: one fixed-flows-only launch on that currency's OIS curve
                 key = (id(pos.model), bond_curve_type(d), d._currency, InstrumentTypes.BOND)
+                groups.setdefault(key, []).append(pos)
+                continue
+            if d.derivative_type == InstrumentTypes.FRN and is_frn(d) and frn_is_single_curve(d):
+                # single-curve FRNs of one model and currency: one float-leg launch on that currency's OIS curve
+                key = (id(pos.model), bond_curve_type(d), d._currency, InstrumentTypes.FRN)
                 groups.setdefault(key, []).append(pos)
                 continue
             if d.derivative_type != InstrumentTypes.OIS_SWAP:
@@ -58,7 +64,7 @@ class Portfolio:
             model = members[0].model
             ir_model = getattr(model.curves, curve_type.name)
             engine = members[0]._engine
-            pricer = price_bonds if kind == InstrumentTypes.BOND else price_batch
+            pricer = {InstrumentTypes.BOND: price_bonds, InstrumentTypes.FRN: price_frns}.get(kind, price_batch)
             res = pricer(engine, ir_model, [p.derivative for p in members], reqs, per_trade=False, aggregate=True)
             part = wrap_result(res, 0, reqs, res["tenors"], currency, curve_type, aggregate=True)
             if RequestTypes.VALUE in reqs:

@@ -22,7 +22,7 @@ import numpy as np
 
 from ... import _native
 from ...requests.results import AnalyticsResult, CashflowItem, Cashflows, Delta, Gamma, Valuation
-from ...trades.compiler import compile_bonds, compile_ois
+from ...trades.compiler import compile_bonds, compile_frns, compile_ois
 from ...utils.error import LibError
 from ...utils.currency import CurrencyTypes
 from ...utils.global_types import (CurveTypes, InstrumentTypes, InterpTypes, RequestTypes, SwapTypes,
@@ -47,6 +47,16 @@ def bond_curve_type(bond):
 def is_bond(derivative) -> bool:
     from ...trades.credit.bond import Bond
     return isinstance(derivative, Bond)
+
+
+def is_frn(derivative) -> bool:
+    from ...trades.credit.frn import FRN
+    return isinstance(derivative, FRN)
+
+
+def frn_is_single_curve(frn) -> bool:
+    """The index curve is the discount curve (the currency's OIS curve, engine.py:711-720, 749)."""
+    return frn._floating_index == bond_curve_type(frn)
 
 
 class Engine:
@@ -94,6 +104,8 @@ class Engine:
             return compute_xccy(self, derivative, reqs)
         if dtype == InstrumentTypes.BOND and is_bond(derivative):
             return self._compute_bond(derivative, reqs)
+        if dtype == InstrumentTypes.FRN and is_frn(derivative):
+            return self._compute_frn(derivative, reqs)
         raise LibError(f"{dtype} not yet implemented")
 
     def _compute_ois(self, derivative, reqs, collateral_type=None):
@@ -152,6 +164,48 @@ class Engine:
                                           discount_factor=float(bond._payment_dfs[i]),
                                           discounted_amount=float(bond._principal_pvs[i]), leg_type="Principal"))
         return Cashflows(items, bond._currency)
+
+    def _compute_frn(self, frn, reqs):
+        """An FRN's curve Greeks (engine.py:700-983): a float leg plus the face at maturity, sign +1, discounted on its
+        currency's OIS curve with forwards off ``model.curves.<floating_index>``.  Dual-curve FRNs have VALUE only:
+        their forwards are read off the index curve's tables and the coupons priced as fixed flows."""
+        curve_type = bond_curve_type(frn)
+        disc_model = getattr(self.model.curves, curve_type.name)
+        index_model = getattr(self.model.curves, frn._floating_index.name)
+        single = frn_is_single_curve(frn)
+        out = AnalyticsResult()
+        if reqs & {RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}:
+            if not single and reqs & {RequestTypes.DELTA, RequestTypes.GAMMA}:
+                raise LibError("Dual-curve FRN delta/gamma not yet implemented. "
+                               "Use same curve for discounting and projection.")
+            res = price_frns(self, disc_model, [frn], reqs, per_trade=True, aggregate=False,
+                             index_model=None if single else index_model)
+            out = wrap_result(res, 0, reqs, ir_model_tenors=res["tenors"], currency=frn._currency, curve_type=curve_type)
+        if RequestTypes.CASHFLOWS in reqs:
+            out = AnalyticsResult(value=out.value, risk=out.risk, gamma=out.gamma,
+                                  cashflows=self._frn_cashflows(frn, disc_model, index_model))
+        return out
+
+    def _frn_cashflows(self, frn, disc_model, index_model):
+        """Coupon and principal items (engine.py:931-981), from `FRN.value` on the curves' own nodes at the model's
+        value date.  The principal item carries the LAST payment's discount factor."""
+        frn.value(self.model.value_dt, disc_model, index_model)
+        items = []
+        last = len(frn._payment_dts) - 1
+        for i, pay_dt in enumerate(frn._payment_dts):
+            coupon = frn._coupon_payments[i]
+            if abs(coupon) > 1e-10:
+                items.append(CashflowItem(payment_date=pay_dt, notional=frn._face_value,
+                                          payment_fraction=frn._rates[i], accrual_period=float(frn._year_fracs[i]),
+                                          amount=float(coupon), discount_factor=float(frn._payment_dfs[i]),
+                                          discounted_amount=float(coupon * frn._payment_dfs[i]),
+                                          leg_type="Floating_Coupon"))
+            if i == last:
+                df = frn._payment_dfs[i] if i < len(frn._payment_dfs) else 0.0
+                items.append(CashflowItem(payment_date=pay_dt, notional=frn._face_value, payment_fraction=1.0,
+                                          accrual_period=0.0, amount=float(frn._face_value), discount_factor=float(df),
+                                          discounted_amount=float(frn._face_value * df), leg_type="Principal"))
+        return Cashflows(items, frn._currency)
 
     # --------------------------------------------------------------- cash flows
     @staticmethod
@@ -213,6 +267,34 @@ def price_bonds(engine: Engine, ir_model, bonds, reqs, per_trade=True, aggregate
                             per_trade=per_trade, aggregate=aggregate)
     finally:
         dev_trades.close()
+    out["tenors"] = cur["tenors"]
+    return out
+
+
+def price_frns(engine: Engine, disc_model, frns, reqs, per_trade=True, aggregate=False, index_model=None):
+    """Compile, upload and price FRNs on ``disc_model``'s curve through the OIS route.  ``index_model``: the index
+    curve of dual-curve FRNs (VALUE only), whose forwards come from its device tables (adr_curve_df).  Coupons paid
+    at the value time are added to the PV here (see `compile_frns`)."""
+    cur = engine._device_curve(disc_model)
+    index_df = None
+    if index_model is not None:
+        idx = engine._device_curve(index_model)
+        index_df = lambda t: _native.curve_df(idx["ctx"], idx["dev"], np.asarray(t, dtype=np.float64))
+    batch, pv_const = compile_frns(frns, disc_model._value_dt, index_df)
+    dev_trades = _native.DeviceTrades(cur["ctx"], batch)
+    try:
+        out = _native.price(cur["ctx"], cur["dev"], dev_trades,
+                            want_value=RequestTypes.VALUE in reqs,
+                            want_delta=RequestTypes.DELTA in reqs,
+                            want_gamma=RequestTypes.GAMMA in reqs,
+                            per_trade=per_trade, aggregate=aggregate)
+    finally:
+        dev_trades.close()
+    if RequestTypes.VALUE in reqs:
+        if per_trade:
+            out["pv"] = out["pv"] + pv_const
+        if aggregate:
+            out["agg_pv"] = out["agg_pv"] + float(pv_const.sum())
     out["tenors"] = cur["tenors"]
     return out
 

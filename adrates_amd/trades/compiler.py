@@ -108,6 +108,71 @@ def compile_bonds(bonds: Iterable, value_dt) -> TradeBatch:
                       empty, empty.copy(), empty.copy(), empty.copy(), f64(notional), np.zeros(n), np.ones(n), np.ones(n))
 
 
+def compile_frns(frns: Iterable, value_dt, index_df=None):
+    """Batch of FRNs as the reference's engine prices them: `_float_leg_jax` plus the face at the adjusted maturity
+    on one curve (cavour/market/position/engine.py:700-880, 2639-2728).  Returns ``(batch, pv_const)``.
+
+    Times are year fractions from ``value_dt`` in the FRN's day count.  Per FRN, sign +1 and ``notional`` = the face:
+    float coupons with ``alpha`` = the FRN's year fraction and ``spread`` = the quoted margin; fixed flows for the face
+    at the maturity time (the engine's strict ``>`` mask) and, where the engine's first-fixing override applies - coupon
+    0 of the WHOLE schedule, paid after the value time - for that coupon, ``(first fixing + margin) alpha_0 face``.
+
+    Coupons paid before the value time are masked and left out.  A coupon paid exactly AT the value time counts (the
+    float leg's ``>=`` mask) with discount factor 1; it goes to ``pv_const`` [n] rather than to the batch (the
+    kernels' fixed-flow mask is ``>``).  Its accrual ends at or before the value time, where the engine's
+    interpolation holds D = 1, so its forward is 0.
+
+    ``index_df``: a vectorised ``t -> D_index(t)`` for dual-curve FRNs.  The forwards then come from it and every
+    coupon becomes a fixed flow on the discount curve; the Greeks of such a batch are the discount curve's only."""
+    fix_off, flt_off = [0], [0]
+    fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_al = [], [], [], [], [], []
+    notional, spread, pv_const = [], [], []
+    for f in frns:
+        if getattr(f, "derivative_type", None) != InstrumentTypes.FRN:
+            raise LibError(f"{getattr(f, 'derivative_type', type(f))} is not an FRN")
+        face, margin, ffr = float(f._face_value), float(f._quoted_margin), f._first_fixing_rate
+        tp = np.array(_times(f._payment_dts, value_dt, f._dc_type))
+        ts = np.array(_times(f._start_accrued_dts, value_dt, f._dc_type))
+        te = np.array(_times(f._end_accrued_dts, value_dt, f._dc_type))
+        al = np.array(f._year_fracs, dtype=np.float64)
+        tm = _times([f._maturity_dt], value_dt, f._dc_type)[0]
+        if index_df is not None:
+            fwd = (np.asarray(index_df(ts)) / np.asarray(index_df(te)) - 1.0) / al
+        else:
+            fwd = np.where(tp == 0.0, 0.0, np.nan)               # D = 1 at and before the value time
+        fixed = np.full(tp.shape, index_df is not None)
+        if ffr is not None:
+            fwd[0], fixed[0] = ffr, True
+        const = 0.0
+        flows = []
+        for j in range(tp.size):
+            if tp[j] < 0.0:
+                continue
+            amount = (fwd[j] + margin) * al[j] * face if fixed[j] or tp[j] == 0.0 else None
+            if tp[j] == 0.0:
+                const += amount
+            elif fixed[j]:
+                flows.append((tp[j], amount))
+            else:
+                flt_tp.append(tp[j]); flt_ts.append(ts[j]); flt_te.append(te[j]); flt_al.append(al[j])
+        if tm > 0.0:
+            flows.append((tm, face))
+        flows.sort(key=lambda x: x[0])
+        fix_tp += [t for t, _ in flows]
+        fix_pay += [a for _, a in flows]
+        fix_off.append(len(fix_tp))
+        flt_off.append(len(flt_tp))
+        notional.append(face)
+        spread.append(margin)
+        pv_const.append(const)
+    n = len(notional)
+    f64 = lambda a: np.array(a, dtype=np.float64)
+    batch = TradeBatch(np.array(fix_off, dtype=np.int64), np.array(flt_off, dtype=np.int64), f64(fix_tp), f64(fix_pay),
+                       f64(flt_tp), f64(flt_ts), f64(flt_te), f64(flt_al), f64(notional), f64(spread), np.ones(n),
+                       np.ones(n))
+    return batch, f64(pv_const)
+
+
 # --------------------------------------------------------------------------------------------------------
 # Vectorised path: trades given by their economic terms, no per-trade objects
 # (SURVEY.md section 8(f) row 4).  Every Python `Date` / `Schedule` / `DayCount` call of the object path

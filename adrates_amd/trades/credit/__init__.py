@@ -1,2 +1,3 @@
-"""Credit products: fixed-rate bonds (cavour/trades/credit/bond.py)."""
+"""Credit products: fixed-rate bonds and floating-rate notes (cavour/trades/credit/)."""
 from .bond import Bond  # noqa: F401
+from .frn import FRN  # noqa: F401

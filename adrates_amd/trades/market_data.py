@@ -90,3 +90,39 @@ def random_bond_book(value_dt, n, seed=7, currency=CurrencyTypes.GBP):
                      amortization_schedule=Bond.generate_equal_principal_schedule(face, b._num_coupons))
         bonds.append(b)
     return bonds, rng.uniform(-0.02, 0.06, size=n)
+
+
+def random_frn_book(value_dt, n, seed=7, currency=CurrencyTypes.GBP):
+    """``n`` single-curve FRNs on ``currency``'s OIS index: 1Y-30Y tenors, monthly to annual coupons, ACT/360 or
+    ACT/365F, margins of -50 to 300bp, payment lags of 0-2 days, faces of 100, 1 000 or 1 000 000.  About 30% are
+    seasoned (issued up to five years before ``value_dt``, with a first fixing of 3-6%; none matures within a month, and
+    every coupon after the fixed one starts on or after ``value_dt``), the rest issued within ten days after it; about
+    10% are capped at 4-8%, 10% floored at 0-2% and 5% both.  Also returns a DM per FRN, between -1% and 4%."""
+    import numpy as np
+    from .credit.frn import FRN
+    index = {CurrencyTypes.GBP: CurveTypes.GBP_OIS_SONIA, CurrencyTypes.USD: CurveTypes.USD_OIS_SOFR,
+             CurrencyTypes.EUR: CurveTypes.EUR_OIS_ESTR}[currency]
+    tenors = ["1Y", "2Y", "3Y", "4Y", "5Y", "7Y", "10Y", "12Y", "15Y", "20Y", "25Y", "30Y"]
+    freqs = [FrequencyTypes.MONTHLY, FrequencyTypes.QUARTERLY, FrequencyTypes.SEMI_ANNUAL, FrequencyTypes.ANNUAL]
+    dcs = [DayCountTypes.ACT_360, DayCountTypes.ACT_365F]
+    rng = np.random.default_rng(seed)
+    frns = []
+    while len(frns) < n:
+        seasoned = rng.random() < 0.3
+        issue = value_dt.add_days(-int(rng.integers(1, 5 * 365)) if seasoned else int(rng.integers(0, 10)))
+        tenor, freq, dc = (tenors[int(rng.integers(len(tenors)))], freqs[int(rng.integers(len(freqs)))],
+                           dcs[int(rng.integers(len(dcs)))])
+        margin = round(float(rng.uniform(-0.005, 0.03)), 5)
+        kind = rng.random()
+        cap = round(float(rng.uniform(0.04, 0.08)), 4) if kind < 0.1 or kind > 0.95 else None
+        floor = round(float(rng.uniform(0.0, 0.02)), 4) if 0.1 <= kind < 0.2 or kind > 0.95 else None
+        f = FRN(issue, tenor, margin, freq, dc, currency, index, face_value=float(rng.choice([100.0, 1000.0, 1e6])),
+                payment_lag=int(rng.integers(0, 3)), cap_rate=cap, floor_rate=floor,
+                first_fixing_rate=round(float(rng.uniform(0.03, 0.06)), 5) if seasoned else None)
+        if f._payment_dts[-1] <= value_dt.add_days(30):
+            continue
+        live = [i for i, d in enumerate(f._payment_dts) if d > value_dt]
+        if seasoned and f._end_accrued_dts[live[0]] < value_dt:
+            continue                                  # the next coupon would need the index before its value date
+        frns.append(f)
+    return frns, rng.uniform(-0.01, 0.04, size=n)
