@@ -1,0 +1,350 @@
+"""Edge books and curves for the bond and FRN measures kernels (csrc/bond_measures.hip, csrc/frn_measures.hip), shared
+by the host and GPU tests: inputs and a small numpy restatement of the kernels' documented formulas, no expected values.
+
+The books sit around the kernels' launch geometry: 16 lanes per instrument, and 8 flows per lane (128 per bond) or 24
+coupons per lane (384 per FRN) held in registers, later ones re-read from global memory on every pass.  The curves
+cover every branch of node_df.hpp: the first segment, the interior, the extrapolation beyond the last node, a 2-node
+table, and tables of 257 and 1024 nodes (two and four passes of the kernels' 256-thread LDS staging loop)."""
+import functools
+import math
+
+import numpy as np
+
+from adrates_amd import _native
+from adrates_amd.market.curves.discount_curve import DiscountCurve
+from adrates_amd.market.curves.interpolator import _point
+from adrates_amd.market.position.bond_book import compile_bond_measures
+from adrates_amd.market.position.frn_book import compile_frn_measures
+from adrates_amd.trades.credit import FRN, Bond
+from adrates_amd.trades.market_data import README_VALUE_DT, gbp_model, random_bond_book, random_frn_book
+from adrates_amd.utils import CurrencyTypes, CurveTypes, Date, DayCountTypes, FrequencyTypes, InterpTypes
+
+GBP, SONIA = CurrencyTypes.GBP, CurveTypes.GBP_OIS_SONIA
+M, Q, A = FrequencyTypes.MONTHLY, FrequencyTypes.QUARTERLY, FrequencyTypes.ANNUAL
+ACT365, ACT360, T360 = DayCountTypes.ACT_365F, DayCountTypes.ACT_360, DayCountTypes.THIRTY_360_BOND
+SCHEMES = (InterpTypes.FLAT_FWD_RATES, InterpTypes.LINEAR_FWD_RATES, InterpTypes.LINEAR_ZERO_RATES)
+VD = README_VALUE_DT                # 30 Apr 2024: every curve's value date and the bonds' settlement
+FRN_SETTLE = Date(16, 1, 2025)      # the FRNs' settlement: after one FRN's principal, before its last coupon
+BUMP = 0.0001
+MAX_NODES = 1024                    # ADR_BOND_MAX_NODES, ADR_FRN_MAX_NODES
+
+
+# ------------------------------------------------------------------------------------------------ books
+def edge_bonds():
+    """``[(name, bond, live flows after VD)]``: flow counts around the 16 lanes (1, 15, 16, 17) and the 128-flow
+    register window (127, 128, 129, 144), and 600 (50Y monthly)."""
+    ann = lambda n, c: Bond.generate_annuity_schedule(1e6, n, c, M)
+    return [
+        ("1_zero_coupon_lag1", Bond(VD, "15M", 0.0, M, ACT360, GBP, face_value=1e6, payment_lag=1), 1),
+        ("15_bullet", Bond(VD, "15M", 0.04, M, ACT365, GBP), 15),
+        ("16_lag2", Bond(VD, "16M", 0.055, M, T360, GBP, payment_lag=2), 16),
+        # seasoned, settling on the coupon date 30 Apr 2024: that coupon is not paid, nothing is accrued
+        ("17_on_coupon_date", Bond(Date(30, 4, 2023), "29M", 0.035, M, ACT365, GBP), 17),
+        ("127_lag1", Bond(VD, "127M", 0.045, M, ACT365, GBP, face_value=1000.0, payment_lag=1), 127),
+        ("128_annuity", Bond(VD, "128M", 0.05, M, ACT360, GBP, face_value=1e6, amortization_schedule=ann(128, 0.05)), 128),
+        ("129_seasoned", Bond(Date(15, 1, 2024), "132M", 0.025, M, ACT365, GBP), 129),
+        ("144_long_annuity_lag2", Bond(Date(15, 2, 2024), "146M", 0.06, M, ACT365, GBP, face_value=1e6, payment_lag=2,
+                                       amortization_schedule=ann(146, 0.06)), 144),
+        ("600_50y_monthly", Bond(Date(1, 5, 2024), "50Y", 0.03, M, ACT365, GBP), 600),
+    ]
+
+
+def edge_frns():
+    """``[(name, frn, live coupons after FRN_SETTLE)]``: coupon counts 1, 17, 383, 384, 385 (around the 384-coupon
+    register window) and 600.  Seasoned ones carry a first fixing; caps, floors and payment lags are mixed in; the
+    1-coupon FRN's principal (15 Jan 2025) is paid before settlement, its last coupon (17 Jan) after it."""
+    mk = lambda issue, tenor, margin, freq, dc, **kw: FRN(issue, tenor, margin, freq, dc, GBP, SONIA, **kw)
+    return [
+        ("1_principal_before_settlement", mk(Date(15, 1, 2024), "1Y", 0.005, Q, ACT360, payment_lag=2,
+                                             first_fixing_rate=0.05), 1),
+        ("17_seasoned_capped", mk(Date(10, 6, 2024), "24M", 0.004, M, ACT365, first_fixing_rate=0.045, cap_rate=0.05), 17),
+        ("383_floored_lag1", mk(Date(1, 2, 2025), "383M", 0.002, M, ACT360, payment_lag=1, floor_rate=0.035), 383),
+        ("384_seasoned_collar", mk(Date(20, 12, 2024), "384M", 0.01, M, ACT365, face_value=1e6, first_fixing_rate=0.04,
+                                   cap_rate=0.06, floor_rate=0.038), 384),
+        ("385_lag2", mk(FRN_SETTLE, "385M", -0.003, M, ACT365, face_value=1000.0, payment_lag=2), 385),
+        ("600_50y_monthly", mk(Date(1, 2, 2025), "50Y", 0.0075, M, ACT360), 600),
+    ]
+
+
+def live_counts(offsets):
+    off = np.asarray(offsets)
+    return list(off[1:] - off[:-1])
+
+
+def bond_arrays(bonds, curve, z_or_price, settle=VD):
+    """``(method, node_t, node_df, book with bond_quote)``: adr_bond_measures' inputs on ``curve``'s own nodes."""
+    book = compile_bond_measures(bonds, curve, settle)
+    book["bond_quote"] = np.broadcast_to(np.asarray(z_or_price, dtype=np.float64), (len(bonds),)).copy()
+    return nodes(curve) + (book,)
+
+
+def frn_arrays(frns, disc, index, quote, guess=0.0, settle=FRN_SETTLE):
+    """``(disc nodes, index nodes, book with frn_quote and frn_guess)``: adr_frn_measures' inputs."""
+    book = compile_frn_measures(frns, disc, index, settle)
+    n = len(frns)
+    book["frn_quote"] = np.broadcast_to(np.asarray(quote, dtype=np.float64), (n,)).copy()
+    book["frn_guess"] = np.broadcast_to(np.asarray(guess, dtype=np.float64), (n,)).copy()
+    return nodes(disc), nodes(index), book
+
+
+def nodes(curve):
+    return (curve._interp_type.value, np.asarray(curve._times, dtype=np.float64),
+            np.asarray(curve._dfs, dtype=np.float64))
+
+
+def filler_bonds(n=15):
+    return random_bond_book(VD, n, seed=11)[0]
+
+
+def filler_frns(n=15):
+    return random_frn_book(VD, n, seed=11)[0]
+
+
+# ------------------------------------------------------------------------------------------------ batches
+BOND_KEYS = ("flow_off", _native.BOND_FLOW_FIELDS, _native.BOND_FIELDS)
+FRN_KEYS = ("cpn_off", _native.FRN_FLOW_FIELDS, _native.FRN_FIELDS)
+
+
+def take(book, idx, keys):
+    """The instruments ``idx`` (any order, repeats allowed) of a compiled book, as a book of their own."""
+    off_key, flow_fields, fields = keys
+    off = np.asarray(book[off_key], dtype=np.int64)
+    idx = np.asarray(idx, dtype=np.int64)
+    counts = off[idx + 1] - off[idx]
+    out = {off_key: np.concatenate(([0], np.cumsum(counts))).astype(np.int64)}
+    flows = np.concatenate([np.arange(off[i], off[i + 1]) for i in idx]) if idx.size else np.zeros(0, np.int64)
+    for k in flow_fields:
+        out[k] = np.asarray(book[k], dtype=np.float64)[flows]
+    for k in fields:
+        out[k] = np.asarray(book[k], dtype=np.float64)[idx]
+    return out
+
+
+def concat(a, b, keys):
+    """Book ``a`` followed by book ``b``."""
+    off_key, flow_fields, fields = keys
+    out = {off_key: np.concatenate((a[off_key], a[off_key][-1] + b[off_key][1:])).astype(np.int64)}
+    for k in flow_fields + fields:
+        out[k] = np.concatenate((a[k], b[k]))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ curves
+def zero_rate(t):
+    """A humped zero curve with a small wiggle, so that the three schemes give visibly different discount factors."""
+    t = np.asarray(t, dtype=np.float64)
+    return 0.032 + 0.015 * (1.0 - np.exp(-t / 6.0)) - 0.01 * t / 50.0 + 0.0015 * np.sin(1.3 * t)
+
+
+def node_curve(years, scheme):
+    """A `DiscountCurve` on VD with a node at each of ``years`` (plus its own node at 0)."""
+    years = np.asarray(years, dtype=np.float64)
+    return DiscountCurve(VD, list(years), list(np.exp(-zero_rate(years) * years)), scheme)
+
+
+CURVES = ("gbp", "short_20y", "two_node", "nodes_257", "nodes_1024")
+
+
+@functools.lru_cache(maxsize=None)
+def curves(scheme):
+    """Every curve of the edge tests under ``scheme``: the GBP model's OIS curve (33 nodes to 50Y); 40 nodes stopping
+    at 20Y, so longer flows extrapolate; 2 nodes (0 and 7Y); 257 nodes to 45Y, whose last node the 50Y flows read;
+    1024 nodes to 55Y."""
+    return {
+        "gbp": gbp_model(interp=scheme).curves.GBP_OIS_SONIA,
+        "short_20y": node_curve(np.arange(1, 41) * 0.5, scheme),
+        "two_node": node_curve([7.0], scheme),
+        "nodes_257": node_curve(np.arange(1, 257) * (45.0 / 256), scheme),
+        "nodes_1024": node_curve(np.arange(1, 1024) * (55.0 / 1023), scheme),
+    }
+
+
+def frn_curve_pairs():
+    """``[(discount curve name, index curve name)]``: node counts differ within every pair; the index curve is taken
+    under the scheme after the discount curve's (see `index_scheme`)."""
+    return [("gbp", "short_20y"), ("short_20y", "nodes_1024"), ("two_node", "gbp"), ("nodes_257", "two_node"),
+            ("nodes_1024", "nodes_257")]
+
+
+def index_scheme(scheme):
+    return SCHEMES[(SCHEMES.index(scheme) + 1) % len(SCHEMES)]
+
+
+def too_many_nodes():
+    """1025 increasing node times and their discount factors: one more than the kernels stage in LDS."""
+    t = np.arange(MAX_NODES + 1) * 0.05
+    return t, np.exp(-zero_rate(t) * t)
+
+
+# ------------------------------------------------------------------------------------------------ raw arrays
+def bonds_on_nodes():
+    """``(method-free node table, z-given book)``: raw arrays no instrument produces.  Bond 0 settles on node 5 and
+    pays 150 flows each exactly on a node time (past the 128-flow register window); bond 1 settles on the first node
+    and pays 20 flows on node times and 3 between nodes and beyond the last one."""
+    t = np.concatenate(([0.0], np.arange(1, 257) * 0.2))
+    d = np.exp(-zero_rate(t) * t)
+    T0 = t[6:156]
+    T1 = np.concatenate((t[10:30], [t[30] + 0.05, t[-1] + 0.3, t[-1] + 2.0]))
+    Ts = np.array([t[5], t[0]])
+    flow_T = np.concatenate((T0, T1))
+    tau = np.concatenate((T0 - Ts[0], T1 - Ts[1]))
+    cpn = np.concatenate((np.full(T0.size, 1.25), np.full(T1.size, 2.0)))
+    prin = np.zeros(flow_T.size)
+    prin[T0.size - 1] = 100.0
+    prin[T0.size + 5] = -3.0                # a principal <= 0 is not paid
+    prin[-1] = 100.0
+    book = {"flow_off": np.array([0, T0.size, flow_T.size], dtype=np.int64), "flow_T": flow_T, "flow_tau": tau,
+            "flow_cpn": cpn, "flow_prin": prin, "bond_Ts": Ts, "bond_tauM": np.array([tau[T0.size - 1], tau[-1]]),
+            "bond_face": np.array([100.0, 100.0]), "bond_acc100": np.array([0.4, 0.0]),
+            "bond_quote": np.array([0.012, -0.004])}
+    return t, d, book
+
+
+def frns_on_nodes():
+    """``(discount table, index table, DM-given book)``: FRN 0 settles on a discount node and has 420 coupons whose
+    payment, start and end times lie on nodes; FRN 1 is the same note, but coupon #400 starts before the index curve's
+    first node (status 3) - beyond the 384-coupon register window, so only the second projection loop sees it."""
+    dt = np.concatenate(([0.0], np.arange(1, 901) * (1.0 / 12.0) * 0.5))
+    dd = np.exp(-zero_rate(dt) * dt)
+    it = 0.3 + np.arange(0, 700) * (1.0 / 12.0) * 0.5
+    idf = np.exp(-(zero_rate(it) + 0.002) * it)
+    k = 420
+    Ts = dt[4]
+    ts = it[np.arange(k)]
+    te = it[np.arange(k) + 1]
+    T = dt[np.arange(k) + 5]
+    cols = {"cpn_T": T, "cpn_ts": ts, "cpn_te": te, "cpn_ialpha": te - ts, "cpn_alpha": np.full(k, 1.0 / 24.0),
+            "cpn_tau": T - Ts, "cpn_fix": np.zeros(k)}
+    cols["cpn_fix"][0] = 1.0
+    bad = {c: v.copy() for c, v in cols.items()}
+    bad["cpn_ts"][399] = it[0] - 0.1
+    book = {"cpn_off": np.array([0, k, 2 * k], dtype=np.int64)}
+    for c in _native.FRN_FLOW_FIELDS:
+        book[c] = np.concatenate((cols[c], bad[c]))
+    one = {"frn_Ts": Ts, "frn_TM": dt[k + 4], "frn_tauM": dt[k + 4] - Ts, "frn_face": 100.0, "frn_margin": 0.004,
+           "frn_cap": np.inf, "frn_floor": -np.inf, "frn_ffr": 0.041, "frn_acc100": 0.05, "frn_quote": 0.003,
+           "frn_guess": 0.0}
+    for c in _native.FRN_FIELDS:
+        book[c] = np.full(2, one[c], dtype=np.float64)
+    return (dt, dd), (it, idf), book
+
+
+# ------------------------------------------------------------------------------------------------ numpy restatement
+def _df(t, node_t, node_df, method):
+    if not t >= node_t[0]:
+        return math.nan
+    return float(_point(float(t), node_t, node_df, method))
+
+
+def _bisect(f, lo, hi):
+    """The root of an increasing or decreasing ``f`` on [lo, hi], to the last bit."""
+    flo = f(lo)
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid in (lo, hi):
+            break
+        fm = f(mid)
+        if (fm < 0.0) == (flo < 0.0):
+            lo, flo = mid, fm
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def restate_bonds_z(method, node_t, node_df, book):
+    """adr_bond_measures' outputs for given z-spreads, restated from its documentation: A_i = (coupon + principal if
+    > 0) D(T_i) / D(T_s) on `_point`, P(x) = sum A_i exp(-x tau_i); dirty = 100 P(z) / face, clean = dirty - accrued,
+    dv01 = (P(z - 1bp) - P(z + 1bp)) / 2; the yield prices the coupons plus the face at tau_M to the dirty value, and
+    duration and convexity are its first and second moments."""
+    off = book["flow_off"]
+    out = {k: np.empty(off.size - 1) for k in _native.BOND_OUTPUTS}
+    for b in range(off.size - 1):
+        s = slice(off[b], off[b + 1])
+        Ds = _df(book["bond_Ts"][b], node_t, node_df, method)
+        T, tau, c, p = (np.asarray(book[k][s]) for k in _native.BOND_FLOW_FIELDS)
+        A = (c + np.maximum(p, 0.0)) * np.array([_df(x, node_t, node_df, method) for x in T]) / Ds
+        P = lambda x: math.fsum(A * np.exp(-x * tau))
+        face, tauM, acc, z = (book[k][b] for k in ("bond_face", "bond_tauM", "bond_acc100", "bond_quote"))
+        dirty = P(z) / face * 100.0
+        ytau, yamt = (np.append(tau, tauM), np.append(c, face)) if tauM > 0.0 else (tau, c)
+        Y = lambda y, k=0: math.fsum(yamt * ytau ** k * np.exp(-y * ytau))
+        y = _bisect(lambda y: Y(y) - dirty / 100.0 * face, -0.5, 0.5)
+        vals = {"z": z, "dirty": dirty, "clean": dirty - acc, "ytm": y, "duration": Y(y, 1) / Y(y),
+                "convexity": Y(y, 2) / Y(y), "dv01": (P(z - BUMP) - P(z + BUMP)) / 2.0}
+        for k, v in vals.items():
+            out[k][b] = v
+    return out
+
+
+def restate_frns_dm(disc, index, book):
+    """adr_frn_measures' outputs for given DMs, restated from its documentation: each coupon's forward on the index
+    nodes (the first fixing where flagged), plus the margin, capped and floored, times the FRN year fraction and the
+    face, times D(pay) / D(settlement) on the discount nodes; the face at T_M when it is paid.  PV(x) = sum
+    A_i exp(-x tau_i); dirty = 100 PV / face, duration = -(dirty(x + 1bp) - dirty(x - 1bp)) / (2bp dirty),
+    dv01 = |PV(x + 1bp) - PV(x)|.  A forward that needs the index curve before its first node: status 3, NaN."""
+    (dm, dt, dd), (im, it, idf) = disc, index
+    off = book["cpn_off"]
+    n = off.size - 1
+    out = {k: np.full(n, np.nan) for k in _native.FRN_OUTPUTS}
+    out["status"] = np.zeros(n, dtype=np.int32)
+    for b in range(n):
+        g = lambda k: book[k][b]
+        Ds = _df(g("frn_Ts"), dt, dd, dm)
+        A, tau, bad = [], [], False
+        for i in range(off[b], off[b + 1]):
+            c = lambda k: book[k][i]
+            if c("cpn_fix") != 0.0:
+                fwd = g("frn_ffr")
+            else:
+                bad |= not (c("cpn_ts") >= it[0] and c("cpn_te") >= it[0])
+                fwd = (_df(c("cpn_ts"), it, idf, im) / _df(c("cpn_te"), it, idf, im) - 1.0) / c("cpn_ialpha")
+            rate = max(min(fwd + g("frn_margin"), g("frn_cap")), g("frn_floor"))
+            A.append(rate * c("cpn_alpha") * g("frn_face") * _df(c("cpn_T"), dt, dd, dm) / Ds)
+            tau.append(c("cpn_tau"))
+        if bad:
+            out["status"][b] = 3
+            continue
+        if g("frn_TM") == g("frn_TM"):
+            A.append(g("frn_face") * _df(g("frn_TM"), dt, dd, dm) / Ds)
+            tau.append(g("frn_tauM"))
+        A, tau = np.array(A), np.array(tau)
+        P = lambda x: math.fsum(A * np.exp(-x * tau))
+        x, face = g("frn_quote"), g("frn_face")
+        dirty = 100.0 * P(x) / face
+        vals = {"dm": x, "dirty": dirty, "clean": dirty - g("frn_acc100"), "pv": P(x),
+                "mod_duration": -(100.0 * P(x + BUMP) / face - 100.0 * P(x - BUMP) / face) / (2 * BUMP * dirty),
+                "dv01": abs(P(x + BUMP) - P(x))}
+        for k, v in vals.items():
+            out[k][b] = v
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ scalar references
+BOND_Z = np.linspace(-0.01, 0.04, 9)                          # a z-spread per edge bond
+FRN_DM = np.array([0.003, -0.004, 0.012, 0.0, 0.02, 0.006])   # a DM per edge FRN
+
+
+@functools.lru_cache(maxsize=None)
+def bond_refs(scheme, curve_name):
+    """``(curve, clean prices at BOND_Z, scalar measures at BOND_Z)`` of the edge bonds: the scalar `Bond` methods on
+    the same curve object.  The clean price at z is the quote of the price mode, so one set of references serves both
+    modes."""
+    from ._bonds import scalar_measures
+    curve = curves(scheme)[curve_name]
+    refs = [scalar_measures(b, curve, VD, z=z) for (_, b, _), z in zip(edge_bonds(), BOND_Z)]
+    return curve, np.array([r["clean"] for r in refs]), refs
+
+
+def frn_scalar(f, disc, index, dm, settle=FRN_SETTLE):
+    return {"dirty": f.dirty_price(settle, disc, index, dm), "clean": f.clean_price(settle, disc, index, dm),
+            "pv": f.value(settle, disc, index, dm), "mod_duration": f.modified_duration(settle, disc, index, dm),
+            "dv01": f.dv01(settle, disc, index, dm)}
+
+
+@functools.lru_cache(maxsize=None)
+def frn_refs(scheme, disc_name, index_name):
+    """``(discount curve, index curve, clean prices at FRN_DM, scalar measures at FRN_DM)`` of the edge FRNs, the
+    discount curve under ``scheme`` and the index curve under `index_scheme`."""
+    disc, index = curves(scheme)[disc_name], curves(index_scheme(scheme))[index_name]
+    refs = [frn_scalar(f, disc, index, dm) for (_, f, _), dm in zip(edge_frns(), FRN_DM)]
+    return disc, index, np.array([r["clean"] for r in refs]), refs
