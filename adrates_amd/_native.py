@@ -85,6 +85,13 @@ _SIGNATURES = {
                                        _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "adr_frn_measures_host": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int64, _i64p,
                                         _dp, _dp, C.c_int, _dp, _i32p]),
+    "adr_yoy_risk": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int64, _i64p, _dp,
+                               C.c_uint32, _dp, _dp, _dp, _dp, _dp]),
+    "adr_yoy_risk_work": (C.c_int64, [C.c_int64, C.c_int]),
+    "adr_yoy_risk_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp,
+                                   C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "adr_yoy_risk_host": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int64, _i64p, _dp,
+                                    C.c_uint32, _dp, _dp, _dp, _dp, _dp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -643,6 +650,81 @@ def frn_measures_dev(ctx: Context, disc_method: int, disc_n: int, index_method: 
                                        int(index_n), p["index_t"], p["index_df"], int(n_frns), int(n_coupons),
                                        p["cpn_off"], p["cpn"], p["frn"], 1 if quote_is_dm else 0, _vp(out_ptr or None),
                                        _vp(status_ptr or None), _vp(stream or None)), "adr_frn_measures_dev")
+
+
+YOY_FIELDS = ("tp", "ts", "te", "scale", "spread")       # rows of adr_yoy_risk's cpn
+YOY_PER_SWAP, YOY_AGG = 8, 16                               # ADR_YOY_PER_SWAP, ADR_YOY_AGG
+YOY_CHUNK = 16                                              # ADR_YOY_CHUNK
+YOY_MAX_PILLARS = 64
+
+
+def yoy_pack(book):
+    """``(cpn_off, cpn [len(YOY_FIELDS), m])``: the field-major arrays adr_yoy_risk reads, from a mapping with
+    ``cpn_off`` and the per-coupon fields YOY_FIELDS."""
+    off = np.ascontiguousarray(book["cpn_off"], dtype=np.int64)
+    n = off.shape[0] - 1
+    if n < 0:
+        raise LibError("cpn_off needs n_swaps + 1 entries")
+    m = int(off[-1]) if n > 0 else 0
+    cpn = np.empty((len(YOY_FIELDS), m))
+    for k, name in enumerate(YOY_FIELDS):
+        v = np.asarray(book[name], dtype=np.float64).reshape(-1)
+        if v.shape != (m,):
+            raise LibError(f"YoY array {name} has {v.size} entries, not {m}")
+        cpn[k] = v
+    return off, cpn
+
+
+def _yoy_call(fn, head, disc, infl, book, req_mask, per_swap, aggregate):
+    (dm, dt, dd), (im, T, b) = _frn_nodes(disc), _frn_nodes(infl)
+    off, cpn = yoy_pack(book)
+    n, m, P = off.shape[0] - 1, cpn.shape[1], T.size
+    mask = int(req_mask) | (YOY_PER_SWAP if per_swap else 0) | (YOY_AGG if aggregate else 0)
+    out = {"amount": np.empty(m)}
+    if per_swap:
+        out.update(pv=np.zeros(n), delta=np.zeros((n, P)), gamma=np.zeros((n, P, P)))
+    if aggregate:
+        out["agg"] = np.zeros(1 + P + P * P)
+    g = lambda k: _ptr(out.get(k))
+    _check(fn(*head, dm, dt.size, _ptr(dt), _ptr(dd), im, P, _ptr(T), _ptr(b), n, m, _ptr(off, _i64p), _ptr(cpn), mask,
+              g("amount"), g("pv"), g("delta"), g("gamma"), g("agg")), fn.__name__)
+    if aggregate:
+        a = out.pop("agg")
+        out.update(agg_pv=float(a[0]), agg_delta=a[1:1 + P].copy(), agg_gamma=a[1 + P:].reshape(P, P).copy())
+    return out
+
+
+def yoy_risk(ctx: Context, disc, infl, book, req_mask=REQ_VALUE | REQ_DELTA | REQ_GAMMA, per_swap=True, aggregate=False):
+    """Projected amounts, inflation-leg PVs and inflation-curve ladders of a YoY swap book on the GPU (adr_yoy_risk,
+    blocking).  ``disc``: ``(interp method, knot times, knot dfs)`` of the engine's discount grid; ``infl``:
+    ``(interp method, pillar times T, breakeven rates b)``; ``book``: ``cpn_off`` and the fields YOY_FIELDS.  Returns
+    ``amount`` [m], and per swap ``pv``, ``delta`` [n, P] (per bp), ``gamma`` [n, P, P] (per bp^2) and / or the book's
+    ``agg_pv``, ``agg_delta``, ``agg_gamma``."""
+    return _yoy_call(load().adr_yoy_risk, (ctx._h,), disc, infl, book, req_mask, per_swap, aggregate)
+
+
+def yoy_risk_host(disc, infl, book, req_mask=REQ_VALUE | REQ_DELTA | REQ_GAMMA, per_swap=True, aggregate=False):
+    """`yoy_risk` on the CPU (adr_yoy_risk_host): the same per-swap code and reduction order; no GPU needed."""
+    return _yoy_call(load().adr_yoy_risk_host, (), disc, infl, book, req_mask, per_swap, aggregate)
+
+
+def yoy_risk_work(n_swaps: int, n_pillars: int) -> int:
+    """Doubles of scratch `yoy_risk_dev` needs for ``YOY_AGG``."""
+    return int(load().adr_yoy_risk_work(int(n_swaps), int(n_pillars)))
+
+
+def yoy_risk_dev(ctx: Context, disc_method: int, K: int, infl_method: int, P: int, n_swaps: int, n_coupons: int, ptrs,
+                 req_mask: int, out_ptrs, stream=0):
+    """Non-blocking form (adr_yoy_risk_dev): ``ptrs`` maps ``times``, ``dfs``, ``T``, ``b``, ``cpn_off`` and ``cpn`` to
+    device pointers (integers, e.g. ``tensor.data_ptr()``); ``out_ptrs`` maps any of ``amount``, ``pv``, ``delta``,
+    ``gamma``, ``agg`` and ``work`` (`yoy_risk_work` doubles) to device pointers; ``req_mask`` includes YOY_PER_SWAP /
+    YOY_AGG as wanted."""
+    p = {k: _vp(int(ptrs[k]) or None) for k in ("times", "dfs", "T", "b", "cpn_off", "cpn")}
+    o = {k: _vp(int(out_ptrs.get(k, 0)) or None) for k in ("amount", "pv", "delta", "gamma", "agg", "work")}
+    _check(load().adr_yoy_risk_dev(ctx._h, int(disc_method), int(K), p["times"], p["dfs"], int(infl_method), int(P), p["T"],
+                                   p["b"], int(n_swaps), int(n_coupons), p["cpn_off"], p["cpn"], int(req_mask), o["amount"],
+                                   o["pv"], o["delta"], o["gamma"], o["agg"], o["work"], _vp(stream or None)),
+           "adr_yoy_risk_dev")
 
 
 _default_ctx = {}

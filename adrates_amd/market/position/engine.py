@@ -54,6 +54,11 @@ def is_frn(derivative) -> bool:
     return isinstance(derivative, FRN)
 
 
+def is_yoy(derivative) -> bool:
+    from ...trades.rates.yoy_inflation_swap import YoYInflationSwap
+    return isinstance(derivative, YoYInflationSwap)
+
+
 def frn_is_single_curve(frn) -> bool:
     """The index curve is the discount curve (the currency's OIS curve, engine.py:711-720, 749)."""
     return frn._floating_index == bond_curve_type(frn)
@@ -106,6 +111,9 @@ class Engine:
             return self._compute_bond(derivative, reqs)
         if dtype == InstrumentTypes.FRN and is_frn(derivative):
             return self._compute_frn(derivative, reqs)
+        if dtype == InstrumentTypes.YOY_INFLATION_SWAP and is_yoy(derivative):
+            from .inflation_engine import compute_yoy
+            return compute_yoy(self, derivative, reqs)
         raise LibError(f"{dtype} not yet implemented")
 
     def _compute_ois(self, derivative, reqs, collateral_type=None):

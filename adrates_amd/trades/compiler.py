@@ -173,6 +173,70 @@ def compile_frns(frns: Iterable, value_dt, index_df=None):
     return batch, f64(pv_const)
 
 
+def _yoy_check(s):
+    if getattr(s, "derivative_type", None) != InstrumentTypes.YOY_INFLATION_SWAP:
+        raise LibError(f"{getattr(s, 'derivative_type', type(s))} is not a YoY inflation swap")
+
+
+def compile_yoy_coupons(swaps: Iterable, value_dt) -> dict:
+    """Inputs of adr_yoy_risk for the inflation legs of YoY swaps, as the reference's engine extracts them
+    (cavour/market/position/engine.py:1105-1127): per coupon the payment time, the YoY start (the accrual end less 12
+    months) and the accrual end, as year fractions from ``value_dt`` in the swap's day count; ``scale`` = leg sign *
+    notional * accrual fraction; the spread.  Returns ``cpn_off`` and the fields of `_native.YOY_FIELDS`."""
+    off = [0]
+    cols = {k: [] for k in ("tp", "ts", "te", "scale", "spread")}
+    for s in swaps:
+        _yoy_check(s)
+        leg, dc = s._inflation_leg, s._fixed_leg._dc_type
+        sign = +1.0 if leg._leg_type == SwapTypes.RECEIVE else -1.0
+        cols["tp"] += _times(leg._payment_dts, value_dt, dc)
+        cols["ts"] += _times(leg._yoy_start_dts, value_dt, dc)
+        cols["te"] += _times(leg._yoy_end_dts, value_dt, dc)
+        cols["scale"] += [sign * float(leg._notional) * float(a) for a in leg._year_fracs]
+        cols["spread"] += [float(leg._spread)] * len(leg._payment_dts)
+        off.append(len(cols["tp"]))
+    out = {"cpn_off": np.array(off, dtype=np.int64)}
+    out.update({k: np.array(v, dtype=np.float64) for k, v in cols.items()})
+    return out
+
+
+def compile_yoy_swaps(swaps: Iterable, value_dt, amounts) -> TradeBatch:
+    """Fixed-flows-only batch of YoY swaps for their discount-curve Greeks: with the inflation curve held fixed the
+    reference's engine (cavour/market/position/engine.py:1129-1353) prices the fixed leg (`_price_fixed_leg_jax`,
+    payments ``coupon * alpha * notional``, principal on the last flow) and the YoY leg's projected amounts at their
+    payment times, both under the strict ``time > value time`` mask.  ``amounts`` [m]: the signed projected YoY amounts
+    in `compile_yoy_coupons` order - the ones adr_yoy_risk wrote.  Signs are folded into the amounts; flows are sorted
+    by time within a swap (stable: fixed before YoY)."""
+    amounts = np.asarray(amounts, dtype=np.float64)
+    fix_off = [0]
+    fix_tp, fix_pay, notional = [], [], []
+    c = 0
+    for s in swaps:
+        _yoy_check(s)
+        fl, leg, dc = s._fixed_leg, s._inflation_leg, s._fixed_leg._dc_type
+        sign = +1.0 if fl._leg_type == SwapTypes.RECEIVE else -1.0
+        pays = [sign * (fl._cpn * float(a) * fl._notional) for a in fl._year_fracs]
+        pays[-1] += sign * float(fl._principal)
+        k = len(leg._payment_dts)
+        if c + k > amounts.size:
+            raise LibError("fewer projected amounts than YoY coupons")
+        flows = list(zip(_times(fl._payment_dts, value_dt, dc), pays))
+        flows += list(zip(_times(leg._payment_dts, value_dt, dc), amounts[c:c + k].tolist()))
+        c += k
+        flows.sort(key=lambda x: x[0])
+        fix_tp += [t for t, _ in flows]
+        fix_pay += [a for _, a in flows]
+        fix_off.append(len(fix_tp))
+        notional.append(float(s._notional))
+    if c != amounts.size:
+        raise LibError("more projected amounts than YoY coupons")
+    n = len(notional)
+    f64 = lambda a: np.array(a, dtype=np.float64)
+    empty = np.zeros(0, dtype=np.float64)
+    return TradeBatch(np.array(fix_off, dtype=np.int64), np.zeros(n + 1, dtype=np.int64), f64(fix_tp), f64(fix_pay),
+                      empty, empty.copy(), empty.copy(), empty.copy(), f64(notional), np.zeros(n), np.ones(n), np.ones(n))
+
+
 # --------------------------------------------------------------------------------------------------------
 # Vectorised path: trades given by their economic terms, no per-trade objects
 # (SURVEY.md section 8(f) row 4).  Every Python `Date` / `Schedule` / `DayCount` call of the object path

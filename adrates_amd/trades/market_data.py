@@ -126,3 +126,61 @@ def random_frn_book(value_dt, n, seed=7, currency=CurrencyTypes.GBP):
             continue                                  # the next coupon would need the index before its value date
         frns.append(f)
     return frns, rng.uniform(-0.01, 0.04, size=n)
+
+
+# inflation: a UK RPI breakeven curve of 20 ZCIS pillars (1Y-50Y, 3.1-3.6%)
+INFL_TENORS = ["1Y", "2Y", "3Y", "4Y", "5Y", "6Y", "7Y", "8Y", "9Y", "10Y",
+               "12Y", "15Y", "20Y", "25Y", "30Y", "35Y", "40Y", "45Y", "50Y", "60Y"]
+INFL_PX = [3.10, 3.18, 3.24, 3.29, 3.33, 3.36, 3.39, 3.41, 3.43, 3.45,
+           3.47, 3.50, 3.53, 3.55, 3.56, 3.57, 3.58, 3.58, 3.59, 3.60]
+
+
+def rpi_index(value_dt=README_VALUE_DT, base_index=360.0, lag_months=3, interp=None, seasonality=None):
+    """A UK RPI index with monthly fixings for the 24 months up to ``value_dt`` (rising 0.25% a month), so that every
+    lagged YoY start of a swap starting on ``value_dt`` has a fixing."""
+    from ..market.indices.inflation_index import InflationIndex
+    from ..utils.global_types import InflationIndexTypes, InflationInterpTypes
+    idx = InflationIndex(InflationIndexTypes.UK_RPI, value_dt.add_months(-24), base_index, CurrencyTypes.GBP, lag_months,
+                         interp or InflationInterpTypes.LINEAR, seasonality)
+    for k in range(1, 25):
+        idx.add_fixing(value_dt.add_months(-24 + k), base_index * (1.0 + 0.0025 * k))
+    return idx
+
+
+def inflation_curve(value_dt=README_VALUE_DT, interp=None, tenors=None, px=None, index=None, base_cpi=380.0):
+    """The GBP RPI inflation curve from par ZCIS quotes in percent (`INFL_TENORS` / `INFL_PX` by default)."""
+    from ..market.curves.inflation_curve import InflationCurve
+    from ..utils.global_types import InflationIndexTypes, InflationInterpTypes
+    from .rates.zcis import ZeroCouponInflationSwap
+    index = index or rpi_index(value_dt)
+    swaps = [ZeroCouponInflationSwap(value_dt, t, SwapTypes.PAY, p / 100.0, index)
+             for t, p in zip(tenors or INFL_TENORS, px or INFL_PX)]
+    return InflationCurve(value_dt, swaps, base_cpi, CurrencyTypes.GBP, InflationIndexTypes.UK_RPI,
+                          interp_type=interp or InflationInterpTypes.LINEAR, check_refit=True)
+
+
+def yoy_model(value_dt=README_VALUE_DT, interp=InterpTypes.LINEAR_ZERO_RATES, infl_interp=None, **curve_kw):
+    """`gbp_model` with the RPI inflation curve put into the model's curve dict as GBP_RPI_INFLATION."""
+    m = gbp_model(value_dt, interp)
+    m._curves_dict["GBP_RPI_INFLATION"] = inflation_curve(value_dt, infl_interp, **curve_kw)
+    return m
+
+
+def random_yoy_book(value_dt, n, seed=7, index=None):
+    """``n`` YoY RPI swaps: annual coupons, 5Y-30Y, effective up to a year before to a month after ``value_dt``, pay
+    or receive fixed at 2.5-4%, notionals of 1-100 million, inflation spreads of -20 to 20bp, ACT/365F or ACT/ACT."""
+    import numpy as np
+    from .rates.yoy_inflation_swap import YoYInflationSwap
+    index = index or rpi_index(value_dt)
+    rng = np.random.default_rng(seed)
+    dcs = [DayCountTypes.ACT_365F, DayCountTypes.ACT_ACT_ISDA]
+    out = []
+    for _ in range(n):
+        eff = value_dt.add_days(int(rng.integers(-365, 31)))
+        out.append(YoYInflationSwap(eff, f"{int(rng.integers(5, 31))}Y",
+                                    SwapTypes.PAY if rng.random() < 0.5 else SwapTypes.RECEIVE,
+                                    round(float(rng.uniform(0.025, 0.04)), 5), index, FrequencyTypes.ANNUAL,
+                                    notional=float(rng.choice([1e6, 1e7, 1e8])),
+                                    inflation_spread=round(float(rng.uniform(-0.002, 0.002)), 5),
+                                    dc_type=dcs[int(rng.integers(len(dcs)))]))
+    return out

@@ -57,6 +57,21 @@ class CurveTypes(Enum):
     EUR_HICP_INFLATION = 8
 
 
+class InflationIndexTypes(Enum):
+    UK_RPI = 1
+    UK_CPI = 2
+    UK_CPIH = 3
+    US_CPI_U = 4
+    EUR_HICP = 5
+    EUR_HICP_EX = 6
+
+
+class InflationInterpTypes(Enum):
+    FLAT = 1
+    LINEAR = 2
+    COMPOUND = 3
+
+
 class CollateralType(Enum):
     USD = 1
     GBP = 2

@@ -456,6 +456,53 @@ int adr_frn_measures_host(int disc_method, int disc_n, const double* disc_t, con
                           const int64_t* cpn_off, const double* cpn, const double* frn, int quote_is_dm, double* out,
                           int32_t* status);
 
+/*
+ * Year-on-year inflation swaps: the inflation leg's projected amounts, PV and inflation-curve delta / gamma
+ * (cavour/market/position/engine.py:986-1353, `_compute_yoy_iis`, with the discount curve held fixed).
+ *
+ * The discount curve is the engine's knot grid: `disc_method` (1, 2 or 4), K (2 .. ADR_YOY_MAX_KNOTS) knot times[K]
+ * (non-decreasing, t = 0 first; repeats allowed) and dfs[K].  The inflation curve is given by its P (1 ..
+ * ADR_YOY_MAX_PILLARS) pillars: `infl_method` (ADR_INTERP_LINEAR_ZERO_RATES or ADR_INTERP_FLAT_FWD_RATES; anything else
+ * is ADR_ERR_UNSUPPORTED), times T[P] (0 < T_1 < ... ) and breakeven rates b[P]; the kernel forms the nodes (0, 1),
+ * (T_k, (1 + b_k)^T_k).  Both curves are read as InterpolatorAd.simple_interpolate reads them.
+ *
+ * Coupons in CSR form: swap i owns coupons cpn_off[i] .. cpn_off[i+1]-1 of the field-major cpn[ADR_YOY_FIELDS][m]:
+ * payment time tp, YoY start ts and end te (years from the value date), scale = leg sign * notional * accrual fraction
+ * and spread.  Per coupon, with 1 + y = I(te) / I(ts):
+ *     amount = scale * (y + spread),   PV += amount * D(tp) / D(0)  when tp > 0.
+ * Outputs (NULL where not wanted): amount[m] (always written when given), and by req_mask - ADR_REQ_VALUE / _DELTA /
+ * _GAMMA choose the measures, ADR_YOY_PER_SWAP writes per-swap rows pv[n], delta[n][P] (per bp) and gamma[n][P][P]
+ * (per bp^2, dense, row-major), ADR_YOY_AGG writes agg[1 + P + P*P] = [pv, delta[P], gamma[P*P]] of the whole book.
+ * agg is a fixed-order sum of the per-swap rows: swaps in chunks of ADR_YOY_CHUNK summed in order, then chunk j added
+ * to lane j % 64 in order, then lanes 0-31 += 32-63, 0-15 += 16-31, ..., 0 += 1.  Results are bit-identical from run to run and do
+ * not depend on the launch shape or the batch; adr_yoy_risk_host runs the same per-swap code and order on the CPU.
+ */
+#define ADR_YOY_FIELDS 5
+#define ADR_YOY_TP 0
+#define ADR_YOY_TS 1
+#define ADR_YOY_TE 2
+#define ADR_YOY_SCALE 3
+#define ADR_YOY_SPREAD 4
+#define ADR_YOY_MAX_KNOTS 4096
+#define ADR_YOY_MAX_PILLARS 64
+#define ADR_YOY_CHUNK 16
+#define ADR_YOY_PER_SWAP 8u
+#define ADR_YOY_AGG 16u
+int adr_yoy_risk(adr_ctx* ctx, int disc_method, int K, const double* times, const double* dfs, int infl_method, int P,
+                 const double* T, const double* b, int64_t n, int64_t m, const int64_t* cpn_off, const double* cpn,
+                 uint32_t req_mask, double* amount, double* pv, double* delta, double* gamma, double* agg);
+/* Doubles of scratch adr_yoy_risk_dev needs for ADR_YOY_AGG: ceil(n / ADR_YOY_CHUNK) * (1 + P + P*P). */
+int64_t adr_yoy_risk_work(int64_t n, int P);
+/* The same with every array in device memory (work: adr_yoy_risk_work doubles, or NULL without ADR_YOY_AGG),
+ * enqueued on `stream` (NULL: the ctx's stream); no allocation, no synchronisation; only the scalars are checked. */
+int adr_yoy_risk_dev(adr_ctx* ctx, int disc_method, int K, const double* times, const double* dfs, int infl_method, int P,
+                     const double* T, const double* b, int64_t n, int64_t m, const int64_t* cpn_off, const double* cpn,
+                     uint32_t req_mask, double* amount, double* pv, double* delta, double* gamma, double* agg,
+                     double* work, void* stream);
+int adr_yoy_risk_host(int disc_method, int K, const double* times, const double* dfs, int infl_method, int P,
+                      const double* T, const double* b, int64_t n, int64_t m, const int64_t* cpn_off, const double* cpn,
+                      uint32_t req_mask, double* amount, double* pv, double* delta, double* gamma, double* agg);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
