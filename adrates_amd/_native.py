@@ -92,6 +92,14 @@ _SIGNATURES = {
                                    C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "adr_yoy_risk_host": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int64, _i64p, _dp,
                                     C.c_uint32, _dp, _dp, _dp, _dp, _dp]),
+    "adr_scenario_pv": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _vp, _dp, _dp]),
+    "adr_scenario_pv_work": (C.c_int64, [C.c_int64, C.c_int]),
+    "adr_scenario_pv_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "adr_scenario_pv_set": (C.c_int, [_vp, _vp, _vp, _dp, _dp]),
+    "adr_curve_set_arrays": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_vp),
+                                       C.POINTER(_vp)]),
+    "adr_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int64, _i64p, _i64p] + [_dp] * 11 +
+                             [_dp, _dp, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -725,6 +733,94 @@ def yoy_risk_dev(ctx: Context, disc_method: int, K: int, infl_method: int, P: in
                                    p["b"], int(n_swaps), int(n_coupons), p["cpn_off"], p["cpn"], int(req_mask), o["amount"],
                                    o["pv"], o["delta"], o["gamma"], o["agg"], o["work"], _vp(stream or None)),
            "adr_yoy_risk_dev")
+
+
+SCENARIO_CHUNK = 64                                         # ADR_SCENARIO_CHUNK
+SCENARIO_MAX_KNOTS = 4096
+
+
+def _scenario_curves(times, dfs):
+    times = _f64(times).reshape(-1)
+    dfs = _f64(np.atleast_2d(dfs))
+    if dfs.ndim != 2 or dfs.shape[1] != times.size:
+        raise LibError(f"dfs must have shape [n_scenarios, {times.size}] (one row per scenario, one column per knot), "
+                       f"not {list(dfs.shape)}")
+    return times, dfs
+
+
+def _scenario_result(book, pv, per_trade):
+    out = {"book_pv": book}
+    if per_trade:
+        out["pv"] = pv.T                # the library's rows are per trade ([n, S]); a view, no copy
+    return out
+
+
+def scenario_pv(ctx: Context, method: int, times, dfs, trades: DeviceTrades, per_trade=False):
+    """PVs of an uploaded batch under the scenario curves ``dfs [S, K]`` on the knots ``times [K]`` (adr_scenario_pv,
+    blocking): ``book_pv [S]`` and, with ``per_trade``, ``pv [S, n]``."""
+    times, dfs = _scenario_curves(times, dfs)
+    S, n = dfs.shape[0], trades.n_trades
+    book = np.empty(S)
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_scenario_pv(ctx._h, int(method), times.size, _ptr(times), S, _ptr(dfs), trades._h, _ptr(pv),
+                                  _ptr(book)), "adr_scenario_pv")
+    return _scenario_result(book, pv, per_trade)
+
+
+def scenario_pv_host(method: int, times, dfs, batch, per_trade=False, n_threads=0):
+    """`scenario_pv` on the CPU (adr_scenario_pv_host) for a `TradeBatch`: the same per-trade arithmetic and the same
+    order of the book sum; no GPU needed."""
+    times, dfs = _scenario_curves(times, dfs)
+    S, n = dfs.shape[0], int(batch.n_trades)
+    fo = np.ascontiguousarray(batch.fix_off, dtype=np.int64)
+    lo = np.ascontiguousarray(batch.flt_off, dtype=np.int64)
+    if fo.shape != (n + 1,) or lo.shape != (n + 1,):
+        raise LibError("offset arrays must have n_trades + 1 entries")
+    a = {k: _f64(getattr(batch, k)) for k in ("fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional",
+                                              "spread", "fix_sign", "flt_sign")}
+    w = getattr(batch, "flt_weight", None)
+    w = None if w is None else _f64(w)
+    if w is not None and w.shape != a["flt_tp"].shape:
+        raise LibError("flt_weight must have one entry per float coupon")
+    book = np.empty(S)
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_scenario_pv_host(int(method), times.size, _ptr(times), S, _ptr(dfs), n, _ptr(fo, _i64p), _ptr(lo, _i64p),
+                                       _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]), _ptr(a["flt_ts"]),
+                                       _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w), _ptr(a["notional"]), _ptr(a["spread"]),
+                                       _ptr(a["fix_sign"]), _ptr(a["flt_sign"]), _ptr(pv), _ptr(book), int(n_threads)),
+           "adr_scenario_pv_host")
+    return _scenario_result(book, pv, per_trade)
+
+
+def scenario_pv_set(ctx: Context, curve_set: CurveSet, trades: DeviceTrades, per_trade=False):
+    """`scenario_pv` on the curves of a `CurveSet`, read where the device builder left them (adr_scenario_pv_set)."""
+    S, n = len(curve_set), trades.n_trades
+    book = np.empty(S)
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_scenario_pv_set(ctx._h, curve_set._h, trades._h, _ptr(pv), _ptr(book)), "adr_scenario_pv_set")
+    return _scenario_result(book, pv, per_trade)
+
+
+def curve_set_arrays(curve_set: CurveSet) -> dict:
+    """``method``, ``K``, ``S`` and the device pointers ``times`` [K] and ``dfs`` [S, K] of a set (adr_curve_set_arrays)."""
+    m, K, S, t, d = C.c_int(), C.c_int(), C.c_int(), _vp(), _vp()
+    _check(load().adr_curve_set_arrays(curve_set._h, C.byref(m), C.byref(K), C.byref(S), C.byref(t), C.byref(d)),
+           "adr_curve_set_arrays")
+    return dict(method=m.value, K=K.value, S=S.value, times=t.value or 0, dfs=d.value or 0)
+
+
+def scenario_pv_work(n_trades: int, n_scenarios: int) -> int:
+    """Doubles of scratch `scenario_pv_dev` needs."""
+    return int(load().adr_scenario_pv_work(int(n_trades), int(n_scenarios)))
+
+
+def scenario_pv_dev(ctx: Context, method: int, K: int, times_ptr: int, S: int, dfs_ptr: int, trades: DeviceTrades,
+                    book_ptr: int, work_ptr: int, pv_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_scenario_pv_dev): device pointers (integers) of ``times`` [K], ``dfs`` [S, K], the outputs
+    ``book_pv`` [S] and ``pv`` [n, S] (trade-major; 0: not wanted) and `scenario_pv_work` doubles of scratch."""
+    v = lambda p: _vp(int(p) or None)
+    _check(load().adr_scenario_pv_dev(ctx._h, int(method), int(K), v(times_ptr), int(S), v(dfs_ptr), trades._h, v(pv_ptr),
+                                      v(book_ptr), v(work_ptr), _vp(stream or None)), "adr_scenario_pv_dev")
 
 
 _default_ctx = {}

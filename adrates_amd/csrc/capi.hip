@@ -147,6 +147,28 @@ int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream) {
     return ADR_OK;
 }
 
+// what scenario_pv.hip needs of the opaque handles: the ctx's compute units, a batch's device arrays and a curve set's
+// dense arrays (knot times [K], discount factors [S][K])
+int adr_ctx_compute_units(const adr_ctx* ctx) { return ctx ? ctx->n_cu : 0; }
+
+const adr::TradesDev* adr_trades_device_view(const adr_trades* trades, const adr_ctx** owner) {
+    if (!trades) return nullptr;
+    *owner = trades->ctx;
+    return &trades->dev;
+}
+
+int adr_curve_set_device_view(const adr_curve_set* set, const adr_ctx** owner, int* method, int* K, int* S,
+                              const double** times_dev, const double** dfs_dev) {
+    if (!set || !set->plan) return fail(ADR_ERR_INVALID, "null curve set");
+    *owner = set->ctx;
+    *method = set->plan->interp;
+    *K = set->plan->base.K;
+    *S = set->n;
+    *times_dev = set->plan->shared.x;
+    *dfs_dev = set->dfs;
+    return ADR_OK;
+}
+
 extern "C" {
 
 int adr_version(void) { return 100; }

@@ -1,0 +1,577 @@
+// Scenario revaluation: the PV of every trade of a batch under S discount curves that share one knot grid
+// (adr_scenario_pv*; declarations, semantics and the order of the book sum: include/adrates.h).
+//
+// pv[i][s] is what adr_price(VALUE) returns for trade i on the curve (times, dfs[s]): the fixed flows
+// fix_sign * pay * D_s(tp) and the float coupons flt_sign * N * w * ((D_s(ts) / D_s(te) - 1) + spread * alpha) * D_s(tp),
+// D_s(t) being InterpolatorAd.simple_interpolate (simple_interp.hpp).  No rates and no Jacobians are involved.
+//
+// Layout: one lane = one scenario, one wave = 64 scenarios (a "group"); a block is kWaves waves of ONE group that share
+// the group's knot table in LDS as tab[k][lane] (ln d under the log-linear schemes, d under LINEAR_FWD_RATES), so a lane
+// reads consecutive doubles and a knot costs one conflict-free ds_read_b64.  The trades are cut into chunks of
+// ADR_SCENARIO_CHUNK consecutive trades; a wave takes chunks round-robin and walks each in trade order.
+//
+// Everything about a date that does not depend on the scenario is computed once per wave.  The knot search is not
+// done by a scalar loop per date (nine dependent LDS reads each) but lane-parallel: lane l describes coupon l of the
+// trade - the segment searches of its dates (si::log_weights / si::locate), the two knot indices and weights - and marks
+// the dates that need no evaluation of their own: an accrual start equal to the previous coupon's accrual end, a payment
+// time equal to the accrual end (no payment lag), a fixed payment time equal to the float payment time of the same
+// index.  The wave then walks the coupons in order, fetching coupon j's description from lane j with v_readlane (into
+// scalar registers: every branch on it is uniform), and each lane evaluates D_s at the dates that are left: one exp of
+// wa * L[a] + wb * L[b] per DISTINCT date under the log schemes, none under LINEAR_FWD_RATES.  An OIS with m annual
+// coupons on both legs costs m + 1 exponentials per scenario instead of 3 m.
+//
+// The book sum: a lane adds its chunk's trades in trade order in a register and writes work[chunk][s]; a second kernel
+// adds the chunks in a fixed order (chunk j to slot j % 64 in order, then a halving tree).  No atomics.  The host twin
+// (adr_scenario_pv_host) runs the same per-date and per-coupon code in the same order on CPU threads.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/adrates.h"
+#include "host_pool.hpp"
+#include "kernels.hpp"
+#include "simple_interp.hpp"
+
+int adr_set_error(int status, const std::string& msg);                          // capi.hip
+int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
+int adr_ctx_compute_units(const adr_ctx* ctx);                                  // capi.hip
+const adr::TradesDev* adr_trades_device_view(const adr_trades* trades, const adr_ctx** owner);              // capi.hip
+int adr_curve_set_device_view(const adr_curve_set* set, const adr_ctx** owner, int* method, int* K, int* S,
+                              const double** times_dev, const double** dfs_dev);                            // capi.hip
+
+// The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
+// exp / log implementations.
+#pragma clang fp contract(off)
+
+namespace adr {
+namespace scen {
+
+constexpr int kWave = 64;
+constexpr int kWaves = 16;                      // waves per block: four per SIMD, all on one scenario group
+constexpr int kThreads = kWave * kWaves;
+constexpr int kChunk = ADR_SCENARIO_CHUNK;      // trades per partial sum of the book
+constexpr int kRedLanes = 64;                   // the book reduction's slots per scenario
+constexpr int kRedEntries = 16;                 // scenarios per reduction block
+constexpr size_t kLdsBudget = 160 * 1024;
+
+// D(t) in weight form on the scenario's table T (T_k = ln d_k when kLog, else d_k):
+//   kLog:  ln D = wa T_a + (b != a ? wb T_b : 0);      else:  D = T_a + (b != a ? wb (T_b - T_a) : 0).
+struct DateW {
+    int a, b;
+    double wa, wb;
+};
+
+template <bool kLog>
+__host__ __device__ inline DateW date_weights(double t, const double* x, int K, int method) {
+    DateW d;
+    if (kLog) {
+        const si::LogWeights w = si::log_weights(t, x, K, method);
+        d.a = w.a; d.b = w.b; d.wa = w.wa; d.wb = w.wb;
+    } else {
+        const si::Where p = si::locate(t, x, K);
+        d.a = p.lo; d.b = p.hi; d.wa = 1.0; d.wb = p.w;
+    }
+    return d;
+}
+
+template <bool kLog, class Tab>
+__host__ __device__ inline double eval_df(const DateW& d, const Tab& tab) {
+    const double la = tab(d.a);
+    if (kLog) {
+        double s = d.wa * la;
+        if (d.b != d.a) s = s + d.wb * tab(d.b);
+        return exp(s);
+    }
+    double f = la;
+    if (d.b != d.a) f = la + d.wb * (tab(d.b) - la);
+    return f;
+}
+
+// Coupon index c of a trade: its float coupon (c < n_flt) and its fixed flow (c < n_fix).  The masks are adr_price's
+// (the reference engine's): a float coupon counts when tp >= 0 and has no forward when alpha <= 0, a fixed flow counts
+// when tp > 0.
+enum : int {
+    kHasFlt = 1, kHasFix = 2,
+    kTsIsPrevTe = 4,     // accrual start == the previous coupon's accrual end: D(ts) is the D(te) just computed
+    kTpIsTe = 8,         // no payment lag: D(tp) is D(te)
+    kFixIsFltTp = 16,    // the fixed flow is paid with the float coupon: D is D(tp)
+    kNoAccrual = 32      // alpha <= 0: the coupon is spread * alpha * D(tp)
+};
+
+struct Slot {
+    int flags;
+    DateW ws, we, wp, wx;
+    double sa, w, pay;   // spread * alpha, the coupon's notional multiplier, the fixed amount
+};
+
+struct Legs {            // one trade's cash flows
+    const double *fix_tp, *fix_pay, *flt_tp, *flt_ts, *flt_te, *flt_alpha, *flt_weight;
+    int64_t f0, l0;
+    int n_fix, n_flt;
+    double spread;
+};
+
+template <bool kLog>
+__host__ __device__ inline Slot make_slot(const Legs& g, int c, const double* x, int K, int method) {
+    Slot s;
+    s.flags = 0;
+    s.ws = s.we = s.wp = s.wx = DateW{0, 0, 0.0, 0.0};
+    s.sa = 0.0; s.w = 1.0; s.pay = 0.0;
+    double tp = 0.0;
+    bool flt = false;
+    if (c < g.n_flt) {
+        const int64_t i = g.l0 + c;
+        tp = g.flt_tp[i];
+        flt = tp >= 0.0;
+    }
+    if (flt) {
+        const int64_t i = g.l0 + c;
+        const double ts = g.flt_ts[i], te = g.flt_te[i], al = g.flt_alpha[i];
+        s.flags |= kHasFlt;
+        s.sa = g.spread * al;
+        if (g.flt_weight) s.w = g.flt_weight[i];
+        if (al > 0.0) {
+            // the previous coupon left its D(te) behind when it counted and accrued
+            if (c > 0 && ts == g.flt_te[i - 1] && g.flt_tp[i - 1] >= 0.0 && g.flt_alpha[i - 1] > 0.0) s.flags |= kTsIsPrevTe;
+            else s.ws = date_weights<kLog>(ts, x, K, method);
+            s.we = date_weights<kLog>(te, x, K, method);
+            if (tp == te) s.flags |= kTpIsTe;
+            else s.wp = date_weights<kLog>(tp, x, K, method);
+        } else {
+            s.flags |= kNoAccrual;
+            s.wp = date_weights<kLog>(tp, x, K, method);
+        }
+    }
+    if (c < g.n_fix) {
+        const int64_t i = g.f0 + c;
+        const double xt = g.fix_tp[i];
+        if (xt > 0.0) {
+            s.flags |= kHasFix;
+            s.pay = g.fix_pay[i];
+            if (flt && xt == tp) s.flags |= kFixIsFltTp;
+            else s.wx = date_weights<kLog>(xt, x, K, method);
+        }
+    }
+    return s;
+}
+
+struct Acc {             // one scenario's running state inside a trade
+    double de, flt, fix; // D(te) of the previous coupon; the legs' sums before sign and notional
+};
+
+template <bool kLog, class Tab>
+__host__ __device__ inline void apply_slot(const Slot& s, bool weighted, const Tab& tab, Acc& a) {
+    double dp = 0.0;
+    if (s.flags & kHasFlt) {
+        double term;
+        if (s.flags & kNoAccrual) {
+            dp = eval_df<kLog>(s.wp, tab);
+            term = s.sa * dp;
+        } else {
+            const double ds = (s.flags & kTsIsPrevTe) ? a.de : eval_df<kLog>(s.ws, tab);
+            const double de = eval_df<kLog>(s.we, tab);
+            dp = (s.flags & kTpIsTe) ? de : eval_df<kLog>(s.wp, tab);
+            term = ((ds / de - 1.0) + s.sa) * dp;
+            a.de = de;
+        }
+        if (weighted) term = s.w * term;
+        a.flt = a.flt + term;
+    }
+    if (s.flags & kHasFix) {
+        const double dx = (s.flags & kFixIsFltTp) ? dp : eval_df<kLog>(s.wx, tab);
+        a.fix = a.fix + s.pay * dx;
+    }
+}
+
+__host__ __device__ inline double trade_pv(const Acc& a, double fix_sign, double flt_sign, double notional) {
+    return fix_sign * a.fix + (flt_sign * notional) * a.flt;
+}
+
+// book[s] = sum over the chunk rows of entry s: chunk j to slot j % 64 in order, then slots 0-31 += 32-63, ..., 0 += 1.
+void reduce_chunks(const double* work, int64_t chunks, int64_t S, double* book) {
+    for (int64_t e = 0; e < S; ++e) {
+        double p[kRedLanes];
+        for (int cl = 0; cl < kRedLanes; ++cl) {
+            p[cl] = 0.0;
+            for (int64_t j = cl; j < chunks; j += kRedLanes) p[cl] = p[cl] + work[j * S + e];
+        }
+        for (int h = kRedLanes / 2; h >= 1; h >>= 1)
+            for (int cl = 0; cl < h; ++cl) p[cl] = p[cl] + p[cl + h];
+        book[e] = p[0];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ device
+struct Args {
+    TradesDev tr;
+    const double *times, *dfs;       // [K], [S][K]
+    int K, S, method;
+    int64_t n_chunks;
+    double *pv, *work;               // [n][S] or null; [n_chunks][S]
+};
+
+__device__ inline int lane_int(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
+__device__ inline double lane_dbl(double v, int j) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+__device__ inline DateW lane_date(const DateW& d, int j) {
+    DateW r;
+    r.a = lane_int(d.a, j);
+    r.b = lane_int(d.b, j);
+    r.wa = lane_dbl(d.wa, j);
+    r.wb = r.b != r.a ? lane_dbl(d.wb, j) : 0.0;
+    return r;
+}
+
+// Lane j's slot in scalar registers; only the parts its flags say will be read.
+__device__ inline Slot lane_slot(const Slot& m, int j, bool weighted) {
+    Slot u;
+    u.flags = lane_int(m.flags, j);
+    u.ws = u.we = u.wp = u.wx = DateW{0, 0, 0.0, 0.0};
+    u.sa = 0.0; u.w = 1.0; u.pay = 0.0;
+    if (u.flags & kHasFlt) {
+        if (!(u.flags & kNoAccrual)) {
+            if (!(u.flags & kTsIsPrevTe)) u.ws = lane_date(m.ws, j);
+            u.we = lane_date(m.we, j);
+        }
+        if (!(u.flags & kTpIsTe)) u.wp = lane_date(m.wp, j);
+        u.sa = lane_dbl(m.sa, j);
+        if (weighted) u.w = lane_dbl(m.w, j);
+    }
+    if (u.flags & kHasFix) {
+        if (!(u.flags & kFixIsFltTp)) u.wx = lane_date(m.wx, j);
+        u.pay = lane_dbl(m.pay, j);
+    }
+    return u;
+}
+
+// kLds: the group's table sits in LDS; otherwise (K too large) every lane reads its scenario's row of dfs.
+template <bool kLog, bool kLds>
+struct DevTab {
+    const double* p;     // kLds: &tab[0][lane]; else &dfs[s][0]
+    __device__ double operator()(int k) const {
+        if (kLds) return p[k * kWave];
+        return kLog ? log(p[k]) : p[k];
+    }
+};
+
+template <bool kLog, bool kLds>
+__global__ __launch_bounds__(kThreads) void scenario_pv_kernel(Args a) {
+    extern __shared__ double lds[];
+    double* s_x = lds;                               // [K]
+    double* s_tab = lds + a.K;                       // [K][64] (kLds)
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int K = a.K, S = a.S;
+    const int64_t s = static_cast<int64_t>(blockIdx.y) * kWave + lane;
+    const bool live = s < S;
+    const double* row = a.dfs + (live ? s : S - 1) * K;     // padding lanes price the last scenario and store nothing
+    for (int k = threadIdx.x; k < K; k += kThreads) s_x[k] = a.times[k];
+    if (kLds)
+        for (int k = wave; k < K; k += kWaves) s_tab[k * kWave + lane] = kLog ? log(row[k]) : row[k];
+    __syncthreads();
+    const DevTab<kLog, kLds> tab{kLds ? s_tab + lane : row};
+    const bool weighted = a.tr.flt_weight != nullptr;
+    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < a.n_chunks;
+         ch += static_cast<int64_t>(gridDim.x) * kWaves) {
+        const int64_t i1 = ch * kChunk + kChunk < a.tr.n ? ch * kChunk + kChunk : a.tr.n;
+        double book = 0.0;
+        for (int64_t i = ch * kChunk; i < i1; ++i) {
+            const TradeHeader h = a.tr.header[i];           // uniform: scalar loads
+            const Legs g{a.tr.fix_tp, a.tr.fix_pay, a.tr.flt_tp, a.tr.flt_ts, a.tr.flt_te, a.tr.flt_alpha, a.tr.flt_weight,
+                         h.fix_begin, h.flt_begin, h.n_fix, h.n_flt, h.spread};
+            const int m = h.n_fix > h.n_flt ? h.n_fix : h.n_flt;
+            Acc acc{0.0, 0.0, 0.0};
+            for (int base = 0; base < m; base += kWave) {
+                const int cnt = m - base < kWave ? m - base : kWave;
+                Slot mine;
+                mine.flags = 0;
+                mine.ws = mine.we = mine.wp = mine.wx = DateW{0, 0, 0.0, 0.0};
+                mine.sa = 0.0; mine.w = 1.0; mine.pay = 0.0;
+                if (lane < cnt) mine = make_slot<kLog>(g, base + lane, s_x, K, a.method);
+                for (int j = 0; j < cnt; ++j) apply_slot<kLog>(lane_slot(mine, j, weighted), weighted, tab, acc);
+            }
+            const double pv = trade_pv(acc, static_cast<double>(h.fix_sign), static_cast<double>(h.flt_sign), h.notional);
+            if (a.pv && live) a.pv[i * S + s] = pv;
+            book = book + pv;
+        }
+        if (live) a.work[ch * S + s] = book;
+    }
+}
+
+// book[e] = the fixed-order sum of the chunk rows (reduce_chunks above is its host form).
+__global__ __launch_bounds__(kRedLanes * kRedEntries) void scenario_book_kernel(const double* work, int64_t chunks, int64_t S,
+                                                                                double* book) {
+    __shared__ double sh[kRedLanes][kRedEntries];
+    const int ei = threadIdx.x % kRedEntries, cl = threadIdx.x / kRedEntries;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kRedEntries + ei;
+    double acc = 0.0;
+    if (e < S) {
+#pragma unroll 8
+        for (int64_t j = cl; j < chunks; j += kRedLanes) acc = acc + work[j * S + e];
+    }
+    sh[cl][ei] = acc;
+    __syncthreads();
+    for (int h = kRedLanes / 2; h >= 1; h >>= 1) {
+        if (cl < h) sh[cl][ei] = sh[cl][ei] + sh[cl + h][ei];
+        __syncthreads();
+    }
+    if (cl == 0 && e < S) book[e] = sh[0][ei];
+}
+
+// -------------------------------------------------------------------------------------------------------------- host
+inline size_t lds_bytes(int K, bool table) { return (static_cast<size_t>(K) + (table ? static_cast<size_t>(K) * kWave : 0)) * sizeof(double); }
+
+int validate(const std::string& w, int method, int K, int S, int64_t n, const void* times, const void* dfs, const void* book) {
+    if (method != ADR_INTERP_FLAT_FWD_RATES && method != ADR_INTERP_LINEAR_FWD_RATES && method != ADR_INTERP_LINEAR_ZERO_RATES)
+        return adr_set_error(ADR_ERR_INVALID, w + ": the scheme must be FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) or "
+                                                  "LINEAR_ZERO_RATES (4)");
+    if (K < 2 || K > ADR_SCENARIO_MAX_KNOTS)
+        return adr_set_error(ADR_ERR_INVALID, w + ": the knot grid needs 2 .. ADR_SCENARIO_MAX_KNOTS (4096) knots");
+    if (S < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one scenario is needed");
+    if (n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
+    if (!times || !dfs) return adr_set_error(ADR_ERR_INVALID, w + ": null curve arrays");
+    if (!book) return adr_set_error(ADR_ERR_INVALID, w + ": book_pv is NULL");
+    return ADR_OK;
+}
+
+int check_curves(const std::string& w, int K, const double* times, int S, const double* dfs) {
+    for (int k = 0; k < K; ++k)
+        if (!std::isfinite(times[k]) || (k > 0 && times[k] < times[k - 1]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": knot times must be finite and non-decreasing");
+    for (int64_t i = 0; i < static_cast<int64_t>(S) * K; ++i)
+        if (!(dfs[i] > 0.0) || !std::isfinite(dfs[i]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": discount factors must be positive and finite (scenario " +
+                                                      std::to_string(i / K) + ", knot " + std::to_string(i % K) + ")");
+    return ADR_OK;
+}
+
+template <bool kLog, bool kLds>
+hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
+    const size_t lds = lds_bytes(a.K, kLds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scenario_pv_kernel<kLog, kLds>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((scenario_pv_kernel<kLog, kLds>), grid, dim3(kThreads), lds, stream, a);
+    return hipGetLastError();
+}
+
+// The two kernels on `stream`; every pointer is device memory.
+int enqueue(const std::string& w, adr_ctx* ctx, int method, int K, const double* times, int S, const double* dfs,
+            const adr_trades* trades, double* pv, double* book, double* work, hipStream_t stream_or_null) {
+    const adr_ctx* owner = nullptr;
+    const TradesDev* tr = adr_trades_device_view(trades, &owner);
+    if (!tr) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
+    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, w + ": the trades belong to another ctx");
+    int rc = validate(w, method, K, S, tr->n, times, dfs, book);
+    if (rc != ADR_OK) return rc;
+    if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_scenario_pv_work doubles are needed)");
+    int device = 0;
+    hipStream_t stream = nullptr;
+    rc = adr_ctx_target(ctx, &device, &stream);
+    if (rc != ADR_OK) return rc;
+    if (stream_or_null) stream = stream_or_null;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    const int64_t chunks = (tr->n + kChunk - 1) / kChunk, groups = (static_cast<int64_t>(S) + kWave - 1) / kWave;
+    if (groups > 65535) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 65535 * 64 scenarios in one launch");
+    // one block per compute unit when the table fills the LDS; a group's blocks share its chunks round-robin
+    const int64_t per_group = std::max<int64_t>(1, (adr_ctx_compute_units(ctx) + groups - 1) / groups);
+    const int64_t bx = std::min<int64_t>((chunks + kWaves - 1) / kWaves, per_group);
+    const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(groups));
+    const Args a{*tr, times, dfs, K, S, method, chunks, pv, work};
+    const bool in_lds = lds_bytes(K, true) <= kLdsBudget;
+    const bool lin = method == ADR_INTERP_LINEAR_FWD_RATES;
+    if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
+    else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(scenario_book_kernel, dim3(static_cast<unsigned>((S + kRedEntries - 1) / kRedEntries)),
+                           dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(S), book);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+// Blocking form: outputs and scratch in one device allocation; the curves are copied in when they are host arrays.
+int run_blocking(const std::string& w, adr_ctx* ctx, int method, int K, const double* times, int S, const double* dfs,
+                 bool curves_on_host, const adr_trades* trades, double* pv, double* book) {
+    const int64_t n = adr_trades_count(trades);
+    int rc = validate(w, method, K, S, trades ? n : 1, times, dfs, book);
+    if (rc == ADR_OK && curves_on_host) rc = check_curves(w, K, times, S, dfs);
+    if (rc != ADR_OK) return rc;
+    if (!trades) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
+    int device = 0;
+    hipStream_t stream = nullptr;
+    rc = adr_ctx_target(ctx, &device, &stream);
+    if (rc != ADR_OK) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    const size_t d = sizeof(double), SK = static_cast<size_t>(S) * K, W = static_cast<size_t>(adr_scenario_pv_work(n, S));
+    const size_t n_dbl = (curves_on_host ? K + SK : 0) + (pv ? static_cast<size_t>(n) * S : 0) + S + W;
+    double* base = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double* p = base;
+    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
+    const double *dt = times, *ddf = dfs;
+    if (curves_on_host) {
+        double *ht = take(K), *hd = take(SK);
+        e = hipMemcpyAsync(ht, times, K * d, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hd, dfs, SK * d, hipMemcpyHostToDevice, stream);
+        dt = ht; ddf = hd;
+    }
+    double* dpv = pv ? take(static_cast<size_t>(n) * S) : nullptr;
+    double *dbook = take(S), *dwork = take(W);
+    if (e == hipSuccess) rc = enqueue(w, ctx, method, K, dt, S, ddf, trades, dpv, dbook, dwork, stream);
+    if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, static_cast<size_t>(n) * S * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, S * d, hipMemcpyDeviceToHost, stream);
+    const hipError_t es = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = es;
+    const hipError_t ef = hipFree(base);
+    if (rc != ADR_OK) return rc;
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+struct HostTab {
+    const double* p;     // the scenario's row of the converted table
+    double operator()(int k) const { return p[k]; }
+};
+
+template <bool kLog>
+void host_chunks(int method, int K, const double* times, int S, const double* tab, int64_t n, const int64_t* fix_off,
+                 const int64_t* flt_off, const Legs& arrays, const double* notional, const double* spread,
+                 const double* fix_sign, const double* flt_sign, double* pv, double* work, int64_t lo, int64_t hi) {
+    std::vector<Acc> acc(static_cast<size_t>(S));
+    std::vector<double> book(static_cast<size_t>(S));
+    const bool weighted = arrays.flt_weight != nullptr;
+    for (int64_t ch = lo; ch < hi; ++ch) {
+        std::fill(book.begin(), book.end(), 0.0);
+        for (int64_t i = ch * kChunk; i < std::min(n, (ch + 1) * kChunk); ++i) {
+            Legs g = arrays;
+            g.f0 = fix_off[i]; g.l0 = flt_off[i];
+            g.n_fix = static_cast<int>(fix_off[i + 1] - fix_off[i]);
+            g.n_flt = static_cast<int>(flt_off[i + 1] - flt_off[i]);
+            g.spread = spread[i];
+            std::fill(acc.begin(), acc.end(), Acc{0.0, 0.0, 0.0});
+            for (int c = 0; c < std::max(g.n_fix, g.n_flt); ++c) {
+                const Slot slot = make_slot<kLog>(g, c, times, K, method);
+                for (int s = 0; s < S; ++s) apply_slot<kLog>(slot, weighted, HostTab{tab + static_cast<size_t>(s) * K}, acc[s]);
+            }
+            for (int s = 0; s < S; ++s) {
+                const double v = trade_pv(acc[s], fix_sign[i], flt_sign[i], notional[i]);
+                if (pv) pv[i * S + s] = v;
+                book[s] = book[s] + v;
+            }
+        }
+        std::copy(book.begin(), book.end(), work + ch * S);
+    }
+}
+
+}  // namespace scen
+}  // namespace adr
+
+namespace SC = adr::scen;
+
+extern "C" {
+
+int64_t adr_scenario_pv_work(int64_t n, int S) {
+    if (n < 1 || S < 1) return 0;
+    return (n + SC::kChunk - 1) / SC::kChunk * S;
+}
+
+int adr_scenario_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S, const double* dfs_dev,
+                        const adr_trades* trades, double* pv_dev, double* book_pv_dev, double* work_dev, void* stream) {
+    return SC::enqueue("adr_scenario_pv_dev", ctx, interp_method, K, times_dev, S, dfs_dev, trades, pv_dev, book_pv_dev, work_dev,
+                       static_cast<hipStream_t>(stream));
+}
+
+int adr_scenario_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S, const double* dfs,
+                    const adr_trades* trades, double* pv, double* book_pv) {
+    return SC::run_blocking("adr_scenario_pv", ctx, interp_method, K, times, S, dfs, true, trades, pv, book_pv);
+}
+
+int adr_curve_set_arrays(const adr_curve_set* set, int* interp_method, int* K, int* S, const double** times_dev,
+                         const double** dfs_dev) {
+    const adr_ctx* owner = nullptr;
+    int m = 0, k = 0, s = 0;
+    const double *t = nullptr, *d = nullptr;
+    const int rc = adr_curve_set_device_view(set, &owner, &m, &k, &s, &t, &d);
+    if (rc != ADR_OK) return rc;
+    if (interp_method) *interp_method = m;
+    if (K) *K = k;
+    if (S) *S = s;
+    if (times_dev) *times_dev = t;
+    if (dfs_dev) *dfs_dev = d;
+    return ADR_OK;
+}
+
+int adr_scenario_pv_set(adr_ctx* ctx, const adr_curve_set* set, const adr_trades* trades, double* pv, double* book_pv) {
+    const adr_ctx* owner = nullptr;
+    int method = 0, K = 0, S = 0;
+    const double *t = nullptr, *d = nullptr;
+    const int rc = adr_curve_set_device_view(set, &owner, &method, &K, &S, &t, &d);
+    if (rc != ADR_OK) return rc;
+    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, "adr_scenario_pv_set: the curve set belongs to another ctx");
+    return SC::run_blocking("adr_scenario_pv_set", ctx, method, K, t, S, d, false, trades, pv, book_pv);
+}
+
+int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
+                         const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                         const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                         const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                         const double* flt_sign, double* pv, double* book_pv, int n_threads) {
+    const std::string w = "adr_scenario_pv_host";
+    int rc = SC::validate(w, interp_method, K, S, n, times, dfs, book_pv);
+    if (rc == ADR_OK) rc = SC::check_curves(w, K, times, S, dfs);
+    if (rc != ADR_OK) return rc;
+    if (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign)
+        return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
+    if (fix_off[0] != 0 || flt_off[0] != 0) return adr_set_error(ADR_ERR_INVALID, w + ": offsets must start at 0");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t mf = fix_off[i + 1] - fix_off[i], ml = flt_off[i + 1] - flt_off[i];
+        if (mf < 0 || ml < 0 || mf > INT16_MAX || ml > INT16_MAX)
+            return adr_set_error(ADR_ERR_INVALID, w + ": offsets must be non-decreasing, <= 32767 flows per leg");
+        if (!std::isfinite(notional[i]) || !std::isfinite(spread[i]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": notionals and spreads must be finite");
+        if (!(fix_sign[i] == 1.0 || fix_sign[i] == -1.0) || !(flt_sign[i] == 1.0 || flt_sign[i] == -1.0))
+            return adr_set_error(ADR_ERR_INVALID, w + ": leg signs must be +1 or -1");
+    }
+    const int64_t n_fix = fix_off[n], n_flt = flt_off[n];
+    if ((n_fix > 0 && (!fix_tp || !fix_pay)) || (n_flt > 0 && (!flt_tp || !flt_ts || !flt_te || !flt_alpha)))
+        return adr_set_error(ADR_ERR_INVALID, w + ": null cash-flow array");
+    auto finite = [](const double* a, int64_t m) {
+        bool ok = true;
+        for (int64_t i = 0; i < m; ++i) ok &= std::isfinite(a[i]);
+        return ok;
+    };
+    if (!finite(fix_tp, n_fix) || !finite(fix_pay, n_fix) || !finite(flt_tp, n_flt) || !finite(flt_ts, n_flt) ||
+        !finite(flt_te, n_flt) || !finite(flt_alpha, n_flt) || (flt_weight && !finite(flt_weight, n_flt)))
+        return adr_set_error(ADR_ERR_INVALID, w + ": times, amounts, accruals and weights must be finite");
+    const bool lin = interp_method == ADR_INTERP_LINEAR_FWD_RATES;
+    std::vector<double> tab(dfs, dfs + static_cast<size_t>(S) * K);
+    if (!lin)
+        for (double& v : tab) v = std::log(v);
+    const int64_t chunks = (n + SC::kChunk - 1) / SC::kChunk;
+    std::vector<double> work(static_cast<size_t>(chunks) * S);
+    const SC::Legs arrays{fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, 0, 0, 0, 0, 0.0};
+    const int threads = n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4);
+    adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
+        if (lin)
+            SC::host_chunks<false>(interp_method, K, times, S, tab.data(), n, fix_off, flt_off, arrays, notional, spread, fix_sign,
+                                   flt_sign, pv, work.data(), lo, hi);
+        else
+            SC::host_chunks<true>(interp_method, K, times, S, tab.data(), n, fix_off, flt_off, arrays, notional, spread, fix_sign,
+                                  flt_sign, pv, work.data(), lo, hi);
+    });
+    SC::reduce_chunks(work.data(), chunks, S, book_pv);
+    return ADR_OK;
+}
+
+}  // extern "C"

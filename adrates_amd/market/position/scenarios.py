@@ -11,6 +11,12 @@ adr_curve_set_build) and every scenario is priced with the ordinary kernels.
 
 Shocks use `Model.scenario`'s convention: a float shifts every quote, a dict
 ``{tenor: shift}`` only the named ones; shifts are in the quotes' units (percent).
+
+Full revaluation - the P&L vector behind historical-simulation VaR, expected
+shortfall and stress tests - does not loop over the scenarios: `ScenarioGrid.revalue`
+/ `pnl` and `revalue_on_curves` price the book under all curves in one launch of
+csrc/scenario_pv.hip (adr_scenario_pv), which reads the trades once and takes
+discount factors only (no Jacobians).
 """
 from __future__ import annotations
 
@@ -19,10 +25,10 @@ from typing import Dict, Iterable, List, Sequence, Union
 import numpy as np
 
 from ... import _native
-from ...trades.compiler import compile_ois
+from ...trades.compiler import TradeBatch, compile_bonds, compile_frns, compile_ois
 from ...utils.error import LibError
-from ...utils.global_types import RequestTypes
-from .engine import _SUPPORTED_INTERP
+from ...utils.global_types import CurveTypes, InstrumentTypes, RequestTypes
+from .engine import BOND_CURVES, _SUPPORTED_INTERP, frn_is_single_curve
 from ..curves.curve_tables import build_engine_curve
 
 Shock = Union[float, Dict[str, float]]
@@ -33,6 +39,132 @@ def shocked_quotes(base_px: Sequence[float], tenors: Sequence[str], shock: Shock
     if isinstance(shock, dict):
         return [base_px[i] + shock.get(t, 0.0) for i, t in enumerate(tenors)]
     return [px + shock for px in base_px]
+
+
+def _concat_batches(batches: Sequence[TradeBatch]) -> TradeBatch:
+    """One batch holding the trades of ``batches`` in order."""
+    batches = [b for b in batches if b.n_trades]
+    if len(batches) == 1:
+        return batches[0]
+    cat = lambda name: np.concatenate([np.asarray(getattr(b, name), dtype=np.float64) for b in batches])
+    offs = lambda name: np.concatenate([[0]] + [np.asarray(getattr(b, name)[1:]) + base for b, base in zip(
+        batches, np.cumsum([0] + [int(getattr(b, name)[-1]) for b in batches[:-1]]))]).astype(np.int64)
+    weight = None
+    if any(b.flt_weight is not None for b in batches):
+        weight = np.concatenate([np.ones(b.flt_tp.shape[0]) if b.flt_weight is None else b.flt_weight for b in batches])
+    return TradeBatch(offs("fix_off"), offs("flt_off"), cat("fix_tp"), cat("fix_pay"), cat("flt_tp"), cat("flt_ts"),
+                      cat("flt_te"), cat("flt_alpha"), cat("notional"), cat("spread"), cat("fix_sign"), cat("flt_sign"),
+                      weight)
+
+
+def compile_book(trades, value_dt, curve_type: CurveTypes):
+    """``(batch, pv_const [n] or None, order)`` for a revaluation on ``curve_type``'s curve.
+
+    ``trades`` is a compiled `TradeBatch` (taken as it is) or a list of `OIS`, `Bond` and single-curve `FRN` objects
+    that all discount and project on that curve.  A mixed list becomes ONE batch, grouped OIS, bonds, FRNs: trade
+    ``order[j]`` of the list is trade ``j`` of the batch.  ``pv_const`` holds what does not depend on the curve (an
+    FRN coupon paid at the value time, `compile_frns`).  A dual-curve FRN, a cross-currency trade or a trade of
+    another currency raises `LibError` naming it."""
+    if isinstance(trades, TradeBatch):
+        if trades.n_trades < 1:
+            raise LibError("the batch holds no trade")
+        return trades, None, None
+    trades = list(trades)
+    if not trades:
+        raise LibError("no trades to revalue")
+    currency = next((c for c, t in BOND_CURVES.items() if t == curve_type), None)
+    kinds = {InstrumentTypes.OIS_SWAP: [], InstrumentTypes.BOND: [], InstrumentTypes.FRN: []}
+    for i, t in enumerate(trades):
+        kind = getattr(t, "derivative_type", None)
+        if kind == InstrumentTypes.XCCY_SWAP:
+            raise LibError(f"trade {i} ({type(t).__name__}) is a cross-currency trade: two curves per scenario are "
+                           "outside the scenario revaluation")
+        if kind not in kinds:
+            raise LibError(f"trade {i} ({type(t).__name__}) is not an OIS, a Bond or an FRN")
+        if kind == InstrumentTypes.FRN and not frn_is_single_curve(t):
+            raise LibError(f"trade {i} is a dual-curve FRN (index {t._floating_index.name}): its forwards need a second "
+                           "curve per scenario")
+        ccy = getattr(t, "_currency", None)
+        if ccy != currency or (kind != InstrumentTypes.BOND and t._floating_index != curve_type):
+            raise LibError(f"trade {i} ({type(t).__name__}, {getattr(ccy, 'name', ccy)}) is not on the grid's curve "
+                           f"{curve_type.name}")
+        kinds[kind].append(i)
+    pick = lambda idx: [trades[i] for i in idx]
+    pieces, order, const = [], [], []
+    for kind, compiler in ((InstrumentTypes.OIS_SWAP, compile_ois), (InstrumentTypes.BOND, compile_bonds),
+                           (InstrumentTypes.FRN, compile_frns)):
+        idx = kinds[kind]
+        if not idx:
+            continue
+        piece = compiler(pick(idx), value_dt)
+        if kind == InstrumentTypes.FRN:
+            piece, c = piece
+            const.append(c)
+        else:
+            const.append(np.zeros(len(idx)))
+        pieces.append(piece)
+        order += idx
+    const = np.concatenate(const)
+    return _concat_batches(pieces), (const if np.any(const != 0.0) else None), np.asarray(order, dtype=np.int64)
+
+
+def _finish(out, const, order, per_trade):
+    """Add the curve-independent amounts and put per-trade rows back into the caller's order."""
+    if const is not None:
+        out["book_pv"] = out["book_pv"] + float(np.sum(const))
+    if per_trade:
+        pv = out["pv"] if const is None else out["pv"] + const[None, :]
+        if order is not None and not np.array_equal(order, np.arange(order.size)):
+            back = np.empty_like(pv)
+            back[:, order] = pv
+            pv = back
+        out["pv"] = pv
+    return out
+
+
+def revalue_on_curves(method, times, dfs, trades, value_dt, per_trade=False, ctx=None, host=False, curve_type=None):
+    """PVs of a book under caller-supplied scenario curves: no `ScenarioGrid`, no bootstrap.
+
+    ``method``: an `InterpTypes` member or its value; ``times [K]``: the knot grid shared by all curves (first knot
+    t = 0); ``dfs [S, K]``: one row of positive discount factors per scenario - historical curves, stress curves, the
+    rows of a `ScenarioGrid`.  ``trades``: see `compile_book` (objects are checked against ``curve_type``, default the
+    GBP OIS curve; a `TradeBatch` is taken as it is).  Returns ``{"book_pv": [S]}`` and, with ``per_trade``,
+    ``"pv": [S, n]``.  ``host=True`` runs the CPU twin of the kernel (same arithmetic and summation order; no GPU)."""
+    method = int(getattr(method, "value", method))
+    if method not in _SUPPORTED_INTERP:
+        raise LibError("Invalid interpolation scheme.")
+    batch, const, order = compile_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA)
+    if host:
+        out = _native.scenario_pv_host(method, times, dfs, batch, per_trade=per_trade)
+    else:
+        ctx = ctx or _native.default_context()
+        dev = _native.DeviceTrades(ctx, batch)
+        try:
+            out = _native.scenario_pv(ctx, method, times, dfs, dev, per_trade=per_trade)
+        finally:
+            dev.close()
+    return _finish(out, const, order, per_trade)
+
+
+def _tail(pnl, level):
+    pnl = np.sort(np.asarray(pnl, dtype=np.float64).reshape(-1))
+    if pnl.size == 0 or not 0.0 < level < 1.0:
+        raise ValueError("a P&L vector and a confidence level inside (0, 1) are needed")
+    # (1 - level) * S in floating point can land a hair above an integer (0.05 * 20 != 1 exactly)
+    k = int(np.ceil(round((1.0 - level) * pnl.size, 9)))
+    return pnl[:max(1, k)]
+
+
+def historical_var(pnl, level: float = 0.99) -> float:
+    """Historical-simulation value at risk: minus the ``k``-th smallest P&L, ``k = ceil((1 - level) * S)`` (at least
+    1) - no interpolation between order statistics.  A loss is a positive VaR."""
+    return float(-_tail(pnl, level)[-1])
+
+
+def expected_shortfall(pnl, level: float = 0.99) -> float:
+    """Minus the mean of the ``ceil((1 - level) * S)`` smallest P&Ls - the tail `historical_var` ends at, that
+    scenario included."""
+    return float(-np.mean(_tail(pnl, level)))
 
 
 class ScenarioGrid:
@@ -88,6 +220,41 @@ class ScenarioGrid:
             trades.close()
         keys = outs[0].keys() if outs else ()
         return {k: np.stack([np.asarray(o[k]) for o in outs]) for k in keys}
+
+    def _dfs(self):
+        """The scenarios' discount factors [S, K] on the host (downloaded once)."""
+        if getattr(self, "_dfs_host", None) is None:
+            self._dfs_host = np.stack([self._set.download(i)[0] for i in range(len(self))])
+        return self._dfs_host
+
+    def _revalue(self, trades, per_trade, with_base):
+        batch, const, order = compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name])
+        dev = _native.DeviceTrades(self._ctx, batch)
+        try:
+            if with_base:
+                out = _native.scenario_pv(self._ctx, self.curve._interp_type.value, self.base.times,
+                                          np.vstack([self._dfs(), self.base.dfs[None, :]]), dev, per_trade=per_trade)
+            else:
+                out = _native.scenario_pv_set(self._ctx, self._set, dev, per_trade=per_trade)
+        finally:
+            dev.close()
+        return _finish(out, const, order, per_trade)
+
+    def revalue(self, trades, per_trade: bool = False):
+        """The book's PV under every scenario, in ONE launch on the grid's own discount factors (`price` makes a
+        launch per scenario and needs OIS): ``{"book_pv": [S]}`` and, with ``per_trade``, ``"pv": [S, n]``.
+
+        ``trades``: a list of `OIS`, `Bond` and single-curve `FRN` objects of the grid's curve (a mixed list is one
+        batch) or a compiled `TradeBatch`; see `compile_book` for what is refused.  Only discount factors are read, so
+        ``ScenarioGrid(..., with_gamma=False)`` is the cheaper grid to feed it (the builder still makes Jacobians)."""
+        return self._revalue(trades, per_trade, False)
+
+    def pnl(self, trades) -> np.ndarray:
+        """``[S]``: the book's PV under each scenario minus its PV on the unshocked curve.  The base curve
+        (``self.base.dfs``, the host builder's) is priced by the same launch as one more scenario row, so the
+        difference carries no noise between kernels: a zero shock whose curve has the base curve's bits gives 0."""
+        book = self._revalue(trades, False, True)["book_pv"]
+        return book[:-1] - book[-1]
 
     def close(self):
         self._set.close()

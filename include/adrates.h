@@ -503,6 +503,50 @@ int adr_yoy_risk_host(int disc_method, int K, const double* times, const double*
                       const double* T, const double* b, int64_t n, int64_t m, const int64_t* cpn_off, const double* cpn,
                       uint32_t req_mask, double* amount, double* pv, double* delta, double* gamma, double* agg);
 
+/*
+ * Scenario revaluation: the PV of every trade of an uploaded batch under S discount curves that share one knot grid -
+ * the P&L vectors behind historical-simulation VaR, expected shortfall and stress tests.  The reference revalues one
+ * Model.scenario at a time (cavour/models/models.py:507-557: a new model, bootstrap and trace per shock).
+ *
+ * Curves: interp_method (1, 2 or 4), K (2 .. ADR_SCENARIO_MAX_KNOTS) knot times[K] (non-decreasing, repeats allowed; the
+ * first knot is the value-time point t = 0 with discount factor 1, as for adr_curve_upload: the PV is not divided by
+ * D(0)) and dfs[S][K], one row of positive discount factors per scenario (S >= 1).  No rates and no Jacobians: the rows
+ * may come from the device curve builder (adr_curve_set_arrays) or from anywhere else.
+ *
+ * pv[i][s] - TRADE-major, [n][S], or NULL - is what adr_price(VALUE) returns for trade i on the curve (times, dfs[s]):
+ *     fix_sign * sum_j pay_j D_s(tp_j) [tp_j > 0]
+ *   + flt_sign * N * sum_j w_j ((D_s(ts_j) / D_s(te_j) - 1) [alpha_j > 0] + spread alpha_j) D_s(tp_j) [tp_j >= 0],
+ * D_s(t) = InterpolatorAd.simple_interpolate on row s; every batch adr_price accepts (payment lag, flt_weight, legs of
+ * any length).  book_pv[s] = sum_i pv[i][s] in a fixed order: the trades in chunks of ADR_SCENARIO_CHUNK summed in
+ * trade order from 0.0, then chunk j added to slot j % 64 in order, then slots 0-31 += 32-63, 0-15 += 16-31, ..., 0 += 1.
+ * A scenario's results do not depend on S, on the other scenarios or on the launch shape, and are bit-identical from
+ * run to run; adr_scenario_pv_host runs the same per-trade arithmetic in the same order on CPU threads (no GPU needed;
+ * n_threads <= 0: as many as the machine suggests, at most 16) and differs from the device by exp / log only.
+ *
+ * adr_scenario_pv: host arrays in and out, blocks.  adr_scenario_pv_dev: device arrays, enqueued on `stream` (NULL: the
+ * ctx's own), no allocation and no synchronisation (capturable into a HIP graph: two kernels in one chain); work_dev
+ * holds adr_scenario_pv_work(n, S) doubles; only the scalars are checked.  adr_scenario_pv_set: the curves of a set built
+ * by adr_curve_set_build, read where they are; host outputs, blocks.  adr_curve_set_arrays: that set's scheme, K, S and
+ * the device pointers of its knot times [K] and discount factors [S][K] (any output may be NULL) for adr_scenario_pv_dev.
+ */
+#define ADR_SCENARIO_MAX_KNOTS 4096
+#define ADR_SCENARIO_CHUNK 64
+int adr_scenario_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S, const double* dfs,
+                    const adr_trades* trades, double* pv, double* book_pv);
+/* Doubles of scratch adr_scenario_pv_dev needs: ceil(n / ADR_SCENARIO_CHUNK) * S. */
+int64_t adr_scenario_pv_work(int64_t n, int S);
+int adr_scenario_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S, const double* dfs_dev,
+                        const adr_trades* trades, double* pv_dev, double* book_pv_dev, double* work_dev, void* stream);
+int adr_scenario_pv_set(adr_ctx* ctx, const adr_curve_set* set, const adr_trades* trades, double* pv, double* book_pv);
+int adr_curve_set_arrays(const adr_curve_set* set, int* interp_method, int* K, int* S, const double** times_dev,
+                         const double** dfs_dev);
+/* The trades as the arrays of adr_trades_upload_weighted (flt_weight may be NULL). */
+int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
+                         const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                         const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                         const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                         const double* flt_sign, double* pv, double* book_pv, int n_threads);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
