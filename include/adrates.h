@@ -476,6 +476,11 @@ int adr_frn_measures_host(int disc_method, int disc_n, const double* disc_t, con
  * agg is a fixed-order sum of the per-swap rows: swaps in chunks of ADR_YOY_CHUNK summed in order, then chunk j added
  * to lane j % 64 in order, then lanes 0-31 += 32-63, 0-15 += 16-31, ..., 0 += 1.  Results are bit-identical from run to run and do
  * not depend on the launch shape or the batch; adr_yoy_risk_host runs the same per-swap code and order on the CPU.
+ * With ADR_YOY_AGG every entry of agg is written: the slots of a measure that req_mask does not name hold 0.0, and
+ * n = 0 gives an all-zero agg.  An output that req_mask does not ask for is never written, whether or not its pointer
+ * is given; amount is written without ADR_YOY_PER_SWAP and ADR_YOY_AGG too.  adr_yoy_risk_dev cannot refuse offsets it
+ * has not read: a swap whose cpn_off pair is negative, decreasing or ends beyond m reads no coupon and gets a NaN PV
+ * (zero delta and gamma rows), which carries into agg[0].
  */
 #define ADR_YOY_FIELDS 5
 #define ADR_YOY_TP 0

@@ -332,3 +332,105 @@ class MpXccy:
             f = lambda s1, s2: self.pv(*self._args(a, [(a, p, s1), (b, q, s2)]))
             g = (f(1, 1) - f(1, -1) - f(-1, 1) + f(-1, -1)) / (4 * _STEP ** 2)
         return float(g) * 1e-8
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Year-on-year inflation legs: the same idea for the inflation side of `_compute_yoy_iis`
+# (cavour/market/position/engine.py:986-1353).  The HIP kernel (csrc/yoy_risk.hip) differentiates in closed form, the
+# torch restatement (tests/_inflation_oracle.py) with autodiff and the reference's chain rule through f = (1 + b)^T;
+# here the leg's PV is a plain mpmath function of the breakeven rates b and is differenced.  The inputs are the
+# kernel's raw inputs, so no market objects are needed.
+# --------------------------------------------------------------------------------------------------------------
+def _plan_knots(plan):
+    return {plan[1]} if plan[0] in ("snap", "flat") else {plan[1], plan[2]}
+
+
+class MpYoY:
+    """PV of one YoY inflation leg as a function of the breakeven rates, in mpmath.  ``disc``: (method, knot times,
+    knot dfs); ``infl``: (method, pillar times T, breakeven rates b); ``coupons``: rows (tp, ts, te, scale, spread).
+    The inflation nodes are (0, 1), (T_k, (1 + b_k) ** T_k); a coupon pays
+    ``scale * (I(te) / I(ts) - 1 + spread) * D(tp) / D(0)`` when ``tp > 0`` (strictly)."""
+
+    def __init__(self, disc, infl, coupons):
+        dm, times, dfs = disc
+        self.im, T, b = infl
+        times = np.asarray(times, dtype=np.float64)
+        self.T = [float(t) for t in np.asarray(T, dtype=np.float64).reshape(-1)]
+        self.b0 = [mpf(float(v)) for v in np.asarray(b, dtype=np.float64).reshape(-1)]
+        self.x = np.concatenate(([0.0], self.T))
+        d = [mpf(float(v)) for v in dfs]
+        d0 = _df(_lookup_plan(times, 0.0, dm), 0.0, times, d, dm)
+        self.cpn = []
+        for tp, ts, te, scale, spread in coupons:
+            tp, ts, te = float(tp), float(ts), float(te)
+            ps, pe = _lookup_plan(self.x, ts, self.im), _lookup_plan(self.x, te, self.im)
+            dfr = _df(_lookup_plan(times, tp, dm), tp, times, d, dm) / d0 if tp > 0.0 else None
+            pillars = frozenset(k - 1 for k in (_plan_knots(ps) | _plan_knots(pe)) if k > 0)
+            self.cpn.append((ts, te, ps, pe, mpf(float(scale)), mpf(float(spread)), dfr, pillars))
+        self._base = None
+
+    def touched(self):
+        """Pillars that a knot of some live coupon's ``ts`` / ``te`` lookup names (a decision on the times alone);
+        every other pillar's delta and gamma entries are structurally zero."""
+        return sorted(set().union(*[c[7] for c in self.cpn if c[6] is not None])) if self.cpn else []
+
+    def _nodes(self, b):
+        return [mpf(1)] + [(1 + bk) ** mpf(t) for bk, t in zip(b, self.T)]
+
+    def _amount(self, c, f):
+        ts, te, ps, pe, scale, spread = c[:6]
+        return scale * (_df(pe, te, self.x, f, self.im) / _df(ps, ts, self.x, f, self.im) - 1 + spread)
+
+    def _terms(self, b, moved=None):
+        """Per-coupon PVs; with ``moved`` (the bumped pillars) a coupon none of whose knots moved keeps its base term -
+        the same number it would get from being evaluated again."""
+        f = self._nodes(b)
+        out = []
+        for i, c in enumerate(self.cpn):
+            if c[6] is None:
+                out.append(mpf(0))
+            elif moved is not None and not (c[7] & moved):
+                out.append(self._base[i])
+            else:
+                out.append(self._amount(c, f) * c[6])
+        return out
+
+    def pv(self, b):
+        return sum(self._terms(b), mpf(0))
+
+    def _bumped(self, shifts):
+        if self._base is None:
+            self._base = self._terms(self.b0)
+        b = list(self.b0)
+        for p, k in shifts:
+            b[p] = b[p] + k * _STEP
+        return sum(self._terms(b, frozenset(p for p, _ in shifts)), mpf(0))
+
+    def value(self):
+        return float(self.pv(self.b0))
+
+    def amounts(self):
+        """The projected amount of every coupon, masked ones included."""
+        f = self._nodes(self.b0)
+        return np.array([float(self._amount(c, f)) for c in self.cpn], dtype=np.float64)
+
+    def delta(self, pillars=None):
+        """[P] per bp; ``pillars``: which entries to compute (others are returned as NaN)."""
+        P = len(self.b0)
+        out = np.full(P, np.nan)
+        for p in (range(P) if pillars is None else pillars):
+            out[p] = float((self._bumped([(p, 1)]) - self._bumped([(p, -1)])) / (2 * _STEP) * mpf(10) ** -4)
+        return out
+
+    def gamma(self, pairs):
+        """{(p, q): d2PV/db_p db_q per bp^2} for the requested pairs."""
+        v0 = self._bumped([])
+        out = {}
+        for p, q in pairs:
+            if p == q:
+                g = (self._bumped([(p, 1)]) - 2 * v0 + self._bumped([(p, -1)])) / _STEP ** 2
+            else:
+                g = (self._bumped([(p, 1), (q, 1)]) - self._bumped([(p, 1), (q, -1)])
+                     - self._bumped([(p, -1), (q, 1)]) + self._bumped([(p, -1), (q, -1)])) / (4 * _STEP ** 2)
+            out[(p, q)] = float(g * mpf(10) ** -8)
+        return out
