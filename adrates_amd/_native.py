@@ -100,6 +100,13 @@ _SIGNATURES = {
                                        C.POINTER(_vp)]),
     "adr_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int64, _i64p, _i64p] + [_dp] * 11 +
                              [_dp, _dp, C.c_int]),
+    "adr_yoy_scenario_pv": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int,
+                                      C.c_int64, C.c_int64, _i64p, _dp, _dp, C.c_int64, _i64p, _dp, _dp, _dp]),
+    "adr_yoy_scenario_pv_work": (C.c_int64, [C.c_int64, C.c_int]),
+    "adr_yoy_scenario_pv_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                          C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "adr_yoy_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int,
+                                           C.c_int64, C.c_int64, _i64p, _dp, _dp, C.c_int64, _i64p, _dp, _dp, _dp, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -821,6 +828,83 @@ def scenario_pv_dev(ctx: Context, method: int, K: int, times_ptr: int, S: int, d
     v = lambda p: _vp(int(p) or None)
     _check(load().adr_scenario_pv_dev(ctx._h, int(method), int(K), v(times_ptr), int(S), v(dfs_ptr), trades._h, v(pv_ptr),
                                       v(book_ptr), v(work_ptr), _vp(stream or None)), "adr_scenario_pv_dev")
+
+
+def _yoy_scenario_inputs(times, dfs, T, b, fixed, book):
+    """The arrays of adr_yoy_scenario_pv from ``dfs`` [S, K] or [K], ``b`` [S, P] or [P], the fixed legs ``(fix_off,
+    fix_tp, fix_pay)`` (None: no fixed flows) and the coupon book (``cpn_off`` and YOY_FIELDS; None: no coupons)."""
+    times, dfs = _scenario_curves(times, dfs)
+    T = _f64(T).reshape(-1)
+    b = _f64(np.atleast_2d(b))
+    if b.ndim != 2 or b.shape[1] != T.size:
+        raise LibError(f"b must have shape [n_scenarios, {T.size}] or [{T.size}] (one column per pillar), not {list(b.shape)}")
+    S = max(dfs.shape[0], b.shape[0])
+    if dfs.shape[0] not in (1, S) or b.shape[0] not in (1, S):
+        raise LibError(f"{dfs.shape[0]} discount rows and {b.shape[0]} breakeven rows: each must be one shared row or "
+                       "one row per scenario")
+    if fixed is None and book is None:
+        raise LibError("neither fixed legs nor YoY coupons")
+    if book is not None:
+        cpn_off, cpn = yoy_pack(book)
+    if fixed is not None:
+        fix_off = np.ascontiguousarray(fixed[0], dtype=np.int64)
+        fix_tp, fix_pay = _f64(fixed[1]).reshape(-1), _f64(fixed[2]).reshape(-1)
+        if fix_off.ndim != 1 or fix_off.size < 1 or fix_tp.shape != fix_pay.shape:
+            raise LibError("fixed legs are (fix_off [n + 1], fix_tp, fix_pay) with one amount per time")
+    else:
+        fix_off, fix_tp, fix_pay = np.zeros_like(cpn_off), np.zeros(0), np.zeros(0)
+    if book is None:
+        cpn_off, cpn = np.zeros_like(fix_off), np.zeros((len(YOY_FIELDS), 0))
+    if fix_off.shape != cpn_off.shape:
+        raise LibError(f"fix_off describes {fix_off.size - 1} swaps, cpn_off {cpn_off.size - 1}")
+    return times, dfs, T, b, S, fix_off, fix_tp, fix_pay, cpn_off, cpn
+
+
+def _yoy_scenario_call(fn, head, tail, disc_method, times, dfs, infl_method, T, b, fixed, book, per_trade):
+    times, dfs, T, b, S, fix_off, fix_tp, fix_pay, cpn_off, cpn = _yoy_scenario_inputs(times, dfs, T, b, fixed, book)
+    n = fix_off.size - 1
+    out_book = np.empty(S)
+    pv = np.empty((n, S)) if per_trade else None
+    _check(fn(*head, int(disc_method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), int(infl_method), T.size, _ptr(T),
+              b.shape[0], _ptr(b), S, n, fix_tp.size, _ptr(fix_off, _i64p), _ptr(fix_tp), _ptr(fix_pay), cpn.shape[1],
+              _ptr(cpn_off, _i64p), _ptr(cpn), _ptr(pv), _ptr(out_book), *tail), fn.__name__)
+    return _scenario_result(out_book, pv, per_trade)
+
+
+def yoy_scenario_pv(ctx: Context, disc_method: int, times, dfs, infl_method: int, T, b, fixed, book, per_trade=False):
+    """PVs of a YoY swap book under scenario PAIRS (adr_yoy_scenario_pv, blocking): discount rows ``dfs`` [S, K] or one
+    shared row [K] on the knots ``times``, breakeven rows ``b`` [S, P] or one shared row [P] on the pillars ``T``.
+    ``fixed``: ``(fix_off, fix_tp, fix_pay)`` (`compile_yoy_fixed_legs`) or None; ``book``: ``cpn_off`` and the fields
+    YOY_FIELDS (`compile_yoy_coupons`) or None.  Returns ``book_pv`` [S] and, with ``per_trade``, ``pv`` [S, n]."""
+    return _yoy_scenario_call(load().adr_yoy_scenario_pv, (ctx._h,), (), disc_method, times, dfs, infl_method, T, b, fixed,
+                              book, per_trade)
+
+
+def yoy_scenario_pv_host(disc_method: int, times, dfs, infl_method: int, T, b, fixed, book, per_trade=False, n_threads=0):
+    """`yoy_scenario_pv` on the CPU (adr_yoy_scenario_pv_host): the same per-coupon arithmetic and the same order of the
+    book sum; no GPU needed."""
+    return _yoy_scenario_call(load().adr_yoy_scenario_pv_host, (), (int(n_threads),), disc_method, times, dfs, infl_method,
+                              T, b, fixed, book, per_trade)
+
+
+def yoy_scenario_pv_work(n_swaps: int, n_scenarios: int) -> int:
+    """Doubles of scratch `yoy_scenario_pv_dev` needs."""
+    return int(load().adr_yoy_scenario_pv_work(int(n_swaps), int(n_scenarios)))
+
+
+def yoy_scenario_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: int, infl_method: int, P: int, S_infl: int, S: int,
+                        n_swaps: int, n_fix: int, n_coupons: int, ptrs, book_ptr: int, work_ptr: int, pv_ptr: int = 0,
+                        stream=0):
+    """Non-blocking form (adr_yoy_scenario_pv_dev): ``ptrs`` maps ``times`` [K], ``dfs`` [S_disc, K], ``T`` [P], ``b``
+    [S_infl, P], ``fix_off``, ``fix_tp``, ``fix_pay``, ``cpn_off`` and ``cpn`` to device pointers (integers; the value
+    arrays of an empty leg may be 0); outputs ``book_pv`` [S] and ``pv`` [n, S] (swap-major; 0: not wanted);
+    `yoy_scenario_pv_work` doubles of scratch."""
+    v = lambda p: _vp(int(p) or None)
+    g = lambda k: v(ptrs.get(k, 0))
+    _check(load().adr_yoy_scenario_pv_dev(ctx._h, int(disc_method), int(K), g("times"), int(S_disc), g("dfs"), int(infl_method),
+                                          int(P), g("T"), int(S_infl), g("b"), int(S), int(n_swaps), int(n_fix), g("fix_off"),
+                                          g("fix_tp"), g("fix_pay"), int(n_coupons), g("cpn_off"), g("cpn"), v(pv_ptr),
+                                          v(book_ptr), v(work_ptr), _vp(stream or None)), "adr_yoy_scenario_pv_dev")
 
 
 _default_ctx = {}

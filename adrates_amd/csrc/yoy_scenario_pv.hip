@@ -1,0 +1,623 @@
+// Inflation scenario revaluation: the PV of every YoY inflation swap of a book under S scenarios, each a pair of a
+// discount curve row and a breakeven row (adr_yoy_scenario_pv*; declarations, semantics and the order of the book sum:
+// include/adrates.h).
+//
+// pv[i][s] = sum_f fix_pay_f D_s(tp_f) [tp_f > 0] + sum_j scale_j (I_s(te_j) / I_s(ts_j) - 1 + spread_j) D_s(tp_j) [tp_j > 0]:
+// D_s is InterpolatorAd.simple_interpolate on (times, dfs[s]) exactly as scenario_pv.hip reads it, I_s the same rule on
+// the nodes (0, 1), (T_k, (1 + b[s][k])^T_k) as yoy_risk.hip forms them.  Both inflation schemes make ln I(t) a weighted
+// sum of at most two L_k = T_k ln(1 + b_k) (simple_interp.hpp::log_weights), so a YoY ratio is ONE exp of the
+// difference of two such sums.
+//
+// Layout (scenario_pv.hip's): one lane = one scenario, a block = kWaves waves of ONE group of 64 scenarios that share
+// the group's two tables in LDS - the discount table tab[k][lane] (ln d under the log-linear schemes, d under
+// LINEAR_FWD_RATES) and the inflation table itab[k][lane] = L_k - so a knot costs one conflict-free ds_read_b64.  Where
+// the two do not fit together the small inflation table stays in LDS and the lanes read their discount rows from global
+// memory.  The swaps are cut into chunks of ADR_SCENARIO_CHUNK; a wave takes chunks round-robin and walks each in swap
+// order.  Lane l describes index l of the swap - YoY coupon l and fixed flow l: their segment searches, knot indices
+// and weights - and marks what needs no evaluation of its own: a YoY start equal to the previous coupon's end (annual
+// legs tile: the weighted sum is the one just computed), ts == te (y = 0 exactly), a fixed flow paid with the coupon of
+// the same index (one D(tp) for both).  The wave then walks the indices in order, fetching index j's description from
+// lane j with v_readlane into scalar registers, and each lane evaluates on its own scenario's tables.
+//
+// A shared curve (S_disc = 1 or S_infl = 1: "not shocked") is read with row stride 0.  The book sum is
+// scenario_pv.hip's: chunk sums in swap order, chunk j to slot j % 64 in order, a halving tree; no atomics.  The host
+// twin (adr_yoy_scenario_pv_host) runs the same per-date and per-coupon code in the same order on CPU threads.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/adrates.h"
+#include "host_pool.hpp"
+#include "simple_interp.hpp"
+
+int adr_set_error(int status, const std::string& msg);                          // capi.hip
+int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
+int adr_ctx_compute_units(const adr_ctx* ctx);                                  // capi.hip
+
+// The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
+// exp / log implementations.
+#pragma clang fp contract(off)
+
+namespace adr {
+namespace yscen {
+
+constexpr int kWave = 64;
+constexpr int kWaves = 16;                      // waves per block: four per SIMD, all on one scenario group
+constexpr int kThreads = kWave * kWaves;
+constexpr int kChunk = ADR_SCENARIO_CHUNK;      // swaps per partial sum of the book
+constexpr int kRedLanes = 64;                   // the book reduction's slots per scenario
+constexpr int kRedEntries = 16;                 // scenarios per reduction block
+constexpr size_t kLdsBudget = 160 * 1024;
+
+// A date in weight form on a table Tb.  Discount (Tb_k = ln d_k when kLog, else d_k):
+//   kLog:  ln D = wa Tb_a + (b != a ? wb Tb_b : 0);      else:  D = Tb_a + (b != a ? wb (Tb_b - Tb_a) : 0).
+// Inflation (Tb_k = L_k, L_0 = 0): ln I = (a > 0 ? wa L_a : 0) + (b != a ? wb L_b : 0).
+struct DateW {
+    int a, b;
+    double wa, wb;
+};
+
+template <bool kLog>
+__host__ __device__ inline DateW disc_weights(double t, const double* x, int K, int method) {
+    DateW d;
+    if (kLog) {
+        const si::LogWeights w = si::log_weights(t, x, K, method);
+        d.a = w.a; d.b = w.b; d.wa = w.wa; d.wb = w.wb;
+    } else {
+        const si::Where p = si::locate(t, x, K);
+        d.a = p.lo; d.b = p.hi; d.wa = 1.0; d.wb = p.w;
+    }
+    return d;
+}
+
+__host__ __device__ inline DateW infl_weights(double t, const double* x, int N, int method) {
+    const si::LogWeights w = si::log_weights(t, x, N, method);
+    return DateW{w.a, w.b, w.wa, w.wb};
+}
+
+template <bool kLog, class Tab>
+__host__ __device__ inline double eval_df(const DateW& d, const Tab& tab) {
+    const double la = tab(d.a);
+    if (kLog) {
+        double s = d.wa * la;
+        if (d.b != d.a) s = s + d.wb * tab(d.b);
+        return exp(s);
+    }
+    double f = la;
+    if (d.b != d.a) f = la + d.wb * (tab(d.b) - la);
+    return f;
+}
+
+template <class Tab>
+__host__ __device__ inline double eval_ln_index(const DateW& d, const Tab& itab) {
+    double s = 0.0;
+    if (d.a > 0) s = d.wa * itab(d.a);          // knot 0 is (0, 1): L = 0 whatever its weight
+    if (d.b != d.a) s = s + d.wb * itab(d.b);
+    return s;
+}
+
+// L_k of a breakeven row, as yoy_risk.hip::make_node forms it (k >= 1; L_0 = 0).
+__host__ __device__ inline double node_log(const double* T, const double* b, int k) {
+    if (k == 0) return 0.0;
+    const double ob = 1.0 + b[k - 1];
+    return T[k - 1] * log(ob);
+}
+
+// Index c of a swap: its YoY coupon (c < n_cpn) and its fixed flow (c < n_fix).  Both masks are strict (tp > 0).
+enum : int {
+    kHasCpn = 1, kHasFix = 2,
+    kTsIsPrevTe = 4,     // YoY start == the previous coupon's YoY end: ln I(ts) is the ln I(te) just computed
+    kTsIsTe = 8,         // y = 0 exactly: no lookups, no exp
+    kFixIsCpnTp = 16     // the fixed flow is paid with the coupon: D is D(tp)
+};
+
+struct Slot {
+    int flags;
+    DateW wp, wx, ws, we;       // D(tp) of the coupon, D of the fixed flow, ln I(ts), ln I(te)
+    double scale, spread, pay;
+};
+
+__host__ __device__ inline Slot empty_slot() {
+    Slot s;
+    s.flags = 0;
+    s.wp = s.wx = s.ws = s.we = DateW{0, 0, 0.0, 0.0};
+    s.scale = 0.0; s.spread = 0.0; s.pay = 0.0;
+    return s;
+}
+
+struct Legs {            // one swap's cash flows
+    const double *fix_tp, *fix_pay, *cpn;
+    int64_t m, f0, c0;
+    int n_fix, n_cpn;
+};
+
+struct Curves {          // what a description needs of the curves: the knots, not the values
+    const double *x, *ix;
+    int K, N, dm, im;    // N = P + 1 inflation nodes
+};
+
+template <bool kLog>
+__host__ __device__ inline Slot make_slot(const Legs& g, int c, const Curves& cv) {
+    Slot s = empty_slot();
+    double tp = 0.0;
+    bool cpn = false;
+    if (c < g.n_cpn) {
+        tp = g.cpn[ADR_YOY_TP * g.m + g.c0 + c];
+        cpn = tp > 0.0;
+    }
+    if (cpn) {
+        const int64_t i = g.c0 + c;
+        const double ts = g.cpn[ADR_YOY_TS * g.m + i], te = g.cpn[ADR_YOY_TE * g.m + i];
+        s.flags |= kHasCpn;
+        s.scale = g.cpn[ADR_YOY_SCALE * g.m + i];
+        s.spread = g.cpn[ADR_YOY_SPREAD * g.m + i];
+        if (ts == te) {
+            s.flags |= kTsIsTe;
+        } else {
+            // the previous coupon left its ln I(te) behind when it counted and looked it up
+            bool prev = false;
+            if (c > 0) {
+                const double pte = g.cpn[ADR_YOY_TE * g.m + i - 1];
+                prev = ts == pte && g.cpn[ADR_YOY_TP * g.m + i - 1] > 0.0 && g.cpn[ADR_YOY_TS * g.m + i - 1] != pte;
+            }
+            if (prev) s.flags |= kTsIsPrevTe;
+            else s.ws = infl_weights(ts, cv.ix, cv.N, cv.im);
+            s.we = infl_weights(te, cv.ix, cv.N, cv.im);
+        }
+        s.wp = disc_weights<kLog>(tp, cv.x, cv.K, cv.dm);
+    }
+    if (c < g.n_fix) {
+        const double xt = g.fix_tp[g.f0 + c];
+        if (xt > 0.0) {
+            s.flags |= kHasFix;
+            s.pay = g.fix_pay[g.f0 + c];
+            if (cpn && xt == tp) s.flags |= kFixIsCpnTp;
+            else s.wx = disc_weights<kLog>(xt, cv.x, cv.K, cv.dm);
+        }
+    }
+    return s;
+}
+
+struct Acc {             // one scenario's running state inside a swap
+    double le, cpn, fix; // ln I(te) of the previous coupon; the legs' sums
+};
+
+template <bool kLog, class Tab, class ITab>
+__host__ __device__ inline void apply_slot(const Slot& s, const Tab& tab, const ITab& itab, Acc& a) {
+    double dp = 0.0;
+    if (s.flags & kHasCpn) {
+        dp = eval_df<kLog>(s.wp, tab);
+        double y = 0.0;
+        if (!(s.flags & kTsIsTe)) {
+            const double ls = (s.flags & kTsIsPrevTe) ? a.le : eval_ln_index(s.ws, itab);
+            const double le = eval_ln_index(s.we, itab);
+            y = exp(le - ls) - 1.0;
+            a.le = le;
+        }
+        a.cpn = a.cpn + (s.scale * (y + s.spread)) * dp;
+    }
+    if (s.flags & kHasFix) {
+        const double dx = (s.flags & kFixIsCpnTp) ? dp : eval_df<kLog>(s.wx, tab);
+        a.fix = a.fix + s.pay * dx;
+    }
+}
+
+__host__ __device__ inline double swap_pv(const Acc& a) { return a.fix + a.cpn; }
+
+// A leg's range of swap i, or false when the offsets cannot be right (then nothing of the leg is read).
+__host__ __device__ inline bool leg_range(const int64_t* off, int64_t i, int64_t total, int64_t* begin, int* count) {
+    const int64_t lo = off[i], hi = off[i + 1];
+    if (lo < 0 || hi < lo || hi > total || hi - lo > INT32_MAX) return false;
+    *begin = lo;
+    *count = static_cast<int>(hi - lo);
+    return true;
+}
+
+// book[s] = sum over the chunk rows of entry s: chunk j to slot j % 64 in order, then slots 0-31 += 32-63, ..., 0 += 1.
+void reduce_chunks(const double* work, int64_t chunks, int64_t S, double* book) {
+    for (int64_t e = 0; e < S; ++e) {
+        double p[kRedLanes];
+        for (int cl = 0; cl < kRedLanes; ++cl) {
+            p[cl] = 0.0;
+            for (int64_t j = cl; j < chunks; j += kRedLanes) p[cl] = p[cl] + work[j * S + e];
+        }
+        for (int h = kRedLanes / 2; h >= 1; h >>= 1)
+            for (int cl = 0; cl < h; ++cl) p[cl] = p[cl] + p[cl + h];
+        book[e] = p[0];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ device
+struct Args {
+    const double *times, *dfs;       // [K], [S_disc][K]
+    const double *T, *b;             // [P], [S_infl][P]
+    int K, P, S, dm, im;
+    int disc_stride, infl_stride;    // K / P, or 0 for a shared row
+    int64_t n, mf, m, n_chunks;
+    const int64_t *fix_off, *cpn_off;
+    const double *fix_tp, *fix_pay, *cpn;
+    double *pv, *work;               // [n][S] or null; [n_chunks][S]
+};
+
+__device__ inline int lane_int(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
+__device__ inline double lane_dbl(double v, int j) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+__device__ inline DateW lane_date(const DateW& d, int j) {
+    DateW r;
+    r.a = lane_int(d.a, j);
+    r.b = lane_int(d.b, j);
+    r.wa = lane_dbl(d.wa, j);
+    r.wb = r.b != r.a ? lane_dbl(d.wb, j) : 0.0;
+    return r;
+}
+
+// Lane j's slot in scalar registers; only the parts its flags say will be read.
+__device__ inline Slot lane_slot(const Slot& m, int j) {
+    Slot u = empty_slot();
+    u.flags = lane_int(m.flags, j);
+    if (u.flags & kHasCpn) {
+        u.wp = lane_date(m.wp, j);
+        if (!(u.flags & kTsIsTe)) {
+            if (!(u.flags & kTsIsPrevTe)) u.ws = lane_date(m.ws, j);
+            u.we = lane_date(m.we, j);
+        }
+        u.scale = lane_dbl(m.scale, j);
+        u.spread = lane_dbl(m.spread, j);
+    }
+    if (u.flags & kHasFix) {
+        if (!(u.flags & kFixIsCpnTp)) u.wx = lane_date(m.wx, j);
+        u.pay = lane_dbl(m.pay, j);
+    }
+    return u;
+}
+
+// kLds: the group's discount table sits in LDS; otherwise every lane reads its scenario's row of dfs.
+template <bool kLog, bool kLds>
+struct DevTab {
+    const double* p;     // kLds: &tab[0][lane]; else &dfs[row][0]
+    __device__ double operator()(int k) const {
+        if (kLds) return p[k * kWave];
+        return kLog ? log(p[k]) : p[k];
+    }
+};
+
+struct DevITab {
+    const double* p;     // &itab[0][lane]
+    __device__ double operator()(int k) const { return p[k * kWave]; }
+};
+
+template <bool kLog, bool kLds>
+__global__ __launch_bounds__(kThreads) void yoy_scenario_pv_kernel(Args a) {
+    extern __shared__ double lds[];
+    const int K = a.K, N = a.P + 1, S = a.S;
+    double* s_x = lds;                               // [K]
+    double* s_ix = s_x + K;                          // [N]
+    double* s_itab = s_ix + N;                       // [N][64]
+    double* s_tab = s_itab + N * kWave;              // [K][64] (kLds)
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t s = static_cast<int64_t>(blockIdx.y) * kWave + lane;
+    const bool live = s < S;
+    const int64_t sr = live ? s : S - 1;                    // padding lanes price the last scenario and store nothing
+    const double* row = a.dfs + sr * a.disc_stride;
+    const double* brow = a.b + sr * a.infl_stride;
+    for (int k = threadIdx.x; k < K; k += kThreads) s_x[k] = a.times[k];
+    for (int k = threadIdx.x; k < N; k += kThreads) s_ix[k] = k ? a.T[k - 1] : 0.0;
+    for (int k = wave; k < N; k += kWaves) s_itab[k * kWave + lane] = node_log(a.T, brow, k);
+    if (kLds)
+        for (int k = wave; k < K; k += kWaves) s_tab[k * kWave + lane] = kLog ? log(row[k]) : row[k];
+    __syncthreads();
+    const DevTab<kLog, kLds> tab{kLds ? s_tab + lane : row};
+    const DevITab itab{s_itab + lane};
+    const Curves cv{s_x, s_ix, K, N, a.dm, a.im};
+    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < a.n_chunks;
+         ch += static_cast<int64_t>(gridDim.x) * kWaves) {
+        const int64_t i1 = ch * kChunk + kChunk < a.n ? ch * kChunk + kChunk : a.n;
+        double book = 0.0;
+        for (int64_t i = ch * kChunk; i < i1; ++i) {
+            Legs g{a.fix_tp, a.fix_pay, a.cpn, a.m, 0, 0, 0, 0};      // uniform: scalar loads
+            const bool ok_fix = leg_range(a.fix_off, i, a.mf, &g.f0, &g.n_fix);
+            const bool ok = leg_range(a.cpn_off, i, a.m, &g.c0, &g.n_cpn) && ok_fix;
+            const int cnt_all = ok ? (g.n_fix > g.n_cpn ? g.n_fix : g.n_cpn) : 0;
+            Acc acc{0.0, 0.0, 0.0};
+            for (int base = 0; base < cnt_all; base += kWave) {
+                const int cnt = cnt_all - base < kWave ? cnt_all - base : kWave;
+                Slot mine = empty_slot();
+                if (lane < cnt) mine = make_slot<kLog>(g, base + lane, cv);
+                for (int j = 0; j < cnt; ++j) apply_slot<kLog>(lane_slot(mine, j), tab, itab, acc);
+            }
+            const double pv = ok ? swap_pv(acc) : NAN;             // malformed offsets: no reads, a NaN PV
+            if (a.pv && live) a.pv[i * S + s] = pv;
+            book = book + pv;
+        }
+        if (live) a.work[ch * S + s] = book;
+    }
+}
+
+// book[e] = the fixed-order sum of the chunk rows (reduce_chunks above is its host form).
+__global__ __launch_bounds__(kRedLanes * kRedEntries) void yoy_scenario_book_kernel(const double* work, int64_t chunks, int64_t S,
+                                                                                    double* book) {
+    __shared__ double sh[kRedLanes][kRedEntries];
+    const int ei = threadIdx.x % kRedEntries, cl = threadIdx.x / kRedEntries;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kRedEntries + ei;
+    double acc = 0.0;
+    if (e < S) {
+#pragma unroll 8
+        for (int64_t j = cl; j < chunks; j += kRedLanes) acc = acc + work[j * S + e];
+    }
+    sh[cl][ei] = acc;
+    __syncthreads();
+    for (int h = kRedLanes / 2; h >= 1; h >>= 1) {
+        if (cl < h) sh[cl][ei] = sh[cl][ei] + sh[cl + h][ei];
+        __syncthreads();
+    }
+    if (cl == 0 && e < S) book[e] = sh[0][ei];
+}
+
+// -------------------------------------------------------------------------------------------------------------- host
+inline size_t lds_bytes(int K, int P, bool table) {
+    const size_t N = static_cast<size_t>(P) + 1;
+    return (static_cast<size_t>(K) + N + N * kWave + (table ? static_cast<size_t>(K) * kWave : 0)) * sizeof(double);
+}
+
+struct Call {            // the scalars and pointers of one call, host or device
+    int dm, K;
+    const double* times;
+    int S_disc;
+    const double* dfs;
+    int im, P;
+    const double* T;
+    int S_infl;
+    const double* b;
+    int S;
+    int64_t n, mf;
+    const int64_t* fix_off;
+    const double *fix_tp, *fix_pay;
+    int64_t m;
+    const int64_t* cpn_off;
+    const double* cpn;
+    double *pv, *book;
+};
+
+int validate(const std::string& w, const Call& c) {
+    if (c.dm != ADR_INTERP_FLAT_FWD_RATES && c.dm != ADR_INTERP_LINEAR_FWD_RATES && c.dm != ADR_INTERP_LINEAR_ZERO_RATES)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": discount scheme must be FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) or "
+                                                      "LINEAR_ZERO_RATES (4)");
+    if (c.im != ADR_INTERP_FLAT_FWD_RATES && c.im != ADR_INTERP_LINEAR_ZERO_RATES)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": inflation scheme must be FLAT_FWD_RATES (1) or LINEAR_ZERO_RATES (4)");
+    if (c.K < 2 || c.K > ADR_SCENARIO_MAX_KNOTS)
+        return adr_set_error(ADR_ERR_INVALID, w + ": the knot grid needs 2 .. ADR_SCENARIO_MAX_KNOTS (4096) knots");
+    if (c.P < 1 || c.P > ADR_YOY_MAX_PILLARS)
+        return adr_set_error(ADR_ERR_INVALID, w + ": the inflation curve needs 1 .. ADR_YOY_MAX_PILLARS (64) pillars");
+    if (c.S < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one scenario is needed");
+    if ((c.S_disc != 1 && c.S_disc != c.S) || (c.S_infl != 1 && c.S_infl != c.S))
+        return adr_set_error(ADR_ERR_INVALID, w + ": S_disc and S_infl must each be 1 (a shared curve) or S");
+    if (c.n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one swap is needed");
+    if (c.mf < 0 || c.m < 0 || c.mf > INT32_MAX || c.m > INT32_MAX)
+        return adr_set_error(ADR_ERR_INVALID, w + ": flow counts must lie in 0 .. 2^31 - 1");
+    if (!c.times || !c.dfs || !c.T || !c.b) return adr_set_error(ADR_ERR_INVALID, w + ": null curve arrays");
+    if (!c.fix_off || !c.cpn_off) return adr_set_error(ADR_ERR_INVALID, w + ": null offsets (an empty leg has offsets of 0)");
+    if ((c.mf > 0 && (!c.fix_tp || !c.fix_pay)) || (c.m > 0 && !c.cpn))
+        return adr_set_error(ADR_ERR_INVALID, w + ": null cash-flow array");
+    if (!c.book) return adr_set_error(ADR_ERR_INVALID, w + ": book_pv is NULL");
+    return ADR_OK;
+}
+
+int check_host_arrays(const std::string& w, const Call& c) {
+    for (int k = 0; k < c.K; ++k)
+        if (!std::isfinite(c.times[k]) || (k > 0 && c.times[k] < c.times[k - 1]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": knot times must be finite and non-decreasing");
+    for (int64_t i = 0; i < static_cast<int64_t>(c.S_disc) * c.K; ++i)
+        if (!(c.dfs[i] > 0.0) || !std::isfinite(c.dfs[i]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": discount factors must be positive and finite (row " +
+                                                      std::to_string(i / c.K) + ", knot " + std::to_string(i % c.K) + ")");
+    for (int k = 0; k < c.P; ++k)
+        if (!std::isfinite(c.T[k]) || !(c.T[k] > (k ? c.T[k - 1] : 0.0)))
+            return adr_set_error(ADR_ERR_INVALID, w + ": pillar times must be increasing from > 0");
+    for (int64_t i = 0; i < static_cast<int64_t>(c.S_infl) * c.P; ++i)
+        if (!std::isfinite(c.b[i]) || !(c.b[i] > -1.0))
+            return adr_set_error(ADR_ERR_INVALID, w + ": breakeven rates must be finite and > -1 (row " +
+                                                      std::to_string(i / c.P) + ", pillar " + std::to_string(i % c.P) + ")");
+    if (c.fix_off[0] != 0 || c.fix_off[c.n] != c.mf) return adr_set_error(ADR_ERR_INVALID, w + ": fix_off must run from 0 to the flow count");
+    if (c.cpn_off[0] != 0 || c.cpn_off[c.n] != c.m) return adr_set_error(ADR_ERR_INVALID, w + ": cpn_off must run from 0 to m");
+    for (int64_t i = 0; i < c.n; ++i)
+        if (c.fix_off[i + 1] < c.fix_off[i] || c.cpn_off[i + 1] < c.cpn_off[i])
+            return adr_set_error(ADR_ERR_INVALID, w + ": offsets must be non-decreasing");
+    for (int64_t i = 0; i < c.mf; ++i)
+        if (!std::isfinite(c.fix_tp[i]) || !std::isfinite(c.fix_pay[i]))
+            return adr_set_error(ADR_ERR_INVALID, w + ": fixed-flow times and amounts must be finite");
+    for (int64_t i = 0; i < ADR_YOY_FIELDS * c.m; ++i)
+        if (!std::isfinite(c.cpn[i])) return adr_set_error(ADR_ERR_INVALID, w + ": coupon fields must be finite");
+    return ADR_OK;
+}
+
+template <bool kLog, bool kLds>
+hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
+    const size_t lds = lds_bytes(a.K, a.P, kLds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&yoy_scenario_pv_kernel<kLog, kLds>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((yoy_scenario_pv_kernel<kLog, kLds>), grid, dim3(kThreads), lds, stream, a);
+    return hipGetLastError();
+}
+
+// The two kernels on `stream`; every pointer of `c` is device memory.
+int enqueue(const std::string& w, adr_ctx* ctx, const Call& c, double* work, hipStream_t stream_or_null) {
+    int rc = validate(w, c);
+    if (rc != ADR_OK) return rc;
+    if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_yoy_scenario_pv_work doubles are needed)");
+    int device = 0;
+    hipStream_t stream = nullptr;
+    rc = adr_ctx_target(ctx, &device, &stream);
+    if (rc != ADR_OK) return rc;
+    if (stream_or_null) stream = stream_or_null;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    const int64_t chunks = (c.n + kChunk - 1) / kChunk, groups = (static_cast<int64_t>(c.S) + kWave - 1) / kWave;
+    if (groups > 65535) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 65535 * 64 scenarios in one launch");
+    // one block per compute unit when the tables fill the LDS; a group's blocks share its chunks round-robin
+    const int64_t per_group = std::max<int64_t>(1, (adr_ctx_compute_units(ctx) + groups - 1) / groups);
+    const int64_t bx = std::min<int64_t>((chunks + kWaves - 1) / kWaves, per_group);
+    const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(groups));
+    const Args a{c.times, c.dfs, c.T, c.b, c.K, c.P, c.S, c.dm, c.im, c.S_disc == 1 ? 0 : c.K, c.S_infl == 1 ? 0 : c.P,
+                 c.n, c.mf, c.m, chunks, c.fix_off, c.cpn_off, c.fix_tp, c.fix_pay, c.cpn, c.pv, work};
+    const bool in_lds = lds_bytes(c.K, c.P, true) <= kLdsBudget;
+    const bool lin = c.dm == ADR_INTERP_LINEAR_FWD_RATES;
+    if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
+    else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(yoy_scenario_book_kernel, dim3(static_cast<unsigned>((c.S + kRedEntries - 1) / kRedEntries)),
+                           dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(c.S), c.book);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+struct HostTab {
+    const double* p;     // the scenario's row of the converted table
+    double operator()(int k) const { return p[k]; }
+};
+
+template <bool kLog>
+void host_chunks(const Call& c, const Curves& cv, const double* tab, const double* itab, double* work, int64_t lo, int64_t hi) {
+    const int S = c.S, N = c.P + 1;
+    const size_t ds = c.S_disc == 1 ? 0 : c.K, is = c.S_infl == 1 ? 0 : N;
+    std::vector<Acc> acc(static_cast<size_t>(S));
+    std::vector<double> book(static_cast<size_t>(S));
+    for (int64_t ch = lo; ch < hi; ++ch) {
+        std::fill(book.begin(), book.end(), 0.0);
+        for (int64_t i = ch * kChunk; i < std::min(c.n, (ch + 1) * kChunk); ++i) {
+            Legs g{c.fix_tp, c.fix_pay, c.cpn, c.m, 0, 0, 0, 0};
+            const bool ok_fix = leg_range(c.fix_off, i, c.mf, &g.f0, &g.n_fix);
+            const bool ok = leg_range(c.cpn_off, i, c.m, &g.c0, &g.n_cpn) && ok_fix;
+            std::fill(acc.begin(), acc.end(), Acc{0.0, 0.0, 0.0});
+            for (int j = 0; ok && j < std::max(g.n_fix, g.n_cpn); ++j) {
+                const Slot slot = make_slot<kLog>(g, j, cv);
+                for (int s = 0; s < S; ++s)
+                    apply_slot<kLog>(slot, HostTab{tab + static_cast<size_t>(s) * ds}, HostTab{itab + static_cast<size_t>(s) * is}, acc[s]);
+            }
+            for (int s = 0; s < S; ++s) {
+                const double v = ok ? swap_pv(acc[s]) : NAN;
+                if (c.pv) c.pv[i * S + s] = v;
+                book[s] = book[s] + v;
+            }
+        }
+        std::copy(book.begin(), book.end(), work + ch * S);
+    }
+}
+
+}  // namespace yscen
+}  // namespace adr
+
+namespace YS = adr::yscen;
+
+extern "C" {
+
+int64_t adr_yoy_scenario_pv_work(int64_t n, int S) {
+    if (n < 1 || S < 1) return 0;
+    return (n + YS::kChunk - 1) / YS::kChunk * S;
+}
+
+int adr_yoy_scenario_pv_dev(adr_ctx* ctx, int disc_method, int K, const double* times_dev, int S_disc, const double* dfs_dev,
+                            int infl_method, int P, const double* T_dev, int S_infl, const double* b_dev, int S, int64_t n,
+                            int64_t n_fix, const int64_t* fix_off_dev, const double* fix_tp_dev, const double* fix_pay_dev,
+                            int64_t m, const int64_t* cpn_off_dev, const double* cpn_dev, double* pv_dev, double* book_pv_dev,
+                            double* work_dev, void* stream) {
+    const YS::Call c{disc_method, K, times_dev, S_disc, dfs_dev, infl_method, P, T_dev, S_infl, b_dev, S, n, n_fix,
+                     fix_off_dev, fix_tp_dev, fix_pay_dev, m, cpn_off_dev, cpn_dev, pv_dev, book_pv_dev};
+    return YS::enqueue("adr_yoy_scenario_pv_dev", ctx, c, work_dev, static_cast<hipStream_t>(stream));
+}
+
+int adr_yoy_scenario_pv(adr_ctx* ctx, int disc_method, int K, const double* times, int S_disc, const double* dfs,
+                        int infl_method, int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
+                        const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m, const int64_t* cpn_off,
+                        const double* cpn, double* pv, double* book_pv) {
+    const std::string w = "adr_yoy_scenario_pv";
+    const YS::Call h{disc_method, K, times, S_disc, dfs, infl_method, P, T, S_infl, b, S, n, n_fix,
+                     fix_off, fix_tp, fix_pay, m, cpn_off, cpn, pv, book_pv};
+    int rc = YS::validate(w, h);
+    if (rc == ADR_OK) rc = YS::check_host_arrays(w, h);
+    if (rc != ADR_OK) return rc;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    rc = adr_ctx_target(ctx, &device, &stream);
+    if (rc != ADR_OK) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    // one allocation: curves, flows, outputs, scratch, then the two offset arrays
+    const size_t d = sizeof(double), SK = static_cast<size_t>(S_disc) * K, SP = static_cast<size_t>(S_infl) * P;
+    const size_t W = static_cast<size_t>(adr_yoy_scenario_pv_work(n, S)), NS = static_cast<size_t>(n) * S;
+    const size_t n_dbl = K + SK + P + SP + 2 * static_cast<size_t>(n_fix) + ADR_YOY_FIELDS * static_cast<size_t>(m) +
+                         (pv ? NS : 0) + S + W;
+    const size_t off_bytes = static_cast<size_t>(n + 1) * sizeof(int64_t);
+    char* base = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + 2 * off_bytes);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double* p = reinterpret_cast<double*>(base);
+    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
+    double *dt = take(K), *ddf = take(SK), *dT = take(P), *db = take(SP);
+    double *dftp = take(n_fix), *dfpay = take(n_fix), *dcpn = take(ADR_YOY_FIELDS * static_cast<size_t>(m));
+    double* dpv = pv ? take(NS) : nullptr;
+    double *dbook = take(S), *dwork = take(W);
+    int64_t* dfo = reinterpret_cast<int64_t*>(p);
+    int64_t* dco = dfo + (n + 1);
+    struct Piece { void* dst; const void* src; size_t bytes; };
+    const Piece in[] = {{dt, times, K * d}, {ddf, dfs, SK * d}, {dT, T, P * d}, {db, b, SP * d},
+                        {dftp, fix_tp, static_cast<size_t>(n_fix) * d}, {dfpay, fix_pay, static_cast<size_t>(n_fix) * d},
+                        {dcpn, cpn, ADR_YOY_FIELDS * static_cast<size_t>(m) * d}, {dfo, fix_off, off_bytes}, {dco, cpn_off, off_bytes}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        const YS::Call c{disc_method, K, dt, S_disc, ddf, infl_method, P, dT, S_infl, db, S, n, n_fix,
+                         dfo, dftp, dfpay, m, dco, dcpn, dpv, dbook};
+        rc = YS::enqueue(w, ctx, c, dwork, stream);
+    }
+    if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book_pv, dbook, S * d, hipMemcpyDeviceToHost, stream);
+    const hipError_t es = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = es;
+    const hipError_t ef = hipFree(base);
+    if (rc != ADR_OK) return rc;
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+int adr_yoy_scenario_pv_host(int disc_method, int K, const double* times, int S_disc, const double* dfs, int infl_method,
+                             int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
+                             const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                             const int64_t* cpn_off, const double* cpn, double* pv, double* book_pv, int n_threads) {
+    const std::string w = "adr_yoy_scenario_pv_host";
+    const YS::Call c{disc_method, K, times, S_disc, dfs, infl_method, P, T, S_infl, b, S, n, n_fix,
+                     fix_off, fix_tp, fix_pay, m, cpn_off, cpn, pv, book_pv};
+    int rc = YS::validate(w, c);
+    if (rc == ADR_OK) rc = YS::check_host_arrays(w, c);
+    if (rc != ADR_OK) return rc;
+    const bool lin = disc_method == ADR_INTERP_LINEAR_FWD_RATES;
+    const int N = P + 1;
+    std::vector<double> tab(dfs, dfs + static_cast<size_t>(S_disc) * K);
+    if (!lin)
+        for (double& v : tab) v = std::log(v);
+    std::vector<double> ix(N), itab(static_cast<size_t>(S_infl) * N);
+    for (int k = 0; k < N; ++k) ix[k] = k ? T[k - 1] : 0.0;
+    for (int s = 0; s < S_infl; ++s)
+        for (int k = 0; k < N; ++k) itab[static_cast<size_t>(s) * N + k] = YS::node_log(T, b + static_cast<size_t>(s) * P, k);
+    const YS::Curves cv{times, ix.data(), K, N, disc_method, infl_method};
+    const int64_t chunks = (n + YS::kChunk - 1) / YS::kChunk;
+    std::vector<double> work(static_cast<size_t>(chunks) * S);
+    const int threads = n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4);
+    adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
+        if (lin) YS::host_chunks<false>(c, cv, tab.data(), itab.data(), work.data(), lo, hi);
+        else YS::host_chunks<true>(c, cv, tab.data(), itab.data(), work.data(), lo, hi);
+    });
+    YS::reduce_chunks(work.data(), chunks, S, book_pv);
+    return ADR_OK;
+}
+
+}  // extern "C"

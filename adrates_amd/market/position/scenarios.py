@@ -25,10 +25,13 @@ from typing import Dict, Iterable, List, Sequence, Union
 import numpy as np
 
 from ... import _native
-from ...trades.compiler import TradeBatch, compile_bonds, compile_frns, compile_ois
+from ...trades.compiler import (TradeBatch, compile_bonds, compile_frns, compile_ois, compile_yoy_coupons,
+                                compile_yoy_fixed_legs)
 from ...utils.error import LibError
-from ...utils.global_types import CurveTypes, InstrumentTypes, RequestTypes
+from ...utils.global_types import CurveTypes, InstrumentTypes, InterpTypes, RequestTypes
+from ...utils.helpers import to_tenor
 from .engine import BOND_CURVES, _SUPPORTED_INTERP, frn_is_single_curve
+from .inflation_engine import inflation_inputs
 from ..curves.curve_tables import build_engine_curve
 
 Shock = Union[float, Dict[str, float]]
@@ -144,6 +147,51 @@ def revalue_on_curves(method, times, dfs, trades, value_dt, per_trade=False, ctx
         finally:
             dev.close()
     return _finish(out, const, order, per_trade)
+
+
+def shocked_breakevens(curve, shock: Shock) -> np.ndarray:
+    """``[P]``: an inflation curve's breakeven rates under a shock in BASIS POINTS - a float shifts every pillar, a dict
+    ``{tenor: shift}`` the named ones, tenors as ``to_tenor(curve.swap_times)`` labels them.  An inflation curve has no
+    bootstrap (its nodes are ``(T_k, (1 + b_k) ** T_k)``), so the shocked rates ARE the shocked curve."""
+    _, T, b = inflation_inputs(curve)
+    if isinstance(shock, dict):
+        tenors = to_tenor(list(T))
+        unknown = sorted(set(shock) - set(tenors))
+        if unknown:
+            raise LibError(f"no pillar named {unknown} on the inflation curve (pillars: {tenors})")
+        return b + np.array([shock.get(t, 0.0) for t in tenors], dtype=np.float64) * 1e-4
+    return b + float(shock) * 1e-4
+
+
+def yoy_book_arrays(swaps_or_book, value_dt):
+    """``(fixed, coupons)`` for adr_yoy_scenario_pv: from a list of `YoYInflationSwap` (compiled against ``value_dt``)
+    or from a ready pair ``((fix_off, fix_tp, fix_pay) or None, coupon dict or None)``, which is taken as it is."""
+    if isinstance(swaps_or_book, tuple) and len(swaps_or_book) == 2 and not hasattr(swaps_or_book[0], "derivative_type"):
+        return swaps_or_book
+    swaps = list(swaps_or_book)
+    if not swaps:
+        raise LibError("no swaps to revalue")
+    return compile_yoy_fixed_legs(swaps, value_dt), compile_yoy_coupons(swaps, value_dt)
+
+
+def revalue_yoy_on_curves(disc_method, times, dfs, infl_method, T, b, swaps_or_book, value_dt, per_trade=False, ctx=None,
+                          host=False):
+    """PVs of a YoY inflation swap book under caller-supplied scenario PAIRS, in one launch of csrc/yoy_scenario_pv.hip.
+
+    ``disc_method`` / ``infl_method``: `InterpTypes` members or their values; ``times [K]`` and ``dfs [S, K]`` the
+    discount scenarios as `revalue_on_curves` takes them, ``T [P]`` and ``b [S, P]`` the inflation pillars and the
+    breakeven rates per scenario (`shocked_breakevens`, or a history of curves).  A single row, ``dfs [K]`` or
+    ``b [P]``, means that curve is not shocked and is shared by all scenarios.  ``swaps_or_book``: `YoYInflationSwap`
+    objects or compiled arrays (`yoy_book_arrays`).  Returns ``{"book_pv": [S]}`` and, with ``per_trade``,
+    ``"pv": [S, n]``.  ``host=True`` runs the CPU twin of the kernel (same arithmetic and summation order; no GPU)."""
+    dm, im = int(getattr(disc_method, "value", disc_method)), int(getattr(infl_method, "value", infl_method))
+    if dm not in _SUPPORTED_INTERP or im not in (InterpTypes.LINEAR_ZERO_RATES.value, InterpTypes.FLAT_FWD_RATES.value):
+        raise LibError("Invalid interpolation scheme.")
+    fixed, coupons = yoy_book_arrays(swaps_or_book, value_dt)
+    if host:
+        return _native.yoy_scenario_pv_host(dm, times, dfs, im, T, b, fixed, coupons, per_trade=per_trade)
+    return _native.yoy_scenario_pv(ctx or _native.default_context(), dm, times, dfs, im, T, b, fixed, coupons,
+                                   per_trade=per_trade)
 
 
 def _tail(pnl, level):

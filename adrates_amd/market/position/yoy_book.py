@@ -15,7 +15,8 @@ from ...trades.rates.yoy_inflation_swap import YoYInflationSwap
 from ...utils.error import LibError
 from ...utils.global_types import RequestTypes
 from .engine import Engine
-from .inflation_engine import price_yoy, yoy_curves
+from .inflation_engine import inflation_inputs, price_yoy, yoy_curves
+from .scenarios import revalue_yoy_on_curves, shocked_breakevens, yoy_book_arrays
 
 
 def tile_yoy_book(book: dict, reps: int) -> dict:
@@ -64,3 +65,96 @@ class YoYBook:
         out["curve_type"], out["inflation_curve_type"], out["currency"] = (self.curve_type, self.inflation_curve_type,
                                                                            self.currency)
         return out
+
+    # ------------------------------------------------------------------------------------------ scenario revaluation
+    def _arrays(self):
+        """The book's fixed legs and YoY coupons, compiled once against the model's value date."""
+        if getattr(self, "_compiled", None) is None:
+            self._compiled = yoy_book_arrays(self.swaps, self.model.value_dt)
+        return self._compiled
+
+    def _breakeven_rows(self, grid, inflation_shocks, breakevens):
+        """``b`` [S, P] or None (the inflation curve is not shocked), after checking the scenario counts."""
+        if inflation_shocks is not None and breakevens is not None:
+            raise LibError("give inflation_shocks or breakevens, not both")
+        b = None
+        if inflation_shocks is not None:
+            b = np.array([shocked_breakevens(self.inflation_curve, s) for s in inflation_shocks], dtype=np.float64)
+        elif breakevens is not None:
+            b = np.asarray(breakevens, dtype=np.float64)
+        P = len(self.inflation_curve.swap_times)
+        if b is not None and (b.ndim != 2 or b.shape[1] != P or b.shape[0] < 1):
+            raise LibError(f"breakeven scenarios must have shape [n_scenarios, {P}], not {list(b.shape)}")
+        if grid is None and b is None:
+            raise LibError("no scenarios: give a ScenarioGrid on the discount curve, inflation_shocks or breakevens")
+        if grid is not None:
+            if grid.curve_name != self.curve_type.name or grid.model.value_dt != self.model.value_dt:
+                raise LibError(f"the grid shocks {grid.curve_name}, the book discounts on {self.curve_type.name} "
+                               "(same value date needed)")
+            if b is not None and b.shape[0] != len(grid):
+                raise LibError(f"{len(grid)} discount scenarios but {b.shape[0]} inflation scenarios")
+        return b
+
+    def _revalue_in_place(self, grid, b, per_trade):
+        """One launch of adr_yoy_scenario_pv_dev that reads the grid's discount factors where the device builder left
+        them (adr_curve_set_arrays): only the book, the breakeven rows and the results cross the bus."""
+        import torch
+        ctx = grid._ctx
+        arr = _native.curve_set_arrays(grid._set)
+        (fix_off, fix_tp, fix_pay), book = self._arrays()
+        cpn_off, cpn = _native.yoy_pack(book)
+        im, T, b0 = inflation_inputs(self.inflation_curve)
+        rows = b0[None, :] if b is None else b
+        dev = torch.device("cuda", ctx.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        t = {k: up(v) for k, v in dict(T=T, b=rows, fix_off=fix_off, fix_tp=fix_tp, fix_pay=fix_pay, cpn_off=cpn_off,
+                                       cpn=cpn).items()}
+        S, n = arr["S"], len(self.swaps)
+        out_book = torch.empty(S, dtype=torch.float64, device=dev)
+        pv = torch.empty((n, S), dtype=torch.float64, device=dev) if per_trade else None
+        work = torch.empty(_native.yoy_scenario_pv_work(n, S), dtype=torch.float64, device=dev)
+        ptrs = {k: v.data_ptr() if v.numel() else 0 for k, v in t.items()}
+        ptrs.update(times=arr["times"], dfs=arr["dfs"])
+        torch.cuda.synchronize(dev)
+        _native.yoy_scenario_pv_dev(ctx, arr["method"], arr["K"], S, im, T.size, rows.shape[0], S, n, fix_tp.size, cpn.shape[1],
+                                    ptrs, out_book.data_ptr(), work.data_ptr(), pv.data_ptr() if per_trade else 0)
+        ctx.sync()
+        out = {"book_pv": out_book.cpu().numpy()}
+        if per_trade:
+            out["pv"] = pv.cpu().numpy().T
+        return out
+
+    def revalue(self, grid=None, inflation_shocks=None, breakevens=None, per_trade: bool = False) -> dict:
+        """The book's PV under joint scenarios, in ONE launch of csrc/yoy_scenario_pv.hip: ``{"book_pv": [S]}`` and,
+        with ``per_trade``, ``"pv": [S, n]``.
+
+        ``grid``: a `ScenarioGrid` on the book's discount curve - scenario s discounts on the grid's curve s, read in
+        place on the device; None: the discount curve is not shocked.  ``inflation_shocks``: a list of shocks in basis
+        points for `shocked_breakevens` (a float shifts every pillar, a dict the named tenors), or ``breakevens``: a
+        ready ``[S, P]`` array of breakeven rates (historical simulation); neither: the inflation curve is not
+        shocked.  Where both curves are shocked the counts must agree: scenario s is the PAIR (discount curve s,
+        breakeven row s).  The result feeds `historical_var` / `expected_shortfall` through `pnl`."""
+        b = self._breakeven_rows(grid, inflation_shocks, breakevens)
+        if grid is not None:
+            return self._revalue_in_place(grid, b, per_trade)
+        host = self._engine._device_curve(self.curve)["host"]
+        im, T, _ = inflation_inputs(self.inflation_curve)
+        return revalue_yoy_on_curves(self.curve._interp_type.value, host.times, host.dfs, im, T, b, self._arrays(),
+                                     self.model.value_dt, per_trade=per_trade, ctx=self._engine._device_curve(self.curve)["ctx"])
+
+    def pnl(self, grid=None, inflation_shocks=None, breakevens=None) -> np.ndarray:
+        """``[S]``: the book's PV under each scenario minus its PV on the unshocked pair, which the same launch prices
+        as one more scenario row (as `ScenarioGrid.pnl` does: the grid's rows are downloaded once and the host
+        builder's base curve appended), so the difference carries no noise between kernels and a zero shock gives
+        exactly 0."""
+        b = self._breakeven_rows(grid, inflation_shocks, breakevens)
+        im, T, b0 = inflation_inputs(self.inflation_curve)
+        if grid is not None:
+            times, dfs, ctx = grid.base.times, np.vstack([grid._dfs(), grid.base.dfs[None, :]]), grid._ctx
+        else:
+            cur = self._engine._device_curve(self.curve)
+            times, dfs, ctx = cur["host"].times, cur["host"].dfs, cur["ctx"]
+        rows = b0 if b is None else np.vstack([b, b0[None, :]])
+        book = revalue_yoy_on_curves(self.curve._interp_type.value, times, dfs, im, T, rows, self._arrays(),
+                                     self.model.value_dt, ctx=ctx)["book_pv"]
+        return book[:-1] - book[-1]

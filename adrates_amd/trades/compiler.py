@@ -200,6 +200,24 @@ def compile_yoy_coupons(swaps: Iterable, value_dt) -> dict:
     return out
 
 
+def compile_yoy_fixed_legs(swaps: Iterable, value_dt):
+    """``(fix_off [n + 1], fix_tp, fix_pay)``: the fixed legs of YoY swaps as adr_yoy_scenario_pv reads them - what
+    `compile_yoy_swaps` builds when every projected amount is left out: payments ``sign * coupon * alpha * notional``
+    in schedule order, the principal on the last flow, times in the swap's day count from ``value_dt``.  Together with
+    `compile_yoy_coupons` it holds the flows of `compile_yoy_swaps`, with the same signs."""
+    fix_off, fix_tp, fix_pay = [0], [], []
+    for s in swaps:
+        _yoy_check(s)
+        fl = s._fixed_leg
+        sign = +1.0 if fl._leg_type == SwapTypes.RECEIVE else -1.0
+        pays = [sign * (fl._cpn * float(a) * fl._notional) for a in fl._year_fracs]
+        pays[-1] += sign * float(fl._principal)
+        fix_tp += _times(fl._payment_dts, value_dt, fl._dc_type)
+        fix_pay += pays
+        fix_off.append(len(fix_tp))
+    return np.array(fix_off, dtype=np.int64), np.array(fix_tp, dtype=np.float64), np.array(fix_pay, dtype=np.float64)
+
+
 def compile_yoy_swaps(swaps: Iterable, value_dt, amounts) -> TradeBatch:
     """Fixed-flows-only batch of YoY swaps for their discount-curve Greeks: with the inflation curve held fixed the
     reference's engine (cavour/market/position/engine.py:1129-1353) prices the fixed leg (`_price_fixed_leg_jax`,

@@ -552,6 +552,60 @@ int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, c
                          const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
                          const double* flt_sign, double* pv, double* book_pv, int n_threads);
 
+/*
+ * Inflation scenario revaluation: the PV of every YoY inflation swap of a book under S scenarios, each a PAIR of a
+ * discount curve row and a breakeven row - VaR, expected shortfall and stress P&L under joint rates-and-breakeven
+ * shocks in one launch, instead of one adr_yoy_risk, one host pass and one adr_price per scenario.
+ *
+ *     pv[i][s] =  sum_f fix_pay_f D_s(tp_f)                                          [tp_f > 0]
+ *               + sum_j scale_j (I_s(te_j) / I_s(ts_j) - 1 + spread_j) D_s(tp_j)     [tp_j > 0]     (both masks strict)
+ *     book_pv[s] = sum_i pv[i][s]
+ *
+ * D_s(t): InterpolatorAd.simple_interpolate on (times[K], dfs[s][K]), disc_method 1, 2 or 4, as adr_scenario_pv reads it
+ * (the first knot is t = 0 with discount factor 1; no division by D(0); K = 2 .. ADR_SCENARIO_MAX_KNOTS).  I_s(t): the
+ * same rule on the nodes (0, 1), (T_k, (1 + b[s][k])^T_k), infl_method ADR_INTERP_LINEAR_ZERO_RATES or
+ * ADR_INTERP_FLAT_FWD_RATES (anything else is ADR_ERR_UNSUPPORTED), P = 1 .. ADR_YOY_MAX_PILLARS, formed as adr_yoy_risk
+ * forms them: for one scenario the projected amounts are adr_yoy_risk's up to the rounding of one exponent.
+ *
+ * Broadcasting: S_disc and S_infl are each 1 or S.  One shared row means "this curve is not shocked" and is read with
+ * stride 0: discount-only, inflation-only and joint scenarios from one entry.
+ *
+ * The book, n >= 1 swaps: the fixed legs in CSR form fix_off[n+1], fix_tp[n_fix], fix_pay[n_fix] (signs folded in, the
+ * principal on the last flow) and the YoY coupons as adr_yoy_risk takes them, cpn_off[n+1] and the field-major
+ * cpn[ADR_YOY_FIELDS][m].  Either leg may be empty, for a swap or for the whole book (offsets of 0; the value arrays
+ * may then be NULL).  Within a swap, index c = 0, 1, ... adds coupon c to the YoY sum and fixed flow c to the fixed
+ * sum, each in order from 0.0; pv = fixed sum + YoY sum.
+ *
+ * Outputs: book_pv[S] always; pv[n][S] (swap-major, the layout of adr_scenario_pv) when given.  book_pv follows
+ * adr_scenario_pv's rule: the swaps in chunks of ADR_SCENARIO_CHUNK summed in order from 0.0, chunk j added to slot
+ * j % 64 in order, then slots 0-31 += 32-63, ..., 0 += 1; no atomics.  A scenario's results do not depend on S, on the
+ * other scenarios, on broadcasting or on the launch shape, and are bit-identical from run to run.
+ *
+ * adr_yoy_scenario_pv: host arrays in and out, blocks; refuses what it can read (offsets that do not run from 0 to
+ * the count or decrease, non-finite times or amounts, 1 + b <= 0, non-positive discount factors, T not increasing from
+ * > 0).  adr_yoy_scenario_pv_dev: device arrays, enqueued on `stream` (NULL: the ctx's own), no allocation and no
+ * synchronisation (two kernels in one chain); work_dev holds adr_yoy_scenario_pv_work(n, S) doubles; only the scalars
+ * are checked: a swap whose offset pair is negative, decreasing or ends beyond the count reads no flow and gets a NaN
+ * PV, which carries into book_pv.  adr_yoy_scenario_pv_host: the same per-date and per-coupon code in the same order on
+ * CPU threads (no GPU; n_threads <= 0: as many as the machine suggests, at most 16); it differs from the device by
+ * exp / log only.
+ */
+int adr_yoy_scenario_pv(adr_ctx* ctx, int disc_method, int K, const double* times, int S_disc, const double* dfs,
+                        int infl_method, int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
+                        const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m, const int64_t* cpn_off,
+                        const double* cpn, double* pv, double* book_pv);
+/* Doubles of scratch adr_yoy_scenario_pv_dev needs: ceil(n / ADR_SCENARIO_CHUNK) * S. */
+int64_t adr_yoy_scenario_pv_work(int64_t n, int S);
+int adr_yoy_scenario_pv_dev(adr_ctx* ctx, int disc_method, int K, const double* times_dev, int S_disc, const double* dfs_dev,
+                            int infl_method, int P, const double* T_dev, int S_infl, const double* b_dev, int S, int64_t n,
+                            int64_t n_fix, const int64_t* fix_off_dev, const double* fix_tp_dev, const double* fix_pay_dev,
+                            int64_t m, const int64_t* cpn_off_dev, const double* cpn_dev, double* pv_dev, double* book_pv_dev,
+                            double* work_dev, void* stream);
+int adr_yoy_scenario_pv_host(int disc_method, int K, const double* times, int S_disc, const double* dfs, int infl_method,
+                             int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
+                             const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                             const int64_t* cpn_off, const double* cpn, double* pv, double* book_pv, int n_threads);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
