@@ -107,6 +107,15 @@ _SIGNATURES = {
                                           C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "adr_yoy_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int,
                                            C.c_int64, C.c_int64, _i64p, _dp, _dp, C.c_int64, _i64p, _dp, _dp, _dp, C.c_int]),
+    "adr_credit_scenario_pv": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _vp, _dp,
+                                         _i32p, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp]),
+    "adr_credit_scenario_pv_set": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _vp, _dp, _i32p, C.c_int64, _dp, C.c_int64, _dp,
+                                             _dp, _dp]),
+    "adr_credit_scenario_pv_work": (C.c_int64, [C.c_int64, C.c_int]),
+    "adr_credit_scenario_pv_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp,
+                                             _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "adr_credit_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int64,
+                                              _i64p, _i64p] + [_dp] * 11 + [_dp, _i32p, _dp, _dp, _dp, _dp, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -905,6 +914,118 @@ def yoy_scenario_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: int, inf
                                           int(P), g("T"), int(S_infl), g("b"), int(S), int(n_swaps), int(n_fix), g("fix_off"),
                                           g("fix_tp"), g("fix_pay"), int(n_coupons), g("cpn_off"), g("cpn"), v(pv_ptr),
                                           v(book_ptr), v(work_ptr), _vp(stream or None)), "adr_yoy_scenario_pv_dev")
+
+
+CREDIT_MAX_BUCKETS = 32                                     # ADR_CREDIT_MAX_BUCKETS
+
+
+def _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, n_fix, n_flt):
+    """The spread side of adr_credit_scenario_pv: ``dz`` [S, G], [G] or None (no buckets), ``z`` [n], ``bucket`` [n]
+    (int32, -1: not shocked), ``fix_tau`` / ``flt_tau`` one spread time per fixed flow / float coupon of the batch."""
+    dz = np.zeros((1, 0)) if dz is None else _f64(np.atleast_2d(dz))
+    if dz.ndim != 2:
+        raise LibError(f"dz must have shape [n_scenarios, n_buckets] or [n_buckets], not {list(dz.shape)}")
+    z = _f64(z).reshape(-1)
+    bucket = np.ascontiguousarray(bucket, dtype=np.int32).reshape(-1)
+    fix_tau, flt_tau = _f64(fix_tau).reshape(-1), _f64(flt_tau).reshape(-1)
+    if z.size != n or bucket.size != n:
+        raise LibError(f"z and bucket need one entry per trade ({n}), not {z.size} and {bucket.size}")
+    if fix_tau.size != n_fix or flt_tau.size != n_flt:
+        raise LibError(f"fix_tau / flt_tau need one entry per fixed flow ({n_fix}) / float coupon ({n_flt}), not "
+                       f"{fix_tau.size} / {flt_tau.size}")
+    return dz, z, bucket, fix_tau, flt_tau
+
+
+def _credit_counts(n_disc, n_spr):
+    S = max(n_disc, n_spr)
+    if n_disc not in (1, S) or n_spr not in (1, S):
+        raise LibError(f"{n_disc} discount rows and {n_spr} spread-shock rows: each must be one shared row or one row per "
+                       "scenario")
+    return S
+
+
+def credit_scenario_pv(ctx: Context, method: int, times, dfs, dz, trades: DeviceTrades, z, bucket, fix_tau, flt_tau,
+                       per_trade=False):
+    """PVs of an uploaded batch under scenario PAIRS (adr_credit_scenario_pv, blocking): discount rows ``dfs`` [S, K] or
+    one shared row [K] on the knots ``times``, spread shocks ``dz`` [S, G], one shared row [G] or None; per trade the
+    spread ``z`` and the bucket (-1: not shocked), per flow the spread times in the batch's flow order.  Returns
+    ``book_pv`` [S] and, with ``per_trade``, ``pv`` [S, n]."""
+    times, dfs = _scenario_curves(times, dfs)
+    n = trades.n_trades
+    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
+    S = _credit_counts(dfs.shape[0], dz.shape[0])
+    book = np.empty(S)
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_credit_scenario_pv(ctx._h, int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), dz.shape[1],
+                                         dz.shape[0], _ptr(dz) if dz.size else None, S, trades._h, _ptr(z), _ptr(bucket, _i32p),
+                                         fix_tau.size, _ptr(fix_tau), flt_tau.size, _ptr(flt_tau), _ptr(pv), _ptr(book)),
+           "adr_credit_scenario_pv")
+    return _scenario_result(book, pv, per_trade)
+
+
+def credit_scenario_pv_set(ctx: Context, curve_set: CurveSet, dz, trades: DeviceTrades, z, bucket, fix_tau, flt_tau,
+                           per_trade=False):
+    """`credit_scenario_pv` on the curves of a `CurveSet`, read in place where `curve_set_arrays` finds them
+    (adr_credit_scenario_pv_set): one scenario per curve of the set; ``dz`` has that many rows, one shared row or is None."""
+    n, S = trades.n_trades, len(curve_set)
+    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
+    if dz.shape[0] not in (1, S):
+        raise LibError(f"{dz.shape[0]} spread-shock rows for a set of {S} curves: one shared row or one row per curve")
+    book = np.empty(S)
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_credit_scenario_pv_set(ctx._h, curve_set._h, dz.shape[1], dz.shape[0], _ptr(dz) if dz.size else None,
+                                             trades._h, _ptr(z), _ptr(bucket, _i32p), fix_tau.size, _ptr(fix_tau), flt_tau.size,
+                                             _ptr(flt_tau), _ptr(pv), _ptr(book)), "adr_credit_scenario_pv_set")
+    return _scenario_result(book, pv, per_trade)
+
+
+def credit_scenario_pv_host(method: int, times, dfs, dz, batch, z, bucket, fix_tau, flt_tau, per_trade=False, n_threads=0):
+    """`credit_scenario_pv` on the CPU (adr_credit_scenario_pv_host) for a `TradeBatch`: the same per-coupon arithmetic
+    and the same order of the book sum; no GPU needed."""
+    times, dfs = _scenario_curves(times, dfs)
+    n = int(batch.n_trades)
+    fo = np.ascontiguousarray(batch.fix_off, dtype=np.int64)
+    lo = np.ascontiguousarray(batch.flt_off, dtype=np.int64)
+    if fo.shape != (n + 1,) or lo.shape != (n + 1,):
+        raise LibError("offset arrays must have n_trades + 1 entries")
+    a = {k: _f64(getattr(batch, k)) for k in ("fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional",
+                                              "spread", "fix_sign", "flt_sign")}
+    w = getattr(batch, "flt_weight", None)
+    w = None if w is None else _f64(w)
+    if w is not None and w.shape != a["flt_tp"].shape:
+        raise LibError("flt_weight must have one entry per float coupon")
+    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, a["fix_tp"].size,
+                                                            a["flt_tp"].size)
+    S = _credit_counts(dfs.shape[0], dz.shape[0])
+    book = np.empty(S)
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_credit_scenario_pv_host(int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), dz.shape[1],
+                                              dz.shape[0], _ptr(dz) if dz.size else None, S, n, _ptr(fo, _i64p), _ptr(lo, _i64p),
+                                              _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]), _ptr(a["flt_ts"]),
+                                              _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w), _ptr(a["notional"]),
+                                              _ptr(a["spread"]), _ptr(a["fix_sign"]), _ptr(a["flt_sign"]), _ptr(z),
+                                              _ptr(bucket, _i32p), _ptr(fix_tau), _ptr(flt_tau), _ptr(pv), _ptr(book),
+                                              int(n_threads)), "adr_credit_scenario_pv_host")
+    return _scenario_result(book, pv, per_trade)
+
+
+def credit_scenario_pv_work(n_trades: int, n_scenarios: int) -> int:
+    """Doubles of scratch `credit_scenario_pv_dev` needs."""
+    return int(load().adr_credit_scenario_pv_work(int(n_trades), int(n_scenarios)))
+
+
+def credit_scenario_pv_dev(ctx: Context, method: int, K: int, S_disc: int, G: int, S_spr: int, S: int, trades: DeviceTrades,
+                           n_fix: int, n_flt: int, ptrs, book_ptr: int, work_ptr: int, pv_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_credit_scenario_pv_dev): ``ptrs`` maps ``times`` [K], ``dfs`` [S_disc, K], ``dz`` [S_spr, G]
+    (0 when G = 0), ``z`` [n], ``bucket`` [n] (int32), ``fix_tau`` [n_fix] and ``flt_tau`` [n_flt] to device pointers
+    (integers); outputs ``book_pv`` [S] and ``pv`` [n, S] (trade-major; 0: not wanted); `credit_scenario_pv_work`
+    doubles of scratch."""
+    v = lambda p: _vp(int(p) or None)
+    g = lambda k: v(ptrs.get(k, 0))
+    _check(load().adr_credit_scenario_pv_dev(ctx._h, int(method), int(K), g("times"), int(S_disc), g("dfs"), int(G), int(S_spr),
+                                             g("dz"), int(S), trades._h, g("z"), g("bucket"), int(n_fix), g("fix_tau"),
+                                             int(n_flt), g("flt_tau"), v(pv_ptr), v(book_ptr), v(work_ptr),
+                                             _vp(stream or None)), "adr_credit_scenario_pv_dev")
 
 
 _default_ctx = {}

@@ -124,3 +124,9 @@ class BondBook:
         out = price_bonds(self._engine, self.curve, self.bonds, reqs, per_trade=per_trade, aggregate=aggregate)
         out["curve_type"], out["currency"] = self.curve_type, self.currency
         return out
+
+    def revalue(self, grid, z_spreads, buckets=None, spread_shocks=None, per_trade=False) -> dict:
+        """The book's PV at the z-spreads ``z_spreads`` (one per bond, e.g. ``measures(...)["z"]``) under every
+        scenario of ``grid``, a `ScenarioGrid` of this book's curve, paired with ``spread_shocks``:
+        `ScenarioGrid.revalue_credit`."""
+        return grid.revalue_credit(self.bonds, z_spreads, buckets=buckets, spread_shocks=spread_shocks, per_trade=per_trade)

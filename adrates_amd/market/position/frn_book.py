@@ -157,3 +157,9 @@ class FRNBook:
                          index_model=None if single else self.index_curve)
         out["curve_type"], out["currency"] = self.curve_type, self.currency
         return out
+
+    def revalue(self, grid, dms, buckets=None, spread_shocks=None, per_trade=False) -> dict:
+        """The book's PV at the discount margins ``dms`` (one per FRN, e.g. ``measures(...)["dm"]``) under every
+        scenario of ``grid``, a `ScenarioGrid` of this book's curve, paired with ``spread_shocks``:
+        `ScenarioGrid.revalue_credit` (single-curve FRNs only)."""
+        return grid.revalue_credit(self.frns, dms, buckets=buckets, spread_shocks=spread_shocks, per_trade=per_trade)

@@ -17,14 +17,22 @@ shortfall and stress tests - does not loop over the scenarios: `ScenarioGrid.rev
 / `pnl` and `revalue_on_curves` price the book under all curves in one launch of
 csrc/scenario_pv.hip (adr_scenario_pv), which reads the trades once and takes
 discount factors only (no Jacobians).
+
+Credit books - bonds at their z-spreads, FRNs at their discount margins - are
+revalued under joint (curve, spread) scenarios by `ScenarioGrid.revalue_credit` /
+`pnl_credit` and `revalue_credit_on_curves` in one launch of
+csrc/credit_scenario_pv.hip (adr_credit_scenario_pv): a spread per trade, a spread
+shock per scenario and credit bucket.
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List, Sequence, Union
+from dataclasses import dataclass
+from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
 from ... import _native
+from ...trades.credit.bond import SPREAD_DAYS_IN_YEAR
 from ...trades.compiler import (TradeBatch, compile_bonds, compile_frns, compile_ois, compile_yoy_coupons,
                                 compile_yoy_fixed_legs)
 from ...utils.error import LibError
@@ -147,6 +155,135 @@ def revalue_on_curves(method, times, dfs, trades, value_dt, per_trade=False, ctx
         finally:
             dev.close()
     return _finish(out, const, order, per_trade)
+
+
+@dataclass
+class CreditBook:
+    """`compile_credit_book`'s result: `compile_book`'s ``batch``, ``pv_const`` and ``order`` plus, in BATCH order, the
+    spread times per fixed flow / float coupon, the spread ``z`` and the bucket index per trade, and the bucket labels."""
+    batch: TradeBatch
+    pv_const: Optional[np.ndarray]
+    order: np.ndarray
+    fix_tau: np.ndarray
+    flt_tau: np.ndarray
+    z: np.ndarray
+    bucket: np.ndarray
+    labels: list
+
+
+def compile_credit_book(trades, value_dt, curve_type: CurveTypes, spreads, buckets=None) -> CreditBook:
+    """A mixed list of `OIS`, `Bond` and single-curve `FRN` objects as ONE batch (`compile_book`: the same lists, the
+    same refusals, the same ``order``) with what adr_credit_scenario_pv needs besides it.
+
+    ``spreads``: one per trade of the list (or one number for all) - the z-spread of a bond, the discount margin of an
+    FRN, as `BondBook.measures` / `FRNBook.measures` return them; an OIS has none: anything but 0 is refused.
+    Spread times: a bond flow's ``(payment_dt - value_dt) / SPREAD_DAYS_IN_YEAR`` (the time of `Bond.z_spread` with
+    settlement at the value date), an FRN flow's year fraction from the value date in the FRN's day count (the DM
+    time with settlement at the value date), 0 for an OIS.  An FRN coupon paid at the value time (``pv_const``) has
+    spread time 0 and stays as it is.
+
+    ``buckets``: one hashable label or None (not shocked) per trade - an issuer, a rating, a sector.  The labels are
+    numbered 0 .. G - 1 in order of first appearance and returned as ``labels``; more than 32 raise `LibError`."""
+    if isinstance(trades, TradeBatch):
+        raise LibError("a compiled TradeBatch carries no dates: the spread times need the Bond and FRN objects")
+    trades = list(trades)
+    batch, const, order = compile_book(trades, value_dt, curve_type)
+    n = len(trades)
+    try:
+        spreads = np.broadcast_to(np.asarray(spreads, dtype=np.float64), (n,))
+    except ValueError:
+        raise LibError(f"spreads needs one entry per trade ({n})") from None
+    if not np.all(np.isfinite(spreads)):
+        raise LibError("spreads must be finite")
+    if buckets is None:
+        buckets = [None] * n
+    buckets = list(buckets)
+    if len(buckets) != n:
+        raise LibError(f"buckets needs one entry per trade ({n}), not {len(buckets)}")
+    labels, index = [], {}
+    for i, lab in enumerate(buckets):
+        if lab is None:
+            continue
+        if trades[i].derivative_type == InstrumentTypes.OIS_SWAP:
+            raise LibError(f"trade {i} is an OIS: it carries no credit spread, so its bucket must be None")
+        if lab not in index:
+            index[lab] = len(labels)
+            labels.append(lab)
+    if len(labels) > _native.CREDIT_MAX_BUCKETS:
+        raise LibError(f"{len(labels)} distinct buckets: at most {_native.CREDIT_MAX_BUCKETS} fit one launch")
+    fix_tau = np.zeros(batch.fix_tp.shape[0])
+    flt_tau = np.zeros(batch.flt_tp.shape[0])
+    for j, i in enumerate(order):
+        t = trades[i]
+        f0, f1 = int(batch.fix_off[j]), int(batch.fix_off[j + 1])
+        l0, l1 = int(batch.flt_off[j]), int(batch.flt_off[j + 1])
+        if t.derivative_type == InstrumentTypes.OIS_SWAP:
+            if spreads[i] != 0.0:
+                raise LibError(f"trade {i} is an OIS: it carries no credit spread, so its spread must be 0")
+        elif t.derivative_type == InstrumentTypes.BOND:
+            tau = [(dt - value_dt) / SPREAD_DAYS_IN_YEAR for dt in t._payment_dts]
+            if len(tau) != f1 - f0:
+                raise LibError(f"trade {i}: {len(tau)} payment dates for {f1 - f0} compiled flows")
+            fix_tau[f0:f1] = tau
+        else:
+            # compile_frns' times ARE year fractions from the value date in the FRN's day count
+            fix_tau[f0:f1] = batch.fix_tp[f0:f1]
+            flt_tau[l0:l1] = batch.flt_tp[l0:l1]
+    z = np.array([spreads[i] for i in order], dtype=np.float64)
+    bucket = np.array([-1 if buckets[i] is None else index[buckets[i]] for i in order], dtype=np.int32)
+    return CreditBook(batch, const, order, fix_tau, flt_tau, z, bucket, labels)
+
+
+def shocked_spreads(labels, shock: Shock) -> np.ndarray:
+    """``[G]``: one scenario's spread shocks in DECIMALS from a shock in BASIS POINTS - a float shifts every bucket, a
+    dict ``{label: shift}`` the named ones; ``labels`` as `compile_credit_book` returns them."""
+    labels = list(labels)
+    if isinstance(shock, dict):
+        unknown = [k for k in shock if k not in labels]
+        if unknown:
+            raise LibError(f"no bucket named {unknown} (buckets: {labels})")
+        return np.array([shock.get(lab, 0.0) for lab in labels], dtype=np.float64) * 1e-4
+    return np.full(len(labels), float(shock) * 1e-4)
+
+
+def _spread_rows(spread_shocks, G):
+    """``spread_shocks`` as [rows, G] decimals, or None where there is nothing to shock."""
+    if spread_shocks is None:
+        return None if G == 0 else np.zeros((1, G))
+    dz = np.atleast_2d(np.asarray(spread_shocks, dtype=np.float64))
+    if dz.ndim != 2 or dz.shape[1] != G:
+        raise LibError(f"spread_shocks must have shape [n_scenarios, {G}] or [{G}] (one column per bucket), not "
+                       f"{list(np.shape(spread_shocks))}")
+    return None if G == 0 else dz
+
+
+def revalue_credit_on_curves(method, times, dfs, spread_shocks, trades, spreads, buckets, value_dt, per_trade=False,
+                             ctx=None, host=False, curve_type=None):
+    """PVs of a credit book under caller-supplied scenario PAIRS, in one launch of csrc/credit_scenario_pv.hip.
+
+    ``times [K]`` and ``dfs [S, K]`` as `revalue_on_curves` takes them; ``spread_shocks [S, G]`` in decimals, one column
+    per bucket label (`shocked_spreads` makes a row).  A single row, ``dfs [K]`` or ``spread_shocks [G]``, is shared
+    by all scenarios; ``spread_shocks=None`` shocks no spread.  ``trades``, ``spreads`` and ``buckets``: see
+    `compile_credit_book`.  Returns ``{"book_pv": [S], "labels": [...]}`` and, with ``per_trade``, ``"pv": [S, n]`` in
+    the list's order.  ``host=True`` runs the CPU twin of the kernel (same arithmetic and summation order; no GPU)."""
+    method = int(getattr(method, "value", method))
+    if method not in _SUPPORTED_INTERP:
+        raise LibError("Invalid interpolation scheme.")
+    book = compile_credit_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA, spreads, buckets)
+    dz = _spread_rows(spread_shocks, len(book.labels))
+    if host:
+        out = _native.credit_scenario_pv_host(method, times, dfs, dz, book.batch, book.z, book.bucket, book.fix_tau,
+                                              book.flt_tau, per_trade=per_trade)
+    else:
+        ctx = ctx or _native.default_context()
+        dev = _native.DeviceTrades(ctx, book.batch)
+        try:
+            out = _native.credit_scenario_pv(ctx, method, times, dfs, dz, dev, book.z, book.bucket, book.fix_tau,
+                                             book.flt_tau, per_trade=per_trade)
+        finally:
+            dev.close()
+    out["labels"] = book.labels
+    return _finish(out, book.pv_const, book.order, per_trade)
 
 
 def shocked_breakevens(curve, shock: Shock) -> np.ndarray:
@@ -302,6 +439,45 @@ class ScenarioGrid:
         (``self.base.dfs``, the host builder's) is priced by the same launch as one more scenario row, so the
         difference carries no noise between kernels: a zero shock whose curve has the base curve's bits gives 0."""
         book = self._revalue(trades, False, True)["book_pv"]
+        return book[:-1] - book[-1]
+
+    def _revalue_credit(self, trades, spreads, buckets, spread_shocks, per_trade, with_base):
+        book = compile_credit_book(trades, self.curve._value_dt, CurveTypes[self.curve_name], spreads, buckets)
+        S, G = len(self), len(book.labels)
+        dz = _spread_rows(spread_shocks, G)
+        if dz is not None and dz.shape[0] not in (1, S):
+            raise LibError(f"{dz.shape[0]} spread-shock rows for a grid of {S} scenarios: one shared row or one per scenario")
+        dev = _native.DeviceTrades(self._ctx, book.batch)
+        try:
+            if with_base:
+                if dz is not None:              # the base pair: the unshocked curve with a zero spread shock
+                    dz = np.vstack([np.broadcast_to(dz, (S, G)), np.zeros((1, G))])
+                out = _native.credit_scenario_pv(self._ctx, self.curve._interp_type.value, self.base.times,
+                                                 np.vstack([self._dfs(), self.base.dfs[None, :]]), dz, dev, book.z,
+                                                 book.bucket, book.fix_tau, book.flt_tau, per_trade=per_trade)
+            else:
+                out = _native.credit_scenario_pv_set(self._ctx, self._set, dz, dev, book.z, book.bucket, book.fix_tau,
+                                                     book.flt_tau, per_trade=per_trade)
+        finally:
+            dev.close()
+        out["labels"] = book.labels
+        return _finish(out, book.pv_const, book.order, per_trade)
+
+    def revalue_credit(self, trades, spreads, buckets=None, spread_shocks=None, per_trade: bool = False):
+        """`revalue` for a credit book: bonds discounted at their z-spreads, FRNs at their discount margins, and
+        scenario ``s`` pairs the grid's curve ``s`` with the spread shocks ``spread_shocks[s]``.
+
+        ``spreads`` and ``buckets``: one per trade, see `compile_credit_book`.  ``spread_shocks``: ``[S, G]`` decimals,
+        one column per bucket in order of first appearance (`shocked_spreads` makes a row from basis points), one
+        shared row ``[G]``, or None (curve shocks only).  The grid's curves are read where the device builder left
+        them.  Returns ``{"book_pv": [S], "labels": [...]}`` and, with ``per_trade``, ``"pv": [S, n]``."""
+        return self._revalue_credit(trades, spreads, buckets, spread_shocks, per_trade, False)
+
+    def pnl_credit(self, trades, spreads, buckets=None, spread_shocks=None) -> np.ndarray:
+        """``[S]``: the credit book's PV under each (curve, spread shock) pair minus its PV on the unshocked curve with
+        unshocked spreads.  As in `pnl`, the base pair is one more row of the same launch: a zero curve shock with a
+        zero spread shock gives exactly 0."""
+        book = self._revalue_credit(trades, spreads, buckets, spread_shocks, False, True)["book_pv"]
         return book[:-1] - book[-1]
 
     def close(self):

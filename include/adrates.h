@@ -606,6 +606,67 @@ int adr_yoy_scenario_pv_host(int disc_method, int K, const double* times, int S_
                              const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
                              const int64_t* cpn_off, const double* cpn, double* pv, double* book_pv, int n_threads);
 
+/*
+ * Credit scenario revaluation: the PV of every trade of an uploaded batch under S scenarios, each a PAIR of a discount
+ * curve row and a row of spread shocks per credit bucket - bonds at their z-spreads and FRNs at their discount margins
+ * under rate-only, spread-only and joint shocks in one launch, instead of one rescaled upload and one adr_price per
+ * scenario.
+ *
+ *     x[i][s]  = z[i] + (bucket[i] >= 0 ? dz[s][bucket[i]] : 0)
+ *     pv[i][s] = fix_sign_i * sum_f fix_pay_f D_s(tp_f) exp(-x fix_tau_f)                                  [tp_f > 0]
+ *              + flt_sign_i * N_i * sum_j w_j ((D_s(ts_j) / D_s(te_j) - 1) [alpha_j > 0] + spread_i alpha_j)
+ *                                         D_s(tp_j) exp(-x flt_tau_j)                                      [tp_j >= 0]
+ *     book_pv[s] = sum_i pv[i][s]
+ *
+ * D_s(t), the masks and the alpha <= 0 rule are adr_scenario_pv's (interp_method 1, 2 or 4; K = 2 ..
+ * ADR_SCENARIO_MAX_KNOTS; the first knot is t = 0; no division by D(0)).  The forward D(ts) / D(te) carries no spread;
+ * only the payment's discount factor does.  Under the log-linear schemes -x tau joins the exponent of D(tp), so a flow
+ * costs one exp.  A trade with z = 0 and bucket = -1 is priced by adr_scenario_pv's own arithmetic.
+ *
+ * New inputs: per trade z[n] (finite) and bucket[n] (-1: no shock, or 0 .. G - 1); per fixed flow fix_tau[n_fix] and per
+ * float coupon flt_tau[n_flt], the spread times, in the order of the batch's flow arrays (n_fix and n_flt are the
+ * batch's flow counts); per scenario dz[S_spr][G], G = 0 .. ADR_CREDIT_MAX_BUCKETS (dz may be NULL when G = 0).
+ *
+ * Broadcasting: S_disc and S_spr are each 1 or S.  One shared row means "not shocked" and is read with stride 0.
+ *
+ * Outputs: book_pv[S] always; pv[n][S] (trade-major) when given.  book_pv follows adr_scenario_pv's rule: the trades in
+ * chunks of ADR_SCENARIO_CHUNK summed in order from 0.0, chunk j added to slot j % 64 in order, then slots 0-31 += 32-63,
+ * ..., 0 += 1; no atomics.  A scenario's results do not depend on S, on the other scenarios, on broadcasting or on the
+ * launch shape, and are bit-identical from run to run.
+ *
+ * adr_credit_scenario_pv: host arrays in and out, blocks; refuses what it can read (non-finite z, dz or spread times,
+ * a bucket outside -1 .. G - 1, non-positive discount factors, knot times that decrease, a broadcast count other than
+ * 1 or S).  adr_credit_scenario_pv_set: the same with the curves of a set built by adr_curve_set_build, read where
+ * adr_curve_set_arrays finds them (S and S_disc are the set's count).  adr_credit_scenario_pv_dev: device arrays,
+ * enqueued on `stream` (NULL: the ctx's own), no allocation and no synchronisation (two kernels in one chain); work_dev
+ * holds adr_credit_scenario_pv_work(n, S) doubles; only the scalars are checked: a trade whose flows do not lie inside
+ * 0 .. n_fix / 0 .. n_flt, or whose bucket is outside -1 .. G - 1, reads no flow and gets a NaN PV, which carries into
+ * book_pv.  adr_credit_scenario_pv_host: the trades as the arrays of adr_trades_upload_weighted, the same per-date and
+ * per-coupon code in the same order on CPU threads (no GPU; n_threads <= 0: as many as the machine suggests, at most
+ * 16); it differs from the device by exp / log only.
+ */
+#define ADR_CREDIT_MAX_BUCKETS 32
+int adr_credit_scenario_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S_disc, const double* dfs, int G,
+                           int S_spr, const double* dz, int S, const adr_trades* trades, const double* z, const int32_t* bucket,
+                           int64_t n_fix, const double* fix_tau, int64_t n_flt, const double* flt_tau, double* pv,
+                           double* book_pv);
+int adr_credit_scenario_pv_set(adr_ctx* ctx, const adr_curve_set* set, int G, int S_spr, const double* dz,
+                               const adr_trades* trades, const double* z, const int32_t* bucket, int64_t n_fix,
+                               const double* fix_tau, int64_t n_flt, const double* flt_tau, double* pv, double* book_pv);
+/* Doubles of scratch adr_credit_scenario_pv_dev needs: ceil(n / ADR_SCENARIO_CHUNK) * S. */
+int64_t adr_credit_scenario_pv_work(int64_t n, int S);
+int adr_credit_scenario_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S_disc, const double* dfs_dev,
+                               int G, int S_spr, const double* dz_dev, int S, const adr_trades* trades, const double* z_dev,
+                               const int32_t* bucket_dev, int64_t n_fix, const double* fix_tau_dev, int64_t n_flt,
+                               const double* flt_tau_dev, double* pv_dev, double* book_pv_dev, double* work_dev, void* stream);
+int adr_credit_scenario_pv_host(int interp_method, int K, const double* times, int S_disc, const double* dfs, int G, int S_spr,
+                                const double* dz, int S, int64_t n, const int64_t* fix_off, const int64_t* flt_off,
+                                const double* fix_tp, const double* fix_pay, const double* flt_tp, const double* flt_ts,
+                                const double* flt_te, const double* flt_alpha, const double* flt_weight, const double* notional,
+                                const double* spread, const double* fix_sign, const double* flt_sign, const double* z,
+                                const int32_t* bucket, const double* fix_tau, const double* flt_tau, double* pv, double* book_pv,
+                                int n_threads);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
