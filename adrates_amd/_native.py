@@ -116,6 +116,28 @@ _SIGNATURES = {
                                              _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "adr_credit_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int64,
                                               _i64p, _i64p] + [_dp] * 11 + [_dp, _i32p, _dp, _dp, _dp, _dp, C.c_int]),
+    "adr_scenario_subbook_plan": (C.c_int64, [C.c_int64, C.c_int64, _i64p, _i64p]),
+    "adr_scenario_subbook_work": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    "adr_scenario_subbook_pv": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _vp, C.c_int64, _i64p, _dp, _dp]),
+    "adr_scenario_subbook_pv_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "adr_scenario_subbook_pv_set": (C.c_int, [_vp, _vp, _vp, C.c_int64, _i64p, _dp, _dp]),
+    "adr_scenario_subbook_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int64, _i64p, _i64p] + [_dp] * 11 +
+                                     [C.c_int64, _i64p, _dp, _dp, C.c_int]),
+    "adr_scenario_subbook_var_es": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _vp, C.c_int64, _i64p, C.c_int, C.c_int,
+                                              _dp, _dp]),
+    "adr_credit_scenario_subbook_pv": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _vp,
+                                                 _dp, _i32p, C.c_int64, _dp, C.c_int64, _dp, C.c_int64, _i64p, _dp, _dp]),
+    "adr_credit_scenario_subbook_pv_set": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _vp, _dp, _i32p, C.c_int64, _dp, C.c_int64,
+                                                     _dp, C.c_int64, _i64p, _dp, _dp]),
+    "adr_credit_scenario_subbook_pv_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int,
+                                                     _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp,
+                                                     _vp, _vp]),
+    "adr_credit_scenario_subbook_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int,
+                                                      C.c_int64, _i64p, _i64p] + [_dp] * 11 +
+                                            [_dp, _i32p, _dp, _dp, C.c_int64, _i64p, _dp, _dp, C.c_int]),
+    "adr_scenario_tail": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "adr_scenario_tail_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "adr_scenario_tail_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1029,6 +1051,228 @@ def credit_scenario_pv_dev(ctx: Context, method: int, K: int, S_disc: int, G: in
 
 
 _default_ctx = {}
+
+
+# ---------------------------------------------------------------------------------------------------------- sub-books
+SCENARIO_TAIL_MAX = 16384
+
+
+def _sub_offsets(sub_off):
+    sub_off = np.ascontiguousarray(sub_off, dtype=np.int64).reshape(-1)
+    if sub_off.size < 2:
+        raise LibError("sub_off needs B + 1 entries for B >= 1 sub-books")
+    return sub_off, sub_off.size - 1
+
+
+def _sub_result(sub_pv, pv, per_trade):
+    out = {"sub_pv": sub_pv}
+    if per_trade:
+        out["pv"] = pv.T
+    return out
+
+
+def _batch_arrays(batch):
+    """The arrays of a `TradeBatch` as the _host entries take them: ``(n, fix_off, flt_off, values dict, flt_weight)``."""
+    n = int(batch.n_trades)
+    fo = np.ascontiguousarray(batch.fix_off, dtype=np.int64)
+    lo = np.ascontiguousarray(batch.flt_off, dtype=np.int64)
+    if fo.shape != (n + 1,) or lo.shape != (n + 1,):
+        raise LibError("offset arrays must have n_trades + 1 entries")
+    a = {k: _f64(getattr(batch, k)) for k in ("fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional",
+                                              "spread", "fix_sign", "flt_sign")}
+    w = getattr(batch, "flt_weight", None)
+    w = None if w is None else _f64(w)
+    if w is not None and w.shape != a["flt_tp"].shape:
+        raise LibError("flt_weight must have one entry per float coupon")
+    return n, fo, lo, a, w
+
+
+def scenario_subbook_plan(n_trades: int, sub_off) -> np.ndarray:
+    """The chunk plan of the sub-books ``sub_off [B + 1]`` (adr_scenario_subbook_plan): the int64 array the ``_dev``
+    entries read on the device.  Offsets that do not run from 0 to ``n_trades`` or that decrease raise `LibError`."""
+    sub_off, B = _sub_offsets(sub_off)
+    size = _check(load().adr_scenario_subbook_plan(int(n_trades), B, _ptr(sub_off, _i64p), None), "adr_scenario_subbook_plan")
+    plan = np.empty(size, dtype=np.int64)
+    _check(load().adr_scenario_subbook_plan(int(n_trades), B, _ptr(sub_off, _i64p), _ptr(plan, _i64p)), "adr_scenario_subbook_plan")
+    return plan
+
+
+def scenario_subbook_work(n_trades: int, n_sub_books: int, n_scenarios: int) -> int:
+    """Doubles of scratch the sub-book ``_dev`` entries need."""
+    return int(load().adr_scenario_subbook_work(int(n_trades), int(n_sub_books), int(n_scenarios)))
+
+
+def scenario_subbook_pv(ctx: Context, method: int, times, dfs, trades: DeviceTrades, sub_off, per_trade=False):
+    """`scenario_pv` per sub-book in one launch (adr_scenario_subbook_pv, blocking): sub-book ``b`` holds the trades
+    ``sub_off[b] .. sub_off[b + 1]``.  ``sub_pv [B, S]`` and, with ``per_trade``, ``pv [S, n]``."""
+    times, dfs = _scenario_curves(times, dfs)
+    sub_off, B = _sub_offsets(sub_off)
+    S, n = dfs.shape[0], trades.n_trades
+    sub_pv = np.empty((B, S))
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_scenario_subbook_pv(ctx._h, int(method), times.size, _ptr(times), S, _ptr(dfs), trades._h, B,
+                                          _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv)), "adr_scenario_subbook_pv")
+    return _sub_result(sub_pv, pv, per_trade)
+
+
+def scenario_subbook_pv_set(ctx: Context, curve_set: CurveSet, trades: DeviceTrades, sub_off, per_trade=False):
+    """`scenario_subbook_pv` on the curves of a `CurveSet`, read where the device builder left them."""
+    sub_off, B = _sub_offsets(sub_off)
+    S, n = len(curve_set), trades.n_trades
+    sub_pv = np.empty((B, S))
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_scenario_subbook_pv_set(ctx._h, curve_set._h, trades._h, B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv)),
+           "adr_scenario_subbook_pv_set")
+    return _sub_result(sub_pv, pv, per_trade)
+
+
+def scenario_subbook_pv_host(method: int, times, dfs, batch, sub_off, per_trade=False, n_threads=0):
+    """`scenario_subbook_pv` on the CPU (adr_scenario_subbook_pv_host) for a `TradeBatch`: the same arithmetic and the
+    same order of every sub-book's sum; no GPU needed."""
+    times, dfs = _scenario_curves(times, dfs)
+    sub_off, B = _sub_offsets(sub_off)
+    n, fo, lo, a, w = _batch_arrays(batch)
+    S = dfs.shape[0]
+    sub_pv = np.empty((B, S))
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_scenario_subbook_pv_host(int(method), times.size, _ptr(times), S, _ptr(dfs), n, _ptr(fo, _i64p),
+                                               _ptr(lo, _i64p), _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]),
+                                               _ptr(a["flt_ts"]), _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w),
+                                               _ptr(a["notional"]), _ptr(a["spread"]), _ptr(a["fix_sign"]), _ptr(a["flt_sign"]),
+                                               B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv), int(n_threads)),
+           "adr_scenario_subbook_pv_host")
+    return _sub_result(sub_pv, pv, per_trade)
+
+
+def scenario_subbook_pv_dev(ctx: Context, method: int, K: int, times_ptr: int, S: int, dfs_ptr: int, trades: DeviceTrades,
+                            B: int, plan_ptr: int, sub_pv_ptr: int, work_ptr: int, pv_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_scenario_subbook_pv_dev): device pointers (integers) of ``times`` [K], ``dfs`` [S, K], the
+    uploaded `scenario_subbook_plan`, the outputs ``sub_pv`` [B, S] and ``pv`` [n, S] (0: not wanted) and
+    `scenario_subbook_work` doubles of scratch."""
+    v = lambda p: _vp(int(p) or None)
+    _check(load().adr_scenario_subbook_pv_dev(ctx._h, int(method), int(K), v(times_ptr), int(S), v(dfs_ptr), trades._h, int(B),
+                                              v(plan_ptr), v(pv_ptr), v(sub_pv_ptr), v(work_ptr), _vp(stream or None)),
+           "adr_scenario_subbook_pv_dev")
+
+
+def scenario_subbook_var_es(ctx: Context, method: int, times, dfs, trades: DeviceTrades, sub_off, k: int, base_col: int = -1):
+    """``(var [B], es [B])`` of the sub-books' rows, the launch and the tail kernel in one chain
+    (adr_scenario_subbook_var_es): the ``[B, S]`` rows stay on the device.  ``base_col`` and ``k``: see `scenario_tail`."""
+    times, dfs = _scenario_curves(times, dfs)
+    sub_off, B = _sub_offsets(sub_off)
+    var, es = np.empty(B), np.empty(B)
+    _check(load().adr_scenario_subbook_var_es(ctx._h, int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), trades._h, B,
+                                              _ptr(sub_off, _i64p), int(base_col), int(k), _ptr(var), _ptr(es)),
+           "adr_scenario_subbook_var_es")
+    return var, es
+
+
+def credit_scenario_subbook_pv(ctx: Context, method: int, times, dfs, dz, trades: DeviceTrades, z, bucket, fix_tau, flt_tau,
+                               sub_off, per_trade=False):
+    """`credit_scenario_pv` per sub-book in one launch (adr_credit_scenario_subbook_pv, blocking): ``sub_pv [B, S]`` and,
+    with ``per_trade``, ``pv [S, n]``."""
+    times, dfs = _scenario_curves(times, dfs)
+    sub_off, B = _sub_offsets(sub_off)
+    n = trades.n_trades
+    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
+    n_fix, n_flt = fix_tau.size, flt_tau.size
+    S = _credit_counts(dfs.shape[0], dz.shape[0])
+    sub_pv = np.empty((B, S))
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_credit_scenario_subbook_pv(ctx._h, int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs),
+                                                 dz.shape[1], dz.shape[0], _ptr(dz) if dz.size else None, S, trades._h, _ptr(z),
+                                                 _ptr(bucket, _i32p), n_fix, _ptr(fix_tau), n_flt, _ptr(flt_tau), B,
+                                                 _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv)), "adr_credit_scenario_subbook_pv")
+    return _sub_result(sub_pv, pv, per_trade)
+
+
+def credit_scenario_subbook_pv_set(ctx: Context, curve_set: CurveSet, dz, trades: DeviceTrades, z, bucket, fix_tau, flt_tau,
+                                   sub_off, per_trade=False):
+    """`credit_scenario_subbook_pv` on the curves of a `CurveSet` (adr_credit_scenario_subbook_pv_set)."""
+    sub_off, B = _sub_offsets(sub_off)
+    n = trades.n_trades
+    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
+    n_fix, n_flt = fix_tau.size, flt_tau.size
+    S = len(curve_set)
+    if dz.shape[0] not in (1, S):
+        raise LibError(f"{dz.shape[0]} spread-shock rows for a set of {S} curves: one shared row or one row per curve")
+    sub_pv = np.empty((B, S))
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_credit_scenario_subbook_pv_set(ctx._h, curve_set._h, dz.shape[1], dz.shape[0],
+                                                     _ptr(dz) if dz.size else None, trades._h, _ptr(z), _ptr(bucket, _i32p), n_fix,
+                                                     _ptr(fix_tau), n_flt, _ptr(flt_tau), B, _ptr(sub_off, _i64p), _ptr(pv),
+                                                     _ptr(sub_pv)), "adr_credit_scenario_subbook_pv_set")
+    return _sub_result(sub_pv, pv, per_trade)
+
+
+def credit_scenario_subbook_pv_host(method: int, times, dfs, dz, batch, z, bucket, fix_tau, flt_tau, sub_off, per_trade=False,
+                                    n_threads=0):
+    """`credit_scenario_subbook_pv` on the CPU (adr_credit_scenario_subbook_pv_host) for a `TradeBatch`."""
+    times, dfs = _scenario_curves(times, dfs)
+    sub_off, B = _sub_offsets(sub_off)
+    n, fo, lo, a, w = _batch_arrays(batch)
+    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, a["fix_tp"].size, a["flt_tp"].size)
+    S = _credit_counts(dfs.shape[0], dz.shape[0])
+    sub_pv = np.empty((B, S))
+    pv = np.empty((n, S)) if per_trade else None
+    _check(load().adr_credit_scenario_subbook_pv_host(int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), dz.shape[1],
+                                                      dz.shape[0], _ptr(dz) if dz.size else None, S, n, _ptr(fo, _i64p),
+                                                      _ptr(lo, _i64p), _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]),
+                                                      _ptr(a["flt_ts"]), _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w),
+                                                      _ptr(a["notional"]), _ptr(a["spread"]), _ptr(a["fix_sign"]),
+                                                      _ptr(a["flt_sign"]), _ptr(z), _ptr(bucket, _i32p), _ptr(fix_tau),
+                                                      _ptr(flt_tau), B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv),
+                                                      int(n_threads)), "adr_credit_scenario_subbook_pv_host")
+    return _sub_result(sub_pv, pv, per_trade)
+
+
+def credit_scenario_subbook_pv_dev(ctx: Context, method: int, K: int, S_disc: int, G: int, S_spr: int, S: int,
+                                   trades: DeviceTrades, n_fix: int, n_flt: int, B: int, ptrs, sub_pv_ptr: int, work_ptr: int,
+                                   pv_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_credit_scenario_subbook_pv_dev): ``ptrs`` as `credit_scenario_pv_dev` takes them plus
+    ``plan``, the uploaded `scenario_subbook_plan`; outputs ``sub_pv`` [B, S] and ``pv`` [n, S] (0: not wanted);
+    `scenario_subbook_work` doubles of scratch."""
+    v = lambda p: _vp(int(p) or None)
+    g = lambda name: v(ptrs.get(name, 0))
+    _check(load().adr_credit_scenario_subbook_pv_dev(ctx._h, int(method), int(K), g("times"), int(S_disc), g("dfs"), int(G),
+                                                     int(S_spr), g("dz"), int(S), trades._h, g("z"), g("bucket"), int(n_fix),
+                                                     g("fix_tau"), int(n_flt), g("flt_tau"), int(B), g("plan"), v(pv_ptr),
+                                                     v(sub_pv_ptr), v(work_ptr), _vp(stream or None)),
+           "adr_credit_scenario_subbook_pv_dev")
+
+
+def _tail_rows(rows):
+    rows = _f64(np.atleast_2d(rows))
+    if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise LibError(f"rows must have shape [n_rows, n_columns], not {list(rows.shape)}")
+    return rows
+
+
+def scenario_tail(ctx: Context, rows, k: int, base_col: int = -1):
+    """``(var [B], es [B])`` of ``rows [B, S]`` on the device (adr_scenario_tail, blocking): minus the ``k``-th smallest
+    P&L, and minus the mean of the ``k`` smallest.  ``base_col >= 0``: the P&L is every other column minus that one."""
+    rows = _tail_rows(rows)
+    var, es = np.empty(rows.shape[0]), np.empty(rows.shape[0])
+    _check(load().adr_scenario_tail(ctx._h, rows.shape[0], rows.shape[1], _ptr(rows), int(base_col), int(k), _ptr(var), _ptr(es)),
+           "adr_scenario_tail")
+    return var, es
+
+
+def scenario_tail_host(rows, k: int, base_col: int = -1):
+    """`scenario_tail` on the CPU (adr_scenario_tail_host): the same sums in the same order, hence the same bits."""
+    rows = _tail_rows(rows)
+    var, es = np.empty(rows.shape[0]), np.empty(rows.shape[0])
+    _check(load().adr_scenario_tail_host(rows.shape[0], rows.shape[1], _ptr(rows), int(base_col), int(k), _ptr(var), _ptr(es)),
+           "adr_scenario_tail_host")
+    return var, es
+
+
+def scenario_tail_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: int, var_ptr: int, es_ptr: int, base_col: int = -1,
+                      stream=0):
+    """Non-blocking form (adr_scenario_tail_dev): device pointers of ``rows`` [B, S_tot], ``var`` [B] and ``es`` [B]."""
+    v = lambda p: _vp(int(p) or None)
+    _check(load().adr_scenario_tail_dev(ctx._h, int(B), int(S_tot), v(rows_ptr), int(base_col), int(k), v(var_ptr), v(es_ptr),
+                                        _vp(stream or None)), "adr_scenario_tail_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

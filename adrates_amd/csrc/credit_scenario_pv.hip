@@ -34,6 +34,7 @@
 #include "host_pool.hpp"
 #include "kernels.hpp"
 #include "simple_interp.hpp"
+#include "subbook.hpp"
 
 int adr_set_error(int status, const std::string& msg);                          // capi.hip
 int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
@@ -244,8 +245,9 @@ struct Args {
     int64_t n_fix, n_flt;
     int K, S, G, method;
     int disc_stride, dz_stride;      // K / G, or 0 for a shared row
-    int64_t n_chunks;
+    int64_t n_chunks;                // kSub: the rows `work` holds, an upper bound of the plan's count
     double *pv, *work;               // [n][S] or null; [n_chunks][S]
+    const int64_t *sub_chunks, *sub_bounds;      // kSub: the plan's chunk count and its [chunks][2] trade bounds (subbook.hpp)
 };
 
 __device__ inline int lane_int(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
@@ -296,7 +298,8 @@ struct DevTab {
     }
 };
 
-template <bool kLog, bool kLds>
+// kSub: the chunks are those of a sub-book plan (their trade bounds come from a table) instead of ch * kChunk.
+template <bool kLog, bool kLds, bool kSub>
 __global__ __launch_bounds__(kThreads) void credit_scenario_pv_kernel(Args a) {
     extern __shared__ double lds[];
     const int K = a.K, S = a.S, G = a.G;
@@ -316,11 +319,22 @@ __global__ __launch_bounds__(kThreads) void credit_scenario_pv_kernel(Args a) {
     __syncthreads();
     const DevTab<kLog, kLds> tab{kLds ? s_tab + lane : row};
     const bool weighted = a.tr.flt_weight != nullptr;
-    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < a.n_chunks;
+    int64_t n_chunks = a.n_chunks;
+    if (kSub) {
+        const int64_t planned = *a.sub_chunks;              // uniform: a scalar load
+        n_chunks = planned < n_chunks ? planned : n_chunks;
+    }
+    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < n_chunks;
          ch += static_cast<int64_t>(gridDim.x) * kWaves) {
-        const int64_t i1 = ch * kChunk + kChunk < a.tr.n ? ch * kChunk + kChunk : a.tr.n;
+        int64_t i0 = ch * kChunk, i1 = ch * kChunk + kChunk;
+        if (kSub) {
+            i0 = a.sub_bounds[2 * ch];                      // uniform: scalar loads
+            i1 = a.sub_bounds[2 * ch + 1];
+            i0 = i0 < 0 ? 0 : i0;
+        }
+        i1 = i1 < a.tr.n ? i1 : a.tr.n;
         double book = 0.0;
-        for (int64_t i = ch * kChunk; i < i1; ++i) {
+        for (int64_t i = i0; i < i1; ++i) {
             const TradeHeader h = a.tr.header[i];           // uniform: scalar loads
             const double z = a.z[i];
             const int bucket = a.bucket[i];
@@ -455,19 +469,25 @@ int check_spreads(const std::string& w, const Curves& c, int64_t n, const Extra&
     return ADR_OK;
 }
 
-template <bool kLog, bool kLds>
-hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
+template <bool kLog, bool kLds, bool kSub>
+hipError_t launch_as(const Args& a, dim3 grid, hipStream_t stream) {
     const size_t lds = lds_bytes(a.K, a.G, kLds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&credit_scenario_pv_kernel<kLog, kLds>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&credit_scenario_pv_kernel<kLog, kLds, kSub>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((credit_scenario_pv_kernel<kLog, kLds>), grid, dim3(kThreads), lds, stream, a);
+    hipLaunchKernelGGL((credit_scenario_pv_kernel<kLog, kLds, kSub>), grid, dim3(kThreads), lds, stream, a);
     return hipGetLastError();
 }
 
-// The two kernels on `stream`; every pointer is device memory.
+template <bool kLog, bool kLds>
+hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
+    return a.sub_bounds ? launch_as<kLog, kLds, true>(a, grid, stream) : launch_as<kLog, kLds, false>(a, grid, stream);
+}
+
+// The two kernels on `stream`; every pointer is device memory.  B > 0: the chunks of the sub-book plan `plan`, and
+// `book` is sub_pv[B][S].
 int enqueue(const std::string& w, adr_ctx* ctx, const Curves& c, const adr_trades* trades, const Extra& x, double* pv,
-            double* book, double* work, hipStream_t stream_or_null) {
+            double* book, double* work, hipStream_t stream_or_null, int64_t B = 0, const int64_t* plan = nullptr) {
     const adr_ctx* owner = nullptr;
     const TradesDev* tr = adr_trades_device_view(trades, &owner);
     if (!tr) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
@@ -475,6 +495,9 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Curves& c, const adr_trade
     int rc = validate(w, c, tr->n, x, book);
     if (rc != ADR_OK) return rc;
     if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_credit_scenario_pv_work doubles are needed)");
+    const bool subs = B != 0 || plan;
+    if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
     int device = 0;
     hipStream_t stream = nullptr;
     rc = adr_ctx_target(ctx, &device, &stream);
@@ -482,19 +505,22 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Curves& c, const adr_trade
     if (stream_or_null) stream = stream_or_null;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    const int64_t chunks = (tr->n + kChunk - 1) / kChunk, groups = (static_cast<int64_t>(c.S) + kWave - 1) / kWave;
+    const int64_t chunks = subs ? sub::max_chunks(tr->n, B, kChunk) : (tr->n + kChunk - 1) / kChunk;
+    const int64_t groups = (static_cast<int64_t>(c.S) + kWave - 1) / kWave;
     if (groups > 65535) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 65535 * 64 scenarios in one launch");
     // one block per compute unit when the tables fill the LDS; a group's blocks share its chunks round-robin
     const int64_t per_group = std::max<int64_t>(1, (adr_ctx_compute_units(ctx) + groups - 1) / groups);
     const int64_t bx = std::min<int64_t>((chunks + kWaves - 1) / kWaves, per_group);
     const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(groups));
+    const sub::Plan pl = subs ? sub::plan_view(plan, B) : sub::Plan{nullptr, nullptr};
     const Args a{*tr, c.times, c.dfs, c.dz, x.z, x.bucket, x.fix_tau, x.flt_tau, x.n_fix, x.n_flt, c.K, c.S, c.G, c.method,
-                 c.S_disc == 1 ? 0 : c.K, c.S_spr == 1 ? 0 : c.G, chunks, pv, work};
+                 c.S_disc == 1 ? 0 : c.K, c.S_spr == 1 ? 0 : c.G, chunks, pv, work, subs ? pl.chunk_off + B : nullptr, pl.bounds};
     const bool in_lds = lds_bytes(c.K, c.G, true) <= kLdsBudget;
     const bool lin = c.method == ADR_INTERP_LINEAR_FWD_RATES;
     if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
     else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && subs) e = sub::enqueue_sum(work, pl.chunk_off, chunks, B, c.S, book, stream);
+    else if (e == hipSuccess) {
         hipLaunchKernelGGL(credit_scenario_book_kernel, dim3(static_cast<unsigned>((c.S + kRedEntries - 1) / kRedEntries)),
                            dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(c.S), book);
         e = hipGetLastError();
@@ -504,8 +530,9 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Curves& c, const adr_trade
 }
 
 // Blocking form: inputs, outputs and scratch in one device allocation; the curves are copied in when they are host arrays.
+// B > 0: `book` is sub_pv[B][S] of the sub-books sub_off (host).
 int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curves_on_host, const adr_trades* trades,
-                 const Extra& x, double* pv, double* book) {
+                 const Extra& x, double* pv, double* book, int64_t B = 0, const int64_t* sub_off = nullptr) {
     const int64_t n = adr_trades_count(trades);
     int rc = validate(w, c, trades ? n : 1, x, book);
     if (rc == ADR_OK && curves_on_host) rc = check_curves(w, c);
@@ -513,6 +540,14 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curve
     if (!trades) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
     rc = check_spreads(w, c, n, x);
     if (rc != ADR_OK) return rc;
+    std::vector<int64_t> plan;
+    if (B > 0) {
+        rc = sub::check_offsets(w, n, B, sub_off);
+        if (rc != ADR_OK) return rc;
+        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, B, sub_off, nullptr)));
+        adr_scenario_subbook_plan(n, B, sub_off, plan.data());
+    }
+    const size_t rows = B > 0 ? static_cast<size_t>(B) : 1;
     int device = 0;
     hipStream_t stream = nullptr;
     rc = adr_ctx_target(ctx, &device, &stream);
@@ -520,9 +555,10 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curve
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     const size_t d = sizeof(double), K = c.K, SK = static_cast<size_t>(c.S_disc) * K, SG = static_cast<size_t>(c.S_spr) * c.G;
-    const size_t W = static_cast<size_t>(adr_credit_scenario_pv_work(n, c.S)), NS = static_cast<size_t>(n) * c.S;
+    const size_t W = static_cast<size_t>(B > 0 ? adr_scenario_subbook_work(n, B, c.S) : adr_credit_scenario_pv_work(n, c.S));
+    const size_t NS = static_cast<size_t>(n) * c.S;
     const size_t nf = static_cast<size_t>(x.n_fix), nl = static_cast<size_t>(x.n_flt);
-    const size_t n_dbl = (curves_on_host ? K + SK : 0) + SG + n + nf + nl + (pv ? NS : 0) + c.S + W;
+    const size_t n_dbl = (curves_on_host ? K + SK : 0) + SG + n + nf + nl + (pv ? NS : 0) + rows * c.S + W + plan.size();
     char* base = nullptr;
     e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + static_cast<size_t>(n) * sizeof(int32_t));
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
@@ -539,7 +575,9 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curve
     }
     double *ddz = take(SG), *dzs = take(n), *dft = take(nf), *dlt = take(nl);
     double* dpv = pv ? take(NS) : nullptr;
-    double *dbook = take(c.S), *dwork = take(W);
+    double *dbook = take(rows * c.S), *dwork = take(W);
+    int64_t* dplan = B > 0 ? reinterpret_cast<int64_t*>(take(plan.size())) : nullptr;
+    if (dplan) in.push_back({dplan, plan.data(), plan.size() * sizeof(int64_t)});
     int32_t* dbucket = reinterpret_cast<int32_t*>(p);
     in.push_back({ddz, c.dz, SG * d});
     in.push_back({dzs, x.z, static_cast<size_t>(n) * d});
@@ -550,9 +588,9 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curve
         if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
     dc.dz = c.G > 0 ? ddz : nullptr;
     const Extra dx{dzs, dbucket, x.n_fix, dft, x.n_flt, dlt};
-    if (e == hipSuccess) rc = enqueue(w, ctx, dc, trades, dx, dpv, dbook, dwork, stream);
+    if (e == hipSuccess) rc = enqueue(w, ctx, dc, trades, dx, dpv, dbook, dwork, stream, B, dplan);
     if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, c.S * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, rows * c.S * d, hipMemcpyDeviceToHost, stream);
     const hipError_t es = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = es;
     const hipError_t ef = hipFree(base);
@@ -575,7 +613,7 @@ struct HostTrades {      // the per-trade arrays of the host entry
 
 template <bool kLog>
 void host_chunks(const Curves& c, const double* tab, const HostTrades& t, const Legs& arrays, const Extra& x, double* pv,
-                 double* work, int64_t lo, int64_t hi) {
+                 double* work, int64_t lo, int64_t hi, const int64_t* bounds = nullptr) {
     const int S = c.S, K = c.K;
     const size_t ds = c.S_disc == 1 ? 0 : K, zs = c.S_spr == 1 ? 0 : c.G;
     std::vector<Acc> acc(static_cast<size_t>(S));
@@ -583,7 +621,8 @@ void host_chunks(const Curves& c, const double* tab, const HostTrades& t, const 
     const bool weighted = arrays.flt_weight != nullptr;
     for (int64_t ch = lo; ch < hi; ++ch) {
         std::fill(book.begin(), book.end(), 0.0);
-        for (int64_t i = ch * kChunk; i < std::min(t.n, (ch + 1) * kChunk); ++i) {
+        const int64_t i0 = bounds ? bounds[2 * ch] : ch * kChunk, i1 = bounds ? bounds[2 * ch + 1] : std::min(t.n, (ch + 1) * kChunk);
+        for (int64_t i = i0; i < i1; ++i) {
             Legs g = arrays;
             g.f0 = t.fix_off[i]; g.l0 = t.flt_off[i];
             g.n_fix = static_cast<int>(t.fix_off[i + 1] - t.fix_off[i]);
@@ -657,14 +696,14 @@ int adr_credit_scenario_pv_set(adr_ctx* ctx, const adr_curve_set* set, int G, in
     return CS::run_blocking("adr_credit_scenario_pv_set", ctx, c, false, trades, x, pv, book_pv);
 }
 
-int adr_credit_scenario_pv_host(int interp_method, int K, const double* times, int S_disc, const double* dfs, int G, int S_spr,
-                                const double* dz, int S, int64_t n, const int64_t* fix_off, const int64_t* flt_off,
-                                const double* fix_tp, const double* fix_pay, const double* flt_tp, const double* flt_ts,
-                                const double* flt_te, const double* flt_alpha, const double* flt_weight, const double* notional,
-                                const double* spread, const double* fix_sign, const double* flt_sign, const double* z,
-                                const int32_t* bucket, const double* fix_tau, const double* flt_tau, double* pv, double* book_pv,
-                                int n_threads) {
-    const std::string w = "adr_credit_scenario_pv_host";
+// The host entries' body; B > 0: book_pv is sub_pv[B][S] of the sub-books sub_off.
+static int credit_host_run(const std::string& w, int interp_method, int K, const double* times, int S_disc, const double* dfs, int G,
+                           int S_spr, const double* dz, int S, int64_t n, const int64_t* fix_off, const int64_t* flt_off,
+                           const double* fix_tp, const double* fix_pay, const double* flt_tp, const double* flt_ts,
+                           const double* flt_te, const double* flt_alpha, const double* flt_weight, const double* notional,
+                           const double* spread, const double* fix_sign, const double* flt_sign, const double* z,
+                           const int32_t* bucket, const double* fix_tau, const double* flt_tau, double* pv, double* book_pv,
+                           int n_threads, int64_t B, const int64_t* sub_off) {
     if (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign)
         return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
     if (n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
@@ -701,17 +740,93 @@ int adr_credit_scenario_pv_host(int interp_method, int K, const double* times, i
     std::vector<double> tab(dfs, dfs + static_cast<size_t>(S_disc) * K);
     if (!lin)
         for (double& v : tab) v = std::log(v);
-    const int64_t chunks = (n + CS::kChunk - 1) / CS::kChunk;
+    std::vector<int64_t> plan;
+    if (B > 0) {
+        rc = adr::sub::check_offsets(w, n, B, sub_off);
+        if (rc != ADR_OK) return rc;
+        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, B, sub_off, nullptr)));
+        adr_scenario_subbook_plan(n, B, sub_off, plan.data());
+    }
+    const int64_t* bounds = B > 0 ? plan.data() + B + 1 : nullptr;
+    const int64_t chunks = B > 0 ? plan[B] : (n + CS::kChunk - 1) / CS::kChunk;
     std::vector<double> work(static_cast<size_t>(chunks) * S);
     const CS::Legs arrays{fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, fix_tau, flt_tau, 0, 0, 0, 0, 0.0};
     const CS::HostTrades t{n, fix_off, flt_off, notional, spread, fix_sign, flt_sign};
     const int threads = n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4);
     adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
-        if (lin) CS::host_chunks<false>(c, tab.data(), t, arrays, x, pv, work.data(), lo, hi);
-        else CS::host_chunks<true>(c, tab.data(), t, arrays, x, pv, work.data(), lo, hi);
+        if (lin) CS::host_chunks<false>(c, tab.data(), t, arrays, x, pv, work.data(), lo, hi, bounds);
+        else CS::host_chunks<true>(c, tab.data(), t, arrays, x, pv, work.data(), lo, hi, bounds);
     });
-    CS::reduce_chunks(work.data(), chunks, S, book_pv);
+    if (B > 0) adr::sub::reduce_subbooks(work.data(), plan.data(), B, S, book_pv);
+    else CS::reduce_chunks(work.data(), chunks, S, book_pv);
     return ADR_OK;
+}
+
+int adr_credit_scenario_pv_host(int interp_method, int K, const double* times, int S_disc, const double* dfs, int G, int S_spr,
+                                const double* dz, int S, int64_t n, const int64_t* fix_off, const int64_t* flt_off,
+                                const double* fix_tp, const double* fix_pay, const double* flt_tp, const double* flt_ts,
+                                const double* flt_te, const double* flt_alpha, const double* flt_weight, const double* notional,
+                                const double* spread, const double* fix_sign, const double* flt_sign, const double* z,
+                                const int32_t* bucket, const double* fix_tau, const double* flt_tau, double* pv, double* book_pv,
+                                int n_threads) {
+    return credit_host_run("adr_credit_scenario_pv_host", interp_method, K, times, S_disc, dfs, G, S_spr, dz, S, n, fix_off, flt_off,
+                           fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, z,
+                           bucket, fix_tau, flt_tau, pv, book_pv, n_threads, 0, nullptr);
+}
+
+int adr_credit_scenario_subbook_pv_host(int interp_method, int K, const double* times, int S_disc, const double* dfs, int G,
+                                        int S_spr, const double* dz, int S, int64_t n, const int64_t* fix_off,
+                                        const int64_t* flt_off, const double* fix_tp, const double* fix_pay, const double* flt_tp,
+                                        const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                                        const double* flt_weight, const double* notional, const double* spread,
+                                        const double* fix_sign, const double* flt_sign, const double* z, const int32_t* bucket,
+                                        const double* fix_tau, const double* flt_tau, int64_t B, const int64_t* sub_off,
+                                        double* pv, double* sub_pv, int n_threads) {
+    const std::string w = "adr_credit_scenario_subbook_pv_host";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    return credit_host_run(w, interp_method, K, times, S_disc, dfs, G, S_spr, dz, S, n, fix_off, flt_off, fix_tp, fix_pay, flt_tp,
+                           flt_ts, flt_te, flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, z, bucket, fix_tau, flt_tau,
+                           pv, sub_pv, n_threads, B, sub_off);
+}
+
+int adr_credit_scenario_subbook_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S_disc, const double* dfs,
+                                   int G, int S_spr, const double* dz, int S, const adr_trades* trades, const double* z,
+                                   const int32_t* bucket, int64_t n_fix, const double* fix_tau, int64_t n_flt,
+                                   const double* flt_tau, int64_t B, const int64_t* sub_off, double* pv, double* sub_pv) {
+    const std::string w = "adr_credit_scenario_subbook_pv";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    const CS::Curves c{interp_method, K, times, S_disc, dfs, G, S_spr, dz, S};
+    const CS::Extra x{z, bucket, n_fix, fix_tau, n_flt, flt_tau};
+    return CS::run_blocking(w, ctx, c, true, trades, x, pv, sub_pv, B, sub_off);
+}
+
+int adr_credit_scenario_subbook_pv_set(adr_ctx* ctx, const adr_curve_set* set, int G, int S_spr, const double* dz,
+                                       const adr_trades* trades, const double* z, const int32_t* bucket, int64_t n_fix,
+                                       const double* fix_tau, int64_t n_flt, const double* flt_tau, int64_t B,
+                                       const int64_t* sub_off, double* pv, double* sub_pv) {
+    const std::string w = "adr_credit_scenario_subbook_pv_set";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    const adr_ctx* owner = nullptr;
+    int method = 0, K = 0, S = 0;
+    const double *t = nullptr, *d = nullptr;
+    const int rc = adr_curve_set_device_view(set, &owner, &method, &K, &S, &t, &d);
+    if (rc != ADR_OK) return rc;
+    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, w + ": the curve set belongs to another ctx");
+    const CS::Curves c{method, K, t, S, d, G, S_spr, dz, S};
+    const CS::Extra x{z, bucket, n_fix, fix_tau, n_flt, flt_tau};
+    return CS::run_blocking(w, ctx, c, false, trades, x, pv, sub_pv, B, sub_off);
+}
+
+int adr_credit_scenario_subbook_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S_disc,
+                                       const double* dfs_dev, int G, int S_spr, const double* dz_dev, int S,
+                                       const adr_trades* trades, const double* z_dev, const int32_t* bucket_dev, int64_t n_fix,
+                                       const double* fix_tau_dev, int64_t n_flt, const double* flt_tau_dev, int64_t B,
+                                       const int64_t* plan_dev, double* pv_dev, double* sub_pv_dev, double* work_dev, void* stream) {
+    const std::string w = "adr_credit_scenario_subbook_pv_dev";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    const CS::Curves c{interp_method, K, times_dev, S_disc, dfs_dev, G, S_spr, dz_dev, S};
+    const CS::Extra x{z_dev, bucket_dev, n_fix, fix_tau_dev, n_flt, flt_tau_dev};
+    return CS::enqueue(w, ctx, c, trades, x, pv_dev, sub_pv_dev, work_dev, static_cast<hipStream_t>(stream), B, plan_dev);
 }
 
 }  // extern "C"

@@ -35,6 +35,7 @@
 #include "host_pool.hpp"
 #include "kernels.hpp"
 #include "simple_interp.hpp"
+#include "subbook.hpp"
 
 int adr_set_error(int status, const std::string& msg);                          // capi.hip
 int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
@@ -210,8 +211,9 @@ struct Args {
     TradesDev tr;
     const double *times, *dfs;       // [K], [S][K]
     int K, S, method;
-    int64_t n_chunks;
+    int64_t n_chunks;                // kSub: the rows `work` holds, an upper bound of the plan's count
     double *pv, *work;               // [n][S] or null; [n_chunks][S]
+    const int64_t *sub_chunks, *sub_bounds;      // kSub: the plan's chunk count and its [chunks][2] trade bounds (subbook.hpp)
 };
 
 __device__ inline int lane_int(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
@@ -259,7 +261,8 @@ struct DevTab {
     }
 };
 
-template <bool kLog, bool kLds>
+// kSub: the chunks are those of a sub-book plan (their trade bounds come from a table) instead of ch * kChunk.
+template <bool kLog, bool kLds, bool kSub>
 __global__ __launch_bounds__(kThreads) void scenario_pv_kernel(Args a) {
     extern __shared__ double lds[];
     double* s_x = lds;                               // [K]
@@ -276,11 +279,22 @@ __global__ __launch_bounds__(kThreads) void scenario_pv_kernel(Args a) {
     __syncthreads();
     const DevTab<kLog, kLds> tab{kLds ? s_tab + lane : row};
     const bool weighted = a.tr.flt_weight != nullptr;
-    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < a.n_chunks;
+    int64_t n_chunks = a.n_chunks;
+    if (kSub) {
+        const int64_t planned = *a.sub_chunks;              // uniform: a scalar load
+        n_chunks = planned < n_chunks ? planned : n_chunks;
+    }
+    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < n_chunks;
          ch += static_cast<int64_t>(gridDim.x) * kWaves) {
-        const int64_t i1 = ch * kChunk + kChunk < a.tr.n ? ch * kChunk + kChunk : a.tr.n;
+        int64_t i0 = ch * kChunk, i1 = ch * kChunk + kChunk;
+        if (kSub) {
+            i0 = a.sub_bounds[2 * ch];                      // uniform: scalar loads
+            i1 = a.sub_bounds[2 * ch + 1];
+            i0 = i0 < 0 ? 0 : i0;
+        }
+        i1 = i1 < a.tr.n ? i1 : a.tr.n;
         double book = 0.0;
-        for (int64_t i = ch * kChunk; i < i1; ++i) {
+        for (int64_t i = i0; i < i1; ++i) {
             const TradeHeader h = a.tr.header[i];           // uniform: scalar loads
             const Legs g{a.tr.fix_tp, a.tr.fix_pay, a.tr.flt_tp, a.tr.flt_ts, a.tr.flt_te, a.tr.flt_alpha, a.tr.flt_weight,
                          h.fix_begin, h.flt_begin, h.n_fix, h.n_flt, h.spread};
@@ -350,19 +364,26 @@ int check_curves(const std::string& w, int K, const double* times, int S, const 
     return ADR_OK;
 }
 
-template <bool kLog, bool kLds>
-hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
+template <bool kLog, bool kLds, bool kSub>
+hipError_t launch_as(const Args& a, dim3 grid, hipStream_t stream) {
     const size_t lds = lds_bytes(a.K, kLds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scenario_pv_kernel<kLog, kLds>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scenario_pv_kernel<kLog, kLds, kSub>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((scenario_pv_kernel<kLog, kLds>), grid, dim3(kThreads), lds, stream, a);
+    hipLaunchKernelGGL((scenario_pv_kernel<kLog, kLds, kSub>), grid, dim3(kThreads), lds, stream, a);
     return hipGetLastError();
 }
 
-// The two kernels on `stream`; every pointer is device memory.
+template <bool kLog, bool kLds>
+hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
+    return a.sub_bounds ? launch_as<kLog, kLds, true>(a, grid, stream) : launch_as<kLog, kLds, false>(a, grid, stream);
+}
+
+// The two kernels on `stream`; every pointer is device memory.  B > 0: the chunks of the sub-book plan `plan`, and
+// `book` is sub_pv[B][S].
 int enqueue(const std::string& w, adr_ctx* ctx, int method, int K, const double* times, int S, const double* dfs,
-            const adr_trades* trades, double* pv, double* book, double* work, hipStream_t stream_or_null) {
+            const adr_trades* trades, double* pv, double* book, double* work, hipStream_t stream_or_null, int64_t B = 0,
+            const int64_t* plan = nullptr) {
     const adr_ctx* owner = nullptr;
     const TradesDev* tr = adr_trades_device_view(trades, &owner);
     if (!tr) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
@@ -370,6 +391,9 @@ int enqueue(const std::string& w, adr_ctx* ctx, int method, int K, const double*
     int rc = validate(w, method, K, S, tr->n, times, dfs, book);
     if (rc != ADR_OK) return rc;
     if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_scenario_pv_work doubles are needed)");
+    const bool subs = B != 0 || plan;
+    if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
     int device = 0;
     hipStream_t stream = nullptr;
     rc = adr_ctx_target(ctx, &device, &stream);
@@ -377,18 +401,21 @@ int enqueue(const std::string& w, adr_ctx* ctx, int method, int K, const double*
     if (stream_or_null) stream = stream_or_null;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    const int64_t chunks = (tr->n + kChunk - 1) / kChunk, groups = (static_cast<int64_t>(S) + kWave - 1) / kWave;
+    const int64_t chunks = subs ? sub::max_chunks(tr->n, B, kChunk) : (tr->n + kChunk - 1) / kChunk;
+    const int64_t groups = (static_cast<int64_t>(S) + kWave - 1) / kWave;
     if (groups > 65535) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 65535 * 64 scenarios in one launch");
     // one block per compute unit when the table fills the LDS; a group's blocks share its chunks round-robin
     const int64_t per_group = std::max<int64_t>(1, (adr_ctx_compute_units(ctx) + groups - 1) / groups);
     const int64_t bx = std::min<int64_t>((chunks + kWaves - 1) / kWaves, per_group);
     const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(groups));
-    const Args a{*tr, times, dfs, K, S, method, chunks, pv, work};
+    const sub::Plan pl = subs ? sub::plan_view(plan, B) : sub::Plan{nullptr, nullptr};
+    const Args a{*tr, times, dfs, K, S, method, chunks, pv, work, subs ? pl.chunk_off + B : nullptr, pl.bounds};
     const bool in_lds = lds_bytes(K, true) <= kLdsBudget;
     const bool lin = method == ADR_INTERP_LINEAR_FWD_RATES;
     if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
     else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && subs) e = sub::enqueue_sum(work, pl.chunk_off, chunks, B, S, book, stream);
+    else if (e == hipSuccess) {
         hipLaunchKernelGGL(scenario_book_kernel, dim3(static_cast<unsigned>((S + kRedEntries - 1) / kRedEntries)),
                            dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(S), book);
         e = hipGetLastError();
@@ -397,22 +424,45 @@ int enqueue(const std::string& w, adr_ctx* ctx, int method, int K, const double*
     return ADR_OK;
 }
 
+// What a sub-book call adds to the blocking form: the offsets (host), and, with k > 0, the tail measures of the rows
+// in place of the rows themselves (book is then not written).
+struct SubRequest {
+    int64_t B;
+    const int64_t* sub_off;
+    int base_col, k;
+    double *var, *es;
+};
+
 // Blocking form: outputs and scratch in one device allocation; the curves are copied in when they are host arrays.
+// sub: `book` is sub_pv[B][S].
 int run_blocking(const std::string& w, adr_ctx* ctx, int method, int K, const double* times, int S, const double* dfs,
-                 bool curves_on_host, const adr_trades* trades, double* pv, double* book) {
+                 bool curves_on_host, const adr_trades* trades, double* pv, double* book, const SubRequest* sub = nullptr) {
     const int64_t n = adr_trades_count(trades);
-    int rc = validate(w, method, K, S, trades ? n : 1, times, dfs, book);
+    const bool tail = sub && sub->k > 0;
+    int rc = validate(w, method, K, S, trades ? n : 1, times, dfs, tail ? static_cast<const void*>(sub->var) : book);
     if (rc == ADR_OK && curves_on_host) rc = check_curves(w, K, times, S, dfs);
     if (rc != ADR_OK) return rc;
     if (!trades) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
+    std::vector<int64_t> plan;
+    if (sub) {
+        rc = sub::check_offsets(w, n, sub->B, sub->sub_off);
+        if (rc == ADR_OK && tail) rc = sub::check_tail(w, sub->B, S, sub->base_col, sub->k);
+        if (rc == ADR_OK && tail && !sub->es) rc = adr_set_error(ADR_ERR_INVALID, w + ": es is NULL");
+        if (rc != ADR_OK) return rc;
+        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, sub->B, sub->sub_off, nullptr)));
+        adr_scenario_subbook_plan(n, sub->B, sub->sub_off, plan.data());
+    }
+    const size_t B = sub ? static_cast<size_t>(sub->B) : 0, rows = sub ? B : 1;
     int device = 0;
     hipStream_t stream = nullptr;
     rc = adr_ctx_target(ctx, &device, &stream);
     if (rc != ADR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    const size_t d = sizeof(double), SK = static_cast<size_t>(S) * K, W = static_cast<size_t>(adr_scenario_pv_work(n, S));
-    const size_t n_dbl = (curves_on_host ? K + SK : 0) + (pv ? static_cast<size_t>(n) * S : 0) + S + W;
+    const size_t d = sizeof(double), SK = static_cast<size_t>(S) * K;
+    const size_t W = static_cast<size_t>(sub ? adr_scenario_subbook_work(n, sub->B, S) : adr_scenario_pv_work(n, S));
+    const size_t n_dbl = (curves_on_host ? K + SK : 0) + (pv ? static_cast<size_t>(n) * S : 0) + rows * S + W + plan.size() +
+                         (tail ? 2 * B : 0);
     double* base = nullptr;
     e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
@@ -426,10 +476,20 @@ int run_blocking(const std::string& w, adr_ctx* ctx, int method, int K, const do
         dt = ht; ddf = hd;
     }
     double* dpv = pv ? take(static_cast<size_t>(n) * S) : nullptr;
-    double *dbook = take(S), *dwork = take(W);
-    if (e == hipSuccess) rc = enqueue(w, ctx, method, K, dt, S, ddf, trades, dpv, dbook, dwork, stream);
+    double *dbook = take(rows * S), *dwork = take(W);
+    int64_t* dplan = nullptr;
+    if (sub) {
+        dplan = reinterpret_cast<int64_t*>(take(plan.size()));
+        if (e == hipSuccess) e = hipMemcpyAsync(dplan, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+    }
+    double *dvar = tail ? take(B) : nullptr, *des = tail ? take(B) : nullptr;
+    if (e == hipSuccess) rc = enqueue(w, ctx, method, K, dt, S, ddf, trades, dpv, dbook, dwork, stream, sub ? sub->B : 0, dplan);
     if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, static_cast<size_t>(n) * S * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, S * d, hipMemcpyDeviceToHost, stream);
+    if (tail) {
+        if (e == hipSuccess && rc == ADR_OK) e = sub::enqueue_tail(dbook, sub->B, S, sub->base_col, sub->k, dvar, des, stream);
+        if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(sub->var, dvar, B * d, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(sub->es, des, B * d, hipMemcpyDeviceToHost, stream);
+    } else if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, rows * S * d, hipMemcpyDeviceToHost, stream);
     const hipError_t es = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = es;
     const hipError_t ef = hipFree(base);
@@ -447,13 +507,15 @@ struct HostTab {
 template <bool kLog>
 void host_chunks(int method, int K, const double* times, int S, const double* tab, int64_t n, const int64_t* fix_off,
                  const int64_t* flt_off, const Legs& arrays, const double* notional, const double* spread,
-                 const double* fix_sign, const double* flt_sign, double* pv, double* work, int64_t lo, int64_t hi) {
+                 const double* fix_sign, const double* flt_sign, double* pv, double* work, int64_t lo, int64_t hi,
+                 const int64_t* bounds = nullptr) {
     std::vector<Acc> acc(static_cast<size_t>(S));
     std::vector<double> book(static_cast<size_t>(S));
     const bool weighted = arrays.flt_weight != nullptr;
     for (int64_t ch = lo; ch < hi; ++ch) {
         std::fill(book.begin(), book.end(), 0.0);
-        for (int64_t i = ch * kChunk; i < std::min(n, (ch + 1) * kChunk); ++i) {
+        const int64_t i0 = bounds ? bounds[2 * ch] : ch * kChunk, i1 = bounds ? bounds[2 * ch + 1] : std::min(n, (ch + 1) * kChunk);
+        for (int64_t i = i0; i < i1; ++i) {
             Legs g = arrays;
             g.f0 = fix_off[i]; g.l0 = flt_off[i];
             g.n_fix = static_cast<int>(fix_off[i + 1] - fix_off[i]);
@@ -522,12 +584,12 @@ int adr_scenario_pv_set(adr_ctx* ctx, const adr_curve_set* set, const adr_trades
     return SC::run_blocking("adr_scenario_pv_set", ctx, method, K, t, S, d, false, trades, pv, book_pv);
 }
 
-int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
-                         const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
-                         const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
-                         const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
-                         const double* flt_sign, double* pv, double* book_pv, int n_threads) {
-    const std::string w = "adr_scenario_pv_host";
+// The host entries' body; B > 0: book_pv is sub_pv[B][S] of the sub-books sub_off.
+static int scenario_host_run(const std::string& w, int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
+                             const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                             const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                             const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                             const double* flt_sign, double* pv, double* book_pv, int n_threads, int64_t B, const int64_t* sub_off) {
     int rc = SC::validate(w, interp_method, K, S, n, times, dfs, book_pv);
     if (rc == ADR_OK) rc = SC::check_curves(w, K, times, S, dfs);
     if (rc != ADR_OK) return rc;
@@ -558,20 +620,87 @@ int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, c
     std::vector<double> tab(dfs, dfs + static_cast<size_t>(S) * K);
     if (!lin)
         for (double& v : tab) v = std::log(v);
-    const int64_t chunks = (n + SC::kChunk - 1) / SC::kChunk;
+    std::vector<int64_t> plan;
+    if (B > 0) {
+        rc = adr::sub::check_offsets(w, n, B, sub_off);
+        if (rc != ADR_OK) return rc;
+        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, B, sub_off, nullptr)));
+        adr_scenario_subbook_plan(n, B, sub_off, plan.data());
+    }
+    const int64_t* bounds = B > 0 ? plan.data() + B + 1 : nullptr;
+    const int64_t chunks = B > 0 ? plan[B] : (n + SC::kChunk - 1) / SC::kChunk;
     std::vector<double> work(static_cast<size_t>(chunks) * S);
     const SC::Legs arrays{fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, 0, 0, 0, 0, 0.0};
-    const int threads = n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4);
+    const int threads = std::max(1, n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4));
     adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
         if (lin)
             SC::host_chunks<false>(interp_method, K, times, S, tab.data(), n, fix_off, flt_off, arrays, notional, spread, fix_sign,
-                                   flt_sign, pv, work.data(), lo, hi);
+                                   flt_sign, pv, work.data(), lo, hi, bounds);
         else
             SC::host_chunks<true>(interp_method, K, times, S, tab.data(), n, fix_off, flt_off, arrays, notional, spread, fix_sign,
-                                  flt_sign, pv, work.data(), lo, hi);
+                                  flt_sign, pv, work.data(), lo, hi, bounds);
     });
-    SC::reduce_chunks(work.data(), chunks, S, book_pv);
+    if (B > 0) adr::sub::reduce_subbooks(work.data(), plan.data(), B, S, book_pv);
+    else SC::reduce_chunks(work.data(), chunks, S, book_pv);
     return ADR_OK;
+}
+
+int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
+                         const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                         const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                         const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                         const double* flt_sign, double* pv, double* book_pv, int n_threads) {
+    return scenario_host_run("adr_scenario_pv_host", interp_method, K, times, S, dfs, n, fix_off, flt_off, fix_tp, fix_pay, flt_tp,
+                             flt_ts, flt_te, flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, pv, book_pv, n_threads, 0,
+                             nullptr);
+}
+
+int adr_scenario_subbook_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
+                                 const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                                 const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                                 const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                                 const double* flt_sign, int64_t B, const int64_t* sub_off, double* pv, double* sub_pv,
+                                 int n_threads) {
+    const std::string w = "adr_scenario_subbook_pv_host";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    return scenario_host_run(w, interp_method, K, times, S, dfs, n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te,
+                             flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, pv, sub_pv, n_threads, B, sub_off);
+}
+
+int adr_scenario_subbook_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S, const double* dfs,
+                            const adr_trades* trades, int64_t B, const int64_t* sub_off, double* pv, double* sub_pv) {
+    const SC::SubRequest sub{B, sub_off, -1, 0, nullptr, nullptr};
+    return SC::run_blocking("adr_scenario_subbook_pv", ctx, interp_method, K, times, S, dfs, true, trades, pv, sub_pv, &sub);
+}
+
+int adr_scenario_subbook_var_es(adr_ctx* ctx, int interp_method, int K, const double* times, int S, const double* dfs,
+                                const adr_trades* trades, int64_t B, const int64_t* sub_off, int base_col, int k, double* var,
+                                double* es) {
+    const std::string w = "adr_scenario_subbook_var_es";
+    if (k < 1) return adr_set_error(ADR_ERR_INVALID, w + ": k must be at least 1");
+    const SC::SubRequest sub{B, sub_off, base_col, k, var, es};
+    return SC::run_blocking(w, ctx, interp_method, K, times, S, dfs, true, trades, nullptr, nullptr, &sub);
+}
+
+int adr_scenario_subbook_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S, const double* dfs_dev,
+                                const adr_trades* trades, int64_t B, const int64_t* plan_dev, double* pv_dev, double* sub_pv_dev,
+                                double* work_dev, void* stream) {
+    const std::string w = "adr_scenario_subbook_pv_dev";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    return SC::enqueue(w, ctx, interp_method, K, times_dev, S, dfs_dev, trades, pv_dev, sub_pv_dev, work_dev,
+                       static_cast<hipStream_t>(stream), B, plan_dev);
+}
+
+int adr_scenario_subbook_pv_set(adr_ctx* ctx, const adr_curve_set* set, const adr_trades* trades, int64_t B, const int64_t* sub_off,
+                                double* pv, double* sub_pv) {
+    const adr_ctx* owner = nullptr;
+    int method = 0, K = 0, S = 0;
+    const double *t = nullptr, *d = nullptr;
+    const int rc = adr_curve_set_device_view(set, &owner, &method, &K, &S, &t, &d);
+    if (rc != ADR_OK) return rc;
+    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, "adr_scenario_subbook_pv_set: the curve set belongs to another ctx");
+    const SC::SubRequest sub{B, sub_off, -1, 0, nullptr, nullptr};
+    return SC::run_blocking("adr_scenario_subbook_pv_set", ctx, method, K, t, S, d, false, trades, pv, sub_pv, &sub);
 }
 
 }  // extern "C"

@@ -1,0 +1,360 @@
+// Sub-books of a scenario revaluation: per-desk, per-counterparty or per-account P&L vectors from ONE launch of the
+// pricing kernels (adr_scenario_subbook_pv*, adr_credit_scenario_subbook_pv*), and their tail measures
+// (adr_scenario_tail*).  Declarations and semantics: include/adrates.h.
+//
+// The pricing kernels cut the batch into chunks at sub-book boundaries (the plan below) and write work[chunk][S] as
+// they always do.  The sum kernel here then adds every sub-book's chunk rows in the parent's order - chunk j of the
+// sub-book to slot j % 64 in order, then a halving tree - so that a row has the bits of the parent's book_pv on that
+// sub-book alone.  One wave = one (sub-book, 64 scenarios) pair, lane = scenario: a chunk row is one coalesced 512-byte
+// read, the 64 slots are registers of the lane (the inner 64 is unrolled) and the tree runs in them: no LDS, no
+// barrier, no atomics.  A sub-book of more than kBigChunks chunks (a whole book as ONE sub-book has 15 625) would keep
+// that one wave busy for milliseconds, so it is left to a second kernel: one block per pair, 16 waves with four slots
+// each, the slots meeting in LDS for the same tree.  Both kernels are always enqueued (the host of a _dev call does not
+// see the plan) and each leaves the other's pairs alone.
+//
+// The tail kernel: one block per row.  The P&L values go to LDS as order-preserving integer keys, padded with +inf to a
+// power of two, and a bitonic network sorts them; thread 0 then adds the k smallest in ascending order.  The keys make
+// the order total (-0.0 before +0.0), so the host twin's std::sort gives the same sequence.
+#include "subbook.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/adrates.h"
+#include "host_pool.hpp"
+
+int adr_set_error(int status, const std::string& msg);                          // capi.hip
+int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
+
+#pragma clang fp contract(off)
+
+namespace adr {
+namespace sub {
+
+constexpr int kWave = 64;
+constexpr int kSlots = 64;                      // the parent's reduction slots
+constexpr int kSumWaves = 4;                    // (sub-book, group) pairs per block of the sum kernel
+constexpr int kChunk = ADR_SCENARIO_CHUNK;
+constexpr int kBigChunks = 64;                  // above (the slot index wraps): the block-per-pair kernel
+constexpr int kBigWaves = 16;                   // its waves, kSlots / kBigWaves slots each
+
+int check_offsets(const std::string& w, int64_t n, int64_t B, const int64_t* sub_off) {
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    if (!sub_off) return adr_set_error(ADR_ERR_INVALID, w + ": sub_off is NULL");
+    if (sub_off[0] != 0) return adr_set_error(ADR_ERR_INVALID, w + ": sub_off must start at 0 (sub-book 0 starts at " +
+                                                                std::to_string(sub_off[0]) + ")");
+    for (int64_t b = 0; b < B; ++b)
+        if (sub_off[b + 1] < sub_off[b])
+            return adr_set_error(ADR_ERR_INVALID, w + ": sub_off decreases at sub-book " + std::to_string(b) + " (" +
+                                                      std::to_string(sub_off[b]) + " .. " + std::to_string(sub_off[b + 1]) + ")");
+    if (sub_off[B] != n)
+        return adr_set_error(ADR_ERR_INVALID, w + ": sub_off must end at the trade count " + std::to_string(n) + " (sub-book " +
+                                                  std::to_string(B - 1) + " ends at " + std::to_string(sub_off[B]) + ")");
+    return ADR_OK;
+}
+
+__global__ __launch_bounds__(kWave * kSumWaves) void subbook_sum_kernel(const double* work, const int64_t* chunk_off,
+                                                                        int64_t chunk_cap, int64_t B, int S, int groups,
+                                                                        double* sub_pv) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t pair = static_cast<int64_t>(blockIdx.x) * kSumWaves + wave;
+    if (pair >= B * groups) return;
+    const int64_t b = pair / groups;
+    const int64_t s = (pair % groups) * kWave + lane;
+    int64_t c0 = chunk_off[b], c1 = chunk_off[b + 1];      // uniform: scalar loads
+    c0 = c0 < 0 ? 0 : c0;
+    c1 = c1 > chunk_cap ? chunk_cap : c1;
+    if (s >= S || c1 - c0 > kBigChunks) return;
+    const double* col = work + s;
+    double p[kSlots];
+#pragma unroll
+    for (int q = 0; q < kSlots; ++q) p[q] = 0.0;
+    for (int64_t base = c0; base < c1; base += kSlots) {
+#pragma unroll
+        for (int q = 0; q < kSlots; ++q)
+            if (base + q < c1) p[q] = p[q] + col[(base + q) * S];
+    }
+#pragma unroll
+    for (int h = kSlots / 2; h >= 1; h >>= 1) {
+#pragma unroll
+        for (int q = 0; q < h; ++q) p[q] = p[q] + p[q + h];
+    }
+    sub_pv[b * S + s] = p[0];
+}
+
+// The same sum for the pairs of sub-books with more than kBigChunks chunks: wave w owns the slots 4 w .. 4 w + 3.
+__global__ __launch_bounds__(kWave * kBigWaves) void subbook_sum_big_kernel(const double* work, const int64_t* chunk_off,
+                                                                            int64_t chunk_cap, int S, int groups, double* sub_pv) {
+    constexpr int kOwn = kSlots / kBigWaves;
+    __shared__ double sh[kSlots][kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t b = blockIdx.x / groups;
+    int64_t c0 = chunk_off[b], c1 = chunk_off[b + 1];      // uniform: scalar loads
+    c0 = c0 < 0 ? 0 : c0;
+    c1 = c1 > chunk_cap ? chunk_cap : c1;
+    if (c1 - c0 <= kBigChunks) return;                      // uniform over the block
+    const int64_t s = static_cast<int64_t>(blockIdx.x % groups) * kWave + lane;
+    const double* col = work + (s < S ? s : S - 1);         // padding lanes add the last scenario and store nothing
+    double p[kOwn];
+#pragma unroll
+    for (int i = 0; i < kOwn; ++i) p[i] = 0.0;
+#pragma unroll 4
+    for (int64_t base = c0 + wave * kOwn; base < c1; base += kSlots) {
+#pragma unroll
+        for (int i = 0; i < kOwn; ++i)
+            if (base + i < c1) p[i] = p[i] + col[(base + i) * S];
+    }
+#pragma unroll
+    for (int i = 0; i < kOwn; ++i) sh[wave * kOwn + i][lane] = p[i];
+    __syncthreads();
+    if (wave != 0) return;
+    double q[kSlots];
+#pragma unroll
+    for (int i = 0; i < kSlots; ++i) q[i] = sh[i][lane];
+#pragma unroll
+    for (int h = kSlots / 2; h >= 1; h >>= 1) {
+#pragma unroll
+        for (int i = 0; i < h; ++i) q[i] = q[i] + q[i + h];
+    }
+    if (s < S) sub_pv[b * S + s] = q[0];
+}
+
+hipError_t enqueue_sum(const double* work, const int64_t* chunk_off, int64_t chunk_cap, int64_t B, int S, double* sub_pv,
+                       hipStream_t stream) {
+    const int groups = (S + kWave - 1) / kWave;
+    const int64_t blocks = (B * groups + kSumWaves - 1) / kSumWaves;
+    if (blocks > INT32_MAX) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(subbook_sum_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kWave * kSumWaves), 0, stream, work,
+                       chunk_off, chunk_cap, B, S, groups, sub_pv);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (B * groups > INT32_MAX) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(subbook_sum_big_kernel, dim3(static_cast<unsigned>(B * groups)), dim3(kWave * kBigWaves), 0, stream, work,
+                       chunk_off, chunk_cap, S, groups, sub_pv);
+    return hipGetLastError();
+}
+
+void reduce_subbooks(const double* work, const int64_t* chunk_off, int64_t B, int64_t S, double* sub_pv) {
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t c0 = chunk_off[b], c1 = chunk_off[b + 1];
+        for (int64_t e = 0; e < S; ++e) {
+            double p[kSlots];
+            for (int q = 0; q < kSlots; ++q) {
+                p[q] = 0.0;
+                for (int64_t j = c0 + q; j < c1; j += kSlots) p[q] = p[q] + work[j * S + e];
+            }
+            for (int h = kSlots / 2; h >= 1; h >>= 1)
+                for (int q = 0; q < h; ++q) p[q] = p[q] + p[q + h];
+            sub_pv[b * S + e] = p[0];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ tail measures
+// A double as an int64 whose signed order is the doubles' order, -0.0 before +0.0; the map is its own inverse.
+__host__ __device__ inline int64_t key_of(double v) {
+    int64_t b;
+    memcpy(&b, &v, sizeof b);
+    return b ^ ((b >> 63) & INT64_MAX);
+}
+__host__ __device__ inline double value_of(int64_t k) {
+    const int64_t b = k ^ ((k >> 63) & INT64_MAX);
+    double v;
+    memcpy(&v, &b, sizeof v);
+    return v;
+}
+
+// P&L value e of a row: column e, stepping over base_col, minus the base column's value.
+__host__ __device__ inline double pnl_at(const double* row, int base_col, int e) {
+    if (base_col < 0) return row[e];
+    return row[e >= base_col ? e + 1 : e] - row[base_col];
+}
+
+__host__ __device__ inline void tail_of_sorted(const int64_t* keys, int k, double* var, double* es) {
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) sum = sum + value_of(keys[i]);
+    *var = -value_of(keys[k - 1]);
+    *es = -sum / static_cast<double>(k);
+}
+
+// m P&L values per row, P = the power of two >= m (the LDS holds P keys).
+__global__ __launch_bounds__(1024) void tail_kernel(const double* rows, int64_t S_tot, int base_col, int m, int P, int k,
+                                                    double* var, double* es) {
+    extern __shared__ int64_t keys[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const double* row = rows + static_cast<int64_t>(blockIdx.x) * S_tot;
+    int nan = 0;
+    for (int e = tid; e < P; e += nt) {
+        double v = INFINITY;
+        if (e < m) {
+            v = pnl_at(row, base_col, e);
+            nan |= v != v;
+        }
+        keys[e] = key_of(v);
+    }
+    if (__syncthreads_or(nan)) {                    // uniform over the block
+        if (tid == 0) {
+            var[blockIdx.x] = NAN;
+            es[blockIdx.x] = NAN;
+        }
+        return;
+    }
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += nt) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const int64_t a = keys[lo], b = keys[hi];
+                if ((a > b) == ((lo & size) == 0)) {
+                    keys[lo] = b;
+                    keys[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) tail_of_sorted(keys, k, var + blockIdx.x, es + blockIdx.x);
+}
+
+inline int pow2_at_least(int m) {
+    int p = 1;
+    while (p < m) p <<= 1;
+    return p;
+}
+
+int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
+    if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
+    if (base_col < -1 || base_col >= S_tot)
+        return adr_set_error(ADR_ERR_INVALID, w + ": base_col must be -1 (the rows are P&L) or a column, 0 .. " +
+                                                  std::to_string(S_tot - 1));
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    if (m < 1) return adr_set_error(ADR_ERR_INVALID, w + ": no P&L value is left beside the base column");
+    if (k < 1 || k > m)
+        return adr_set_error(ADR_ERR_INVALID, w + ": k must lie in 1 .. " + std::to_string(m) + " (the P&L values per row)");
+    if (m > ADR_SCENARIO_TAIL_MAX)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": " + std::to_string(m) + " P&L values per row; a row of at most "
+                                                  "ADR_SCENARIO_TAIL_MAX (16384) fits the LDS");
+    return ADR_OK;
+}
+
+hipError_t enqueue_tail(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var, double* es, hipStream_t stream) {
+    if (B > INT32_MAX) return hipErrorInvalidConfiguration;
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot, P = pow2_at_least(m);
+    const int threads = std::min(1024, std::max(kWave, P / 2));
+    const size_t lds = static_cast<size_t>(P) * sizeof(int64_t);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(tail_kernel, dim3(static_cast<unsigned>(B)), dim3(threads), lds, stream, rows, static_cast<int64_t>(S_tot),
+                       base_col, m, P, k, var, es);
+    return hipGetLastError();
+}
+
+}  // namespace sub
+}  // namespace adr
+
+namespace SB = adr::sub;
+
+extern "C" {
+
+int64_t adr_scenario_subbook_work(int64_t n, int64_t B, int S) {
+    if (n < 1 || B < 1 || S < 1) return 0;
+    return SB::max_chunks(n, B, SB::kChunk) * S;
+}
+
+int64_t adr_scenario_subbook_plan(int64_t n, int64_t B, const int64_t* sub_off, int64_t* plan) {
+    const int rc = SB::check_offsets("adr_scenario_subbook_plan", n, B, sub_off);
+    if (rc != ADR_OK) return rc;
+    int64_t C = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        if (plan) plan[b] = C;
+        C += (sub_off[b + 1] - sub_off[b] + SB::kChunk - 1) / SB::kChunk;
+    }
+    if (plan) {
+        plan[B] = C;
+        int64_t* bounds = plan + B + 1;
+        for (int64_t b = 0; b < B; ++b)
+            for (int64_t i = sub_off[b]; i < sub_off[b + 1]; i += SB::kChunk) {
+                *bounds++ = i;
+                *bounds++ = std::min(i + SB::kChunk, sub_off[b + 1]);
+            }
+    }
+    return B + 1 + 2 * C;
+}
+
+int adr_scenario_tail_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k, double* var_dev,
+                          double* es_dev, void* stream) {
+    const std::string w = "adr_scenario_tail_dev";
+    int rc = SB::check_tail(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows_dev || !var_dev || !es_dev) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    int device = 0;
+    hipStream_t own = nullptr;
+    rc = adr_ctx_target(ctx, &device, &own);
+    if (rc != ADR_OK) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = SB::enqueue_tail(rows_dev, B, S_tot, base_col, k, var_dev, es_dev, stream ? static_cast<hipStream_t>(stream) : own);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+int adr_scenario_tail(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es) {
+    const std::string w = "adr_scenario_tail";
+    int rc = SB::check_tail(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    int device = 0;
+    hipStream_t stream = nullptr;
+    rc = adr_ctx_target(ctx, &device, &stream);
+    if (rc != ADR_OK) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot;
+    double* base = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&base), (R + 2 * static_cast<size_t>(B)) * d);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double *dvar = base + R, *des = dvar + B;
+    e = hipMemcpyAsync(base, rows, R * d, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = SB::enqueue_tail(base, B, S_tot, base_col, k, dvar, des, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(var, dvar, B * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(es, des, B * d, hipMemcpyDeviceToHost, stream);
+    const hipError_t es_ = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = es_;
+    const hipError_t ef = hipFree(base);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+int adr_scenario_tail_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es) {
+    const std::string w = "adr_scenario_tail_host";
+    const int rc = SB::check_tail(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    adr::parallel_ranges(B, adr::pool_threads(B, 64), [&](int, int64_t lo, int64_t hi) {
+        std::vector<int64_t> keys(static_cast<size_t>(m));
+        for (int64_t b = lo; b < hi; ++b) {
+            const double* row = rows + b * S_tot;
+            bool nan = false;
+            for (int e = 0; e < m; ++e) {
+                const double v = SB::pnl_at(row, base_col, e);
+                nan |= v != v;
+                keys[e] = SB::key_of(v);
+            }
+            if (nan) {
+                var[b] = es[b] = NAN;
+                continue;
+            }
+            std::sort(keys.begin(), keys.end());
+            SB::tail_of_sorted(keys.data(), k, var + b, es + b);
+        }
+    });
+    return ADR_OK;
+}
+
+}  // extern "C"

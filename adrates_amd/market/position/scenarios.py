@@ -23,6 +23,11 @@ revalued under joint (curve, spread) scenarios by `ScenarioGrid.revalue_credit` 
 `pnl_credit` and `revalue_credit_on_curves` in one launch of
 csrc/credit_scenario_pv.hip (adr_credit_scenario_pv): a spread per trade, a spread
 shock per scenario and credit bucket.
+
+Sub-books - desks, counterparties, margin accounts - get their P&L vectors from the SAME single launch:
+`ScenarioGrid.revalue_sub_books` / `pnl_sub_books` (and the credit forms) take one key per trade and return one row
+per distinct key, each with the bits the whole-book call gives on that sub-book alone; `tail_measures` and
+`ScenarioGrid.sub_book_var_es` turn the rows into VaR and expected shortfall on the device (csrc/subbook.hip).
 """
 from __future__ import annotations
 
@@ -286,6 +291,153 @@ def revalue_credit_on_curves(method, times, dfs, spread_shocks, trades, spreads,
     return _finish(out, book.pv_const, book.order, per_trade)
 
 
+def _permute_batch(batch: TradeBatch, perm: np.ndarray):
+    """``(batch with trade j = trade perm[j] of ``batch``, fixed-flow gather index, float-coupon gather index)``."""
+    def gather(off):
+        off = np.asarray(off, dtype=np.int64)
+        length = (off[1:] - off[:-1])[perm]
+        new_off = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+        idx = np.repeat(off[:-1][perm] - new_off[:-1], length) + np.arange(int(new_off[-1]), dtype=np.int64)
+        return new_off, idx
+    fix_off, fi = gather(batch.fix_off)
+    flt_off, li = gather(batch.flt_off)
+    f = lambda name, idx: np.asarray(getattr(batch, name), dtype=np.float64)[idx]
+    weight = None if batch.flt_weight is None else np.asarray(batch.flt_weight, dtype=np.float64)[li]
+    return TradeBatch(fix_off, flt_off, f("fix_tp", fi), f("fix_pay", fi), f("flt_tp", li), f("flt_ts", li), f("flt_te", li),
+                      f("flt_alpha", li), f("notional", perm), f("spread", perm), f("fix_sign", perm), f("flt_sign", perm),
+                      weight), fi, li
+
+
+@dataclass
+class SubBooks:
+    """`split_sub_books`' result: the batch with every sub-book's trades consecutive, ``pv_const`` and ``order`` to match
+    (`compile_book`), the labels in order of first appearance, ``sub_off [B + 1]`` (sub-book ``b`` is the trades
+    ``sub_off[b] .. sub_off[b + 1]`` of the batch) and, where the batch was re-ordered, the gather indices of its trades,
+    fixed flows and float coupons (None: left as it was)."""
+    batch: TradeBatch
+    pv_const: Optional[np.ndarray]
+    order: Optional[np.ndarray]
+    labels: list
+    sub_off: np.ndarray
+    perm: Optional[np.ndarray] = None
+    fix_idx: Optional[np.ndarray] = None
+    flt_idx: Optional[np.ndarray] = None
+
+
+def split_sub_books(batch: TradeBatch, pv_const, order, keys) -> SubBooks:
+    """Cut a compiled book (`compile_book`'s triple) into sub-books by ``keys``, one hashable value per trade of the
+    CALLER's input, labelled in order of first appearance.
+
+    From an object list (``order`` given) the batch is stably sorted by label after `compile_book`'s own grouping, so a
+    sub-book's trades keep the order `compile_book` gives that sub-book alone.  A `TradeBatch` (``order`` None) is taken
+    as it is and must already hold each label's trades consecutively: `LibError` names the first label that reappears."""
+    keys = list(keys)
+    n = batch.n_trades
+    if len(keys) != n:
+        raise LibError(f"keys needs one entry per trade ({n}), not {len(keys)}")
+    labels, index = [], {}
+    for k in keys:
+        if k not in index:
+            index[k] = len(labels)
+            labels.append(k)
+    if order is None:
+        code = np.array([index[k] for k in keys], dtype=np.int64)
+        back = np.nonzero(code[1:] < code[:-1])[0]
+        # labels are numbered by first appearance, so a consecutive layout is a non-decreasing one
+        if back.size:
+            j = int(back[0]) + 1
+            raise LibError(f"the batch does not hold the trades of sub-book {keys[j]!r} consecutively: it reappears at trade "
+                           f"{j}; sort the batch by key, or pass the trade objects")
+        perm = None
+    else:
+        code = np.array([index[keys[i]] for i in order], dtype=np.int64)
+        perm = np.argsort(code, kind="stable")
+        code = code[perm]
+        if np.array_equal(perm, np.arange(n)):
+            perm = None
+    sub_off = np.searchsorted(code, np.arange(len(labels) + 1), side="left").astype(np.int64)
+    if perm is None:
+        return SubBooks(batch, pv_const, order, labels, sub_off)
+    batch, fi, li = _permute_batch(batch, perm)
+    return SubBooks(batch, None if pv_const is None else pv_const[perm], order[perm], labels, sub_off, perm, fi, li)
+
+
+def _finish_sub_books(out, sb: SubBooks, per_trade):
+    """Add the curve-independent amounts per sub-book in batch order and put per-trade rows back into the caller's order."""
+    const = sb.pv_const
+    if const is not None:
+        add = np.array([float(np.sum(const[lo:hi])) if np.any(const[lo:hi] != 0.0) else 0.0
+                        for lo, hi in zip(sb.sub_off[:-1], sb.sub_off[1:])])
+        live = add != 0.0
+        out["sub_pv"][live] = out["sub_pv"][live] + add[live, None]
+    out["labels"] = sb.labels
+    if per_trade:
+        pv = out["pv"] if const is None else out["pv"] + const[None, :]
+        if sb.order is not None and not np.array_equal(sb.order, np.arange(sb.order.size)):
+            back = np.empty_like(pv)
+            back[:, sb.order] = pv
+            pv = back
+        out["pv"] = pv
+    return out
+
+
+def revalue_on_curves_sub_books(method, times, dfs, trades, keys, value_dt, per_trade=False, ctx=None, host=False,
+                                curve_type=None):
+    """`revalue_on_curves` per sub-book, in ONE launch: ``keys`` holds one hashable value per trade (a desk, a
+    counterparty, an account).  Returns ``{"labels": [...], "sub_pv": [B, S]}`` - the labels in order of first appearance,
+    row ``b`` the PV vector of sub-book ``labels[b]``, bit for bit what `revalue_on_curves` gives on that sub-book alone
+    - and, with ``per_trade``, ``"pv": [S, n]`` in the caller's order.  A `TradeBatch` must hold each label's trades
+    consecutively (`split_sub_books`)."""
+    method = int(getattr(method, "value", method))
+    if method not in _SUPPORTED_INTERP:
+        raise LibError("Invalid interpolation scheme.")
+    sb = split_sub_books(*compile_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA), keys)
+    if host:
+        out = _native.scenario_subbook_pv_host(method, times, dfs, sb.batch, sb.sub_off, per_trade=per_trade)
+    else:
+        ctx = ctx or _native.default_context()
+        dev = _native.DeviceTrades(ctx, sb.batch)
+        try:
+            out = _native.scenario_subbook_pv(ctx, method, times, dfs, dev, sb.sub_off, per_trade=per_trade)
+        finally:
+            dev.close()
+    return _finish_sub_books(out, sb, per_trade)
+
+
+def _split_credit_sub_books(book: CreditBook, keys):
+    """`split_sub_books` for a credit book: ``(sub-books, z, bucket, fix_tau, flt_tau)`` in the re-ordered batch's order."""
+    sb = split_sub_books(book.batch, book.pv_const, book.order, keys)
+    if sb.perm is None:
+        return sb, book.z, book.bucket, book.fix_tau, book.flt_tau
+    return sb, book.z[sb.perm], book.bucket[sb.perm], book.fix_tau[sb.fix_idx], book.flt_tau[sb.flt_idx]
+
+
+def revalue_credit_on_curves_sub_books(method, times, dfs, spread_shocks, trades, spreads, buckets, keys, value_dt,
+                                       per_trade=False, ctx=None, host=False, curve_type=None):
+    """`revalue_credit_on_curves` per sub-book, in ONE launch (``keys``: see `revalue_on_curves_sub_books`; a sub-book
+    may cut across credit buckets).  Returns ``{"labels": [...], "sub_pv": [B, S], "buckets": [...]}`` - ``buckets`` the
+    credit-bucket labels, one column of ``spread_shocks`` each - and, with ``per_trade``, ``"pv": [S, n]``."""
+    method = int(getattr(method, "value", method))
+    if method not in _SUPPORTED_INTERP:
+        raise LibError("Invalid interpolation scheme.")
+    book = compile_credit_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA, spreads, buckets)
+    dz = _spread_rows(spread_shocks, len(book.labels))
+    sb, z, bucket, fix_tau, flt_tau = _split_credit_sub_books(book, keys)
+    if host:
+        out = _native.credit_scenario_subbook_pv_host(method, times, dfs, dz, sb.batch, z, bucket, fix_tau, flt_tau, sb.sub_off,
+                                                      per_trade=per_trade)
+    else:
+        ctx = ctx or _native.default_context()
+        dev = _native.DeviceTrades(ctx, sb.batch)
+        try:
+            out = _native.credit_scenario_subbook_pv(ctx, method, times, dfs, dz, dev, z, bucket, fix_tau, flt_tau, sb.sub_off,
+                                                     per_trade=per_trade)
+        finally:
+            dev.close()
+    out["buckets"] = book.labels
+    return _finish_sub_books(out, sb, per_trade)
+
+
 def shocked_breakevens(curve, shock: Shock) -> np.ndarray:
     """``[P]``: an inflation curve's breakeven rates under a shock in BASIS POINTS - a float shifts every pillar, a dict
     ``{tenor: shift}`` the named ones, tenors as ``to_tenor(curve.swap_times)`` labels them.  An inflation curve has no
@@ -350,6 +502,35 @@ def expected_shortfall(pnl, level: float = 0.99) -> float:
     """Minus the mean of the ``ceil((1 - level) * S)`` smallest P&Ls - the tail `historical_var` ends at, that
     scenario included."""
     return float(-np.mean(_tail(pnl, level)))
+
+
+def tail_count(level: float, n_pnl: int) -> int:
+    """``k`` of `historical_var` / `expected_shortfall` for ``n_pnl`` P&L values: ``ceil((1 - level) * n_pnl)``, at least 1."""
+    if n_pnl < 1 or not 0.0 < level < 1.0:
+        raise ValueError("a P&L vector and a confidence level inside (0, 1) are needed")
+    return max(1, int(np.ceil(round((1.0 - level) * n_pnl, 9))))
+
+
+def tail_measures(rows, level: float = 0.99, base_col: int = -1, host: bool = False, ctx=None):
+    """``(var [B], es [B])``: `historical_var` and `expected_shortfall` of every row of ``rows [B, S]`` in one kernel
+    (adr_scenario_tail; ``host=True``: its CPU twin, the same bits).  ``base_col >= 0``: the P&L of a row is every OTHER
+    column minus that column (the base curve priced as one more scenario); -1: the rows already are P&L.  ``es`` adds the
+    tail in ascending order, so it agrees with `expected_shortfall` (NumPy's pairwise mean) to rounding, not bit for
+    bit; ``var`` is the same order statistic.  A row holding a NaN gives NaN.  Rows wider than
+    ``_native.SCENARIO_TAIL_MAX`` P&L values do not fit the kernel's LDS and are done by NumPy per row."""
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    if rows.ndim != 2 or not -1 <= base_col < rows.shape[1]:
+        raise LibError(f"rows must have shape [n_rows, n_columns] and base_col be -1 or a column, not {list(rows.shape)}, {base_col}")
+    m = rows.shape[1] - (1 if base_col >= 0 else 0)
+    k = tail_count(level, m)
+    if m > _native.SCENARIO_TAIL_MAX:
+        pnl = rows if base_col < 0 else np.delete(rows, base_col, axis=1) - rows[:, base_col:base_col + 1]
+        out = np.array([[historical_var(r, level), expected_shortfall(r, level)] if not np.any(np.isnan(r)) else [np.nan, np.nan]
+                        for r in pnl]).reshape(-1, 2)
+        return out[:, 0].copy(), out[:, 1].copy()
+    if host:
+        return _native.scenario_tail_host(rows, k, base_col)
+    return _native.scenario_tail(ctx or _native.default_context(), rows, k, base_col)
 
 
 class ScenarioGrid:
@@ -479,6 +660,86 @@ class ScenarioGrid:
         zero spread shock gives exactly 0."""
         book = self._revalue_credit(trades, spreads, buckets, spread_shocks, False, True)["book_pv"]
         return book[:-1] - book[-1]
+
+    def _revalue_sub_books(self, trades, keys, per_trade, with_base):
+        sb = split_sub_books(*compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name]), keys)
+        dev = _native.DeviceTrades(self._ctx, sb.batch)
+        try:
+            if with_base:
+                out = _native.scenario_subbook_pv(self._ctx, self.curve._interp_type.value, self.base.times,
+                                                  np.vstack([self._dfs(), self.base.dfs[None, :]]), dev, sb.sub_off,
+                                                  per_trade=per_trade)
+            else:
+                out = _native.scenario_subbook_pv_set(self._ctx, self._set, dev, sb.sub_off, per_trade=per_trade)
+        finally:
+            dev.close()
+        return _finish_sub_books(out, sb, per_trade)
+
+    def revalue_sub_books(self, trades, keys, per_trade: bool = False):
+        """`revalue` per sub-book, in the SAME single launch: ``keys`` holds one hashable value per trade (a desk, a
+        counterparty, a margin account).  Returns ``{"labels": [...], "sub_pv": [B, S]}``: the labels in order of first
+        appearance, row ``b`` the PV vector of sub-book ``labels[b]`` - bit for bit `revalue`'s ``book_pv`` on that
+        sub-book alone, ready for `historical_var` - and, with ``per_trade``, ``"pv": [S, n]`` in the caller's order.
+        A `TradeBatch` must hold each label's trades consecutively (`split_sub_books`)."""
+        return self._revalue_sub_books(trades, keys, per_trade, False)
+
+    def pnl_sub_books(self, trades, keys) -> np.ndarray:
+        """``[B, S]``: `pnl` per sub-book (rows in the order of `revalue_sub_books`' labels), the base curve priced by
+        the same launch as one more scenario: a zero shock gives exactly 0 in every sub-book."""
+        sub = self._revalue_sub_books(trades, keys, False, True)["sub_pv"]
+        return sub[:, :-1] - sub[:, -1:]
+
+    def sub_book_var_es(self, trades, keys, level: float = 0.99):
+        """``{"labels": [...], "var": [B], "es": [B]}`` straight from the trades: the sub-book launch and the tail kernel
+        in one chain, so the ``[B, S]`` P&L matrix never leaves the device.  The P&L is `pnl_sub_books`' (scenario minus
+        base curve; what does not depend on the curve cancels and is not added), ``var`` and ``es`` are `tail_measures`'."""
+        sb = split_sub_books(*compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name]), keys)
+        S = len(self)
+        if S > _native.SCENARIO_TAIL_MAX:
+            raise LibError(f"{S} scenarios: at most {_native.SCENARIO_TAIL_MAX} fit the tail kernel; use pnl_sub_books and "
+                           "tail_measures")
+        dev = _native.DeviceTrades(self._ctx, sb.batch)
+        try:
+            var, es = _native.scenario_subbook_var_es(self._ctx, self.curve._interp_type.value, self.base.times,
+                                                      np.vstack([self._dfs(), self.base.dfs[None, :]]), dev, sb.sub_off,
+                                                      tail_count(level, S), base_col=S)
+        finally:
+            dev.close()
+        return {"labels": sb.labels, "var": var, "es": es}
+
+    def _revalue_credit_sub_books(self, trades, spreads, buckets, keys, spread_shocks, per_trade, with_base):
+        book = compile_credit_book(trades, self.curve._value_dt, CurveTypes[self.curve_name], spreads, buckets)
+        S, G = len(self), len(book.labels)
+        dz = _spread_rows(spread_shocks, G)
+        if dz is not None and dz.shape[0] not in (1, S):
+            raise LibError(f"{dz.shape[0]} spread-shock rows for a grid of {S} scenarios: one shared row or one per scenario")
+        sb, z, bucket, fix_tau, flt_tau = _split_credit_sub_books(book, keys)
+        dev = _native.DeviceTrades(self._ctx, sb.batch)
+        try:
+            if with_base:
+                if dz is not None:              # the base pair: the unshocked curve with a zero spread shock
+                    dz = np.vstack([np.broadcast_to(dz, (S, G)), np.zeros((1, G))])
+                out = _native.credit_scenario_subbook_pv(self._ctx, self.curve._interp_type.value, self.base.times,
+                                                         np.vstack([self._dfs(), self.base.dfs[None, :]]), dz, dev, z, bucket,
+                                                         fix_tau, flt_tau, sb.sub_off, per_trade=per_trade)
+            else:
+                out = _native.credit_scenario_subbook_pv_set(self._ctx, self._set, dz, dev, z, bucket, fix_tau, flt_tau,
+                                                             sb.sub_off, per_trade=per_trade)
+        finally:
+            dev.close()
+        out["buckets"] = book.labels
+        return _finish_sub_books(out, sb, per_trade)
+
+    def revalue_credit_sub_books(self, trades, spreads, keys, buckets=None, spread_shocks=None, per_trade: bool = False):
+        """`revalue_credit` per sub-book in one launch; ``keys`` as in `revalue_sub_books` (a sub-book may cut across
+        credit buckets).  Returns ``{"labels": [...], "sub_pv": [B, S], "buckets": [...]}`` - ``buckets`` the credit-bucket
+        labels, one column of ``spread_shocks`` each - and, with ``per_trade``, ``"pv": [S, n]``."""
+        return self._revalue_credit_sub_books(trades, spreads, buckets, keys, spread_shocks, per_trade, False)
+
+    def pnl_credit_sub_books(self, trades, spreads, keys, buckets=None, spread_shocks=None) -> np.ndarray:
+        """``[B, S]``: `pnl_credit` per sub-book, the base pair priced by the same launch as one more row."""
+        sub = self._revalue_credit_sub_books(trades, spreads, buckets, keys, spread_shocks, False, True)["sub_pv"]
+        return sub[:, :-1] - sub[:, -1:]
 
     def close(self):
         self._set.close()

@@ -83,6 +83,14 @@ pnl = grid.pnl(book_swaps)
 print(f"1 000 swaps x 250 scenarios: 99% VaR {historical_var(pnl, 0.99):,.0f}, 97.5% ES {expected_shortfall(pnl, 0.975):,.0f} GBP "
       f"(worst scenario {pnl.min():,.0f}, best {pnl.max():,.0f})")
 
+# ---- the same launch per desk: one key per trade, one P&L row, VaR and ES per sub-book (rows never leave the GPU)
+desks = [f"desk {int(d)}" for d in rng.integers(0, 8, len(book_swaps))]
+per_desk = grid.sub_book_var_es(book_swaps, desks, level=0.99)
+worst = int(np.argmax(per_desk["var"]))
+print(f"8 desks: largest 99% VaR {per_desk['var'][worst]:,.0f} GBP ({per_desk['labels'][worst]}), its ES "
+      f"{per_desk['es'][worst]:,.0f}; sum of desk VaRs {per_desk['var'].sum():,.0f} against the book's "
+      f"{historical_var(pnl, 0.99):,.0f}")
+
 # ---- inflation swaps under JOINT scenarios: the same 250 OIS curves, each paired with a breakeven move (basis points)
 from adrates_amd.market.position.yoy_book import YoYBook
 from adrates_amd.trades.market_data import inflation_curve, random_yoy_book

@@ -667,6 +667,89 @@ int adr_credit_scenario_pv_host(int interp_method, int K, const double* times, i
                                 const int32_t* bucket, const double* fix_tau, const double* flt_tau, double* pv, double* book_pv,
                                 int n_threads);
 
+/*
+ * Sub-books: the P&L vectors of B disjoint parts of a batch - desks, counterparties, margin accounts - from ONE launch
+ * of the scenario kernels, and their tail measures on the device.  The entries mirror adr_scenario_pv* and
+ * adr_credit_scenario_pv* and take everything their parents take, plus B >= 1 and sub_off[B + 1]: sub-book b holds the
+ * trades sub_off[b] .. sub_off[b + 1] of the batch.  The offsets run from 0 to n and do not decrease; a sub-book may be
+ * empty.  Outputs: sub_pv[B][S], row-major, always; pv[n][S] when given, with the parent's bits.
+ *
+ * sub_pv[b][s] has exactly the bits of the parent's book_pv[s] on a batch holding sub-book b's trades alone, in order:
+ * chunk c of sub-book b is the trades sub_off[b] + 64 c .., summed in order from 0.0; the sub-book's chunk j is added to
+ * slot j % 64 in order; then slots 0-31 += 32-63, ..., 0 += 1.  No atomics.  An empty sub-book's row is +0.0.  A row
+ * does not depend on B, on the other sub-books, on S or on the launch shape, and is bit-identical from run to run.
+ *
+ * How the chunks reach the device: as a PLAN, B + 1 + 2 C int64 for C chunks, which the caller of a _dev entry fills on
+ * the host with adr_scenario_subbook_plan and uploads (the blocking entries do both themselves).  plan[0 .. B] is the
+ * prefix of the sub-books' chunk counts (plan[B] = C <= ceil(n / 64) + B), then come C pairs (first trade, one past the
+ * last).  adr_scenario_subbook_plan(n, B, sub_off, plan) checks the offsets (ADR_ERR_INVALID naming the sub-book),
+ * fills plan when it is not NULL and returns the plan's length in int64.  adr_scenario_subbook_work(n, B, S) is the
+ * scratch of the _dev entries in doubles, (ceil(n / 64) + B) * S, for both families.
+ *
+ * The _dev entries take device arrays and the uploaded plan, enqueue on `stream` (NULL: the ctx's own) without
+ * allocation or synchronisation (three kernels in one chain: pricing, and the sum for small and for large sub-books)
+ * and check scalars only: a plan whose bounds leave 0 .. n is
+ * cut to that range, one with more chunks than the scratch holds is cut there.  The host-array entries refuse offsets
+ * that are not 0 .. n or that decrease.  The _host twins run the same code in the same order on CPU threads.
+ * adr_scenario_subbook_var_es chains adr_scenario_tail_dev's kernel behind the launch: var[B] and es[B] come back, the
+ * [B][S] rows never leave the device.
+ */
+int64_t adr_scenario_subbook_plan(int64_t n, int64_t B, const int64_t* sub_off, int64_t* plan);
+int64_t adr_scenario_subbook_work(int64_t n, int64_t B, int S);
+int adr_scenario_subbook_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S, const double* dfs,
+                            const adr_trades* trades, int64_t B, const int64_t* sub_off, double* pv, double* sub_pv);
+int adr_scenario_subbook_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S, const double* dfs_dev,
+                                const adr_trades* trades, int64_t B, const int64_t* plan_dev, double* pv_dev, double* sub_pv_dev,
+                                double* work_dev, void* stream);
+int adr_scenario_subbook_pv_set(adr_ctx* ctx, const adr_curve_set* set, const adr_trades* trades, int64_t B, const int64_t* sub_off,
+                                double* pv, double* sub_pv);
+int adr_scenario_subbook_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
+                                 const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                                 const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                                 const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                                 const double* flt_sign, int64_t B, const int64_t* sub_off, double* pv, double* sub_pv,
+                                 int n_threads);
+int adr_scenario_subbook_var_es(adr_ctx* ctx, int interp_method, int K, const double* times, int S, const double* dfs,
+                                const adr_trades* trades, int64_t B, const int64_t* sub_off, int base_col, int k, double* var,
+                                double* es);
+int adr_credit_scenario_subbook_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S_disc, const double* dfs,
+                                   int G, int S_spr, const double* dz, int S, const adr_trades* trades, const double* z,
+                                   const int32_t* bucket, int64_t n_fix, const double* fix_tau, int64_t n_flt,
+                                   const double* flt_tau, int64_t B, const int64_t* sub_off, double* pv, double* sub_pv);
+int adr_credit_scenario_subbook_pv_set(adr_ctx* ctx, const adr_curve_set* set, int G, int S_spr, const double* dz,
+                                       const adr_trades* trades, const double* z, const int32_t* bucket, int64_t n_fix,
+                                       const double* fix_tau, int64_t n_flt, const double* flt_tau, int64_t B,
+                                       const int64_t* sub_off, double* pv, double* sub_pv);
+int adr_credit_scenario_subbook_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S_disc,
+                                       const double* dfs_dev, int G, int S_spr, const double* dz_dev, int S,
+                                       const adr_trades* trades, const double* z_dev, const int32_t* bucket_dev, int64_t n_fix,
+                                       const double* fix_tau_dev, int64_t n_flt, const double* flt_tau_dev, int64_t B,
+                                       const int64_t* plan_dev, double* pv_dev, double* sub_pv_dev, double* work_dev, void* stream);
+int adr_credit_scenario_subbook_pv_host(int interp_method, int K, const double* times, int S_disc, const double* dfs, int G,
+                                        int S_spr, const double* dz, int S, int64_t n, const int64_t* fix_off,
+                                        const int64_t* flt_off, const double* fix_tp, const double* fix_pay, const double* flt_tp,
+                                        const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                                        const double* flt_weight, const double* notional, const double* spread,
+                                        const double* fix_sign, const double* flt_sign, const double* z, const int32_t* bucket,
+                                        const double* fix_tau, const double* flt_tau, int64_t B, const int64_t* sub_off,
+                                        double* pv, double* sub_pv, int n_threads);
+
+/*
+ * Tail measures of B rows at once: historical-simulation VaR and expected shortfall per sub-book.  rows[B][S_tot];
+ * base_col >= 0: the P&L of row b is rows[b][s] - rows[b][base_col] for every OTHER column s (the base curve priced as
+ * one more scenario); base_col = -1: the rows already are P&L.  k = 1 .. the P&L values per row.  var[b] is minus the
+ * k-th smallest P&L; es[b] is minus the sum of the k smallest, added in ascending order from 0.0, divided by k.  A row
+ * holding a NaN gives NaN in both.  No interpolation between order statistics.  One block per row sorts the row in LDS
+ * (a bitonic network over the next power of two, padded with +inf); rows of more than ADR_SCENARIO_TAIL_MAX P&L values
+ * are ADR_ERR_UNSUPPORTED.  adr_scenario_tail: host arrays, blocks; _dev: device arrays on `stream`, no allocation, no
+ * synchronisation; _host: the CPU twin, the same sums in the same order, hence the same bits.
+ */
+#define ADR_SCENARIO_TAIL_MAX 16384
+int adr_scenario_tail(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es);
+int adr_scenario_tail_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k, double* var_dev,
+                          double* es_dev, void* stream);
+int adr_scenario_tail_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 

@@ -1,0 +1,287 @@
+"""Sub-books of a scenario revaluation on the device: adr_scenario_subbook_pv*, adr_credit_scenario_subbook_pv*,
+adr_scenario_tail* and the `ScenarioGrid` methods over them.  The CPU twins: tests/test_subbook_scenarios_host.py."""
+import numpy as np
+import pytest
+import torch
+
+from adrates_amd import _native
+from adrates_amd.market.position.scenarios import ScenarioGrid, expected_shortfall, historical_var, tail_count, tail_measures
+from adrates_amd.utils.error import LibError
+
+from . import _credit_scenario_cases as CC
+from . import _fixtures as F
+from . import _scenario_cases as SC
+from . import _subbook_cases as SB
+from ._parity import REL_TOL
+from .test_subbook_scenarios_host import _mixed_list
+
+pytestmark = pytest.mark.gpu
+VD = SC.VD
+GUARD = -1.2345e300
+TAIL = 16
+
+
+@pytest.fixture(scope="module")
+def curves():
+    return SC.shocked_curves()
+
+
+def _device(ctx, method, times, dfs, batch, sub_off, per_trade=True):
+    dev = _native.DeviceTrades(ctx, batch)
+    try:
+        return _native.scenario_subbook_pv(ctx, method, times, dfs, dev, sub_off, per_trade=per_trade)
+    finally:
+        dev.close()
+
+
+def _parent(ctx, method, times, dfs, batch, per_trade=False):
+    dev = _native.DeviceTrades(ctx, batch)
+    try:
+        return _native.scenario_pv(ctx, method, times, dfs, dev, per_trade=per_trade)
+    finally:
+        dev.close()
+
+
+@pytest.fixture(scope="module")
+def sized(gpu_ctx):
+    """The sized book, its offsets and the device's result on the 9 curves (computed once, never changed)."""
+    times, dfs = SC.shocked_curves()
+    batch, sub_off = SB.sized_book(), SB.offsets(SB.SIZES)
+    return batch, sub_off, _device(gpu_ctx, 4, times, dfs, batch, sub_off)
+
+
+def test_every_sub_book_equals_itself_uploaded_alone(gpu_ctx, curves, sized):
+    times, dfs = curves
+    batch, sub_off, out = sized
+    parent = _parent(gpu_ctx, 4, times, dfs, batch, True)
+    assert np.array_equal(out["pv"], parent["pv"])                       # per-trade rows: the parent launch's bits
+    for b, (lo, hi) in enumerate(zip(sub_off[:-1], sub_off[1:])):
+        if lo == hi:
+            assert np.all(out["sub_pv"][b] == 0.0) and not np.any(np.signbit(out["sub_pv"][b]))
+            continue
+        alone = _parent(gpu_ctx, 4, times, dfs, SB.take(batch, lo, hi))["book_pv"]
+        assert np.array_equal(out["sub_pv"][b], alone), (b, lo, hi)
+        assert np.array_equal(out["sub_pv"][b], SC.book_sum(out["pv"][:, lo:hi])), (b, lo, hi)
+    # the host twin: within REL_TOL of the sub-book's gross notional
+    host = _native.scenario_subbook_pv_host(4, times, dfs, batch, sub_off)["sub_pv"]
+    err = np.max(np.abs(out["sub_pv"] - host) / SB.gross(batch, sub_off)[:, None])
+    print(f"device vs host twin per gross notional: {err:.2e}")
+    assert err <= REL_TOL
+
+
+def test_oracle_parity_of_the_per_trade_rows(gpu_ctx, curves):
+    times, dfs = curves
+    batch = SC.books()["300 mixed OIS"]
+    got = _device(gpu_ctx, 4, times, dfs, batch, SB.cuts(batch.n_trades, 7, 3))
+    err = SC.worst_unit_err(got["pv"], SC.oracle_pv(4, times, dfs, batch), batch)
+    print(f"sub-book launch vs the C oracle: {err:.2e}")
+    assert err <= REL_TOL
+
+
+@pytest.mark.parametrize("scheme", SC.SCHEMES, ids=lambda s: s.name)
+def test_one_sub_book_is_the_parent(gpu_ctx, curves, scheme):
+    times, dfs = curves
+    for name, batch in SC.books().items():
+        parent = _parent(gpu_ctx, scheme.value, times, dfs, batch, True)
+        got = _device(gpu_ctx, scheme.value, times, dfs, batch, [0, batch.n_trades])
+        assert np.array_equal(got["sub_pv"][0], parent["book_pv"]) and np.array_equal(got["pv"], parent["pv"]), name
+
+
+def test_independence_of_runs_order_and_scenario_count(gpu_ctx, curves, sized):
+    times, dfs = curves
+    batch, sub_off, out = sized
+    again = _device(gpu_ctx, 4, times, dfs, batch, sub_off)
+    assert np.array_equal(again["sub_pv"], out["sub_pv"]) and np.array_equal(again["pv"], out["pv"])
+    order = np.random.default_rng(4).permutation(len(SB.SIZES))
+    pbatch, poff = SB.permuted(batch, sub_off, order)
+    assert np.array_equal(_device(gpu_ctx, 4, times, dfs, pbatch, poff, False)["sub_pv"], out["sub_pv"][order])
+    wt, wide = SB.wide_curves()
+    small, small_off = SB.take(batch, 0, 400), SB.offsets((0, 1, 63, 64, 0, 0, 65, 127, 80, 0))
+    dev = _native.DeviceTrades(gpu_ctx, small)
+    full = _native.scenario_subbook_pv(gpu_ctx, 4, wt, wide, dev, small_off)["sub_pv"]
+    for S in SB.S_VALUES:                                                 # 1, 63, 65 and 130 end in a partial group
+        assert np.array_equal(_native.scenario_subbook_pv(gpu_ctx, 4, wt, wide[:S], dev, small_off)["sub_pv"], full[:, :S]), S
+    dev.close()
+
+
+@pytest.mark.parametrize("scheme", [SC.SCHEMES[0], SC.SCHEMES[2]], ids=lambda s: s.name)
+def test_large_knot_grid(gpu_ctx, scheme):
+    """K = 856: the knot tables of 64 scenarios no longer fit the LDS; the global-table variants."""
+    fine, rows, dz, case = CC.large_grid_call()
+    assert fine.size == 856
+    sub_off = SB.cuts(case.batch.n_trades, 5, 11)
+    got = _device(gpu_ctx, scheme.value, fine, rows, case.batch, sub_off)
+    dev = _native.DeviceTrades(gpu_ctx, case.batch)
+    cgot = _native.credit_scenario_subbook_pv(gpu_ctx, scheme.value, fine, rows, dz, dev, case.z, case.bucket, case.fix_tau,
+                                              case.flt_tau, sub_off)
+    dev.close()
+    for b, (lo, hi) in enumerate(zip(sub_off[:-1], sub_off[1:])):
+        if lo == hi:
+            continue
+        assert np.array_equal(got["sub_pv"][b], _parent(gpu_ctx, scheme.value, fine, rows, SB.take(case.batch, lo, hi))["book_pv"])
+        alone = CC.device_pv(gpu_ctx, scheme.value, fine, rows, dz, SB.take_case(case, lo, hi), False)["book_pv"]
+        assert np.array_equal(cgot["sub_pv"][b], alone)
+
+
+@pytest.mark.parametrize("shape", ["joint", "shared spread row", "shared curve"])
+def test_credit_sub_books_cut_across_buckets(gpu_ctx, curves, shape):
+    times, dfs = curves
+    G = 5
+    dz = CC.spread_shocks(dfs.shape[0], G)
+    if shape == "shared spread row":
+        dz = dz[1:2]
+    if shape == "shared curve":
+        dfs = dfs[2:3]
+    for scheme in SC.SCHEMES:
+        for name, case in CC.cases(G).items():
+            n = case.batch.n_trades
+            sub_off = SB.cuts(n, 6, len(name))
+            parent = CC.device_pv(gpu_ctx, scheme.value, times, dfs, dz, case)
+            dev = _native.DeviceTrades(gpu_ctx, case.batch)
+            args = (dev, case.z, case.bucket, case.fix_tau, case.flt_tau)
+            got = _native.credit_scenario_subbook_pv(gpu_ctx, scheme.value, times, dfs, dz, *args, sub_off, per_trade=True)
+            one = _native.credit_scenario_subbook_pv(gpu_ctx, scheme.value, times, dfs, dz, *args, [0, n])
+            dev.close()
+            assert np.array_equal(got["pv"], parent["pv"]) and np.array_equal(one["sub_pv"][0], parent["book_pv"]), name
+            host = _native.credit_scenario_subbook_pv_host(scheme.value, times, dfs, dz, case.batch, case.z, case.bucket,
+                                                           case.fix_tau, case.flt_tau, sub_off)["sub_pv"]
+            assert np.max(np.abs(got["sub_pv"] - host) / SB.gross(case.batch, sub_off)[:, None]) <= REL_TOL, name
+            for b, (lo, hi) in enumerate(zip(sub_off[:-1], sub_off[1:])):
+                if lo == hi:
+                    assert np.all(got["sub_pv"][b] == 0.0) and not np.any(np.signbit(got["sub_pv"][b]))
+                    continue
+                alone = CC.device_pv(gpu_ctx, scheme.value, times, dfs, dz, SB.take_case(case, lo, hi), False)["book_pv"]
+                assert np.array_equal(got["sub_pv"][b], alone), (name, b)
+                assert np.array_equal(got["sub_pv"][b], SC.book_sum(got["pv"][:, lo:hi])), (name, b)
+
+
+def _guarded(count, dev):
+    return torch.full((count + TAIL,), GUARD, dtype=torch.float64, device=dev)
+
+
+def test_dev_entries_on_a_callers_stream_into_guarded_buffers(gpu_ctx, sized):
+    """adr_scenario_subbook_pv_dev, adr_credit_scenario_subbook_pv_dev and adr_scenario_tail_dev: 16 words behind sub_pv,
+    pv, work, var and es keep their pattern; pv = NULL writes no per-trade row."""
+    batch, sub_off, out = sized
+    wt, wide = SB.wide_curves(65)
+    B, n, S = len(SB.SIZES), batch.n_trades, 65
+    want = _device(gpu_ctx, 4, wt, wide, batch, sub_off)
+    dev = torch.device("cuda", 0)
+    trades = _native.DeviceTrades(gpu_ctx, batch)
+    times_t, dfs_t = torch.from_numpy(wt).to(dev), torch.from_numpy(wide).to(dev)
+    plan_t = torch.from_numpy(_native.scenario_subbook_plan(n, sub_off)).to(dev)
+    W = _native.scenario_subbook_work(n, B, S)
+    stream = torch.cuda.Stream(dev)
+    k = 3
+    for per_trade in (True, False):
+        sub, work, pv = _guarded(B * S, dev), _guarded(W, dev), _guarded(n * S, dev)
+        var, es = _guarded(B, dev), _guarded(B, dev)
+        with torch.cuda.stream(stream):
+            _native.scenario_subbook_pv_dev(gpu_ctx, 4, wt.size, times_t.data_ptr(), S, dfs_t.data_ptr(), trades, B,
+                                            plan_t.data_ptr(), sub.data_ptr(), work.data_ptr(), pv.data_ptr() if per_trade else 0,
+                                            stream.cuda_stream)
+            _native.scenario_tail_dev(gpu_ctx, B, S, sub.data_ptr(), k, var.data_ptr(), es.data_ptr(), base_col=S - 1,
+                                      stream=stream.cuda_stream)
+            stream.synchronize()
+        for buf, count in ((sub, B * S), (work, W), (pv, n * S), (var, B), (es, B)):
+            assert torch.all(buf[count:] == GUARD)
+        assert np.array_equal(sub[:B * S].reshape(B, S).cpu().numpy(), want["sub_pv"])
+        if per_trade:
+            assert np.array_equal(pv[:n * S].reshape(n, S).cpu().numpy().T, want["pv"])
+        else:
+            assert torch.all(pv == GUARD)
+        hv, he = _native.scenario_tail_host(want["sub_pv"], k, base_col=S - 1)
+        assert np.array_equal(var[:B].cpu().numpy(), hv) and np.array_equal(es[:B].cpu().numpy(), he)
+    with pytest.raises(LibError, match="plan is NULL"):
+        _native.scenario_subbook_pv_dev(gpu_ctx, 4, wt.size, times_t.data_ptr(), S, dfs_t.data_ptr(), trades, B, 0,
+                                        sub.data_ptr(), work.data_ptr())
+    trades.close()
+    # the credit entry
+    G = 5
+    case = CC.cases(G)["payment lag"]
+    n, sub_off = case.batch.n_trades, SB.cuts(case.batch.n_trades, 6, 2)
+    B = 6
+    dz = CC.spread_shocks(S, G)
+    trades = _native.DeviceTrades(gpu_ctx, case.batch)
+    want = _native.credit_scenario_subbook_pv(gpu_ctx, 4, wt, wide, dz, trades, case.z, case.bucket, case.fix_tau, case.flt_tau,
+                                              sub_off, per_trade=True)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    held = dict(times=times_t, dfs=dfs_t, dz=up(dz), z=up(case.z), bucket=up(case.bucket.astype(np.int32)), fix_tau=up(case.fix_tau),
+                flt_tau=up(case.flt_tau), plan=up(_native.scenario_subbook_plan(n, sub_off)))
+    ptrs = {name: t.data_ptr() for name, t in held.items()}
+    W = _native.scenario_subbook_work(n, B, S)
+    for per_trade in (True, False):
+        sub, work, pv = _guarded(B * S, dev), _guarded(W, dev), _guarded(n * S, dev)
+        with torch.cuda.stream(stream):
+            _native.credit_scenario_subbook_pv_dev(gpu_ctx, 4, wt.size, S, G, S, S, trades, case.fix_tau.size, case.flt_tau.size, B,
+                                                   ptrs, sub.data_ptr(), work.data_ptr(), pv.data_ptr() if per_trade else 0,
+                                                   stream.cuda_stream)
+            stream.synchronize()
+        for buf, count in ((sub, B * S), (work, W), (pv, n * S)):
+            assert torch.all(buf[count:] == GUARD)
+        assert np.array_equal(sub[:B * S].reshape(B, S).cpu().numpy(), want["sub_pv"])
+        if per_trade:
+            assert np.array_equal(pv[:n * S].reshape(n, S).cpu().numpy().T, want["pv"])
+        else:
+            assert torch.all(pv == GUARD)
+    trades.close()
+
+
+def test_tail_kernel(gpu_ctx):
+    for rows, base_col, k, nan_row in SB.tail_calls():
+        var, es = _native.scenario_tail(gpu_ctx, rows, k, base_col)
+        hv, he = _native.scenario_tail_host(rows, k, base_col)
+        assert np.array_equal(var, hv, equal_nan=True) and np.array_equal(es, he, equal_nan=True), (rows.shape, base_col, k)
+        assert np.array_equal(np.signbit(var), np.signbit(hv))
+        SB.check_tail(var, es, rows, base_col, k, nan_row)
+    wide = np.random.default_rng(3).normal(0.0, 1.0, (2, 16385))
+    with pytest.raises(LibError, match=r"\(-2\).*16384"):                 # ADR_ERR_UNSUPPORTED
+        _native.scenario_tail(gpu_ctx, wide, 3)
+    var, es = tail_measures(wide, 0.99, ctx=gpu_ctx)                      # falls back to NumPy per row
+    assert var[1] == historical_var(wide[1], 0.99) and es[1] == expected_shortfall(wide[1], 0.99)
+
+
+def test_grid_methods(gpu_ctx):
+    model = F.gbp_model(VD)
+    trades, keys = _mixed_list()
+    shocks = [0.0, 0.01, -0.01, 0.5, -0.5, 2.0, -2.0, {"5Y": 0.25}, {"3M": -0.1, "30Y": 0.2}]
+    grid = ScenarioGrid(model, "GBP_OIS_SONIA", shocks, with_gamma=False, ctx=gpu_ctx)
+    try:
+        labels = grid.revalue_sub_books(trades, keys)["labels"]
+        pnl = grid.pnl_sub_books(trades, keys)
+        assert pnl.shape == (len(labels), 9) and np.all(pnl[:, 0] == 0.0)          # a zero shock: exactly 0 in every sub-book
+        out = grid.revalue_sub_books(trades, keys, per_trade=True)
+        assert np.array_equal(out["pv"], grid.revalue(trades, per_trade=True)["pv"])
+        for b, lab in enumerate(labels):
+            mine = [t for t, k in zip(trades, keys) if k == lab]
+            assert np.array_equal(pnl[b], grid.pnl(mine)), lab
+            assert np.array_equal(out["sub_pv"][b], grid.revalue(mine)["book_pv"]), lab
+        spreads = [0.0 if type(t).__name__ == "OIS" else 0.004 + 0.0001 * (i % 7) for i, t in enumerate(trades)]
+        buckets = [None if type(t).__name__ == "OIS" else "AA" for t in trades]
+        dz = np.linspace(0.0, 0.002, 9)[:, None]
+        cpnl = grid.pnl_credit_sub_books(trades, spreads, keys, buckets, dz)
+        assert np.all(cpnl[:, 0] == 0.0)
+        for b, lab in enumerate(labels):
+            idx = [i for i, k in enumerate(keys) if k == lab]
+            sub_b = [buckets[i] for i in idx]
+            alone = grid.pnl_credit([trades[i] for i in idx], [spreads[i] for i in idx], sub_b,
+                                    dz if any(x is not None for x in sub_b) else None)
+            assert np.array_equal(cpnl[b], alone), lab
+        # straight to VaR and ES: the bounds of the tail kernel's test, on the downloaded P&L rows
+        swaps = [t for t in trades if type(t).__name__ == "OIS"]
+        skeys = [k for t, k in zip(trades, keys) if type(t).__name__ == "OIS"]
+        got = grid.sub_book_var_es(swaps, skeys, level=0.75)
+        rows = grid.pnl_sub_books(swaps, skeys)
+        k = tail_count(0.75, 9)
+        assert k == 3 and got["labels"] == grid.revalue_sub_books(swaps, skeys)["labels"]
+        for b, row in enumerate(rows):
+            assert got["var"][b] == historical_var(row, 0.75)
+            bound = (k + 1) * 2.0 ** -52 * np.mean(np.abs(np.sort(row)[:k]))
+            assert abs(got["es"][b] - expected_shortfall(row, 0.75)) <= bound
+        batch = SC.lag_book(30, seed=3)
+        with pytest.raises(LibError, match="sub-book 'a'.*reappears at trade 20"):
+            grid.revalue_sub_books(batch, ["a"] * 10 + ["b"] * 10 + ["a"] * 10)
+        with pytest.raises(LibError, match="keys needs one entry per trade"):
+            grid.pnl_sub_books(trades, keys[:-1])
+    finally:
+        grid.close()
