@@ -805,11 +805,9 @@ def scenario_pv(ctx: Context, method: int, times, dfs, trades: DeviceTrades, per
     return _scenario_result(book, pv, per_trade)
 
 
-def scenario_pv_host(method: int, times, dfs, batch, per_trade=False, n_threads=0):
-    """`scenario_pv` on the CPU (adr_scenario_pv_host) for a `TradeBatch`: the same per-trade arithmetic and the same
-    order of the book sum; no GPU needed."""
-    times, dfs = _scenario_curves(times, dfs)
-    S, n = dfs.shape[0], int(batch.n_trades)
+def _batch_arrays(batch):
+    """The arrays of a `TradeBatch` as the _host entries take them: ``(n, fix_off, flt_off, values dict, flt_weight)``."""
+    n = int(batch.n_trades)
     fo = np.ascontiguousarray(batch.fix_off, dtype=np.int64)
     lo = np.ascontiguousarray(batch.flt_off, dtype=np.int64)
     if fo.shape != (n + 1,) or lo.shape != (n + 1,):
@@ -820,6 +818,15 @@ def scenario_pv_host(method: int, times, dfs, batch, per_trade=False, n_threads=
     w = None if w is None else _f64(w)
     if w is not None and w.shape != a["flt_tp"].shape:
         raise LibError("flt_weight must have one entry per float coupon")
+    return n, fo, lo, a, w
+
+
+def scenario_pv_host(method: int, times, dfs, batch, per_trade=False, n_threads=0):
+    """`scenario_pv` on the CPU (adr_scenario_pv_host) for a `TradeBatch`: the same per-trade arithmetic and the same
+    order of the book sum; no GPU needed."""
+    times, dfs = _scenario_curves(times, dfs)
+    n, fo, lo, a, w = _batch_arrays(batch)
+    S = dfs.shape[0]
     book = np.empty(S)
     pv = np.empty((n, S)) if per_trade else None
     _check(load().adr_scenario_pv_host(int(method), times.size, _ptr(times), S, _ptr(dfs), n, _ptr(fo, _i64p), _ptr(lo, _i64p),
@@ -1005,17 +1012,7 @@ def credit_scenario_pv_host(method: int, times, dfs, dz, batch, z, bucket, fix_t
     """`credit_scenario_pv` on the CPU (adr_credit_scenario_pv_host) for a `TradeBatch`: the same per-coupon arithmetic
     and the same order of the book sum; no GPU needed."""
     times, dfs = _scenario_curves(times, dfs)
-    n = int(batch.n_trades)
-    fo = np.ascontiguousarray(batch.fix_off, dtype=np.int64)
-    lo = np.ascontiguousarray(batch.flt_off, dtype=np.int64)
-    if fo.shape != (n + 1,) or lo.shape != (n + 1,):
-        raise LibError("offset arrays must have n_trades + 1 entries")
-    a = {k: _f64(getattr(batch, k)) for k in ("fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional",
-                                              "spread", "fix_sign", "flt_sign")}
-    w = getattr(batch, "flt_weight", None)
-    w = None if w is None else _f64(w)
-    if w is not None and w.shape != a["flt_tp"].shape:
-        raise LibError("flt_weight must have one entry per float coupon")
+    n, fo, lo, a, w = _batch_arrays(batch)
     dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, a["fix_tp"].size,
                                                             a["flt_tp"].size)
     S = _credit_counts(dfs.shape[0], dz.shape[0])
@@ -1069,22 +1066,6 @@ def _sub_result(sub_pv, pv, per_trade):
     if per_trade:
         out["pv"] = pv.T
     return out
-
-
-def _batch_arrays(batch):
-    """The arrays of a `TradeBatch` as the _host entries take them: ``(n, fix_off, flt_off, values dict, flt_weight)``."""
-    n = int(batch.n_trades)
-    fo = np.ascontiguousarray(batch.fix_off, dtype=np.int64)
-    lo = np.ascontiguousarray(batch.flt_off, dtype=np.int64)
-    if fo.shape != (n + 1,) or lo.shape != (n + 1,):
-        raise LibError("offset arrays must have n_trades + 1 entries")
-    a = {k: _f64(getattr(batch, k)) for k in ("fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional",
-                                              "spread", "fix_sign", "flt_sign")}
-    w = getattr(batch, "flt_weight", None)
-    w = None if w is None else _f64(w)
-    if w is not None and w.shape != a["flt_tp"].shape:
-        raise LibError("flt_weight must have one entry per float coupon")
-    return n, fo, lo, a, w
 
 
 def scenario_subbook_plan(n_trades: int, sub_off) -> np.ndarray:

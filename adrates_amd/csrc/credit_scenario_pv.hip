@@ -7,20 +7,16 @@
 // carries no spread.  Under the log-linear schemes ln D(tp) is a weighted sum of two table entries, so -x tau is added
 // to the exponent and a bond flow still costs ONE exp; under LINEAR_FWD_RATES the factor is an exp of its own.
 //
-// Layout (scenario_pv.hip's): one lane = one scenario, a block = kWaves waves of ONE group of 64 scenarios that share
-// the group's discount table in LDS as tab[k][lane] (ln d under the log-linear schemes, d under LINEAR_FWD_RATES) and
-// the group's spread table dzt[g][lane], so x costs one conflict-free ds_read_b64 per trade.  Where the two do not fit
-// together the small spread table stays in LDS and the lanes read their discount rows from global memory.  The trades
-// are cut into chunks of ADR_SCENARIO_CHUNK; a wave takes chunks round-robin and walks each in trade order.  Lane l
-// describes coupon l of the trade (scenario_pv.hip: segment searches, knot indices and weights, the dates that need no
-// evaluation of their own) and the wave walks the coupons in order, fetching coupon j's description from lane j with
-// v_readlane into scalar registers.
+// Layout, lookup form, lane broadcast and book sum: scenario_common.hpp.  Beside the group's discount table the block
+// holds the group's spread table dzt[g][lane], so x costs one conflict-free ds_read_b64 per trade.  Where the two do not
+// fit together the small spread table stays in LDS and the lanes read their discount rows from global memory.  Lane l
+// describes coupon l of the trade as in scenario_pv.hip (segment searches, knot indices and weights, the dates that need
+// no evaluation of their own).
 //
 // A trade with z = 0 and bucket = -1 has no spread: that is uniform over the wave, and such a trade takes
 // scenario_pv.hip's own coupon code behind a uniform branch (no tau is read, no factor formed).
 //
-// A shared row (S_disc = 1 or S_spr = 1: "not shocked") is read with row stride 0.  The book sum is scenario_pv.hip's:
-// chunk sums in trade order, chunk j to slot j % 64 in order, a halving tree; no atomics.  The host twin
+// A shared row (S_disc = 1 or S_spr = 1: "not shocked") is read with row stride 0.  The host twin
 // (adr_credit_scenario_pv_host) runs the same per-date and per-coupon code in the same order on CPU threads.
 #include <hip/hip_runtime.h>
 
@@ -32,51 +28,15 @@
 
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
-#include "kernels.hpp"
-#include "simple_interp.hpp"
+#include "scenario_common.hpp"
 #include "subbook.hpp"
 
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
-int adr_ctx_compute_units(const adr_ctx* ctx);                                  // capi.hip
-const adr::TradesDev* adr_trades_device_view(const adr_trades* trades, const adr_ctx** owner);              // capi.hip
-int adr_curve_set_device_view(const adr_curve_set* set, const adr_ctx** owner, int* method, int* K, int* S,
-                              const double** times_dev, const double** dfs_dev);                            // capi.hip
-
-// The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
-// exp / log implementations.
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
 
 namespace adr {
 namespace cscen {
 
-constexpr int kWave = 64;
-constexpr int kWaves = 16;                      // waves per block: four per SIMD, all on one scenario group
-constexpr int kThreads = kWave * kWaves;
-constexpr int kChunk = ADR_SCENARIO_CHUNK;      // trades per partial sum of the book
-constexpr int kRedLanes = 64;                   // the book reduction's slots per scenario
-constexpr int kRedEntries = 16;                 // scenarios per reduction block
-constexpr size_t kLdsBudget = 160 * 1024;
-
-// D(t) in weight form on the scenario's table T (T_k = ln d_k when kLog, else d_k):
-//   kLog:  ln D = wa T_a + (b != a ? wb T_b : 0);      else:  D = T_a + (b != a ? wb (T_b - T_a) : 0).
-struct DateW {
-    int a, b;
-    double wa, wb;
-};
-
-template <bool kLog>
-__host__ __device__ inline DateW date_weights(double t, const double* x, int K, int method) {
-    DateW d;
-    if (kLog) {
-        const si::LogWeights w = si::log_weights(t, x, K, method);
-        d.a = w.a; d.b = w.b; d.wa = w.wa; d.wb = w.wb;
-    } else {
-        const si::Where p = si::locate(t, x, K);
-        d.a = p.lo; d.b = p.hi; d.wa = 1.0; d.wb = p.w;
-    }
-    return d;
-}
+using namespace scen;    // the shared pieces (scenario_common.hpp)
 
 // ln D (kLog) or D on the table: the part of a discount factor before its exponential.
 template <bool kLog, class Tab>
@@ -221,20 +181,6 @@ __host__ __device__ inline bool leg_fits(int64_t begin, int64_t count, int64_t t
     return begin >= 0 && count >= 0 && begin + count <= total;
 }
 
-// book[s] = sum over the chunk rows of entry s: chunk j to slot j % 64 in order, then slots 0-31 += 32-63, ..., 0 += 1.
-void reduce_chunks(const double* work, int64_t chunks, int64_t S, double* book) {
-    for (int64_t e = 0; e < S; ++e) {
-        double p[kRedLanes];
-        for (int cl = 0; cl < kRedLanes; ++cl) {
-            p[cl] = 0.0;
-            for (int64_t j = cl; j < chunks; j += kRedLanes) p[cl] = p[cl] + work[j * S + e];
-        }
-        for (int h = kRedLanes / 2; h >= 1; h >>= 1)
-            for (int cl = 0; cl < h; ++cl) p[cl] = p[cl] + p[cl + h];
-        book[e] = p[0];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------ device
 struct Args {
     TradesDev tr;
@@ -249,19 +195,6 @@ struct Args {
     double *pv, *work;               // [n][S] or null; [n_chunks][S]
     const int64_t *sub_chunks, *sub_bounds;      // kSub: the plan's chunk count and its [chunks][2] trade bounds (subbook.hpp)
 };
-
-__device__ inline int lane_int(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-__device__ inline double lane_dbl(double v, int j) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
-}
-__device__ inline DateW lane_date(const DateW& d, int j) {
-    DateW r;
-    r.a = lane_int(d.a, j);
-    r.b = lane_int(d.b, j);
-    r.wa = lane_dbl(d.wa, j);
-    r.wb = r.b != r.a ? lane_dbl(d.wb, j) : 0.0;
-    return r;
-}
 
 // Lane j's slot in scalar registers; only the parts its flags say will be read.
 template <bool kSpread>
@@ -287,16 +220,6 @@ __device__ inline Slot lane_slot(const Slot& m, int j, bool weighted) {
     }
     return u;
 }
-
-// kLds: the group's discount table sits in LDS; otherwise every lane reads its scenario's row of dfs.
-template <bool kLog, bool kLds>
-struct DevTab {
-    const double* p;     // kLds: &tab[0][lane]; else &dfs[row][0]
-    __device__ double operator()(int k) const {
-        if (kLds) return p[k * kWave];
-        return kLog ? log(p[k]) : p[k];
-    }
-};
 
 // kSub: the chunks are those of a sub-book plan (their trade bounds come from a table) instead of ch * kChunk.
 template <bool kLog, bool kLds, bool kSub>
@@ -326,15 +249,9 @@ __global__ __launch_bounds__(kThreads) void credit_scenario_pv_kernel(Args a) {
     }
     for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < n_chunks;
          ch += static_cast<int64_t>(gridDim.x) * kWaves) {
-        int64_t i0 = ch * kChunk, i1 = ch * kChunk + kChunk;
-        if (kSub) {
-            i0 = a.sub_bounds[2 * ch];                      // uniform: scalar loads
-            i1 = a.sub_bounds[2 * ch + 1];
-            i0 = i0 < 0 ? 0 : i0;
-        }
-        i1 = i1 < a.tr.n ? i1 : a.tr.n;
+        const ChunkRange r = chunk_range<kSub>(ch, a.sub_bounds, a.tr.n);
         double book = 0.0;
-        for (int64_t i = i0; i < i1; ++i) {
+        for (int64_t i = r.i0; i < r.i1; ++i) {
             const TradeHeader h = a.tr.header[i];           // uniform: scalar loads
             const double z = a.z[i];
             const int bucket = a.bucket[i];
@@ -370,26 +287,6 @@ __global__ __launch_bounds__(kThreads) void credit_scenario_pv_kernel(Args a) {
     }
 }
 
-// book[e] = the fixed-order sum of the chunk rows (reduce_chunks above is its host form).
-__global__ __launch_bounds__(kRedLanes * kRedEntries) void credit_scenario_book_kernel(const double* work, int64_t chunks,
-                                                                                       int64_t S, double* book) {
-    __shared__ double sh[kRedLanes][kRedEntries];
-    const int ei = threadIdx.x % kRedEntries, cl = threadIdx.x / kRedEntries;
-    const int64_t e = static_cast<int64_t>(blockIdx.x) * kRedEntries + ei;
-    double acc = 0.0;
-    if (e < S) {
-#pragma unroll 8
-        for (int64_t j = cl; j < chunks; j += kRedLanes) acc = acc + work[j * S + e];
-    }
-    sh[cl][ei] = acc;
-    __syncthreads();
-    for (int h = kRedLanes / 2; h >= 1; h >>= 1) {
-        if (cl < h) sh[cl][ei] = sh[cl][ei] + sh[cl + h][ei];
-        __syncthreads();
-    }
-    if (cl == 0 && e < S) book[e] = sh[0][ei];
-}
-
 // -------------------------------------------------------------------------------------------------------------- host
 // Knot times, the spread table and (table) the discount table: 8 (65 K + 64 G) bytes, so with G = 32 the discount table
 // stays in LDS up to K = (20480 - 2048) / 65 = 283 knots, with G = 0 up to scenario_pv.hip's 315.
@@ -417,11 +314,8 @@ struct Extra {           // what the trades carry besides the batch
 };
 
 int validate(const std::string& w, const Curves& c, int64_t n, const Extra& x, const void* book) {
-    if (c.method != ADR_INTERP_FLAT_FWD_RATES && c.method != ADR_INTERP_LINEAR_FWD_RATES && c.method != ADR_INTERP_LINEAR_ZERO_RATES)
-        return adr_set_error(ADR_ERR_INVALID, w + ": the scheme must be FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) or "
-                                                  "LINEAR_ZERO_RATES (4)");
-    if (c.K < 2 || c.K > ADR_SCENARIO_MAX_KNOTS)
-        return adr_set_error(ADR_ERR_INVALID, w + ": the knot grid needs 2 .. ADR_SCENARIO_MAX_KNOTS (4096) knots");
+    const int rc = check_scheme_knots(w, c.method, c.K);
+    if (rc != ADR_OK) return rc;
     if (c.G < 0 || c.G > ADR_CREDIT_MAX_BUCKETS)
         return adr_set_error(ADR_ERR_INVALID, w + ": 0 .. ADR_CREDIT_MAX_BUCKETS (32) spread buckets are allowed");
     if (c.S < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one scenario is needed");
@@ -436,17 +330,6 @@ int validate(const std::string& w, const Curves& c, int64_t n, const Extra& x, c
     if ((x.n_fix > 0 && !x.fix_tau) || (x.n_flt > 0 && !x.flt_tau))
         return adr_set_error(ADR_ERR_INVALID, w + ": null spread-time array");
     if (!book) return adr_set_error(ADR_ERR_INVALID, w + ": book_pv is NULL");
-    return ADR_OK;
-}
-
-int check_curves(const std::string& w, const Curves& c) {
-    for (int k = 0; k < c.K; ++k)
-        if (!std::isfinite(c.times[k]) || (k > 0 && c.times[k] < c.times[k - 1]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": knot times must be finite and non-decreasing");
-    for (int64_t i = 0; i < static_cast<int64_t>(c.S_disc) * c.K; ++i)
-        if (!(c.dfs[i] > 0.0) || !std::isfinite(c.dfs[i]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": discount factors must be positive and finite (row " +
-                                                      std::to_string(i / c.K) + ", knot " + std::to_string(i % c.K) + ")");
     return ADR_OK;
 }
 
@@ -469,19 +352,11 @@ int check_spreads(const std::string& w, const Curves& c, int64_t n, const Extra&
     return ADR_OK;
 }
 
-template <bool kLog, bool kLds, bool kSub>
-hipError_t launch_as(const Args& a, dim3 grid, hipStream_t stream) {
-    const size_t lds = lds_bytes(a.K, a.G, kLds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&credit_scenario_pv_kernel<kLog, kLds, kSub>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((credit_scenario_pv_kernel<kLog, kLds, kSub>), grid, dim3(kThreads), lds, stream, a);
-    return hipGetLastError();
-}
-
 template <bool kLog, bool kLds>
 hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
-    return a.sub_bounds ? launch_as<kLog, kLds, true>(a, grid, stream) : launch_as<kLog, kLds, false>(a, grid, stream);
+    const size_t lds = lds_bytes(a.K, a.G, kLds);
+    if (a.sub_bounds) return launch_with_lds(&credit_scenario_pv_kernel<kLog, kLds, true>, a, lds, grid, stream);
+    return launch_with_lds(&credit_scenario_pv_kernel<kLog, kLds, false>, a, lds, grid, stream);
 }
 
 // The two kernels on `stream`; every pointer is device memory.  B > 0: the chunks of the sub-book plan `plan`, and
@@ -498,33 +373,23 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Curves& c, const adr_trade
     const bool subs = B != 0 || plan;
     if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
     if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
-    if (stream_or_null) stream = stream_or_null;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     const int64_t chunks = subs ? sub::max_chunks(tr->n, B, kChunk) : (tr->n + kChunk - 1) / kChunk;
-    const int64_t groups = (static_cast<int64_t>(c.S) + kWave - 1) / kWave;
-    if (groups > 65535) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 65535 * 64 scenarios in one launch");
-    // one block per compute unit when the tables fill the LDS; a group's blocks share its chunks round-robin
-    const int64_t per_group = std::max<int64_t>(1, (adr_ctx_compute_units(ctx) + groups - 1) / groups);
-    const int64_t bx = std::min<int64_t>((chunks + kWaves - 1) / kWaves, per_group);
-    const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(groups));
+    dim3 grid;
+    rc = launch_grid(w, ctx, chunks, c.S, &grid);
+    if (rc != ADR_OK) return rc;
     const sub::Plan pl = subs ? sub::plan_view(plan, B) : sub::Plan{nullptr, nullptr};
     const Args a{*tr, c.times, c.dfs, c.dz, x.z, x.bucket, x.fix_tau, x.flt_tau, x.n_fix, x.n_flt, c.K, c.S, c.G, c.method,
                  c.S_disc == 1 ? 0 : c.K, c.S_spr == 1 ? 0 : c.G, chunks, pv, work, subs ? pl.chunk_off + B : nullptr, pl.bounds};
     const bool in_lds = lds_bytes(c.K, c.G, true) <= kLdsBudget;
     const bool lin = c.method == ADR_INTERP_LINEAR_FWD_RATES;
+    hipError_t e;
     if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
     else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
     if (e == hipSuccess && subs) e = sub::enqueue_sum(work, pl.chunk_off, chunks, B, c.S, book, stream);
-    else if (e == hipSuccess) {
-        hipLaunchKernelGGL(credit_scenario_book_kernel, dim3(static_cast<unsigned>((c.S + kRedEntries - 1) / kRedEntries)),
-                           dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(c.S), book);
-        e = hipGetLastError();
-    }
+    else if (e == hipSuccess) e = enqueue_book_sum(work, chunks, c.S, book, stream);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
 }
@@ -535,32 +400,27 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curve
                  const Extra& x, double* pv, double* book, int64_t B = 0, const int64_t* sub_off = nullptr) {
     const int64_t n = adr_trades_count(trades);
     int rc = validate(w, c, trades ? n : 1, x, book);
-    if (rc == ADR_OK && curves_on_host) rc = check_curves(w, c);
+    if (rc == ADR_OK && curves_on_host) rc = check_curves(w, c.K, c.times, c.S_disc, c.dfs, "row");
     if (rc != ADR_OK) return rc;
     if (!trades) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
     rc = check_spreads(w, c, n, x);
     if (rc != ADR_OK) return rc;
     std::vector<int64_t> plan;
     if (B > 0) {
-        rc = sub::check_offsets(w, n, B, sub_off);
+        rc = sub::build_plan(w, n, B, sub_off, plan);
         if (rc != ADR_OK) return rc;
-        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, B, sub_off, nullptr)));
-        adr_scenario_subbook_plan(n, B, sub_off, plan.data());
     }
     const size_t rows = B > 0 ? static_cast<size_t>(B) : 1;
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     const size_t d = sizeof(double), K = c.K, SK = static_cast<size_t>(c.S_disc) * K, SG = static_cast<size_t>(c.S_spr) * c.G;
     const size_t W = static_cast<size_t>(B > 0 ? adr_scenario_subbook_work(n, B, c.S) : adr_credit_scenario_pv_work(n, c.S));
     const size_t NS = static_cast<size_t>(n) * c.S;
     const size_t nf = static_cast<size_t>(x.n_fix), nl = static_cast<size_t>(x.n_flt);
     const size_t n_dbl = (curves_on_host ? K + SK : 0) + SG + n + nf + nl + (pv ? NS : 0) + rows * c.S + W + plan.size();
     char* base = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + static_cast<size_t>(n) * sizeof(int32_t));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + static_cast<size_t>(n) * sizeof(int32_t));
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
     double* p = reinterpret_cast<double*>(base);
     auto take = [&p](size_t count) { double* q = p; p += count; return q; };
@@ -591,28 +451,11 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curve
     if (e == hipSuccess) rc = enqueue(w, ctx, dc, trades, dx, dpv, dbook, dwork, stream, B, dplan);
     if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, rows * c.S * d, hipMemcpyDeviceToHost, stream);
-    const hipError_t es = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = es;
-    const hipError_t ef = hipFree(base);
-    if (rc != ADR_OK) return rc;
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return ADR_OK;
+    return finish_blocking(w, rc, e, stream, base);
 }
 
-struct HostTab {
-    const double* p;     // the scenario's row of the converted table
-    double operator()(int k) const { return p[k]; }
-};
-
-struct HostTrades {      // the per-trade arrays of the host entry
-    int64_t n;
-    const int64_t *fix_off, *flt_off;
-    const double *notional, *spread, *fix_sign, *flt_sign;
-};
-
 template <bool kLog>
-void host_chunks(const Curves& c, const double* tab, const HostTrades& t, const Legs& arrays, const Extra& x, double* pv,
+void host_chunks(const Curves& c, const double* tab, const HostBatch& t, const Legs& arrays, const Extra& x, double* pv,
                  double* work, int64_t lo, int64_t hi, const int64_t* bounds = nullptr) {
     const int S = c.S, K = c.K;
     const size_t ds = c.S_disc == 1 ? 0 : K, zs = c.S_spr == 1 ? 0 : c.G;
@@ -621,8 +464,8 @@ void host_chunks(const Curves& c, const double* tab, const HostTrades& t, const 
     const bool weighted = arrays.flt_weight != nullptr;
     for (int64_t ch = lo; ch < hi; ++ch) {
         std::fill(book.begin(), book.end(), 0.0);
-        const int64_t i0 = bounds ? bounds[2 * ch] : ch * kChunk, i1 = bounds ? bounds[2 * ch + 1] : std::min(t.n, (ch + 1) * kChunk);
-        for (int64_t i = i0; i < i1; ++i) {
+        const ChunkRange r = host_chunk_range(ch, bounds, t.n);
+        for (int64_t i = r.i0; i < r.i1; ++i) {
             Legs g = arrays;
             g.f0 = t.fix_off[i]; g.l0 = t.flt_off[i];
             g.n_fix = static_cast<int>(t.fix_off[i + 1] - t.fix_off[i]);
@@ -659,10 +502,7 @@ namespace CS = adr::cscen;
 
 extern "C" {
 
-int64_t adr_credit_scenario_pv_work(int64_t n, int S) {
-    if (n < 1 || S < 1) return 0;
-    return (n + CS::kChunk - 1) / CS::kChunk * S;
-}
+int64_t adr_credit_scenario_pv_work(int64_t n, int S) { return adr_scenario_pv_work(n, S); }     // the same chunks
 
 int adr_credit_scenario_pv_dev(adr_ctx* ctx, int interp_method, int K, const double* times_dev, int S_disc, const double* dfs_dev,
                                int G, int S_spr, const double* dz_dev, int S, const adr_trades* trades, const double* z_dev,
@@ -685,73 +525,46 @@ int adr_credit_scenario_pv(adr_ctx* ctx, int interp_method, int K, const double*
 int adr_credit_scenario_pv_set(adr_ctx* ctx, const adr_curve_set* set, int G, int S_spr, const double* dz,
                                const adr_trades* trades, const double* z, const int32_t* bucket, int64_t n_fix,
                                const double* fix_tau, int64_t n_flt, const double* flt_tau, double* pv, double* book_pv) {
-    const adr_ctx* owner = nullptr;
-    int method = 0, K = 0, S = 0;
-    const double *t = nullptr, *d = nullptr;
-    const int rc = adr_curve_set_device_view(set, &owner, &method, &K, &S, &t, &d);      // adr_curve_set_arrays' arrays
+    const std::string w = "adr_credit_scenario_pv_set";
+    CS::SetCurves v;                                        // adr_curve_set_arrays' arrays
+    const int rc = CS::curve_set_curves(w, ctx, set, &v);
     if (rc != ADR_OK) return rc;
-    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, "adr_credit_scenario_pv_set: the curve set belongs to another ctx");
-    const CS::Curves c{method, K, t, S, d, G, S_spr, dz, S};
+    const CS::Curves c{v.method, v.K, v.times, v.S, v.dfs, G, S_spr, dz, v.S};
     const CS::Extra x{z, bucket, n_fix, fix_tau, n_flt, flt_tau};
-    return CS::run_blocking("adr_credit_scenario_pv_set", ctx, c, false, trades, x, pv, book_pv);
+    return CS::run_blocking(w, ctx, c, false, trades, x, pv, book_pv);
 }
 
 // The host entries' body; B > 0: book_pv is sub_pv[B][S] of the sub-books sub_off.
-static int credit_host_run(const std::string& w, int interp_method, int K, const double* times, int S_disc, const double* dfs, int G,
-                           int S_spr, const double* dz, int S, int64_t n, const int64_t* fix_off, const int64_t* flt_off,
-                           const double* fix_tp, const double* fix_pay, const double* flt_tp, const double* flt_ts,
-                           const double* flt_te, const double* flt_alpha, const double* flt_weight, const double* notional,
-                           const double* spread, const double* fix_sign, const double* flt_sign, const double* z,
-                           const int32_t* bucket, const double* fix_tau, const double* flt_tau, double* pv, double* book_pv,
-                           int n_threads, int64_t B, const int64_t* sub_off) {
-    if (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign)
+static int credit_host_run(const std::string& w, const CS::Curves& c, const CS::HostBatch& t, const double* z, const int32_t* bucket,
+                           const double* fix_tau, const double* flt_tau, double* pv, double* book_pv, int n_threads, int64_t B,
+                           const int64_t* sub_off) {
+    const int64_t n = t.n;
+    if (!t.fix_off || !t.flt_off || !t.notional || !t.spread || !t.fix_sign || !t.flt_sign)
         return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
     if (n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
-    if (fix_off[0] != 0 || flt_off[0] != 0) return adr_set_error(ADR_ERR_INVALID, w + ": offsets must start at 0");
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t mf = fix_off[i + 1] - fix_off[i], ml = flt_off[i + 1] - flt_off[i];
-        if (mf < 0 || ml < 0 || mf > INT16_MAX || ml > INT16_MAX)
-            return adr_set_error(ADR_ERR_INVALID, w + ": offsets must be non-decreasing, <= 32767 flows per leg");
-    }
-    const int64_t n_fix = fix_off[n], n_flt = flt_off[n];
-    const CS::Curves c{interp_method, K, times, S_disc, dfs, G, S_spr, dz, S};
-    const CS::Extra x{z, bucket, n_fix, fix_tau, n_flt, flt_tau};
-    int rc = CS::validate(w, c, n, x, book_pv);
-    if (rc == ADR_OK) rc = CS::check_curves(w, c);
-    if (rc == ADR_OK) rc = CS::check_spreads(w, c, n, x);
+    int rc = CS::check_leg_offsets(w, t, 0, n);
     if (rc != ADR_OK) return rc;
-    for (int64_t i = 0; i < n; ++i) {
-        if (!std::isfinite(notional[i]) || !std::isfinite(spread[i]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": notionals and spreads must be finite");
-        if (!(fix_sign[i] == 1.0 || fix_sign[i] == -1.0) || !(flt_sign[i] == 1.0 || flt_sign[i] == -1.0))
-            return adr_set_error(ADR_ERR_INVALID, w + ": leg signs must be +1 or -1");
-    }
-    if ((n_fix > 0 && (!fix_tp || !fix_pay)) || (n_flt > 0 && (!flt_tp || !flt_ts || !flt_te || !flt_alpha)))
-        return adr_set_error(ADR_ERR_INVALID, w + ": null cash-flow array");
-    auto finite = [](const double* a, int64_t m) {
-        bool ok = true;
-        for (int64_t i = 0; i < m; ++i) ok &= std::isfinite(a[i]);
-        return ok;
-    };
-    if (!finite(fix_tp, n_fix) || !finite(fix_pay, n_fix) || !finite(flt_tp, n_flt) || !finite(flt_ts, n_flt) ||
-        !finite(flt_te, n_flt) || !finite(flt_alpha, n_flt) || (flt_weight && !finite(flt_weight, n_flt)))
-        return adr_set_error(ADR_ERR_INVALID, w + ": times, amounts, accruals and weights must be finite");
-    const bool lin = interp_method == ADR_INTERP_LINEAR_FWD_RATES;
-    std::vector<double> tab(dfs, dfs + static_cast<size_t>(S_disc) * K);
+    const CS::Extra x{z, bucket, t.fix_off[n], fix_tau, t.flt_off[n], flt_tau};
+    rc = CS::validate(w, c, n, x, book_pv);
+    if (rc == ADR_OK) rc = CS::check_curves(w, c.K, c.times, c.S_disc, c.dfs, "row");
+    if (rc == ADR_OK) rc = CS::check_spreads(w, c, n, x);
+    if (rc == ADR_OK) rc = CS::check_trade_values(w, t, 0, n);
+    if (rc == ADR_OK) rc = CS::check_flows(w, t);
+    if (rc != ADR_OK) return rc;
+    const int S = c.S;
+    const bool lin = c.method == ADR_INTERP_LINEAR_FWD_RATES;
+    std::vector<double> tab(c.dfs, c.dfs + static_cast<size_t>(c.S_disc) * c.K);
     if (!lin)
         for (double& v : tab) v = std::log(v);
     std::vector<int64_t> plan;
     if (B > 0) {
-        rc = adr::sub::check_offsets(w, n, B, sub_off);
+        rc = adr::sub::build_plan(w, n, B, sub_off, plan);
         if (rc != ADR_OK) return rc;
-        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, B, sub_off, nullptr)));
-        adr_scenario_subbook_plan(n, B, sub_off, plan.data());
     }
     const int64_t* bounds = B > 0 ? plan.data() + B + 1 : nullptr;
     const int64_t chunks = B > 0 ? plan[B] : (n + CS::kChunk - 1) / CS::kChunk;
     std::vector<double> work(static_cast<size_t>(chunks) * S);
-    const CS::Legs arrays{fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, fix_tau, flt_tau, 0, 0, 0, 0, 0.0};
-    const CS::HostTrades t{n, fix_off, flt_off, notional, spread, fix_sign, flt_sign};
+    const CS::Legs arrays{t.fix_tp, t.fix_pay, t.flt_tp, t.flt_ts, t.flt_te, t.flt_alpha, t.flt_weight, fix_tau, flt_tau, 0, 0, 0, 0, 0.0};
     const int threads = n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4);
     adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
         if (lin) CS::host_chunks<false>(c, tab.data(), t, arrays, x, pv, work.data(), lo, hi, bounds);
@@ -769,9 +582,10 @@ int adr_credit_scenario_pv_host(int interp_method, int K, const double* times, i
                                 const double* spread, const double* fix_sign, const double* flt_sign, const double* z,
                                 const int32_t* bucket, const double* fix_tau, const double* flt_tau, double* pv, double* book_pv,
                                 int n_threads) {
-    return credit_host_run("adr_credit_scenario_pv_host", interp_method, K, times, S_disc, dfs, G, S_spr, dz, S, n, fix_off, flt_off,
-                           fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, z,
-                           bucket, fix_tau, flt_tau, pv, book_pv, n_threads, 0, nullptr);
+    const CS::Curves c{interp_method, K, times, S_disc, dfs, G, S_spr, dz, S};
+    const CS::HostBatch t{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread,
+                          fix_sign, flt_sign};
+    return credit_host_run("adr_credit_scenario_pv_host", c, t, z, bucket, fix_tau, flt_tau, pv, book_pv, n_threads, 0, nullptr);
 }
 
 int adr_credit_scenario_subbook_pv_host(int interp_method, int K, const double* times, int S_disc, const double* dfs, int G,
@@ -784,9 +598,10 @@ int adr_credit_scenario_subbook_pv_host(int interp_method, int K, const double* 
                                         double* pv, double* sub_pv, int n_threads) {
     const std::string w = "adr_credit_scenario_subbook_pv_host";
     if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
-    return credit_host_run(w, interp_method, K, times, S_disc, dfs, G, S_spr, dz, S, n, fix_off, flt_off, fix_tp, fix_pay, flt_tp,
-                           flt_ts, flt_te, flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, z, bucket, fix_tau, flt_tau,
-                           pv, sub_pv, n_threads, B, sub_off);
+    const CS::Curves c{interp_method, K, times, S_disc, dfs, G, S_spr, dz, S};
+    const CS::HostBatch t{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread,
+                          fix_sign, flt_sign};
+    return credit_host_run(w, c, t, z, bucket, fix_tau, flt_tau, pv, sub_pv, n_threads, B, sub_off);
 }
 
 int adr_credit_scenario_subbook_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S_disc, const double* dfs,
@@ -806,13 +621,10 @@ int adr_credit_scenario_subbook_pv_set(adr_ctx* ctx, const adr_curve_set* set, i
                                        const int64_t* sub_off, double* pv, double* sub_pv) {
     const std::string w = "adr_credit_scenario_subbook_pv_set";
     if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
-    const adr_ctx* owner = nullptr;
-    int method = 0, K = 0, S = 0;
-    const double *t = nullptr, *d = nullptr;
-    const int rc = adr_curve_set_device_view(set, &owner, &method, &K, &S, &t, &d);
+    CS::SetCurves v;
+    const int rc = CS::curve_set_curves(w, ctx, set, &v);
     if (rc != ADR_OK) return rc;
-    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, w + ": the curve set belongs to another ctx");
-    const CS::Curves c{method, K, t, S, d, G, S_spr, dz, S};
+    const CS::Curves c{v.method, v.K, v.times, v.S, v.dfs, G, S_spr, dz, v.S};
     const CS::Extra x{z, bucket, n_fix, fix_tau, n_flt, flt_tau};
     return CS::run_blocking(w, ctx, c, false, trades, x, pv, sub_pv, B, sub_off);
 }

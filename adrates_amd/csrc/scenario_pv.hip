@@ -5,10 +5,9 @@
 // fix_sign * pay * D_s(tp) and the float coupons flt_sign * N * w * ((D_s(ts) / D_s(te) - 1) + spread * alpha) * D_s(tp),
 // D_s(t) being InterpolatorAd.simple_interpolate (simple_interp.hpp).  No rates and no Jacobians are involved.
 //
-// Layout: one lane = one scenario, one wave = 64 scenarios (a "group"); a block is kWaves waves of ONE group that share
-// the group's knot table in LDS as tab[k][lane] (ln d under the log-linear schemes, d under LINEAR_FWD_RATES), so a lane
-// reads consecutive doubles and a knot costs one conflict-free ds_read_b64.  The trades are cut into chunks of
-// ADR_SCENARIO_CHUNK consecutive trades; a wave takes chunks round-robin and walks each in trade order.
+// Layout, lookup form, lane broadcast and book sum: scenario_common.hpp.  The group's table tab[k][lane] holds ln d under
+// the log-linear schemes and d under LINEAR_FWD_RATES; a lane reads consecutive doubles, so a knot costs one
+// conflict-free ds_read_b64.
 //
 // Everything about a date that does not depend on the scenario is computed once per wave.  The knot search is not
 // done by a scalar loop per date (nine dependent LDS reads each) but lane-parallel: lane l describes coupon l of the
@@ -20,9 +19,7 @@
 // wa * L[a] + wb * L[b] per DISTINCT date under the log schemes, none under LINEAR_FWD_RATES.  An OIS with m annual
 // coupons on both legs costs m + 1 exponentials per scenario instead of 3 m.
 //
-// The book sum: a lane adds its chunk's trades in trade order in a register and writes work[chunk][s]; a second kernel
-// adds the chunks in a fixed order (chunk j to slot j % 64 in order, then a halving tree).  No atomics.  The host twin
-// (adr_scenario_pv_host) runs the same per-date and per-coupon code in the same order on CPU threads.
+// The host twin (adr_scenario_pv_host) runs the same per-date and per-coupon code in the same order on CPU threads.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,64 +30,13 @@
 
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
-#include "kernels.hpp"
-#include "simple_interp.hpp"
+#include "scenario_common.hpp"
 #include "subbook.hpp"
 
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
-int adr_ctx_compute_units(const adr_ctx* ctx);                                  // capi.hip
-const adr::TradesDev* adr_trades_device_view(const adr_trades* trades, const adr_ctx** owner);              // capi.hip
-int adr_curve_set_device_view(const adr_curve_set* set, const adr_ctx** owner, int* method, int* K, int* S,
-                              const double** times_dev, const double** dfs_dev);                            // capi.hip
-
-// The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
-// exp / log implementations.
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
 
 namespace adr {
 namespace scen {
-
-constexpr int kWave = 64;
-constexpr int kWaves = 16;                      // waves per block: four per SIMD, all on one scenario group
-constexpr int kThreads = kWave * kWaves;
-constexpr int kChunk = ADR_SCENARIO_CHUNK;      // trades per partial sum of the book
-constexpr int kRedLanes = 64;                   // the book reduction's slots per scenario
-constexpr int kRedEntries = 16;                 // scenarios per reduction block
-constexpr size_t kLdsBudget = 160 * 1024;
-
-// D(t) in weight form on the scenario's table T (T_k = ln d_k when kLog, else d_k):
-//   kLog:  ln D = wa T_a + (b != a ? wb T_b : 0);      else:  D = T_a + (b != a ? wb (T_b - T_a) : 0).
-struct DateW {
-    int a, b;
-    double wa, wb;
-};
-
-template <bool kLog>
-__host__ __device__ inline DateW date_weights(double t, const double* x, int K, int method) {
-    DateW d;
-    if (kLog) {
-        const si::LogWeights w = si::log_weights(t, x, K, method);
-        d.a = w.a; d.b = w.b; d.wa = w.wa; d.wb = w.wb;
-    } else {
-        const si::Where p = si::locate(t, x, K);
-        d.a = p.lo; d.b = p.hi; d.wa = 1.0; d.wb = p.w;
-    }
-    return d;
-}
-
-template <bool kLog, class Tab>
-__host__ __device__ inline double eval_df(const DateW& d, const Tab& tab) {
-    const double la = tab(d.a);
-    if (kLog) {
-        double s = d.wa * la;
-        if (d.b != d.a) s = s + d.wb * tab(d.b);
-        return exp(s);
-    }
-    double f = la;
-    if (d.b != d.a) f = la + d.wb * (tab(d.b) - la);
-    return f;
-}
 
 // Coupon index c of a trade: its float coupon (c < n_flt) and its fixed flow (c < n_fix).  The masks are adr_price's
 // (the reference engine's): a float coupon counts when tp >= 0 and has no forward when alpha <= 0, a fixed flow counts
@@ -192,20 +138,6 @@ __host__ __device__ inline double trade_pv(const Acc& a, double fix_sign, double
     return fix_sign * a.fix + (flt_sign * notional) * a.flt;
 }
 
-// book[s] = sum over the chunk rows of entry s: chunk j to slot j % 64 in order, then slots 0-31 += 32-63, ..., 0 += 1.
-void reduce_chunks(const double* work, int64_t chunks, int64_t S, double* book) {
-    for (int64_t e = 0; e < S; ++e) {
-        double p[kRedLanes];
-        for (int cl = 0; cl < kRedLanes; ++cl) {
-            p[cl] = 0.0;
-            for (int64_t j = cl; j < chunks; j += kRedLanes) p[cl] = p[cl] + work[j * S + e];
-        }
-        for (int h = kRedLanes / 2; h >= 1; h >>= 1)
-            for (int cl = 0; cl < h; ++cl) p[cl] = p[cl] + p[cl + h];
-        book[e] = p[0];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------ device
 struct Args {
     TradesDev tr;
@@ -215,19 +147,6 @@ struct Args {
     double *pv, *work;               // [n][S] or null; [n_chunks][S]
     const int64_t *sub_chunks, *sub_bounds;      // kSub: the plan's chunk count and its [chunks][2] trade bounds (subbook.hpp)
 };
-
-__device__ inline int lane_int(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-__device__ inline double lane_dbl(double v, int j) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
-}
-__device__ inline DateW lane_date(const DateW& d, int j) {
-    DateW r;
-    r.a = lane_int(d.a, j);
-    r.b = lane_int(d.b, j);
-    r.wa = lane_dbl(d.wa, j);
-    r.wb = r.b != r.a ? lane_dbl(d.wb, j) : 0.0;
-    return r;
-}
 
 // Lane j's slot in scalar registers; only the parts its flags say will be read.
 __device__ inline Slot lane_slot(const Slot& m, int j, bool weighted) {
@@ -250,16 +169,6 @@ __device__ inline Slot lane_slot(const Slot& m, int j, bool weighted) {
     }
     return u;
 }
-
-// kLds: the group's table sits in LDS; otherwise (K too large) every lane reads its scenario's row of dfs.
-template <bool kLog, bool kLds>
-struct DevTab {
-    const double* p;     // kLds: &tab[0][lane]; else &dfs[s][0]
-    __device__ double operator()(int k) const {
-        if (kLds) return p[k * kWave];
-        return kLog ? log(p[k]) : p[k];
-    }
-};
 
 // kSub: the chunks are those of a sub-book plan (their trade bounds come from a table) instead of ch * kChunk.
 template <bool kLog, bool kLds, bool kSub>
@@ -286,15 +195,9 @@ __global__ __launch_bounds__(kThreads) void scenario_pv_kernel(Args a) {
     }
     for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < n_chunks;
          ch += static_cast<int64_t>(gridDim.x) * kWaves) {
-        int64_t i0 = ch * kChunk, i1 = ch * kChunk + kChunk;
-        if (kSub) {
-            i0 = a.sub_bounds[2 * ch];                      // uniform: scalar loads
-            i1 = a.sub_bounds[2 * ch + 1];
-            i0 = i0 < 0 ? 0 : i0;
-        }
-        i1 = i1 < a.tr.n ? i1 : a.tr.n;
+        const ChunkRange r = chunk_range<kSub>(ch, a.sub_bounds, a.tr.n);
         double book = 0.0;
-        for (int64_t i = i0; i < i1; ++i) {
+        for (int64_t i = r.i0; i < r.i1; ++i) {
             const TradeHeader h = a.tr.header[i];           // uniform: scalar loads
             const Legs g{a.tr.fix_tp, a.tr.fix_pay, a.tr.flt_tp, a.tr.flt_ts, a.tr.flt_te, a.tr.flt_alpha, a.tr.flt_weight,
                          h.fix_begin, h.flt_begin, h.n_fix, h.n_flt, h.spread};
@@ -317,35 +220,12 @@ __global__ __launch_bounds__(kThreads) void scenario_pv_kernel(Args a) {
     }
 }
 
-// book[e] = the fixed-order sum of the chunk rows (reduce_chunks above is its host form).
-__global__ __launch_bounds__(kRedLanes * kRedEntries) void scenario_book_kernel(const double* work, int64_t chunks, int64_t S,
-                                                                                double* book) {
-    __shared__ double sh[kRedLanes][kRedEntries];
-    const int ei = threadIdx.x % kRedEntries, cl = threadIdx.x / kRedEntries;
-    const int64_t e = static_cast<int64_t>(blockIdx.x) * kRedEntries + ei;
-    double acc = 0.0;
-    if (e < S) {
-#pragma unroll 8
-        for (int64_t j = cl; j < chunks; j += kRedLanes) acc = acc + work[j * S + e];
-    }
-    sh[cl][ei] = acc;
-    __syncthreads();
-    for (int h = kRedLanes / 2; h >= 1; h >>= 1) {
-        if (cl < h) sh[cl][ei] = sh[cl][ei] + sh[cl + h][ei];
-        __syncthreads();
-    }
-    if (cl == 0 && e < S) book[e] = sh[0][ei];
-}
-
 // -------------------------------------------------------------------------------------------------------------- host
 inline size_t lds_bytes(int K, bool table) { return (static_cast<size_t>(K) + (table ? static_cast<size_t>(K) * kWave : 0)) * sizeof(double); }
 
 int validate(const std::string& w, int method, int K, int S, int64_t n, const void* times, const void* dfs, const void* book) {
-    if (method != ADR_INTERP_FLAT_FWD_RATES && method != ADR_INTERP_LINEAR_FWD_RATES && method != ADR_INTERP_LINEAR_ZERO_RATES)
-        return adr_set_error(ADR_ERR_INVALID, w + ": the scheme must be FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) or "
-                                                  "LINEAR_ZERO_RATES (4)");
-    if (K < 2 || K > ADR_SCENARIO_MAX_KNOTS)
-        return adr_set_error(ADR_ERR_INVALID, w + ": the knot grid needs 2 .. ADR_SCENARIO_MAX_KNOTS (4096) knots");
+    const int rc = check_scheme_knots(w, method, K);
+    if (rc != ADR_OK) return rc;
     if (S < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one scenario is needed");
     if (n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
     if (!times || !dfs) return adr_set_error(ADR_ERR_INVALID, w + ": null curve arrays");
@@ -353,30 +233,11 @@ int validate(const std::string& w, int method, int K, int S, int64_t n, const vo
     return ADR_OK;
 }
 
-int check_curves(const std::string& w, int K, const double* times, int S, const double* dfs) {
-    for (int k = 0; k < K; ++k)
-        if (!std::isfinite(times[k]) || (k > 0 && times[k] < times[k - 1]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": knot times must be finite and non-decreasing");
-    for (int64_t i = 0; i < static_cast<int64_t>(S) * K; ++i)
-        if (!(dfs[i] > 0.0) || !std::isfinite(dfs[i]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": discount factors must be positive and finite (scenario " +
-                                                      std::to_string(i / K) + ", knot " + std::to_string(i % K) + ")");
-    return ADR_OK;
-}
-
-template <bool kLog, bool kLds, bool kSub>
-hipError_t launch_as(const Args& a, dim3 grid, hipStream_t stream) {
-    const size_t lds = lds_bytes(a.K, kLds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scenario_pv_kernel<kLog, kLds, kSub>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((scenario_pv_kernel<kLog, kLds, kSub>), grid, dim3(kThreads), lds, stream, a);
-    return hipGetLastError();
-}
-
 template <bool kLog, bool kLds>
 hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
-    return a.sub_bounds ? launch_as<kLog, kLds, true>(a, grid, stream) : launch_as<kLog, kLds, false>(a, grid, stream);
+    const size_t lds = lds_bytes(a.K, kLds);
+    if (a.sub_bounds) return launch_with_lds(&scenario_pv_kernel<kLog, kLds, true>, a, lds, grid, stream);
+    return launch_with_lds(&scenario_pv_kernel<kLog, kLds, false>, a, lds, grid, stream);
 }
 
 // The two kernels on `stream`; every pointer is device memory.  B > 0: the chunks of the sub-book plan `plan`, and
@@ -394,32 +255,22 @@ int enqueue(const std::string& w, adr_ctx* ctx, int method, int K, const double*
     const bool subs = B != 0 || plan;
     if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
     if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
-    if (stream_or_null) stream = stream_or_null;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     const int64_t chunks = subs ? sub::max_chunks(tr->n, B, kChunk) : (tr->n + kChunk - 1) / kChunk;
-    const int64_t groups = (static_cast<int64_t>(S) + kWave - 1) / kWave;
-    if (groups > 65535) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 65535 * 64 scenarios in one launch");
-    // one block per compute unit when the table fills the LDS; a group's blocks share its chunks round-robin
-    const int64_t per_group = std::max<int64_t>(1, (adr_ctx_compute_units(ctx) + groups - 1) / groups);
-    const int64_t bx = std::min<int64_t>((chunks + kWaves - 1) / kWaves, per_group);
-    const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(groups));
+    dim3 grid;
+    rc = launch_grid(w, ctx, chunks, S, &grid);
+    if (rc != ADR_OK) return rc;
     const sub::Plan pl = subs ? sub::plan_view(plan, B) : sub::Plan{nullptr, nullptr};
     const Args a{*tr, times, dfs, K, S, method, chunks, pv, work, subs ? pl.chunk_off + B : nullptr, pl.bounds};
     const bool in_lds = lds_bytes(K, true) <= kLdsBudget;
     const bool lin = method == ADR_INTERP_LINEAR_FWD_RATES;
+    hipError_t e;
     if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
     else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
     if (e == hipSuccess && subs) e = sub::enqueue_sum(work, pl.chunk_off, chunks, B, S, book, stream);
-    else if (e == hipSuccess) {
-        hipLaunchKernelGGL(scenario_book_kernel, dim3(static_cast<unsigned>((S + kRedEntries - 1) / kRedEntries)),
-                           dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(S), book);
-        e = hipGetLastError();
-    }
+    else if (e == hipSuccess) e = enqueue_book_sum(work, chunks, S, book, stream);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
 }
@@ -440,31 +291,26 @@ int run_blocking(const std::string& w, adr_ctx* ctx, int method, int K, const do
     const int64_t n = adr_trades_count(trades);
     const bool tail = sub && sub->k > 0;
     int rc = validate(w, method, K, S, trades ? n : 1, times, dfs, tail ? static_cast<const void*>(sub->var) : book);
-    if (rc == ADR_OK && curves_on_host) rc = check_curves(w, K, times, S, dfs);
+    if (rc == ADR_OK && curves_on_host) rc = check_curves(w, K, times, S, dfs, "scenario");
     if (rc != ADR_OK) return rc;
     if (!trades) return adr_set_error(ADR_ERR_INVALID, w + ": null trades");
     std::vector<int64_t> plan;
     if (sub) {
-        rc = sub::check_offsets(w, n, sub->B, sub->sub_off);
+        rc = sub::build_plan(w, n, sub->B, sub->sub_off, plan);
         if (rc == ADR_OK && tail) rc = sub::check_tail(w, sub->B, S, sub->base_col, sub->k);
         if (rc == ADR_OK && tail && !sub->es) rc = adr_set_error(ADR_ERR_INVALID, w + ": es is NULL");
         if (rc != ADR_OK) return rc;
-        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, sub->B, sub->sub_off, nullptr)));
-        adr_scenario_subbook_plan(n, sub->B, sub->sub_off, plan.data());
     }
     const size_t B = sub ? static_cast<size_t>(sub->B) : 0, rows = sub ? B : 1;
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     const size_t d = sizeof(double), SK = static_cast<size_t>(S) * K;
     const size_t W = static_cast<size_t>(sub ? adr_scenario_subbook_work(n, sub->B, S) : adr_scenario_pv_work(n, S));
     const size_t n_dbl = (curves_on_host ? K + SK : 0) + (pv ? static_cast<size_t>(n) * S : 0) + rows * S + W + plan.size() +
                          (tail ? 2 * B : 0);
     double* base = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
     double* p = base;
     auto take = [&p](size_t count) { double* q = p; p += count; return q; };
@@ -490,44 +336,31 @@ int run_blocking(const std::string& w, adr_ctx* ctx, int method, int K, const do
         if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(sub->var, dvar, B * d, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(sub->es, des, B * d, hipMemcpyDeviceToHost, stream);
     } else if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, rows * S * d, hipMemcpyDeviceToHost, stream);
-    const hipError_t es = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = es;
-    const hipError_t ef = hipFree(base);
-    if (rc != ADR_OK) return rc;
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return ADR_OK;
+    return finish_blocking(w, rc, e, stream, base);
 }
 
-struct HostTab {
-    const double* p;     // the scenario's row of the converted table
-    double operator()(int k) const { return p[k]; }
-};
-
 template <bool kLog>
-void host_chunks(int method, int K, const double* times, int S, const double* tab, int64_t n, const int64_t* fix_off,
-                 const int64_t* flt_off, const Legs& arrays, const double* notional, const double* spread,
-                 const double* fix_sign, const double* flt_sign, double* pv, double* work, int64_t lo, int64_t hi,
-                 const int64_t* bounds = nullptr) {
+void host_chunks(int method, int K, const double* times, int S, const double* tab, const HostBatch& t, const Legs& arrays,
+                 double* pv, double* work, int64_t lo, int64_t hi, const int64_t* bounds = nullptr) {
     std::vector<Acc> acc(static_cast<size_t>(S));
     std::vector<double> book(static_cast<size_t>(S));
     const bool weighted = arrays.flt_weight != nullptr;
     for (int64_t ch = lo; ch < hi; ++ch) {
         std::fill(book.begin(), book.end(), 0.0);
-        const int64_t i0 = bounds ? bounds[2 * ch] : ch * kChunk, i1 = bounds ? bounds[2 * ch + 1] : std::min(n, (ch + 1) * kChunk);
-        for (int64_t i = i0; i < i1; ++i) {
+        const ChunkRange r = host_chunk_range(ch, bounds, t.n);
+        for (int64_t i = r.i0; i < r.i1; ++i) {
             Legs g = arrays;
-            g.f0 = fix_off[i]; g.l0 = flt_off[i];
-            g.n_fix = static_cast<int>(fix_off[i + 1] - fix_off[i]);
-            g.n_flt = static_cast<int>(flt_off[i + 1] - flt_off[i]);
-            g.spread = spread[i];
+            g.f0 = t.fix_off[i]; g.l0 = t.flt_off[i];
+            g.n_fix = static_cast<int>(t.fix_off[i + 1] - t.fix_off[i]);
+            g.n_flt = static_cast<int>(t.flt_off[i + 1] - t.flt_off[i]);
+            g.spread = t.spread[i];
             std::fill(acc.begin(), acc.end(), Acc{0.0, 0.0, 0.0});
             for (int c = 0; c < std::max(g.n_fix, g.n_flt); ++c) {
                 const Slot slot = make_slot<kLog>(g, c, times, K, method);
                 for (int s = 0; s < S; ++s) apply_slot<kLog>(slot, weighted, HostTab{tab + static_cast<size_t>(s) * K}, acc[s]);
             }
             for (int s = 0; s < S; ++s) {
-                const double v = trade_pv(acc[s], fix_sign[i], flt_sign[i], notional[i]);
+                const double v = trade_pv(acc[s], t.fix_sign[i], t.flt_sign[i], t.notional[i]);
                 if (pv) pv[i * S + s] = v;
                 book[s] = book[s] + v;
             }
@@ -575,70 +408,45 @@ int adr_curve_set_arrays(const adr_curve_set* set, int* interp_method, int* K, i
 }
 
 int adr_scenario_pv_set(adr_ctx* ctx, const adr_curve_set* set, const adr_trades* trades, double* pv, double* book_pv) {
-    const adr_ctx* owner = nullptr;
-    int method = 0, K = 0, S = 0;
-    const double *t = nullptr, *d = nullptr;
-    const int rc = adr_curve_set_device_view(set, &owner, &method, &K, &S, &t, &d);
+    const std::string w = "adr_scenario_pv_set";
+    SC::SetCurves c;
+    const int rc = SC::curve_set_curves(w, ctx, set, &c);
     if (rc != ADR_OK) return rc;
-    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, "adr_scenario_pv_set: the curve set belongs to another ctx");
-    return SC::run_blocking("adr_scenario_pv_set", ctx, method, K, t, S, d, false, trades, pv, book_pv);
+    return SC::run_blocking(w, ctx, c.method, c.K, c.times, c.S, c.dfs, false, trades, pv, book_pv);
 }
 
 // The host entries' body; B > 0: book_pv is sub_pv[B][S] of the sub-books sub_off.
-static int scenario_host_run(const std::string& w, int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
-                             const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
-                             const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
-                             const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
-                             const double* flt_sign, double* pv, double* book_pv, int n_threads, int64_t B, const int64_t* sub_off) {
+static int scenario_host_run(const std::string& w, int interp_method, int K, const double* times, int S, const double* dfs,
+                             const SC::HostBatch& t, double* pv, double* book_pv, int n_threads, int64_t B, const int64_t* sub_off) {
+    const int64_t n = t.n;
     int rc = SC::validate(w, interp_method, K, S, n, times, dfs, book_pv);
-    if (rc == ADR_OK) rc = SC::check_curves(w, K, times, S, dfs);
+    if (rc == ADR_OK) rc = SC::check_curves(w, K, times, S, dfs, "scenario");
     if (rc != ADR_OK) return rc;
-    if (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign)
+    if (!t.fix_off || !t.flt_off || !t.notional || !t.spread || !t.fix_sign || !t.flt_sign)
         return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
-    if (fix_off[0] != 0 || flt_off[0] != 0) return adr_set_error(ADR_ERR_INVALID, w + ": offsets must start at 0");
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t mf = fix_off[i + 1] - fix_off[i], ml = flt_off[i + 1] - flt_off[i];
-        if (mf < 0 || ml < 0 || mf > INT16_MAX || ml > INT16_MAX)
-            return adr_set_error(ADR_ERR_INVALID, w + ": offsets must be non-decreasing, <= 32767 flows per leg");
-        if (!std::isfinite(notional[i]) || !std::isfinite(spread[i]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": notionals and spreads must be finite");
-        if (!(fix_sign[i] == 1.0 || fix_sign[i] == -1.0) || !(flt_sign[i] == 1.0 || flt_sign[i] == -1.0))
-            return adr_set_error(ADR_ERR_INVALID, w + ": leg signs must be +1 or -1");
+    for (int64_t i = 0; rc == ADR_OK && i < n; ++i) {      // trade by trade: the first trade at fault decides the message
+        rc = SC::check_leg_offsets(w, t, i, i + 1);
+        if (rc == ADR_OK) rc = SC::check_trade_values(w, t, i, i + 1);
     }
-    const int64_t n_fix = fix_off[n], n_flt = flt_off[n];
-    if ((n_fix > 0 && (!fix_tp || !fix_pay)) || (n_flt > 0 && (!flt_tp || !flt_ts || !flt_te || !flt_alpha)))
-        return adr_set_error(ADR_ERR_INVALID, w + ": null cash-flow array");
-    auto finite = [](const double* a, int64_t m) {
-        bool ok = true;
-        for (int64_t i = 0; i < m; ++i) ok &= std::isfinite(a[i]);
-        return ok;
-    };
-    if (!finite(fix_tp, n_fix) || !finite(fix_pay, n_fix) || !finite(flt_tp, n_flt) || !finite(flt_ts, n_flt) ||
-        !finite(flt_te, n_flt) || !finite(flt_alpha, n_flt) || (flt_weight && !finite(flt_weight, n_flt)))
-        return adr_set_error(ADR_ERR_INVALID, w + ": times, amounts, accruals and weights must be finite");
+    if (rc == ADR_OK) rc = SC::check_flows(w, t);
+    if (rc != ADR_OK) return rc;
     const bool lin = interp_method == ADR_INTERP_LINEAR_FWD_RATES;
     std::vector<double> tab(dfs, dfs + static_cast<size_t>(S) * K);
     if (!lin)
         for (double& v : tab) v = std::log(v);
     std::vector<int64_t> plan;
     if (B > 0) {
-        rc = adr::sub::check_offsets(w, n, B, sub_off);
+        rc = adr::sub::build_plan(w, n, B, sub_off, plan);
         if (rc != ADR_OK) return rc;
-        plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, B, sub_off, nullptr)));
-        adr_scenario_subbook_plan(n, B, sub_off, plan.data());
     }
     const int64_t* bounds = B > 0 ? plan.data() + B + 1 : nullptr;
     const int64_t chunks = B > 0 ? plan[B] : (n + SC::kChunk - 1) / SC::kChunk;
     std::vector<double> work(static_cast<size_t>(chunks) * S);
-    const SC::Legs arrays{fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, 0, 0, 0, 0, 0.0};
+    const SC::Legs arrays{t.fix_tp, t.fix_pay, t.flt_tp, t.flt_ts, t.flt_te, t.flt_alpha, t.flt_weight, 0, 0, 0, 0, 0.0};
     const int threads = std::max(1, n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4));
     adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
-        if (lin)
-            SC::host_chunks<false>(interp_method, K, times, S, tab.data(), n, fix_off, flt_off, arrays, notional, spread, fix_sign,
-                                   flt_sign, pv, work.data(), lo, hi, bounds);
-        else
-            SC::host_chunks<true>(interp_method, K, times, S, tab.data(), n, fix_off, flt_off, arrays, notional, spread, fix_sign,
-                                  flt_sign, pv, work.data(), lo, hi, bounds);
+        if (lin) SC::host_chunks<false>(interp_method, K, times, S, tab.data(), t, arrays, pv, work.data(), lo, hi, bounds);
+        else SC::host_chunks<true>(interp_method, K, times, S, tab.data(), t, arrays, pv, work.data(), lo, hi, bounds);
     });
     if (B > 0) adr::sub::reduce_subbooks(work.data(), plan.data(), B, S, book_pv);
     else SC::reduce_chunks(work.data(), chunks, S, book_pv);
@@ -650,9 +458,9 @@ int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, c
                          const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
                          const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
                          const double* flt_sign, double* pv, double* book_pv, int n_threads) {
-    return scenario_host_run("adr_scenario_pv_host", interp_method, K, times, S, dfs, n, fix_off, flt_off, fix_tp, fix_pay, flt_tp,
-                             flt_ts, flt_te, flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, pv, book_pv, n_threads, 0,
-                             nullptr);
+    const SC::HostBatch t{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread,
+                          fix_sign, flt_sign};
+    return scenario_host_run("adr_scenario_pv_host", interp_method, K, times, S, dfs, t, pv, book_pv, n_threads, 0, nullptr);
 }
 
 int adr_scenario_subbook_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,
@@ -663,8 +471,9 @@ int adr_scenario_subbook_pv_host(int interp_method, int K, const double* times, 
                                  int n_threads) {
     const std::string w = "adr_scenario_subbook_pv_host";
     if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
-    return scenario_host_run(w, interp_method, K, times, S, dfs, n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te,
-                             flt_alpha, flt_weight, notional, spread, fix_sign, flt_sign, pv, sub_pv, n_threads, B, sub_off);
+    const SC::HostBatch t{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread,
+                          fix_sign, flt_sign};
+    return scenario_host_run(w, interp_method, K, times, S, dfs, t, pv, sub_pv, n_threads, B, sub_off);
 }
 
 int adr_scenario_subbook_pv(adr_ctx* ctx, int interp_method, int K, const double* times, int S, const double* dfs,
@@ -693,14 +502,12 @@ int adr_scenario_subbook_pv_dev(adr_ctx* ctx, int interp_method, int K, const do
 
 int adr_scenario_subbook_pv_set(adr_ctx* ctx, const adr_curve_set* set, const adr_trades* trades, int64_t B, const int64_t* sub_off,
                                 double* pv, double* sub_pv) {
-    const adr_ctx* owner = nullptr;
-    int method = 0, K = 0, S = 0;
-    const double *t = nullptr, *d = nullptr;
-    const int rc = adr_curve_set_device_view(set, &owner, &method, &K, &S, &t, &d);
+    const std::string w = "adr_scenario_subbook_pv_set";
+    SC::SetCurves c;
+    const int rc = SC::curve_set_curves(w, ctx, set, &c);
     if (rc != ADR_OK) return rc;
-    if (owner != ctx) return adr_set_error(ADR_ERR_INVALID, "adr_scenario_subbook_pv_set: the curve set belongs to another ctx");
     const SC::SubRequest sub{B, sub_off, -1, 0, nullptr, nullptr};
-    return SC::run_blocking("adr_scenario_subbook_pv_set", ctx, method, K, t, S, d, false, trades, pv, sub_pv, &sub);
+    return SC::run_blocking(w, ctx, c.method, c.K, c.times, c.S, c.dfs, false, trades, pv, sub_pv, &sub);
 }
 
 }  // extern "C"

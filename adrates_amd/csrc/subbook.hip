@@ -24,19 +24,61 @@
 
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
-
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
+#include "scenario_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace adr {
+namespace scen {
+
+// The whole book's sum, the parent of the sub-book sums below: book[e] = the fixed-order sum of the chunk rows
+// (scenario_common.hpp; reduce_chunks is its host form).
+__global__ __launch_bounds__(kRedLanes * kRedEntries) void scenario_book_kernel(const double* work, int64_t chunks, int64_t S,
+                                                                                double* book) {
+    __shared__ double sh[kRedLanes][kRedEntries];
+    const int ei = threadIdx.x % kRedEntries, cl = threadIdx.x / kRedEntries;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kRedEntries + ei;
+    double acc = 0.0;
+    if (e < S) {
+#pragma unroll 8
+        for (int64_t j = cl; j < chunks; j += kRedLanes) acc = acc + work[j * S + e];
+    }
+    sh[cl][ei] = acc;
+    __syncthreads();
+    for (int h = kRedLanes / 2; h >= 1; h >>= 1) {
+        if (cl < h) sh[cl][ei] = sh[cl][ei] + sh[cl + h][ei];
+        __syncthreads();
+    }
+    if (cl == 0 && e < S) book[e] = sh[0][ei];
+}
+
+hipError_t enqueue_book_sum(const double* work, int64_t chunks, int S, double* book, hipStream_t stream) {
+    hipLaunchKernelGGL(scenario_book_kernel, dim3(static_cast<unsigned>((S + kRedEntries - 1) / kRedEntries)),
+                       dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(S), book);
+    return hipGetLastError();
+}
+
+void reduce_chunks(const double* work, int64_t chunks, int64_t S, double* book) {
+    for (int64_t e = 0; e < S; ++e) {
+        double p[kRedLanes];
+        for (int cl = 0; cl < kRedLanes; ++cl) {
+            p[cl] = 0.0;
+            for (int64_t j = cl; j < chunks; j += kRedLanes) p[cl] = p[cl] + work[j * S + e];
+        }
+        for (int h = kRedLanes / 2; h >= 1; h >>= 1)
+            for (int cl = 0; cl < h; ++cl) p[cl] = p[cl] + p[cl + h];
+        book[e] = p[0];
+    }
+}
+
+}  // namespace scen
+
 namespace sub {
 
-constexpr int kWave = 64;
+using scen::kChunk;
+using scen::kWave;
 constexpr int kSlots = 64;                      // the parent's reduction slots
 constexpr int kSumWaves = 4;                    // (sub-book, group) pairs per block of the sum kernel
-constexpr int kChunk = ADR_SCENARIO_CHUNK;
 constexpr int kBigChunks = 64;                  // above (the slot index wraps): the block-per-pair kernel
 constexpr int kBigWaves = 16;                   // its waves, kSlots / kBigWaves slots each
 
@@ -52,6 +94,14 @@ int check_offsets(const std::string& w, int64_t n, int64_t B, const int64_t* sub
     if (sub_off[B] != n)
         return adr_set_error(ADR_ERR_INVALID, w + ": sub_off must end at the trade count " + std::to_string(n) + " (sub-book " +
                                                   std::to_string(B - 1) + " ends at " + std::to_string(sub_off[B]) + ")");
+    return ADR_OK;
+}
+
+int build_plan(const std::string& w, int64_t n, int64_t B, const int64_t* sub_off, std::vector<int64_t>& plan) {
+    const int rc = check_offsets(w, n, B, sub_off);
+    if (rc != ADR_OK) return rc;
+    plan.resize(static_cast<size_t>(adr_scenario_subbook_plan(n, B, sub_off, nullptr)));
+    adr_scenario_subbook_plan(n, B, sub_off, plan.data());
     return ADR_OK;
 }
 
@@ -307,27 +357,19 @@ int adr_scenario_tail(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, in
     int rc = SB::check_tail(w, B, S_tot, base_col, k);
     if (rc != ADR_OK) return rc;
     if (!rows || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot;
     double* base = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&base), (R + 2 * static_cast<size_t>(B)) * d);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (R + 2 * static_cast<size_t>(B)) * d);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
     double *dvar = base + R, *des = dvar + B;
     e = hipMemcpyAsync(base, rows, R * d, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = SB::enqueue_tail(base, B, S_tot, base_col, k, dvar, des, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(var, dvar, B * d, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(es, des, B * d, hipMemcpyDeviceToHost, stream);
-    const hipError_t es_ = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = es_;
-    const hipError_t ef = hipFree(base);
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return ADR_OK;
+    return adr::scen::finish_blocking(w, ADR_OK, e, stream, base);
 }
 
 int adr_scenario_tail_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es) {

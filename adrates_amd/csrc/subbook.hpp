@@ -1,10 +1,12 @@
 // Sub-books of a scenario revaluation (subbook.hip): the chunk plan, the fixed-order sum per sub-book and the tail
-// measures; shared by scenario_pv.hip and credit_scenario_pv.hip.
+// measures; shared by scenario_pv.hip and credit_scenario_pv.hip.  The whole book's sum, which subbook.hip holds too, is
+// declared in scenario_common.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace adr {
 namespace sub {
@@ -22,6 +24,9 @@ inline int64_t max_chunks(int64_t n, int64_t B, int chunk) { return (n + chunk -
 
 // ADR_ERR_INVALID naming the sub-book unless sub_off runs from 0 to n without decreasing.
 int check_offsets(const std::string& w, int64_t n, int64_t B, const int64_t* sub_off);
+
+// check_offsets, then `plan` resized and filled (adr_scenario_subbook_plan).
+int build_plan(const std::string& w, int64_t n, int64_t B, const int64_t* sub_off, std::vector<int64_t>& plan);
 
 // sub_pv[b][e] = the fixed-order sum of sub-book b's chunk rows: its chunk j to slot j % 64 in order, then a halving
 // tree.  Chunk counts beyond chunk_cap are cut there (work holds that many rows).

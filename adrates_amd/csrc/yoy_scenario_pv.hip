@@ -8,20 +8,17 @@
 // sum of at most two L_k = T_k ln(1 + b_k) (simple_interp.hpp::log_weights), so a YoY ratio is ONE exp of the
 // difference of two such sums.
 //
-// Layout (scenario_pv.hip's): one lane = one scenario, a block = kWaves waves of ONE group of 64 scenarios that share
-// the group's two tables in LDS - the discount table tab[k][lane] (ln d under the log-linear schemes, d under
-// LINEAR_FWD_RATES) and the inflation table itab[k][lane] = L_k - so a knot costs one conflict-free ds_read_b64.  Where
-// the two do not fit together the small inflation table stays in LDS and the lanes read their discount rows from global
-// memory.  The swaps are cut into chunks of ADR_SCENARIO_CHUNK; a wave takes chunks round-robin and walks each in swap
-// order.  Lane l describes index l of the swap - YoY coupon l and fixed flow l: their segment searches, knot indices
-// and weights - and marks what needs no evaluation of its own: a YoY start equal to the previous coupon's end (annual
-// legs tile: the weighted sum is the one just computed), ts == te (y = 0 exactly), a fixed flow paid with the coupon of
-// the same index (one D(tp) for both).  The wave then walks the indices in order, fetching index j's description from
-// lane j with v_readlane into scalar registers, and each lane evaluates on its own scenario's tables.
+// Layout, lookup form, lane broadcast and book sum: scenario_common.hpp, swaps for trades.  Beside the group's discount
+// table the block holds the group's inflation table itab[k][lane] = L_k.  Where the two do not fit together the small
+// inflation table stays in LDS and the lanes read their discount rows from global memory.  Lane l describes index l of
+// the swap - YoY coupon l and fixed flow l: their segment searches, knot indices and weights - and marks what needs no
+// evaluation of its own: a YoY start equal to the previous coupon's end (annual legs tile: the weighted sum is the one
+// just computed), ts == te (y = 0 exactly), a fixed flow paid with the coupon of the same index (one D(tp) for both).
+// The wave then walks the indices in order, fetching index j's description from lane j with v_readlane into scalar
+// registers, and each lane evaluates on its own scenario's tables.
 //
-// A shared curve (S_disc = 1 or S_infl = 1: "not shocked") is read with row stride 0.  The book sum is
-// scenario_pv.hip's: chunk sums in swap order, chunk j to slot j % 64 in order, a halving tree; no atomics.  The host
-// twin (adr_yoy_scenario_pv_host) runs the same per-date and per-coupon code in the same order on CPU threads.
+// A shared curve (S_disc = 1 or S_infl = 1: "not shocked") is read with row stride 0.  The host twin
+// (adr_yoy_scenario_pv_host) runs the same per-date and per-coupon code in the same order on CPU threads.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,64 +29,20 @@
 
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
-#include "simple_interp.hpp"
+#include "scenario_common.hpp"
 
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
-int adr_ctx_compute_units(const adr_ctx* ctx);                                  // capi.hip
-
-// The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
-// exp / log implementations.
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
 
 namespace adr {
 namespace yscen {
 
-constexpr int kWave = 64;
-constexpr int kWaves = 16;                      // waves per block: four per SIMD, all on one scenario group
-constexpr int kThreads = kWave * kWaves;
-constexpr int kChunk = ADR_SCENARIO_CHUNK;      // swaps per partial sum of the book
-constexpr int kRedLanes = 64;                   // the book reduction's slots per scenario
-constexpr int kRedEntries = 16;                 // scenarios per reduction block
-constexpr size_t kLdsBudget = 160 * 1024;
+using namespace scen;    // the shared pieces (scenario_common.hpp)
 
-// A date in weight form on a table Tb.  Discount (Tb_k = ln d_k when kLog, else d_k):
-//   kLog:  ln D = wa Tb_a + (b != a ? wb Tb_b : 0);      else:  D = Tb_a + (b != a ? wb (Tb_b - Tb_a) : 0).
-// Inflation (Tb_k = L_k, L_0 = 0): ln I = (a > 0 ? wa L_a : 0) + (b != a ? wb L_b : 0).
-struct DateW {
-    int a, b;
-    double wa, wb;
-};
-
-template <bool kLog>
-__host__ __device__ inline DateW disc_weights(double t, const double* x, int K, int method) {
-    DateW d;
-    if (kLog) {
-        const si::LogWeights w = si::log_weights(t, x, K, method);
-        d.a = w.a; d.b = w.b; d.wa = w.wa; d.wb = w.wb;
-    } else {
-        const si::Where p = si::locate(t, x, K);
-        d.a = p.lo; d.b = p.hi; d.wa = 1.0; d.wb = p.w;
-    }
-    return d;
-}
-
+// A date on the inflation table (Tb_k = L_k, L_0 = 0) has scenario_common.hpp's weight form too:
+//   ln I = (a > 0 ? wa L_a : 0) + (b != a ? wb L_b : 0).
 __host__ __device__ inline DateW infl_weights(double t, const double* x, int N, int method) {
     const si::LogWeights w = si::log_weights(t, x, N, method);
     return DateW{w.a, w.b, w.wa, w.wb};
-}
-
-template <bool kLog, class Tab>
-__host__ __device__ inline double eval_df(const DateW& d, const Tab& tab) {
-    const double la = tab(d.a);
-    if (kLog) {
-        double s = d.wa * la;
-        if (d.b != d.a) s = s + d.wb * tab(d.b);
-        return exp(s);
-    }
-    double f = la;
-    if (d.b != d.a) f = la + d.wb * (tab(d.b) - la);
-    return f;
 }
 
 template <class Tab>
@@ -168,7 +121,7 @@ __host__ __device__ inline Slot make_slot(const Legs& g, int c, const Curves& cv
             else s.ws = infl_weights(ts, cv.ix, cv.N, cv.im);
             s.we = infl_weights(te, cv.ix, cv.N, cv.im);
         }
-        s.wp = disc_weights<kLog>(tp, cv.x, cv.K, cv.dm);
+        s.wp = date_weights<kLog>(tp, cv.x, cv.K, cv.dm);
     }
     if (c < g.n_fix) {
         const double xt = g.fix_tp[g.f0 + c];
@@ -176,7 +129,7 @@ __host__ __device__ inline Slot make_slot(const Legs& g, int c, const Curves& cv
             s.flags |= kHasFix;
             s.pay = g.fix_pay[g.f0 + c];
             if (cpn && xt == tp) s.flags |= kFixIsCpnTp;
-            else s.wx = disc_weights<kLog>(xt, cv.x, cv.K, cv.dm);
+            else s.wx = date_weights<kLog>(xt, cv.x, cv.K, cv.dm);
         }
     }
     return s;
@@ -217,20 +170,6 @@ __host__ __device__ inline bool leg_range(const int64_t* off, int64_t i, int64_t
     return true;
 }
 
-// book[s] = sum over the chunk rows of entry s: chunk j to slot j % 64 in order, then slots 0-31 += 32-63, ..., 0 += 1.
-void reduce_chunks(const double* work, int64_t chunks, int64_t S, double* book) {
-    for (int64_t e = 0; e < S; ++e) {
-        double p[kRedLanes];
-        for (int cl = 0; cl < kRedLanes; ++cl) {
-            p[cl] = 0.0;
-            for (int64_t j = cl; j < chunks; j += kRedLanes) p[cl] = p[cl] + work[j * S + e];
-        }
-        for (int h = kRedLanes / 2; h >= 1; h >>= 1)
-            for (int cl = 0; cl < h; ++cl) p[cl] = p[cl] + p[cl + h];
-        book[e] = p[0];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------ device
 struct Args {
     const double *times, *dfs;       // [K], [S_disc][K]
@@ -242,19 +181,6 @@ struct Args {
     const double *fix_tp, *fix_pay, *cpn;
     double *pv, *work;               // [n][S] or null; [n_chunks][S]
 };
-
-__device__ inline int lane_int(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-__device__ inline double lane_dbl(double v, int j) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
-}
-__device__ inline DateW lane_date(const DateW& d, int j) {
-    DateW r;
-    r.a = lane_int(d.a, j);
-    r.b = lane_int(d.b, j);
-    r.wa = lane_dbl(d.wa, j);
-    r.wb = r.b != r.a ? lane_dbl(d.wb, j) : 0.0;
-    return r;
-}
 
 // Lane j's slot in scalar registers; only the parts its flags say will be read.
 __device__ inline Slot lane_slot(const Slot& m, int j) {
@@ -275,16 +201,6 @@ __device__ inline Slot lane_slot(const Slot& m, int j) {
     }
     return u;
 }
-
-// kLds: the group's discount table sits in LDS; otherwise every lane reads its scenario's row of dfs.
-template <bool kLog, bool kLds>
-struct DevTab {
-    const double* p;     // kLds: &tab[0][lane]; else &dfs[row][0]
-    __device__ double operator()(int k) const {
-        if (kLds) return p[k * kWave];
-        return kLog ? log(p[k]) : p[k];
-    }
-};
 
 struct DevITab {
     const double* p;     // &itab[0][lane]
@@ -317,9 +233,9 @@ __global__ __launch_bounds__(kThreads) void yoy_scenario_pv_kernel(Args a) {
     const Curves cv{s_x, s_ix, K, N, a.dm, a.im};
     for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < a.n_chunks;
          ch += static_cast<int64_t>(gridDim.x) * kWaves) {
-        const int64_t i1 = ch * kChunk + kChunk < a.n ? ch * kChunk + kChunk : a.n;
+        const ChunkRange r = chunk_range<false>(ch, nullptr, a.n);
         double book = 0.0;
-        for (int64_t i = ch * kChunk; i < i1; ++i) {
+        for (int64_t i = r.i0; i < r.i1; ++i) {
             Legs g{a.fix_tp, a.fix_pay, a.cpn, a.m, 0, 0, 0, 0};      // uniform: scalar loads
             const bool ok_fix = leg_range(a.fix_off, i, a.mf, &g.f0, &g.n_fix);
             const bool ok = leg_range(a.cpn_off, i, a.m, &g.c0, &g.n_cpn) && ok_fix;
@@ -337,26 +253,6 @@ __global__ __launch_bounds__(kThreads) void yoy_scenario_pv_kernel(Args a) {
         }
         if (live) a.work[ch * S + s] = book;
     }
-}
-
-// book[e] = the fixed-order sum of the chunk rows (reduce_chunks above is its host form).
-__global__ __launch_bounds__(kRedLanes * kRedEntries) void yoy_scenario_book_kernel(const double* work, int64_t chunks, int64_t S,
-                                                                                    double* book) {
-    __shared__ double sh[kRedLanes][kRedEntries];
-    const int ei = threadIdx.x % kRedEntries, cl = threadIdx.x / kRedEntries;
-    const int64_t e = static_cast<int64_t>(blockIdx.x) * kRedEntries + ei;
-    double acc = 0.0;
-    if (e < S) {
-#pragma unroll 8
-        for (int64_t j = cl; j < chunks; j += kRedLanes) acc = acc + work[j * S + e];
-    }
-    sh[cl][ei] = acc;
-    __syncthreads();
-    for (int h = kRedLanes / 2; h >= 1; h >>= 1) {
-        if (cl < h) sh[cl][ei] = sh[cl][ei] + sh[cl + h][ei];
-        __syncthreads();
-    }
-    if (cl == 0 && e < S) book[e] = sh[0][ei];
 }
 
 // -------------------------------------------------------------------------------------------------------------- host
@@ -409,13 +305,8 @@ int validate(const std::string& w, const Call& c) {
 }
 
 int check_host_arrays(const std::string& w, const Call& c) {
-    for (int k = 0; k < c.K; ++k)
-        if (!std::isfinite(c.times[k]) || (k > 0 && c.times[k] < c.times[k - 1]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": knot times must be finite and non-decreasing");
-    for (int64_t i = 0; i < static_cast<int64_t>(c.S_disc) * c.K; ++i)
-        if (!(c.dfs[i] > 0.0) || !std::isfinite(c.dfs[i]))
-            return adr_set_error(ADR_ERR_INVALID, w + ": discount factors must be positive and finite (row " +
-                                                      std::to_string(i / c.K) + ", knot " + std::to_string(i % c.K) + ")");
+    const int rc = check_curves(w, c.K, c.times, c.S_disc, c.dfs, "row");
+    if (rc != ADR_OK) return rc;
     for (int k = 0; k < c.P; ++k)
         if (!std::isfinite(c.T[k]) || !(c.T[k] > (k ? c.T[k - 1] : 0.0)))
             return adr_set_error(ADR_ERR_INVALID, w + ": pillar times must be increasing from > 0");
@@ -438,12 +329,7 @@ int check_host_arrays(const std::string& w, const Call& c) {
 
 template <bool kLog, bool kLds>
 hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
-    const size_t lds = lds_bytes(a.K, a.P, kLds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&yoy_scenario_pv_kernel<kLog, kLds>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((yoy_scenario_pv_kernel<kLog, kLds>), grid, dim3(kThreads), lds, stream, a);
-    return hipGetLastError();
+    return launch_with_lds(&yoy_scenario_pv_kernel<kLog, kLds>, a, lds_bytes(a.K, a.P, kLds), grid, stream);
 }
 
 // The two kernels on `stream`; every pointer of `c` is device memory.
@@ -451,38 +337,24 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Call& c, double* work, hip
     int rc = validate(w, c);
     if (rc != ADR_OK) return rc;
     if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_yoy_scenario_pv_work doubles are needed)");
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
-    if (stream_or_null) stream = stream_or_null;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    const int64_t chunks = (c.n + kChunk - 1) / kChunk, groups = (static_cast<int64_t>(c.S) + kWave - 1) / kWave;
-    if (groups > 65535) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 65535 * 64 scenarios in one launch");
-    // one block per compute unit when the tables fill the LDS; a group's blocks share its chunks round-robin
-    const int64_t per_group = std::max<int64_t>(1, (adr_ctx_compute_units(ctx) + groups - 1) / groups);
-    const int64_t bx = std::min<int64_t>((chunks + kWaves - 1) / kWaves, per_group);
-    const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(groups));
+    const int64_t chunks = (c.n + kChunk - 1) / kChunk;
+    dim3 grid;
+    rc = launch_grid(w, ctx, chunks, c.S, &grid);
+    if (rc != ADR_OK) return rc;
     const Args a{c.times, c.dfs, c.T, c.b, c.K, c.P, c.S, c.dm, c.im, c.S_disc == 1 ? 0 : c.K, c.S_infl == 1 ? 0 : c.P,
                  c.n, c.mf, c.m, chunks, c.fix_off, c.cpn_off, c.fix_tp, c.fix_pay, c.cpn, c.pv, work};
     const bool in_lds = lds_bytes(c.K, c.P, true) <= kLdsBudget;
     const bool lin = c.dm == ADR_INTERP_LINEAR_FWD_RATES;
+    hipError_t e;
     if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
     else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(yoy_scenario_book_kernel, dim3(static_cast<unsigned>((c.S + kRedEntries - 1) / kRedEntries)),
-                           dim3(kRedLanes * kRedEntries), 0, stream, work, chunks, static_cast<int64_t>(c.S), c.book);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = enqueue_book_sum(work, chunks, c.S, c.book, stream);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
 }
-
-struct HostTab {
-    const double* p;     // the scenario's row of the converted table
-    double operator()(int k) const { return p[k]; }
-};
 
 template <bool kLog>
 void host_chunks(const Call& c, const Curves& cv, const double* tab, const double* itab, double* work, int64_t lo, int64_t hi) {
@@ -492,7 +364,8 @@ void host_chunks(const Call& c, const Curves& cv, const double* tab, const doubl
     std::vector<double> book(static_cast<size_t>(S));
     for (int64_t ch = lo; ch < hi; ++ch) {
         std::fill(book.begin(), book.end(), 0.0);
-        for (int64_t i = ch * kChunk; i < std::min(c.n, (ch + 1) * kChunk); ++i) {
+        const ChunkRange r = host_chunk_range(ch, nullptr, c.n);
+        for (int64_t i = r.i0; i < r.i1; ++i) {
             Legs g{c.fix_tp, c.fix_pay, c.cpn, c.m, 0, 0, 0, 0};
             const bool ok_fix = leg_range(c.fix_off, i, c.mf, &g.f0, &g.n_fix);
             const bool ok = leg_range(c.cpn_off, i, c.m, &g.c0, &g.n_cpn) && ok_fix;
@@ -519,10 +392,7 @@ namespace YS = adr::yscen;
 
 extern "C" {
 
-int64_t adr_yoy_scenario_pv_work(int64_t n, int S) {
-    if (n < 1 || S < 1) return 0;
-    return (n + YS::kChunk - 1) / YS::kChunk * S;
-}
+int64_t adr_yoy_scenario_pv_work(int64_t n, int S) { return adr_scenario_pv_work(n, S); }     // the same chunks
 
 int adr_yoy_scenario_pv_dev(adr_ctx* ctx, int disc_method, int K, const double* times_dev, int S_disc, const double* dfs_dev,
                             int infl_method, int P, const double* T_dev, int S_infl, const double* b_dev, int S, int64_t n,
@@ -544,12 +414,9 @@ int adr_yoy_scenario_pv(adr_ctx* ctx, int disc_method, int K, const double* time
     int rc = YS::validate(w, h);
     if (rc == ADR_OK) rc = YS::check_host_arrays(w, h);
     if (rc != ADR_OK) return rc;
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = YS::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     // one allocation: curves, flows, outputs, scratch, then the two offset arrays
     const size_t d = sizeof(double), SK = static_cast<size_t>(S_disc) * K, SP = static_cast<size_t>(S_infl) * P;
     const size_t W = static_cast<size_t>(adr_yoy_scenario_pv_work(n, S)), NS = static_cast<size_t>(n) * S;
@@ -557,7 +424,7 @@ int adr_yoy_scenario_pv(adr_ctx* ctx, int disc_method, int K, const double* time
                          (pv ? NS : 0) + S + W;
     const size_t off_bytes = static_cast<size_t>(n + 1) * sizeof(int64_t);
     char* base = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + 2 * off_bytes);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + 2 * off_bytes);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
     double* p = reinterpret_cast<double*>(base);
     auto take = [&p](size_t count) { double* q = p; p += count; return q; };
@@ -580,13 +447,7 @@ int adr_yoy_scenario_pv(adr_ctx* ctx, int disc_method, int K, const double* time
     }
     if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book_pv, dbook, S * d, hipMemcpyDeviceToHost, stream);
-    const hipError_t es = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = es;
-    const hipError_t ef = hipFree(base);
-    if (rc != ADR_OK) return rc;
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return ADR_OK;
+    return YS::finish_blocking(w, rc, e, stream, base);
 }
 
 int adr_yoy_scenario_pv_host(int disc_method, int K, const double* times, int S_disc, const double* dfs, int infl_method,
