@@ -138,6 +138,18 @@ _SIGNATURES = {
     "adr_scenario_tail": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "adr_scenario_tail_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "adr_scenario_tail_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "adr_yoy_scenario_subbook_pv": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp,
+                                              C.c_int, C.c_int64, C.c_int64, _i64p, _dp, _dp, C.c_int64, _i64p, _dp, C.c_int64,
+                                              _i64p, _dp, _dp]),
+    "adr_yoy_scenario_subbook_pv_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp,
+                                                  C.c_int, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64,
+                                                  _vp, _vp, _vp, _vp, _vp]),
+    "adr_yoy_scenario_subbook_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp,
+                                                   C.c_int, C.c_int64, C.c_int64, _i64p, _dp, _dp, C.c_int64, _i64p, _dp,
+                                                   C.c_int64, _i64p, _dp, _dp, C.c_int]),
+    "adr_scenario_tail_alloc": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "adr_scenario_tail_alloc_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "adr_scenario_tail_alloc_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1254,6 +1266,83 @@ def scenario_tail_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: int, v
     v = lambda p: _vp(int(p) or None)
     _check(load().adr_scenario_tail_dev(ctx._h, int(B), int(S_tot), v(rows_ptr), int(base_col), int(k), v(var_ptr), v(es_ptr),
                                         _vp(stream or None)), "adr_scenario_tail_dev")
+
+
+def _yoy_subbook_call(fn, head, tail, disc_method, times, dfs, infl_method, T, b, fixed, book, sub_off, per_trade):
+    times, dfs, T, b, S, fix_off, fix_tp, fix_pay, cpn_off, cpn = _yoy_scenario_inputs(times, dfs, T, b, fixed, book)
+    sub_off, B = _sub_offsets(sub_off)
+    n = fix_off.size - 1
+    sub_pv = np.empty((B, S))
+    pv = np.empty((n, S)) if per_trade else None
+    _check(fn(*head, int(disc_method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), int(infl_method), T.size, _ptr(T),
+              b.shape[0], _ptr(b), S, n, fix_tp.size, _ptr(fix_off, _i64p), _ptr(fix_tp), _ptr(fix_pay), cpn.shape[1],
+              _ptr(cpn_off, _i64p), _ptr(cpn), B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv), *tail), fn.__name__)
+    return _sub_result(sub_pv, pv, per_trade)
+
+
+def yoy_scenario_subbook_pv(ctx: Context, disc_method: int, times, dfs, infl_method: int, T, b, fixed, book, sub_off,
+                            per_trade=False):
+    """`yoy_scenario_pv` per sub-book in one launch (adr_yoy_scenario_subbook_pv, blocking): sub-book ``b`` holds the swaps
+    ``sub_off[b] .. sub_off[b + 1]``.  ``sub_pv [B, S]`` and, with ``per_trade``, ``pv [S, n]``."""
+    return _yoy_subbook_call(load().adr_yoy_scenario_subbook_pv, (ctx._h,), (), disc_method, times, dfs, infl_method, T, b,
+                             fixed, book, sub_off, per_trade)
+
+
+def yoy_scenario_subbook_pv_host(disc_method: int, times, dfs, infl_method: int, T, b, fixed, book, sub_off, per_trade=False,
+                                 n_threads=0):
+    """`yoy_scenario_subbook_pv` on the CPU (adr_yoy_scenario_subbook_pv_host): the same arithmetic and the same order of
+    every sub-book's sum; no GPU needed."""
+    return _yoy_subbook_call(load().adr_yoy_scenario_subbook_pv_host, (), (int(n_threads),), disc_method, times, dfs,
+                             infl_method, T, b, fixed, book, sub_off, per_trade)
+
+
+def yoy_scenario_subbook_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: int, infl_method: int, P: int, S_infl: int,
+                                S: int, n_swaps: int, n_fix: int, n_coupons: int, B: int, ptrs, sub_pv_ptr: int, work_ptr: int,
+                                pv_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_yoy_scenario_subbook_pv_dev): ``ptrs`` as `yoy_scenario_pv_dev` takes them plus ``plan``, the
+    uploaded `scenario_subbook_plan`; outputs ``sub_pv`` [B, S] and ``pv`` [n, S] (0: not wanted); `scenario_subbook_work`
+    doubles of scratch."""
+    v = lambda p: _vp(int(p) or None)
+    g = lambda k: v(ptrs.get(k, 0))
+    _check(load().adr_yoy_scenario_subbook_pv_dev(ctx._h, int(disc_method), int(K), g("times"), int(S_disc), g("dfs"),
+                                                  int(infl_method), int(P), g("T"), int(S_infl), g("b"), int(S), int(n_swaps),
+                                                  int(n_fix), g("fix_off"), g("fix_tp"), g("fix_pay"), int(n_coupons),
+                                                  g("cpn_off"), g("cpn"), int(B), g("plan"), v(pv_ptr), v(sub_pv_ptr),
+                                                  v(work_ptr), _vp(stream or None)), "adr_yoy_scenario_subbook_pv_dev")
+
+
+SCENARIO_ALLOC_MAX = 8192                                   # ADR_SCENARIO_ALLOC_MAX
+
+
+def _alloc_call(fn, head, rows, k, base_col):
+    rows = _tail_rows(rows)
+    B = rows.shape[0]
+    tot, comp_var, comp_es = np.empty(2), np.empty(B), np.empty(B)
+    _check(fn(*head, B, rows.shape[1], _ptr(rows), int(base_col), int(k), _ptr(tot[0:1]), _ptr(tot[1:2]), _ptr(comp_var),
+              _ptr(comp_es)), fn.__name__)
+    return {"var": float(tot[0]), "es": float(tot[1]), "comp_var": comp_var, "comp_es": comp_es}
+
+
+def scenario_tail_alloc(ctx: Context, rows, k: int, base_col: int = -1):
+    """The firm's tail and its Euler allocation to the rows of ``rows [B, S]`` on the device (adr_scenario_tail_alloc,
+    blocking): ``var`` and ``es`` of the column sums, and per row ``comp_var`` (its P&L in the firm's ``k``-th worst
+    scenario, negated) and ``comp_es`` (minus its mean P&L over the firm's ``k`` worst scenarios)."""
+    return _alloc_call(load().adr_scenario_tail_alloc, (ctx._h,), rows, k, base_col)
+
+
+def scenario_tail_alloc_host(rows, k: int, base_col: int = -1):
+    """`scenario_tail_alloc` on the CPU (adr_scenario_tail_alloc_host): the same sums in the same order, the same bits."""
+    return _alloc_call(load().adr_scenario_tail_alloc_host, (), rows, k, base_col)
+
+
+def scenario_tail_alloc_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: int, var_ptr: int, es_ptr: int,
+                            comp_var_ptr: int, comp_es_ptr: int, work_ptr: int, base_col: int = -1, stream=0):
+    """Non-blocking form (adr_scenario_tail_alloc_dev): device pointers of ``rows`` [B, S_tot], ``var`` [1], ``es`` [1],
+    ``comp_var`` [B], ``comp_es`` [B] and ``S_tot`` doubles of scratch."""
+    v = lambda p: _vp(int(p) or None)
+    _check(load().adr_scenario_tail_alloc_dev(ctx._h, int(B), int(S_tot), v(rows_ptr), int(base_col), int(k), v(var_ptr),
+                                              v(es_ptr), v(comp_var_ptr), v(comp_es_ptr), v(work_ptr), _vp(stream or None)),
+           "adr_scenario_tail_alloc_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

@@ -15,6 +15,9 @@
 // The tail kernel: one block per row.  The P&L values go to LDS as order-preserving integer keys, padded with +inf to a
 // power of two, and a bitonic network sorts them; thread 0 then adds the k smallest in ascending order.  The keys make
 // the order total (-0.0 before +0.0), so the host twin's std::sort gives the same sequence.
+//
+// The tail allocation (adr_scenario_tail_alloc*): the firm's total per scenario, the scenarios ordered by it, and every
+// row's P&L over the firm's k worst scenarios - see the section below.
 #include "subbook.hpp"
 
 #include <algorithm>
@@ -304,6 +307,150 @@ hipError_t enqueue_tail(const double* rows, int64_t B, int S_tot, int base_col, 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------- tail allocation
+// The Euler allocation of the firm's tail to the rows (adr_scenario_tail_alloc*), three kernels in one chain:
+//   1. tot[e] = the fixed-order sum over the rows of pnl[b][e]: row b to slot b % 64 in order, then the halving tree -
+//      scenario_book_kernel's shape, 64 slots x 16 scenarios per block, so a slot's chain is B / 64 adds long;
+//   2. one block orders the scenarios by (key(tot[e]), e) with a bitonic network over (key, index) pairs in LDS, adds
+//      the firm's tail and leaves the first k indices where tot was (the scratch is S_tot doubles, k <= S_tot);
+//   3. one thread per row adds the row's P&L over those k scenarios in that order.
+// A NaN total is passed on as index -1 in the first slot; every output is then NaN.
+struct KeyIdx {
+    int64_t key, idx;
+};
+__host__ __device__ inline bool after(const KeyIdx& a, const KeyIdx& b) { return a.key > b.key || (a.key == b.key && a.idx > b.idx); }
+
+__global__ __launch_bounds__(scen::kRedLanes * scen::kRedEntries) void alloc_total_kernel(const double* rows, int64_t B, int64_t S_tot,
+                                                                                          int base_col, int m, double* tot) {
+    constexpr int kLanes = scen::kRedLanes, kEntries = scen::kRedEntries;
+    __shared__ double sh[kLanes][kEntries];
+    const int ei = threadIdx.x % kEntries, cl = threadIdx.x / kEntries;
+    const int e = blockIdx.x * kEntries + ei;
+    double acc = 0.0;
+    if (e < m) {
+#pragma unroll 8
+        for (int64_t b = cl; b < B; b += kLanes) acc = acc + pnl_at(rows + b * S_tot, base_col, e);
+    }
+    sh[cl][ei] = acc;
+    __syncthreads();
+    for (int h = kLanes / 2; h >= 1; h >>= 1) {
+        if (cl < h) sh[cl][ei] = sh[cl][ei] + sh[cl + h][ei];
+        __syncthreads();
+    }
+    if (cl == 0 && e < m) tot[e] = sh[0][ei];
+}
+
+// The firm's measures from the ordered pairs; both sums run over the first k in order from 0.0.
+__host__ __device__ inline void total_of_sorted(const KeyIdx* pairs, int k, double* var_tot, double* es_tot) {
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) sum = sum + value_of(pairs[i].key);
+    *var_tot = -value_of(pairs[k - 1].key);
+    *es_tot = -sum / static_cast<double>(k);
+}
+
+// m totals, P = the power of two >= m (the LDS holds P pairs; the padding is +inf with indices m .. P - 1, behind
+// every total).  `tot` comes in as doubles and goes out as the first k scenario indices, int64.
+__global__ __launch_bounds__(1024) void alloc_order_kernel(double* tot, int m, int P, int k, double* var_tot, double* es_tot) {
+    extern __shared__ KeyIdx pairs[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    int nan = 0;
+    for (int e = tid; e < P; e += nt) {
+        double v = INFINITY;
+        if (e < m) {
+            v = tot[e];
+            nan |= v != v;
+        }
+        pairs[e] = KeyIdx{key_of(v), e};
+    }
+    int64_t* order = reinterpret_cast<int64_t*>(tot);
+    if (__syncthreads_or(nan)) {                    // uniform over the block; every total has been read
+        if (tid == 0) {
+            order[0] = -1;
+            *var_tot = NAN;
+            *es_tot = NAN;
+        }
+        return;
+    }
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += nt) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const KeyIdx a = pairs[lo], b = pairs[hi];
+                if (after(a, b) == ((lo & size) == 0)) {
+                    pairs[lo] = b;
+                    pairs[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < k; i += nt) order[i] = pairs[i].idx;
+    if (tid == 0) total_of_sorted(pairs, k, var_tot, es_tot);
+}
+
+// A row's components over the k ordered scenarios.
+__host__ __device__ inline void components_of(const double* row, int base_col, const int64_t* order, int k, double* comp_var,
+                                              double* comp_es) {
+    double sum = 0.0, last = 0.0;
+    for (int i = 0; i < k; ++i) {
+        last = pnl_at(row, base_col, static_cast<int>(order[i]));
+        sum = sum + last;
+    }
+    *comp_var = -last;
+    *comp_es = -sum / static_cast<double>(k);
+}
+
+__global__ __launch_bounds__(256) void alloc_rows_kernel(const double* rows, int64_t B, int64_t S_tot, int base_col, int m,
+                                                         const int64_t* order, int k, double* comp_var, double* comp_es) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t first = order[0];                 // uniform: a scalar load
+    if (first < 0 || first >= m) {                  // a NaN total
+        comp_var[b] = NAN;
+        comp_es[b] = NAN;
+        return;
+    }
+    components_of(rows + b * S_tot, base_col, order, k, comp_var + b, comp_es + b);
+}
+
+int check_alloc(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
+    if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
+    if (base_col < -1 || base_col >= S_tot)
+        return adr_set_error(ADR_ERR_INVALID, w + ": base_col must be -1 (the rows are P&L) or a column, 0 .. " +
+                                                  std::to_string(S_tot - 1));
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    if (m < 1) return adr_set_error(ADR_ERR_INVALID, w + ": no P&L value is left beside the base column");
+    if (k < 1 || k > m)
+        return adr_set_error(ADR_ERR_INVALID, w + ": k must lie in 1 .. " + std::to_string(m) + " (the P&L values per row)");
+    if (m > ADR_SCENARIO_ALLOC_MAX)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": " + std::to_string(m) + " P&L values per row; at most "
+                                                  "ADR_SCENARIO_ALLOC_MAX (8192) (key, index) pairs fit the LDS");
+    return ADR_OK;
+}
+
+hipError_t enqueue_alloc(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var_tot, double* es_tot,
+                         double* comp_var, double* comp_es, double* work, hipStream_t stream) {
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot, P = pow2_at_least(m);
+    const int64_t row_blocks = (B + 255) / 256;
+    if (row_blocks > INT32_MAX) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(alloc_total_kernel, dim3(static_cast<unsigned>((m + scen::kRedEntries - 1) / scen::kRedEntries)),
+                       dim3(scen::kRedLanes * scen::kRedEntries), 0, stream, rows, B, static_cast<int64_t>(S_tot), base_col, m, work);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int threads = std::min(1024, std::max(kWave, P / 2));
+    const size_t lds = static_cast<size_t>(P) * sizeof(KeyIdx);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&alloc_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(alloc_order_kernel, dim3(1), dim3(threads), lds, stream, work, m, P, k, var_tot, es_tot);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(alloc_rows_kernel, dim3(static_cast<unsigned>(row_blocks)), dim3(256), 0, stream, rows, B,
+                       static_cast<int64_t>(S_tot), base_col, m, reinterpret_cast<const int64_t*>(work), k, comp_var, comp_es);
+    return hipGetLastError();
+}
+
 }  // namespace sub
 }  // namespace adr
 
@@ -395,6 +542,88 @@ int adr_scenario_tail_host(int64_t B, int S_tot, const double* rows, int base_co
             std::sort(keys.begin(), keys.end());
             SB::tail_of_sorted(keys.data(), k, var + b, es + b);
         }
+    });
+    return ADR_OK;
+}
+
+int adr_scenario_tail_alloc_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k,
+                                double* var_tot_dev, double* es_tot_dev, double* comp_var_dev, double* comp_es_dev,
+                                double* work_dev, void* stream) {
+    const std::string w = "adr_scenario_tail_alloc_dev";
+    int rc = SB::check_alloc(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows_dev || !var_tot_dev || !es_tot_dev || !comp_var_dev || !comp_es_dev) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    if (!work_dev) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (S_tot doubles are needed)");
+    hipStream_t s = nullptr;
+    rc = adr::scen::target_stream(w, ctx, static_cast<hipStream_t>(stream), &s);
+    if (rc != ADR_OK) return rc;
+    const hipError_t e = SB::enqueue_alloc(rows_dev, B, S_tot, base_col, k, var_tot_dev, es_tot_dev, comp_var_dev, comp_es_dev,
+                                           work_dev, s);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+int adr_scenario_tail_alloc(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, double* var_tot,
+                            double* es_tot, double* comp_var, double* comp_es) {
+    const std::string w = "adr_scenario_tail_alloc";
+    int rc = SB::check_alloc(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !var_tot || !es_tot || !comp_var || !comp_es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    hipStream_t stream = nullptr;
+    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
+    if (rc != ADR_OK) return rc;
+    // one allocation: the rows, the scratch, the two totals, the two component vectors
+    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot, nb = static_cast<size_t>(B);
+    double* base = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (R + S_tot + 2 + 2 * nb) * d);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double *dwork = base + R, *dtot = dwork + S_tot, *dcv = dtot + 2, *dce = dcv + nb;
+    e = hipMemcpyAsync(base, rows, R * d, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = SB::enqueue_alloc(base, B, S_tot, base_col, k, dtot, dtot + 1, dcv, dce, dwork, stream);
+    double totals[2] = {0.0, 0.0};
+    if (e == hipSuccess) e = hipMemcpyAsync(totals, dtot, 2 * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(comp_var, dcv, nb * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(comp_es, dce, nb * d, hipMemcpyDeviceToHost, stream);
+    rc = adr::scen::finish_blocking(w, ADR_OK, e, stream, base);
+    if (rc == ADR_OK) {
+        *var_tot = totals[0];
+        *es_tot = totals[1];
+    }
+    return rc;
+}
+
+int adr_scenario_tail_alloc_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var_tot, double* es_tot,
+                                 double* comp_var, double* comp_es) {
+    const std::string w = "adr_scenario_tail_alloc_host";
+    const int rc = SB::check_alloc(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !var_tot || !es_tot || !comp_var || !comp_es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    std::vector<SB::KeyIdx> pairs(static_cast<size_t>(m));
+    bool nan = false;
+    for (int e = 0; e < m; ++e) {
+        double p[SB::kSlots];
+        for (int q = 0; q < SB::kSlots; ++q) {
+            p[q] = 0.0;
+            for (int64_t b = q; b < B; b += SB::kSlots) p[q] = p[q] + SB::pnl_at(rows + b * S_tot, base_col, e);
+        }
+        for (int h = SB::kSlots / 2; h >= 1; h >>= 1)
+            for (int q = 0; q < h; ++q) p[q] = p[q] + p[q + h];
+        nan |= p[0] != p[0];
+        pairs[e] = SB::KeyIdx{SB::key_of(p[0]), e};
+    }
+    if (nan) {
+        *var_tot = *es_tot = NAN;
+        std::fill(comp_var, comp_var + B, NAN);
+        std::fill(comp_es, comp_es + B, NAN);
+        return ADR_OK;
+    }
+    std::sort(pairs.begin(), pairs.end(), [](const SB::KeyIdx& a, const SB::KeyIdx& b) { return SB::after(b, a); });
+    SB::total_of_sorted(pairs.data(), k, var_tot, es_tot);
+    std::vector<int64_t> order(static_cast<size_t>(k));
+    for (int i = 0; i < k; ++i) order[i] = pairs[i].idx;
+    adr::parallel_ranges(B, adr::pool_threads(B, 64), [&](int, int64_t lo, int64_t hi) {
+        for (int64_t b = lo; b < hi; ++b) SB::components_of(rows + b * S_tot, base_col, order.data(), k, comp_var + b, comp_es + b);
     });
     return ADR_OK;
 }

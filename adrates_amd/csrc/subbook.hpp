@@ -1,5 +1,5 @@
 // Sub-books of a scenario revaluation (subbook.hip): the chunk plan, the fixed-order sum per sub-book and the tail
-// measures; shared by scenario_pv.hip and credit_scenario_pv.hip.  The whole book's sum, which subbook.hip holds too, is
+// measures and their allocation; shared by scenario_pv.hip, credit_scenario_pv.hip and yoy_scenario_pv.hip.  The whole book's sum, which subbook.hip holds too, is
 // declared in scenario_common.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +37,12 @@ void reduce_subbooks(const double* work, const int64_t* chunk_off, int64_t B, in
 // var[b], es[b] of rows[b][S_tot] (adr_scenario_tail's rule); k and the width have been checked.
 hipError_t enqueue_tail(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var, double* es, hipStream_t stream);
 int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k);
+
+// The tail allocation of rows[b][S_tot] (adr_scenario_tail_alloc's rule): the firm's var and es and every row's
+// components; `work` holds S_tot doubles; k and the width have been checked.  Three kernels on `stream`.
+hipError_t enqueue_alloc(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var_tot, double* es_tot,
+                         double* comp_var, double* comp_es, double* work, hipStream_t stream);
+int check_alloc(const std::string& w, int64_t B, int S_tot, int base_col, int k);
 
 }  // namespace sub
 }  // namespace adr

@@ -30,6 +30,7 @@
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
 #include "scenario_common.hpp"
+#include "subbook.hpp"
 
 #pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
 
@@ -176,10 +177,12 @@ struct Args {
     const double *T, *b;             // [P], [S_infl][P]
     int K, P, S, dm, im;
     int disc_stride, infl_stride;    // K / P, or 0 for a shared row
-    int64_t n, mf, m, n_chunks;
+    int64_t n, mf, m;
+    int64_t n_chunks;                // kSub: the rows `work` holds, an upper bound of the plan's count
     const int64_t *fix_off, *cpn_off;
     const double *fix_tp, *fix_pay, *cpn;
     double *pv, *work;               // [n][S] or null; [n_chunks][S]
+    const int64_t *sub_chunks, *sub_bounds;      // kSub: the plan's chunk count and its [chunks][2] swap bounds (subbook.hpp)
 };
 
 // Lane j's slot in scalar registers; only the parts its flags say will be read.
@@ -207,7 +210,8 @@ struct DevITab {
     __device__ double operator()(int k) const { return p[k * kWave]; }
 };
 
-template <bool kLog, bool kLds>
+// kSub: the chunks are those of a sub-book plan (their swap bounds come from a table) instead of ch * kChunk.
+template <bool kLog, bool kLds, bool kSub>
 __global__ __launch_bounds__(kThreads) void yoy_scenario_pv_kernel(Args a) {
     extern __shared__ double lds[];
     const int K = a.K, N = a.P + 1, S = a.S;
@@ -231,9 +235,14 @@ __global__ __launch_bounds__(kThreads) void yoy_scenario_pv_kernel(Args a) {
     const DevTab<kLog, kLds> tab{kLds ? s_tab + lane : row};
     const DevITab itab{s_itab + lane};
     const Curves cv{s_x, s_ix, K, N, a.dm, a.im};
-    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < a.n_chunks;
+    int64_t n_chunks = a.n_chunks;
+    if (kSub) {
+        const int64_t planned = *a.sub_chunks;              // uniform: a scalar load
+        n_chunks = planned < n_chunks ? planned : n_chunks;
+    }
+    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * kWaves + wave; ch < n_chunks;
          ch += static_cast<int64_t>(gridDim.x) * kWaves) {
-        const ChunkRange r = chunk_range<false>(ch, nullptr, a.n);
+        const ChunkRange r = chunk_range<kSub>(ch, a.sub_bounds, a.n);
         double book = 0.0;
         for (int64_t i = r.i0; i < r.i1; ++i) {
             Legs g{a.fix_tp, a.fix_pay, a.cpn, a.m, 0, 0, 0, 0};      // uniform: scalar loads
@@ -329,42 +338,53 @@ int check_host_arrays(const std::string& w, const Call& c) {
 
 template <bool kLog, bool kLds>
 hipError_t launch(const Args& a, dim3 grid, hipStream_t stream) {
-    return launch_with_lds(&yoy_scenario_pv_kernel<kLog, kLds>, a, lds_bytes(a.K, a.P, kLds), grid, stream);
+    const size_t lds = lds_bytes(a.K, a.P, kLds);
+    if (a.sub_bounds) return launch_with_lds(&yoy_scenario_pv_kernel<kLog, kLds, true>, a, lds, grid, stream);
+    return launch_with_lds(&yoy_scenario_pv_kernel<kLog, kLds, false>, a, lds, grid, stream);
 }
 
-// The two kernels on `stream`; every pointer of `c` is device memory.
-int enqueue(const std::string& w, adr_ctx* ctx, const Call& c, double* work, hipStream_t stream_or_null) {
+// The two kernels on `stream`; every pointer of `c` is device memory.  B > 0: the chunks of the sub-book plan `plan`, and
+// c.book is sub_pv[B][S].
+int enqueue(const std::string& w, adr_ctx* ctx, const Call& c, double* work, hipStream_t stream_or_null, int64_t B = 0,
+            const int64_t* plan = nullptr) {
     int rc = validate(w, c);
     if (rc != ADR_OK) return rc;
     if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_yoy_scenario_pv_work doubles are needed)");
+    const bool subs = B != 0 || plan;
+    if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
     hipStream_t stream = nullptr;
     rc = target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
-    const int64_t chunks = (c.n + kChunk - 1) / kChunk;
+    const int64_t chunks = subs ? sub::max_chunks(c.n, B, kChunk) : (c.n + kChunk - 1) / kChunk;
     dim3 grid;
     rc = launch_grid(w, ctx, chunks, c.S, &grid);
     if (rc != ADR_OK) return rc;
+    const sub::Plan pl = subs ? sub::plan_view(plan, B) : sub::Plan{nullptr, nullptr};
     const Args a{c.times, c.dfs, c.T, c.b, c.K, c.P, c.S, c.dm, c.im, c.S_disc == 1 ? 0 : c.K, c.S_infl == 1 ? 0 : c.P,
-                 c.n, c.mf, c.m, chunks, c.fix_off, c.cpn_off, c.fix_tp, c.fix_pay, c.cpn, c.pv, work};
+                 c.n, c.mf, c.m, chunks, c.fix_off, c.cpn_off, c.fix_tp, c.fix_pay, c.cpn, c.pv, work,
+                 subs ? pl.chunk_off + B : nullptr, pl.bounds};
     const bool in_lds = lds_bytes(c.K, c.P, true) <= kLdsBudget;
     const bool lin = c.dm == ADR_INTERP_LINEAR_FWD_RATES;
     hipError_t e;
     if (lin) e = in_lds ? launch<false, true>(a, grid, stream) : launch<false, false>(a, grid, stream);
     else e = in_lds ? launch<true, true>(a, grid, stream) : launch<true, false>(a, grid, stream);
-    if (e == hipSuccess) e = enqueue_book_sum(work, chunks, c.S, c.book, stream);
+    if (e == hipSuccess && subs) e = sub::enqueue_sum(work, pl.chunk_off, chunks, B, c.S, c.book, stream);
+    else if (e == hipSuccess) e = enqueue_book_sum(work, chunks, c.S, c.book, stream);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
 }
 
 template <bool kLog>
-void host_chunks(const Call& c, const Curves& cv, const double* tab, const double* itab, double* work, int64_t lo, int64_t hi) {
+void host_chunks(const Call& c, const Curves& cv, const double* tab, const double* itab, double* work, int64_t lo, int64_t hi,
+                 const int64_t* bounds = nullptr) {
     const int S = c.S, N = c.P + 1;
     const size_t ds = c.S_disc == 1 ? 0 : c.K, is = c.S_infl == 1 ? 0 : N;
     std::vector<Acc> acc(static_cast<size_t>(S));
     std::vector<double> book(static_cast<size_t>(S));
     for (int64_t ch = lo; ch < hi; ++ch) {
         std::fill(book.begin(), book.end(), 0.0);
-        const ChunkRange r = host_chunk_range(ch, nullptr, c.n);
+        const ChunkRange r = host_chunk_range(ch, bounds, c.n);
         for (int64_t i = r.i0; i < r.i1; ++i) {
             Legs g{c.fix_tp, c.fix_pay, c.cpn, c.m, 0, 0, 0, 0};
             const bool ok_fix = leg_range(c.fix_off, i, c.mf, &g.f0, &g.n_fix);
@@ -383,6 +403,89 @@ void host_chunks(const Call& c, const Curves& cv, const double* tab, const doubl
         }
         std::copy(book.begin(), book.end(), work + ch * S);
     }
+}
+
+// Blocking form: inputs, outputs and scratch in one device allocation.  B > 0: h.book is sub_pv[B][S] of the sub-books
+// sub_off (host), and the plan is built and uploaded here.
+int run_blocking(const std::string& w, adr_ctx* ctx, const Call& h, int64_t B = 0, const int64_t* sub_off = nullptr) {
+    int rc = validate(w, h);
+    if (rc == ADR_OK) rc = check_host_arrays(w, h);
+    if (rc != ADR_OK) return rc;
+    std::vector<int64_t> plan;
+    if (B > 0) {
+        rc = sub::build_plan(w, h.n, B, sub_off, plan);
+        if (rc != ADR_OK) return rc;
+    }
+    hipStream_t stream = nullptr;
+    rc = target_stream(w, ctx, nullptr, &stream);
+    if (rc != ADR_OK) return rc;
+    // one allocation: curves, flows, outputs, scratch, then the plan and the two offset arrays
+    const int K = h.K, P = h.P, S = h.S;
+    const int64_t n = h.n;
+    const size_t rows = B > 0 ? static_cast<size_t>(B) : 1;
+    const size_t d = sizeof(double), SK = static_cast<size_t>(h.S_disc) * K, SP = static_cast<size_t>(h.S_infl) * P;
+    const size_t W = static_cast<size_t>(B > 0 ? adr_scenario_subbook_work(n, B, S) : adr_yoy_scenario_pv_work(n, S));
+    const size_t NS = static_cast<size_t>(n) * S, mf = static_cast<size_t>(h.mf), mc = ADR_YOY_FIELDS * static_cast<size_t>(h.m);
+    const size_t n_dbl = K + SK + P + SP + 2 * mf + mc + (h.pv ? NS : 0) + rows * S + W;
+    const size_t off_bytes = static_cast<size_t>(n + 1) * sizeof(int64_t), plan_bytes = plan.size() * sizeof(int64_t);
+    char* base = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + plan_bytes + 2 * off_bytes);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double* p = reinterpret_cast<double*>(base);
+    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
+    double *dt = take(K), *ddf = take(SK), *dT = take(P), *db = take(SP);
+    double *dftp = take(mf), *dfpay = take(mf), *dcpn = take(mc);
+    double* dpv = h.pv ? take(NS) : nullptr;
+    double *dbook = take(rows * S), *dwork = take(W);
+    int64_t* dplan = reinterpret_cast<int64_t*>(p);
+    int64_t* dfo = dplan + plan.size();
+    int64_t* dco = dfo + (n + 1);
+    struct Piece { void* dst; const void* src; size_t bytes; };
+    const Piece in[] = {{dt, h.times, K * d}, {ddf, h.dfs, SK * d}, {dT, h.T, P * d}, {db, h.b, SP * d},
+                        {dftp, h.fix_tp, mf * d}, {dfpay, h.fix_pay, mf * d}, {dcpn, h.cpn, mc * d},
+                        {dplan, plan.data(), plan_bytes}, {dfo, h.fix_off, off_bytes}, {dco, h.cpn_off, off_bytes}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        const Call c{h.dm, K, dt, h.S_disc, ddf, h.im, P, dT, h.S_infl, db, S, n, h.mf, dfo, dftp, dfpay, h.m, dco, dcpn, dpv, dbook};
+        rc = enqueue(w, ctx, c, dwork, stream, B, B > 0 ? dplan : nullptr);
+    }
+    if (e == hipSuccess && rc == ADR_OK && h.pv) e = hipMemcpyAsync(h.pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(h.book, dbook, rows * S * d, hipMemcpyDeviceToHost, stream);
+    return finish_blocking(w, rc, e, stream, base);
+}
+
+// The host entries' body; B > 0: c.book is sub_pv[B][S] of the sub-books sub_off.
+int host_run(const std::string& w, const Call& c, int n_threads, int64_t B = 0, const int64_t* sub_off = nullptr) {
+    int rc = validate(w, c);
+    if (rc == ADR_OK) rc = check_host_arrays(w, c);
+    if (rc != ADR_OK) return rc;
+    std::vector<int64_t> plan;
+    if (B > 0) {
+        rc = sub::build_plan(w, c.n, B, sub_off, plan);
+        if (rc != ADR_OK) return rc;
+    }
+    const bool lin = c.dm == ADR_INTERP_LINEAR_FWD_RATES;
+    const int N = c.P + 1, S = c.S;
+    std::vector<double> tab(c.dfs, c.dfs + static_cast<size_t>(c.S_disc) * c.K);
+    if (!lin)
+        for (double& v : tab) v = std::log(v);
+    std::vector<double> ix(N), itab(static_cast<size_t>(c.S_infl) * N);
+    for (int k = 0; k < N; ++k) ix[k] = k ? c.T[k - 1] : 0.0;
+    for (int s = 0; s < c.S_infl; ++s)
+        for (int k = 0; k < N; ++k) itab[static_cast<size_t>(s) * N + k] = node_log(c.T, c.b + static_cast<size_t>(s) * c.P, k);
+    const Curves cv{c.times, ix.data(), c.K, N, c.dm, c.im};
+    const int64_t* bounds = B > 0 ? plan.data() + B + 1 : nullptr;
+    const int64_t chunks = B > 0 ? plan[B] : (c.n + kChunk - 1) / kChunk;
+    std::vector<double> work(static_cast<size_t>(chunks) * S);
+    const int threads = n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4);
+    adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
+        if (lin) host_chunks<false>(c, cv, tab.data(), itab.data(), work.data(), lo, hi, bounds);
+        else host_chunks<true>(c, cv, tab.data(), itab.data(), work.data(), lo, hi, bounds);
+    });
+    if (B > 0) sub::reduce_subbooks(work.data(), plan.data(), B, S, c.book);
+    else reduce_chunks(work.data(), chunks, S, c.book);
+    return ADR_OK;
 }
 
 }  // namespace yscen
@@ -408,77 +511,55 @@ int adr_yoy_scenario_pv(adr_ctx* ctx, int disc_method, int K, const double* time
                         int infl_method, int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
                         const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m, const int64_t* cpn_off,
                         const double* cpn, double* pv, double* book_pv) {
-    const std::string w = "adr_yoy_scenario_pv";
     const YS::Call h{disc_method, K, times, S_disc, dfs, infl_method, P, T, S_infl, b, S, n, n_fix,
                      fix_off, fix_tp, fix_pay, m, cpn_off, cpn, pv, book_pv};
-    int rc = YS::validate(w, h);
-    if (rc == ADR_OK) rc = YS::check_host_arrays(w, h);
-    if (rc != ADR_OK) return rc;
-    hipStream_t stream = nullptr;
-    rc = YS::target_stream(w, ctx, nullptr, &stream);
-    if (rc != ADR_OK) return rc;
-    // one allocation: curves, flows, outputs, scratch, then the two offset arrays
-    const size_t d = sizeof(double), SK = static_cast<size_t>(S_disc) * K, SP = static_cast<size_t>(S_infl) * P;
-    const size_t W = static_cast<size_t>(adr_yoy_scenario_pv_work(n, S)), NS = static_cast<size_t>(n) * S;
-    const size_t n_dbl = K + SK + P + SP + 2 * static_cast<size_t>(n_fix) + ADR_YOY_FIELDS * static_cast<size_t>(m) +
-                         (pv ? NS : 0) + S + W;
-    const size_t off_bytes = static_cast<size_t>(n + 1) * sizeof(int64_t);
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + 2 * off_bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double* p = reinterpret_cast<double*>(base);
-    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
-    double *dt = take(K), *ddf = take(SK), *dT = take(P), *db = take(SP);
-    double *dftp = take(n_fix), *dfpay = take(n_fix), *dcpn = take(ADR_YOY_FIELDS * static_cast<size_t>(m));
-    double* dpv = pv ? take(NS) : nullptr;
-    double *dbook = take(S), *dwork = take(W);
-    int64_t* dfo = reinterpret_cast<int64_t*>(p);
-    int64_t* dco = dfo + (n + 1);
-    struct Piece { void* dst; const void* src; size_t bytes; };
-    const Piece in[] = {{dt, times, K * d}, {ddf, dfs, SK * d}, {dT, T, P * d}, {db, b, SP * d},
-                        {dftp, fix_tp, static_cast<size_t>(n_fix) * d}, {dfpay, fix_pay, static_cast<size_t>(n_fix) * d},
-                        {dcpn, cpn, ADR_YOY_FIELDS * static_cast<size_t>(m) * d}, {dfo, fix_off, off_bytes}, {dco, cpn_off, off_bytes}};
-    for (const Piece& pc : in)
-        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) {
-        const YS::Call c{disc_method, K, dt, S_disc, ddf, infl_method, P, dT, S_infl, db, S, n, n_fix,
-                         dfo, dftp, dfpay, m, dco, dcpn, dpv, dbook};
-        rc = YS::enqueue(w, ctx, c, dwork, stream);
-    }
-    if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book_pv, dbook, S * d, hipMemcpyDeviceToHost, stream);
-    return YS::finish_blocking(w, rc, e, stream, base);
+    return YS::run_blocking("adr_yoy_scenario_pv", ctx, h);
 }
 
 int adr_yoy_scenario_pv_host(int disc_method, int K, const double* times, int S_disc, const double* dfs, int infl_method,
                              int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
                              const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
                              const int64_t* cpn_off, const double* cpn, double* pv, double* book_pv, int n_threads) {
-    const std::string w = "adr_yoy_scenario_pv_host";
     const YS::Call c{disc_method, K, times, S_disc, dfs, infl_method, P, T, S_infl, b, S, n, n_fix,
                      fix_off, fix_tp, fix_pay, m, cpn_off, cpn, pv, book_pv};
-    int rc = YS::validate(w, c);
-    if (rc == ADR_OK) rc = YS::check_host_arrays(w, c);
-    if (rc != ADR_OK) return rc;
-    const bool lin = disc_method == ADR_INTERP_LINEAR_FWD_RATES;
-    const int N = P + 1;
-    std::vector<double> tab(dfs, dfs + static_cast<size_t>(S_disc) * K);
-    if (!lin)
-        for (double& v : tab) v = std::log(v);
-    std::vector<double> ix(N), itab(static_cast<size_t>(S_infl) * N);
-    for (int k = 0; k < N; ++k) ix[k] = k ? T[k - 1] : 0.0;
-    for (int s = 0; s < S_infl; ++s)
-        for (int k = 0; k < N; ++k) itab[static_cast<size_t>(s) * N + k] = YS::node_log(T, b + static_cast<size_t>(s) * P, k);
-    const YS::Curves cv{times, ix.data(), K, N, disc_method, infl_method};
-    const int64_t chunks = (n + YS::kChunk - 1) / YS::kChunk;
-    std::vector<double> work(static_cast<size_t>(chunks) * S);
-    const int threads = n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4);
-    adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
-        if (lin) YS::host_chunks<false>(c, cv, tab.data(), itab.data(), work.data(), lo, hi);
-        else YS::host_chunks<true>(c, cv, tab.data(), itab.data(), work.data(), lo, hi);
-    });
-    YS::reduce_chunks(work.data(), chunks, S, book_pv);
-    return ADR_OK;
+    return YS::host_run("adr_yoy_scenario_pv_host", c, n_threads);
+}
+
+int adr_yoy_scenario_subbook_pv(adr_ctx* ctx, int disc_method, int K, const double* times, int S_disc, const double* dfs,
+                                int infl_method, int P, const double* T, int S_infl, const double* b, int S, int64_t n,
+                                int64_t n_fix, const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                                const int64_t* cpn_off, const double* cpn, int64_t B, const int64_t* sub_off, double* pv,
+                                double* sub_pv) {
+    const std::string w = "adr_yoy_scenario_subbook_pv";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    const YS::Call h{disc_method, K, times, S_disc, dfs, infl_method, P, T, S_infl, b, S, n, n_fix,
+                     fix_off, fix_tp, fix_pay, m, cpn_off, cpn, pv, sub_pv};
+    return YS::run_blocking(w, ctx, h, B, sub_off);
+}
+
+int adr_yoy_scenario_subbook_pv_dev(adr_ctx* ctx, int disc_method, int K, const double* times_dev, int S_disc,
+                                    const double* dfs_dev, int infl_method, int P, const double* T_dev, int S_infl,
+                                    const double* b_dev, int S, int64_t n, int64_t n_fix, const int64_t* fix_off_dev,
+                                    const double* fix_tp_dev, const double* fix_pay_dev, int64_t m, const int64_t* cpn_off_dev,
+                                    const double* cpn_dev, int64_t B, const int64_t* plan_dev, double* pv_dev, double* sub_pv_dev,
+                                    double* work_dev, void* stream) {
+    const std::string w = "adr_yoy_scenario_subbook_pv_dev";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    const YS::Call c{disc_method, K, times_dev, S_disc, dfs_dev, infl_method, P, T_dev, S_infl, b_dev, S, n, n_fix,
+                     fix_off_dev, fix_tp_dev, fix_pay_dev, m, cpn_off_dev, cpn_dev, pv_dev, sub_pv_dev};
+    return YS::enqueue(w, ctx, c, work_dev, static_cast<hipStream_t>(stream), B, plan_dev);
+}
+
+int adr_yoy_scenario_subbook_pv_host(int disc_method, int K, const double* times, int S_disc, const double* dfs, int infl_method,
+                                     int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
+                                     const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                                     const int64_t* cpn_off, const double* cpn, int64_t B, const int64_t* sub_off, double* pv,
+                                     double* sub_pv, int n_threads) {
+    const std::string w = "adr_yoy_scenario_subbook_pv_host";
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    const YS::Call c{disc_method, K, times, S_disc, dfs, infl_method, P, T, S_infl, b, S, n, n_fix,
+                     fix_off, fix_tp, fix_pay, m, cpn_off, cpn, pv, sub_pv};
+    return YS::host_run(w, c, n_threads, B, sub_off);
 }
 
 }  // extern "C"

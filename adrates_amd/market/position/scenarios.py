@@ -28,6 +28,10 @@ Sub-books - desks, counterparties, margin accounts - get their P&L vectors from 
 `ScenarioGrid.revalue_sub_books` / `pnl_sub_books` (and the credit forms) take one key per trade and return one row
 per distinct key, each with the bits the whole-book call gives on that sub-book alone; `tail_measures` and
 `ScenarioGrid.sub_book_var_es` turn the rows into VaR and expected shortfall on the device (csrc/subbook.hip).
+YoY books have the same through `revalue_yoy_on_curves_sub_books` and `YoYBook.revalue_sub_books`.
+
+Firm-wide: `combine_sub_book_rows` adds the per-desk rows of the rates, credit and inflation launches by label and
+`allocate_tail` splits the firm's VaR and expected shortfall among the desks (adr_scenario_tail_alloc, csrc/subbook.hip).
 """
 from __future__ import annotations
 
@@ -483,6 +487,84 @@ def revalue_yoy_on_curves(disc_method, times, dfs, infl_method, T, b, swaps_or_b
                                    per_trade=per_trade)
 
 
+def _gather_offsets(off, perm):
+    """``(offsets of the rows perm of a CSR array, gather index of their entries)``."""
+    off = np.asarray(off, dtype=np.int64)
+    length = (off[1:] - off[:-1])[perm]
+    new_off = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+    idx = np.repeat(off[:-1][perm] - new_off[:-1], length) + np.arange(int(new_off[-1]), dtype=np.int64)
+    return new_off, idx
+
+
+@dataclass
+class YoYSubBooks:
+    """`split_yoy_sub_books`' result: the compiled arrays with every sub-book's swaps consecutive, the labels in order of
+    first appearance, ``sub_off [B + 1]`` and ``perm`` (swap ``j`` of the arrays is swap ``perm[j]`` of the caller's; None:
+    left as it was)."""
+    fixed: Optional[tuple]
+    coupons: Optional[dict]
+    labels: list
+    sub_off: np.ndarray
+    perm: Optional[np.ndarray] = None
+
+
+def split_yoy_sub_books(fixed, coupons, keys) -> YoYSubBooks:
+    """Cut a compiled YoY book (`yoy_book_arrays`' pair) into sub-books by ``keys``, one hashable value per swap,
+    labelled in order of first appearance.  The swaps are stably sorted by label, so a sub-book's swaps keep the order
+    they have in the caller's list - the order the whole-book call gives that sub-book alone."""
+    keys = list(keys)
+    if fixed is None and coupons is None:
+        raise LibError("neither fixed legs nor YoY coupons")
+    n = (np.asarray(fixed[0]) if fixed is not None else np.asarray(coupons["cpn_off"])).size - 1
+    if len(keys) != n:
+        raise LibError(f"keys needs one entry per swap ({n}), not {len(keys)}")
+    labels, index = [], {}
+    for k in keys:
+        if k not in index:
+            index[k] = len(labels)
+            labels.append(k)
+    code = np.array([index[k] for k in keys], dtype=np.int64)
+    perm = np.argsort(code, kind="stable")
+    sub_off = np.searchsorted(code[perm], np.arange(len(labels) + 1), side="left").astype(np.int64)
+    if np.array_equal(perm, np.arange(n)):
+        return YoYSubBooks(fixed, coupons, labels, sub_off)
+    if fixed is not None:
+        off, idx = _gather_offsets(fixed[0], perm)
+        fixed = (off, np.asarray(fixed[1], dtype=np.float64)[idx], np.asarray(fixed[2], dtype=np.float64)[idx])
+    if coupons is not None:
+        off, idx = _gather_offsets(coupons["cpn_off"], perm)
+        coupons = dict({k: np.asarray(coupons[k], dtype=np.float64)[idx] for k in _native.YOY_FIELDS}, cpn_off=off)
+    return YoYSubBooks(fixed, coupons, labels, sub_off, perm)
+
+
+def _finish_yoy_sub_books(out, sb: YoYSubBooks, per_trade):
+    """The labels, and the per-swap rows back in the caller's order."""
+    out["labels"] = sb.labels
+    if per_trade and sb.perm is not None:
+        back = np.empty_like(out["pv"])
+        back[:, sb.perm] = out["pv"]
+        out["pv"] = back
+    return out
+
+
+def revalue_yoy_on_curves_sub_books(disc_method, times, dfs, infl_method, T, b, swaps_or_book, keys, value_dt, per_trade=False,
+                                    ctx=None, host=False):
+    """`revalue_yoy_on_curves` per sub-book, in ONE launch: ``keys`` holds one hashable value per swap (a desk, a
+    counterparty, an account).  Returns ``{"labels": [...], "sub_pv": [B, S]}`` - the labels in order of first appearance,
+    row ``b`` the PV vector of sub-book ``labels[b]``, bit for bit what `revalue_yoy_on_curves` gives on that sub-book
+    alone - and, with ``per_trade``, ``"pv": [S, n]`` in the caller's order."""
+    dm, im = int(getattr(disc_method, "value", disc_method)), int(getattr(infl_method, "value", infl_method))
+    if dm not in _SUPPORTED_INTERP or im not in (InterpTypes.LINEAR_ZERO_RATES.value, InterpTypes.FLAT_FWD_RATES.value):
+        raise LibError("Invalid interpolation scheme.")
+    sb = split_yoy_sub_books(*yoy_book_arrays(swaps_or_book, value_dt), keys)
+    if host:
+        out = _native.yoy_scenario_subbook_pv_host(dm, times, dfs, im, T, b, sb.fixed, sb.coupons, sb.sub_off, per_trade=per_trade)
+    else:
+        out = _native.yoy_scenario_subbook_pv(ctx or _native.default_context(), dm, times, dfs, im, T, b, sb.fixed, sb.coupons,
+                                              sb.sub_off, per_trade=per_trade)
+    return _finish_yoy_sub_books(out, sb, per_trade)
+
+
 def _tail(pnl, level):
     pnl = np.sort(np.asarray(pnl, dtype=np.float64).reshape(-1))
     if pnl.size == 0 or not 0.0 < level < 1.0:
@@ -531,6 +613,85 @@ def tail_measures(rows, level: float = 0.99, base_col: int = -1, host: bool = Fa
     if host:
         return _native.scenario_tail_host(rows, k, base_col)
     return _native.scenario_tail(ctx or _native.default_context(), rows, k, base_col)
+
+
+def _allocate_tail_numpy(rows, k, base_col):
+    """adr_scenario_tail_alloc's rule in NumPy, sum for sum: the same bits as the kernel and its host twin."""
+    pnl = rows if base_col < 0 else np.delete(rows, base_col, axis=1) - rows[:, base_col:base_col + 1]
+    B, m = pnl.shape
+    slots = np.zeros((64, m))
+    for r in range(B):                                  # row r to slot r % 64, in row order from 0.0
+        slots[r % 64] = slots[r % 64] + pnl[r]
+    h = 32
+    while h >= 1:
+        slots[:h] = slots[:h] + slots[h:2 * h]
+        h //= 2
+    tot = slots[0]
+    if np.any(np.isnan(tot)):
+        return {"var": np.nan, "es": np.nan, "comp_var": np.full(B, np.nan), "comp_es": np.full(B, np.nan)}
+    bits = tot.view(np.int64)
+    key = bits ^ ((bits >> 63) & np.int64(0x7FFFFFFFFFFFFFFF))       # the tail kernel's total order: -0.0 before +0.0
+    order = np.lexsort((np.arange(m), key))[:k]
+    es, comp = 0.0, np.zeros(B)
+    for e in order:
+        es = es + tot[e]
+        comp = comp + pnl[:, e]
+    return {"var": float(-tot[order[-1]]), "es": float(-es / float(k)), "comp_var": -pnl[:, order[-1]],
+            "comp_es": -comp / float(k)}
+
+
+def allocate_tail(rows, level: float = 0.99, base_col: int = -1, host: bool = False, ctx=None):
+    """The firm's tail and how much of it every row carries - the Euler allocation of VaR and expected shortfall to the
+    desks, in one chain of kernels (adr_scenario_tail_alloc; ``host=True``: its CPU twin, the same bits).
+
+    ``rows [B, S]``: one row per desk, as `pnl_sub_books` or `combine_sub_book_rows` give them; ``base_col`` as in
+    `tail_measures`.  With ``k = tail_count(level, S)`` and the scenarios ordered by the FIRM's P&L (the column sums in a
+    fixed order; ties go to the earlier scenario), ``var`` and ``es`` are the firm's `historical_var` and expected
+    shortfall, ``comp_var [B]`` every row's loss in the firm's ``k``-th worst scenario and ``comp_es [B]`` its mean loss
+    over the firm's ``k`` worst: ``comp_es`` sums to ``es`` and ``comp_var`` to ``var`` up to rounding.  A NaN anywhere
+    gives NaN everywhere.  Rows wider than ``_native.SCENARIO_ALLOC_MAX`` P&L values do not fit the kernel's LDS and are
+    done by NumPy under the same rule."""
+    rows = np.ascontiguousarray(np.atleast_2d(np.asarray(rows, dtype=np.float64)))
+    if rows.ndim != 2 or rows.shape[0] < 1 or not -1 <= base_col < rows.shape[1]:
+        raise LibError(f"rows must have shape [n_rows, n_columns] and base_col be -1 or a column, not {list(rows.shape)}, {base_col}")
+    m = rows.shape[1] - (1 if base_col >= 0 else 0)
+    k = tail_count(level, m)
+    if m > _native.SCENARIO_ALLOC_MAX:
+        return _allocate_tail_numpy(rows, k, base_col)
+    if host:
+        return _native.scenario_tail_alloc_host(rows, k, base_col)
+    return _native.scenario_tail_alloc(ctx or _native.default_context(), rows, k, base_col)
+
+
+def combine_sub_book_rows(parts):
+    """One row per label across several sub-book results: ``parts`` is a list of ``(labels, rows [B_i, S])`` - the
+    ``labels`` and ``sub_pv`` (or P&L rows) of the rates, credit and YoY sub-book calls on the same scenarios.  Returns
+    ``{"labels": [...], "rows": [B, S]}`` with the labels in order of first appearance across the parts; a label's row is
+    its first part's row with the later parts' rows added in list order, so a label found in one part only keeps that
+    part's bits."""
+    labels, index, out = [], {}, []
+    width = None
+    for i, (labs, rows) in enumerate(parts):
+        rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+        labs = list(labs)
+        if rows.ndim != 2 or rows.shape[0] != len(labs):
+            raise LibError(f"part {i}: {len(labs)} labels for rows of shape {list(rows.shape)}")
+        if width is None:
+            width = rows.shape[1]
+        if rows.shape[1] != width:
+            raise LibError(f"part {i} has {rows.shape[1]} columns, the parts before it {width}: the scenarios must be the same")
+        if len(set(labs)) != len(labs):
+            raise LibError(f"part {i} names a label twice")
+        for lab, row in zip(labs, rows):
+            if lab not in index:
+                index[lab] = len(labels)
+                labels.append(lab)
+                out.append(row.copy())
+            else:
+                out[index[lab]] = out[index[lab]] + row
+    if not out:
+        raise LibError("no parts to combine")
+    return {"labels": labels, "rows": np.stack(out)}
 
 
 class ScenarioGrid:

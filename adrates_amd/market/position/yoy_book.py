@@ -16,7 +16,8 @@ from ...utils.error import LibError
 from ...utils.global_types import RequestTypes
 from .engine import Engine
 from .inflation_engine import inflation_inputs, price_yoy, yoy_curves
-from .scenarios import revalue_yoy_on_curves, shocked_breakevens, yoy_book_arrays
+from .scenarios import (revalue_yoy_on_curves, revalue_yoy_on_curves_sub_books, shocked_breakevens, split_yoy_sub_books,
+                        tail_count, yoy_book_arrays, _finish_yoy_sub_books)
 
 
 def tile_yoy_book(book: dict, reps: int) -> dict:
@@ -158,3 +159,102 @@ class YoYBook:
         book = revalue_yoy_on_curves(self.curve._interp_type.value, times, dfs, im, T, rows, self._arrays(),
                                      self.model.value_dt, ctx=ctx)["book_pv"]
         return book[:-1] - book[-1]
+
+    # ---------------------------------------------------------------------------------------------------- sub-books
+    def _sub_books_on_device(self, ctx, sb, method, times, dfs, b, per_trade=False, tail=None):
+        """One launch of adr_yoy_scenario_subbook_pv_dev on the ctx's own stream.  ``times`` / ``dfs``: host arrays
+        (``dfs [S_disc, K]``) or device pointers ``(K, S_disc, times_ptr, dfs_ptr)``; ``b [S_infl, P]``.  ``tail``:
+        ``(base_col, k)`` chains adr_scenario_tail_dev behind it and returns ``(var, es)``; the rows then stay on the
+        device."""
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        fixed, book = sb.fixed, sb.coupons
+        cpn_off, cpn = _native.yoy_pack(book)
+        im, T, _ = inflation_inputs(self.inflation_curve)
+        n, B = cpn_off.size - 1, sb.sub_off.size - 1
+        held = dict(T=up(T), b=up(b), fix_off=up(fixed[0]), fix_tp=up(fixed[1]), fix_pay=up(fixed[2]), cpn_off=up(cpn_off),
+                    cpn=up(cpn), plan=up(_native.scenario_subbook_plan(n, sb.sub_off)))
+        if isinstance(times, tuple):
+            K, S_disc, times_ptr, dfs_ptr = times
+        else:
+            held.update(times=up(np.asarray(times, dtype=np.float64)), dfs=up(np.atleast_2d(np.asarray(dfs, dtype=np.float64))))
+            K, S_disc = held["times"].numel(), held["dfs"].shape[0]
+            times_ptr, dfs_ptr = held["times"].data_ptr(), held["dfs"].data_ptr()
+        S = max(S_disc, b.shape[0])
+        ptrs = {k: v.data_ptr() if v.numel() else 0 for k, v in held.items()}
+        ptrs.update(times=times_ptr, dfs=dfs_ptr)
+        sub = torch.empty((B, S), dtype=torch.float64, device=dev)
+        pv = torch.empty((n, S), dtype=torch.float64, device=dev) if per_trade else None
+        work = torch.empty(_native.scenario_subbook_work(n, B, S), dtype=torch.float64, device=dev)
+        var_es = torch.empty((2, B), dtype=torch.float64, device=dev) if tail else None
+        torch.cuda.synchronize(dev)
+        _native.yoy_scenario_subbook_pv_dev(ctx, method, K, S_disc, im, T.size, b.shape[0], S, n, fixed[1].size, cpn.shape[1], B,
+                                            ptrs, sub.data_ptr(), work.data_ptr(), pv.data_ptr() if per_trade else 0)
+        if tail:
+            _native.scenario_tail_dev(ctx, B, S, sub.data_ptr(), tail[1], var_es[0].data_ptr(), var_es[1].data_ptr(),
+                                      base_col=tail[0])
+        ctx.sync()
+        if tail:
+            out = var_es.cpu().numpy()
+            return out[0].copy(), out[1].copy()
+        out = {"sub_pv": sub.cpu().numpy()}
+        if per_trade:
+            out["pv"] = pv.cpu().numpy().T
+        return out
+
+    def _split(self, keys):
+        return split_yoy_sub_books(*self._arrays(), keys)
+
+    def _base_pair(self, grid, b):
+        """``(times, dfs, breakeven rows, ctx)`` with the unshocked pair appended as one more scenario, as `pnl` does."""
+        _, _, b0 = inflation_inputs(self.inflation_curve)
+        if grid is not None:
+            times, dfs, ctx = grid.base.times, np.vstack([grid._dfs(), grid.base.dfs[None, :]]), grid._ctx
+        else:
+            cur = self._engine._device_curve(self.curve)
+            times, dfs, ctx = cur["host"].times, cur["host"].dfs, cur["ctx"]
+        return times, dfs, (b0 if b is None else np.vstack([b, b0[None, :]])), ctx
+
+    def revalue_sub_books(self, keys, grid=None, inflation_shocks=None, breakevens=None, per_trade: bool = False) -> dict:
+        """`revalue` per sub-book, in the SAME single launch: ``keys`` holds one hashable value per swap (a desk, a
+        counterparty, a margin account).  Returns ``{"labels": [...], "sub_pv": [B, S]}`` - the labels in order of first
+        appearance, row ``b`` bit for bit `revalue`'s ``book_pv`` of a `YoYBook` holding sub-book ``labels[b]`` alone - and,
+        with ``per_trade``, ``"pv": [S, n]`` in the book's order.  Scenarios: see `revalue`."""
+        b = self._breakeven_rows(grid, inflation_shocks, breakevens)
+        im, T, b0 = inflation_inputs(self.inflation_curve)
+        if grid is not None:
+            sb = self._split(keys)
+            arr = _native.curve_set_arrays(grid._set)
+            out = self._sub_books_on_device(grid._ctx, sb, arr["method"], (arr["K"], arr["S"], arr["times"], arr["dfs"]), None,
+                                            b0[None, :] if b is None else b, per_trade)
+            return _finish_yoy_sub_books(out, sb, per_trade)
+        cur = self._engine._device_curve(self.curve)
+        return revalue_yoy_on_curves_sub_books(self.curve._interp_type.value, cur["host"].times, cur["host"].dfs, im, T, b,
+                                               self._arrays(), keys, self.model.value_dt, per_trade=per_trade, ctx=cur["ctx"])
+
+    def pnl_sub_books(self, keys, grid=None, inflation_shocks=None, breakevens=None) -> np.ndarray:
+        """``[B, S]``: `pnl` per sub-book (rows in the order of `revalue_sub_books`' labels).  The unshocked pair is priced
+        as one more column of the same launch, so a zero shock is exactly 0 in every row."""
+        b = self._breakeven_rows(grid, inflation_shocks, breakevens)
+        im, T, _ = inflation_inputs(self.inflation_curve)
+        times, dfs, rows, ctx = self._base_pair(grid, b)
+        sub = revalue_yoy_on_curves_sub_books(self.curve._interp_type.value, times, dfs, im, T, rows, self._arrays(), keys,
+                                              self.model.value_dt, ctx=ctx)["sub_pv"]
+        return sub[:, :-1] - sub[:, -1:]
+
+    def sub_book_var_es(self, keys, level: float = 0.99, grid=None, inflation_shocks=None, breakevens=None) -> dict:
+        """``{"labels": [...], "var": [B], "es": [B]}``: the sub-book launch and the tail kernel chained on one stream, so
+        the ``[B, S]`` matrix never leaves the device.  The P&L is `pnl_sub_books`'; ``var`` and ``es`` are
+        `tail_measures`'."""
+        b = self._breakeven_rows(grid, inflation_shocks, breakevens)
+        times, dfs, rows, ctx = self._base_pair(grid, b)
+        rows, dfs = np.atleast_2d(rows), np.atleast_2d(dfs)
+        S = max(rows.shape[0], dfs.shape[0]) - 1
+        if S > _native.SCENARIO_TAIL_MAX:
+            raise LibError(f"{S} scenarios: at most {_native.SCENARIO_TAIL_MAX} fit the tail kernel; use pnl_sub_books and "
+                           "tail_measures")
+        sb = self._split(keys)
+        var, es = self._sub_books_on_device(ctx, sb, self.curve._interp_type.value, times, dfs, rows,
+                                            tail=(S, tail_count(level, S)))
+        return {"labels": sb.labels, "var": var, "es": es}

@@ -118,6 +118,17 @@ credit_pnl = grid.pnl_credit(bonds, z, issuers, spread_moves)
 print(f"300 bonds x 250 joint scenarios: 99% VaR {historical_var(credit_pnl, 0.99):,.0f}, 97.5% ES "
       f"{expected_shortfall(credit_pnl, 0.975):,.0f}; rates alone: 99% VaR "
       f"{historical_var(grid.pnl_credit(bonds, z, issuers), 0.99):,.0f}")
+
+# ---- firm-wide: desks across the OIS book and the YoY book, their P&L rows added by label, the firm's ES split among them
+from adrates_amd.market.position.scenarios import allocate_tail, combine_sub_book_rows
+yoy_desks = [("desk 0", "desk 1", "inflation desk")[i % 3] for i in range(len(yoy_book))]
+firm = combine_sub_book_rows([                                      # labels are numbered by first appearance in each call
+    (list(dict.fromkeys(desks)), grid.pnl_sub_books(book_swaps, desks)),
+    (list(dict.fromkeys(yoy_desks)), yoy_book.pnl_sub_books(yoy_desks, grid=grid, inflation_shocks=breakeven_moves))])
+alloc = allocate_tail(firm["rows"], level=0.975)                    # the Euler allocation: each desk's mean loss in the firm's tail
+top = int(np.argmax(alloc["comp_es"]))
+print(f"{len(firm['labels'])} desks across rates and inflation: firm 97.5% ES {alloc['es']:,.0f} GBP = sum of the desks' shares "
+      f"{alloc['comp_es'].sum():,.0f}; the largest share {alloc['comp_es'][top]:,.0f} ({firm['labels'][top]})")
 grid.close()
 
 # ---- a million trades from their terms, without a million Python objects

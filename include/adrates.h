@@ -750,6 +750,65 @@ int adr_scenario_tail_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows
                           double* es_dev, void* stream);
 int adr_scenario_tail_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es);
 
+/*
+ * YoY sub-books: adr_yoy_scenario_pv* per sub-book in one launch.  The entries take what adr_yoy_scenario_pv* take plus
+ * B >= 1, sub_off[B + 1] (sub-book b holds the swaps sub_off[b] .. sub_off[b + 1]; from 0 to n, not decreasing, empty
+ * sub-books allowed) and sub_pv[B][S], under the contract of the sub-book entries above, word for word: sub_pv[b][s]
+ * has exactly the bits of adr_yoy_scenario_pv's book_pv[s] on a batch holding sub-book b's swaps alone - chunks of 64
+ * swaps from sub_off[b], the sub-book's chunk j to slot j % 64 in order, then the halving tree, no atomics; an empty
+ * sub-book gives +0.0; a row does not depend on B, on the other sub-books, on S or on whether the discount table is in
+ * LDS; pv[n][S], when given, has the parent's bits.  The blocking and the _host entries check the offsets
+ * (ADR_ERR_INVALID naming the sub-book) and build the plan themselves.  The _dev entry takes the uploaded plan of
+ * adr_scenario_subbook_plan and adr_scenario_subbook_work(n, B, S) doubles of scratch, enqueues three kernels on
+ * `stream` without allocation or synchronisation and checks scalars only: a plan whose bounds leave 0 .. n is cut to
+ * that range, one with more chunks than the scratch holds is cut there.
+ */
+int adr_yoy_scenario_subbook_pv(adr_ctx* ctx, int disc_method, int K, const double* times, int S_disc, const double* dfs,
+                                int infl_method, int P, const double* T, int S_infl, const double* b, int S, int64_t n,
+                                int64_t n_fix, const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                                const int64_t* cpn_off, const double* cpn, int64_t B, const int64_t* sub_off, double* pv,
+                                double* sub_pv);
+int adr_yoy_scenario_subbook_pv_dev(adr_ctx* ctx, int disc_method, int K, const double* times_dev, int S_disc,
+                                    const double* dfs_dev, int infl_method, int P, const double* T_dev, int S_infl,
+                                    const double* b_dev, int S, int64_t n, int64_t n_fix, const int64_t* fix_off_dev,
+                                    const double* fix_tp_dev, const double* fix_pay_dev, int64_t m, const int64_t* cpn_off_dev,
+                                    const double* cpn_dev, int64_t B, const int64_t* plan_dev, double* pv_dev, double* sub_pv_dev,
+                                    double* work_dev, void* stream);
+int adr_yoy_scenario_subbook_pv_host(int disc_method, int K, const double* times, int S_disc, const double* dfs, int infl_method,
+                                     int P, const double* T, int S_infl, const double* b, int S, int64_t n, int64_t n_fix,
+                                     const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                                     const int64_t* cpn_off, const double* cpn, int64_t B, const int64_t* sub_off, double* pv,
+                                     double* sub_pv, int n_threads);
+
+/*
+ * Tail allocation: how much of the FIRM's VaR and expected shortfall each row (desk) carries - the Euler allocation, the
+ * one that adds up to the firm's figure.  rows[B][S_tot], base_col and k as in adr_scenario_tail; pnl[b][e] is P&L value
+ * e of row b (every other column minus base_col, or the row itself when base_col = -1).
+ *
+ *   tot[e]  = sum_b pnl[b][e] in a fixed order: row b to slot b % 64, each slot added in row order from 0.0, then slots
+ *             0-31 += 32-63, ..., 0 += 1.
+ *   e_1 ..  = the scenarios ordered by (key(tot[e]), e) ascending: adr_scenario_tail's total order of the doubles
+ *             (-0.0 before +0.0), ties to the lower scenario index.
+ *   var_tot = -tot[e_k];       es_tot     = -(tot[e_1] + .. + tot[e_k]) / k, added in that order from 0.0
+ *   comp_var[b] = -pnl[b][e_k]; comp_es[b] = -(pnl[b][e_1] + .. + pnl[b][e_k]) / k, in the same order from 0.0
+ *
+ * If any tot[e] is NaN every output is NaN.  var_tot and es_tot are adr_scenario_tail's var and es of the one-row matrix
+ * tot, bit for bit; sum_b comp_es[b] = es_tot and sum_b comp_var[b] = var_tot up to the rounding of the sums.  No
+ * atomics, no interpolation.  The ordering is a bitonic network over (key, index) pairs of 16 bytes in LDS, so rows of
+ * more than ADR_SCENARIO_ALLOC_MAX P&L values are ADR_ERR_UNSUPPORTED.  adr_scenario_tail_alloc: host arrays, blocks;
+ * _dev: device arrays on `stream` (NULL: the ctx's own), work_dev holds S_tot doubles, no allocation and no
+ * synchronisation (three kernels in one chain); _host: the CPU twin, the same sums in the same order, hence the same
+ * bits.
+ */
+#define ADR_SCENARIO_ALLOC_MAX 8192
+int adr_scenario_tail_alloc(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, double* var_tot,
+                            double* es_tot, double* comp_var, double* comp_es);
+int adr_scenario_tail_alloc_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k,
+                                double* var_tot_dev, double* es_tot_dev, double* comp_var_dev, double* comp_es_dev,
+                                double* work_dev, void* stream);
+int adr_scenario_tail_alloc_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var_tot, double* es_tot,
+                                 double* comp_var, double* comp_es);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
