@@ -20,6 +20,7 @@ _LIB_PATH = os.environ.get("ADRATES_HIP_LIB") or os.path.join(os.path.dirname(os
 _lib = None
 
 REQ_VALUE, REQ_DELTA, REQ_GAMMA = 1, 2, 4
+ADR_ERR_UNSUPPORTED = -2     # a `LibError` raised by `_check` carries the library's code as ``status``
 MAX_PILLARS = 256            # ADR_MAX_PILLARS (uploaded curves); the device curve builder: 64
 
 _dp = C.POINTER(C.c_double)
@@ -181,7 +182,7 @@ def load():
 def _check(rc: int, what: str):
     if rc < 0:
         msg = load().adr_last_error().decode("utf-8", "replace")
-        raise LibError(f"{what} failed ({rc}): {msg}")
+        raise LibError(f"{what} failed ({rc}): {msg}", status=rc)
     return rc
 
 
@@ -375,6 +376,12 @@ class DeviceTrades:
         if getattr(self, "_h", None):
             load().adr_free_trades(self._h)
             self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
@@ -798,23 +805,64 @@ def _scenario_curves(times, dfs):
     return times, dfs
 
 
-def _scenario_result(book, pv, per_trade):
-    out = {"book_pv": book}
+# The scenario entries share one argument list, in this order: the curves (host arrays, or a context and a `CurveSet`), the
+# credit scenario group, the trades (a handle, or the host arrays of a `TradeBatch`), the credit per-trade group, the
+# sub-books, then ``pv``, the output and, on the host, ``n_threads``.  One helper per group returns its arguments.
+def _curve_args(method, times, dfs):
+    return [int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs)]
+
+
+def _spread_args(dz):
+    return [dz.shape[1], dz.shape[0], _ptr(dz) if dz.size else None]
+
+
+def _batch_args(n, fo, lo, a, w):
+    """`_batch_arrays`' result as the _host entries take it."""
+    p = lambda *names: [_ptr(a[k]) for k in names]
+    return ([n, _ptr(fo, _i64p), _ptr(lo, _i64p)] + p("fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha") + [_ptr(w)] +
+            p("notional", "spread", "fix_sign", "flt_sign"))
+
+
+def _credit_trade_args(z, bucket, fix_tau, flt_tau, counts):
+    """``counts``: beside a trades handle the entries take the two flow counts, beside host arrays they know them."""
+    if counts:
+        return [_ptr(z), _ptr(bucket, _i32p), fix_tau.size, _ptr(fix_tau), flt_tau.size, _ptr(flt_tau)]
+    return [_ptr(z), _ptr(bucket, _i32p), _ptr(fix_tau), _ptr(flt_tau)]
+
+
+def _scenario_call(fn, args, n, S, per_trade, sub=None, tail=()):
+    """Call a blocking or host scenario entry with ``args``, the sub-book group of ``sub`` (`_sub_offsets`' pair; None: the
+    whole book), the outputs it allocates and ``tail``: ``book_pv [S]`` or ``sub_pv [B, S]`` and, with ``per_trade``,
+    ``pv [S, n]``."""
+    pv = np.empty((n, S)) if per_trade else None
+    if sub is None:
+        key, out = "book_pv", np.empty(S)
+    else:
+        key, out = "sub_pv", np.empty((sub[1], S))
+        args = args + [sub[1], _ptr(sub[0], _i64p)]
+    _check(fn(*args, _ptr(pv), _ptr(out), *tail), fn.__name__)
+    res = {key: out}
     if per_trade:
-        out["pv"] = pv.T                # the library's rows are per trade ([n, S]); a view, no copy
-    return out
+        res["pv"] = pv.T                # the library's rows are per trade ([n, S]); a view, no copy
+    return res
+
+
+def _dev(p):
+    """A device pointer given as an integer (0: none) as the ``_dev`` entries take it."""
+    return _vp(int(p) or None)
+
+
+def _dev_of(ptrs):
+    """The same by name, from a mapping of names to device pointers (a name left out: none)."""
+    return lambda k: _dev(ptrs.get(k, 0))
 
 
 def scenario_pv(ctx: Context, method: int, times, dfs, trades: DeviceTrades, per_trade=False):
     """PVs of an uploaded batch under the scenario curves ``dfs [S, K]`` on the knots ``times [K]`` (adr_scenario_pv,
     blocking): ``book_pv [S]`` and, with ``per_trade``, ``pv [S, n]``."""
     times, dfs = _scenario_curves(times, dfs)
-    S, n = dfs.shape[0], trades.n_trades
-    book = np.empty(S)
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_scenario_pv(ctx._h, int(method), times.size, _ptr(times), S, _ptr(dfs), trades._h, _ptr(pv),
-                                  _ptr(book)), "adr_scenario_pv")
-    return _scenario_result(book, pv, per_trade)
+    return _scenario_call(load().adr_scenario_pv, [ctx._h] + _curve_args(method, times, dfs) + [trades._h], trades.n_trades,
+                          dfs.shape[0], per_trade)
 
 
 def _batch_arrays(batch):
@@ -837,25 +885,15 @@ def scenario_pv_host(method: int, times, dfs, batch, per_trade=False, n_threads=
     """`scenario_pv` on the CPU (adr_scenario_pv_host) for a `TradeBatch`: the same per-trade arithmetic and the same
     order of the book sum; no GPU needed."""
     times, dfs = _scenario_curves(times, dfs)
-    n, fo, lo, a, w = _batch_arrays(batch)
-    S = dfs.shape[0]
-    book = np.empty(S)
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_scenario_pv_host(int(method), times.size, _ptr(times), S, _ptr(dfs), n, _ptr(fo, _i64p), _ptr(lo, _i64p),
-                                       _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]), _ptr(a["flt_ts"]),
-                                       _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w), _ptr(a["notional"]), _ptr(a["spread"]),
-                                       _ptr(a["fix_sign"]), _ptr(a["flt_sign"]), _ptr(pv), _ptr(book), int(n_threads)),
-           "adr_scenario_pv_host")
-    return _scenario_result(book, pv, per_trade)
+    arrays = _batch_arrays(batch)
+    return _scenario_call(load().adr_scenario_pv_host, _curve_args(method, times, dfs) + _batch_args(*arrays), arrays[0],
+                          dfs.shape[0], per_trade, tail=(int(n_threads),))
 
 
 def scenario_pv_set(ctx: Context, curve_set: CurveSet, trades: DeviceTrades, per_trade=False):
     """`scenario_pv` on the curves of a `CurveSet`, read where the device builder left them (adr_scenario_pv_set)."""
-    S, n = len(curve_set), trades.n_trades
-    book = np.empty(S)
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_scenario_pv_set(ctx._h, curve_set._h, trades._h, _ptr(pv), _ptr(book)), "adr_scenario_pv_set")
-    return _scenario_result(book, pv, per_trade)
+    return _scenario_call(load().adr_scenario_pv_set, [ctx._h, curve_set._h, trades._h], trades.n_trades, len(curve_set),
+                          per_trade)
 
 
 def curve_set_arrays(curve_set: CurveSet) -> dict:
@@ -875,9 +913,8 @@ def scenario_pv_dev(ctx: Context, method: int, K: int, times_ptr: int, S: int, d
                     book_ptr: int, work_ptr: int, pv_ptr: int = 0, stream=0):
     """Non-blocking form (adr_scenario_pv_dev): device pointers (integers) of ``times`` [K], ``dfs`` [S, K], the outputs
     ``book_pv`` [S] and ``pv`` [n, S] (trade-major; 0: not wanted) and `scenario_pv_work` doubles of scratch."""
-    v = lambda p: _vp(int(p) or None)
-    _check(load().adr_scenario_pv_dev(ctx._h, int(method), int(K), v(times_ptr), int(S), v(dfs_ptr), trades._h, v(pv_ptr),
-                                      v(book_ptr), v(work_ptr), _vp(stream or None)), "adr_scenario_pv_dev")
+    _check(load().adr_scenario_pv_dev(ctx._h, int(method), int(K), _dev(times_ptr), int(S), _dev(dfs_ptr), trades._h,
+                                      _dev(pv_ptr), _dev(book_ptr), _dev(work_ptr), _vp(stream or None)), "adr_scenario_pv_dev")
 
 
 def _yoy_scenario_inputs(times, dfs, T, b, fixed, book):
@@ -910,15 +947,15 @@ def _yoy_scenario_inputs(times, dfs, T, b, fixed, book):
     return times, dfs, T, b, S, fix_off, fix_tp, fix_pay, cpn_off, cpn
 
 
-def _yoy_scenario_call(fn, head, tail, disc_method, times, dfs, infl_method, T, b, fixed, book, per_trade):
+def _yoy_scenario_call(fn, head, tail, disc_method, times, dfs, infl_method, T, b, fixed, book, per_trade, *sub_off):
+    """The four blocking and host YoY entries: ``head`` the context or nothing, ``tail`` ``n_threads`` or nothing,
+    ``sub_off`` given for the sub-book entries."""
     times, dfs, T, b, S, fix_off, fix_tp, fix_pay, cpn_off, cpn = _yoy_scenario_inputs(times, dfs, T, b, fixed, book)
+    sub = _sub_offsets(*sub_off) if sub_off else None
     n = fix_off.size - 1
-    out_book = np.empty(S)
-    pv = np.empty((n, S)) if per_trade else None
-    _check(fn(*head, int(disc_method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), int(infl_method), T.size, _ptr(T),
-              b.shape[0], _ptr(b), S, n, fix_tp.size, _ptr(fix_off, _i64p), _ptr(fix_tp), _ptr(fix_pay), cpn.shape[1],
-              _ptr(cpn_off, _i64p), _ptr(cpn), _ptr(pv), _ptr(out_book), *tail), fn.__name__)
-    return _scenario_result(out_book, pv, per_trade)
+    args = [*head, *_curve_args(disc_method, times, dfs), int(infl_method), T.size, _ptr(T), b.shape[0], _ptr(b), S, n,
+            fix_tp.size, _ptr(fix_off, _i64p), _ptr(fix_tp), _ptr(fix_pay), cpn.shape[1], _ptr(cpn_off, _i64p), _ptr(cpn)]
+    return _scenario_call(fn, args, n, S, per_trade, sub, tail)
 
 
 def yoy_scenario_pv(ctx: Context, disc_method: int, times, dfs, infl_method: int, T, b, fixed, book, per_trade=False):
@@ -949,12 +986,11 @@ def yoy_scenario_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: int, inf
     [S_infl, P], ``fix_off``, ``fix_tp``, ``fix_pay``, ``cpn_off`` and ``cpn`` to device pointers (integers; the value
     arrays of an empty leg may be 0); outputs ``book_pv`` [S] and ``pv`` [n, S] (swap-major; 0: not wanted);
     `yoy_scenario_pv_work` doubles of scratch."""
-    v = lambda p: _vp(int(p) or None)
-    g = lambda k: v(ptrs.get(k, 0))
+    g = _dev_of(ptrs)
     _check(load().adr_yoy_scenario_pv_dev(ctx._h, int(disc_method), int(K), g("times"), int(S_disc), g("dfs"), int(infl_method),
                                           int(P), g("T"), int(S_infl), g("b"), int(S), int(n_swaps), int(n_fix), g("fix_off"),
-                                          g("fix_tp"), g("fix_pay"), int(n_coupons), g("cpn_off"), g("cpn"), v(pv_ptr),
-                                          v(book_ptr), v(work_ptr), _vp(stream or None)), "adr_yoy_scenario_pv_dev")
+                                          g("fix_tp"), g("fix_pay"), int(n_coupons), g("cpn_off"), g("cpn"), _dev(pv_ptr),
+                                          _dev(book_ptr), _dev(work_ptr), _vp(stream or None)), "adr_yoy_scenario_pv_dev")
 
 
 CREDIT_MAX_BUCKETS = 32                                     # ADR_CREDIT_MAX_BUCKETS
@@ -985,59 +1021,63 @@ def _credit_counts(n_disc, n_spr):
     return S
 
 
+def _credit_call(fn, ctx, method, times, dfs, dz, trades, z, bucket, fix_tau, flt_tau, per_trade, *sub_off):
+    """The two blocking credit entries on host curves and an uploaded batch; ``sub_off`` given for the sub-book entry."""
+    times, dfs = _scenario_curves(times, dfs)
+    sub = _sub_offsets(*sub_off) if sub_off else None
+    n = trades.n_trades
+    dz, *per = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
+    S = _credit_counts(dfs.shape[0], dz.shape[0])
+    args = [ctx._h] + _curve_args(method, times, dfs) + _spread_args(dz) + [S, trades._h] + _credit_trade_args(*per, counts=True)
+    return _scenario_call(fn, args, n, S, per_trade, sub)
+
+
+def _credit_set_call(fn, ctx, curve_set, dz, trades, z, bucket, fix_tau, flt_tau, per_trade, *sub_off):
+    """The same on the curves of a `CurveSet`."""
+    sub = _sub_offsets(*sub_off) if sub_off else None
+    n, S = trades.n_trades, len(curve_set)
+    dz, *per = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
+    if dz.shape[0] not in (1, S):
+        raise LibError(f"{dz.shape[0]} spread-shock rows for a set of {S} curves: one shared row or one row per curve")
+    args = [ctx._h, curve_set._h] + _spread_args(dz) + [trades._h] + _credit_trade_args(*per, counts=True)
+    return _scenario_call(fn, args, n, S, per_trade, sub)
+
+
+def _credit_host_call(fn, method, times, dfs, dz, batch, z, bucket, fix_tau, flt_tau, per_trade, n_threads, *sub_off):
+    """The same on the CPU for a `TradeBatch`."""
+    times, dfs = _scenario_curves(times, dfs)
+    sub = _sub_offsets(*sub_off) if sub_off else None
+    arrays = _batch_arrays(batch)
+    n, a = arrays[0], arrays[3]
+    dz, *per = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, a["fix_tp"].size, a["flt_tp"].size)
+    S = _credit_counts(dfs.shape[0], dz.shape[0])
+    args = _curve_args(method, times, dfs) + _spread_args(dz) + [S] + _batch_args(*arrays) + _credit_trade_args(*per, counts=False)
+    return _scenario_call(fn, args, n, S, per_trade, sub, (int(n_threads),))
+
+
 def credit_scenario_pv(ctx: Context, method: int, times, dfs, dz, trades: DeviceTrades, z, bucket, fix_tau, flt_tau,
                        per_trade=False):
     """PVs of an uploaded batch under scenario PAIRS (adr_credit_scenario_pv, blocking): discount rows ``dfs`` [S, K] or
     one shared row [K] on the knots ``times``, spread shocks ``dz`` [S, G], one shared row [G] or None; per trade the
     spread ``z`` and the bucket (-1: not shocked), per flow the spread times in the batch's flow order.  Returns
     ``book_pv`` [S] and, with ``per_trade``, ``pv`` [S, n]."""
-    times, dfs = _scenario_curves(times, dfs)
-    n = trades.n_trades
-    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
-    S = _credit_counts(dfs.shape[0], dz.shape[0])
-    book = np.empty(S)
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_credit_scenario_pv(ctx._h, int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), dz.shape[1],
-                                         dz.shape[0], _ptr(dz) if dz.size else None, S, trades._h, _ptr(z), _ptr(bucket, _i32p),
-                                         fix_tau.size, _ptr(fix_tau), flt_tau.size, _ptr(flt_tau), _ptr(pv), _ptr(book)),
-           "adr_credit_scenario_pv")
-    return _scenario_result(book, pv, per_trade)
+    return _credit_call(load().adr_credit_scenario_pv, ctx, method, times, dfs, dz, trades, z, bucket, fix_tau, flt_tau,
+                        per_trade)
 
 
 def credit_scenario_pv_set(ctx: Context, curve_set: CurveSet, dz, trades: DeviceTrades, z, bucket, fix_tau, flt_tau,
                            per_trade=False):
     """`credit_scenario_pv` on the curves of a `CurveSet`, read in place where `curve_set_arrays` finds them
     (adr_credit_scenario_pv_set): one scenario per curve of the set; ``dz`` has that many rows, one shared row or is None."""
-    n, S = trades.n_trades, len(curve_set)
-    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
-    if dz.shape[0] not in (1, S):
-        raise LibError(f"{dz.shape[0]} spread-shock rows for a set of {S} curves: one shared row or one row per curve")
-    book = np.empty(S)
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_credit_scenario_pv_set(ctx._h, curve_set._h, dz.shape[1], dz.shape[0], _ptr(dz) if dz.size else None,
-                                             trades._h, _ptr(z), _ptr(bucket, _i32p), fix_tau.size, _ptr(fix_tau), flt_tau.size,
-                                             _ptr(flt_tau), _ptr(pv), _ptr(book)), "adr_credit_scenario_pv_set")
-    return _scenario_result(book, pv, per_trade)
+    return _credit_set_call(load().adr_credit_scenario_pv_set, ctx, curve_set, dz, trades, z, bucket, fix_tau, flt_tau,
+                            per_trade)
 
 
 def credit_scenario_pv_host(method: int, times, dfs, dz, batch, z, bucket, fix_tau, flt_tau, per_trade=False, n_threads=0):
     """`credit_scenario_pv` on the CPU (adr_credit_scenario_pv_host) for a `TradeBatch`: the same per-coupon arithmetic
     and the same order of the book sum; no GPU needed."""
-    times, dfs = _scenario_curves(times, dfs)
-    n, fo, lo, a, w = _batch_arrays(batch)
-    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, a["fix_tp"].size,
-                                                            a["flt_tp"].size)
-    S = _credit_counts(dfs.shape[0], dz.shape[0])
-    book = np.empty(S)
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_credit_scenario_pv_host(int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), dz.shape[1],
-                                              dz.shape[0], _ptr(dz) if dz.size else None, S, n, _ptr(fo, _i64p), _ptr(lo, _i64p),
-                                              _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]), _ptr(a["flt_ts"]),
-                                              _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w), _ptr(a["notional"]),
-                                              _ptr(a["spread"]), _ptr(a["fix_sign"]), _ptr(a["flt_sign"]), _ptr(z),
-                                              _ptr(bucket, _i32p), _ptr(fix_tau), _ptr(flt_tau), _ptr(pv), _ptr(book),
-                                              int(n_threads)), "adr_credit_scenario_pv_host")
-    return _scenario_result(book, pv, per_trade)
+    return _credit_host_call(load().adr_credit_scenario_pv_host, method, times, dfs, dz, batch, z, bucket, fix_tau, flt_tau,
+                             per_trade, n_threads)
 
 
 def credit_scenario_pv_work(n_trades: int, n_scenarios: int) -> int:
@@ -1051,11 +1091,10 @@ def credit_scenario_pv_dev(ctx: Context, method: int, K: int, S_disc: int, G: in
     (0 when G = 0), ``z`` [n], ``bucket`` [n] (int32), ``fix_tau`` [n_fix] and ``flt_tau`` [n_flt] to device pointers
     (integers); outputs ``book_pv`` [S] and ``pv`` [n, S] (trade-major; 0: not wanted); `credit_scenario_pv_work`
     doubles of scratch."""
-    v = lambda p: _vp(int(p) or None)
-    g = lambda k: v(ptrs.get(k, 0))
+    g = _dev_of(ptrs)
     _check(load().adr_credit_scenario_pv_dev(ctx._h, int(method), int(K), g("times"), int(S_disc), g("dfs"), int(G), int(S_spr),
                                              g("dz"), int(S), trades._h, g("z"), g("bucket"), int(n_fix), g("fix_tau"),
-                                             int(n_flt), g("flt_tau"), v(pv_ptr), v(book_ptr), v(work_ptr),
+                                             int(n_flt), g("flt_tau"), _dev(pv_ptr), _dev(book_ptr), _dev(work_ptr),
                                              _vp(stream or None)), "adr_credit_scenario_pv_dev")
 
 
@@ -1071,13 +1110,6 @@ def _sub_offsets(sub_off):
     if sub_off.size < 2:
         raise LibError("sub_off needs B + 1 entries for B >= 1 sub-books")
     return sub_off, sub_off.size - 1
-
-
-def _sub_result(sub_pv, pv, per_trade):
-    out = {"sub_pv": sub_pv}
-    if per_trade:
-        out["pv"] = pv.T
-    return out
 
 
 def scenario_subbook_plan(n_trades: int, sub_off) -> np.ndarray:
@@ -1099,42 +1131,26 @@ def scenario_subbook_pv(ctx: Context, method: int, times, dfs, trades: DeviceTra
     """`scenario_pv` per sub-book in one launch (adr_scenario_subbook_pv, blocking): sub-book ``b`` holds the trades
     ``sub_off[b] .. sub_off[b + 1]``.  ``sub_pv [B, S]`` and, with ``per_trade``, ``pv [S, n]``."""
     times, dfs = _scenario_curves(times, dfs)
-    sub_off, B = _sub_offsets(sub_off)
-    S, n = dfs.shape[0], trades.n_trades
-    sub_pv = np.empty((B, S))
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_scenario_subbook_pv(ctx._h, int(method), times.size, _ptr(times), S, _ptr(dfs), trades._h, B,
-                                          _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv)), "adr_scenario_subbook_pv")
-    return _sub_result(sub_pv, pv, per_trade)
+    sub = _sub_offsets(sub_off)
+    return _scenario_call(load().adr_scenario_subbook_pv, [ctx._h] + _curve_args(method, times, dfs) + [trades._h],
+                          trades.n_trades, dfs.shape[0], per_trade, sub)
 
 
 def scenario_subbook_pv_set(ctx: Context, curve_set: CurveSet, trades: DeviceTrades, sub_off, per_trade=False):
     """`scenario_subbook_pv` on the curves of a `CurveSet`, read where the device builder left them."""
-    sub_off, B = _sub_offsets(sub_off)
-    S, n = len(curve_set), trades.n_trades
-    sub_pv = np.empty((B, S))
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_scenario_subbook_pv_set(ctx._h, curve_set._h, trades._h, B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv)),
-           "adr_scenario_subbook_pv_set")
-    return _sub_result(sub_pv, pv, per_trade)
+    sub = _sub_offsets(sub_off)
+    return _scenario_call(load().adr_scenario_subbook_pv_set, [ctx._h, curve_set._h, trades._h], trades.n_trades,
+                          len(curve_set), per_trade, sub)
 
 
 def scenario_subbook_pv_host(method: int, times, dfs, batch, sub_off, per_trade=False, n_threads=0):
     """`scenario_subbook_pv` on the CPU (adr_scenario_subbook_pv_host) for a `TradeBatch`: the same arithmetic and the
     same order of every sub-book's sum; no GPU needed."""
     times, dfs = _scenario_curves(times, dfs)
-    sub_off, B = _sub_offsets(sub_off)
-    n, fo, lo, a, w = _batch_arrays(batch)
-    S = dfs.shape[0]
-    sub_pv = np.empty((B, S))
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_scenario_subbook_pv_host(int(method), times.size, _ptr(times), S, _ptr(dfs), n, _ptr(fo, _i64p),
-                                               _ptr(lo, _i64p), _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]),
-                                               _ptr(a["flt_ts"]), _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w),
-                                               _ptr(a["notional"]), _ptr(a["spread"]), _ptr(a["fix_sign"]), _ptr(a["flt_sign"]),
-                                               B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv), int(n_threads)),
-           "adr_scenario_subbook_pv_host")
-    return _sub_result(sub_pv, pv, per_trade)
+    sub = _sub_offsets(sub_off)
+    arrays = _batch_arrays(batch)
+    return _scenario_call(load().adr_scenario_subbook_pv_host, _curve_args(method, times, dfs) + _batch_args(*arrays),
+                          arrays[0], dfs.shape[0], per_trade, sub, (int(n_threads),))
 
 
 def scenario_subbook_pv_dev(ctx: Context, method: int, K: int, times_ptr: int, S: int, dfs_ptr: int, trades: DeviceTrades,
@@ -1142,10 +1158,9 @@ def scenario_subbook_pv_dev(ctx: Context, method: int, K: int, times_ptr: int, S
     """Non-blocking form (adr_scenario_subbook_pv_dev): device pointers (integers) of ``times`` [K], ``dfs`` [S, K], the
     uploaded `scenario_subbook_plan`, the outputs ``sub_pv`` [B, S] and ``pv`` [n, S] (0: not wanted) and
     `scenario_subbook_work` doubles of scratch."""
-    v = lambda p: _vp(int(p) or None)
-    _check(load().adr_scenario_subbook_pv_dev(ctx._h, int(method), int(K), v(times_ptr), int(S), v(dfs_ptr), trades._h, int(B),
-                                              v(plan_ptr), v(pv_ptr), v(sub_pv_ptr), v(work_ptr), _vp(stream or None)),
-           "adr_scenario_subbook_pv_dev")
+    _check(load().adr_scenario_subbook_pv_dev(ctx._h, int(method), int(K), _dev(times_ptr), int(S), _dev(dfs_ptr), trades._h,
+                                              int(B), _dev(plan_ptr), _dev(pv_ptr), _dev(sub_pv_ptr), _dev(work_ptr),
+                                              _vp(stream or None)), "adr_scenario_subbook_pv_dev")
 
 
 def scenario_subbook_var_es(ctx: Context, method: int, times, dfs, trades: DeviceTrades, sub_off, k: int, base_col: int = -1):
@@ -1154,9 +1169,8 @@ def scenario_subbook_var_es(ctx: Context, method: int, times, dfs, trades: Devic
     times, dfs = _scenario_curves(times, dfs)
     sub_off, B = _sub_offsets(sub_off)
     var, es = np.empty(B), np.empty(B)
-    _check(load().adr_scenario_subbook_var_es(ctx._h, int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), trades._h, B,
-                                              _ptr(sub_off, _i64p), int(base_col), int(k), _ptr(var), _ptr(es)),
-           "adr_scenario_subbook_var_es")
+    _check(load().adr_scenario_subbook_var_es(ctx._h, *_curve_args(method, times, dfs), trades._h, B, _ptr(sub_off, _i64p),
+                                              int(base_col), int(k), _ptr(var), _ptr(es)), "adr_scenario_subbook_var_es")
     return var, es
 
 
@@ -1164,59 +1178,22 @@ def credit_scenario_subbook_pv(ctx: Context, method: int, times, dfs, dz, trades
                                sub_off, per_trade=False):
     """`credit_scenario_pv` per sub-book in one launch (adr_credit_scenario_subbook_pv, blocking): ``sub_pv [B, S]`` and,
     with ``per_trade``, ``pv [S, n]``."""
-    times, dfs = _scenario_curves(times, dfs)
-    sub_off, B = _sub_offsets(sub_off)
-    n = trades.n_trades
-    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
-    n_fix, n_flt = fix_tau.size, flt_tau.size
-    S = _credit_counts(dfs.shape[0], dz.shape[0])
-    sub_pv = np.empty((B, S))
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_credit_scenario_subbook_pv(ctx._h, int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs),
-                                                 dz.shape[1], dz.shape[0], _ptr(dz) if dz.size else None, S, trades._h, _ptr(z),
-                                                 _ptr(bucket, _i32p), n_fix, _ptr(fix_tau), n_flt, _ptr(flt_tau), B,
-                                                 _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv)), "adr_credit_scenario_subbook_pv")
-    return _sub_result(sub_pv, pv, per_trade)
+    return _credit_call(load().adr_credit_scenario_subbook_pv, ctx, method, times, dfs, dz, trades, z, bucket, fix_tau,
+                        flt_tau, per_trade, sub_off)
 
 
 def credit_scenario_subbook_pv_set(ctx: Context, curve_set: CurveSet, dz, trades: DeviceTrades, z, bucket, fix_tau, flt_tau,
                                    sub_off, per_trade=False):
     """`credit_scenario_subbook_pv` on the curves of a `CurveSet` (adr_credit_scenario_subbook_pv_set)."""
-    sub_off, B = _sub_offsets(sub_off)
-    n = trades.n_trades
-    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, np.size(fix_tau), np.size(flt_tau))
-    n_fix, n_flt = fix_tau.size, flt_tau.size
-    S = len(curve_set)
-    if dz.shape[0] not in (1, S):
-        raise LibError(f"{dz.shape[0]} spread-shock rows for a set of {S} curves: one shared row or one row per curve")
-    sub_pv = np.empty((B, S))
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_credit_scenario_subbook_pv_set(ctx._h, curve_set._h, dz.shape[1], dz.shape[0],
-                                                     _ptr(dz) if dz.size else None, trades._h, _ptr(z), _ptr(bucket, _i32p), n_fix,
-                                                     _ptr(fix_tau), n_flt, _ptr(flt_tau), B, _ptr(sub_off, _i64p), _ptr(pv),
-                                                     _ptr(sub_pv)), "adr_credit_scenario_subbook_pv_set")
-    return _sub_result(sub_pv, pv, per_trade)
+    return _credit_set_call(load().adr_credit_scenario_subbook_pv_set, ctx, curve_set, dz, trades, z, bucket, fix_tau,
+                            flt_tau, per_trade, sub_off)
 
 
 def credit_scenario_subbook_pv_host(method: int, times, dfs, dz, batch, z, bucket, fix_tau, flt_tau, sub_off, per_trade=False,
                                     n_threads=0):
     """`credit_scenario_subbook_pv` on the CPU (adr_credit_scenario_subbook_pv_host) for a `TradeBatch`."""
-    times, dfs = _scenario_curves(times, dfs)
-    sub_off, B = _sub_offsets(sub_off)
-    n, fo, lo, a, w = _batch_arrays(batch)
-    dz, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(dz, z, bucket, fix_tau, flt_tau, n, a["fix_tp"].size, a["flt_tp"].size)
-    S = _credit_counts(dfs.shape[0], dz.shape[0])
-    sub_pv = np.empty((B, S))
-    pv = np.empty((n, S)) if per_trade else None
-    _check(load().adr_credit_scenario_subbook_pv_host(int(method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), dz.shape[1],
-                                                      dz.shape[0], _ptr(dz) if dz.size else None, S, n, _ptr(fo, _i64p),
-                                                      _ptr(lo, _i64p), _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]),
-                                                      _ptr(a["flt_ts"]), _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w),
-                                                      _ptr(a["notional"]), _ptr(a["spread"]), _ptr(a["fix_sign"]),
-                                                      _ptr(a["flt_sign"]), _ptr(z), _ptr(bucket, _i32p), _ptr(fix_tau),
-                                                      _ptr(flt_tau), B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv),
-                                                      int(n_threads)), "adr_credit_scenario_subbook_pv_host")
-    return _sub_result(sub_pv, pv, per_trade)
+    return _credit_host_call(load().adr_credit_scenario_subbook_pv_host, method, times, dfs, dz, batch, z, bucket, fix_tau,
+                             flt_tau, per_trade, n_threads, sub_off)
 
 
 def credit_scenario_subbook_pv_dev(ctx: Context, method: int, K: int, S_disc: int, G: int, S_spr: int, S: int,
@@ -1225,12 +1202,11 @@ def credit_scenario_subbook_pv_dev(ctx: Context, method: int, K: int, S_disc: in
     """Non-blocking form (adr_credit_scenario_subbook_pv_dev): ``ptrs`` as `credit_scenario_pv_dev` takes them plus
     ``plan``, the uploaded `scenario_subbook_plan`; outputs ``sub_pv`` [B, S] and ``pv`` [n, S] (0: not wanted);
     `scenario_subbook_work` doubles of scratch."""
-    v = lambda p: _vp(int(p) or None)
-    g = lambda name: v(ptrs.get(name, 0))
+    g = _dev_of(ptrs)
     _check(load().adr_credit_scenario_subbook_pv_dev(ctx._h, int(method), int(K), g("times"), int(S_disc), g("dfs"), int(G),
                                                      int(S_spr), g("dz"), int(S), trades._h, g("z"), g("bucket"), int(n_fix),
-                                                     g("fix_tau"), int(n_flt), g("flt_tau"), int(B), g("plan"), v(pv_ptr),
-                                                     v(sub_pv_ptr), v(work_ptr), _vp(stream or None)),
+                                                     g("fix_tau"), int(n_flt), g("flt_tau"), int(B), g("plan"), _dev(pv_ptr),
+                                                     _dev(sub_pv_ptr), _dev(work_ptr), _vp(stream or None)),
            "adr_credit_scenario_subbook_pv_dev")
 
 
@@ -1241,59 +1217,45 @@ def _tail_rows(rows):
     return rows
 
 
+def _tail_call(fn, head, rows, k, base_col):
+    rows = _tail_rows(rows)
+    var, es = np.empty(rows.shape[0]), np.empty(rows.shape[0])
+    _check(fn(*head, rows.shape[0], rows.shape[1], _ptr(rows), int(base_col), int(k), _ptr(var), _ptr(es)), fn.__name__)
+    return var, es
+
+
 def scenario_tail(ctx: Context, rows, k: int, base_col: int = -1):
     """``(var [B], es [B])`` of ``rows [B, S]`` on the device (adr_scenario_tail, blocking): minus the ``k``-th smallest
     P&L, and minus the mean of the ``k`` smallest.  ``base_col >= 0``: the P&L is every other column minus that one."""
-    rows = _tail_rows(rows)
-    var, es = np.empty(rows.shape[0]), np.empty(rows.shape[0])
-    _check(load().adr_scenario_tail(ctx._h, rows.shape[0], rows.shape[1], _ptr(rows), int(base_col), int(k), _ptr(var), _ptr(es)),
-           "adr_scenario_tail")
-    return var, es
+    return _tail_call(load().adr_scenario_tail, (ctx._h,), rows, k, base_col)
 
 
 def scenario_tail_host(rows, k: int, base_col: int = -1):
     """`scenario_tail` on the CPU (adr_scenario_tail_host): the same sums in the same order, hence the same bits."""
-    rows = _tail_rows(rows)
-    var, es = np.empty(rows.shape[0]), np.empty(rows.shape[0])
-    _check(load().adr_scenario_tail_host(rows.shape[0], rows.shape[1], _ptr(rows), int(base_col), int(k), _ptr(var), _ptr(es)),
-           "adr_scenario_tail_host")
-    return var, es
+    return _tail_call(load().adr_scenario_tail_host, (), rows, k, base_col)
 
 
 def scenario_tail_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: int, var_ptr: int, es_ptr: int, base_col: int = -1,
                       stream=0):
     """Non-blocking form (adr_scenario_tail_dev): device pointers of ``rows`` [B, S_tot], ``var`` [B] and ``es`` [B]."""
-    v = lambda p: _vp(int(p) or None)
-    _check(load().adr_scenario_tail_dev(ctx._h, int(B), int(S_tot), v(rows_ptr), int(base_col), int(k), v(var_ptr), v(es_ptr),
-                                        _vp(stream or None)), "adr_scenario_tail_dev")
-
-
-def _yoy_subbook_call(fn, head, tail, disc_method, times, dfs, infl_method, T, b, fixed, book, sub_off, per_trade):
-    times, dfs, T, b, S, fix_off, fix_tp, fix_pay, cpn_off, cpn = _yoy_scenario_inputs(times, dfs, T, b, fixed, book)
-    sub_off, B = _sub_offsets(sub_off)
-    n = fix_off.size - 1
-    sub_pv = np.empty((B, S))
-    pv = np.empty((n, S)) if per_trade else None
-    _check(fn(*head, int(disc_method), times.size, _ptr(times), dfs.shape[0], _ptr(dfs), int(infl_method), T.size, _ptr(T),
-              b.shape[0], _ptr(b), S, n, fix_tp.size, _ptr(fix_off, _i64p), _ptr(fix_tp), _ptr(fix_pay), cpn.shape[1],
-              _ptr(cpn_off, _i64p), _ptr(cpn), B, _ptr(sub_off, _i64p), _ptr(pv), _ptr(sub_pv), *tail), fn.__name__)
-    return _sub_result(sub_pv, pv, per_trade)
+    _check(load().adr_scenario_tail_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), int(k), _dev(var_ptr),
+                                        _dev(es_ptr), _vp(stream or None)), "adr_scenario_tail_dev")
 
 
 def yoy_scenario_subbook_pv(ctx: Context, disc_method: int, times, dfs, infl_method: int, T, b, fixed, book, sub_off,
                             per_trade=False):
     """`yoy_scenario_pv` per sub-book in one launch (adr_yoy_scenario_subbook_pv, blocking): sub-book ``b`` holds the swaps
     ``sub_off[b] .. sub_off[b + 1]``.  ``sub_pv [B, S]`` and, with ``per_trade``, ``pv [S, n]``."""
-    return _yoy_subbook_call(load().adr_yoy_scenario_subbook_pv, (ctx._h,), (), disc_method, times, dfs, infl_method, T, b,
-                             fixed, book, sub_off, per_trade)
+    return _yoy_scenario_call(load().adr_yoy_scenario_subbook_pv, (ctx._h,), (), disc_method, times, dfs, infl_method, T, b,
+                              fixed, book, per_trade, sub_off)
 
 
 def yoy_scenario_subbook_pv_host(disc_method: int, times, dfs, infl_method: int, T, b, fixed, book, sub_off, per_trade=False,
                                  n_threads=0):
     """`yoy_scenario_subbook_pv` on the CPU (adr_yoy_scenario_subbook_pv_host): the same arithmetic and the same order of
     every sub-book's sum; no GPU needed."""
-    return _yoy_subbook_call(load().adr_yoy_scenario_subbook_pv_host, (), (int(n_threads),), disc_method, times, dfs,
-                             infl_method, T, b, fixed, book, sub_off, per_trade)
+    return _yoy_scenario_call(load().adr_yoy_scenario_subbook_pv_host, (), (int(n_threads),), disc_method, times, dfs,
+                              infl_method, T, b, fixed, book, per_trade, sub_off)
 
 
 def yoy_scenario_subbook_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: int, infl_method: int, P: int, S_infl: int,
@@ -1302,13 +1264,12 @@ def yoy_scenario_subbook_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: 
     """Non-blocking form (adr_yoy_scenario_subbook_pv_dev): ``ptrs`` as `yoy_scenario_pv_dev` takes them plus ``plan``, the
     uploaded `scenario_subbook_plan`; outputs ``sub_pv`` [B, S] and ``pv`` [n, S] (0: not wanted); `scenario_subbook_work`
     doubles of scratch."""
-    v = lambda p: _vp(int(p) or None)
-    g = lambda k: v(ptrs.get(k, 0))
+    g = _dev_of(ptrs)
     _check(load().adr_yoy_scenario_subbook_pv_dev(ctx._h, int(disc_method), int(K), g("times"), int(S_disc), g("dfs"),
                                                   int(infl_method), int(P), g("T"), int(S_infl), g("b"), int(S), int(n_swaps),
                                                   int(n_fix), g("fix_off"), g("fix_tp"), g("fix_pay"), int(n_coupons),
-                                                  g("cpn_off"), g("cpn"), int(B), g("plan"), v(pv_ptr), v(sub_pv_ptr),
-                                                  v(work_ptr), _vp(stream or None)), "adr_yoy_scenario_subbook_pv_dev")
+                                                  g("cpn_off"), g("cpn"), int(B), g("plan"), _dev(pv_ptr), _dev(sub_pv_ptr),
+                                                  _dev(work_ptr), _vp(stream or None)), "adr_yoy_scenario_subbook_pv_dev")
 
 
 SCENARIO_ALLOC_MAX = 8192                                   # ADR_SCENARIO_ALLOC_MAX
@@ -1339,10 +1300,9 @@ def scenario_tail_alloc_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: 
                             comp_var_ptr: int, comp_es_ptr: int, work_ptr: int, base_col: int = -1, stream=0):
     """Non-blocking form (adr_scenario_tail_alloc_dev): device pointers of ``rows`` [B, S_tot], ``var`` [1], ``es`` [1],
     ``comp_var`` [B], ``comp_es`` [B] and ``S_tot`` doubles of scratch."""
-    v = lambda p: _vp(int(p) or None)
-    _check(load().adr_scenario_tail_alloc_dev(ctx._h, int(B), int(S_tot), v(rows_ptr), int(base_col), int(k), v(var_ptr),
-                                              v(es_ptr), v(comp_var_ptr), v(comp_es_ptr), v(work_ptr), _vp(stream or None)),
-           "adr_scenario_tail_alloc_dev")
+    _check(load().adr_scenario_tail_alloc_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), int(k), _dev(var_ptr),
+                                              _dev(es_ptr), _dev(comp_var_ptr), _dev(comp_es_ptr), _dev(work_ptr),
+                                              _vp(stream or None)), "adr_scenario_tail_alloc_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

@@ -61,6 +61,31 @@ def shocked_quotes(base_px: Sequence[float], tenors: Sequence[str], shock: Shock
     return [px + shock for px in base_px]
 
 
+def _interp_value(method) -> int:
+    """An `InterpTypes` member or its value as the value of a scheme the kernels take."""
+    method = int(getattr(method, "value", method))
+    if method not in _SUPPORTED_INTERP:
+        raise LibError("Invalid interpolation scheme.")
+    return method
+
+
+def _disc_infl_methods(disc_method, infl_method):
+    """The same for a YoY pair: the discount curve's scheme and the inflation curve's, which has two to choose from."""
+    dm, im = int(getattr(disc_method, "value", disc_method)), int(getattr(infl_method, "value", infl_method))
+    if dm not in _SUPPORTED_INTERP or im not in (InterpTypes.LINEAR_ZERO_RATES.value, InterpTypes.FLAT_FWD_RATES.value):
+        raise LibError("Invalid interpolation scheme.")
+    return dm, im
+
+
+def _first_appearance(keys):
+    """``(labels, index)``: the distinct ``keys`` in order of first appearance, and the number of each."""
+    index = {}
+    for k in keys:
+        if k not in index:
+            index[k] = len(index)
+    return list(index), index
+
+
 def _concat_batches(batches: Sequence[TradeBatch]) -> TradeBatch:
     """One batch holding the trades of ``batches`` in order."""
     batches = [b for b in batches if b.n_trades]
@@ -128,10 +153,16 @@ def compile_book(trades, value_dt, curve_type: CurveTypes):
     return _concat_batches(pieces), (const if np.any(const != 0.0) else None), np.asarray(order, dtype=np.int64)
 
 
-def _finish(out, const, order, per_trade):
-    """Add the curve-independent amounts and put per-trade rows back into the caller's order."""
-    if const is not None:
+def _finish(out, const, order, per_trade, sub_off=None):
+    """Add the curve-independent amounts - to the book, or with ``sub_off`` per sub-book in batch order - and put per-trade
+    rows back into the caller's order."""
+    if const is not None and sub_off is None:
         out["book_pv"] = out["book_pv"] + float(np.sum(const))
+    elif const is not None:
+        add = np.array([float(np.sum(const[lo:hi])) if np.any(const[lo:hi] != 0.0) else 0.0
+                        for lo, hi in zip(sub_off[:-1], sub_off[1:])])
+        live = add != 0.0
+        out["sub_pv"][live] = out["sub_pv"][live] + add[live, None]
     if per_trade:
         pv = out["pv"] if const is None else out["pv"] + const[None, :]
         if order is not None and not np.array_equal(order, np.arange(order.size)):
@@ -150,20 +181,9 @@ def revalue_on_curves(method, times, dfs, trades, value_dt, per_trade=False, ctx
     rows of a `ScenarioGrid`.  ``trades``: see `compile_book` (objects are checked against ``curve_type``, default the
     GBP OIS curve; a `TradeBatch` is taken as it is).  Returns ``{"book_pv": [S]}`` and, with ``per_trade``,
     ``"pv": [S, n]``.  ``host=True`` runs the CPU twin of the kernel (same arithmetic and summation order; no GPU)."""
-    method = int(getattr(method, "value", method))
-    if method not in _SUPPORTED_INTERP:
-        raise LibError("Invalid interpolation scheme.")
-    batch, const, order = compile_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA)
-    if host:
-        out = _native.scenario_pv_host(method, times, dfs, batch, per_trade=per_trade)
-    else:
-        ctx = ctx or _native.default_context()
-        dev = _native.DeviceTrades(ctx, batch)
-        try:
-            out = _native.scenario_pv(ctx, method, times, dfs, dev, per_trade=per_trade)
-        finally:
-            dev.close()
-    return _finish(out, const, order, per_trade)
+    method = _interp_value(method)
+    book = compile_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA)
+    return _revalue(_Curves.on_arrays(method, times, dfs, ctx, host), per_trade, book)
 
 
 @dataclass
@@ -209,15 +229,14 @@ def compile_credit_book(trades, value_dt, curve_type: CurveTypes, spreads, bucke
     buckets = list(buckets)
     if len(buckets) != n:
         raise LibError(f"buckets needs one entry per trade ({n}), not {len(buckets)}")
-    labels, index = [], {}
-    for i, lab in enumerate(buckets):
-        if lab is None:
-            continue
-        if trades[i].derivative_type == InstrumentTypes.OIS_SWAP:
-            raise LibError(f"trade {i} is an OIS: it carries no credit spread, so its bucket must be None")
-        if lab not in index:
-            index[lab] = len(labels)
-            labels.append(lab)
+    def bucketed():                     # the labels to number; an OIS among them is refused where it stands
+        for i, lab in enumerate(buckets):
+            if lab is None:
+                continue
+            if trades[i].derivative_type == InstrumentTypes.OIS_SWAP:
+                raise LibError(f"trade {i} is an OIS: it carries no credit spread, so its bucket must be None")
+            yield lab
+    labels, index = _first_appearance(bucketed())
     if len(labels) > _native.CREDIT_MAX_BUCKETS:
         raise LibError(f"{len(labels)} distinct buckets: at most {_native.CREDIT_MAX_BUCKETS} fit one launch")
     fix_tau = np.zeros(batch.fix_tp.shape[0])
@@ -266,6 +285,15 @@ def _spread_rows(spread_shocks, G):
     return None if G == 0 else dz
 
 
+def _grid_spread_rows(dz, S, G, with_base):
+    """`_spread_rows`' result checked against a grid of ``S`` scenarios; ``with_base`` appends the base pair's row."""
+    if dz is not None and dz.shape[0] not in (1, S):
+        raise LibError(f"{dz.shape[0]} spread-shock rows for a grid of {S} scenarios: one shared row or one per scenario")
+    if with_base and dz is not None:            # the base pair: the unshocked curve with a zero spread shock
+        dz = np.vstack([np.broadcast_to(dz, (S, G)), np.zeros((1, G))])
+    return dz
+
+
 def revalue_credit_on_curves(method, times, dfs, spread_shocks, trades, spreads, buckets, value_dt, per_trade=False,
                              ctx=None, host=False, curve_type=None):
     """PVs of a credit book under caller-supplied scenario PAIRS, in one launch of csrc/credit_scenario_pv.hip.
@@ -275,36 +303,25 @@ def revalue_credit_on_curves(method, times, dfs, spread_shocks, trades, spreads,
     by all scenarios; ``spread_shocks=None`` shocks no spread.  ``trades``, ``spreads`` and ``buckets``: see
     `compile_credit_book`.  Returns ``{"book_pv": [S], "labels": [...]}`` and, with ``per_trade``, ``"pv": [S, n]`` in
     the list's order.  ``host=True`` runs the CPU twin of the kernel (same arithmetic and summation order; no GPU)."""
-    method = int(getattr(method, "value", method))
-    if method not in _SUPPORTED_INTERP:
-        raise LibError("Invalid interpolation scheme.")
+    method = _interp_value(method)
     book = compile_credit_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA, spreads, buckets)
     dz = _spread_rows(spread_shocks, len(book.labels))
-    if host:
-        out = _native.credit_scenario_pv_host(method, times, dfs, dz, book.batch, book.z, book.bucket, book.fix_tau,
-                                              book.flt_tau, per_trade=per_trade)
-    else:
-        ctx = ctx or _native.default_context()
-        dev = _native.DeviceTrades(ctx, book.batch)
-        try:
-            out = _native.credit_scenario_pv(ctx, method, times, dfs, dz, dev, book.z, book.bucket, book.fix_tau,
-                                             book.flt_tau, per_trade=per_trade)
-        finally:
-            dev.close()
-    out["labels"] = book.labels
-    return _finish(out, book.pv_const, book.order, per_trade)
+    return _revalue(_Curves.on_arrays(method, times, dfs, ctx, host), per_trade, book, dz)
+
+
+def _gather_offsets(off, perm):
+    """``(offsets of the rows perm of a CSR array, gather index of their entries)``."""
+    off = np.asarray(off, dtype=np.int64)
+    length = (off[1:] - off[:-1])[perm]
+    new_off = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+    idx = np.repeat(off[:-1][perm] - new_off[:-1], length) + np.arange(int(new_off[-1]), dtype=np.int64)
+    return new_off, idx
 
 
 def _permute_batch(batch: TradeBatch, perm: np.ndarray):
     """``(batch with trade j = trade perm[j] of ``batch``, fixed-flow gather index, float-coupon gather index)``."""
-    def gather(off):
-        off = np.asarray(off, dtype=np.int64)
-        length = (off[1:] - off[:-1])[perm]
-        new_off = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
-        idx = np.repeat(off[:-1][perm] - new_off[:-1], length) + np.arange(int(new_off[-1]), dtype=np.int64)
-        return new_off, idx
-    fix_off, fi = gather(batch.fix_off)
-    flt_off, li = gather(batch.flt_off)
+    fix_off, fi = _gather_offsets(batch.fix_off, perm)
+    flt_off, li = _gather_offsets(batch.flt_off, perm)
     f = lambda name, idx: np.asarray(getattr(batch, name), dtype=np.float64)[idx]
     weight = None if batch.flt_weight is None else np.asarray(batch.flt_weight, dtype=np.float64)[li]
     return TradeBatch(fix_off, flt_off, f("fix_tp", fi), f("fix_pay", fi), f("flt_tp", li), f("flt_ts", li), f("flt_te", li),
@@ -339,11 +356,7 @@ def split_sub_books(batch: TradeBatch, pv_const, order, keys) -> SubBooks:
     n = batch.n_trades
     if len(keys) != n:
         raise LibError(f"keys needs one entry per trade ({n}), not {len(keys)}")
-    labels, index = [], {}
-    for k in keys:
-        if k not in index:
-            index[k] = len(labels)
-            labels.append(k)
+    labels, index = _first_appearance(keys)
     if order is None:
         code = np.array([index[k] for k in keys], dtype=np.int64)
         back = np.nonzero(code[1:] < code[:-1])[0]
@@ -366,23 +379,50 @@ def split_sub_books(batch: TradeBatch, pv_const, order, keys) -> SubBooks:
     return SubBooks(batch, None if pv_const is None else pv_const[perm], order[perm], labels, sub_off, perm, fi, li)
 
 
-def _finish_sub_books(out, sb: SubBooks, per_trade):
-    """Add the curve-independent amounts per sub-book in batch order and put per-trade rows back into the caller's order."""
-    const = sb.pv_const
-    if const is not None:
-        add = np.array([float(np.sum(const[lo:hi])) if np.any(const[lo:hi] != 0.0) else 0.0
-                        for lo, hi in zip(sb.sub_off[:-1], sb.sub_off[1:])])
-        live = add != 0.0
-        out["sub_pv"][live] = out["sub_pv"][live] + add[live, None]
-    out["labels"] = sb.labels
-    if per_trade:
-        pv = out["pv"] if const is None else out["pv"] + const[None, :]
-        if sb.order is not None and not np.array_equal(sb.order, np.arange(sb.order.size)):
-            back = np.empty_like(pv)
-            back[:, sb.order] = pv
-            pv = back
-        out["pv"] = pv
-    return out
+@dataclass
+class _Curves:
+    """Where the discount rows of a revaluation come from, as the `_native` scenario entries take them: host arrays priced
+    on the device (``suffix`` "", ``head`` the scheme, ``times`` and ``dfs``), the same on the host twin ("_host", no
+    context) or a `CurveSet` read in place ("_set", ``head`` the set)."""
+    suffix: str
+    head: tuple
+    ctx: Optional[_native.Context] = None          # None on the device: the default context, made when the call is
+
+    @classmethod
+    def on_arrays(cls, method, times, dfs, ctx, host):
+        return cls("_host" if host else "", (method, times, dfs), ctx)
+
+    def call(self, entry, batch, dz, per_trade_data, sub_off, per_trade):
+        """The entry ``entry`` of this kind; the optional groups are sequences, empty where the entry has none."""
+        fn = getattr(_native, entry + self.suffix)
+        if self.suffix == "_host":
+            return fn(*self.head, *dz, batch, *per_trade_data, *sub_off, per_trade=per_trade)
+        ctx = self.ctx or _native.default_context()
+        with _native.DeviceTrades(ctx, batch) as dev:
+            return fn(ctx, *self.head, *dz, dev, *per_trade_data, *sub_off, per_trade=per_trade)
+
+
+def _revalue(curves: _Curves, per_trade, book, dz=None, *keys):
+    """One revaluation of a compiled book, in one launch: ``book`` is `compile_book`'s triple (``dz`` stays None) or a
+    `CreditBook` (``dz`` holds its spread-shock rows, `_spread_rows`), cut into sub-books where ``keys`` is given
+    (`split_sub_books`)."""
+    credit = isinstance(book, CreditBook)
+    batch, const, order = (book.batch, book.pv_const, book.order) if credit else book
+    data = [book.z, book.bucket, book.fix_tau, book.flt_tau] if credit else []
+    sub_off = ()
+    if keys:
+        sb = split_sub_books(batch, const, order, *keys)
+        batch, const, order, sub_off = sb.batch, sb.pv_const, sb.order, (sb.sub_off,)
+        if credit and sb.perm is not None:          # the re-ordered batch's order
+            data = [book.z[sb.perm], book.bucket[sb.perm], book.fix_tau[sb.fix_idx], book.flt_tau[sb.flt_idx]]
+    entry = ("credit_scenario_subbook_pv" if keys else "credit_scenario_pv") if credit else \
+        ("scenario_subbook_pv" if keys else "scenario_pv")
+    out = curves.call(entry, batch, [dz] if credit else [], data, sub_off, per_trade)
+    if credit:
+        out["buckets" if keys else "labels"] = book.labels
+    if keys:
+        out["labels"] = sb.labels
+    return _finish(out, const, order, per_trade, *sub_off)
 
 
 def revalue_on_curves_sub_books(method, times, dfs, trades, keys, value_dt, per_trade=False, ctx=None, host=False,
@@ -392,28 +432,9 @@ def revalue_on_curves_sub_books(method, times, dfs, trades, keys, value_dt, per_
     row ``b`` the PV vector of sub-book ``labels[b]``, bit for bit what `revalue_on_curves` gives on that sub-book alone
     - and, with ``per_trade``, ``"pv": [S, n]`` in the caller's order.  A `TradeBatch` must hold each label's trades
     consecutively (`split_sub_books`)."""
-    method = int(getattr(method, "value", method))
-    if method not in _SUPPORTED_INTERP:
-        raise LibError("Invalid interpolation scheme.")
-    sb = split_sub_books(*compile_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA), keys)
-    if host:
-        out = _native.scenario_subbook_pv_host(method, times, dfs, sb.batch, sb.sub_off, per_trade=per_trade)
-    else:
-        ctx = ctx or _native.default_context()
-        dev = _native.DeviceTrades(ctx, sb.batch)
-        try:
-            out = _native.scenario_subbook_pv(ctx, method, times, dfs, dev, sb.sub_off, per_trade=per_trade)
-        finally:
-            dev.close()
-    return _finish_sub_books(out, sb, per_trade)
-
-
-def _split_credit_sub_books(book: CreditBook, keys):
-    """`split_sub_books` for a credit book: ``(sub-books, z, bucket, fix_tau, flt_tau)`` in the re-ordered batch's order."""
-    sb = split_sub_books(book.batch, book.pv_const, book.order, keys)
-    if sb.perm is None:
-        return sb, book.z, book.bucket, book.fix_tau, book.flt_tau
-    return sb, book.z[sb.perm], book.bucket[sb.perm], book.fix_tau[sb.fix_idx], book.flt_tau[sb.flt_idx]
+    method = _interp_value(method)
+    book = compile_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA)
+    return _revalue(_Curves.on_arrays(method, times, dfs, ctx, host), per_trade, book, None, keys)
 
 
 def revalue_credit_on_curves_sub_books(method, times, dfs, spread_shocks, trades, spreads, buckets, keys, value_dt,
@@ -421,25 +442,10 @@ def revalue_credit_on_curves_sub_books(method, times, dfs, spread_shocks, trades
     """`revalue_credit_on_curves` per sub-book, in ONE launch (``keys``: see `revalue_on_curves_sub_books`; a sub-book
     may cut across credit buckets).  Returns ``{"labels": [...], "sub_pv": [B, S], "buckets": [...]}`` - ``buckets`` the
     credit-bucket labels, one column of ``spread_shocks`` each - and, with ``per_trade``, ``"pv": [S, n]``."""
-    method = int(getattr(method, "value", method))
-    if method not in _SUPPORTED_INTERP:
-        raise LibError("Invalid interpolation scheme.")
+    method = _interp_value(method)
     book = compile_credit_book(trades, value_dt, curve_type or CurveTypes.GBP_OIS_SONIA, spreads, buckets)
     dz = _spread_rows(spread_shocks, len(book.labels))
-    sb, z, bucket, fix_tau, flt_tau = _split_credit_sub_books(book, keys)
-    if host:
-        out = _native.credit_scenario_subbook_pv_host(method, times, dfs, dz, sb.batch, z, bucket, fix_tau, flt_tau, sb.sub_off,
-                                                      per_trade=per_trade)
-    else:
-        ctx = ctx or _native.default_context()
-        dev = _native.DeviceTrades(ctx, sb.batch)
-        try:
-            out = _native.credit_scenario_subbook_pv(ctx, method, times, dfs, dz, dev, z, bucket, fix_tau, flt_tau, sb.sub_off,
-                                                     per_trade=per_trade)
-        finally:
-            dev.close()
-    out["buckets"] = book.labels
-    return _finish_sub_books(out, sb, per_trade)
+    return _revalue(_Curves.on_arrays(method, times, dfs, ctx, host), per_trade, book, dz, keys)
 
 
 def shocked_breakevens(curve, shock: Shock) -> np.ndarray:
@@ -477,23 +483,12 @@ def revalue_yoy_on_curves(disc_method, times, dfs, infl_method, T, b, swaps_or_b
     ``b [P]``, means that curve is not shocked and is shared by all scenarios.  ``swaps_or_book``: `YoYInflationSwap`
     objects or compiled arrays (`yoy_book_arrays`).  Returns ``{"book_pv": [S]}`` and, with ``per_trade``,
     ``"pv": [S, n]``.  ``host=True`` runs the CPU twin of the kernel (same arithmetic and summation order; no GPU)."""
-    dm, im = int(getattr(disc_method, "value", disc_method)), int(getattr(infl_method, "value", infl_method))
-    if dm not in _SUPPORTED_INTERP or im not in (InterpTypes.LINEAR_ZERO_RATES.value, InterpTypes.FLAT_FWD_RATES.value):
-        raise LibError("Invalid interpolation scheme.")
+    dm, im = _disc_infl_methods(disc_method, infl_method)
     fixed, coupons = yoy_book_arrays(swaps_or_book, value_dt)
     if host:
         return _native.yoy_scenario_pv_host(dm, times, dfs, im, T, b, fixed, coupons, per_trade=per_trade)
     return _native.yoy_scenario_pv(ctx or _native.default_context(), dm, times, dfs, im, T, b, fixed, coupons,
                                    per_trade=per_trade)
-
-
-def _gather_offsets(off, perm):
-    """``(offsets of the rows perm of a CSR array, gather index of their entries)``."""
-    off = np.asarray(off, dtype=np.int64)
-    length = (off[1:] - off[:-1])[perm]
-    new_off = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
-    idx = np.repeat(off[:-1][perm] - new_off[:-1], length) + np.arange(int(new_off[-1]), dtype=np.int64)
-    return new_off, idx
 
 
 @dataclass
@@ -518,11 +513,7 @@ def split_yoy_sub_books(fixed, coupons, keys) -> YoYSubBooks:
     n = (np.asarray(fixed[0]) if fixed is not None else np.asarray(coupons["cpn_off"])).size - 1
     if len(keys) != n:
         raise LibError(f"keys needs one entry per swap ({n}), not {len(keys)}")
-    labels, index = [], {}
-    for k in keys:
-        if k not in index:
-            index[k] = len(labels)
-            labels.append(k)
+    labels, index = _first_appearance(keys)
     code = np.array([index[k] for k in keys], dtype=np.int64)
     perm = np.argsort(code, kind="stable")
     sub_off = np.searchsorted(code[perm], np.arange(len(labels) + 1), side="left").astype(np.int64)
@@ -553,9 +544,7 @@ def revalue_yoy_on_curves_sub_books(disc_method, times, dfs, infl_method, T, b, 
     counterparty, an account).  Returns ``{"labels": [...], "sub_pv": [B, S]}`` - the labels in order of first appearance,
     row ``b`` the PV vector of sub-book ``labels[b]``, bit for bit what `revalue_yoy_on_curves` gives on that sub-book
     alone - and, with ``per_trade``, ``"pv": [S, n]`` in the caller's order."""
-    dm, im = int(getattr(disc_method, "value", disc_method)), int(getattr(infl_method, "value", infl_method))
-    if dm not in _SUPPORTED_INTERP or im not in (InterpTypes.LINEAR_ZERO_RATES.value, InterpTypes.FLAT_FWD_RATES.value):
-        raise LibError("Invalid interpolation scheme.")
+    dm, im = _disc_infl_methods(disc_method, infl_method)
     sb = split_yoy_sub_books(*yoy_book_arrays(swaps_or_book, value_dt), keys)
     if host:
         out = _native.yoy_scenario_subbook_pv_host(dm, times, dfs, im, T, b, sb.fixed, sb.coupons, sb.sub_off, per_trade=per_trade)
@@ -593,6 +582,16 @@ def tail_count(level: float, n_pnl: int) -> int:
     return max(1, int(np.ceil(round((1.0 - level) * n_pnl, 9))))
 
 
+def _tail_args(rows, base_col, level, min_rows):
+    """``(rows [B, S_tot] as float64, the P&L values per row, their tail count)`` after the check `tail_measures` and
+    `allocate_tail` share."""
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    if rows.ndim != 2 or rows.shape[0] < min_rows or not -1 <= base_col < rows.shape[1]:
+        raise LibError(f"rows must have shape [n_rows, n_columns] and base_col be -1 or a column, not {list(rows.shape)}, {base_col}")
+    m = rows.shape[1] - (1 if base_col >= 0 else 0)
+    return rows, m, tail_count(level, m)
+
+
 def tail_measures(rows, level: float = 0.99, base_col: int = -1, host: bool = False, ctx=None):
     """``(var [B], es [B])``: `historical_var` and `expected_shortfall` of every row of ``rows [B, S]`` in one kernel
     (adr_scenario_tail; ``host=True``: its CPU twin, the same bits).  ``base_col >= 0``: the P&L of a row is every OTHER
@@ -600,11 +599,7 @@ def tail_measures(rows, level: float = 0.99, base_col: int = -1, host: bool = Fa
     tail in ascending order, so it agrees with `expected_shortfall` (NumPy's pairwise mean) to rounding, not bit for
     bit; ``var`` is the same order statistic.  A row holding a NaN gives NaN.  Rows wider than
     ``_native.SCENARIO_TAIL_MAX`` P&L values do not fit the kernel's LDS and are done by NumPy per row."""
-    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
-    if rows.ndim != 2 or not -1 <= base_col < rows.shape[1]:
-        raise LibError(f"rows must have shape [n_rows, n_columns] and base_col be -1 or a column, not {list(rows.shape)}, {base_col}")
-    m = rows.shape[1] - (1 if base_col >= 0 else 0)
-    k = tail_count(level, m)
+    rows, m, k = _tail_args(rows, base_col, level, 0)
     if m > _native.SCENARIO_TAIL_MAX:
         pnl = rows if base_col < 0 else np.delete(rows, base_col, axis=1) - rows[:, base_col:base_col + 1]
         out = np.array([[historical_var(r, level), expected_shortfall(r, level)] if not np.any(np.isnan(r)) else [np.nan, np.nan]
@@ -651,11 +646,8 @@ def allocate_tail(rows, level: float = 0.99, base_col: int = -1, host: bool = Fa
     over the firm's ``k`` worst: ``comp_es`` sums to ``es`` and ``comp_var`` to ``var`` up to rounding.  A NaN anywhere
     gives NaN everywhere.  Rows wider than ``_native.SCENARIO_ALLOC_MAX`` P&L values do not fit the kernel's LDS and are
     done by NumPy under the same rule."""
-    rows = np.ascontiguousarray(np.atleast_2d(np.asarray(rows, dtype=np.float64)))
-    if rows.ndim != 2 or rows.shape[0] < 1 or not -1 <= base_col < rows.shape[1]:
-        raise LibError(f"rows must have shape [n_rows, n_columns] and base_col be -1 or a column, not {list(rows.shape)}, {base_col}")
-    m = rows.shape[1] - (1 if base_col >= 0 else 0)
-    k = tail_count(level, m)
+    rows, m, k = _tail_args(rows, base_col, level, 1)
+    rows = np.ascontiguousarray(rows)
     if m > _native.SCENARIO_ALLOC_MAX:
         return _allocate_tail_numpy(rows, k, base_col)
     if host:
@@ -669,8 +661,7 @@ def combine_sub_book_rows(parts):
     ``{"labels": [...], "rows": [B, S]}`` with the labels in order of first appearance across the parts; a label's row is
     its first part's row with the later parts' rows added in list order, so a label found in one part only keeps that
     part's bits."""
-    labels, index, out = [], {}, []
-    width = None
+    checked, width = [], None
     for i, (labs, rows) in enumerate(parts):
         rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
         labs = list(labs)
@@ -682,15 +673,14 @@ def combine_sub_book_rows(parts):
             raise LibError(f"part {i} has {rows.shape[1]} columns, the parts before it {width}: the scenarios must be the same")
         if len(set(labs)) != len(labs):
             raise LibError(f"part {i} names a label twice")
-        for lab, row in zip(labs, rows):
-            if lab not in index:
-                index[lab] = len(labels)
-                labels.append(lab)
-                out.append(row.copy())
-            else:
-                out[index[lab]] = out[index[lab]] + row
-    if not out:
+        checked += zip(labs, rows)
+    if not checked:
         raise LibError("no parts to combine")
+    labels, index = _first_appearance(lab for lab, _ in checked)
+    out = [None] * len(labels)
+    for lab, row in checked:
+        j = index[lab]
+        out[j] = row.copy() if out[j] is None else out[j] + row
     return {"labels": labels, "rows": np.stack(out)}
 
 
@@ -703,9 +693,7 @@ class ScenarioGrid:
         params = model._curve_params_dict[curve_name]
         self.model, self.curve_name = model, curve_name
         self.curve = getattr(model.curves, curve_name)
-        method = self.curve._interp_type.value
-        if method not in _SUPPORTED_INTERP:
-            raise LibError("Invalid interpolation scheme.")
+        method = _interp_value(self.curve._interp_type)
         self.shocks = list(shocks)
         # OISCurve stores quote / 100 as the swap's fixed coupon (models.py build_curve); same division here
         self.rates = np.array([[px / 100.0 for px in shocked_quotes(params["px_list"], params["tenor_list"], s)]
@@ -734,17 +722,14 @@ class ScenarioGrid:
         ``gamma [S, n, P, P]`` (per request), or ``agg_*`` sums over the trades when ``aggregate``."""
         reqs = set(reqs)
         batch = compile_ois(list(derivatives), self.curve._value_dt)
-        trades = _native.DeviceTrades(self._ctx, batch)
         outs = []
-        try:
+        with _native.DeviceTrades(self._ctx, batch) as trades:
             for i in range(len(self)):
                 outs.append(_native.price(self._ctx, self._set[i], trades,
                                           want_value=RequestTypes.VALUE in reqs,
                                           want_delta=RequestTypes.DELTA in reqs,
                                           want_gamma=RequestTypes.GAMMA in reqs,
                                           per_trade=not aggregate, aggregate=aggregate))
-        finally:
-            trades.close()
         keys = outs[0].keys() if outs else ()
         return {k: np.stack([np.asarray(o[k]) for o in outs]) for k in keys}
 
@@ -754,18 +739,23 @@ class ScenarioGrid:
             self._dfs_host = np.stack([self._set.download(i)[0] for i in range(len(self))])
         return self._dfs_host
 
-    def _revalue(self, trades, per_trade, with_base):
-        batch, const, order = compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name])
-        dev = _native.DeviceTrades(self._ctx, batch)
-        try:
-            if with_base:
-                out = _native.scenario_pv(self._ctx, self.curve._interp_type.value, self.base.times,
-                                          np.vstack([self._dfs(), self.base.dfs[None, :]]), dev, per_trade=per_trade)
-            else:
-                out = _native.scenario_pv_set(self._ctx, self._set, dev, per_trade=per_trade)
-        finally:
-            dev.close()
-        return _finish(out, const, order, per_trade)
+    def _with_base(self):
+        """``(times, dfs [S + 1, K])``: the scenarios' rows with the base curve (the host builder's) appended as one more."""
+        return self.base.times, np.vstack([self._dfs(), self.base.dfs[None, :]])
+
+    def _curves(self, with_base) -> _Curves:
+        """The set read in place, or with ``with_base`` the host rows of `_with_base`."""
+        if with_base:
+            return _Curves("", (self.curve._interp_type.value, *self._with_base()), self._ctx)
+        return _Curves("_set", (self._set,), self._ctx)
+
+    def _book(self, trades):
+        return compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name])
+
+    def _credit_book(self, trades, spreads, buckets, spread_shocks, with_base):
+        """``(credit book, spread-shock rows)`` for the grid's scenarios, with ``with_base`` those of the base pair too."""
+        book = compile_credit_book(trades, self.curve._value_dt, CurveTypes[self.curve_name], spreads, buckets)
+        return book, _grid_spread_rows(_spread_rows(spread_shocks, len(book.labels)), len(self), len(book.labels), with_base)
 
     def revalue(self, trades, per_trade: bool = False):
         """The book's PV under every scenario, in ONE launch on the grid's own discount factors (`price` makes a
@@ -774,36 +764,14 @@ class ScenarioGrid:
         ``trades``: a list of `OIS`, `Bond` and single-curve `FRN` objects of the grid's curve (a mixed list is one
         batch) or a compiled `TradeBatch`; see `compile_book` for what is refused.  Only discount factors are read, so
         ``ScenarioGrid(..., with_gamma=False)`` is the cheaper grid to feed it (the builder still makes Jacobians)."""
-        return self._revalue(trades, per_trade, False)
+        return _revalue(self._curves(False), per_trade, self._book(trades))
 
     def pnl(self, trades) -> np.ndarray:
         """``[S]``: the book's PV under each scenario minus its PV on the unshocked curve.  The base curve
         (``self.base.dfs``, the host builder's) is priced by the same launch as one more scenario row, so the
         difference carries no noise between kernels: a zero shock whose curve has the base curve's bits gives 0."""
-        book = self._revalue(trades, False, True)["book_pv"]
+        book = _revalue(self._curves(True), False, self._book(trades))["book_pv"]
         return book[:-1] - book[-1]
-
-    def _revalue_credit(self, trades, spreads, buckets, spread_shocks, per_trade, with_base):
-        book = compile_credit_book(trades, self.curve._value_dt, CurveTypes[self.curve_name], spreads, buckets)
-        S, G = len(self), len(book.labels)
-        dz = _spread_rows(spread_shocks, G)
-        if dz is not None and dz.shape[0] not in (1, S):
-            raise LibError(f"{dz.shape[0]} spread-shock rows for a grid of {S} scenarios: one shared row or one per scenario")
-        dev = _native.DeviceTrades(self._ctx, book.batch)
-        try:
-            if with_base:
-                if dz is not None:              # the base pair: the unshocked curve with a zero spread shock
-                    dz = np.vstack([np.broadcast_to(dz, (S, G)), np.zeros((1, G))])
-                out = _native.credit_scenario_pv(self._ctx, self.curve._interp_type.value, self.base.times,
-                                                 np.vstack([self._dfs(), self.base.dfs[None, :]]), dz, dev, book.z,
-                                                 book.bucket, book.fix_tau, book.flt_tau, per_trade=per_trade)
-            else:
-                out = _native.credit_scenario_pv_set(self._ctx, self._set, dz, dev, book.z, book.bucket, book.fix_tau,
-                                                     book.flt_tau, per_trade=per_trade)
-        finally:
-            dev.close()
-        out["labels"] = book.labels
-        return _finish(out, book.pv_const, book.order, per_trade)
 
     def revalue_credit(self, trades, spreads, buckets=None, spread_shocks=None, per_trade: bool = False):
         """`revalue` for a credit book: bonds discounted at their z-spreads, FRNs at their discount margins, and
@@ -813,28 +781,15 @@ class ScenarioGrid:
         one column per bucket in order of first appearance (`shocked_spreads` makes a row from basis points), one
         shared row ``[G]``, or None (curve shocks only).  The grid's curves are read where the device builder left
         them.  Returns ``{"book_pv": [S], "labels": [...]}`` and, with ``per_trade``, ``"pv": [S, n]``."""
-        return self._revalue_credit(trades, spreads, buckets, spread_shocks, per_trade, False)
+        return _revalue(self._curves(False), per_trade, *self._credit_book(trades, spreads, buckets, spread_shocks, False))
 
     def pnl_credit(self, trades, spreads, buckets=None, spread_shocks=None) -> np.ndarray:
         """``[S]``: the credit book's PV under each (curve, spread shock) pair minus its PV on the unshocked curve with
         unshocked spreads.  As in `pnl`, the base pair is one more row of the same launch: a zero curve shock with a
         zero spread shock gives exactly 0."""
-        book = self._revalue_credit(trades, spreads, buckets, spread_shocks, False, True)["book_pv"]
+        book = _revalue(self._curves(True), False,
+                        *self._credit_book(trades, spreads, buckets, spread_shocks, True))["book_pv"]
         return book[:-1] - book[-1]
-
-    def _revalue_sub_books(self, trades, keys, per_trade, with_base):
-        sb = split_sub_books(*compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name]), keys)
-        dev = _native.DeviceTrades(self._ctx, sb.batch)
-        try:
-            if with_base:
-                out = _native.scenario_subbook_pv(self._ctx, self.curve._interp_type.value, self.base.times,
-                                                  np.vstack([self._dfs(), self.base.dfs[None, :]]), dev, sb.sub_off,
-                                                  per_trade=per_trade)
-            else:
-                out = _native.scenario_subbook_pv_set(self._ctx, self._set, dev, sb.sub_off, per_trade=per_trade)
-        finally:
-            dev.close()
-        return _finish_sub_books(out, sb, per_trade)
 
     def revalue_sub_books(self, trades, keys, per_trade: bool = False):
         """`revalue` per sub-book, in the SAME single launch: ``keys`` holds one hashable value per trade (a desk, a
@@ -842,64 +797,39 @@ class ScenarioGrid:
         appearance, row ``b`` the PV vector of sub-book ``labels[b]`` - bit for bit `revalue`'s ``book_pv`` on that
         sub-book alone, ready for `historical_var` - and, with ``per_trade``, ``"pv": [S, n]`` in the caller's order.
         A `TradeBatch` must hold each label's trades consecutively (`split_sub_books`)."""
-        return self._revalue_sub_books(trades, keys, per_trade, False)
+        return _revalue(self._curves(False), per_trade, self._book(trades), None, keys)
 
     def pnl_sub_books(self, trades, keys) -> np.ndarray:
         """``[B, S]``: `pnl` per sub-book (rows in the order of `revalue_sub_books`' labels), the base curve priced by
         the same launch as one more scenario: a zero shock gives exactly 0 in every sub-book."""
-        sub = self._revalue_sub_books(trades, keys, False, True)["sub_pv"]
+        sub = _revalue(self._curves(True), False, self._book(trades), None, keys)["sub_pv"]
         return sub[:, :-1] - sub[:, -1:]
 
     def sub_book_var_es(self, trades, keys, level: float = 0.99):
         """``{"labels": [...], "var": [B], "es": [B]}`` straight from the trades: the sub-book launch and the tail kernel
         in one chain, so the ``[B, S]`` P&L matrix never leaves the device.  The P&L is `pnl_sub_books`' (scenario minus
         base curve; what does not depend on the curve cancels and is not added), ``var`` and ``es`` are `tail_measures`'."""
-        sb = split_sub_books(*compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name]), keys)
+        sb = split_sub_books(*self._book(trades), keys)
         S = len(self)
         if S > _native.SCENARIO_TAIL_MAX:
             raise LibError(f"{S} scenarios: at most {_native.SCENARIO_TAIL_MAX} fit the tail kernel; use pnl_sub_books and "
                            "tail_measures")
-        dev = _native.DeviceTrades(self._ctx, sb.batch)
-        try:
-            var, es = _native.scenario_subbook_var_es(self._ctx, self.curve._interp_type.value, self.base.times,
-                                                      np.vstack([self._dfs(), self.base.dfs[None, :]]), dev, sb.sub_off,
-                                                      tail_count(level, S), base_col=S)
-        finally:
-            dev.close()
+        with _native.DeviceTrades(self._ctx, sb.batch) as dev:
+            var, es = _native.scenario_subbook_var_es(self._ctx, self.curve._interp_type.value, *self._with_base(), dev,
+                                                      sb.sub_off, tail_count(level, S), base_col=S)
         return {"labels": sb.labels, "var": var, "es": es}
-
-    def _revalue_credit_sub_books(self, trades, spreads, buckets, keys, spread_shocks, per_trade, with_base):
-        book = compile_credit_book(trades, self.curve._value_dt, CurveTypes[self.curve_name], spreads, buckets)
-        S, G = len(self), len(book.labels)
-        dz = _spread_rows(spread_shocks, G)
-        if dz is not None and dz.shape[0] not in (1, S):
-            raise LibError(f"{dz.shape[0]} spread-shock rows for a grid of {S} scenarios: one shared row or one per scenario")
-        sb, z, bucket, fix_tau, flt_tau = _split_credit_sub_books(book, keys)
-        dev = _native.DeviceTrades(self._ctx, sb.batch)
-        try:
-            if with_base:
-                if dz is not None:              # the base pair: the unshocked curve with a zero spread shock
-                    dz = np.vstack([np.broadcast_to(dz, (S, G)), np.zeros((1, G))])
-                out = _native.credit_scenario_subbook_pv(self._ctx, self.curve._interp_type.value, self.base.times,
-                                                         np.vstack([self._dfs(), self.base.dfs[None, :]]), dz, dev, z, bucket,
-                                                         fix_tau, flt_tau, sb.sub_off, per_trade=per_trade)
-            else:
-                out = _native.credit_scenario_subbook_pv_set(self._ctx, self._set, dz, dev, z, bucket, fix_tau, flt_tau,
-                                                             sb.sub_off, per_trade=per_trade)
-        finally:
-            dev.close()
-        out["buckets"] = book.labels
-        return _finish_sub_books(out, sb, per_trade)
 
     def revalue_credit_sub_books(self, trades, spreads, keys, buckets=None, spread_shocks=None, per_trade: bool = False):
         """`revalue_credit` per sub-book in one launch; ``keys`` as in `revalue_sub_books` (a sub-book may cut across
         credit buckets).  Returns ``{"labels": [...], "sub_pv": [B, S], "buckets": [...]}`` - ``buckets`` the credit-bucket
         labels, one column of ``spread_shocks`` each - and, with ``per_trade``, ``"pv": [S, n]``."""
-        return self._revalue_credit_sub_books(trades, spreads, buckets, keys, spread_shocks, per_trade, False)
+        return _revalue(self._curves(False), per_trade,
+                        *self._credit_book(trades, spreads, buckets, spread_shocks, False), keys)
 
     def pnl_credit_sub_books(self, trades, spreads, keys, buckets=None, spread_shocks=None) -> np.ndarray:
         """``[B, S]``: `pnl_credit` per sub-book, the base pair priced by the same launch as one more row."""
-        sub = self._revalue_credit_sub_books(trades, spreads, buckets, keys, spread_shocks, False, True)["sub_pv"]
+        sub = _revalue(self._curves(True), False,
+                       *self._credit_book(trades, spreads, buckets, spread_shocks, True), keys)["sub_pv"]
         return sub[:, :-1] - sub[:, -1:]
 
     def close(self):

@@ -513,7 +513,7 @@ def _price_fused(engine, swaps, want_value, want_delta, per_trade, aggregate):
             frn = _native.price_xccy_foreign(ctx, for_cur["dev"], x_dev, for_tr, want_value=want_value, want_delta=want_delta,
                                              per_trade=per_trade, aggregate=aggregate)
         except LibError as exc:
-            if "(-2)" in str(exc):          # ADR_ERR_UNSUPPORTED: not a book for this launch
+            if exc.status == _native.ADR_ERR_UNSUPPORTED:          # not a book for this launch
                 return None
             raise
         dom = _native.price(ctx, dom_cur["dev"], dom_tr, want_value=want_value, want_delta=want_delta, want_gamma=False,

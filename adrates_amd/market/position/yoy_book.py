@@ -149,13 +149,8 @@ class YoYBook:
         builder's base curve appended), so the difference carries no noise between kernels and a zero shock gives
         exactly 0."""
         b = self._breakeven_rows(grid, inflation_shocks, breakevens)
-        im, T, b0 = inflation_inputs(self.inflation_curve)
-        if grid is not None:
-            times, dfs, ctx = grid.base.times, np.vstack([grid._dfs(), grid.base.dfs[None, :]]), grid._ctx
-        else:
-            cur = self._engine._device_curve(self.curve)
-            times, dfs, ctx = cur["host"].times, cur["host"].dfs, cur["ctx"]
-        rows = b0 if b is None else np.vstack([b, b0[None, :]])
+        im, T, _ = inflation_inputs(self.inflation_curve)
+        times, dfs, rows, ctx = self._base_pair(grid, b)
         book = revalue_yoy_on_curves(self.curve._interp_type.value, times, dfs, im, T, rows, self._arrays(),
                                      self.model.value_dt, ctx=ctx)["book_pv"]
         return book[:-1] - book[-1]
@@ -207,10 +202,11 @@ class YoYBook:
         return split_yoy_sub_books(*self._arrays(), keys)
 
     def _base_pair(self, grid, b):
-        """``(times, dfs, breakeven rows, ctx)`` with the unshocked pair appended as one more scenario, as `pnl` does."""
+        """``(times, dfs, breakeven rows, ctx)`` with the unshocked pair appended as one more scenario (the grid's rows with
+        the host builder's base curve, `ScenarioGrid._with_base`): what `pnl` and the sub-book forms price."""
         _, _, b0 = inflation_inputs(self.inflation_curve)
         if grid is not None:
-            times, dfs, ctx = grid.base.times, np.vstack([grid._dfs(), grid.base.dfs[None, :]]), grid._ctx
+            (times, dfs), ctx = grid._with_base(), grid._ctx
         else:
             cur = self._engine._device_curve(self.curve)
             times, dfs, ctx = cur["host"].times, cur["host"].dfs, cur["ctx"]

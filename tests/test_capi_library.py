@@ -47,6 +47,44 @@ def test_no_cpu_fallback(native_lib):
         swap.position(model).compute([RequestTypes.VALUE])
 
 
+def test_lib_error_carries_the_status_code(native_lib):
+    """`_native._check` puts the library's return code on the `LibError` as ``status``: callers compare the code (the
+    cross-currency engine's fallback on ADR_ERR_UNSUPPORTED), not the message text."""
+    import numpy as np
+    with pytest.raises(LibError) as err:
+        _native.scenario_subbook_plan(3, [0, 2])
+    assert err.value.status < 0 and err.value.status == int(re.search(r"failed \((-?\d+)\)", str(err.value)).group(1))
+    with pytest.raises(LibError) as err:
+        _native.scenario_tail_alloc_host(np.zeros((2, _native.SCENARIO_ALLOC_MAX + 1)), 3)
+    assert err.value.status == _native.ADR_ERR_UNSUPPORTED and "(-2)" in str(err.value)
+    assert LibError("raised in Python").status is None
+
+
+def test_lib_error_frees_its_frames_at_once(native_lib):
+    """The error `_check` raises is in no reference cycle: once it is handled, the frames it passed through - and the
+    contexts and uploaded batches they hold - are freed then and in order, not whenever the cycle collector next runs."""
+    import gc
+    import weakref
+
+    class Held:
+        pass
+
+    def caller():
+        held = Held()
+        try:
+            _native.scenario_subbook_plan(3, [0, 2])
+        except LibError:
+            pass
+        return weakref.ref(held)
+
+    gc.collect()
+    gc.disable()
+    try:
+        assert caller()() is None
+    finally:
+        gc.enable()
+
+
 def test_product_never_imports_oracle():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     bad = []

@@ -54,7 +54,8 @@ def _host_no_two_curve_launch(ctx, *a, **k):
     fallback of the product path.  The one-launch path is compared with it and with the oracle on the GPU
     (tests/test_gpu_xccy.py)."""
     from adrates_amd.utils.error import LibError
-    raise LibError("adr_price_xccy_foreign failed (-2): no two-curve launch on the host stand-in")
+    raise LibError("adr_price_xccy_foreign failed (-2): no two-curve launch on the host stand-in",
+                   status=_native.ADR_ERR_UNSUPPORTED)
 
 
 def _host_two_curve_launch(ctx, for_curve, x_curve, legs, want_value=True, want_delta=True, per_trade=True, aggregate=False):
