@@ -8,11 +8,9 @@
 // Discount factors come from the curve's OWN node set, interpolated like market/curves/interpolator.py::_point
 // (not curve_lookup.hpp's engine interpolation, which snaps knots and treats the ends differently).
 //
-// Layout: kGroup lanes per bond, flows dealt across the lanes (flow i on lane i % kGroup); the first kRegFlows flows of
-// each lane stay in VGPRs across the solver's iterations, later ones (long bonds) are re-derived from global memory on
-// every pass.  Each pass over the flows ends in one fixed-order butterfly over the group's lanes, so every lane holds the
-// same bits and a bond's results do not depend on the launch shape.  The host entry point runs the same per-bond code
-// with the same per-lane order and the same reduction tree.  No atomics.
+// Layout (measures_common.hpp): kGroup lanes per bond; the first kRegFlows flows of each lane stay in VGPRs across the
+// solver's iterations, later ones (long bonds) are re-derived from global memory on every pass.  The host entry point runs
+// the same per-bond code with the same per-lane order and the same reduction tree.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -22,10 +20,8 @@
 
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
+#include "measures_common.hpp"
 #include "node_df.hpp"
-
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
 
 // The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
 // exp / log implementations.
@@ -34,18 +30,12 @@ int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      /
 namespace adr {
 namespace bond {
 
-constexpr int kGroup = 16;                  // lanes per bond
+using namespace meas;
+
 constexpr int kRegFlows = 8;                // flows per lane held in registers (kGroup * kRegFlows = 128 per bond)
-constexpr int kBlock = 256;
-constexpr int kBondsPerBlock = kBlock / kGroup;
-constexpr int kMaxIter = 100;
-constexpr double kBump = 0.0001;            // 1bp, bond.py dv01 / cs01
+static_assert(ADR_BOND_MAX_NODES == kMaxNodes, "measures_common.hpp's checks");
 
 enum Kind { Z_NEWTON = 0, Z_PRICES = 1, Y_NEWTON = 2, Y_MOMENTS = 3 };
-
-struct V3 {
-    double a, b, c;
-};
 
 struct Args {
     int method, n_nodes;
@@ -89,10 +79,6 @@ __host__ __device__ inline V3 term(int kind, double x, double A, double tau, dou
     }
 }
 
-__host__ __device__ inline bool finite(double x) { return x - x == 0.0; }    // false for NaN and +-inf
-
-__host__ __device__ inline V3 add(V3 p, V3 q) { return {p.a + q.a, p.b + q.b, p.c + q.c}; }
-
 // The face at the unadjusted maturity, added after the pass (bond.py:488-503, 648-750); tau_M <= 0: matured.
 template <class Group>
 __host__ __device__ inline V3 pass(Group& g, int kind, double x, double face, double tauM) {
@@ -104,56 +90,7 @@ __host__ __device__ inline V3 pass(Group& g, int kind, double x, double face, do
     return s;
 }
 
-// Root of pass(x).a - target.  The bracket [lo, hi] first (brentq's test: no sign change -> fall back); inside it a
-// safeguarded Newton whose steps are clipped into the shrinking sign-change bracket (bisection when a step leaves it).
-// Without a bracket an unbracketed Newton from x0.  Stop when |step| <= 1e-15 max(1, |x|) or after kMaxIter steps.
-// Returns 0 (bracketed), 1 (fallback converged) or 2 (no root).
-template <class Group>
-__host__ __device__ inline int solve(Group& g, int kind, double face, double tauM, double target, double lo, double hi,
-                                     double x0, double* root) {
-    V3 pa = pass(g, kind, lo, face, tauM), pb = pass(g, kind, hi, face, tauM);
-    double fa = pa.a - target, fb = pb.a - target;
-    if (fa == 0.0) { *root = lo; return 0; }
-    if (fb == 0.0) { *root = hi; return 0; }
-    if (fa * fb < 0.0) {
-        double a = lo, b = hi;
-        double x = a - fa / pa.b;
-        if (!(x > a && x < b)) x = 0.5 * (a + b);
-        for (int it = 0; it < kMaxIter; ++it) {
-            const V3 p = pass(g, kind, x, face, tauM);
-            const double f = p.a - target;
-            if (f == 0.0) break;
-            if ((f < 0.0) == (fa < 0.0)) { a = x; fa = f; } else { b = x; }
-            double xn = x - f / p.b;
-            if (!(xn > fmin(a, b) && xn < fmax(a, b))) xn = 0.5 * (a + b);
-            const double step = xn - x;
-            x = xn;
-            if (fabs(step) <= 1e-15 * fmax(1.0, fabs(x))) break;
-        }
-        *root = x;
-        return 0;
-    }
-    double x = x0;
-    for (int it = 0; it < kMaxIter; ++it) {
-        const V3 p = pass(g, kind, x, face, tauM);
-        const double f = p.a - target;
-        if (!finite(f) || !finite(p.b)) break;
-        if (f == 0.0) { *root = x; return 1; }
-        if (p.b == 0.0) break;
-        const double xn = x - f / p.b;
-        if (!finite(xn)) break;
-        const double step = xn - x;
-        x = xn;
-        if (fabs(step) <= 1e-15 * fmax(1.0, fabs(x))) { *root = x; return 1; }
-    }
-    *root = NAN;
-    return 2;
-}
-
-struct Result {
-    double v[ADR_BOND_OUTPUTS];
-    int32_t status;
-};
+using Result = meas::Result<ADR_BOND_OUTPUTS>;
 
 template <class Group>
 __host__ __device__ inline Result measures(Group& g, double face, double tauM, double acc100, double quote, int quote_is_z) {
@@ -162,9 +99,9 @@ __host__ __device__ inline Result measures(Group& g, double face, double tauM, d
     int sz = 0;
     if (!quote_is_z) {
         const double target = ((quote + acc100) / 100.0) * face;
-        sz = solve(g, Z_NEWTON, face, tauM, target, -0.1, 0.5, 0.01, &z);
+        sz = solve([&](double x) { return pass(g, Z_NEWTON, x, face, tauM); }, target, -0.1, 0.5, 0.01, &z);
     }
-    if (sz == 2) {
+    if (sz == 2) {                                          // nan_result(2), written in place: see the kernel
         for (int k = 0; k < ADR_BOND_OUTPUTS; ++k) r.v[k] = NAN;
         r.status = 2;
         return r;
@@ -177,7 +114,8 @@ __host__ __device__ inline Result measures(Group& g, double face, double tauM, d
     r.v[ADR_BOND_CLEAN] = clean;
     r.v[ADR_BOND_DV01] = (p.b - p.c) / 2.0;
     double y = NAN;
-    const int sy = solve(g, Y_NEWTON, face, tauM, ((clean + acc100) / 100.0) * face, -0.5, 0.5, 0.05, &y);
+    const int sy = solve([&](double x) { return pass(g, Y_NEWTON, x, face, tauM); }, ((clean + acc100) / 100.0) * face, -0.5, 0.5,
+                         0.05, &y);
     r.v[ADR_BOND_YTM] = y;
     r.v[ADR_BOND_DURATION] = r.v[ADR_BOND_CONVEXITY] = NAN;
     if (sy != 2) {
@@ -226,13 +164,7 @@ struct DeviceGroup {
             flow(f0 + i, Ai, ti, ci);
             s = add(s, term(kind, x, Ai, ti, ci));
         }
-#pragma unroll
-        for (int m = kGroup / 2; m >= 1; m >>= 1) {
-            s.a = s.a + __shfl_xor(s.a, m);
-            s.b = s.b + __shfl_xor(s.b, m);
-            s.c = s.c + __shfl_xor(s.c, m);
-        }
-        return s;
+        return group_sum(s);
     }
 };
 
@@ -243,12 +175,14 @@ __global__ __launch_bounds__(kBlock) void bond_measures_kernel(Args a) {
         s_d[k] = a.node_df[k];
     }
     __syncthreads();
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * kBondsPerBlock + threadIdx.x / kGroup;
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * kPerBlock + threadIdx.x / kGroup;
     if (b >= a.n) return;
     const int lane = threadIdx.x % kGroup;
     const int64_t f0 = a.flow_off[b], f1 = a.flow_off[b + 1];
     Result r;
-    if (f1 < f0 || f1 - f0 > (int64_t(1) << 30)) {          // malformed offsets: no reads, NaN and status 2
+    // malformed offsets: no reads, NaN and status 2 - nan_result(2), written in place here and in measures because the
+    // call orders the constant moves of these paths differently, and the kernel's instructions are kept as they were
+    if (f1 < f0 || f1 - f0 > kMaxFlows) {
         for (int k = 0; k < ADR_BOND_OUTPUTS; ++k) r.v[k] = NAN;
         r.status = 2;
     } else {
@@ -265,7 +199,6 @@ __global__ __launch_bounds__(kBlock) void bond_measures_kernel(Args a) {
 }
 
 // -------------------------------------------------------------------------------------------------------------- host
-// The device's lanes in sequence: lane l sums flows l, l + kGroup, ... in order, then the butterfly's tree (lane 0's view).
 struct HostGroup {
     const double* A;
     const double* tau;
@@ -273,14 +206,7 @@ struct HostGroup {
     int nf;
 
     V3 sum(int kind, double x) const {
-        V3 p[kGroup];
-        for (int l = 0; l < kGroup; ++l) {
-            p[l] = {0.0, 0.0, 0.0};
-            for (int i = l; i < nf; i += kGroup) p[l] = add(p[l], term(kind, x, A[i], tau[i], c[i]));
-        }
-        for (int m = kGroup / 2; m >= 1; m >>= 1)
-            for (int l = 0; l < m; ++l) p[l] = add(p[l], p[l + m]);
-        return p[0];
+        return host_group_sum(nf, [&](int i) { return term(kind, x, A[i], tau[i], c[i]); });
     }
 };
 
@@ -288,11 +214,9 @@ int validate(const char* who, int method, int n_nodes, const double* node_t, con
              const void* off, const void* T, const void* tau, const void* cpn, const void* prin, const void* Ts,
              const void* tauM, const void* face, const void* acc, const void* quote, const void* out, const void* status) {
     const std::string w(who);
-    if (method != ADR_INTERP_FLAT_FWD_RATES && method != ADR_INTERP_LINEAR_FWD_RATES && method != ADR_INTERP_LINEAR_ZERO_RATES)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and LINEAR_ZERO_RATES (4)");
-    if (n_nodes < 2 || n_nodes > ADR_BOND_MAX_NODES)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": the curve needs 2 .. ADR_BOND_MAX_NODES (1024) nodes");
-    if (!node_t || !node_df) return adr_set_error(ADR_ERR_INVALID, w + ": null node arrays");
+    int rc = check_scheme(w, method);
+    if (rc == ADR_OK) rc = check_node_table(w, n_nodes, node_t, node_df, ": the curve needs 2 .. ADR_BOND_MAX_NODES (1024) nodes");
+    if (rc != ADR_OK) return rc;
     if (n < 0 || (n > 0 && (!off || !Ts || !tauM || !face || !acc || !quote || !out || !status)))
         return adr_set_error(ADR_ERR_INVALID, w + ": bad count / null array");
     (void)T; (void)tau; (void)cpn; (void)prin;
@@ -302,14 +226,11 @@ int validate(const char* who, int method, int n_nodes, const double* node_t, con
 int check_host_arrays(const char* who, int n_nodes, const double* node_t, int64_t n, const int64_t* off, const double* T,
                       const double* tau, const double* cpn, const double* prin, const double* Ts) {
     const std::string w(who);
-    for (int k = 0; k < n_nodes; ++k)
-        if (!std::isfinite(node_t[k]) || (k > 0 && !(node_t[k] > node_t[k - 1])))
-            return adr_set_error(ADR_ERR_INVALID, w + ": node times must be finite and increasing");
-    if (n == 0) return ADR_OK;
+    int rc = check_node_times(w, n_nodes, node_t);
+    if (rc != ADR_OK || n == 0) return rc;
     if (off[0] != 0) return adr_set_error(ADR_ERR_INVALID, w + ": flow_off[0] must be 0");
-    for (int64_t b = 0; b < n; ++b)
-        if (off[b + 1] < off[b] || off[b + 1] - off[b] > (int64_t(1) << 30))
-            return adr_set_error(ADR_ERR_INVALID, w + ": flow offsets must be non-decreasing");
+    rc = check_offsets(w, n, off, "flow");
+    if (rc != ADR_OK) return rc;
     const int64_t m = off[n];
     if (m > 0 && (!T || !tau || !cpn || !prin)) return adr_set_error(ADR_ERR_INVALID, w + ": null flow arrays");
     for (int64_t i = 0; i < m; ++i)
@@ -337,22 +258,9 @@ int adr_bond_measures_dev(adr_ctx* ctx, int interp_method, int n_nodes, const do
     int rc = B::validate("adr_bond_measures_dev", interp_method, n_nodes, node_t, node_df, n, flow_off, flow_T, flow_tau,
                          flow_cpn, flow_prin, bond_Ts, bond_tauM, bond_face, bond_acc100, bond_quote, out, status);
     if (rc != ADR_OK) return rc;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
-    if (rc != ADR_OK) return rc;
-    if (n == 0) return ADR_OK;
-    if (stream_v) stream = static_cast<hipStream_t>(stream_v);
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures_dev: ") + hipGetErrorString(e));
-    B::Args a{interp_method, n_nodes, node_t, node_df, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin, bond_Ts, bond_tauM,
-              bond_face, bond_acc100, bond_quote, quote_is_z ? 1 : 0, out, status};
-    const int64_t blocks = (n + B::kBondsPerBlock - 1) / B::kBondsPerBlock;
-    if (blocks > 0x7fffffff) return adr_set_error(ADR_ERR_UNSUPPORTED, "adr_bond_measures_dev: too many bonds for one launch");
-    hipLaunchKernelGGL(B::bond_measures_kernel, dim3(static_cast<unsigned>(blocks)), dim3(B::kBlock), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures_dev: ") + hipGetErrorString(e));
-    return ADR_OK;
+    const B::Args a{interp_method, n_nodes, node_t, node_df, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin, bond_Ts, bond_tauM,
+                    bond_face, bond_acc100, bond_quote, quote_is_z ? 1 : 0, out, status};
+    return adr::meas::launch("adr_bond_measures_dev", ctx, stream_v, B::bond_measures_kernel, a, "bonds");
 }
 
 int adr_bond_measures(adr_ctx* ctx, int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,
@@ -364,12 +272,9 @@ int adr_bond_measures(adr_ctx* ctx, int interp_method, int n_nodes, const double
                          bond_Ts, bond_tauM, bond_face, bond_acc100, bond_quote, out, status);
     if (rc == ADR_OK) rc = B::check_host_arrays(who, n_nodes, node_t, n, flow_off, flow_T, flow_tau, flow_cpn, flow_prin, bond_Ts);
     if (rc != ADR_OK) return rc;
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = adr::meas::target_stream(who, ctx, n, nullptr, &stream);
     if (rc != ADR_OK || n == 0) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures: ") + hipGetErrorString(e));
     const int64_t m = flow_off[n];
     const size_t d = sizeof(double);
     // one allocation: nodes, flows, bonds, outputs, then the offsets and the status words
@@ -377,33 +282,25 @@ int adr_bond_measures(adr_ctx* ctx, int interp_method, int n_nodes, const double
                          ADR_BOND_OUTPUTS * static_cast<size_t>(n);
     const size_t bytes = n_dbl * d + static_cast<size_t>(n + 1) * sizeof(int64_t) + static_cast<size_t>(n) * sizeof(int32_t);
     char* base = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures: hipMalloc: ") + hipGetErrorString(e));
-    double* p = reinterpret_cast<double*>(base);
-    struct Piece { const void* src; size_t bytes; };
-    double *dt = p, *dd = dt + n_nodes, *dT = dd + n_nodes, *dtau = dT + m, *dcpn = dtau + m, *dprin = dcpn + m;
-    double *dTs = dprin + m, *dtauM = dTs + n, *dface = dtauM + n, *dacc = dface + n, *dquote = dacc + n, *dout = dquote + n;
+    double *dt = reinterpret_cast<double*>(base), *dd = dt + n_nodes, *dT = dd + n_nodes, *dtau = dT + m, *dcpn = dtau + m;
+    double *dprin = dcpn + m, *dTs = dprin + m, *dtauM = dTs + n, *dface = dtauM + n, *dacc = dface + n, *dquote = dacc + n;
+    double* dout = dquote + n;
     int64_t* doff = reinterpret_cast<int64_t*>(dout + ADR_BOND_OUTPUTS * n);
     int32_t* dstatus = reinterpret_cast<int32_t*>(doff + n + 1);
-    const Piece pieces[] = {{node_t, n_nodes * d}, {node_df, n_nodes * d}, {flow_T, m * d}, {flow_tau, m * d},
-                            {flow_cpn, m * d},     {flow_prin, m * d},     {bond_Ts, n * d}, {bond_tauM, n * d},
-                            {bond_face, n * d},    {bond_acc100, n * d},   {bond_quote, n * d}};
-    char* dst = base;
-    for (const Piece& pc : pieces) {
-        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
-        dst += pc.bytes;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(doff, flow_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+    const adr::call::Piece in[] = {{dt, node_t, n_nodes * d}, {dd, node_df, n_nodes * d}, {dT, flow_T, m * d},
+                                   {dtau, flow_tau, m * d},   {dcpn, flow_cpn, m * d},    {dprin, flow_prin, m * d},
+                                   {dTs, bond_Ts, n * d},     {dtauM, bond_tauM, n * d},  {dface, bond_face, n * d},
+                                   {dacc, bond_acc100, n * d}, {dquote, bond_quote, n * d},
+                                   {doff, flow_off, (n + 1) * sizeof(int64_t)}};
+    const adr::call::Piece res[] = {{out, dout, ADR_BOND_OUTPUTS * n * d}, {status, dstatus, n * sizeof(int32_t)}};
+    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess)
         rc = adr_bond_measures_dev(ctx, interp_method, n_nodes, dt, dd, n, doff, dT, dtau, dcpn, dprin, dTs, dtauM, dface, dacc,
                                    dquote, quote_is_z, dout, dstatus, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, ADR_BOND_OUTPUTS * n * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(status, dstatus, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipStreamSynchronize(stream);
-    hipFree(base);
-    if (rc != ADR_OK) return rc;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures: ") + hipGetErrorString(e));
-    return ADR_OK;
+    if (e == hipSuccess && rc == ADR_OK) e = adr::call::copy_pieces(res, hipMemcpyDeviceToHost, stream);
+    return adr::call::finish_blocking(who, rc, e, stream, base);
 }
 
 int adr_bond_measures_host(int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,

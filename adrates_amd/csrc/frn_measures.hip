@@ -12,12 +12,10 @@
 // Each solver pass costs one exp per flow; the projection is not repeated.  Discount factors come from the curves' OWN
 // node sets (node_df.hpp), as `DiscountCurve.df` reads them.
 //
-// Layout (that of bond_measures.hip): kGroup lanes per FRN, coupons dealt across the lanes (coupon i on lane i % kGroup);
-// the first kRegFlows coupons of each lane stay projected in VGPRs, later ones (FRNs with more than kGroup * kRegFlows
-// coupons left) are projected again from global memory on every pass.  Both node tables are staged in LDS once per
-// block.  Each pass ends in one fixed-order butterfly over the group's lanes, so every lane holds the same bits and an
-// FRN's results do not depend on the launch shape.  The host entry point runs the same per-FRN code with the same
-// per-lane order and reduction tree.  No atomics.
+// Layout (measures_common.hpp): kGroup lanes per FRN; the first kRegFlows coupons of each lane stay projected in VGPRs,
+// later ones (FRNs with more than kGroup * kRegFlows coupons left) are projected again from global memory on every pass.
+// Both node tables are staged in LDS once per block.  The host entry point runs the same per-FRN code with the same
+// per-lane order and reduction tree.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,10 +25,8 @@
 
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
+#include "measures_common.hpp"
 #include "node_df.hpp"
-
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
 
 // The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
 // exp / log implementations.
@@ -39,19 +35,13 @@ int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      /
 namespace adr {
 namespace frn {
 
-constexpr int kGroup = 16;                  // lanes per FRN
+using namespace meas;
+
 constexpr int kRegFlows = 24;               // coupons per lane held in registers (384 per FRN: 30Y monthly fits)
-constexpr int kBlock = 256;
-constexpr int kFrnsPerBlock = kBlock / kGroup;
-constexpr int kMaxIter = 100;
-constexpr double kBump = 0.0001;            // 1bp, frn.py modified_duration / dv01
 constexpr double kLo = -0.10, kHi = 0.20;   // frn.py discount_margin: brentq's bracket
+static_assert(ADR_FRN_MAX_NODES == kMaxNodes, "measures_common.hpp's checks");
 
 enum Kind { NEWTON = 0, PRICES = 1 };
-
-struct V3 {
-    double a, b, c;
-};
 
 struct Nodes {
     const double* t;
@@ -109,10 +99,6 @@ __host__ __device__ inline V3 term(int kind, double x, double A, double tau) {
     return {A * exp(-x * tau), A * exp(-(x + kBump) * tau), A * exp(-(x - kBump) * tau)};
 }
 
-__host__ __device__ inline bool finite(double x) { return x - x == 0.0; }    // false for NaN and +-inf
-
-__host__ __device__ inline V3 add(V3 p, V3 q) { return {p.a + q.a, p.b + q.b, p.c + q.c}; }
-
 // The face at the adjusted maturity, added after the pass (frn.py:334-349); AM is NaN when it is not paid.
 template <class Group>
 __host__ __device__ inline V3 pass(Group& g, int kind, double x, double AM, double tauM) {
@@ -121,69 +107,16 @@ __host__ __device__ inline V3 pass(Group& g, int kind, double x, double AM, doub
     return s;
 }
 
-// Root of pass(x).a - target: bond_measures.hip's scheme on frn.py's bracket.  brentq's test first (no sign change ->
-// fall back); inside the bracket a safeguarded Newton whose steps are clipped into the shrinking sign-change bracket;
-// without one an unbracketed Newton from x0.  Returns 0 (bracketed), 1 (fallback converged) or 2 (no root).
-template <class Group>
-__host__ __device__ inline int solve(Group& g, double AM, double tauM, double target, double x0, double* root) {
-    V3 pa = pass(g, NEWTON, kLo, AM, tauM), pb = pass(g, NEWTON, kHi, AM, tauM);
-    double fa = pa.a - target, fb = pb.a - target;
-    if (fa == 0.0) { *root = kLo; return 0; }
-    if (fb == 0.0) { *root = kHi; return 0; }
-    if (fa * fb < 0.0) {
-        double a = kLo, b = kHi;
-        double x = a - fa / pa.b;
-        if (!(x > a && x < b)) x = 0.5 * (a + b);
-        for (int it = 0; it < kMaxIter; ++it) {
-            const V3 p = pass(g, NEWTON, x, AM, tauM);
-            const double f = p.a - target;
-            if (f == 0.0) break;
-            if ((f < 0.0) == (fa < 0.0)) { a = x; fa = f; } else { b = x; }
-            double xn = x - f / p.b;
-            if (!(xn > fmin(a, b) && xn < fmax(a, b))) xn = 0.5 * (a + b);
-            const double step = xn - x;
-            x = xn;
-            if (fabs(step) <= 1e-15 * fmax(1.0, fabs(x))) break;
-        }
-        *root = x;
-        return 0;
-    }
-    double x = x0;
-    for (int it = 0; it < kMaxIter; ++it) {
-        const V3 p = pass(g, NEWTON, x, AM, tauM);
-        const double f = p.a - target;
-        if (!finite(f) || !finite(p.b)) break;
-        if (f == 0.0) { *root = x; return 1; }
-        if (p.b == 0.0) break;
-        const double xn = x - f / p.b;
-        if (!finite(xn)) break;
-        const double step = xn - x;
-        x = xn;
-        if (fabs(step) <= 1e-15 * fmax(1.0, fabs(x))) { *root = x; return 1; }
-    }
-    *root = NAN;
-    return 2;
-}
-
-struct Result {
-    double v[ADR_FRN_OUTPUTS];
-    int32_t status;
-};
-
-__host__ __device__ inline Result nan_result(int32_t status) {
-    Result r;
-    for (int k = 0; k < ADR_FRN_OUTPUTS; ++k) r.v[k] = NAN;
-    r.status = status;
-    return r;
-}
+using Result = meas::Result<ADR_FRN_OUTPUTS>;
 
 template <class Group>
 __host__ __device__ inline Result measures(Group& g, double face, double AM, double tauM, double acc100, double quote,
                                            double guess, int quote_is_dm) {
     double dm = quote;
     int s = 0;
-    if (!quote_is_dm) s = solve(g, AM, tauM, ((quote + acc100) / 100.0) * face, guess, &dm);
-    if (s == 2) return nan_result(2);
+    if (!quote_is_dm)
+        s = solve([&](double x) { return pass(g, NEWTON, x, AM, tauM); }, ((quote + acc100) / 100.0) * face, kLo, kHi, guess, &dm);
+    if (s == 2) return nan_result<ADR_FRN_OUTPUTS>(2);
     const V3 p = pass(g, PRICES, dm, AM, tauM);
     Result r;
     const double dirty = 100.0 * p.a / face;
@@ -220,10 +153,7 @@ struct DeviceGroup {
             }
         }
         for (int i = lane + kRegFlows * kGroup; i < nc; i += kGroup) project(disc, index, f, a->cpn, a->m, c0 + i, bad);
-        int any = bad ? 1 : 0;
-#pragma unroll
-        for (int m = kGroup / 2; m >= 1; m >>= 1) any |= __shfl_xor(any, m);
-        return any != 0;
+        return group_or(bad ? 1 : 0) != 0;
     }
 
     __device__ V3 sum(int kind, double x) const {
@@ -236,13 +166,7 @@ struct DeviceGroup {
             const double Ai = project(disc, index, f, a->cpn, a->m, c0 + i, bad);
             s = add(s, term(kind, x, Ai, a->cpn[ADR_FRN_CPN_TAU * a->m + c0 + i]));
         }
-#pragma unroll
-        for (int m = kGroup / 2; m >= 1; m >>= 1) {
-            s.a = s.a + __shfl_xor(s.a, m);
-            s.b = s.b + __shfl_xor(s.b, m);
-            s.c = s.c + __shfl_xor(s.c, m);
-        }
-        return s;
+        return group_sum(s);
     }
 };
 
@@ -257,14 +181,14 @@ __global__ __launch_bounds__(kBlock) void frn_measures_kernel(Args a) {
         s_id[k] = a.index.d[k];
     }
     __syncthreads();
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * kFrnsPerBlock + threadIdx.x / kGroup;
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * kPerBlock + threadIdx.x / kGroup;
     if (b >= a.n) return;
     const int lane = threadIdx.x % kGroup;
     const int64_t c0 = a.cpn_off[b], c1 = a.cpn_off[b + 1];
     const int64_t n = a.n;
     Result r;
     if (c0 < 0 || c1 < c0 || c1 > a.m) {                   // malformed offsets: no reads, NaN and status 2
-        r = nan_result(2);
+        r = nan_result<ADR_FRN_OUTPUTS>(2);
     } else {
         DeviceGroup g;
         g.a = &a;
@@ -275,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void frn_measures_kernel(Args a) {
         const double TM = a.frn[ADR_FRN_TM * n + b];
         const double AM = TM == TM ? g.f.face * (node_df(TM, g.disc.t, g.disc.d, g.disc.n, g.disc.method) / g.f.Ds) : NAN;
         if (g.load())
-            r = nan_result(3);
+            r = nan_result<ADR_FRN_OUTPUTS>(3);
         else
             r = measures(g, g.f.face, AM, a.frn[ADR_FRN_TAUM * n + b], a.frn[ADR_FRN_ACC100 * n + b],
                          a.frn[ADR_FRN_QUOTE * n + b], a.frn[ADR_FRN_GUESS * n + b], a.quote_is_dm);
@@ -287,8 +211,6 @@ __global__ __launch_bounds__(kBlock) void frn_measures_kernel(Args a) {
 }
 
 // -------------------------------------------------------------------------------------------------------------- host
-// The device's lanes in sequence: lane l sums coupons l, l + kGroup, ... in order, then the butterfly's tree (lane 0's
-// view).
 struct HostGroup {
     const double* A;
     const double* tau;
@@ -296,32 +218,18 @@ struct HostGroup {
     int64_t m;
 
     V3 sum(int kind, double x) const {
-        V3 p[kGroup];
-        for (int l = 0; l < kGroup; ++l) {
-            p[l] = {0.0, 0.0, 0.0};
-            for (int i = l; i < nc; i += kGroup) p[l] = add(p[l], term(kind, x, A[i], tau[ADR_FRN_CPN_TAU * m + i]));
-        }
-        for (int s = kGroup / 2; s >= 1; s >>= 1)
-            for (int l = 0; l < s; ++l) p[l] = add(p[l], p[l + s]);
-        return p[0];
+        return host_group_sum(nc, [&](int i) { return term(kind, x, A[i], tau[ADR_FRN_CPN_TAU * m + i]); });
     }
 };
-
-bool method_ok(int method) {
-    return method == ADR_INTERP_FLAT_FWD_RATES || method == ADR_INTERP_LINEAR_FWD_RATES ||
-           method == ADR_INTERP_LINEAR_ZERO_RATES;
-}
 
 int validate(const char* who, const Nodes& disc, const Nodes& index, int64_t n, int64_t m, const void* off, const void* cpn,
              const void* frn, const void* out, const void* status) {
     const std::string w(who);
-    if (!method_ok(disc.method) || !method_ok(index.method))
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and LINEAR_ZERO_RATES (4)");
-    for (const Nodes* c : {&disc, &index}) {
-        if (c->n < 2 || c->n > ADR_FRN_MAX_NODES)
-            return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": each curve needs 2 .. ADR_FRN_MAX_NODES (1024) nodes");
-        if (!c->t || !c->d) return adr_set_error(ADR_ERR_INVALID, w + ": null node arrays");
-    }
+    int rc = check_scheme(w, disc.method);
+    if (rc == ADR_OK) rc = check_scheme(w, index.method);
+    for (const Nodes* c : {&disc, &index})
+        if (rc == ADR_OK) rc = check_node_table(w, c->n, c->t, c->d, ": each curve needs 2 .. ADR_FRN_MAX_NODES (1024) nodes");
+    if (rc != ADR_OK) return rc;
     if (n < 0 || m < 0 || (n > 0 && (!off || !frn || !out || !status)) || (m > 0 && !cpn))
         return adr_set_error(ADR_ERR_INVALID, w + ": bad count / null array");
     return ADR_OK;
@@ -330,15 +238,13 @@ int validate(const char* who, const Nodes& disc, const Nodes& index, int64_t n, 
 int check_host_arrays(const char* who, const Nodes& disc, const Nodes& index, int64_t n, int64_t m, const int64_t* off,
                       const double* cpn, const double* frn) {
     const std::string w(who);
-    for (const Nodes* c : {&disc, &index})
-        for (int k = 0; k < c->n; ++k)
-            if (!std::isfinite(c->t[k]) || (k > 0 && !(c->t[k] > c->t[k - 1])))
-                return adr_set_error(ADR_ERR_INVALID, w + ": node times must be finite and increasing");
+    int rc = check_node_times(w, disc.n, disc.t);
+    if (rc == ADR_OK) rc = check_node_times(w, index.n, index.t);
+    if (rc != ADR_OK) return rc;
     if (n == 0) return m == 0 ? ADR_OK : adr_set_error(ADR_ERR_INVALID, w + ": coupons without FRNs");
     if (off[0] != 0 || off[n] != m) return adr_set_error(ADR_ERR_INVALID, w + ": cpn_off must run from 0 to m");
-    for (int64_t b = 0; b < n; ++b)
-        if (off[b + 1] < off[b] || off[b + 1] - off[b] > (int64_t(1) << 30))
-            return adr_set_error(ADR_ERR_INVALID, w + ": coupon offsets must be non-decreasing");
+    rc = check_offsets(w, n, off, "coupon");
+    if (rc != ADR_OK) return rc;
     for (int k = 0; k < ADR_FRN_FLOW_FIELDS; ++k)
         for (int64_t i = 0; i < m; ++i)
             if (!std::isfinite(cpn[k * m + i]))
@@ -377,21 +283,8 @@ int adr_frn_measures_dev(adr_ctx* ctx, int disc_method, int disc_n, const double
     const F::Nodes disc{disc_t, disc_df, disc_n, disc_method}, index{index_t, index_df, index_n, index_method};
     int rc = F::validate("adr_frn_measures_dev", disc, index, n, m, cpn_off, cpn, frn, out, status);
     if (rc != ADR_OK) return rc;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
-    if (rc != ADR_OK) return rc;
-    if (n == 0) return ADR_OK;
-    if (stream_v) stream = static_cast<hipStream_t>(stream_v);
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_frn_measures_dev: ") + hipGetErrorString(e));
     const F::Args a{disc, index, n, m, cpn_off, cpn, frn, quote_is_dm ? 1 : 0, out, status};
-    const int64_t blocks = (n + F::kFrnsPerBlock - 1) / F::kFrnsPerBlock;
-    if (blocks > 0x7fffffff) return adr_set_error(ADR_ERR_UNSUPPORTED, "adr_frn_measures_dev: too many FRNs for one launch");
-    hipLaunchKernelGGL(F::frn_measures_kernel, dim3(static_cast<unsigned>(blocks)), dim3(F::kBlock), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_frn_measures_dev: ") + hipGetErrorString(e));
-    return ADR_OK;
+    return adr::meas::launch("adr_frn_measures_dev", ctx, stream_v, F::frn_measures_kernel, a, "FRNs");
 }
 
 int adr_frn_measures(adr_ctx* ctx, int disc_method, int disc_n, const double* disc_t, const double* disc_df,
@@ -403,12 +296,9 @@ int adr_frn_measures(adr_ctx* ctx, int disc_method, int disc_n, const double* di
     int rc = F::validate(who, disc, index, n, m, cpn_off, cpn, frn, out, status);
     if (rc == ADR_OK) rc = F::check_host_arrays(who, disc, index, n, m, cpn_off, cpn, frn);
     if (rc != ADR_OK) return rc;
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = adr::meas::target_stream(who, ctx, n, nullptr, &stream);
     if (rc != ADR_OK || n == 0) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_frn_measures: ") + hipGetErrorString(e));
     const size_t d = sizeof(double);
     // one allocation: the two node tables, coupons, FRNs, outputs, then the offsets and the status words
     const size_t n_dbl = 2 * static_cast<size_t>(disc_n) + 2 * static_cast<size_t>(index_n) +
@@ -416,30 +306,23 @@ int adr_frn_measures(adr_ctx* ctx, int disc_method, int disc_n, const double* di
                          ADR_FRN_OUTPUTS * static_cast<size_t>(n);
     const size_t bytes = n_dbl * d + static_cast<size_t>(n + 1) * sizeof(int64_t) + static_cast<size_t>(n) * sizeof(int32_t);
     char* base = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_frn_measures: hipMalloc: ") + hipGetErrorString(e));
     double *ddt = reinterpret_cast<double*>(base), *ddd = ddt + disc_n, *dit = ddd + disc_n, *did = dit + index_n;
     double *dcpn = did + index_n, *dfrn = dcpn + ADR_FRN_FLOW_FIELDS * m, *dout = dfrn + ADR_FRN_FIELDS * n;
     int64_t* doff = reinterpret_cast<int64_t*>(dout + ADR_FRN_OUTPUTS * n);
     int32_t* dstatus = reinterpret_cast<int32_t*>(doff + n + 1);
-    struct Piece { void* dst; const void* src; size_t bytes; };
-    const Piece pieces[] = {{ddt, disc_t, disc_n * d},   {ddd, disc_df, disc_n * d},
-                            {dit, index_t, index_n * d}, {did, index_df, index_n * d},
-                            {dcpn, cpn, ADR_FRN_FLOW_FIELDS * m * d}, {dfrn, frn, ADR_FRN_FIELDS * n * d},
-                            {doff, cpn_off, (n + 1) * sizeof(int64_t)}};
-    for (const Piece& pc : pieces)
-        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
+    const adr::call::Piece in[] = {{ddt, disc_t, disc_n * d},   {ddd, disc_df, disc_n * d},
+                                   {dit, index_t, index_n * d}, {did, index_df, index_n * d},
+                                   {dcpn, cpn, ADR_FRN_FLOW_FIELDS * m * d}, {dfrn, frn, ADR_FRN_FIELDS * n * d},
+                                   {doff, cpn_off, (n + 1) * sizeof(int64_t)}};
+    const adr::call::Piece res[] = {{out, dout, ADR_FRN_OUTPUTS * n * d}, {status, dstatus, n * sizeof(int32_t)}};
+    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess)
         rc = adr_frn_measures_dev(ctx, disc_method, disc_n, ddt, ddd, index_method, index_n, dit, did, n, m, doff, dcpn, dfrn,
                                   quote_is_dm, dout, dstatus, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, ADR_FRN_OUTPUTS * n * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(status, dstatus, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipStreamSynchronize(stream);
-    const hipError_t ef = hipFree(base);
-    if (rc != ADR_OK) return rc;
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_frn_measures: ") + hipGetErrorString(e));
-    return ADR_OK;
+    if (e == hipSuccess && rc == ADR_OK) e = adr::call::copy_pieces(res, hipMemcpyDeviceToHost, stream);
+    return adr::call::finish_blocking(who, rc, e, stream, base);
 }
 
 int adr_frn_measures_host(int disc_method, int disc_n, const double* disc_t, const double* disc_df, int index_method,
@@ -464,7 +347,7 @@ int adr_frn_measures_host(int disc_method, int disc_n, const double* disc_t, con
             for (int i = 0; i < nc; ++i) A[i] = F::project(disc, index, f, cpn, m, c0 + i, bad);
             F::Result r;
             if (bad) {
-                r = F::nan_result(3);
+                r = F::nan_result<ADR_FRN_OUTPUTS>(3);
             } else {
                 F::HostGroup g{A.data(), cpn + c0, nc, m};
                 r = F::measures(g, f.face, AM, frn[ADR_FRN_TAUM * n + b], frn[ADR_FRN_ACC100 * n + b],

@@ -18,11 +18,10 @@
 #include <string>
 
 #include "../../include/adrates.h"
+#include "blocking_call.hpp"
 #include "kernels.hpp"
 #include "simple_interp.hpp"
 
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
 int adr_ctx_compute_units(const adr_ctx* ctx);                                  // capi.hip
 const adr::TradesDev* adr_trades_device_view(const adr_trades* trades, const adr_ctx** owner);              // capi.hip
 int adr_curve_set_device_view(const adr_curve_set* set, const adr_ctx** owner, int* method, int* K, int* S,
@@ -159,27 +158,9 @@ hipError_t launch_with_lds(Kernel kernel, const Args& a, size_t lds, dim3 grid, 
     return hipGetLastError();
 }
 
-// The stream a call on `ctx` runs on - the caller's, or else the ctx's own - with the ctx's device made current.
-inline int target_stream(const std::string& w, const adr_ctx* ctx, hipStream_t stream_or_null, hipStream_t* stream) {
-    int device = 0;
-    const int rc = adr_ctx_target(ctx, &device, stream);
-    if (rc != ADR_OK) return rc;
-    if (stream_or_null) *stream = stream_or_null;
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return ADR_OK;
-}
-
-// The end of a blocking call: wait for the stream, free the call's one allocation, report the first failure.
-inline int finish_blocking(const std::string& w, int rc, hipError_t e, hipStream_t stream, void* base) {
-    const hipError_t es = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = es;
-    const hipError_t ef = hipFree(base);
-    if (rc != ADR_OK) return rc;
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return ADR_OK;
-}
+// The stream of a call and the end of a blocking one: blocking_call.hpp's, under this namespace's names.
+using call::finish_blocking;
+using call::target_stream;
 
 // ------------------------------------------------------------------------------------------------------- host checks
 // The first failing check decides an entry's message, so each entry calls these in its own order.

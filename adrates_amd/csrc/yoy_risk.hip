@@ -27,11 +27,9 @@
 #include <vector>
 
 #include "../../include/adrates.h"
+#include "blocking_call.hpp"
 #include "host_pool.hpp"
 #include "simple_interp.hpp"
-
-int adr_set_error(int status, const std::string& msg);                          // capi.hip
-int adr_ctx_target(const adr_ctx* ctx, int* device, hipStream_t* stream);      // capi.hip
 
 // The host and the device evaluate the same expressions; no contraction into fma, so the two differ only by their
 // exp / log implementations.
@@ -343,13 +341,10 @@ int adr_yoy_risk_dev(adr_ctx* ctx, int disc_method, int K, const double* times, 
     if (rc != ADR_OK) return rc;
     const bool agg_on = req_mask & ADR_YOY_AGG;
     if (agg_on && n > 0 && !work) return adr_set_error(ADR_ERR_INVALID, std::string(who) + ": ADR_YOY_AGG without work");
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = adr::call::target_stream(who, ctx, static_cast<hipStream_t>(stream_v), &stream);
     if (rc != ADR_OK) return rc;
-    if (stream_v) stream = static_cast<hipStream_t>(stream_v);
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    hipError_t e = hipSuccess;
     const int64_t blocks = (n + Y::kChunk - 1) / Y::kChunk;
     if (blocks > 0x7fffffff) return adr_set_error(ADR_ERR_UNSUPPORTED, std::string(who) + ": too many swaps for one launch");
     if (blocks > 0) {
@@ -379,12 +374,9 @@ int adr_yoy_risk(adr_ctx* ctx, int disc_method, int K, const double* times, cons
                          gamma, agg);
     if (rc == ADR_OK) rc = Y::check_host_arrays(who, K, times, dfs, P, T, b, n, m, cpn_off, cpn);
     if (rc != ADR_OK) return rc;
-    int device = 0;
     hipStream_t stream = nullptr;
-    rc = adr_ctx_target(ctx, &device, &stream);
+    rc = adr::call::target_stream(who, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     const bool per = req_mask & ADR_YOY_PER_SWAP, agg_on = req_mask & ADR_YOY_AGG;
     const bool wv = per && (req_mask & ADR_REQ_VALUE), wd = per && (req_mask & ADR_REQ_DELTA);
     const bool wg = per && (req_mask & ADR_REQ_GAMMA);
@@ -395,7 +387,7 @@ int adr_yoy_risk(adr_ctx* ctx, int disc_method, int K, const double* times, cons
                          (amount ? m : 0) + (wv ? n : 0) + (wd ? n * P : 0) + (wg ? n * PP : 0) + (agg_on ? R + W : 0);
     const size_t bytes = n_dbl * d + static_cast<size_t>(n + 1) * sizeof(int64_t);
     char* base = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
     double* p = reinterpret_cast<double*>(base);
     auto take = [&p](int64_t count, bool on) { double* q = on ? p : nullptr; if (on) p += count; return q; };
@@ -404,24 +396,18 @@ int adr_yoy_risk(adr_ctx* ctx, int disc_method, int K, const double* times, cons
     double *damt = take(m, amount != nullptr), *dpv = take(n, wv), *ddl = take(n * P, wd), *dg = take(n * PP, wg);
     double *dagg = take(R, agg_on), *dwork = take(W, agg_on);
     int64_t* doff = reinterpret_cast<int64_t*>(p);
-    struct Piece { void* dst; const void* src; size_t bytes; };
-    const Piece in[] = {{dt, times, K * d}, {ddf, dfs, K * d}, {dT, T, P * d}, {db, b, P * d},
-                        {dcpn, cpn, ADR_YOY_FIELDS * m * d}, {doff, cpn_off, n > 0 ? (n + 1) * sizeof(int64_t) : 0}};
-    for (const Piece& pc : in)
-        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
+    const adr::call::Piece in[] = {{dt, times, K * d}, {ddf, dfs, K * d}, {dT, T, P * d}, {db, b, P * d},
+                                   {dcpn, cpn, ADR_YOY_FIELDS * m * d},
+                                   {doff, cpn_off, n > 0 ? (n + 1) * sizeof(int64_t) : 0}};
+    const adr::call::Piece res[] = {{amount, damt, amount ? m * d : 0}, {pv, dpv, wv ? n * d : 0},
+                                    {delta, ddl, wd ? n * P * d : 0}, {gamma, dg, wg ? n * PP * d : 0},
+                                    {agg, dagg, agg_on ? R * d : 0}};
+    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess)
         rc = adr_yoy_risk_dev(ctx, disc_method, K, dt, ddf, infl_method, P, dT, db, n, m, n > 0 ? doff : nullptr, dcpn,
                               req_mask, damt, dpv, ddl, dg, dagg, dwork, stream);
-    const Piece out[] = {{amount, damt, amount ? m * d : 0}, {pv, dpv, wv ? n * d : 0}, {delta, ddl, wd ? n * P * d : 0},
-                         {gamma, dg, wg ? n * PP * d : 0}, {agg, dagg, agg_on ? R * d : 0}};
-    for (const Piece& pc : out)
-        if (e == hipSuccess && rc == ADR_OK && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipStreamSynchronize(stream);
-    const hipError_t ef = hipFree(base);
-    if (rc != ADR_OK) return rc;
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return ADR_OK;
+    if (e == hipSuccess && rc == ADR_OK) e = adr::call::copy_pieces(res, hipMemcpyDeviceToHost, stream);
+    return adr::call::finish_blocking(who, rc, e, stream, base);
 }
 
 int adr_yoy_risk_host(int disc_method, int K, const double* times, const double* dfs, int infl_method, int P,
