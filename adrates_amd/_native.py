@@ -151,6 +151,12 @@ _SIGNATURES = {
     "adr_scenario_tail_alloc": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "adr_scenario_tail_alloc_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "adr_scenario_tail_alloc_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "adr_trades_ratio_flags_host": (C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint8)]),
+    "adr_subbook_ladders_work": (C.c_int64, [_vp, C.c_int64, C.c_int64, C.c_uint32, _i64p]),
+    "adr_subbook_ladders": (C.c_int, [_vp, _vp, _vp, C.c_int64, _i64p, C.c_uint32, _dp]),
+    "adr_subbook_ladders_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "adr_subbook_ladders_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64p, _i64p] + [_dp] * 11 +
+                                 [C.c_int64, _i64p, C.c_uint32, _dp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1303,6 +1309,76 @@ def scenario_tail_alloc_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: 
     _check(load().adr_scenario_tail_alloc_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), int(k), _dev(var_ptr),
                                               _dev(es_ptr), _dev(comp_var_ptr), _dev(comp_es_ptr), _dev(work_ptr),
                                               _vp(stream or None)), "adr_scenario_tail_alloc_dev")
+
+
+# ------------------------------------------------------------------------------------------------- sub-book Greeks
+def _request_mask(want_delta, want_gamma):
+    return REQ_VALUE | (REQ_DELTA if want_delta else 0) | (REQ_GAMMA if want_gamma else 0)
+
+
+def _ladder_rows(out, P):
+    """``out [B, 1 + P + P P]`` as ``pv [B]``, ``delta [B, P]``, ``gamma [B, P, P]``."""
+    return {"pv": out[:, 0].copy(), "delta": out[:, 1:1 + P].copy(), "gamma": out[:, 1 + P:].reshape(-1, P, P).copy()}
+
+
+def ratio_flags_host(batch) -> np.ndarray:
+    """``[n]`` bool: the trade has a ratio node - a float coupon that accrues and is not paid on its accrual end, or a
+    per-coupon notional other than 1 (adr_trades_ratio_flags_host: the rule the upload applies)."""
+    n, fo, lo, a, w = _batch_arrays(batch)
+    out = np.zeros(n, dtype=np.uint8)
+    _check(load().adr_trades_ratio_flags_host(n, _ptr(lo, _i64p), _ptr(a["flt_tp"]), _ptr(a["flt_te"]), _ptr(a["flt_alpha"]),
+                                              _ptr(w), _ptr(out, C.POINTER(C.c_uint8))), "adr_trades_ratio_flags_host")
+    return out.astype(bool)
+
+
+def subbook_ladders(ctx: Context, curve: DeviceCurve, trades: DeviceTrades, sub_off, want_delta=True, want_gamma=True):
+    """The PV, delta and gamma ladders of every sub-book of an uploaded batch from one launch chain (adr_subbook_ladders,
+    blocking): sub-book ``b`` holds the trades ``sub_off[b] .. sub_off[b + 1]``.  Returns ``pv [B]``, ``delta [B, P]``,
+    ``gamma [B, P, P]``; what was not requested is zeros.  A batch with a ratio node (payment lag, per-coupon notional)
+    raises `LibError` (ADR_ERR_UNSUPPORTED) naming the trade."""
+    sub_off, B = _sub_offsets(sub_off)
+    P = curve.n_pillars
+    out = np.empty((B, 1 + P + P * P))
+    _check(load().adr_subbook_ladders(ctx._h, curve._h, trades._h, B, _ptr(sub_off, _i64p), _request_mask(want_delta, want_gamma),
+                                      _ptr(out)), "adr_subbook_ladders")
+    return _ladder_rows(out, P)
+
+
+def subbook_ladders_host(interp_method: int, times, dfs, jac, hess, batch, sub_off, want_delta=True, want_gamma=True):
+    """`subbook_ladders` on the CPU (adr_subbook_ladders_host) for a `TradeBatch` and the curve arrays `DeviceCurve`
+    takes: the same node and projection code, chunks and summation orders; no GPU needed."""
+    sub_off, B = _sub_offsets(sub_off)
+    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
+    K, P = jac.shape
+    if times.shape != (K,) or dfs.shape != (K,):
+        raise LibError("curve arrays have inconsistent shapes")
+    hess = None if hess is None else _f64(hess)
+    if hess is not None and hess.shape != (K, P, P):
+        raise LibError("hess must have shape [K, P, P]")
+    out = np.empty((B, 1 + P + P * P))
+    _check(load().adr_subbook_ladders_host(int(interp_method), K, P, _ptr(times), _ptr(dfs), _ptr(jac), _ptr(hess),
+                                           *_batch_args(*_batch_arrays(batch)), B, _ptr(sub_off, _i64p),
+                                           _request_mask(want_delta, want_gamma), _ptr(out)), "adr_subbook_ladders_host")
+    return _ladder_rows(out, P)
+
+
+def subbook_ladders_work(curve: DeviceCurve, n_trades: int, n_sub_books: int, want_gamma=True):
+    """``(doubles of scratch, rows of chunk records it holds)`` of `subbook_ladders_dev` (adr_subbook_ladders_work)."""
+    chunks = C.c_int64(0)
+    work = load().adr_subbook_ladders_work(curve._h, int(n_trades), int(n_sub_books), _request_mask(True, want_gamma),
+                                           C.cast(C.byref(chunks), _i64p))
+    if work <= 0:
+        raise LibError("adr_subbook_ladders_work: a curve, at least one trade and at least one sub-book are needed")
+    return int(work), int(chunks.value)
+
+
+def subbook_ladders_dev(ctx: Context, curve: DeviceCurve, trades: DeviceTrades, B: int, plan_ptr: int, mask: int, out_ptr: int,
+                        work_ptr: int, stream=0):
+    """Non-blocking form (adr_subbook_ladders_dev): device pointers (integers) of the uploaded `scenario_subbook_plan` -
+    built once per (batch, sub_off) and reused -, the output ``[B, 1 + P + P P]`` and `subbook_ladders_work` doubles of
+    scratch."""
+    _check(load().adr_subbook_ladders_dev(ctx._h, curve._h, trades._h, int(B), _dev(plan_ptr), int(mask), _dev(out_ptr),
+                                          _dev(work_ptr), _vp(stream or None)), "adr_subbook_ladders_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

@@ -110,6 +110,7 @@ struct adr_trades {
     adr::TradesDev set[R::kSets] = {};
     adr::LiteRowsDev lite[2] = {};
     R::TradeCounts counts;           // what the launch plan needs to know about the batch
+    int64_t first_ratio = -1;        // the first trade with a ratio node (route.hpp, flag_lagged), -1 for none
     // per-wave stash of the payment-lag variant (kernels.hpp, OutputsDev::lag_scratch), sized for a grid of counts.lag_blocks
     // blocks.  It belongs to the BATCH (not to the ctx): two batches priced on two streams never share it.
     double* lag_scratch = nullptr;
@@ -156,6 +157,15 @@ const adr::TradesDev* adr_trades_device_view(const adr_trades* trades, const adr
     *owner = trades->ctx;
     return &trades->dev;
 }
+
+// what subbook_ladder.hip needs: a curve's tables and the first trade of a batch that has a ratio node (-1: none)
+const adr::CurveDev* adr_curve_device_view(const adr_curve* curve, const adr_ctx** owner) {
+    if (!curve) return nullptr;
+    *owner = curve->ctx;
+    return &curve->dev;
+}
+
+int64_t adr_trades_first_ratio(const adr_trades* trades) { return trades ? trades->first_ratio : -1; }
 
 int adr_curve_set_device_view(const adr_curve_set* set, const adr_ctx** owner, int* method, int* K, int* S,
                               const double** times_dev, const double** dfs_dev) {
@@ -782,6 +792,10 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
     tr->n_fix_flows = n_fix;
     tr->n_flt_flows = n_flt;
     tr->counts = L.counts;
+    {
+        const auto it = std::find(lagged_of.begin(), lagged_of.end(), uint8_t(1));
+        if (it != lagged_of.end()) tr->first_ratio = it - lagged_of.begin();
+    }
     hipError_t e = hipSuccess;
     hipStream_t stream = ctx->stream;
     auto alloc = [&](size_t bytes) -> void* {

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "kernels.hpp"
+#include "knot_tables.hpp"
 
 namespace adr {
 
@@ -42,25 +43,6 @@ __global__ __launch_bounds__(256) void knot_reduce_kernel(const double* partials
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     if (lane == 0) reduced[i] = s;
-}
-
-__device__ __forceinline__ double lj_at(const CurveDev& cv, int k, int p) {
-    if (cv.wide_nch > 0 && cv.lj64) return cv.lj64[static_cast<size_t>(k) * kWidePad + p];
-    return cv.lj[(static_cast<size_t>(p / kPillarPad) * cv.Kc + k) * kPillarPad + p % kPillarPad];
-}
-
-// LC[k][p][q]: the wide layout's packed triangle in position space, or the 32 x 32 tiles of the general kernel
-__device__ __forceinline__ double lc_at(const CurveDev& cv, const int* col_off, int k, int p, int q) {
-    if (cv.wide_nch > 0 && cv.lcflat) {
-        int a = cv.wide_pos[p], b = cv.wide_pos[q];
-        if (a > b) { const int t = a; a = b; b = t; }
-        return cv.lcflat[static_cast<size_t>(k) * (cv.wide_nch * kWideChunk) + col_off[b] + a];
-    }
-    int ti = p / kPillarPad, tj = q / kPillarPad;
-    if (ti > tj) { int t = p; p = q; q = t; t = ti; ti = tj; tj = t; }       // (symmetric)
-    const int r = p % kPillarPad, c = q % kPillarPad;
-    const int lane = (r >> 2) * 8 + (c >> 2), e = (r & 3) * 4 + (c & 3);
-    return cv.lc_lanes[((static_cast<size_t>(tj * (tj + 1) / 2 + ti) * cv.Kc + k) * 64 + lane) * kGammaPerLane + e];
 }
 
 // Block p < P: row p of the gamma matrix (lane q); block P: pv and the delta ladder (lane p).  Sixteen wavefronts per block, each
@@ -80,10 +62,7 @@ __global__ __launch_bounds__(64 * kProjectWaves) void knot_project_kernel(CurveD
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n_values = want_gamma ? 1 + (2 + bands) * Kc : 1 + Kc;
     for (int i = threadIdx.x; i < n_values; i += 64 * kProjectWaves) s_red[i] = reduced[i];
-    if (threadIdx.x == 0) {
-        col_off[0] = 0;
-        for (int b = 0; b < kWidePad; ++b) col_off[b + 1] = col_off[b] + 2 * ((b + 2) / 2);
-    }
+    if (threadIdx.x == 0) fill_col_off(col_off);
     __syncthreads();
     const double* w = s_red + 1;
     const double* D = w + Kc;

@@ -1,0 +1,638 @@
+// Sub-book Greeks: per-desk PV, delta and gamma ladders of one batch on one curve from ONE launch chain
+// (adr_subbook_ladders*; declarations and semantics: include/adrates.h).
+//
+// The book's ladder is a projection of its knot-space sums (kernels_knot.hip): per node omega = c exp(ba L[ka] + bb L[kb])
+//     pv += omega,   w_k += omega b_k,   D_k += omega b_k^2,   O_ka += omega ba bb
+// (under LINEAR_FWD_RATES a node is two single-knot amounts with weight 1 and no cross term).  Here those sums are kept per
+// SUB-BOOK and projected once per sub-book:
+//
+//   1. subbook_knot_kernel: one wave takes one chunk of the sub-book plan (subbook.hpp: at most ADR_SCENARIO_CHUNK
+//      consecutive trades, never across a sub-book boundary).  Lane l holds the header of the chunk's trade l; the chunk's
+//      float coupons and fixed flows are two contiguous runs of the CSR arrays, walked 64 at a time, lane = flow.  A lane
+//      finds its flow's trade with six steps over the lanes' headers, folds the coupon into nodes by the lite kernel's
+//      rules (a coupon's start is the previous coupon's end: one node; a fixed flow paid with the coupon joins it), does
+//      the lookup of each node's date (si::log_weights / si::locate, compact knots) and adds the node's numbers to the
+//      wave's own tables in LDS.  A chunk starts from zeroed tables and ends by writing work[chunk] = [pv, w, D, O]: the
+//      record depends on the chunk's trades alone.
+//   2. sub::enqueue_sum adds every sub-book's records in the plan's order (chunk j to slot j % 64, then the halving tree).
+//   3. subbook_project_kernel: out[b] = [pv, delta[P], gamma[P][P]], kernels_knot.hip's expression once per sub-book.  A
+//      block takes kProjDesks sub-books and one row of the ladder, so a row of LJ / LC is read once for all of them.
+//
+// Trades with ratio nodes (payment lag, per-coupon notionals) are refused.  The host twin (adr_subbook_ladders_host) runs
+// the same node and projection code in the same chunks and summation orders on the CPU.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/adrates.h"
+#include "curve_tables.hpp"
+#include "host_pool.hpp"
+#include "knot_tables.hpp"
+#include "route.hpp"
+#include "scenario_common.hpp"
+#include "subbook.hpp"
+
+const adr::CurveDev* adr_curve_device_view(const adr_curve* curve, const adr_ctx** owner);     // capi.hip
+int64_t adr_trades_first_ratio(const adr_trades* trades);                                      // capi.hip
+
+#pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
+
+namespace adr {
+namespace sbl {
+
+using scen::DateW;
+using scen::kChunk;
+using scen::kWave;
+
+constexpr int kMaxWaves = 16;
+constexpr int kProjWaves = 8;       // waves of a projection block, each taking every eighth knot; summed in wave order
+constexpr int kProjDesks = 8;       // sub-books per projection block
+
+// ---------------------------------------------------------------------------------------------------- nodes (shared)
+struct Flows {           // the cash-flow arrays of a batch
+    const double *fix_tp, *fix_pay, *flt_tp, *flt_ts, *flt_te, *flt_alpha;
+};
+
+struct TradeRef {        // one trade
+    int64_t f0, l0;      // its first fixed flow and float coupon
+    int n_fix, n_flt;
+    double notional, spread, fix_sign, flt_sign;
+};
+
+struct Amount {          // a node before its lookup: amount a at time t
+    double t, a;
+    bool on;
+};
+
+// Float coupon c of a trade without ratio nodes: N ((D(ts) / D(tp) - 1) + s alpha) D(tp) = N D(ts) + N (s alpha - 1) D(tp).
+// The masks are the lite kernel's: a coupon counts when tp >= 0 and has no forward when alpha <= 0; the next coupon's
+// start joins this payment node when it is the same date, and so does the fixed flow of the same index.
+__host__ __device__ inline void float_nodes(const Flows& g, const TradeRef& r, int c, Amount* pay, Amount* start) {
+    const int64_t i = r.l0 + c;
+    const double tp = g.flt_tp[i], ts = g.flt_ts[i], al = g.flt_alpha[i];
+    const bool valid = tp >= 0.0, accrues = al > 0.0;
+    const double sn = r.flt_sign * r.notional;
+    double a = valid ? sn * (r.spread * al - (accrues ? 1.0 : 0.0)) : 0.0;
+    if (c + 1 < r.n_flt && g.flt_alpha[i + 1] > 0.0 && g.flt_tp[i + 1] >= 0.0 && g.flt_ts[i + 1] == tp) a = a + sn;
+    if (c < r.n_fix) {
+        const double xt = g.fix_tp[r.f0 + c];
+        if (xt == tp && xt > 0.0) a = a + r.fix_sign * g.fix_pay[r.f0 + c];
+    }
+    pay->t = tp; pay->a = a; pay->on = a != 0.0;
+    start->t = ts; start->a = sn;
+    start->on = valid && accrues && !(c > 0 && g.flt_tp[i - 1] == ts);
+}
+
+// Fixed flow c: counts when tp > 0, unless it went with the float coupon of the same index.
+__host__ __device__ inline Amount fixed_node(const Flows& g, const TradeRef& r, int c) {
+    const double xt = g.fix_tp[r.f0 + c];
+    const bool merged = c < r.n_flt && g.flt_tp[r.l0 + c] == xt;
+    Amount n;
+    n.t = xt;
+    n.a = r.fix_sign * g.fix_pay[r.f0 + c];
+    n.on = !merged && xt > 0.0 && n.a != 0.0;
+    return n;
+}
+
+// The lookup of a date on the raw grid, its knots then renamed to the compact order.
+template <bool kLog, class Comp>
+__host__ __device__ inline DateW lookup(double t, const double* x, int K, int method, const Comp* compact_of) {
+    DateW d = scen::date_weights<kLog>(t, x, K, method);
+    d.a = compact_of[d.a];
+    d.b = compact_of[d.b];
+    return d;
+}
+
+struct Terms {           // what a node adds: pv, w at its two knots, D at its two knots, O at the first
+    double pv, wa, wb, da, db, o;
+};
+
+// L: ln d of the compact knots.
+template <bool kLog>
+__host__ __device__ inline Terms node_terms(const DateW& d, double amount, const double* L) {
+    Terms t;
+    const bool two = d.b != d.a;
+    if (kLog) {
+        double s = d.wa * L[d.a];
+        if (two) s = s + d.wb * L[d.b];
+        const double om = amount * exp(s);
+        t.pv = om;
+        t.wa = om * d.wa;
+        t.wb = two ? om * d.wb : 0.0;
+        t.da = t.wa * d.wa;
+        t.db = t.wb * d.wb;
+        t.o = two ? t.wa * d.wb : 0.0;
+    } else {                 // D = d_a + w (d_b - d_a): the amounts on the two discount factors
+        const double ca = two ? amount * (1.0 - d.wb) * exp(L[d.a]) : amount * exp(L[d.a]);
+        const double cb = two ? amount * d.wb * exp(L[d.b]) : 0.0;
+        t.pv = ca + cb;
+        t.wa = ca; t.wb = cb; t.da = ca; t.db = cb; t.o = 0.0;
+    }
+    return t;
+}
+
+// ----------------------------------------------------------------------------------------------- projection (shared)
+// One knot's part of gamma[p][q]: a = LJ[k], b = LJ[k + 1] (read only where O_k is not zero), lc = LC[k][p][q].
+__host__ __device__ inline double gamma_step(double s, double wk, double dk, double ok, double ap, double aq, double bp,
+                                             double bq, double lc) {
+    s = s + (dk * ap) * aq;
+    if (ok != 0.0) s = s + ok * (ap * bq + bp * aq);
+    if (wk != 0.0) s = s + wk * lc;
+    return s;
+}
+
+__host__ __device__ inline double delta_step(double s, double wk, double aq) { return s + wk * aq; }
+
+// ------------------------------------------------------------------------------------------------------------ device
+struct KnotArgs {
+    CurveDev cv;
+    TradesDev tr;
+    int64_t chunk_cap;               // the rows `work` holds, an upper bound of the plan's count
+    const int64_t *sub_chunks, *sub_bounds;      // the plan's chunk count and its [chunks][2] trade bounds (subbook.hpp)
+    double* work;                    // [chunk_cap][S]
+    int S, waves;
+};
+
+template <bool kLog, bool kGamma>
+__device__ inline void add_node(const Amount& n, const double* s_x, const int16_t* s_comp, const double* s_log, int K, int Kc,
+                                int method, double* tab, double& pv) {
+    if (!n.on) return;
+    const DateW d = lookup<kLog>(n.t, s_x, K, method, s_comp);
+    const Terms t = node_terms<kLog>(d, n.a, s_log);
+    const bool two = d.b != d.a;
+    pv = pv + t.pv;
+    // The bit contract rests on these LDS adds: where several lanes of ONE instruction add to the same address, the
+    // hardware applies them in an order fixed by the lane ids and not by the table's base address, so a chunk's sums are
+    // the same in whichever wave runs it.  gfx950 behaves so (tests: desk alone == desk in the book, run-to-run bits); it is
+    // observed behaviour of ds_add_f64, not an architectural guarantee - a part or compiler that breaks it fails those tests.
+    __hip_atomic_fetch_add(tab + d.a, t.wa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    if (two) __hip_atomic_fetch_add(tab + d.b, t.wb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    if (kGamma) {
+        __hip_atomic_fetch_add(tab + Kc + d.a, t.da, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (two) {
+            __hip_atomic_fetch_add(tab + Kc + d.b, t.db, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (kLog) __hip_atomic_fetch_add(tab + 2 * Kc + d.a, t.o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+    }
+}
+
+// The wave's own LDS traffic in program order, for the compiler too.
+__device__ inline void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The lane that holds the trade of flow f: the last lane j < cnt whose `begin` is <= f (the flows of a chunk are one
+// contiguous run, so an empty trade shares its begin with its successor and never wins).  Every lane takes the six steps.
+__device__ inline int owner_lane(int begin, int cnt, int f) {
+    int pos = 0;
+#pragma unroll
+    for (int step = kWave / 2; step >= 1; step >>= 1) {
+        const int cand = pos + step;
+        const int v = __shfl(begin, cand & (kWave - 1), kWave);
+        if (cand < cnt && v <= f) pos = cand;
+    }
+    return pos;
+}
+
+__device__ inline TradeRef owner_trade(const TradeHeader& h, int j) {
+    TradeRef r;
+    r.l0 = __shfl(h.flt_begin, j, kWave);
+    r.f0 = __shfl(h.fix_begin, j, kWave);
+    const int counts = __shfl(static_cast<int>(h.n_flt) | (static_cast<int>(h.n_fix) << 16), j, kWave);
+    r.n_flt = counts & 0xffff;
+    r.n_fix = counts >> 16;
+    r.notional = __shfl(h.notional, j, kWave);
+    r.spread = __shfl(h.spread, j, kWave);
+    const int signs = __shfl((h.fix_sign < 0 ? 1 : 0) | (h.flt_sign < 0 ? 2 : 0), j, kWave);
+    r.fix_sign = (signs & 1) ? -1.0 : 1.0;
+    r.flt_sign = (signs & 2) ? -1.0 : 1.0;
+    return r;
+}
+
+template <bool kLog, bool kGamma>
+__global__ __launch_bounds__(kWave * kMaxWaves) void subbook_knot_kernel(KnotArgs a) {
+    constexpr int NT = kGamma ? 3 : 1;
+    extern __shared__ double lds[];
+    const int K = a.cv.K, Kc = a.cv.Kc, waves = a.waves;
+    double* s_tab = lds;                                 // [waves][NT][Kc]
+    double* s_x = s_tab + waves * NT * Kc;               // [K]
+    double* s_log = s_x + K;                             // [Kc]
+    int16_t* s_comp = reinterpret_cast<int16_t*>(s_log + Kc);      // [K]
+    const int threads = kWave * waves;
+    for (int i = threadIdx.x; i < waves * NT * Kc; i += threads) s_tab[i] = 0.0;
+    for (int i = threadIdx.x; i < K; i += threads) {
+        s_x[i] = a.cv.x[i];
+        s_comp[i] = a.cv.compact_of[i];
+    }
+    for (int i = threadIdx.x; i < Kc; i += threads) s_log[i] = a.cv.log_df[i];
+    __syncthreads();
+
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double* tab = s_tab + wave * (NT * Kc);
+    const Flows g{a.tr.fix_tp, a.tr.fix_pay, a.tr.flt_tp, a.tr.flt_ts, a.tr.flt_te, a.tr.flt_alpha};
+    const int method = a.cv.method;
+    int64_t n_chunks = *a.sub_chunks;                    // uniform: a scalar load
+    n_chunks = n_chunks < a.chunk_cap ? n_chunks : a.chunk_cap;
+    for (int64_t ch = static_cast<int64_t>(blockIdx.x) * waves + wave; ch < n_chunks; ch += static_cast<int64_t>(gridDim.x) * waves) {
+        scen::ChunkRange r = scen::chunk_range<true>(ch, a.sub_bounds, a.tr.n);
+        if (r.i1 > r.i0 + kChunk) r.i1 = r.i0 + kChunk;  // (a plan of build_plan never asks for more)
+        const int cnt = r.i1 > r.i0 ? static_cast<int>(r.i1 - r.i0) : 0;
+        TradeHeader h{};
+        if (lane < cnt) h = a.tr.header[r.i0 + lane];
+        double pv = 0.0;
+        if (cnt > 0) {
+            const int l_begin = scen::lane_int(h.flt_begin, 0), l_end = scen::lane_int(h.flt_begin + h.n_flt, cnt - 1);
+            for (int base = l_begin; base < l_end; base += kWave) {
+                const int f = base + lane;
+                const TradeRef t = owner_trade(h, owner_lane(h.flt_begin, cnt, f));
+                if (f < l_end) {
+                    Amount pay, start;
+                    float_nodes(g, t, static_cast<int>(f - t.l0), &pay, &start);
+                    add_node<kLog, kGamma>(pay, s_x, s_comp, s_log, K, Kc, method, tab, pv);
+                    add_node<kLog, kGamma>(start, s_x, s_comp, s_log, K, Kc, method, tab, pv);
+                }
+            }
+            const int x_begin = scen::lane_int(h.fix_begin, 0), x_end = scen::lane_int(h.fix_begin + h.n_fix, cnt - 1);
+            for (int base = x_begin; base < x_end; base += kWave) {
+                const int f = base + lane;
+                const TradeRef t = owner_trade(h, owner_lane(h.fix_begin, cnt, f));
+                if (f < x_end) add_node<kLog, kGamma>(fixed_node(g, t, static_cast<int>(f - t.f0)), s_x, s_comp, s_log, K, Kc, method, tab, pv);
+            }
+        }
+#pragma unroll
+        for (int off = kWave / 2; off >= 1; off >>= 1) pv = pv + __shfl_xor(pv, off, kWave);
+        wave_lds_order();
+        double* rec = a.work + ch * a.S;
+        if (lane == 0) rec[0] = pv;
+        for (int k = lane; k < NT * Kc; k += kWave) {
+            rec[1 + k] = tab[k];
+            tab[k] = 0.0;
+        }
+        wave_lds_order();
+    }
+}
+
+struct ProjectArgs {
+    CurveDev cv;
+    const double* sums;              // [B][S]
+    int S;
+    int64_t B;
+    int want_delta, want_gamma;
+    double* out;                     // [B][1 + P + P P]
+};
+
+// blockIdx.y < P: row p of the gamma matrices (lane q); blockIdx.y == P: pv and the delta ladders (lane p).
+__global__ __launch_bounds__(kWave * kProjWaves) void subbook_project_kernel(ProjectArgs a) {
+    __shared__ int col_off[kWidePad + 1];
+    __shared__ double s_part[kProjWaves][kProjDesks][kWave];
+    const CurveDev& cv = a.cv;
+    const int P = cv.P, Kc = cv.Kc;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kProjDesks;
+    const int nd = a.B - b0 < kProjDesks ? static_cast<int>(a.B - b0) : kProjDesks;
+    const int64_t stride = 1 + P + static_cast<int64_t>(P) * P;
+    const bool first = static_cast<int>(blockIdx.y) == P;
+    const int p = first ? 0 : blockIdx.y;
+    if (threadIdx.x == 0) fill_col_off(col_off);
+    __syncthreads();
+    if (first && threadIdx.x < nd) a.out[(b0 + threadIdx.x) * stride] = a.sums[(b0 + threadIdx.x) * a.S];
+    const bool wanted = first ? a.want_delta != 0 : a.want_gamma != 0;
+    double* dst = a.out + b0 * stride + (first ? 1 : 1 + P + static_cast<int64_t>(p) * P);
+    for (int q0 = 0; q0 < P; q0 += kWave) {              // columns in blocks of one wavefront
+        const int q = q0 + lane, qq = q < P ? q : 0;     // lanes beyond the ladder compute a copy of column 0 and store nothing
+        double s[kProjDesks];
+#pragma unroll
+        for (int d = 0; d < kProjDesks; ++d) s[d] = 0.0;
+        if (wanted) {
+            for (int k = wave; k < Kc; k += kProjWaves) {
+                const double aq = lj_at(cv, k, qq);
+                if (first) {
+#pragma unroll
+                    for (int d = 0; d < kProjDesks; ++d)
+                        if (d < nd) s[d] = delta_step(s[d], a.sums[(b0 + d) * a.S + 1 + k], aq);
+                    continue;
+                }
+                const bool next = k + 1 < Kc;
+                const double ap = lj_at(cv, k, p);
+                const double bp = next ? lj_at(cv, k + 1, p) : 0.0, bq = next ? lj_at(cv, k + 1, qq) : 0.0;
+                const double lc = lc_at(cv, col_off, k, p, qq);
+#pragma unroll
+                for (int d = 0; d < kProjDesks; ++d)
+                    if (d < nd) {
+                        const double* rec = a.sums + (b0 + d) * a.S + 1 + k;           // uniform: scalar loads
+                        s[d] = gamma_step(s[d], rec[0], rec[Kc], next ? rec[2 * Kc] : 0.0, ap, aq, bp, bq, lc);
+                    }
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < kProjDesks; ++d) s_part[wave][d][lane] = s[d];
+        __syncthreads();
+        if (wave == 0 && q < P) {
+            for (int d = 0; d < nd; ++d) {
+                double t = s_part[0][d][lane];
+#pragma unroll
+                for (int i = 1; i < kProjWaves; ++i) t = t + s_part[i][d][lane];
+                dst[d * stride + q] = t * (first ? 1e-4 : 1e-8);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------- host
+inline size_t shared_bytes(int K, int Kc) { return (static_cast<size_t>(K) + Kc) * sizeof(double) + ((static_cast<size_t>(K) * sizeof(int16_t) + 7) & ~size_t(7)); }
+
+// The waves of a block of the knot kernel on this curve: as many as the LDS budget holds, 0 when not even one fits.
+inline int knot_waves(int K, int Kc, bool gamma) {
+    const size_t per_wave = static_cast<size_t>(gamma ? 3 : 1) * Kc * sizeof(double), shared = shared_bytes(K, Kc);
+    if (shared + per_wave > scen::kLdsBudget) return 0;
+    return static_cast<int>(std::min<size_t>(kMaxWaves, (scen::kLdsBudget - shared) / per_wave));
+}
+
+inline int record_doubles(int Kc, bool gamma) { return 1 + (gamma ? 3 : 1) * Kc; }
+
+struct Request {
+    bool delta, gamma;
+};
+inline Request request_of(uint32_t req_mask) {
+    const bool gamma = (req_mask & ADR_REQ_GAMMA) != 0;
+    return Request{gamma || (req_mask & ADR_REQ_DELTA) != 0, gamma};
+}
+
+inline std::string ratio_message(int64_t trade) {
+    return ": trade " + std::to_string(trade) + " has a ratio node (a payment lag or a per-coupon notional); sub-book ladders "
+           "take trades whose float coupons are paid on their accrual end";
+}
+
+template <bool kLog>
+hipError_t launch_knot(const KnotArgs& a, bool gamma, size_t lds, unsigned blocks, hipStream_t stream) {
+    auto kernel = gamma ? &subbook_knot_kernel<kLog, true> : &subbook_knot_kernel<kLog, false>;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWave * a.waves), lds, stream, a);
+    return hipGetLastError();
+}
+
+// What an entry needs of its handles, checked.
+struct Handles {
+    const CurveDev* cv;
+    const TradesDev* tr;
+};
+
+int handles(const std::string& w, const adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, int64_t B, const Request& rq,
+            Handles* h) {
+    if (!ctx || !curve || !trades) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx/curve/trades");
+    const adr_ctx *co = nullptr, *to = nullptr;
+    h->cv = adr_curve_device_view(curve, &co);
+    h->tr = adr_trades_device_view(trades, &to);
+    if (co != ctx || to != ctx) return adr_set_error(ADR_ERR_INVALID, w + ": curve/trades were uploaded through another ctx");
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    if (h->tr->n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
+    if (rq.gamma && !h->cv->lc_lanes && !h->cv->lcflat)
+        return adr_set_error(ADR_ERR_INVALID, w + ": GAMMA requested but the curve was uploaded without hess");
+    if (knot_waves(h->cv->K, h->cv->Kc, rq.gamma) < 1)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": the knot tables of one wave (" + std::to_string(h->cv->Kc) +
+                                                      " knots) do not fit the 160 KiB LDS of a CU");
+    const int64_t ratio = adr_trades_first_ratio(trades);
+    if (ratio >= 0) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ratio_message(ratio));
+    return ADR_OK;
+}
+
+// The three steps on `stream`; every pointer is device memory.  work: adr_subbook_ladders_work doubles.
+int enqueue(const std::string& w, adr_ctx* ctx, const Handles& h, int64_t B, const int64_t* plan, const Request& rq, double* out,
+            double* work, hipStream_t stream_or_null) {
+    if (!plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
+    if (!out) return adr_set_error(ADR_ERR_INVALID, w + ": out is NULL");
+    if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_subbook_ladders_work doubles are needed)");
+    hipStream_t stream = nullptr;
+    const int rc = scen::target_stream(w, ctx, stream_or_null, &stream);
+    if (rc != ADR_OK) return rc;
+    const CurveDev& cv = *h.cv;
+    const int S = record_doubles(cv.Kc, rq.gamma), waves = knot_waves(cv.K, cv.Kc, rq.gamma);
+    const int64_t cap = sub::max_chunks(h.tr->n, B, kChunk);
+    const sub::Plan pl = sub::plan_view(plan, B);
+    double* sums = work + cap * S;                       // [B][S]
+    const size_t lds = shared_bytes(cv.K, cv.Kc) + static_cast<size_t>(waves) * (S - 1) * sizeof(double);
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, static_cast<int64_t>(scen::kLdsBudget / lds)));
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((cap + waves - 1) / waves, per_cu * adr_ctx_compute_units(ctx)));
+    const KnotArgs ka{cv, *h.tr, cap, pl.chunk_off + B, pl.bounds, work, S, waves};
+    hipError_t e = cv.method == ADR_INTERP_LINEAR_FWD_RATES ? launch_knot<false>(ka, rq.gamma, lds, static_cast<unsigned>(blocks), stream)
+                                                            : launch_knot<true>(ka, rq.gamma, lds, static_cast<unsigned>(blocks), stream);
+    if (e == hipSuccess) e = sub::enqueue_sum(work, pl.chunk_off, cap, B, S, sums, stream);
+    const int64_t tiles = (B + kProjDesks - 1) / kProjDesks;
+    if (e == hipSuccess && tiles > INT32_MAX) e = hipErrorInvalidConfiguration;
+    if (e == hipSuccess) {
+        const ProjectArgs pa{cv, sums, S, B, rq.delta ? 1 : 0, rq.gamma ? 1 : 0, out};
+        hipLaunchKernelGGL(subbook_project_kernel, dim3(static_cast<unsigned>(tiles), static_cast<unsigned>(cv.P + 1)),
+                           dim3(kWave * kProjWaves), 0, stream, pa);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+// The chunks [lo, hi) of the plan on the host: work[ch] = the chunk's record.
+template <bool kLog>
+void host_chunks(const CurveTables& t, int method, bool gamma, const scen::HostBatch& b, const int64_t* bounds, int S, double* work,
+                 int64_t lo, int64_t hi) {
+    const int K = t.K, Kc = t.Kc;
+    const Flows g{b.fix_tp, b.fix_pay, b.flt_tp, b.flt_ts, b.flt_te, b.flt_alpha};
+    for (int64_t ch = lo; ch < hi; ++ch) {
+        double* rec = work + ch * S;
+        std::fill(rec, rec + S, 0.0);
+        auto add = [&](const Amount& n) {
+            if (!n.on) return;
+            const DateW d = lookup<kLog>(n.t, t.x.data(), K, method, t.compact_of.data());
+            const Terms u = node_terms<kLog>(d, n.a, t.log_df.data());
+            const bool two = d.b != d.a;
+            rec[0] = rec[0] + u.pv;
+            rec[1 + d.a] = rec[1 + d.a] + u.wa;
+            if (two) rec[1 + d.b] = rec[1 + d.b] + u.wb;
+            if (!gamma) return;
+            rec[1 + Kc + d.a] = rec[1 + Kc + d.a] + u.da;
+            if (two) {
+                rec[1 + Kc + d.b] = rec[1 + Kc + d.b] + u.db;
+                if (kLog) rec[1 + 2 * Kc + d.a] = rec[1 + 2 * Kc + d.a] + u.o;
+            }
+        };
+        const scen::ChunkRange r = scen::host_chunk_range(ch, bounds, b.n);
+        for (int64_t i = r.i0; i < r.i1; ++i) {
+            const TradeRef tr{b.fix_off[i], b.flt_off[i], static_cast<int>(b.fix_off[i + 1] - b.fix_off[i]),
+                              static_cast<int>(b.flt_off[i + 1] - b.flt_off[i]), b.notional[i], b.spread[i], b.fix_sign[i], b.flt_sign[i]};
+            for (int c = 0; c < tr.n_flt; ++c) {
+                Amount pay, start;
+                float_nodes(g, tr, c, &pay, &start);
+                add(pay);
+                add(start);
+            }
+            for (int c = 0; c < tr.n_fix; ++c) add(fixed_node(g, tr, c));
+        }
+    }
+}
+
+// out[b] of the sub-books [lo, hi) from their sums: subbook_project_kernel's expression and order.
+void host_project(const CurveTables& t, const Request& rq, const double* sums, int S, double* out, int64_t lo, int64_t hi) {
+    const int P = t.P, Kc = t.Kc;
+    const size_t stride = 1 + P + static_cast<size_t>(P) * P;
+    auto lj = [&](int k, int p) { return t.lj[(static_cast<size_t>(p / kPillarPad) * Kc + k) * kPillarPad + p % kPillarPad]; };
+    for (int64_t b = lo; b < hi; ++b) {
+        const double *rec = sums + b * S, *w = rec + 1, *D = w + Kc, *O = D + Kc;
+        double* o = out + b * stride;
+        std::fill(o, o + stride, 0.0);
+        o[0] = rec[0];
+        for (int q = 0; rq.delta && q < P; ++q) {
+            double tot = 0.0;
+            for (int wave = 0; wave < kProjWaves; ++wave) {
+                double s = 0.0;
+                for (int k = wave; k < Kc; k += kProjWaves) s = delta_step(s, w[k], lj(k, q));
+                tot = wave == 0 ? s : tot + s;
+            }
+            o[1 + q] = tot * 1e-4;
+        }
+        for (int p = 0; rq.gamma && p < P; ++p)
+            for (int q = 0; q < P; ++q) {
+                double tot = 0.0;
+                for (int wave = 0; wave < kProjWaves; ++wave) {
+                    double s = 0.0;
+                    for (int k = wave; k < Kc; k += kProjWaves) {
+                        const bool next = k + 1 < Kc;
+                        s = gamma_step(s, w[k], D[k], next ? O[k] : 0.0, lj(k, p), lj(k, q), next ? lj(k + 1, p) : 0.0,
+                                       next ? lj(k + 1, q) : 0.0, t.lc[(static_cast<size_t>(k) * P + p) * P + q]);
+                    }
+                    tot = wave == 0 ? s : tot + s;
+                }
+                o[1 + P + static_cast<size_t>(p) * P + q] = tot * 1e-8;
+            }
+    }
+}
+
+}  // namespace sbl
+}  // namespace adr
+
+namespace SL = adr::sbl;
+
+extern "C" {
+
+int adr_trades_ratio_flags_host(int64_t n, const int64_t* flt_off, const double* flt_tp, const double* flt_te,
+                                const double* flt_alpha, const double* flt_weight, uint8_t* flags) {
+    const std::string w = "adr_trades_ratio_flags_host";
+    if (n < 0 || (n > 0 && (!flt_off || !flags))) return adr_set_error(ADR_ERR_INVALID, w + ": bad count / null array");
+    if (n > 0 && flt_off[n] > 0 && (!flt_tp || !flt_te || !flt_alpha)) return adr_set_error(ADR_ERR_INVALID, w + ": null cash-flow array");
+    adr::route::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, flags);
+    return ADR_OK;
+}
+
+int64_t adr_subbook_ladders_work(const adr_curve* curve, int64_t n, int64_t B, uint32_t req_mask, int64_t* chunks) {
+    const adr_ctx* owner = nullptr;
+    const adr::CurveDev* cv = adr_curve_device_view(curve, &owner);
+    if (!cv || n < 1 || B < 1) return 0;
+    const int64_t cap = adr::sub::max_chunks(n, B, SL::kChunk);
+    if (chunks) *chunks = cap;
+    return (cap + B) * SL::record_doubles(cv->Kc, SL::request_of(req_mask).gamma);
+}
+
+int adr_subbook_ladders_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, int64_t B, const int64_t* plan_dev,
+                            uint32_t req_mask, double* out_dev, double* work_dev, void* stream) {
+    const std::string w = "adr_subbook_ladders_dev";
+    const SL::Request rq = SL::request_of(req_mask);
+    SL::Handles h{};
+    const int rc = SL::handles(w, ctx, curve, trades, B, rq, &h);
+    if (rc != ADR_OK) return rc;
+    return SL::enqueue(w, ctx, h, B, plan_dev, rq, out_dev, work_dev, static_cast<hipStream_t>(stream));
+}
+
+int adr_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, int64_t B, const int64_t* sub_off,
+                        uint32_t req_mask, double* out) {
+    const std::string w = "adr_subbook_ladders";
+    const SL::Request rq = SL::request_of(req_mask);
+    SL::Handles h{};
+    int rc = SL::handles(w, ctx, curve, trades, B, rq, &h);
+    if (rc != ADR_OK) return rc;
+    if (!out) return adr_set_error(ADR_ERR_INVALID, w + ": out is NULL");
+    std::vector<int64_t> plan;
+    rc = adr::sub::build_plan(w, h.tr->n, B, sub_off, plan);
+    if (rc != ADR_OK) return rc;
+    hipStream_t stream = nullptr;
+    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
+    if (rc != ADR_OK) return rc;
+    // one allocation: the ladders, the scratch, the plan
+    const int P = h.cv->P;
+    const size_t d = sizeof(double), n_out = static_cast<size_t>(B) * (1 + P + static_cast<size_t>(P) * P);
+    const size_t W = static_cast<size_t>(adr_subbook_ladders_work(curve, h.tr->n, B, req_mask, nullptr));
+    double* base = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (n_out + W + plan.size()) * d);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double *dout = base, *dwork = dout + n_out;
+    int64_t* dplan = reinterpret_cast<int64_t*>(dwork + W);
+    e = hipMemcpyAsync(dplan, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) rc = SL::enqueue(w, ctx, h, B, dplan, rq, dout, dwork, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, n_out * d, hipMemcpyDeviceToHost, stream);
+    return adr::scen::finish_blocking(w, rc, e, stream, base);
+}
+
+int adr_subbook_ladders_host(int interp_method, int K, int P, const double* times, const double* dfs, const double* jac,
+                             const double* hess, int64_t n, const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp,
+                             const double* fix_pay, const double* flt_tp, const double* flt_ts, const double* flt_te,
+                             const double* flt_alpha, const double* flt_weight, const double* notional, const double* spread,
+                             const double* fix_sign, const double* flt_sign, int64_t B, const int64_t* sub_off, uint32_t req_mask,
+                             double* out) {
+    const std::string w = "adr_subbook_ladders_host";
+    namespace SC = adr::scen;
+    const SL::Request rq = SL::request_of(req_mask);
+    if (interp_method != ADR_INTERP_FLAT_FWD_RATES && interp_method != ADR_INTERP_LINEAR_FWD_RATES &&
+        interp_method != ADR_INTERP_LINEAR_ZERO_RATES)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and LINEAR_ZERO_RATES (4) "
+                                                      "are implemented");
+    if (n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
+    if (!out) return adr_set_error(ADR_ERR_INVALID, w + ": out is NULL");
+    if (!times || !dfs || !jac) return adr_set_error(ADR_ERR_INVALID, w + ": null curve arrays");
+    if (rq.gamma && !hess) return adr_set_error(ADR_ERR_INVALID, w + ": GAMMA requested but hess is NULL");
+    if (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign)
+        return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
+    const SC::HostBatch b{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread,
+                          fix_sign, flt_sign};
+    int rc = ADR_OK;
+    for (int64_t i = 0; rc == ADR_OK && i < n; ++i) {      // trade by trade: the first trade at fault decides the message
+        rc = SC::check_leg_offsets(w, b, i, i + 1);
+        if (rc == ADR_OK) rc = SC::check_trade_values(w, b, i, i + 1);
+    }
+    if (rc == ADR_OK) rc = SC::check_flows(w, b);
+    if (rc != ADR_OK) return rc;
+    std::vector<int64_t> plan;
+    rc = adr::sub::build_plan(w, n, B, sub_off, plan);
+    if (rc != ADR_OK) return rc;
+    {
+        std::vector<uint8_t> ratio(static_cast<size_t>(n));
+        adr::route::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, ratio.data());
+        const auto it = std::find(ratio.begin(), ratio.end(), uint8_t(1));
+        if (it != ratio.end()) return adr_set_error(ADR_ERR_UNSUPPORTED, w + SL::ratio_message(it - ratio.begin()));
+    }
+    adr::CurveTables t;
+    const std::string err = adr::build_curve_tables(K, P, times, dfs, jac, rq.gamma ? hess : nullptr, t);
+    if (!err.empty()) return adr_set_error(ADR_ERR_INVALID, w + ": " + err);
+    const int S = SL::record_doubles(t.Kc, rq.gamma);
+    const int64_t chunks = plan[B];
+    std::vector<double> work(static_cast<size_t>(chunks) * S), sums(static_cast<size_t>(B) * S);
+    const int64_t* bounds = plan.data() + B + 1;
+    const bool lin = interp_method == ADR_INTERP_LINEAR_FWD_RATES;
+    adr::parallel_ranges(chunks, adr::pool_threads(chunks, 4), [&](int, int64_t lo, int64_t hi) {
+        if (lin) SL::host_chunks<false>(t, interp_method, rq.gamma, b, bounds, S, work.data(), lo, hi);
+        else SL::host_chunks<true>(t, interp_method, rq.gamma, b, bounds, S, work.data(), lo, hi);
+    });
+    adr::sub::reduce_subbooks(work.data(), plan.data(), B, S, sums.data());
+    adr::parallel_ranges(B, adr::pool_threads(B, 1), [&](int, int64_t lo, int64_t hi) {
+        SL::host_project(t, rq, sums.data(), S, out, lo, hi);
+    });
+    return ADR_OK;
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@ from ...utils.global_types import InstrumentTypes, RequestTypes
 from ..position.engine import (Engine, bond_curve_type, frn_is_single_curve, is_bond, is_frn, price_batch, price_bonds,
                                price_frns, wrap_result)
 from ..position.position import Position
+from ..position.sub_book_ladders import price_sub_books
 
 
 class Portfolio:
@@ -74,3 +75,48 @@ class Portfolio:
             if RequestTypes.GAMMA in reqs:
                 total_gamma = part.gamma if total_gamma is None else total_gamma + part.gamma
         return AnalyticsResult(value=total_val, risk=total_delta, gamma=total_gamma)
+
+    def compute_sub_books(self, request_list: Iterable[RequestTypes], keys) -> dict:
+        """`compute` per sub-book: ``keys`` holds one hashable key per position, and the result is ``{"labels": [...],
+        "results": [AnalyticsResult, ...]}`` with the labels in order of first appearance.
+
+        Positions are grouped by (model, curve, currency) as `compute` groups them, and each group is ONE launch
+        (`price_sub_books`); a desk's results are combined across groups with the `+` `compute` uses, so mismatched
+        curves raise as they do there.  A position `compute` prices on its own (cross-currency swaps, dual-curve FRNs,
+        YoY swaps) is refused with a `ValueError` naming the first of them."""
+        reqs = set(request_list)
+        keys = list(keys)
+        if len(keys) != len(self._positions):
+            raise ValueError(f"keys needs one entry per position ({len(self._positions)}), not {len(keys)}")
+        labels = list(dict.fromkeys(keys))
+        groups = {}   # (model id, curve, currency) -> (positions, their keys), in first-seen order
+        for i, (pos, key) in enumerate(zip(self._positions, keys)):
+            d = pos.derivative
+            kind = d.derivative_type
+            if kind == InstrumentTypes.BOND and is_bond(d):
+                curve_type = bond_curve_type(d)
+            elif kind == InstrumentTypes.FRN and is_frn(d) and frn_is_single_curve(d):
+                curve_type = bond_curve_type(d)
+            elif kind == InstrumentTypes.OIS_SWAP:
+                curve_type = d._floating_index
+            else:
+                raise ValueError(f"position {i} ({type(d).__name__}) is priced on its own by compute and has no place in a "
+                                 "sub-book launch")
+            members = groups.setdefault((id(pos.model), curve_type, d._currency), ([], []))
+            members[0].append(pos)
+            members[1].append(key)
+        totals = {label: [None, None, None] for label in labels}
+        for (_, curve_type, currency), (members, member_keys) in groups.items():
+            ir_model = getattr(members[0].model.curves, curve_type.name)
+            res = price_sub_books(members[0]._engine, ir_model, [p.derivative for p in members], member_keys, reqs,
+                                  curve_type=curve_type)
+            for b, label in enumerate(res["labels"]):
+                row = {"agg_pv": res["pv"][b], "agg_delta": res["delta"][b], "agg_gamma": res["gamma"][b]}
+                part = wrap_result(row, 0, reqs, res["tenors"], currency, curve_type, aggregate=True)
+                tot = totals[label]
+                for j, (want, piece) in enumerate(((RequestTypes.VALUE, part.value), (RequestTypes.DELTA, part.risk),
+                                                   (RequestTypes.GAMMA, part.gamma))):
+                    if want in reqs:
+                        tot[j] = piece if tot[j] is None else tot[j] + piece
+        return {"labels": labels, "results": [AnalyticsResult(value=v, risk=d, gamma=g) for v, d, g in
+                                              (totals[label] for label in labels)]}

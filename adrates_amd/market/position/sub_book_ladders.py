@@ -1,0 +1,102 @@
+"""Per-desk PV, delta and gamma ladders of a book from one launch (adr_subbook_ladders): `price_sub_books`.
+
+The book is compiled, sorted by key and cut exactly as the scenario sub-books are (`scenarios.compile_book`,
+`split_sub_books`), and every desk's row is the projection of that desk's own knot-space sums.  A desk's row has
+exactly the bits of the same call on that desk's trades alone.
+
+Trades with ratio nodes (a payment lag, a per-coupon notional) are outside the launch.  They are taken out before the
+upload by `has_ratio_node`, priced per desk by ``price_batch`` (OIS) or ``price_frns`` (FRNs) with ``per_trade=False,
+aggregate=True`` and added to the desk's row in float64: such desks are outside the bit contract.  The host route (``host=True``) has no pricer for them
+and refuses such a book.
+"""
+import numpy as np
+
+from ... import _native
+from ...trades.compiler import TradeBatch
+from ...utils.error import LibError
+from ...utils.global_types import CurveTypes, InstrumentTypes, RequestTypes
+from ...utils.helpers import to_tenor
+from ..curves.curve_tables import build_engine_curve
+from .engine import Engine, price_batch, price_frns
+from .scenarios import _permute_batch, compile_book, split_sub_books
+
+
+def has_ratio_node(batch: TradeBatch) -> np.ndarray:
+    """``[n]`` bool: the trade has a float coupon that accrues and is not paid on its accrual end, or a per-coupon
+    notional other than 1 (the library's own rule, route::flag_lagged, which the upload applies)."""
+    return _native.ratio_flags_host(batch)
+
+
+def _curve_type_of(engine, ir_model):
+    """The `CurveTypes` under which ``engine``'s model holds ``ir_model``."""
+    for ct in CurveTypes:
+        if getattr(engine.model.curves, ct.name, None) is ir_model:
+            return ct
+    raise LibError("ir_model is not a curve of the engine's model: pass curve_type")
+
+
+def _host_curve(ir_model):
+    host = build_engine_curve(ir_model.swap_rates, ir_model.swap_times, ir_model.year_fracs)
+    return host, to_tenor(list(ir_model.swap_times))
+
+
+def price_sub_books(engine: Engine, ir_model, trades, keys, reqs, host=False, curve_type=None):
+    """``{"labels", "pv" [B], "delta" [B, P], "gamma" [B, P, P], "tenors"}`` of the sub-books of ``trades`` by ``keys``
+    (one hashable key per trade; labels in order of first appearance).
+
+    ``trades``: a mixed list of OIS, bonds and single-curve FRNs on ``ir_model``'s curve.  What ``reqs`` does not ask
+    for is zeros.  ``host``: the CPU twin (adr_subbook_ladders_host), no GPU needed.  ``curve_type``: the curve the
+    trades are checked against (`compile_book`), default the one under which the engine's model holds ``ir_model``."""
+    reqs = set(reqs)
+    want_gamma = RequestTypes.GAMMA in reqs
+    want_delta = want_gamma or RequestTypes.DELTA in reqs
+    trades, keys = list(trades), list(keys)
+    batch, const, order = compile_book(trades, ir_model._value_dt, curve_type or _curve_type_of(engine, ir_model))
+    sb = split_sub_books(batch, const, order, keys)
+    B, off = len(sb.labels), sb.sub_off
+    ratio = has_ratio_node(sb.batch)
+    plain = sb.batch
+    plain_off = off
+    if ratio.any():
+        if host:
+            j = int(np.nonzero(ratio)[0][0])
+            raise LibError(f"trade {int(sb.order[j])} has a ratio node (a payment lag or a per-coupon notional): the host "
+                           "route of price_sub_books has no pricer for it")
+        keep = np.nonzero(~ratio)[0]
+        plain_off = np.concatenate([[0], np.cumsum(~ratio)])[off].astype(np.int64)
+        plain = _permute_batch(sb.batch, keep)[0] if keep.size else None
+    method = ir_model._interp_type.value
+    if host:
+        curve, tenors = _host_curve(ir_model)
+        out = _native.subbook_ladders_host(method, curve.times, curve.dfs, curve.jac, curve.hess if want_gamma else None,
+                                           plain, plain_off, want_delta, want_gamma)
+    else:
+        cur = engine._device_curve(ir_model)
+        tenors = cur["tenors"]
+        P = cur["dev"].n_pillars
+        if plain is None:
+            out = {"pv": np.zeros(B), "delta": np.zeros((B, P)), "gamma": np.zeros((B, P, P))}
+        else:
+            with _native.DeviceTrades(cur["ctx"], plain) as dev_trades:
+                out = _native.subbook_ladders(cur["ctx"], cur["dev"], dev_trades, plain_off, want_delta, want_gamma)
+        for b in range(B):                   # the desks that hold trades with ratio nodes: one aggregate launch per kind
+            idx = [int(sb.order[j]) for j in range(off[b], off[b + 1]) if ratio[j]]
+            for pricer, kind in ((price_batch, InstrumentTypes.OIS_SWAP), (price_frns, InstrumentTypes.FRN)):
+                mine = [trades[i] for i in idx if trades[i].derivative_type == kind]
+                if not mine:
+                    continue
+                res = pricer(engine, ir_model, mine, reqs | {RequestTypes.VALUE}, per_trade=False, aggregate=True)
+                out["pv"][b] += res["agg_pv"]
+                if want_delta:
+                    out["delta"][b] += res["agg_delta"]
+                if want_gamma:
+                    out["gamma"][b] += res["agg_gamma"]
+    if sb.pv_const is not None:              # the FRN compiler's curve-independent amounts, per desk; price_frns has added
+        const = np.where(ratio, 0.0, sb.pv_const)      # those of the trades it priced
+        for b in range(B):
+            c = const[off[b]:off[b + 1]]
+            if np.any(c != 0.0):
+                out["pv"][b] += float(np.sum(c))
+    out["labels"] = sb.labels
+    out["tenors"] = tenors
+    return out

@@ -809,6 +809,48 @@ int adr_scenario_tail_alloc_dev(adr_ctx* ctx, int64_t B, int S_tot, const double
 int adr_scenario_tail_alloc_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var_tot, double* es_tot,
                                  double* comp_var, double* comp_es);
 
+/*
+ * Sub-book Greeks: the PV, delta and gamma ladders of every sub-book of a batch on one curve from one launch chain -
+ * what one aggregate-only adr_price per desk returns, without the loop.  B >= 1 and sub_off[B + 1] as for the scenario
+ * sub-books above (from 0 to n, not decreasing, empty sub-books allowed).  out[B][1 + P + P * P], row-major, is
+ * adr_price's agg per sub-book: [pv, delta[P], gamma[P][P]]; pv always, delta with ADR_REQ_DELTA or ADR_REQ_GAMMA, gamma
+ * with ADR_REQ_GAMMA, the blocks not requested are zeros.  The entries write and do not add.
+ *
+ * The batch is read from its CSR arrays in chunks of ADR_SCENARIO_CHUNK trades cut at sub-book boundaries (the plan of
+ * adr_scenario_subbook_plan).  A chunk's knot-space record [pv, w[Kc], D[Kc], O[Kc]] (without GAMMA: [pv, w[Kc]])
+ * depends on its trades alone; a sub-book's records are added in the plan's order (chunk j to slot j % 64 in order,
+ * then slots 0-31 += 32-63, ..., 0 += 1; no atomics to global memory) and projected once per sub-book.  So a
+ * sub-book's row has exactly the bits of the same entry called with B = 1 on a batch holding its trades alone, does not
+ * depend on B or on the other sub-books, and is bit-identical from run to run; an empty sub-book's row is +0.0.
+ *
+ * Covered: every trade without ratio nodes - no per-coupon notional other than 1 and every accruing float coupon paid
+ * on its accrual end (bonds, single-curve FRNs, OIS without payment lag) -, the three interpolation schemes, any pillar
+ * count the curve handle carries.  A batch that holds a ratio node is ADR_ERR_UNSUPPORTED, naming the first such trade;
+ * so is a curve whose knot tables for one wave (24 Kc bytes with GAMMA) do not fit the LDS.
+ *
+ * adr_subbook_ladders: host out, blocks.  _dev: device out and scratch, the uploaded plan, enqueues on `stream` (NULL:
+ * the ctx's own) without allocation or synchronisation (knot sums, the sum for small and for large sub-books, the
+ * projection) and checks scalars only, cutting the plan as the scenario _dev entries do.  adr_subbook_ladders_work is
+ * its scratch in doubles, (ceil(n / 64) + 2 B) records, and leaves the rows of chunk records that scratch holds in
+ * *chunks when that is not NULL.  _host: the CPU twin on the curve's (times, dfs, jac, hess) as adr_curve_upload takes
+ * them (hess may be NULL without GAMMA) and a TradeBatch's arrays: the same node and projection code, chunks and
+ * summation orders; it differs from the device by the two exp implementations only.
+ */
+/* flags[i] = 1 where trade i has a ratio node (the rule adr_trades_upload applies), else 0; flt_weight may be NULL. */
+int adr_trades_ratio_flags_host(int64_t n, const int64_t* flt_off, const double* flt_tp, const double* flt_te,
+                                const double* flt_alpha, const double* flt_weight, uint8_t* flags);
+int64_t adr_subbook_ladders_work(const adr_curve* curve, int64_t n, int64_t B, uint32_t req_mask, int64_t* chunks);
+int adr_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, int64_t B, const int64_t* sub_off,
+                        uint32_t req_mask, double* out);
+int adr_subbook_ladders_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, int64_t B, const int64_t* plan_dev,
+                            uint32_t req_mask, double* out_dev, double* work_dev, void* stream);
+int adr_subbook_ladders_host(int interp_method, int K, int P, const double* times, const double* dfs, const double* jac,
+                             const double* hess, int64_t n, const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp,
+                             const double* fix_pay, const double* flt_tp, const double* flt_ts, const double* flt_te,
+                             const double* flt_alpha, const double* flt_weight, const double* notional, const double* spread,
+                             const double* fix_sign, const double* flt_sign, int64_t B, const int64_t* sub_off, uint32_t req_mask,
+                             double* out);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
