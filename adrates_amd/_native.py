@@ -157,6 +157,9 @@ _SIGNATURES = {
     "adr_subbook_ladders_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_uint32, _vp, _vp, _vp]),
     "adr_subbook_ladders_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64p, _i64p] + [_dp] * 11 +
                                  [C.c_int64, _i64p, C.c_uint32, _dp]),
+    "adr_ladder_pnl": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "adr_ladder_pnl_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "adr_ladder_pnl_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1379,6 +1382,45 @@ def subbook_ladders_dev(ctx: Context, curve: DeviceCurve, trades: DeviceTrades, 
     scratch."""
     _check(load().adr_subbook_ladders_dev(ctx._h, curve._h, trades._h, int(B), _dev(plan_ptr), int(mask), _dev(out_ptr),
                                           _dev(work_ptr), _vp(stream or None)), "adr_subbook_ladders_dev")
+
+
+# --------------------------------------------------------------------------------------- delta-gamma P&L of ladders
+LADDER_PNL_MAX_PILLARS = 256                                # ADR_LADDER_PNL_MAX_PILLARS
+
+
+def _ladder_pnl_call(fn, head, ladders, shocks_bp, want):
+    ladders, shocks_bp = _f64(ladders), _f64(shocks_bp)
+    if ladders.ndim != 2 or shocks_bp.ndim != 2:
+        raise LibError(f"ladders [B, 1 + P + P P] and shocks_bp [S, P] are needed, not {list(ladders.shape)} and "
+                       f"{list(shocks_bp.shape)}")
+    (B, width), (S, P) = ladders.shape, shocks_bp.shape
+    if width != 1 + P + P * P:
+        raise LibError(f"ladder rows of {width} entries do not match shocks of {P} pillars (1 + P + P P = {1 + P + P * P})")
+    names = ("pnl", "delta_pnl", "gamma_pnl")
+    out = {k: np.empty((B, S)) for k, w in zip(names, want) if w}
+    _check(fn(*head, B, P, _ptr(ladders), S, _ptr(shocks_bp), *[_ptr(out.get(k)) for k in names]), fn.__name__)
+    return out
+
+
+def ladder_pnl(ctx: Context, ladders, shocks_bp, want=(True, False, False)):
+    """Delta-gamma P&L of ladder rows under a shock set on the device (adr_ladder_pnl, blocking).  ``ladders
+    [B, 1 + P + P P]``: rows ``[pv, delta[P] per bp, gamma[P][P] per bp^2]`` as `subbook_ladders` and ``price``'s ``agg``
+    lay them out; ``shocks_bp [S, P]``: the move of every par quote per scenario, in basis points.  ``want``: which of
+    ``pnl``, ``delta_pnl`` (``delta . x``) and ``gamma_pnl`` (``x' gamma x / 2``) to return, ``[B, S]`` each."""
+    return _ladder_pnl_call(load().adr_ladder_pnl, (ctx._h,), ladders, shocks_bp, want)
+
+
+def ladder_pnl_host(ladders, shocks_bp, want=(True, False, False)):
+    """`ladder_pnl` on the CPU (adr_ladder_pnl_host): the same fused multiply-adds in the same order, the same bits."""
+    return _ladder_pnl_call(load().adr_ladder_pnl_host, (), ladders, shocks_bp, want)
+
+
+def ladder_pnl_dev(ctx: Context, B: int, P: int, ladders_ptr: int, S: int, shocks_ptr: int, pnl_ptr: int = 0,
+                   delta_pnl_ptr: int = 0, gamma_pnl_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_ladder_pnl_dev): device pointers of ``ladders`` [B, 1 + P + P P], ``shocks_bp`` [S, P] and
+    the outputs [B, S] (0: not wanted, not touched)."""
+    _check(load().adr_ladder_pnl_dev(ctx._h, int(B), int(P), _dev(ladders_ptr), int(S), _dev(shocks_ptr), _dev(pnl_ptr),
+                                     _dev(delta_pnl_ptr), _dev(gamma_pnl_ptr), _vp(stream or None)), "adr_ladder_pnl_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

@@ -30,6 +30,11 @@ per distinct key, each with the bits the whole-book call gives on that sub-book 
 `ScenarioGrid.sub_book_var_es` turn the rows into VaR and expected shortfall on the device (csrc/subbook.hip).
 YoY books have the same through `revalue_yoy_on_curves_sub_books` and `YoYBook.revalue_sub_books`.
 
+Delta-gamma P&L: `ScenarioGrid.pnl_delta_gamma` / `pnl_delta_gamma_sub_books` put the grid's shocks, in basis points,
+through the desks' delta and gamma ladders instead of revaluing (market/position/ladder_pnl.py, adr_ladder_pnl);
+`explain_sub_books` sets that beside `pnl_sub_books` - the unexplained P&L per desk and scenario - and
+`sub_book_delta_gamma_var_es` chains ladders, P&L and tail kernel on the device.
+
 Firm-wide: `combine_sub_book_rows` adds the per-desk rows of the rates, credit and inflation launches by label and
 `allocate_tail` splits the firm's VaR and expected shortfall among the desks (adr_scenario_tail_alloc, csrc/subbook.hip).
 """
@@ -49,6 +54,7 @@ from ...utils.global_types import CurveTypes, InstrumentTypes, InterpTypes, Requ
 from ...utils.helpers import to_tenor
 from .engine import BOND_CURVES, _SUPPORTED_INTERP, frn_is_single_curve
 from .inflation_engine import inflation_inputs
+from .ladder_pnl import delta_gamma_sub_books, first_ratio_trade, shock_matrix_bp
 from ..curves.curve_tables import build_engine_curve
 
 Shock = Union[float, Dict[str, float]]
@@ -832,7 +838,94 @@ class ScenarioGrid:
                        *self._credit_book(trades, spreads, buckets, spread_shocks, True), keys)["sub_pv"]
         return sub[:, :-1] - sub[:, -1:]
 
+    # ---------------------------------------------------------------------------------------------- delta-gamma P&L
+    def shocks_bp(self) -> np.ndarray:
+        """``[S, P]``: the grid's shocks as moves of the par quotes in basis points (quotes are in percent: 100 bp per
+        unit), from the shocks themselves - what `ladder_pnl` takes beside the curve's ladders."""
+        return shock_matrix_bp(self.model._curve_params_dict[self.curve_name]["tenor_list"], self.shocks, 100.0)
+
+    def _engine(self):
+        from .engine import Engine
+        if getattr(self, "_ladder_engine", None) is None:
+            self._ladder_engine = Engine(self.model)
+        return self._ladder_engine
+
+    def pnl_delta_gamma_sub_books(self, trades, keys, parts: bool = False) -> dict:
+        """`pnl_sub_books` without the revaluation: every desk's ladders on the base curve (`price_sub_books`, one launch)
+        times the grid's shocks (`ladder_pnl`, one kernel).  Returns `delta_gamma_sub_books`' dict: ``{"labels", "pnl"
+        [B, S], "pv", "delta", "gamma", "tenors"}`` plus ``"delta_pnl"`` and ``"gamma_pnl"`` with ``parts``; the labels and
+        rows are in `pnl_sub_books`' order."""
+        return delta_gamma_sub_books(self._engine(), self.curve, trades, keys, self.shocks_bp(), parts=parts,
+                                     curve_type=CurveTypes[self.curve_name])
+
+    def pnl_delta_gamma(self, trades) -> np.ndarray:
+        """``[S]``: the book's delta-gamma P&L under the grid's shocks - `pnl` to second order in the shocks, from one
+        ladder launch instead of a revaluation (the sub-book form with one key, its row)."""
+        trades = trades if isinstance(trades, TradeBatch) else list(trades)
+        n = trades.n_trades if isinstance(trades, TradeBatch) else len(trades)
+        return self.pnl_delta_gamma_sub_books(trades, [0] * n)["pnl"][0]
+
+    def explain_sub_books(self, trades, keys) -> dict:
+        """P&L explain per desk and scenario: ``{"labels", "full", "delta_pnl", "gamma_pnl", "unexplained"}``, all
+        ``[B, S]`` - ``full`` is `pnl_sub_books`' full revaluation, the parts are `pnl_delta_gamma_sub_books`', and
+        ``unexplained = full - (delta_pnl + gamma_pnl)``: third order in the shocks where the ladders describe the book."""
+        trades = trades if isinstance(trades, TradeBatch) else list(trades)
+        keys = list(keys)
+        sub = _revalue(self._curves(True), False, self._book(trades), None, keys)         # `pnl_sub_books`, with its labels
+        full = sub["sub_pv"][:, :-1] - sub["sub_pv"][:, -1:]
+        dg = self.pnl_delta_gamma_sub_books(trades, keys, parts=True)
+        assert dg["labels"] == sub["labels"] and full.shape == dg["pnl"].shape, "the two routes order the desks differently"
+        return {"labels": sub["labels"], "full": full, "delta_pnl": dg["delta_pnl"], "gamma_pnl": dg["gamma_pnl"],
+                "unexplained": full - (dg["delta_pnl"] + dg["gamma_pnl"])}
+
+    def _ladder_curve(self):
+        """The base curve with its Jacobian and Hessian on the grid's context, uploaded once."""
+        if getattr(self, "_base_dev", None) is None:
+            base = self.base                # a grid built with with_gamma=False has no Hessian: the host builder makes one
+            if base.hess is None:
+                base = build_engine_curve(self.curve.swap_rates, self.curve.swap_times, self.curve.year_fracs)
+            self._base_dev = _native.DeviceCurve(self._ctx, self.curve._interp_type.value, base.times, base.dfs, base.jac, base.hess)
+        return self._base_dev
+
+    def sub_book_delta_gamma_var_es(self, trades, keys, level: float = 0.99) -> dict:
+        """``{"labels": [...], "var": [B], "es": [B]}`` of the delta-gamma P&L straight from the trades: the ladder launch
+        (adr_subbook_ladders_dev), the P&L kernel (adr_ladder_pnl_dev) and the tail kernel (adr_scenario_tail_dev) in one
+        chain on one stream, so neither the ladders nor the ``[B, S]`` matrix leave the device.  ``var`` and ``es`` are
+        `tail_measures`' of `pnl_delta_gamma_sub_books`' ``pnl``, bit for bit.  A book holding a trade with a ratio node
+        (a payment lag, a per-coupon notional) is refused: the chain has no pricer for it.  The buffers are torch tensors;
+        where torch brings a HIP runtime of its own, import torch before the first call into this library, as the tools do."""
+        import torch
+        sb = split_sub_books(*self._book(trades), keys)
+        S = len(self)
+        if S > _native.SCENARIO_TAIL_MAX:
+            raise LibError(f"{S} scenarios: at most {_native.SCENARIO_TAIL_MAX} fit the tail kernel; use "
+                           "pnl_delta_gamma_sub_books and tail_measures")
+        bad = first_ratio_trade(sb, _native.ratio_flags_host(sb.batch))
+        if bad >= 0:
+            raise LibError(f"trade {bad} has a ratio node (a payment lag or a per-coupon notional): the device chain has no "
+                           "pricer for it; use pnl_delta_gamma_sub_books and tail_measures", status=_native.ADR_ERR_UNSUPPORTED)
+        ctx, curve = self._ctx, self._ladder_curve()
+        B, P, n = len(sb.labels), curve.n_pillars, sb.batch.n_trades
+        dev = torch.device("cuda", ctx.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        plan, shocks = up(_native.scenario_subbook_plan(n, sb.sub_off)), up(self.shocks_bp())
+        ladders, work, pnl, var_es = new(B, 1 + P + P * P), new(_native.subbook_ladders_work(curve, n, B)[0]), new(B, S), new(2, B)
+        torch.cuda.synchronize(dev)
+        with _native.DeviceTrades(ctx, sb.batch) as dev_trades:
+            _native.subbook_ladders_dev(ctx, curve, dev_trades, B, plan.data_ptr(), _native.REQ_VALUE | _native.REQ_DELTA |
+                                        _native.REQ_GAMMA, ladders.data_ptr(), work.data_ptr())
+            _native.ladder_pnl_dev(ctx, B, P, ladders.data_ptr(), S, shocks.data_ptr(), pnl.data_ptr())
+            _native.scenario_tail_dev(ctx, B, S, pnl.data_ptr(), tail_count(level, S), var_es[0].data_ptr(),
+                                      var_es[1].data_ptr(), base_col=-1)
+            ctx.sync()
+        out = var_es.cpu().numpy()
+        return {"labels": sb.labels, "var": out[0].copy(), "es": out[1].copy()}
+
     def close(self):
+        if getattr(self, "_base_dev", None) is not None:
+            self._base_dev.close()
+            self._base_dev = None
         self._set.close()
         self._plan.close()
 

@@ -44,13 +44,14 @@ def price_sub_books(engine: Engine, ir_model, trades, keys, reqs, host=False, cu
     """``{"labels", "pv" [B], "delta" [B, P], "gamma" [B, P, P], "tenors"}`` of the sub-books of ``trades`` by ``keys``
     (one hashable key per trade; labels in order of first appearance).
 
-    ``trades``: a mixed list of OIS, bonds and single-curve FRNs on ``ir_model``'s curve.  What ``reqs`` does not ask
+    ``trades``: a mixed list of OIS, bonds and single-curve FRNs on ``ir_model``'s curve, or a compiled `TradeBatch`
+    without ratio nodes that holds each key's trades consecutively (`split_sub_books`).  What ``reqs`` does not ask
     for is zeros.  ``host``: the CPU twin (adr_subbook_ladders_host), no GPU needed.  ``curve_type``: the curve the
     trades are checked against (`compile_book`), default the one under which the engine's model holds ``ir_model``."""
     reqs = set(reqs)
     want_gamma = RequestTypes.GAMMA in reqs
     want_delta = want_gamma or RequestTypes.DELTA in reqs
-    trades, keys = list(trades), list(keys)
+    trades, keys = trades if isinstance(trades, TradeBatch) else list(trades), list(keys)
     batch, const, order = compile_book(trades, ir_model._value_dt, curve_type or _curve_type_of(engine, ir_model))
     sb = split_sub_books(batch, const, order, keys)
     B, off = len(sb.labels), sb.sub_off
@@ -58,10 +59,11 @@ def price_sub_books(engine: Engine, ir_model, trades, keys, reqs, host=False, cu
     plain = sb.batch
     plain_off = off
     if ratio.any():
-        if host:
+        if host or sb.order is None:
             j = int(np.nonzero(ratio)[0][0])
-            raise LibError(f"trade {int(sb.order[j])} has a ratio node (a payment lag or a per-coupon notional): the host "
-                           "route of price_sub_books has no pricer for it")
+            raise LibError(f"trade {j if sb.order is None else int(sb.order[j])} has a ratio node (a payment lag or a "
+                           "per-coupon notional): " + ("the host route of price_sub_books has no pricer for it" if host else
+                                                       "a compiled TradeBatch carries no objects to price it from"))
         keep = np.nonzero(~ratio)[0]
         plain_off = np.concatenate([[0], np.cumsum(~ratio)])[off].astype(np.int64)
         plain = _permute_batch(sb.batch, keep)[0] if keep.size else None

@@ -155,6 +155,28 @@ class YoYBook:
                                      self.model.value_dt, ctx=ctx)["book_pv"]
         return book[:-1] - book[-1]
 
+    def pnl_delta_gamma(self, grid=None, inflation_shocks=None, breakevens=None) -> np.ndarray:
+        """``[S]``: `pnl` to second order from the book's ladders (`compute` with ``aggregate``), without a revaluation:
+        the discount ladders under the grid's shocks plus the inflation ladders under the breakeven shocks in basis
+        points (``inflation_shocks`` as they are, ``breakevens`` as ``(b - b0) * 1e4``) - two `ladder_pnl` calls.  There
+        is no discount x inflation cross term, as in the engine's Greeks, so with both curves shocked the gap to `pnl`
+        is second order.  Scenarios and their checks: see `revalue`."""
+        from .ladder_pnl import ladder_pnl, shock_matrix_bp
+        b = self._breakeven_rows(grid, inflation_shocks, breakevens)
+        res = self.compute({RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}, per_trade=False, aggregate=True)
+        ctx = self._engine._device_curve(self.curve)["ctx"]
+        pnl = None
+        if grid is not None:
+            pnl = ladder_pnl(res["agg_delta"][None, :], res["agg_gamma"][None, :, :], grid.shocks_bp(), ctx=ctx)[0]
+        if b is not None:
+            if inflation_shocks is not None:
+                x = shock_matrix_bp(res["infl_tenors"], inflation_shocks, 1.0)
+            else:
+                x = (b - inflation_inputs(self.inflation_curve)[2][None, :]) * 1e4
+            infl = ladder_pnl(res["agg_infl_delta"][None, :], res["agg_infl_gamma"][None, :, :], x, ctx=ctx)[0]
+            pnl = infl if pnl is None else pnl + infl
+        return pnl
+
     # ---------------------------------------------------------------------------------------------------- sub-books
     def _sub_books_on_device(self, ctx, sb, method, times, dfs, b, per_trade=False, tail=None):
         """One launch of adr_yoy_scenario_subbook_pv_dev on the ctx's own stream.  ``times`` / ``dfs``: host arrays

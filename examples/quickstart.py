@@ -8,6 +8,7 @@ Run on an MI355X after `python -c "import __graft_entry__ as g; g.build()"`:  py
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+import torch  # noqa: F401  (the device-chained calls below hold their buffers in torch tensors: load torch's HIP runtime first)
 
 from adrates_amd.market.curves.interpolator import InterpTypes
 from adrates_amd.market.portfolio.portfolio import Portfolio
@@ -90,6 +91,13 @@ worst = int(np.argmax(per_desk["var"]))
 print(f"8 desks: largest 99% VaR {per_desk['var'][worst]:,.0f} GBP ({per_desk['labels'][worst]}), its ES "
       f"{per_desk['es'][worst]:,.0f}; sum of desk VaRs {per_desk['var'].sum():,.0f} against the book's "
       f"{historical_var(pnl, 0.99):,.0f}")
+
+# ---- the desks' intraday number without revaluing: their delta and gamma ladders times the shocks, and what that leaves out
+explain = grid.explain_sub_books(book_swaps, desks)                # full revaluation, delta P&L, gamma P&L, unexplained: [8, 250] each
+dg_tail = grid.sub_book_delta_gamma_var_es(book_swaps, desks, level=0.99)      # ladders -> P&L -> VaR / ES, all on the device
+print(f"delta-gamma 99% VaR of {per_desk['labels'][worst]}: {dg_tail['var'][worst]:,.0f} GBP against {per_desk['var'][worst]:,.0f} "
+      f"by full revaluation; largest unexplained P&L {np.abs(explain['unexplained']).max():,.0f} GBP of a largest move of "
+      f"{np.abs(explain['full']).max():,.0f}")
 
 # ---- inflation swaps under JOINT scenarios: the same 250 OIS curves, each paired with a breakeven move (basis points)
 from adrates_amd.market.position.yoy_book import YoYBook

@@ -851,6 +851,43 @@ int adr_subbook_ladders_host(int interp_method, int K, int P, const double* time
                              const double* fix_sign, const double* flt_sign, int64_t B, const int64_t* sub_off, uint32_t req_mask,
                              double* out);
 
+/*
+ * Delta-gamma P&L of ladders under a scenario set: what the rows of adr_subbook_ladders* (or adr_price's agg) say a desk
+ * makes when the par quotes move, without a revaluation.  ladders[B][1 + P + P * P] has exactly that layout - pv,
+ * delta[P] per bp, gamma[P][P] per bp^2, row-major -; the pv slot is not read, and gamma is used as given (no symmetry is
+ * assumed).  shocks_bp[S][P]: shocks_bp[s][p] is scenario s's move of par quote p in basis points.  Outputs [B][S] each:
+ *
+ *   pnl_delta[b][s] = sum_p delta_p x_p
+ *   pnl_gamma[b][s] = 1/2 sum_p sum_q gamma_pq x_p x_q
+ *   pnl[b][s]       = pnl_delta[b][s] + pnl_gamma[b][s]
+ *
+ * Any of the three may be NULL (at least one is asked for); an output not asked for is not touched.  Every step is one
+ * fused multiply-add, rounded once, in this order (x = shocks_bp[s], the row b of ladders):
+ *
+ *   dl  = fma(delta_p, x_p, dl)       p = 0 .. P - 1 ascending, from +0.0
+ *   t_p = fma(gamma_pq, x_q, t_p)     q = 0 .. P - 1 ascending, from +0.0, for every row p of gamma
+ *   gm  = fma(t_p, x_p, gm)           p = 0 .. P - 1 ascending, from +0.0
+ *   pnl_delta = dl,   pnl_gamma = 0.5 * gm (exact),   pnl = dl + 0.5 * gm
+ *
+ * so pnl == pnl_delta + pnl_gamma bit for bit.  There is no exp, no atomic and no sum across lanes: the device and the
+ * host twin agree BIT FOR BIT, and pnl[b][s] depends on ladder row b and shock row s alone - not on B, S, the position
+ * of either row, or the run.  A NaN in row b makes pnl[b][.] NaN and touches no other row.  With only pnl_delta asked
+ * for gamma is not read.
+ *
+ * B >= 0 (B = 0 writes nothing and succeeds; ladders may then be NULL), S >= 1 (at most 65535 * 64 on the device),
+ * 1 <= P <= ADR_LADDER_PNL_MAX_PILLARS - beyond that ADR_ERR_UNSUPPORTED: the shocks of 64 scenarios sit in the LDS of a
+ * CU, 512 P bytes.  Bad scalars, a NULL input or no output: ADR_ERR_INVALID.  adr_ladder_pnl: host arrays, blocks (one
+ * allocation); _dev: device arrays, one kernel on `stream` (NULL: the ctx's own), no allocation, no synchronisation,
+ * scalar checks only; _host: the CPU twin, the same expression per element.
+ */
+#define ADR_LADDER_PNL_MAX_PILLARS 256
+int adr_ladder_pnl(adr_ctx* ctx, int64_t B, int P, const double* ladders, int S, const double* shocks_bp, double* pnl,
+                   double* pnl_delta, double* pnl_gamma);
+int adr_ladder_pnl_dev(adr_ctx* ctx, int64_t B, int P, const double* ladders_dev, int S, const double* shocks_bp_dev,
+                       double* pnl_dev, double* pnl_delta_dev, double* pnl_gamma_dev, void* stream);
+int adr_ladder_pnl_host(int64_t B, int P, const double* ladders, int S, const double* shocks_bp, double* pnl, double* pnl_delta,
+                        double* pnl_gamma);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
