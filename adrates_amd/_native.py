@@ -157,6 +157,13 @@ _SIGNATURES = {
     "adr_subbook_ladders_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_uint32, _vp, _vp, _vp]),
     "adr_subbook_ladders_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64p, _i64p] + [_dp] * 11 +
                                  [C.c_int64, _i64p, C.c_uint32, _dp]),
+    "adr_credit_subbook_ladders_work": (C.c_int64, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _i64p]),
+    "adr_credit_subbook_ladders": (C.c_int, [_vp, _vp, _vp, _dp, _i32p, C.c_int64, _dp, C.c_int64, _dp, C.c_int, C.c_int64, _i64p,
+                                             C.c_uint32, _dp]),
+    "adr_credit_subbook_ladders_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int, C.c_int64,
+                                                 C.c_int64, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "adr_credit_subbook_ladders_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64p, _i64p] +
+                                        [_dp] * 11 + [_dp, _i32p, _dp, _dp, C.c_int, C.c_int64, _i64p, C.c_uint32, _dp]),
     "adr_ladder_pnl": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "adr_ladder_pnl_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "adr_ladder_pnl_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
@@ -1382,6 +1389,112 @@ def subbook_ladders_dev(ctx: Context, curve: DeviceCurve, trades: DeviceTrades, 
     scratch."""
     _check(load().adr_subbook_ladders_dev(ctx._h, curve._h, trades._h, int(B), _dev(plan_ptr), int(mask), _dev(out_ptr),
                                           _dev(work_ptr), _vp(stream or None)), "adr_subbook_ladders_dev")
+
+
+# ------------------------------------------------------------------------------------------ credit sub-book Greeks
+def _credit_ladder_rows(out, P, G):
+    """``out [B, 1 + Q + Q Q]`` (Q = P + G) as its blocks; ``ladders`` is ``out`` itself, what `ladder_pnl` takes beside
+    shock rows ``[x_bp (P), dz * 1e4 (G)]``."""
+    Q = P + G
+    g = out[:, 1 + Q:].reshape(-1, Q, Q)
+    diag = np.arange(P, Q)
+    return {"pv": out[:, 0].copy(), "delta": out[:, 1:1 + P].copy(), "gamma": g[:, :P, :P].copy(), "cs01": out[:, 1 + P:1 + Q].copy(),
+            "spread_gamma": g[:, diag, diag].copy(), "cross_gamma": g[:, P:, :P].copy(), "ladders": out}
+
+
+def _credit_ladder_inputs(z, bucket, fix_tau, flt_tau, G, n, n_fix, n_flt):
+    _, z, bucket, fix_tau, flt_tau = _credit_spread_inputs(None, z, bucket, fix_tau, flt_tau, n, n_fix, n_flt)
+    return z, bucket, fix_tau, flt_tau, int(G)
+
+
+def credit_subbook_cells(bucket, sub_off):
+    """The (sub-book, bucket) cells of a batch ordered by (sub-book, bucket), as `credit_subbook_ladders_dev` takes them:
+    ``(cell_off [C + 1], desk_cell_off [B + 1], cell_bucket [C])`` - only cells that hold trades exist, and
+    ``scenario_subbook_plan(n, cell_off)`` is the chunk plan over them."""
+    sub_off, B = _sub_offsets(sub_off)
+    bucket = np.ascontiguousarray(bucket, dtype=np.int32).reshape(-1)
+    n = bucket.size
+    if sub_off[0] != 0 or sub_off[-1] != n or np.any(np.diff(sub_off) < 0):
+        raise LibError(f"sub_off must run from 0 to the trade count {n} without decreasing")
+    desk = np.repeat(np.arange(B, dtype=np.int64), np.diff(sub_off))
+    back = np.nonzero((desk[1:] == desk[:-1]) & (bucket[1:] < bucket[:-1]))[0]
+    if back.size:
+        i = int(back[0]) + 1
+        raise LibError(f"sub-book {int(desk[i])} is not ordered by bucket: trade {i} (bucket {int(bucket[i])}) follows bucket "
+                       f"{int(bucket[i - 1])}")
+    start = np.ones(n, dtype=bool)
+    start[1:] = (desk[1:] != desk[:-1]) | (bucket[1:] != bucket[:-1])
+    first = np.nonzero(start)[0]
+    cell_off = np.concatenate([first, [n]]).astype(np.int64)
+    desk_cell_off = np.searchsorted(desk[first], np.arange(B + 1), side="left").astype(np.int64)
+    return cell_off, desk_cell_off, bucket[first].copy()
+
+
+def credit_subbook_ladders(ctx: Context, curve: DeviceCurve, trades: DeviceTrades, z, bucket, fix_tau, flt_tau, G: int, sub_off,
+                           want_delta=True, want_gamma=True):
+    """The ladders of every sub-book of an uploaded credit batch AT ITS SPREADS plus the spread Greeks per bucket, from one
+    launch chain (adr_credit_subbook_ladders, blocking).  ``z [n]``, ``bucket [n]`` (int32, -1: none) and the spread times
+    per flow as `credit_scenario_pv` takes them; the batch must be ordered by (sub-book, bucket).  Returns ``pv [B]``,
+    ``delta [B, P]``, ``gamma [B, P, P]``, ``cs01 [B, G]``, ``spread_gamma [B, G]``, ``cross_gamma [B, G, P]`` and the
+    augmented rows ``ladders [B, 1 + Q + Q Q]``, Q = P + G; what was not requested is zeros."""
+    sub_off, B = _sub_offsets(sub_off)
+    z, bucket, fix_tau, flt_tau, G = _credit_ladder_inputs(z, bucket, fix_tau, flt_tau, G, trades.n_trades, np.size(fix_tau),
+                                                           np.size(flt_tau))
+    P = curve.n_pillars
+    Q = P + max(G, 0)
+    out = np.empty((B, 1 + Q + Q * Q))
+    _check(load().adr_credit_subbook_ladders(ctx._h, curve._h, trades._h, *_credit_trade_args(z, bucket, fix_tau, flt_tau, True), G,
+                                             B, _ptr(sub_off, _i64p), _request_mask(want_delta, want_gamma), _ptr(out)),
+           "adr_credit_subbook_ladders")
+    return _credit_ladder_rows(out, P, G)
+
+
+def credit_subbook_ladders_host(interp_method: int, times, dfs, jac, hess, batch, z, bucket, fix_tau, flt_tau, G: int, sub_off,
+                                want_delta=True, want_gamma=True):
+    """`credit_subbook_ladders` on the CPU (adr_credit_subbook_ladders_host) for a `TradeBatch` and the curve arrays
+    `DeviceCurve` takes: the same node, sum and projection code, chunks and orders; no GPU needed."""
+    sub_off, B = _sub_offsets(sub_off)
+    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
+    K, P = jac.shape
+    if times.shape != (K,) or dfs.shape != (K,):
+        raise LibError("curve arrays have inconsistent shapes")
+    hess = None if hess is None else _f64(hess)
+    if hess is not None and hess.shape != (K, P, P):
+        raise LibError("hess must have shape [K, P, P]")
+    arrays = _batch_arrays(batch)
+    n, a = arrays[0], arrays[3]
+    z, bucket, fix_tau, flt_tau, G = _credit_ladder_inputs(z, bucket, fix_tau, flt_tau, G, n, a["fix_tp"].size, a["flt_tp"].size)
+    Q = P + max(G, 0)
+    out = np.empty((B, 1 + Q + Q * Q))
+    _check(load().adr_credit_subbook_ladders_host(int(interp_method), K, P, _ptr(times), _ptr(dfs), _ptr(jac), _ptr(hess),
+                                                  *_batch_args(*arrays), *_credit_trade_args(z, bucket, fix_tau, flt_tau, False),
+                                                  G, B, _ptr(sub_off, _i64p), _request_mask(want_delta, want_gamma), _ptr(out)),
+           "adr_credit_subbook_ladders_host")
+    return _credit_ladder_rows(out, P, G)
+
+
+def credit_subbook_ladders_work(curve: DeviceCurve, n_trades: int, n_sub_books: int, n_cells: int, want_gamma=True):
+    """``(doubles of scratch, rows of chunk records it holds)`` of `credit_subbook_ladders_dev`
+    (adr_credit_subbook_ladders_work)."""
+    chunks = C.c_int64(0)
+    work = load().adr_credit_subbook_ladders_work(curve._h, int(n_trades), int(n_sub_books), int(n_cells),
+                                                  _request_mask(True, want_gamma), C.cast(C.byref(chunks), _i64p))
+    if work <= 0:
+        raise LibError("adr_credit_subbook_ladders_work: a curve, at least one trade and sub-book and 1 .. n_trades cells are needed")
+    return int(work), int(chunks.value)
+
+
+def credit_subbook_ladders_dev(ctx: Context, curve: DeviceCurve, trades: DeviceTrades, n_fix: int, n_flt: int, G: int, B: int,
+                               n_cells: int, ptrs, mask: int, out_ptr: int, work_ptr: int, stream=0):
+    """Non-blocking form (adr_credit_subbook_ladders_dev): ``ptrs`` maps ``z`` [n], ``bucket`` [n] (int32), ``fix_tau``
+    [n_fix], ``flt_tau`` [n_flt], ``cell_plan`` (`scenario_subbook_plan` over `credit_subbook_cells`' ``cell_off``),
+    ``desk_cell_off`` [B + 1] and ``cell_bucket`` [C] (int32) to device pointers (integers); the output
+    ``[B, 1 + Q + Q Q]`` and `credit_subbook_ladders_work` doubles of scratch."""
+    g = _dev_of(ptrs)
+    _check(load().adr_credit_subbook_ladders_dev(ctx._h, curve._h, trades._h, g("z"), g("bucket"), int(n_fix), g("fix_tau"),
+                                                 int(n_flt), g("flt_tau"), int(G), int(B), int(n_cells), g("cell_plan"),
+                                                 g("desk_cell_off"), g("cell_bucket"), int(mask), _dev(out_ptr), _dev(work_ptr),
+                                                 _vp(stream or None)), "adr_credit_subbook_ladders_dev")
 
 
 # --------------------------------------------------------------------------------------- delta-gamma P&L of ladders

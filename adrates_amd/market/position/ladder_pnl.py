@@ -11,6 +11,10 @@ inflation ladders of `YoYBook.compute` the breakeven shocks.
 `delta_gamma_sub_books` joins `price_sub_books` and `ladder_pnl`: every desk's intraday P&L vector from one ladder launch
 and one P&L launch.  The gap to full revaluation - the unexplained P&L per desk and scenario - is
 `ScenarioGrid.explain_sub_books`.
+
+Credit desks take the same kernel: `price_credit_sub_books`' augmented rows hold, beside the curve ladders at the spreads,
+CS01, spread gamma and the rate x spread cross gamma per bucket in the layout of a ladder over ``P + G`` "pillars", so
+`credit_delta_gamma_sub_books` is `ladder_pnl` on those rows and `credit_shock_matrix_bp`'s joint shocks.
 """
 from __future__ import annotations
 
@@ -101,5 +105,57 @@ def delta_gamma_sub_books(engine, ir_model, trades, keys, shocks_bp, parts=False
     out = price_sub_books(engine, ir_model, trades, keys, reqs, host=host, curve_type=curve_type)
     ctx = None if host else engine._device_curve(ir_model)["ctx"]
     pnl = ladder_pnl(out["delta"], out["gamma"], shocks_bp, parts=parts, host=host, ctx=ctx)
+    out.update(pnl if parts else {"pnl": pnl})
+    return out
+
+
+def credit_shock_matrix_bp(shocks_bp, spread_shocks) -> np.ndarray:
+    """``[S, P + G]``: joint shock rows for the augmented ladders of `price_credit_sub_books` - the curve shocks
+    ``shocks_bp [S, P]`` in basis points as they are, then the spread shocks ``spread_shocks [S, G]`` in DECIMALS (as
+    `pnl_credit_sub_books` takes them) times 1e4.  Either side may be one row, shared by all scenarios; ``spread_shocks=None``
+    with no bucket."""
+    x = np.atleast_2d(np.asarray(shocks_bp, dtype=np.float64))
+    y = np.zeros((1, 0)) if spread_shocks is None else np.atleast_2d(np.asarray(spread_shocks, dtype=np.float64))
+    if x.ndim != 2 or y.ndim != 2:
+        raise LibError(f"shocks_bp [S, P] and spread_shocks [S, G] are needed, not {list(x.shape)} and {list(y.shape)}")
+    S = max(x.shape[0], y.shape[0])
+    if x.shape[0] not in (1, S) or y.shape[0] not in (1, S):
+        raise LibError(f"{x.shape[0]} curve-shock rows and {y.shape[0]} spread-shock rows: each must be one shared row or one "
+                       "row per scenario")
+    return np.ascontiguousarray(np.hstack([np.broadcast_to(x, (S, x.shape[1])), np.broadcast_to(y, (S, y.shape[1])) * 1e4]))
+
+
+def augmented_ladder_pnl(ladders, shocks, parts=False, host=False, ctx=None):
+    """`ladder_pnl` on ready rows ``ladders [B, 1 + Q + Q Q]`` and ``shocks [S, Q]``: ``[B, S]``, or with ``parts`` the
+    dict of `ladder_pnl`."""
+    want = (True, True, True) if parts else (True, False, False)
+    if host:
+        out = _native.ladder_pnl_host(ladders, shocks, want)
+    else:
+        out = _native.ladder_pnl(ctx or _native.default_context(), ladders, shocks, want)
+    return {k: out[k] for k in _PARTS} if parts else out["pnl"]
+
+
+def credit_delta_gamma_sub_books(engine, ir_model, trades, spreads, keys, buckets, shocks_bp, spread_shocks=None, parts=False,
+                                 host=False, curve_type=None):
+    """Every credit desk's delta-gamma P&L under joint (curve, spread) shocks: `price_credit_sub_books` (one launch chain)
+    and then `ladder_pnl` on the augmented rows (one kernel),
+
+        delta . x + x' Gamma x / 2 + sum_g (cs01_g y_g + csg_g y_g^2 / 2 + y_g cross_g . x),
+
+    ``x`` the curve shocks in bp (``shocks_bp [S, P]``), ``y`` the spread shocks in bp (``spread_shocks [S, G]`` in
+    decimals, one column per bucket label in order of first appearance; None: none).  Returns `price_credit_sub_books`'
+    dict plus ``"pnl" [B, S]`` and, with ``parts``, ``"delta_pnl"`` (first order, CS01 included) and ``"gamma_pnl"``.
+    ``host=True`` runs both steps on their CPU twins; no GPU needed."""
+    from .sub_book_ladders import price_credit_sub_books
+    reqs = {RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}
+    out = price_credit_sub_books(engine, ir_model, trades, spreads, keys, buckets, reqs, host=host, curve_type=curve_type)
+    G = len(out["buckets"])
+    if spread_shocks is not None and np.shape(np.atleast_2d(spread_shocks))[1] != G:
+        raise LibError(f"spread_shocks must have shape [n_scenarios, {G}] or [{G}] (one column per bucket), not "
+                       f"{list(np.shape(spread_shocks))}")
+    shocks = credit_shock_matrix_bp(shocks_bp, (np.zeros((1, G)) if spread_shocks is None else spread_shocks) if G else None)
+    ctx = None if host else engine._device_curve(ir_model)["ctx"]
+    pnl = augmented_ladder_pnl(out["ladders"], shocks, parts=parts, host=host, ctx=ctx)
     out.update(pnl if parts else {"pnl": pnl})
     return out

@@ -35,6 +35,10 @@ through the desks' delta and gamma ladders instead of revaluing (market/position
 `explain_sub_books` sets that beside `pnl_sub_books` - the unexplained P&L per desk and scenario - and
 `sub_book_delta_gamma_var_es` chains ladders, P&L and tail kernel on the device.
 
+Credit desks have the same three: `pnl_credit_delta_gamma_sub_books` (ladders at the spreads plus CS01, spread gamma and the
+rate x spread cross gamma per bucket, adr_credit_subbook_ladders), `explain_credit_sub_books` beside `pnl_credit_sub_books`
+and `sub_book_credit_delta_gamma_var_es`.
+
 Firm-wide: `combine_sub_book_rows` adds the per-desk rows of the rates, credit and inflation launches by label and
 `allocate_tail` splits the firm's VaR and expected shortfall among the desks (adr_scenario_tail_alloc, csrc/subbook.hip).
 """
@@ -54,7 +58,8 @@ from ...utils.global_types import CurveTypes, InstrumentTypes, InterpTypes, Requ
 from ...utils.helpers import to_tenor
 from .engine import BOND_CURVES, _SUPPORTED_INTERP, frn_is_single_curve
 from .inflation_engine import inflation_inputs
-from .ladder_pnl import delta_gamma_sub_books, first_ratio_trade, shock_matrix_bp
+from .ladder_pnl import (credit_delta_gamma_sub_books, credit_shock_matrix_bp, delta_gamma_sub_books, first_ratio_trade,
+                         shock_matrix_bp)
 from ..curves.curve_tables import build_engine_curve
 
 Shock = Union[float, Dict[str, float]]
@@ -921,6 +926,88 @@ class ScenarioGrid:
             ctx.sync()
         out = var_es.cpu().numpy()
         return {"labels": sb.labels, "var": out[0].copy(), "es": out[1].copy()}
+
+    # --------------------------------------------------------------------------------------- credit delta-gamma P&L
+    def pnl_credit_delta_gamma_sub_books(self, trades, spreads, keys, buckets=None, spread_shocks=None, parts: bool = False) -> dict:
+        """`pnl_credit_sub_books` without the revaluation: every desk's ladders at its spreads with CS01, spread gamma and
+        cross gamma per bucket (`price_credit_sub_books`, one launch chain) times the grid's joint shocks (`ladder_pnl`, one
+        kernel).  ``spread_shocks`` as `pnl_credit_sub_books` takes them.  Returns `credit_delta_gamma_sub_books`' dict;
+        the labels and rows are in `pnl_credit_sub_books`' order.  A trade with a ratio node is refused."""
+        trades = list(trades)
+        dz = None
+        if spread_shocks is not None:
+            dz = np.atleast_2d(np.asarray(spread_shocks, dtype=np.float64))
+            if dz.shape[0] not in (1, len(self)):
+                raise LibError(f"{dz.shape[0]} spread-shock rows for a grid of {len(self)} scenarios: one shared row or one per "
+                               "scenario")
+            dz = None if dz.shape[1] == 0 else dz
+        return credit_delta_gamma_sub_books(self._engine(), self.curve, trades, spreads, keys, buckets, self.shocks_bp(), dz,
+                                            parts=parts, curve_type=CurveTypes[self.curve_name])
+
+    def pnl_credit_delta_gamma(self, trades, spreads, buckets=None, spread_shocks=None) -> np.ndarray:
+        """``[S]``: the credit book's delta-gamma P&L under the grid's joint shocks - `pnl_credit` to second order (the
+        sub-book form with one key, its row)."""
+        trades = list(trades)
+        return self.pnl_credit_delta_gamma_sub_books(trades, spreads, [0] * len(trades), buckets, spread_shocks)["pnl"][0]
+
+    def explain_credit_sub_books(self, trades, spreads, keys, buckets=None, spread_shocks=None) -> dict:
+        """P&L explain per credit desk and scenario: ``{"labels", "full", "delta_pnl", "gamma_pnl", "unexplained"}``, all
+        ``[B, S]`` - ``full`` is `pnl_credit_sub_books`' full revaluation under the joint shocks, the parts are
+        `pnl_credit_delta_gamma_sub_books`' (``delta_pnl`` holds the CS01 term, ``gamma_pnl`` the spread and cross gammas),
+        and ``unexplained = full - (delta_pnl + gamma_pnl)``: third order in the shocks."""
+        trades, keys = list(trades), list(keys)
+        sub = _revalue(self._curves(True), False, *self._credit_book(trades, spreads, buckets, spread_shocks, True), keys)
+        full = sub["sub_pv"][:, :-1] - sub["sub_pv"][:, -1:]
+        dg = self.pnl_credit_delta_gamma_sub_books(trades, spreads, keys, buckets, spread_shocks, parts=True)
+        assert dg["labels"] == sub["labels"] and dg["buckets"] == sub["buckets"] and full.shape == dg["pnl"].shape, \
+            "the two routes order the desks differently"
+        return {"labels": sub["labels"], "full": full, "delta_pnl": dg["delta_pnl"], "gamma_pnl": dg["gamma_pnl"],
+                "unexplained": full - (dg["delta_pnl"] + dg["gamma_pnl"])}
+
+    def sub_book_credit_delta_gamma_var_es(self, trades, spreads, keys, buckets=None, spread_shocks=None, level: float = 0.99) -> dict:
+        """``{"labels": [...], "var": [B], "es": [B]}`` of the credit delta-gamma P&L straight from the trades: the ladder
+        chain (adr_credit_subbook_ladders_dev), the P&L kernel (adr_ladder_pnl_dev on the augmented rows) and the tail kernel
+        (adr_scenario_tail_dev) on one stream, so neither the ladders nor the ``[B, S]`` matrix leave the device.  ``var`` and
+        ``es`` are `tail_measures`' of `pnl_credit_delta_gamma_sub_books`' ``pnl``, bit for bit.  A trade with a ratio node is
+        refused.  The buffers are torch tensors; where torch brings a HIP runtime of its own, import torch before the first
+        call into this library, as the tools do."""
+        import torch
+        from .sub_book_ladders import credit_cell_book
+        S = len(self)
+        if S > _native.SCENARIO_TAIL_MAX:
+            raise LibError(f"{S} scenarios: at most {_native.SCENARIO_TAIL_MAX} fit the tail kernel; use "
+                           "pnl_credit_delta_gamma_sub_books and tail_measures")
+        cb = credit_cell_book(list(trades), self.curve._value_dt, CurveTypes[self.curve_name], spreads, keys, buckets)
+        G = len(cb.buckets)
+        dz = _grid_spread_rows(_spread_rows(spread_shocks, G), S, G, False)
+        ctx, curve = self._ctx, self._ladder_curve()
+        B, P, n = len(cb.labels), curve.n_pillars, cb.batch.n_trades
+        Q = P + G
+        if Q > _native.LADDER_PNL_MAX_PILLARS:
+            raise LibError(f"{P} pillars and {G} buckets: at most {_native.LADDER_PNL_MAX_PILLARS} columns fit the P&L kernel")
+        cell_off, desk_cell_off, cell_bucket = _native.credit_subbook_cells(cb.bucket, cb.sub_off)
+        C = cell_bucket.size
+        dev = torch.device("cuda", ctx.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        bufs = {"z": up(cb.z), "bucket": up(cb.bucket), "fix_tau": up(cb.fix_tau), "flt_tau": up(cb.flt_tau),
+                "cell_plan": up(_native.scenario_subbook_plan(n, cell_off)), "desk_cell_off": up(desk_cell_off),
+                "cell_bucket": up(cell_bucket)}
+        shocks = up(credit_shock_matrix_bp(self.shocks_bp(), dz))
+        ladders, work = new(B, 1 + Q + Q * Q), new(_native.credit_subbook_ladders_work(curve, n, B, C)[0])
+        pnl, var_es = new(B, S), new(2, B)
+        torch.cuda.synchronize(dev)
+        with _native.DeviceTrades(ctx, cb.batch) as dev_trades:
+            _native.credit_subbook_ladders_dev(ctx, curve, dev_trades, cb.fix_tau.size, cb.flt_tau.size, G, B, C,
+                                               {k: v.data_ptr() if v.numel() else 0 for k, v in bufs.items()},
+                                               _native.REQ_VALUE | _native.REQ_DELTA | _native.REQ_GAMMA, ladders.data_ptr(),
+                                               work.data_ptr())
+            _native.ladder_pnl_dev(ctx, B, Q, ladders.data_ptr(), S, shocks.data_ptr(), pnl.data_ptr())
+            _native.scenario_tail_dev(ctx, B, S, pnl.data_ptr(), tail_count(level, S), var_es[0].data_ptr(),
+                                      var_es[1].data_ptr(), base_col=-1)
+            ctx.sync()
+        out = var_es.cpu().numpy()
+        return {"labels": cb.labels, "var": out[0].copy(), "es": out[1].copy()}
 
     def close(self):
         if getattr(self, "_base_dev", None) is not None:

@@ -8,7 +8,13 @@ Trades with ratio nodes (a payment lag, a per-coupon notional) are outside the l
 upload by `has_ratio_node`, priced per desk by ``price_batch`` (OIS) or ``price_frns`` (FRNs) with ``per_trade=False,
 aggregate=True`` and added to the desk's row in float64: such desks are outside the bit contract.  The host route (``host=True``) has no pricer for them
 and refuses such a book.
+
+Credit desks: `price_credit_sub_books` prices bonds at their z-spreads and FRNs at their discount margins and returns, beside
+the curve ladders AT THE SPREADS, every desk's CS01 and spread gamma per credit bucket and the rate x spread cross gamma
+(adr_credit_subbook_ladders).  It has no route for ratio nodes and refuses such a trade.
 """
+from dataclasses import dataclass
+
 import numpy as np
 
 from ... import _native
@@ -18,7 +24,7 @@ from ...utils.global_types import CurveTypes, InstrumentTypes, RequestTypes
 from ...utils.helpers import to_tenor
 from ..curves.curve_tables import build_engine_curve
 from .engine import Engine, price_batch, price_frns
-from .scenarios import _permute_batch, compile_book, split_sub_books
+from .scenarios import _permute_batch, compile_book, compile_credit_book, split_sub_books
 
 
 def has_ratio_node(batch: TradeBatch) -> np.ndarray:
@@ -101,4 +107,83 @@ def price_sub_books(engine: Engine, ir_model, trades, keys, reqs, host=False, cu
                 out["pv"][b] += float(np.sum(c))
     out["labels"] = sb.labels
     out["tenors"] = tenors
+    return out
+
+
+@dataclass
+class CreditCells:
+    """`credit_cell_book`'s result: the batch ordered by (desk, bucket) - within a desk the unbucketed trades first, then
+    the buckets ascending, a stable sort of `split_sub_books`' order - with the per-trade and per-flow spread arrays to
+    match, ``pv_const`` (or None), ``order`` (trade ``j`` of the batch is trade ``order[j]`` of the caller's list), the desk
+    labels, ``sub_off [B + 1]`` and the bucket labels."""
+    batch: TradeBatch
+    pv_const: object
+    order: np.ndarray
+    labels: list
+    sub_off: np.ndarray
+    z: np.ndarray
+    bucket: np.ndarray
+    fix_tau: np.ndarray
+    flt_tau: np.ndarray
+    buckets: list
+
+
+def credit_cell_book(trades, value_dt, curve_type, spreads, keys, buckets=None) -> CreditCells:
+    """`compile_credit_book`, `split_sub_books` and the (desk, bucket) ordering adr_credit_subbook_ladders asks for.  A trade
+    with a ratio node is refused by its index in the caller's list."""
+    book = compile_credit_book(trades, value_dt, curve_type, spreads, buckets)
+    sb = split_sub_books(book.batch, book.pv_const, book.order, list(keys))
+    z, bucket, fix_tau, flt_tau = book.z, book.bucket, book.fix_tau, book.flt_tau
+    if sb.perm is not None:
+        z, bucket, fix_tau, flt_tau = z[sb.perm], bucket[sb.perm], fix_tau[sb.fix_idx], flt_tau[sb.flt_idx]
+    batch, const, order = sb.batch, sb.pv_const, sb.order
+    desk = np.repeat(np.arange(len(sb.labels), dtype=np.int64), np.diff(sb.sub_off))
+    perm = np.lexsort((bucket, desk))                    # stable; the desks stay where they are
+    if not np.array_equal(perm, np.arange(perm.size)):
+        batch, fi, li = _permute_batch(batch, perm)
+        z, bucket, fix_tau, flt_tau = z[perm], bucket[perm], fix_tau[fi], flt_tau[li]
+        const, order = (None if const is None else const[perm]), order[perm]
+    ratio = np.nonzero(has_ratio_node(batch))[0]
+    if ratio.size:
+        raise LibError(f"trade {int(order[ratio[0]])} has a ratio node (a payment lag or a per-coupon notional): the credit "
+                       "sub-book ladders take trades whose float coupons are paid on their accrual end; "
+                       "pnl_credit_sub_books revalues such a book", status=_native.ADR_ERR_UNSUPPORTED)
+    return CreditCells(batch, const, order, sb.labels, sb.sub_off, z, bucket, fix_tau, flt_tau, book.labels)
+
+
+def price_credit_sub_books(engine: Engine, ir_model, trades, spreads, keys, buckets, reqs, host=False, curve_type=None):
+    """The desks' ladders at their spreads and their spread Greeks, from one launch chain (adr_credit_subbook_ladders).
+
+    ``trades``: a list of `OIS`, `Bond` and single-curve `FRN` objects on ``ir_model``'s curve; ``spreads`` and ``buckets``
+    one per trade as `compile_credit_book` takes them (``buckets=None``: no bucket anywhere); ``keys`` one hashable desk key
+    per trade.  Returns ``{"labels", "buckets", "tenors", "pv" [B], "delta" [B, P], "gamma" [B, P, P], "cs01" [B, G],
+    "spread_gamma" [B, G], "cross_gamma" [B, G, P], "ladders" [B, 1 + Q + Q Q]}``: ``delta`` per bp of a par quote and
+    ``gamma`` per bp squared, both at the spreads; ``cs01`` per bp of the bucket's spread, ``spread_gamma`` and
+    ``cross_gamma`` per bp squared; ``ladders`` the augmented rows (Q = P + G) that `ladder_pnl` takes beside
+    `credit_shock_matrix_bp`'s rows.  What ``reqs`` does not ask for is zeros.  ``host``: the CPU twin, no GPU needed.  A
+    trade with a ratio node is refused by its index in ``trades``."""
+    reqs = set(reqs)
+    want_gamma = RequestTypes.GAMMA in reqs
+    want_delta = want_gamma or RequestTypes.DELTA in reqs
+    cb = credit_cell_book(list(trades), ir_model._value_dt, curve_type or _curve_type_of(engine, ir_model), spreads, keys, buckets)
+    G = len(cb.buckets)
+    method = ir_model._interp_type.value
+    if host:
+        curve, tenors = _host_curve(ir_model)
+        out = _native.credit_subbook_ladders_host(method, curve.times, curve.dfs, curve.jac, curve.hess if want_gamma else None,
+                                                  cb.batch, cb.z, cb.bucket, cb.fix_tau, cb.flt_tau, G, cb.sub_off, want_delta,
+                                                  want_gamma)
+    else:
+        cur = engine._device_curve(ir_model)
+        tenors = cur["tenors"]
+        with _native.DeviceTrades(cur["ctx"], cb.batch) as dev_trades:
+            out = _native.credit_subbook_ladders(cur["ctx"], cur["dev"], dev_trades, cb.z, cb.bucket, cb.fix_tau, cb.flt_tau, G,
+                                                 cb.sub_off, want_delta, want_gamma)
+    if cb.pv_const is not None:              # the FRN compiler's curve-independent amounts (spread time 0), per desk
+        for b in range(len(cb.labels)):
+            c = cb.pv_const[cb.sub_off[b]:cb.sub_off[b + 1]]
+            if np.any(c != 0.0):
+                out["pv"][b] += float(np.sum(c))
+                out["ladders"][b, 0] = out["pv"][b]
+    out["labels"], out["buckets"], out["tenors"] = cb.labels, cb.buckets, tenors
     return out

@@ -127,6 +127,14 @@ print(f"300 bonds x 250 joint scenarios: 99% VaR {historical_var(credit_pnl, 0.9
       f"{expected_shortfall(credit_pnl, 0.975):,.0f}; rates alone: 99% VaR "
       f"{historical_var(grid.pnl_credit(bonds, z, issuers), 0.99):,.0f}")
 
+# ---- the bond desks' credit Greeks from one launch chain: CS01 per issuer, and the joint delta-gamma P&L set beside the revaluation
+bond_desks = [f"credit desk {i % 3}" for i in range(len(bonds))]
+cs = grid.pnl_credit_delta_gamma_sub_books(bonds, z, bond_desks, issuers, spread_moves)           # ladders at the spreads + spread Greeks
+cr = grid.explain_credit_sub_books(bonds, z, bond_desks, issuers, spread_moves)                   # against pnl_credit_sub_books
+print(f"{cs['labels'][0]}: CS01 by issuer {np.round(cs['cs01'][0], 0).tolist()} GBP per bp, DV01 {cs['delta'][0].sum():,.0f}; "
+      f"largest unexplained P&L of the 3 desks {np.abs(cr['unexplained']).max():,.0f} GBP of a largest move of "
+      f"{np.abs(cr['full']).max():,.0f}")
+
 # ---- firm-wide: desks across the OIS book and the YoY book, their P&L rows added by label, the firm's ES split among them
 from adrates_amd.market.position.scenarios import allocate_tail, combine_sub_book_rows
 yoy_desks = [("desk 0", "desk 1", "inflation desk")[i % 3] for i in range(len(yoy_book))]

@@ -888,6 +888,74 @@ int adr_ladder_pnl_dev(adr_ctx* ctx, int64_t B, int P, const double* ladders_dev
 int adr_ladder_pnl_host(int64_t B, int P, const double* ladders, int S, const double* shocks_bp, double* pnl, double* pnl_delta,
                         double* pnl_gamma);
 
+/*
+ * Credit sub-book Greeks: per sub-book the PV, the curve delta and gamma AT THE TRADES' SPREADS, CS01 and spread gamma
+ * per credit bucket and the rate x spread cross gamma, from one launch chain.  The spread side is adr_credit_scenario_pv's:
+ * z[n] (z-spread of a bond, discount margin of an FRN), bucket[n] in -1 .. G - 1 (-1: no bucket), 0 <= G <=
+ * ADR_CREDIT_MAX_BUCKETS, and one spread time per fixed flow / float coupon (fix_tau[n_fix], flt_tau[n_flt]); every
+ * payment is discounted at D(tp) exp(-z tau), the forward carries no spread.  The batch must be ordered by (sub-book,
+ * bucket): inside a sub-book the buckets do not decrease (unbucketed trades first).  A (sub-book, bucket) pair that holds
+ * trades is a CELL; C <= min(n, B (G + 1)) cells exist.
+ *
+ * out[B][1 + Q + Q * Q], Q = P + G, row-major, is an AUGMENTED ladder in agg's layout with Q in place of P:
+ *
+ *   out[b][0]                           pv of sub-book b at its spreads
+ *   delta'[p < P]                       curve delta per bp, at the spreads
+ *   delta'[P + g]                       CS01: dPV / dz of the sub-book's trades of bucket g, per bp
+ *   gamma'[p][q], p, q < P              curve gamma per bp^2, at the spreads
+ *   gamma'[p][P + g] = gamma'[P + g][p] d2PV / dz dquote_p of cell (b, g), per bp^2: ONE value stored twice
+ *   gamma'[P + g][P + g]                d2PV / dz^2 of cell (b, g), per bp^2
+ *   everything else                     +0.0 (a trade has one bucket: the spread-spread block is diagonal)
+ *
+ * so adr_ladder_pnl* with P := Q and shock rows [x_bp[P], dz * 1e4 [G]] gives the joint second-order expansion
+ * delta . x + x' Gamma x / 2 + sum_g (cs01_g y_g + csg_g y_g^2 / 2 + y_g cross_g . x), and adr_scenario_tail* apply to the
+ * result as they stand (Q <= ADR_LADDER_PNL_MAX_PILLARS is a limit of that step, not of these entries).  A sub-book
+ * without bucket g has +0.0 there; unbucketed trades are priced at their z and enter the curve block only.  pv always,
+ * delta' with ADR_REQ_DELTA or ADR_REQ_GAMMA, gamma' with ADR_REQ_GAMMA; blocks not requested are zeros.  The entries write
+ * and do not add.
+ *
+ * A chunk (at most ADR_SCENARIO_CHUNK trades of ONE cell) gives the record [pv, w[Kc], D[Kc], O[Kc], wz[Kc], cs, csg]
+ * (without GAMMA [pv, w[Kc], cs]); a cell's records are added in the plan's order by adr_subbook_ladders' rule, and by
+ * the same rule a sub-book's cell sums (cell j of the sub-book to slot j % 64, then the halving tree).  The curve block is
+ * projected from the sub-book's sums, the spread rows and columns from the cells' sums.  Contract: a sub-book's row has
+ * exactly the bits of the same entry called with B = 1 on that sub-book's trades alone with the same buckets and G - on
+ * the host twin and on the device -, does not depend on B or on the other sub-books, and repeats bit for bit from run to
+ * run; an empty sub-book's row is +0.0 throughout; gamma' is symmetric bit for bit in its cross rows and columns.  The
+ * device part rests on the same observed ordering of the LDS adds (ds_add_f64) as adr_subbook_ladders.  On the host twin,
+ * z = 0 everywhere and G = 0 give adr_subbook_ladders_host's rows bit for bit; on the device the rows agree with
+ * adr_subbook_ladders' to rounding only (the two knot kernels are different programs).  A trade with z == 0 has the
+ * factor 1.0 exactly, whatever its spread times hold.
+ *
+ * Refused: a ratio node (ADR_ERR_UNSUPPORTED, adr_subbook_ladders' wording), a curve whose tables for one wave (32 Kc
+ * bytes with GAMMA, 8 Kc without) do not fit the LDS (ADR_ERR_UNSUPPORTED); by the blocking entry and the host twin also
+ * what they can read: non-finite z or spread times, a bucket outside -1 .. G - 1, G outside 0 .. ADR_CREDIT_MAX_BUCKETS,
+ * a sub-book whose trades are not ordered by bucket (ADR_ERR_INVALID, naming the trade).  _dev checks scalars only; there
+ * a trade whose bucket or whose flows leave 0 .. n_fix / 0 .. n_flt makes its chunk read nothing and its cell's sums NaN.
+ *
+ * adr_credit_subbook_ladders: host arrays, builds the cells and the plan itself, blocks (one allocation).  _dev: device
+ * arrays - C, cell_plan_dev = adr_scenario_subbook_plan(n, C, cell_off), desk_cell_off_dev[B + 1] (sub-book b owns the
+ * cells desk_cell_off[b] .. desk_cell_off[b + 1]) and cell_bucket_dev[C] -, enqueues on `stream` (NULL: the ctx's own)
+ * without allocation, synchronisation or atomics to global memory.  adr_credit_subbook_ladders_work is its scratch in
+ * doubles, (ceil(n / 64) + 2 C + B) records, and leaves the rows of chunk records in *chunks when that is not NULL.
+ * _host: the CPU twin on the curve's arrays and a TradeBatch's: the same node, sum and projection code, chunks and orders.
+ */
+int64_t adr_credit_subbook_ladders_work(const adr_curve* curve, int64_t n, int64_t B, int64_t C, uint32_t req_mask, int64_t* chunks);
+int adr_credit_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, const double* z, const int32_t* bucket,
+                               int64_t n_fix, const double* fix_tau, int64_t n_flt, const double* flt_tau, int G, int64_t B,
+                               const int64_t* sub_off, uint32_t req_mask, double* out);
+int adr_credit_subbook_ladders_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, const double* z_dev,
+                                   const int32_t* bucket_dev, int64_t n_fix, const double* fix_tau_dev, int64_t n_flt,
+                                   const double* flt_tau_dev, int G, int64_t B, int64_t C, const int64_t* cell_plan_dev,
+                                   const int64_t* desk_cell_off_dev, const int32_t* cell_bucket_dev, uint32_t req_mask,
+                                   double* out_dev, double* work_dev, void* stream);
+int adr_credit_subbook_ladders_host(int interp_method, int K, int P, const double* times, const double* dfs, const double* jac,
+                                    const double* hess, int64_t n, const int64_t* fix_off, const int64_t* flt_off,
+                                    const double* fix_tp, const double* fix_pay, const double* flt_tp, const double* flt_ts,
+                                    const double* flt_te, const double* flt_alpha, const double* flt_weight, const double* notional,
+                                    const double* spread, const double* fix_sign, const double* flt_sign, const double* z,
+                                    const int32_t* bucket, const double* fix_tau, const double* flt_tau, int G, int64_t B,
+                                    const int64_t* sub_off, uint32_t req_mask, double* out);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
