@@ -499,12 +499,23 @@ def curve_df(ctx: Context, curve: DeviceCurve, t):
     return float(out[0]) if np.ndim(t) == 0 else out.reshape(np.shape(t))
 
 
+def _curve_arrays(times, dfs, jac, hess, shapes=False):
+    """``(times, dfs, jac, hess or None, K, P)`` as contiguous float64 arrays; ``shapes``: refuse arrays that do not fit
+    jac's ``[K, P]``."""
+    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
+    K, P = jac.shape
+    if shapes and (times.shape != (K,) or dfs.shape != (K,)):
+        raise LibError("curve arrays have inconsistent shapes")
+    hess = None if hess is None else _f64(hess)
+    if shapes and hess is not None and hess.shape != (K, P, P):
+        raise LibError("hess must have shape [K, P, P]")
+    return times, dfs, jac, hess, K, P
+
+
 def curve_tables_host(times, dfs, jac, hess=None):
     """Log-space tables of the reachable knots, computed by the library's host
     code (no GPU needed) - used by the CPU tests."""
-    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
-    K, P = jac.shape
-    hess_c = None if hess is None else _f64(hess)
+    times, dfs, jac, hess_c, K, P = _curve_arrays(times, dfs, jac, hess)
     lib = load()
     kc = _check(lib.adr_curve_tables_host(K, P, _ptr(times), _ptr(dfs), _ptr(jac), _ptr(hess_c),
                                           None, None, None, None), "adr_curve_tables_host")
@@ -519,9 +530,7 @@ def curve_tables_host(times, dfs, jac, hess=None):
 
 def curve_layout_host(times, dfs, jac, hess=None):
     """LDS layout the fast kernels would use for this curve (diagnostic; no GPU needed)."""
-    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
-    K, P = jac.shape
-    hess_c = None if hess is None else _f64(hess)
+    times, dfs, jac, hess_c, K, P = _curve_arrays(times, dfs, jac, hess)
     info = np.zeros(16, dtype=np.int64)
     _check(load().adr_curve_layout_host(K, P, _ptr(times), _ptr(dfs), _ptr(jac), _ptr(hess_c), _ptr(info, _i64p)),
            "adr_curve_layout_host")
@@ -1358,13 +1367,7 @@ def subbook_ladders_host(interp_method: int, times, dfs, jac, hess, batch, sub_o
     """`subbook_ladders` on the CPU (adr_subbook_ladders_host) for a `TradeBatch` and the curve arrays `DeviceCurve`
     takes: the same node and projection code, chunks and summation orders; no GPU needed."""
     sub_off, B = _sub_offsets(sub_off)
-    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
-    K, P = jac.shape
-    if times.shape != (K,) or dfs.shape != (K,):
-        raise LibError("curve arrays have inconsistent shapes")
-    hess = None if hess is None else _f64(hess)
-    if hess is not None and hess.shape != (K, P, P):
-        raise LibError("hess must have shape [K, P, P]")
+    times, dfs, jac, hess, K, P = _curve_arrays(times, dfs, jac, hess, shapes=True)
     out = np.empty((B, 1 + P + P * P))
     _check(load().adr_subbook_ladders_host(int(interp_method), K, P, _ptr(times), _ptr(dfs), _ptr(jac), _ptr(hess),
                                            *_batch_args(*_batch_arrays(batch)), B, _ptr(sub_off, _i64p),
@@ -1454,13 +1457,7 @@ def credit_subbook_ladders_host(interp_method: int, times, dfs, jac, hess, batch
     """`credit_subbook_ladders` on the CPU (adr_credit_subbook_ladders_host) for a `TradeBatch` and the curve arrays
     `DeviceCurve` takes: the same node, sum and projection code, chunks and orders; no GPU needed."""
     sub_off, B = _sub_offsets(sub_off)
-    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
-    K, P = jac.shape
-    if times.shape != (K,) or dfs.shape != (K,):
-        raise LibError("curve arrays have inconsistent shapes")
-    hess = None if hess is None else _f64(hess)
-    if hess is not None and hess.shape != (K, P, P):
-        raise LibError("hess must have shape [K, P, P]")
+    times, dfs, jac, hess, K, P = _curve_arrays(times, dfs, jac, hess, shapes=True)
     arrays = _batch_arrays(batch)
     n, a = arrays[0], arrays[3]
     z, bucket, fix_tau, flt_tau, G = _credit_ladder_inputs(z, bucket, fix_tau, flt_tau, G, n, a["fix_tp"].size, a["flt_tp"].size)
@@ -1592,9 +1589,7 @@ def route_host(interp_method: int, times, dfs, jac, hess, batch, req_mask: int, 
     """The launch plan adr_price_dev would replay for this curve, batch and request, and how often it prices each trade
     (adr_route_host; no GPU needed).  Returns ``(launches, cover)``: launches = [(family, set, items, blocks)], names from
     ROUTE_FAMILIES / ROUTE_SETS; cover [n] int32."""
-    times, dfs, jac = _f64(times), _f64(dfs), _f64(jac)
-    K, P = jac.shape
-    hess_c = None if hess is None else _f64(hess)
+    times, dfs, jac, hess_c, K, P = _curve_arrays(times, dfs, jac, hess)
     n = batch.n_trades
     fo, lo = np.ascontiguousarray(batch.fix_off, dtype=np.int64), np.ascontiguousarray(batch.flt_off, dtype=np.int64)
     tp, te, al = _f64(batch.flt_tp), _f64(batch.flt_te), _f64(batch.flt_alpha)

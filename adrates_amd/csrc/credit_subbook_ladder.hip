@@ -16,11 +16,14 @@
 //      beside the flow and a fourth table wz per wave.  work[chunk] = [pv, w, D, O, wz, cs, csg] ([pv, w, cs] without GAMMA).
 //   2. sub::enqueue_sum adds every cell's chunk records, then by the same rule every desk's cell sums.
 //   3. credit_project_kernel writes the curve block of the augmented ladder out[b] = [pv, delta'[Q], gamma'[Q][Q]],
-//      Q = P + G, from the desk sums (subbook_project_kernel's expression and order) and zeros elsewhere;
+//      Q = P + G, from the desk sums (sbl::project_curve_block, the code subbook_project_kernel runs) and zeros elsewhere;
 //      credit_cell_kernel then writes the spread rows and columns from the cell sums.
 //
 // Trades with ratio nodes are refused.  The host twin (adr_credit_subbook_ladders_host) runs the same node, sum and
-// projection code in the same chunks and orders on the CPU.
+// projection code in the same chunks and orders on the CPU.  The projection of the curve block, the knot launch, the
+// checks of the handles and of the host arrays and the host's trade walk are subbook_ladder_common.hpp's, shared with
+// subbook_ladder.hip; this source keeps the knot kernel, the cell kernel and the spread side's checks, which each entry
+// puts between the shared ones in its own order.
 #include "subbook_ladder_common.hpp"
 
 #pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
@@ -237,66 +240,8 @@ struct ProjectArgs {
     double* out;                     // [B][1 + Q + Q Q]
 };
 
-// The curve block of the augmented ladder from the desks' sums - subbook_project_kernel's expression and order - and +0.0
-// in every spread row and column.  blockIdx.y < Q: row y of gamma' (lane = column); blockIdx.y == Q: pv and delta'.
-__global__ __launch_bounds__(kWave * kProjWaves) void credit_project_kernel(ProjectArgs a) {
-    __shared__ int col_off[kWidePad + 1];
-    __shared__ double s_part[kProjWaves][kProjDesks][kWave];
-    const CurveDev& cv = a.cv;
-    const int P = cv.P, Kc = cv.Kc, Q = P + a.G;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kProjDesks;
-    const int nd = a.B - b0 < kProjDesks ? static_cast<int>(a.B - b0) : kProjDesks;
-    const int64_t stride = 1 + Q + static_cast<int64_t>(Q) * Q;
-    const bool first = static_cast<int>(blockIdx.y) == Q;
-    const int row = first ? 0 : blockIdx.y;
-    const int p = row < P ? row : 0;
-    if (threadIdx.x == 0) fill_col_off(col_off);
-    __syncthreads();
-    if (first && threadIdx.x < nd) a.out[(b0 + threadIdx.x) * stride] = a.sums[(b0 + threadIdx.x) * a.S];
-    const bool wanted = (first ? a.want_delta != 0 : a.want_gamma != 0) && row < P;
-    double* dst = a.out + b0 * stride + (first ? 1 : 1 + Q + static_cast<int64_t>(row) * Q);
-    for (int q0 = 0; q0 < Q; q0 += kWave) {              // columns in blocks of one wavefront
-        const int q = q0 + lane, qq = q < P ? q : 0;     // lanes beyond the curve block compute a copy of column 0
-        double s[kProjDesks];
-#pragma unroll
-        for (int d = 0; d < kProjDesks; ++d) s[d] = 0.0;
-        if (wanted && q0 < P) {
-            for (int k = wave; k < Kc; k += kProjWaves) {
-                const double aq = lj_at(cv, k, qq);
-                if (first) {
-#pragma unroll
-                    for (int d = 0; d < kProjDesks; ++d)
-                        if (d < nd) s[d] = delta_step(s[d], a.sums[(b0 + d) * a.S + 1 + k], aq);
-                    continue;
-                }
-                const bool next = k + 1 < Kc;
-                const double ap = lj_at(cv, k, p);
-                const double bp = next ? lj_at(cv, k + 1, p) : 0.0, bq = next ? lj_at(cv, k + 1, qq) : 0.0;
-                const double lc = lc_at(cv, col_off, k, p, qq);
-#pragma unroll
-                for (int d = 0; d < kProjDesks; ++d)
-                    if (d < nd) {
-                        const double* rec = a.sums + (b0 + d) * a.S + 1 + k;           // uniform: scalar loads
-                        s[d] = gamma_step(s[d], rec[0], rec[Kc], next ? rec[2 * Kc] : 0.0, ap, aq, bp, bq, lc);
-                    }
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < kProjDesks; ++d) s_part[wave][d][lane] = s[d];
-        __syncthreads();
-        if (wave == 0 && q < Q) {
-            for (int d = 0; d < nd; ++d) {
-                double t = s_part[0][d][lane];
-#pragma unroll
-                for (int i = 1; i < kProjWaves; ++i) t = t + s_part[i][d][lane];
-                dst[d * stride + q] = q < P ? t * (first ? 1e-4 : 1e-8) : 0.0;
-            }
-        }
-        __syncthreads();
-    }
-}
+// The curve block of the augmented ladder from the desks' sums and +0.0 in every spread row and column.
+__global__ __launch_bounds__(kWave * kProjWaves) void credit_project_kernel(ProjectArgs a) { project_curve_block<true>(a); }
 
 // One pillar's cross term of a cell: sum_k wz_k LJ[k][p], the knots taken as the projection's waves take them.
 template <class LJ>
@@ -344,28 +289,6 @@ __global__ __launch_bounds__(kWave * kCellWaves) void credit_cell_kernel(Project
 }
 
 // -------------------------------------------------------------------------------------------------------------- host
-// The waves of a block of the knot kernel on this curve: as many as the LDS budget holds, 0 when not even one fits.
-inline int knot_waves(int K, int Kc, bool gamma) {
-    const size_t per_wave = static_cast<size_t>(tables(gamma)) * Kc * sizeof(double), shared = shared_bytes(K, Kc);
-    if (shared + per_wave > scen::kLdsBudget) return 0;
-    return static_cast<int>(std::min<size_t>(kMaxWaves, (scen::kLdsBudget - shared) / per_wave));
-}
-
-template <bool kLog>
-hipError_t launch_knot(const KnotArgs& a, bool gamma, size_t lds, unsigned blocks, hipStream_t stream) {
-    auto kernel = gamma ? &credit_subbook_knot_kernel<kLog, true> : &credit_subbook_knot_kernel<kLog, false>;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWave * a.waves), lds, stream, a);
-    return hipGetLastError();
-}
-
-struct Handles {
-    const CurveDev* cv;
-    const TradesDev* tr;
-};
-
 struct Extra {           // what the trades carry besides the batch
     const double* z;
     const int32_t* bucket;
@@ -385,27 +308,14 @@ int check_buckets(const std::string& w, int G) {
 // The scalars and handles of an entry, checked.
 int handles(const std::string& w, const adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, const Extra& x, int64_t B,
             const Request& rq, Handles* h) {
-    if (!ctx || !curve || !trades) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx/curve/trades");
-    const adr_ctx *co = nullptr, *to = nullptr;
-    h->cv = adr_curve_device_view(curve, &co);
-    h->tr = adr_trades_device_view(trades, &to);
-    if (co != ctx || to != ctx) return adr_set_error(ADR_ERR_INVALID, w + ": curve/trades were uploaded through another ctx");
-    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
-    if (h->tr->n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
-    const int rc = check_buckets(w, x.G);
+    int rc = check_handles(w, ctx, curve, trades, B, h);
+    if (rc == ADR_OK) rc = check_buckets(w, x.G);
     if (rc != ADR_OK) return rc;
     if (!x.z || !x.bucket) return adr_set_error(ADR_ERR_INVALID, w + ": z or bucket is NULL");
     if (x.n_fix < 0 || x.n_flt < 0 || x.n_fix > INT32_MAX || x.n_flt > INT32_MAX)
         return adr_set_error(ADR_ERR_INVALID, w + ": flow counts must lie in 0 .. 2^31 - 1");
     if ((x.n_fix > 0 && !x.fix_tau) || (x.n_flt > 0 && !x.flt_tau)) return adr_set_error(ADR_ERR_INVALID, w + ": null spread-time array");
-    if (rq.gamma && !h->cv->lc_lanes && !h->cv->lcflat)
-        return adr_set_error(ADR_ERR_INVALID, w + ": GAMMA requested but the curve was uploaded without hess");
-    if (knot_waves(h->cv->K, h->cv->Kc, rq.gamma) < 1)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": the knot tables of one wave (" + std::to_string(h->cv->Kc) +
-                                                      " knots) do not fit the 160 KiB LDS of a CU");
-    const int64_t ratio = adr_trades_first_ratio(trades);
-    if (ratio >= 0) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ratio_message(ratio));
-    return ADR_OK;
+    return check_fit(w, trades, *h, rq, tables(rq.gamma));
 }
 
 // The spread side on the host: finite z and spread times, buckets inside -1 .. G - 1 (credit_scenario_pv.hip's wording).
@@ -480,17 +390,17 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Handles& h, int64_t B, con
     const int rc = scen::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const CurveDev& cv = *h.cv;
-    const int S = record_doubles(cv.Kc, rq.gamma), waves = knot_waves(cv.K, cv.Kc, rq.gamma);
+    const int S = record_doubles(cv.Kc, rq.gamma);
     const int64_t C = d.C, cap = sub::max_chunks(h.tr->n, C, kChunk);
     const sub::Plan pl = sub::plan_view(d.cell_plan, C);
     double *cells = work + cap * S, *sums = cells + C * S;
-    const size_t lds = shared_bytes(cv.K, cv.Kc) + static_cast<size_t>(waves) * tables(rq.gamma) * cv.Kc * sizeof(double);
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, static_cast<int64_t>(scen::kLdsBudget / lds)));
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((cap + waves - 1) / waves, per_cu * adr_ctx_compute_units(ctx)));
+    const KnotGrid kg = knot_grid(ctx, cv, tables(rq.gamma), cap);
     const KnotArgs ka{cv, *h.tr, d.x.z, d.x.bucket, Taus{d.x.fix_tau, d.x.flt_tau}, d.x.n_fix, d.x.n_flt, d.x.G, cap, pl.chunk_off + C,
-                      pl.bounds, work, S, waves};
-    hipError_t e = cv.method == ADR_INTERP_LINEAR_FWD_RATES ? launch_knot<false>(ka, rq.gamma, lds, static_cast<unsigned>(blocks), stream)
-                                                            : launch_knot<true>(ka, rq.gamma, lds, static_cast<unsigned>(blocks), stream);
+                      pl.bounds, work, S, kg.waves};
+    const bool is_log = cv.method != ADR_INTERP_LINEAR_FWD_RATES;
+    hipError_t e = launch_knot(rq.gamma ? (is_log ? &credit_subbook_knot_kernel<true, true> : &credit_subbook_knot_kernel<false, true>)
+                                        : (is_log ? &credit_subbook_knot_kernel<true, false> : &credit_subbook_knot_kernel<false, false>),
+                               ka, kg, stream);
     if (e == hipSuccess) e = sub::enqueue_sum(work, pl.chunk_off, cap, C, S, cells, stream);
     if (e == hipSuccess) e = sub::enqueue_sum(cells, d.desk_cell_off, C, B, S, sums, stream);
     const int64_t tiles = (B + kProjDesks - 1) / kProjDesks, cell_blocks = (C + kCellWaves - 1) / kCellWaves;
@@ -540,18 +450,15 @@ void host_chunks(const CurveTables& t, int method, bool gamma, const scen::HostB
             rec[1 + 3 * Kc + d.a] = rec[1 + 3 * Kc + d.a] + v1.wa;
             if (two) rec[1 + 3 * Kc + d.b] = rec[1 + 3 * Kc + d.b] + v1.wb;
         };
-        const scen::ChunkRange r = scen::host_chunk_range(ch, bounds, b.n);
-        for (int64_t i = r.i0; i < r.i1; ++i) {
-            const TradeRef tr{b.fix_off[i], b.flt_off[i], static_cast<int>(b.fix_off[i + 1] - b.fix_off[i]),
-                              static_cast<int>(b.flt_off[i + 1] - b.flt_off[i]), b.notional[i], b.spread[i], b.fix_sign[i], b.flt_sign[i]};
-            for (int c = 0; c < tr.n_flt; ++c) {
+        host_chunk_walk(
+            b, bounds, ch,
+            [&](const TradeRef& tr, int64_t i, int c) {
                 Amount3 pay, start;
                 float_nodes(g, u, tr, x.z[i], c, &pay, &start);
                 add(pay);
                 add(start);
-            }
-            for (int c = 0; c < tr.n_fix; ++c) add(fixed_node(g, u, tr, x.z[i], c));
-        }
+            },
+            [&](const TradeRef& tr, int64_t i, int c) { add(fixed_node(g, u, tr, x.z[i], c)); });
     }
 }
 
@@ -562,35 +469,8 @@ void host_project(const CurveTables& t, const Request& rq, int G, const double* 
     const size_t stride = 1 + Q + static_cast<size_t>(Q) * Q;
     const int nt = tables(rq.gamma);
     for (int64_t b = lo; b < hi; ++b) {
-        const double *rec = sums + b * S, *w = rec + 1, *D = w + Kc, *O = D + Kc;
-        double* o = out + b * stride;
-        std::fill(o, o + stride, 0.0);
-        o[0] = rec[0];
-        double* gamma = o + 1 + Q;
-        for (int q = 0; rq.delta && q < P; ++q) {
-            double tot = 0.0;
-            for (int wave = 0; wave < kProjWaves; ++wave) {
-                double s = 0.0;
-                for (int k = wave; k < Kc; k += kProjWaves) s = delta_step(s, w[k], host_lj(t, k, q));
-                tot = wave == 0 ? s : tot + s;
-            }
-            o[1 + q] = tot * 1e-4;
-        }
-        for (int p = 0; rq.gamma && p < P; ++p)
-            for (int q = 0; q < P; ++q) {
-                double tot = 0.0;
-                for (int wave = 0; wave < kProjWaves; ++wave) {
-                    double s = 0.0;
-                    for (int k = wave; k < Kc; k += kProjWaves) {
-                        const bool next = k + 1 < Kc;
-                        s = gamma_step(s, w[k], D[k], next ? O[k] : 0.0, host_lj(t, k, p), host_lj(t, k, q),
-                                       next ? host_lj(t, k + 1, p) : 0.0, next ? host_lj(t, k + 1, q) : 0.0,
-                                       t.lc[(static_cast<size_t>(k) * P + p) * P + q]);
-                    }
-                    tot = wave == 0 ? s : tot + s;
-                }
-                gamma[static_cast<size_t>(p) * Q + q] = tot * 1e-8;
-            }
+        double *o = out + b * stride, *gamma = o + 1 + Q;
+        host_project_curve(t, rq, sums + b * S, Q, o);
         for (int64_t j = c.desk_cell_off[b]; rq.delta && j < c.desk_cell_off[b + 1]; ++j) {
             const int g = c.cell_bucket[j];
             if (g < 0) continue;
@@ -674,12 +554,12 @@ int adr_credit_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, const adr_t
     double *dout = take(n_out), *dwork = take(W), *dz = take(nn), *dft = take(nf), *dlt = take(nl);
     int64_t *dplan = reinterpret_cast<int64_t*>(take(plan.size())), *ddesk = reinterpret_cast<int64_t*>(take(static_cast<size_t>(B + 1)));
     int32_t *dbucket = reinterpret_cast<int32_t*>(p), *dcellb = dbucket + nn;
-    struct Piece { void* dst; const void* src; size_t bytes; };
-    const Piece in[] = {{dz, z, nn * d}, {dft, fix_tau, nf * d}, {dlt, flt_tau, nl * d}, {dplan, plan.data(), plan.size() * sizeof(int64_t)},
-                        {ddesk, cells.desk_cell_off.data(), static_cast<size_t>(B + 1) * sizeof(int64_t)},
-                        {dbucket, bucket, nn * sizeof(int32_t)}, {dcellb, cells.cell_bucket.data(), static_cast<size_t>(C) * sizeof(int32_t)}};
-    for (const Piece& pc : in)
-        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
+    const adr::call::Piece in[] = {{dz, z, nn * d}, {dft, fix_tau, nf * d}, {dlt, flt_tau, nl * d},
+                                   {dplan, plan.data(), plan.size() * sizeof(int64_t)},
+                                   {ddesk, cells.desk_cell_off.data(), static_cast<size_t>(B + 1) * sizeof(int64_t)},
+                                   {dbucket, bucket, nn * sizeof(int32_t)},
+                                   {dcellb, cells.cell_bucket.data(), static_cast<size_t>(C) * sizeof(int32_t)}};
+    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
     const CL::DevArrays da{CL::Extra{dz, dbucket, n_fix, dft, n_flt, dlt, G}, C, dplan, ddesk, dcellb};
     if (e == hipSuccess) rc = CL::enqueue(w, ctx, h, B, da, rq, dout, dwork, stream);
     if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, n_out * d, hipMemcpyDeviceToHost, stream);
@@ -696,27 +576,15 @@ int adr_credit_subbook_ladders_host(int interp_method, int K, int P, const doubl
     const std::string w = "adr_credit_subbook_ladders_host";
     namespace SC = adr::scen;
     const CL::Request rq = CL::request_of(req_mask);
-    if (interp_method != ADR_INTERP_FLAT_FWD_RATES && interp_method != ADR_INTERP_LINEAR_FWD_RATES &&
-        interp_method != ADR_INTERP_LINEAR_ZERO_RATES)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and LINEAR_ZERO_RATES (4) "
-                                                      "are implemented");
-    if (n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
-    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
-    int rc = CL::check_buckets(w, G);
-    if (rc != ADR_OK) return rc;
-    if (!out) return adr_set_error(ADR_ERR_INVALID, w + ": out is NULL");
-    if (!times || !dfs || !jac) return adr_set_error(ADR_ERR_INVALID, w + ": null curve arrays");
-    if (rq.gamma && !hess) return adr_set_error(ADR_ERR_INVALID, w + ": GAMMA requested but hess is NULL");
-    if (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign)
-        return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
-    if (!z || !bucket) return adr_set_error(ADR_ERR_INVALID, w + ": z or bucket is NULL");
+    const CL::HostCurve c{interp_method, K, P, times, dfs, jac, hess};
     const SC::HostBatch b{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread,
                           fix_sign, flt_sign};
-    for (int64_t i = 0; rc == ADR_OK && i < n; ++i) {      // trade by trade: the first trade at fault decides the message
-        rc = SC::check_leg_offsets(w, b, i, i + 1);
-        if (rc == ADR_OK) rc = SC::check_trade_values(w, b, i, i + 1);
-    }
-    if (rc == ADR_OK) rc = SC::check_flows(w, b);
+    int rc = CL::check_host_counts(w, interp_method, n, B);
+    if (rc == ADR_OK) rc = CL::check_buckets(w, G);
+    if (rc == ADR_OK) rc = CL::check_host_arrays(w, c, b, rq, out);
+    if (rc != ADR_OK) return rc;
+    if (!z || !bucket) return adr_set_error(ADR_ERR_INVALID, w + ": z or bucket is NULL");
+    rc = CL::check_host_trades(w, b);
     if (rc != ADR_OK) return rc;
     const CL::Extra x{z, bucket, fix_off[n], fix_tau, flt_off[n], flt_tau, G};
     if ((x.n_fix > 0 && !fix_tau) || (x.n_flt > 0 && !flt_tau)) return adr_set_error(ADR_ERR_INVALID, w + ": null spread-time array");
@@ -729,15 +597,9 @@ int adr_credit_subbook_ladders_host(int interp_method, int K, int P, const doubl
     std::vector<int64_t> plan;
     rc = adr::sub::build_plan(w, n, C, cells.cell_off.data(), plan);
     if (rc != ADR_OK) return rc;
-    {
-        std::vector<uint8_t> ratio(static_cast<size_t>(n));
-        adr::route::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, ratio.data());
-        const auto it = std::find(ratio.begin(), ratio.end(), uint8_t(1));
-        if (it != ratio.end()) return adr_set_error(ADR_ERR_UNSUPPORTED, w + CL::ratio_message(it - ratio.begin()));
-    }
     adr::CurveTables t;
-    const std::string err = adr::build_curve_tables(K, P, times, dfs, jac, rq.gamma ? hess : nullptr, t);
-    if (!err.empty()) return adr_set_error(ADR_ERR_INVALID, w + ": " + err);
+    rc = CL::host_tables(w, c, b, rq, t);
+    if (rc != ADR_OK) return rc;
     const int S = CL::record_doubles(t.Kc, rq.gamma);
     const int64_t chunks = plan[C];
     std::vector<double> work(static_cast<size_t>(chunks) * S), csum(static_cast<size_t>(C) * S), sums(static_cast<size_t>(B) * S);

@@ -15,11 +15,13 @@
 //      wave's own tables in LDS.  A chunk starts from zeroed tables and ends by writing work[chunk] = [pv, w, D, O]: the
 //      record depends on the chunk's trades alone.
 //   2. sub::enqueue_sum adds every sub-book's records in the plan's order (chunk j to slot j % 64, then the halving tree).
-//   3. subbook_project_kernel: out[b] = [pv, delta[P], gamma[P][P]], kernels_knot.hip's expression once per sub-book.  A
-//      block takes kProjDesks sub-books and one row of the ladder, so a row of LJ / LC is read once for all of them.
+//   3. subbook_project_kernel: out[b] = [pv, delta[P], gamma[P][P]], kernels_knot.hip's expression once per sub-book
+//      (sbl::project_curve_block, subbook_ladder_common.hpp).
 //
 // Trades with ratio nodes (payment lag, per-coupon notionals) are refused.  The host twin (adr_subbook_ladders_host) runs
-// the same node and projection code in the same chunks and summation orders on the CPU.
+// the same node and projection code in the same chunks and summation orders on the CPU.  The projection, the knot launch,
+// the checks of the handles and of the host arrays and the host's trade walk are subbook_ladder_common.hpp's, shared with
+// credit_subbook_ladder.hip; this source keeps the knot kernel, its record and the order of each entry's checks.
 #include "subbook_ladder_common.hpp"
 
 #pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
@@ -133,108 +135,17 @@ struct ProjectArgs {
     double* out;                     // [B][1 + P + P P]
 };
 
-// blockIdx.y < P: row p of the gamma matrices (lane q); blockIdx.y == P: pv and the delta ladders (lane p).
-__global__ __launch_bounds__(kWave * kProjWaves) void subbook_project_kernel(ProjectArgs a) {
-    __shared__ int col_off[kWidePad + 1];
-    __shared__ double s_part[kProjWaves][kProjDesks][kWave];
-    const CurveDev& cv = a.cv;
-    const int P = cv.P, Kc = cv.Kc;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kProjDesks;
-    const int nd = a.B - b0 < kProjDesks ? static_cast<int>(a.B - b0) : kProjDesks;
-    const int64_t stride = 1 + P + static_cast<int64_t>(P) * P;
-    const bool first = static_cast<int>(blockIdx.y) == P;
-    const int p = first ? 0 : blockIdx.y;
-    if (threadIdx.x == 0) fill_col_off(col_off);
-    __syncthreads();
-    if (first && threadIdx.x < nd) a.out[(b0 + threadIdx.x) * stride] = a.sums[(b0 + threadIdx.x) * a.S];
-    const bool wanted = first ? a.want_delta != 0 : a.want_gamma != 0;
-    double* dst = a.out + b0 * stride + (first ? 1 : 1 + P + static_cast<int64_t>(p) * P);
-    for (int q0 = 0; q0 < P; q0 += kWave) {              // columns in blocks of one wavefront
-        const int q = q0 + lane, qq = q < P ? q : 0;     // lanes beyond the ladder compute a copy of column 0 and store nothing
-        double s[kProjDesks];
-#pragma unroll
-        for (int d = 0; d < kProjDesks; ++d) s[d] = 0.0;
-        if (wanted) {
-            for (int k = wave; k < Kc; k += kProjWaves) {
-                const double aq = lj_at(cv, k, qq);
-                if (first) {
-#pragma unroll
-                    for (int d = 0; d < kProjDesks; ++d)
-                        if (d < nd) s[d] = delta_step(s[d], a.sums[(b0 + d) * a.S + 1 + k], aq);
-                    continue;
-                }
-                const bool next = k + 1 < Kc;
-                const double ap = lj_at(cv, k, p);
-                const double bp = next ? lj_at(cv, k + 1, p) : 0.0, bq = next ? lj_at(cv, k + 1, qq) : 0.0;
-                const double lc = lc_at(cv, col_off, k, p, qq);
-#pragma unroll
-                for (int d = 0; d < kProjDesks; ++d)
-                    if (d < nd) {
-                        const double* rec = a.sums + (b0 + d) * a.S + 1 + k;           // uniform: scalar loads
-                        s[d] = gamma_step(s[d], rec[0], rec[Kc], next ? rec[2 * Kc] : 0.0, ap, aq, bp, bq, lc);
-                    }
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < kProjDesks; ++d) s_part[wave][d][lane] = s[d];
-        __syncthreads();
-        if (wave == 0 && q < P) {
-            for (int d = 0; d < nd; ++d) {
-                double t = s_part[0][d][lane];
-#pragma unroll
-                for (int i = 1; i < kProjWaves; ++i) t = t + s_part[i][d][lane];
-                dst[d * stride + q] = t * (first ? 1e-4 : 1e-8);
-            }
-        }
-        __syncthreads();
-    }
-}
+__global__ __launch_bounds__(kWave * kProjWaves) void subbook_project_kernel(ProjectArgs a) { project_curve_block<false>(a); }
 
 // -------------------------------------------------------------------------------------------------------------- host
-// The waves of a block of the knot kernel on this curve: as many as the LDS budget holds, 0 when not even one fits.
-inline int knot_waves(int K, int Kc, bool gamma) {
-    const size_t per_wave = static_cast<size_t>(gamma ? 3 : 1) * Kc * sizeof(double), shared = shared_bytes(K, Kc);
-    if (shared + per_wave > scen::kLdsBudget) return 0;
-    return static_cast<int>(std::min<size_t>(kMaxWaves, (scen::kLdsBudget - shared) / per_wave));
-}
-
-inline int record_doubles(int Kc, bool gamma) { return 1 + (gamma ? 3 : 1) * Kc; }
-
-template <bool kLog>
-hipError_t launch_knot(const KnotArgs& a, bool gamma, size_t lds, unsigned blocks, hipStream_t stream) {
-    auto kernel = gamma ? &subbook_knot_kernel<kLog, true> : &subbook_knot_kernel<kLog, false>;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWave * a.waves), lds, stream, a);
-    return hipGetLastError();
-}
+inline int tables(bool gamma) { return gamma ? 3 : 1; }
+inline int record_doubles(int Kc, bool gamma) { return 1 + tables(gamma) * Kc; }
 
 // What an entry needs of its handles, checked.
-struct Handles {
-    const CurveDev* cv;
-    const TradesDev* tr;
-};
-
 int handles(const std::string& w, const adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, int64_t B, const Request& rq,
             Handles* h) {
-    if (!ctx || !curve || !trades) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx/curve/trades");
-    const adr_ctx *co = nullptr, *to = nullptr;
-    h->cv = adr_curve_device_view(curve, &co);
-    h->tr = adr_trades_device_view(trades, &to);
-    if (co != ctx || to != ctx) return adr_set_error(ADR_ERR_INVALID, w + ": curve/trades were uploaded through another ctx");
-    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
-    if (h->tr->n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
-    if (rq.gamma && !h->cv->lc_lanes && !h->cv->lcflat)
-        return adr_set_error(ADR_ERR_INVALID, w + ": GAMMA requested but the curve was uploaded without hess");
-    if (knot_waves(h->cv->K, h->cv->Kc, rq.gamma) < 1)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": the knot tables of one wave (" + std::to_string(h->cv->Kc) +
-                                                      " knots) do not fit the 160 KiB LDS of a CU");
-    const int64_t ratio = adr_trades_first_ratio(trades);
-    if (ratio >= 0) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ratio_message(ratio));
-    return ADR_OK;
+    const int rc = check_handles(w, ctx, curve, trades, B, h);
+    return rc != ADR_OK ? rc : check_fit(w, trades, *h, rq, tables(rq.gamma));
 }
 
 // The three steps on `stream`; every pointer is device memory.  work: adr_subbook_ladders_work doubles.
@@ -247,16 +158,16 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Handles& h, int64_t B, con
     const int rc = scen::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const CurveDev& cv = *h.cv;
-    const int S = record_doubles(cv.Kc, rq.gamma), waves = knot_waves(cv.K, cv.Kc, rq.gamma);
+    const int S = record_doubles(cv.Kc, rq.gamma);
     const int64_t cap = sub::max_chunks(h.tr->n, B, kChunk);
     const sub::Plan pl = sub::plan_view(plan, B);
     double* sums = work + cap * S;                       // [B][S]
-    const size_t lds = shared_bytes(cv.K, cv.Kc) + static_cast<size_t>(waves) * (S - 1) * sizeof(double);
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, static_cast<int64_t>(scen::kLdsBudget / lds)));
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((cap + waves - 1) / waves, per_cu * adr_ctx_compute_units(ctx)));
-    const KnotArgs ka{cv, *h.tr, cap, pl.chunk_off + B, pl.bounds, work, S, waves};
-    hipError_t e = cv.method == ADR_INTERP_LINEAR_FWD_RATES ? launch_knot<false>(ka, rq.gamma, lds, static_cast<unsigned>(blocks), stream)
-                                                            : launch_knot<true>(ka, rq.gamma, lds, static_cast<unsigned>(blocks), stream);
+    const KnotGrid kg = knot_grid(ctx, cv, tables(rq.gamma), cap);
+    const KnotArgs ka{cv, *h.tr, cap, pl.chunk_off + B, pl.bounds, work, S, kg.waves};
+    const bool is_log = cv.method != ADR_INTERP_LINEAR_FWD_RATES;
+    hipError_t e = launch_knot(rq.gamma ? (is_log ? &subbook_knot_kernel<true, true> : &subbook_knot_kernel<false, true>)
+                                        : (is_log ? &subbook_knot_kernel<true, false> : &subbook_knot_kernel<false, false>),
+                               ka, kg, stream);
     if (e == hipSuccess) e = sub::enqueue_sum(work, pl.chunk_off, cap, B, S, sums, stream);
     const int64_t tiles = (B + kProjDesks - 1) / kProjDesks;
     if (e == hipSuccess && tiles > INT32_MAX) e = hipErrorInvalidConfiguration;
@@ -294,55 +205,22 @@ void host_chunks(const CurveTables& t, int method, bool gamma, const scen::HostB
                 if (kLog) rec[1 + 2 * Kc + d.a] = rec[1 + 2 * Kc + d.a] + u.o;
             }
         };
-        const scen::ChunkRange r = scen::host_chunk_range(ch, bounds, b.n);
-        for (int64_t i = r.i0; i < r.i1; ++i) {
-            const TradeRef tr{b.fix_off[i], b.flt_off[i], static_cast<int>(b.fix_off[i + 1] - b.fix_off[i]),
-                              static_cast<int>(b.flt_off[i + 1] - b.flt_off[i]), b.notional[i], b.spread[i], b.fix_sign[i], b.flt_sign[i]};
-            for (int c = 0; c < tr.n_flt; ++c) {
+        host_chunk_walk(
+            b, bounds, ch,
+            [&](const TradeRef& tr, int64_t, int c) {
                 Amount pay, start;
                 float_nodes(g, tr, c, &pay, &start);
                 add(pay);
                 add(start);
-            }
-            for (int c = 0; c < tr.n_fix; ++c) add(fixed_node(g, tr, c));
-        }
+            },
+            [&](const TradeRef& tr, int64_t, int c) { add(fixed_node(g, tr, c)); });
     }
 }
 
 // out[b] of the sub-books [lo, hi) from their sums: subbook_project_kernel's expression and order.
 void host_project(const CurveTables& t, const Request& rq, const double* sums, int S, double* out, int64_t lo, int64_t hi) {
-    const int P = t.P, Kc = t.Kc;
-    const size_t stride = 1 + P + static_cast<size_t>(P) * P;
-    auto lj = [&](int k, int p) { return t.lj[(static_cast<size_t>(p / kPillarPad) * Kc + k) * kPillarPad + p % kPillarPad]; };
-    for (int64_t b = lo; b < hi; ++b) {
-        const double *rec = sums + b * S, *w = rec + 1, *D = w + Kc, *O = D + Kc;
-        double* o = out + b * stride;
-        std::fill(o, o + stride, 0.0);
-        o[0] = rec[0];
-        for (int q = 0; rq.delta && q < P; ++q) {
-            double tot = 0.0;
-            for (int wave = 0; wave < kProjWaves; ++wave) {
-                double s = 0.0;
-                for (int k = wave; k < Kc; k += kProjWaves) s = delta_step(s, w[k], lj(k, q));
-                tot = wave == 0 ? s : tot + s;
-            }
-            o[1 + q] = tot * 1e-4;
-        }
-        for (int p = 0; rq.gamma && p < P; ++p)
-            for (int q = 0; q < P; ++q) {
-                double tot = 0.0;
-                for (int wave = 0; wave < kProjWaves; ++wave) {
-                    double s = 0.0;
-                    for (int k = wave; k < Kc; k += kProjWaves) {
-                        const bool next = k + 1 < Kc;
-                        s = gamma_step(s, w[k], D[k], next ? O[k] : 0.0, lj(k, p), lj(k, q), next ? lj(k + 1, p) : 0.0,
-                                       next ? lj(k + 1, q) : 0.0, t.lc[(static_cast<size_t>(k) * P + p) * P + q]);
-                    }
-                    tot = wave == 0 ? s : tot + s;
-                }
-                o[1 + P + static_cast<size_t>(p) * P + q] = tot * 1e-8;
-            }
-    }
+    const size_t stride = 1 + t.P + static_cast<size_t>(t.P) * t.P;
+    for (int64_t b = lo; b < hi; ++b) host_project_curve(t, rq, sums + b * S, t.P, out + b * stride);
 }
 
 }  // namespace sbl
@@ -418,38 +296,19 @@ int adr_subbook_ladders_host(int interp_method, int K, int P, const double* time
     const std::string w = "adr_subbook_ladders_host";
     namespace SC = adr::scen;
     const SL::Request rq = SL::request_of(req_mask);
-    if (interp_method != ADR_INTERP_FLAT_FWD_RATES && interp_method != ADR_INTERP_LINEAR_FWD_RATES &&
-        interp_method != ADR_INTERP_LINEAR_ZERO_RATES)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and LINEAR_ZERO_RATES (4) "
-                                                      "are implemented");
-    if (n < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one trade is needed");
-    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
-    if (!out) return adr_set_error(ADR_ERR_INVALID, w + ": out is NULL");
-    if (!times || !dfs || !jac) return adr_set_error(ADR_ERR_INVALID, w + ": null curve arrays");
-    if (rq.gamma && !hess) return adr_set_error(ADR_ERR_INVALID, w + ": GAMMA requested but hess is NULL");
-    if (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign)
-        return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
+    const SL::HostCurve c{interp_method, K, P, times, dfs, jac, hess};
     const SC::HostBatch b{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, flt_weight, notional, spread,
                           fix_sign, flt_sign};
-    int rc = ADR_OK;
-    for (int64_t i = 0; rc == ADR_OK && i < n; ++i) {      // trade by trade: the first trade at fault decides the message
-        rc = SC::check_leg_offsets(w, b, i, i + 1);
-        if (rc == ADR_OK) rc = SC::check_trade_values(w, b, i, i + 1);
-    }
-    if (rc == ADR_OK) rc = SC::check_flows(w, b);
+    int rc = SL::check_host_counts(w, interp_method, n, B);
+    if (rc == ADR_OK) rc = SL::check_host_arrays(w, c, b, rq, out);
+    if (rc == ADR_OK) rc = SL::check_host_trades(w, b);
     if (rc != ADR_OK) return rc;
     std::vector<int64_t> plan;
     rc = adr::sub::build_plan(w, n, B, sub_off, plan);
     if (rc != ADR_OK) return rc;
-    {
-        std::vector<uint8_t> ratio(static_cast<size_t>(n));
-        adr::route::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, ratio.data());
-        const auto it = std::find(ratio.begin(), ratio.end(), uint8_t(1));
-        if (it != ratio.end()) return adr_set_error(ADR_ERR_UNSUPPORTED, w + SL::ratio_message(it - ratio.begin()));
-    }
     adr::CurveTables t;
-    const std::string err = adr::build_curve_tables(K, P, times, dfs, jac, rq.gamma ? hess : nullptr, t);
-    if (!err.empty()) return adr_set_error(ADR_ERR_INVALID, w + ": " + err);
+    rc = SL::host_tables(w, c, b, rq, t);
+    if (rc != ADR_OK) return rc;
     const int S = SL::record_doubles(t.Kc, rq.gamma);
     const int64_t chunks = plan[B];
     std::vector<double> work(static_cast<size_t>(chunks) * S), sums(static_cast<size_t>(B) * S);
