@@ -20,6 +20,7 @@ _LIB_PATH = os.environ.get("ADRATES_HIP_LIB") or os.path.join(os.path.dirname(os
 _lib = None
 
 REQ_VALUE, REQ_DELTA, REQ_GAMMA = 1, 2, 4
+SCHEDULE_GROUPS_AUTO, SCHEDULE_GROUPS_OFF, SCHEDULE_GROUPS_FORCE = 0, 1, 2      # adr_trades_set_schedule_groups
 ADR_ERR_UNSUPPORTED = -2     # a `LibError` raised by `_check` carries the library's code as ``status``
 MAX_PILLARS = 256            # ADR_MAX_PILLARS (uploaded curves); the device curve builder: 64
 
@@ -56,6 +57,10 @@ _SIGNATURES = {
     "adr_free_trades": (None, [_vp]),
     "adr_trades_count": (C.c_int64, [_vp]),
     "adr_trades_input_bytes": (C.c_int64, [_vp]),
+    "adr_trades_set_schedule_groups": (C.c_int, [_vp, C.c_int]),
+    "adr_trades_set_schedule_segment": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "adr_trades_schedule_groups_info": (C.c_int, [_vp, _i64p]),
+    "adr_schedule_groups_host": (C.c_int, [C.c_int64, _i64p, _i64p] + [_dp] * 11 + [_i32p, _dp, _dp, _i64p, _i64p] + [_dp] * 8),
     "adr_price": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _dp, _dp, _dp, _dp]),
     "adr_price_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "adr_allreduce_agg": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
@@ -388,6 +393,23 @@ class DeviceTrades:
     def input_bytes(self) -> int:
         return int(load().adr_trades_input_bytes(self._h))
 
+    def set_schedule_groups(self, mode: int, segment: int | None = None, blocks: int = 0) -> None:
+        """The schedule-group route of this batch (adr_trades_set_schedule_groups): ``SCHEDULE_GROUPS_AUTO`` / ``_OFF`` /
+        ``_FORCE``; ``segment``: records per wavefront of the store pass (0 = default) and ``blocks``: its persistent grid
+        (0 = one wavefront per segment) - adr_trades_set_schedule_segment.
+        Rebuilds device tables: not while a pricing call on the batch is in flight."""
+        if segment is not None:
+            _check(load().adr_trades_set_schedule_segment(self._h, int(segment), int(blocks)), "adr_trades_set_schedule_segment")
+        _check(load().adr_trades_set_schedule_groups(self._h, int(mode)), "adr_trades_set_schedule_groups")
+
+    def schedule_groups_info(self) -> dict:
+        """adr_trades_schedule_groups_info: groups of two or more trades found at upload, trades in them, whether the route
+        is active, the groups / trades it uses and the segment length."""
+        info = np.zeros(7, dtype=np.int64)
+        _check(load().adr_trades_schedule_groups_info(self._h, _ptr(info, _i64p)), "adr_trades_schedule_groups_info")
+        return {"groups": int(info[0]), "grouped": int(info[1]), "active": bool(info[2]), "used_groups": int(info[3]),
+                "used_trades": int(info[4]), "segment": int(info[5]), "blocks": int(info[6])}
+
     def close(self):
         if getattr(self, "_h", None):
             load().adr_free_trades(self._h)
@@ -404,6 +426,36 @@ class DeviceTrades:
             self.close()
         except Exception:
             pass
+
+
+def schedule_groups_host(batch):
+    """The schedule groups of ``batch`` on the host (adr_schedule_groups_host; no GPU needed).  Returns ``(group_of [n],
+    cF [n], cX [n], basis)``: ``basis`` holds the arrays of a batch of 2 G pseudo-trades (2g: the float leg of group g per
+    unit notional, 2g + 1: its fixed leg per unit of the last payment), named as a batch's attributes."""
+    n = int(batch.n_trades)
+    a = {k: _f64(getattr(batch, k)) for k in ("fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional", "spread",
+                                              "fix_sign", "flt_sign")}
+    fo, lo = np.ascontiguousarray(batch.fix_off, dtype=np.int64), np.ascontiguousarray(batch.flt_off, dtype=np.int64)
+    w = getattr(batch, "flt_weight", None)
+    w = _f64(w) if w is not None else None
+    group_of, cF, cX = np.full(n, -1, dtype=np.int32), np.zeros(n), np.zeros(n)
+    bfo, blo = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    n_fix, n_flt = len(a["fix_tp"]), len(a["flt_tp"])
+    bf = [np.zeros(n_fix) for _ in range(2)]
+    bl = [np.zeros(n_flt) for _ in range(4)]
+    b_notional, b_spread = np.zeros(n), np.zeros(n)
+    G = _check(load().adr_schedule_groups_host(
+        n, _ptr(fo, _i64p), _ptr(lo, _i64p), _ptr(a["fix_tp"]), _ptr(a["fix_pay"]), _ptr(a["flt_tp"]), _ptr(a["flt_ts"]),
+        _ptr(a["flt_te"]), _ptr(a["flt_alpha"]), _ptr(w), _ptr(a["notional"]), _ptr(a["spread"]), _ptr(a["fix_sign"]),
+        _ptr(a["flt_sign"]), _ptr(group_of, _i32p), _ptr(cF), _ptr(cX), _ptr(bfo, _i64p), _ptr(blo, _i64p), _ptr(bf[0]), _ptr(bf[1]),
+        _ptr(bl[0]), _ptr(bl[1]), _ptr(bl[2]), _ptr(bl[3]), _ptr(b_notional), _ptr(b_spread)), "adr_schedule_groups_host")
+    m = 2 * G
+    bfo, blo = bfo[:m + 1].copy(), blo[:m + 1].copy()
+    basis = dict(n_trades=m, fix_off=bfo, flt_off=blo, fix_tp=bf[0][:bfo[-1]].copy(), fix_pay=bf[1][:bfo[-1]].copy(),
+                 flt_tp=bl[0][:blo[-1]].copy(), flt_ts=bl[1][:blo[-1]].copy(), flt_te=bl[2][:blo[-1]].copy(),
+                 flt_alpha=bl[3][:blo[-1]].copy(), notional=b_notional[:m].copy(), spread=b_spread[:m].copy(),
+                 fix_sign=np.ones(m), flt_sign=np.ones(m))
+    return group_of, cF, cX, basis
 
 
 def upload_many(ctx: Context, batches):

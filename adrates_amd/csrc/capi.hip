@@ -18,6 +18,7 @@
 #include "host_pool.hpp"
 #include "kernels.hpp"
 #include "route.hpp"
+#include "schedule_groups.hpp"
 
 namespace {
 
@@ -115,6 +116,23 @@ struct adr_trades {
     // blocks.  It belongs to the BATCH (not to the ctx): two batches priced on two streams never share it.
     double* lag_scratch = nullptr;
     std::vector<void*> allocations;
+
+    // Schedule groups (schedule_groups.hpp).  The upload finds the groups and keeps them on the host;
+    // the device tables of the groups in use under `mode` are (re)built by apply_schedule_groups - at upload and when
+    // adr_trades_set_schedule_groups / _segment change a knob.  adr_price_dev only reads them.
+    struct Grouping {
+        adr::ScheduleGroups found;           // every group of at least two trades
+        std::vector<int32_t> rows_order;     // the trades of the plain row table, in table order
+        adr::CsrDev csr{};                   // the caller's arrays on the device (the ungrouped table is gathered from them)
+        int mode = ADR_SCHEDULE_GROUPS_AUTO;
+        int segment = 0;                     // records per wave of the store pass, 0: kScheduleSegment
+        int blocks = 0;                      // 0: one wave per segment, else the size of a persistent grid
+        bool active = false;
+        int64_t used_groups = 0, used_trades = 0;
+        adr::CombineDev combine{};
+        adr::TradesDev basis{}, ungrouped{}; // row tables: two pseudo-trades per group / the plain rows outside the groups
+        std::vector<void*> allocations;
+    } grouping;
 
     // The plan of the last (curve class, request) this batch was priced with: built on first use, replayed afterwards.  A
     // caller gets a reference-counted immutable plan, taken under the lock: a concurrent call with another request replaces
@@ -692,8 +710,247 @@ int adr_curve_set_download(const adr_curve_set* set, int i, double* dfs, double*
 void adr_free_trades(adr_trades* t) {
     if (!t) return;
     if (t->ctx) hipSetDevice(t->ctx->device);
+    for (void* p : t->grouping.allocations) hipFree(p);
     for (void* p : t->allocations) hipFree(p);
     delete t;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Policy of the grouped route under ADR_SCHEDULE_GROUPS_AUTO, both measured ("policy"): a group is
+// used from kScheduleMinGroup trades on (its two basis walks and their 16 KB of ladders against the walks its members no
+// longer make: on 262 144 trades in equal groups the route is 1 % slower than the direct one at 32 per group and 7 % faster
+// at 64), a batch takes the route from kScheduleMinGrouped such trades on (three more launches: slower at 16 384, faster at
+// 32 768).  FORCE: every group of two or more, whatever the batch size.
+constexpr int kScheduleMinGroup = 64;
+constexpr int64_t kScheduleMinGrouped = 32768;
+constexpr int kScheduleSegment = 16;         // records per wave of the store pass (kernels_combine.hip)
+
+// (Re)builds the device tables of the batch's schedule groups for its current knobs.  Allocates and synchronises: never
+// called from adr_price_dev, and not while a pricing call on the batch is in flight.
+hipError_t apply_schedule_groups(adr_trades* tr) {
+    adr_trades::Grouping& G = tr->grouping;
+    hipStream_t stream = tr->ctx->stream;
+    hipError_t e = hipStreamSynchronize(stream);
+    for (void* p : G.allocations) hipFree(p);
+    G.allocations.clear();
+    G.active = false;
+    G.used_groups = G.used_trades = 0;
+    G.combine = adr::CombineDev{};
+    if (e != hipSuccess) return e;
+    const adr::ScheduleGroups& F = G.found;
+    if (G.mode == ADR_SCHEDULE_GROUPS_OFF || F.n_groups == 0) return hipSuccess;
+
+    // the groups in use, renumbered in order
+    const int min_group = G.mode == ADR_SCHEDULE_GROUPS_FORCE ? 2 : kScheduleMinGroup;
+    std::vector<int32_t> new_id(static_cast<size_t>(F.n_groups), -1);
+    std::vector<int64_t> first;              // first record of every group in use, then the total
+    for (int64_t g = 0; g < F.n_groups; ++g)
+        if (F.size[static_cast<size_t>(g)] >= min_group) {
+            new_id[static_cast<size_t>(g)] = static_cast<int32_t>(G.used_groups++);
+            first.push_back(G.used_trades);
+            G.used_trades += F.size[static_cast<size_t>(g)];
+        }
+    first.push_back(G.used_trades);
+    if (G.used_groups == 0 || (G.mode == ADR_SCHEDULE_GROUPS_AUTO && G.used_trades < kScheduleMinGrouped)) {
+        G.used_groups = G.used_trades = 0;
+        return hipSuccess;
+    }
+    const size_t ng = static_cast<size_t>(G.used_groups);
+
+    // records sorted by group, in trade order inside a group; the coefficient sums in trade order
+    std::vector<adr::GroupRecord> rec(static_cast<size_t>(G.used_trades));
+    std::vector<double> sum_f(ng, 0.0), sum_x(ng, 0.0);
+    {
+        std::vector<int64_t> at(first.begin(), first.end() - 1);
+        const int64_t n = static_cast<int64_t>(F.group_of.size());
+        for (int64_t t = 0; t < n; ++t) {
+            const int32_t old = F.group_of[static_cast<size_t>(t)];
+            const int32_t g = old >= 0 ? new_id[static_cast<size_t>(old)] : -1;
+            if (g < 0) continue;
+            rec[static_cast<size_t>(at[static_cast<size_t>(g)]++)] =
+                adr::GroupRecord{static_cast<int32_t>(t), g, F.cF[static_cast<size_t>(t)], F.cX[static_cast<size_t>(t)], 0};
+            sum_f[static_cast<size_t>(g)] += F.cF[static_cast<size_t>(t)];
+            sum_x[static_cast<size_t>(g)] += F.cX[static_cast<size_t>(t)];
+        }
+    }
+    // segments: no wave straddles two groups
+    const int R = G.segment > 0 ? G.segment : kScheduleSegment;
+    std::vector<adr::GroupSegment> seg;
+    for (size_t g = 0; g < ng; ++g)
+        for (int64_t at = first[g]; at < first[g + 1]; at += R)
+            seg.push_back(adr::GroupSegment{static_cast<int32_t>(g), static_cast<int32_t>(at),
+                                            static_cast<int32_t>(std::min<int64_t>(R, first[g + 1] - at)), 0});
+    // the plain rows outside the groups in use, in the table's order
+    std::vector<int32_t> rest;
+    for (int32_t t : G.rows_order) {
+        const int32_t old = F.group_of[static_cast<size_t>(t)];
+        if (old < 0 || new_id[static_cast<size_t>(old)] < 0) rest.push_back(t);
+    }
+    // the basis trades of the groups in use: a small CSR batch of their own
+    std::vector<int64_t> b_fix_off(1, 0), b_flt_off(1, 0);
+    std::vector<double> b_fix_tp, b_fix_pay, b_flt_tp, b_flt_ts, b_flt_te, b_flt_alpha, b_notional, b_spread;
+    for (int64_t g = 0; g < F.n_groups; ++g) {
+        if (new_id[static_cast<size_t>(g)] < 0) continue;
+        for (int64_t k = 2 * g; k < 2 * g + 2; ++k) {
+            const size_t f0 = static_cast<size_t>(F.fix_off[static_cast<size_t>(k)]), f1 = static_cast<size_t>(F.fix_off[static_cast<size_t>(k) + 1]);
+            const size_t l0 = static_cast<size_t>(F.flt_off[static_cast<size_t>(k)]), l1 = static_cast<size_t>(F.flt_off[static_cast<size_t>(k) + 1]);
+            b_fix_tp.insert(b_fix_tp.end(), F.fix_tp.begin() + f0, F.fix_tp.begin() + f1);
+            b_fix_pay.insert(b_fix_pay.end(), F.fix_pay.begin() + f0, F.fix_pay.begin() + f1);
+            b_flt_tp.insert(b_flt_tp.end(), F.flt_tp.begin() + l0, F.flt_tp.begin() + l1);
+            b_flt_ts.insert(b_flt_ts.end(), F.flt_ts.begin() + l0, F.flt_ts.begin() + l1);
+            b_flt_te.insert(b_flt_te.end(), F.flt_te.begin() + l0, F.flt_te.begin() + l1);
+            b_flt_alpha.insert(b_flt_alpha.end(), F.flt_alpha.begin() + l0, F.flt_alpha.begin() + l1);
+            b_fix_off.push_back(static_cast<int64_t>(b_fix_tp.size()));
+            b_flt_off.push_back(static_cast<int64_t>(b_flt_tp.size()));
+            b_notional.push_back(F.notional[static_cast<size_t>(k)]);
+            b_spread.push_back(F.spread[static_cast<size_t>(k)]);
+        }
+    }
+    const std::vector<double> b_sign(2 * ng, 1.0);
+    std::vector<int32_t> b_rows(2 * ng);
+    for (size_t k = 0; k < 2 * ng; ++k) b_rows[k] = static_cast<int32_t>(k);
+
+    auto alloc = [&](size_t bytes) -> void* {
+        if (e != hipSuccess) return nullptr;
+        void* p = nullptr;
+        e = hipMalloc(&p, bytes + 64);       // (as the upload: the kernels' neighbour reads never leave the buffer)
+        if (e != hipSuccess) return nullptr;
+        G.allocations.push_back(p);
+        return p;
+    };
+    auto put = [&](const void* src, size_t bytes) -> void* {
+        void* p = alloc(bytes);
+        if (p && bytes && e == hipSuccess) e = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream);
+        return p;
+    };
+    auto putd = [&](const std::vector<double>& v) { return static_cast<const double*>(put(v.data(), v.size() * sizeof(double))); };
+    auto put64 = [&](const std::vector<int64_t>& v) { return static_cast<const int64_t*>(put(v.data(), v.size() * sizeof(int64_t))); };
+    auto rows_of = [&](const adr::CsrDev& csr, const std::vector<int32_t>& trades, adr::TradesDev& dst) {
+        dst = tr->dev;
+        dst.n_rows = 0;
+        if (trades.empty()) return;
+        const size_t rows = trades.size(), S = adr::kRowSlots;
+        adr::RowBuildDev rb{};
+        rb.rows = static_cast<int64_t>(rows);
+        rb.piece_trade = static_cast<const int32_t*>(put(trades.data(), rows * sizeof(int32_t)));
+        rb.row_tp = static_cast<double*>(alloc(rows * S * sizeof(double)));
+        rb.row_ts = static_cast<double*>(alloc(rows * S * sizeof(double)));
+        rb.row_alpha = static_cast<double*>(alloc(rows * S * sizeof(double)));
+        rb.row_xtp = static_cast<double*>(alloc(rows * S * sizeof(double)));
+        rb.row_xpay = static_cast<double*>(alloc(rows * S * sizeof(double)));
+        rb.row_notional = static_cast<double*>(alloc(rows * sizeof(double)));
+        rb.row_spread = static_cast<double*>(alloc(rows * sizeof(double)));
+        rb.row_meta = static_cast<int32_t*>(alloc(rows * sizeof(int32_t)));
+        rb.row_trade = static_cast<int32_t*>(alloc(rows * sizeof(int32_t)));
+        if (e == hipSuccess) e = adr::launch_build_rows(csr, rb, stream);
+        dst.n_rows = static_cast<int64_t>(rows);
+        dst.row_tp = rb.row_tp; dst.row_ts = rb.row_ts; dst.row_alpha = rb.row_alpha; dst.row_xtp = rb.row_xtp; dst.row_xpay = rb.row_xpay;
+        dst.row_notional = rb.row_notional; dst.row_spread = rb.row_spread; dst.row_meta = rb.row_meta; dst.row_trade = rb.row_trade;
+        dst.rows_chained = 0; dst.rows_lagged = 0; dst.row_te = nullptr; dst.row_w = nullptr;
+    };
+    rows_of(G.csr, rest, G.ungrouped);
+    adr::CsrDev bc{};
+    bc.n = static_cast<int64_t>(2 * ng);
+    bc.fix_off = put64(b_fix_off); bc.flt_off = put64(b_flt_off);
+    bc.fix_tp = putd(b_fix_tp); bc.fix_pay = putd(b_fix_pay);
+    bc.flt_tp = putd(b_flt_tp); bc.flt_ts = putd(b_flt_ts); bc.flt_te = putd(b_flt_te); bc.flt_alpha = putd(b_flt_alpha);
+    bc.notional = putd(b_notional); bc.spread = putd(b_spread); bc.fix_sign = putd(b_sign); bc.flt_sign = putd(b_sign);
+    rows_of(bc, b_rows, G.basis);
+    G.basis.n = bc.n;
+
+    adr::CombineDev& cd = G.combine;
+    cd.rec = static_cast<const adr::GroupRecord*>(put(rec.data(), rec.size() * sizeof(adr::GroupRecord)));
+    cd.seg = static_cast<const adr::GroupSegment*>(put(seg.data(), seg.size() * sizeof(adr::GroupSegment)));
+    cd.n_seg = static_cast<int64_t>(seg.size());
+    cd.max_blocks = G.blocks;
+    cd.n_groups = G.used_groups;
+    cd.sum_f = putd(sum_f); cd.sum_x = putd(sum_x);
+    // the basis ladders of a pricing call, for any curve of up to 32 pillars
+    constexpr size_t PM = adr::kPillarPad;
+    cd.b_pv = static_cast<double*>(alloc(2 * ng * sizeof(double)));
+    cd.b_delta = static_cast<double*>(alloc(2 * ng * PM * sizeof(double)));
+    cd.b_gamma = static_cast<double*>(alloc(2 * ng * PM * PM * sizeof(double)));
+    {
+        const hipError_t es = hipStreamSynchronize(stream);      // (also on errors: the copies read this function's vectors)
+        if (e == hipSuccess) e = es;
+    }
+    if (e != hipSuccess) {
+        for (void* p : G.allocations) hipFree(p);
+        G.allocations.clear();
+        G.combine = adr::CombineDev{};
+        G.used_groups = G.used_trades = 0;
+        return e;
+    }
+    G.active = true;
+    return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int adr_trades_set_schedule_groups(adr_trades* trades, int mode) {
+    if (!trades) return fail(ADR_ERR_INVALID, "adr_trades_set_schedule_groups: null batch");
+    if (mode != ADR_SCHEDULE_GROUPS_AUTO && mode != ADR_SCHEDULE_GROUPS_OFF && mode != ADR_SCHEDULE_GROUPS_FORCE)
+        return fail(ADR_ERR_INVALID, "adr_trades_set_schedule_groups: mode must be AUTO, OFF or FORCE");
+    ADR_HIP(hipSetDevice(trades->ctx->device));
+    trades->grouping.mode = mode;
+    ADR_HIP(apply_schedule_groups(trades));
+    return ADR_OK;
+}
+
+int adr_trades_set_schedule_segment(adr_trades* trades, int records, int blocks) {
+    if (!trades || records < 0 || blocks < 0) return fail(ADR_ERR_INVALID, "adr_trades_set_schedule_segment: null batch / negative argument");
+    ADR_HIP(hipSetDevice(trades->ctx->device));
+    trades->grouping.segment = records;
+    trades->grouping.blocks = blocks;
+    ADR_HIP(apply_schedule_groups(trades));
+    return ADR_OK;
+}
+
+int adr_trades_schedule_groups_info(const adr_trades* trades, int64_t* info) {
+    if (!trades || !info) return fail(ADR_ERR_INVALID, "adr_trades_schedule_groups_info: null argument");
+    const adr_trades::Grouping& G = trades->grouping;
+    info[0] = G.found.n_groups; info[1] = G.found.n_grouped; info[2] = G.active ? 1 : 0;
+    info[3] = G.used_groups; info[4] = G.used_trades; info[5] = G.segment > 0 ? G.segment : kScheduleSegment; info[6] = G.blocks;
+    return ADR_OK;
+}
+
+int adr_schedule_groups_host(int64_t n, const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                             const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                             const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                             const double* flt_sign, int32_t* group_of, double* cF, double* cX, int64_t* basis_fix_off,
+                             int64_t* basis_flt_off, double* basis_fix_tp, double* basis_fix_pay, double* basis_flt_tp,
+                             double* basis_flt_ts, double* basis_flt_te, double* basis_flt_alpha, double* basis_notional,
+                             double* basis_spread) {
+    if (n < 0 || (n > 0 && (!fix_off || !flt_off || !notional || !spread || !fix_sign || !flt_sign || !group_of || !cF || !cX)) ||
+        !basis_fix_off || !basis_flt_off)
+        return fail(ADR_ERR_INVALID, "adr_schedule_groups_host: bad count / null array");
+    if (n > INT32_MAX) return fail(ADR_ERR_UNSUPPORTED, "adr_schedule_groups_host: more than 2^31 trades");
+    for (int64_t t = 0; t < n; ++t)
+        if (fix_off[t + 1] < fix_off[t] || flt_off[t + 1] < flt_off[t] || fix_off[0] != 0 || flt_off[0] != 0)
+            return fail(ADR_ERR_INVALID, "adr_schedule_groups_host: offsets must start at 0 and be non-decreasing");
+    std::vector<uint8_t> lagged_of(static_cast<size_t>(n), 0);
+    R::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, lagged_of.data());
+    std::vector<int32_t> eligible;           // the rule of the plain row table (route.cpp, trade_layout)
+    for (int64_t t = 0; t < n; ++t)
+        if (!lagged_of[static_cast<size_t>(t)] && fix_off[t + 1] - fix_off[t] <= adr::kRowSlots && flt_off[t + 1] - flt_off[t] <= adr::kRowSlots)
+            eligible.push_back(static_cast<int32_t>(t));
+    const adr::CsrHost csr{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, notional, spread, fix_sign, flt_sign};
+    adr::ScheduleGroups F;
+    adr::build_schedule_groups(csr, eligible.data(), static_cast<int64_t>(eligible.size()), F);
+    std::copy(F.group_of.begin(), F.group_of.end(), group_of);
+    std::copy(F.cF.begin(), F.cF.end(), cF);
+    std::copy(F.cX.begin(), F.cX.end(), cX);
+    std::copy(F.fix_off.begin(), F.fix_off.end(), basis_fix_off);
+    std::copy(F.flt_off.begin(), F.flt_off.end(), basis_flt_off);
+    auto give = [](const std::vector<double>& v, double* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
+    give(F.fix_tp, basis_fix_tp); give(F.fix_pay, basis_fix_pay); give(F.flt_tp, basis_flt_tp); give(F.flt_ts, basis_flt_ts);
+    give(F.flt_te, basis_flt_te); give(F.flt_alpha, basis_flt_alpha); give(F.notional, basis_notional); give(F.spread, basis_spread);
+    return static_cast<int>(F.n_groups);
 }
 
 int64_t adr_trades_count(const adr_trades* t) { return t ? t->dev.n : 0; }
@@ -916,6 +1173,19 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
         if (e == hipSuccess) e = adr::launch_build_lite(csr, lb, stream);
         lt.tp_ts = lb.tp_ts; lt.al_xtp = lb.al_xtp; lt.xpay = lb.xpay; lt.te_w = lb.te_w; lt.slot = lb.slot;
     }
+    // schedule groups among the trades of the plain row table: the host search runs while the device gathers the tables above
+    // (apply_schedule_groups synchronises the stream before it builds its own)
+    if (e == hipSuccess && !L.trades[R::S_ROWS].empty()) {
+        const adr::CsrHost host{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, notional, spread, fix_sign, flt_sign};
+        adr::build_schedule_groups(host, L.trades[R::S_ROWS].data(), static_cast<int64_t>(L.trades[R::S_ROWS].size()), tr->grouping.found);
+        if (tr->grouping.found.n_groups > 0) {
+            tr->grouping.rows_order = L.trades[R::S_ROWS];
+            tr->grouping.csr = csr;
+            e = apply_schedule_groups(tr);
+        } else {
+            tr->grouping.found = adr::ScheduleGroups();
+        }
+    }
     // the copies and the table builders run on the ctx's stream: the batch is usable once they are done
     {
         const hipError_t es = hipStreamSynchronize(stream);        // (also on errors: the copies read this function's vectors)
@@ -975,6 +1245,31 @@ int adr_price_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades
             case R::F_LITE:
             case R::F_LITE_LAG: ADR_HIP(adr::launch_price_lite(curve->dev, trades->lite[L.set], o, want_delta, L.blocks, stream)); break;
             case R::F_FAST:
+                if (L.set == R::S_ROWS && want_gamma && o.gamma && agg_dev && trades->grouping.active) {
+                    // Schedule groups: the basis trades of every group into the batch's basis buffers,
+                    // the members' ladders from them in a store pass, the fast kernel for the plain rows outside the groups.
+                    // (With agg_dev only: such calls are serial on the ctx - include/adrates.h -, so nothing else is using
+                    // the batch's basis buffers.)  The grouped trades' share of the aggregate goes to block records of the
+                    // launch's range that no block wrote, slices of the groups in group order; the rest of them are zeroed.
+                    const adr_trades::Grouping& G = trades->grouping;
+                    const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(2, kLdsBudget / adr::fast_kernel_lds_bytes(curve->dev, true))));
+                    const int waves = adr::fast_kernel_threads(false) / 64, groups = adr::fast_kernel_groups();
+                    const int64_t cap = static_cast<int64_t>(ctx->n_cu) * per_cu;
+                    adr::OutputsDev ob = o;
+                    ob.pv = G.combine.b_pv; ob.delta = G.combine.b_delta; ob.gamma = G.combine.b_gamma; ob.block_partials = nullptr;
+                    ADR_HIP(adr::launch_price_fast(curve->dev, G.basis, ob, true, true,
+                                                   R::blocks_for((G.basis.n_rows + groups - 1) / groups, waves, cap), stream));
+                    ADR_HIP(adr::launch_combine(G.combine, P, o.pv, o.delta, o.gamma, stream));
+                    int prior = 0;
+                    if (G.ungrouped.n_rows > 0) {
+                        // (one record of the launch's range is kept free for the groups' share when there are two or more)
+                        prior = std::min(std::max(1, L.blocks - 1), R::blocks_for((G.ungrouped.n_rows + groups - 1) / groups, waves, cap));
+                        ADR_HIP(adr::launch_price_fast(curve->dev, G.ungrouped, o, want_delta, want_gamma, prior, stream));
+                    }
+                    ADR_HIP(adr::launch_group_aggregate(G.combine, P, o.block_partials, prior, L.blocks, stream));
+                    break;
+                }
+                [[fallthrough]];
             case R::F_FAST_CHAINED:
             case R::F_FAST_LAG:
             case R::F_FAST_LAG_CHAINED: ADR_HIP(adr::launch_price_fast(curve->dev, trades->set[L.set], o, want_delta, want_gamma, L.blocks, stream)); break;

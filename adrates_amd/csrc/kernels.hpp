@@ -298,4 +298,32 @@ hipError_t launch_knot_project(const CurveDev& cv, const double* partials, int n
 hipError_t launch_reduce_partials(const double* partials, int n_blocks, int P, bool has_gamma, double* agg,
                                   hipStream_t stream, int tile_i = 0, int tile_j = 0);
 
+// Schedule groups (schedule_groups.hpp, kernels_combine.hip): the members' ladders from their group's two basis ladders.
+struct GroupRecord {              // 32 bytes, read with scalar loads; sorted by group, trade order inside a group
+    int32_t trade, group;
+    double cF, cX;                // out[trade] = cF * BF[group] + cX * BX[group]
+    int64_t pad;
+};
+static_assert(sizeof(GroupRecord) == 32, "GroupRecord is read as 32-byte records");
+struct GroupSegment {             // the records one wave writes: all of one group
+    int32_t group, first, count, pad;
+};
+struct CombineDev {
+    const GroupRecord* rec;       // [grouped trades]
+    const GroupSegment* seg;      // [n_seg]
+    int64_t n_seg;
+    int max_blocks;               // 0: one wave per segment; else a persistent grid of at most this many blocks walks the segments
+    int64_t n_groups;
+    // the basis ladders, written by the fast kernel as the outputs of pseudo-trades 2g (float leg) and 2g + 1 (fixed leg)
+    double *b_pv, *b_delta, *b_gamma;      // [2 n_groups], [2 n_groups][P], [2 n_groups][P][P]
+    const double *sum_f, *sum_x;  // [n_groups] the members' coefficient sums, taken in trade order
+};
+// pv / delta may be null (requests without VALUE / DELTA); any P <= 32
+hipError_t launch_combine(const CombineDev& cd, int P, double* pv, double* delta, double* gamma, hipStream_t stream);
+// The grouped trades' share of the aggregate, sum_g (sum_f[g] BF[g] + sum_x[g] BX[g]), into the block-partial records
+// `slots` ([n_slots][kAggStride], the fast kernel's layout) of which a launch has written the first n_prior: slices of the
+// groups, each summed in group order, go to free records n_prior .., the free records left over are zeroed; with no free
+// record the one sum is added to record 0.
+hipError_t launch_group_aggregate(const CombineDev& cd, int P, double* slots, int n_prior, int n_slots, hipStream_t stream);
+
 }  // namespace adr

@@ -265,6 +265,55 @@ int64_t adr_trades_count(const adr_trades* trades);
 int64_t adr_trades_input_bytes(const adr_trades* trades);
 
 /*
+ * Schedule groups.  A trade's [pv, delta, gamma] is linear in its cash amounts, and everything
+ * non-linear depends on its node times only; seen from the value date, the swaps of one maturity date and roll convention
+ * share their remaining schedule.  adr_trades_upload finds, among the trades of the plain one-row table (no payment lag, no
+ * weights, at most 32 coupons per leg), the groups whose coupon counts, times, accrual fractions and spread agree bit for bit
+ * and whose fixed payments are proportional to 16 ulp of the last payment (a trade whose last payment is 0 joins only with a
+ * fixed leg of zeros; a trade that fails the test stays ungrouped).  A pricing call then prices TWO basis trades per group -
+ * the float leg per unit notional, the fixed leg per unit of its last payment - and forms the members' ladders as
+ *   out[t] = cF BF[g] + cX BX[g],   cF = flt_sign notional,   cX = fix_sign fix_pay[last]
+ * in a store pass; the plain-row trades outside the groups take the fast kernel as before.  Nothing in the grouping reads
+ * notionals, coupon levels or signs: flipping a batch's signs negates its results exactly, doubling its amounts doubles them.
+ *
+ * adr_price_dev takes this route only for requests with GAMMA and a per-trade gamma pointer AND agg_dev != NULL: the basis
+ * ladders live in buffers owned by the BATCH, and only aggregate-producing calls are serial on a ctx (stream rule 1 of
+ * adr_price_dev) - calls without agg_dev may run concurrently on one batch and keep the direct route.  Results of the two
+ * routes agree to rounding (about 1e-12 of the ladder's scale), not bit for bit.
+ *
+ * adr_trades_set_schedule_groups: AUTO (the default) uses the groups of at least 64 trades when the batch has at least 32768
+ * trades in such groups; OFF never; FORCE every group of two or more trades whatever the batch size.
+ * adr_trades_set_schedule_segment: records one wavefront of the store pass writes (0 = the default) and the size of its
+ * grid (blocks = 0, the default: one wavefront per segment; else a persistent grid of that many 4-wave blocks walks the
+ * segments) - the knobs DESIGN.md section 22 measures.  Both rebuild the
+ * batch's device tables: they allocate and synchronise, and must not run while a pricing call on the batch is in flight or
+ * between the capture and the last replay of a graph that prices it.
+ * adr_trades_schedule_groups_info: info[7] = {groups of two or more found, trades in them, route active (0 / 1), groups in
+ * use, trades in them, segment length, persistent blocks}.
+ */
+#define ADR_SCHEDULE_GROUPS_AUTO 0
+#define ADR_SCHEDULE_GROUPS_OFF 1
+#define ADR_SCHEDULE_GROUPS_FORCE 2
+int adr_trades_set_schedule_groups(adr_trades* trades, int mode);
+int adr_trades_set_schedule_segment(adr_trades* trades, int records, int blocks);
+int adr_trades_schedule_groups_info(const adr_trades* trades, int64_t* info);
+/*
+ * The grouping alone, on the host (no GPU needed), for a batch given as the arrays of adr_trades_upload_weighted:
+ * group_of[n] (-1: ungrouped; groups are numbered by their lowest trade), cF[n], cX[n] (0 for ungrouped trades) and the
+ * basis trades as a CSR batch of 2 G pseudo-trades - 2g: the float leg of group g with notional 1 at the group's spread and
+ * no fixed flows, 2g + 1: its fixed leg x^ with no float coupons and notional 0; all signs +1.  The caller sizes the basis
+ * arrays for the worst case: basis_fix_off / basis_flt_off [n + 1], basis_notional / basis_spread [n], the fixed arrays
+ * [fix_off[n]], the float arrays [flt_off[n]].  Returns G (every group of two or more trades) or a negative status.
+ */
+int adr_schedule_groups_host(int64_t n, const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                             const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                             const double* flt_weight, const double* notional, const double* spread, const double* fix_sign,
+                             const double* flt_sign, int32_t* group_of, double* cF, double* cX, int64_t* basis_fix_off,
+                             int64_t* basis_flt_off, double* basis_fix_tp, double* basis_fix_pay, double* basis_flt_tp,
+                             double* basis_flt_ts, double* basis_flt_te, double* basis_flt_alpha, double* basis_notional,
+                             double* basis_spread);
+
+/*
  * Price the batch: per-trade PV [n], delta ladder [n*P] and gamma [n*P*P]
  * (row-major, full symmetric matrix), units as the reference: delta per 1 bp
  * (x1e-4), gamma per bp^2 (x1e-8).  Any output may be NULL; req_mask says what
@@ -295,6 +344,9 @@ int adr_price(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades,
  * (2) A batch that holds payment-lag or weighted coupons owns a per-wave scratch used by GAMMA requests:
  * calls with GAMMA on the SAME adr_trades must be stream-ordered.  Everything else - different batches on
  * different streams, calls without agg_dev - may run concurrently on one ctx.
+ * (3) A batch with active schedule groups (adr_trades_set_schedule_groups) prices through per-batch basis buffers, but
+ * only in calls with GAMMA, a per-trade gamma pointer and agg_dev != NULL - calls rule (1) already serialises; every other
+ * call takes the direct route and stays free to run concurrently.
  */
 int adr_price_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades,
                   uint32_t req_mask,

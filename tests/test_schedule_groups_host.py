@@ -1,0 +1,121 @@
+"""Schedule groups on the CPU (adr_schedule_groups_host): which trades share a group, what splits a
+group, and that the basis trades, priced by the C oracle and recombined with the members' coefficients, give the oracle's
+per-trade ladders (no GPU)."""
+import copy
+
+import numpy as np
+import pytest
+
+from adrates_amd import _native
+from adrates_amd.market.position.scenarios import _concat_batches
+from adrates_amd.trades import synthetic
+from oracle import port
+
+from . import _schedule_group_cases as S
+from ._parity import REL_TOL, assert_batch_parity
+
+
+def groups_of(batch):
+    return _native.schedule_groups_host(batch)
+
+
+def test_offgrid_book_is_360_groups():
+    batch = synthetic.synthesize(S.VD, 50_000, kind="offgrid")
+    group_of, cF, cX, basis = groups_of(batch)
+    assert basis["n_trades"] == 2 * 360 and group_of.min() == 0 and group_of.max() == 359
+    sizes = np.bincount(group_of)
+    assert sizes.min() >= 2 and sizes.sum() == 50_000
+    # groups are numbered by their lowest trade
+    first = np.array([np.flatnonzero(group_of == g)[0] for g in range(360)])
+    assert np.all(np.diff(first) > 0)
+    # the coefficients: signed notional and signed last payment
+    last = batch.fix_pay[batch.fix_off[1:] - 1]
+    assert np.array_equal(cF, batch.flt_sign * batch.notional) and np.array_equal(cX, batch.fix_sign * last)
+    # the basis trades: float leg at notional 1, fixed leg ending in 1
+    assert np.all(basis["notional"][0::2] == 1.0) and np.all(basis["notional"][1::2] == 0.0)
+    assert np.all(np.diff(basis["flt_off"])[1::2] == 0) and np.all(np.diff(basis["fix_off"])[0::2] == 0)
+    assert np.all(basis["fix_pay"][basis["fix_off"][2::2] - 1] == 1.0)
+
+
+def test_grouping_ignores_amounts_and_signs():
+    batch, _ = S.edge_book(filler=500)
+    g0, cF, cX, basis = groups_of(batch)
+    g2, cF2, cX2, basis2 = groups_of(S.doubled(batch))
+    g3, cF3, cX3, basis3 = groups_of(S.flipped(batch))
+    assert np.array_equal(g0, g2) and np.array_equal(g0, g3)
+    assert np.array_equal(cF2, 2.0 * cF) and np.array_equal(cX2, 2.0 * cX)
+    assert np.array_equal(cF3, -cF) and np.array_equal(cX3, -cX)
+    for k in basis:                      # the basis trades are the same bits
+        assert np.array_equal(basis[k], basis2[k]) and np.array_equal(basis[k], basis3[k]), k
+
+
+def test_edge_book_groups():
+    batch, marks = S.edge_book(filler=0)
+    group_of, cF, cX, _ = groups_of(batch)
+
+    def ids(name):
+        lo, hi = marks[name]
+        return group_of[lo:hi]
+
+    assert ids("size1")[0] == -1                                         # alone on its schedule
+    for size in (2, 3, S.R - 1, S.R, S.R + 1, 2 * S.R + 1):
+        g = ids(f"size{size}")
+        assert g[0] >= 0 and np.all(g == g[0]) and np.sum(group_of == g[0]) == size
+    for m in (1, 2, 30, 32):
+        g = ids(f"coupons{m}")
+        assert g[0] >= 0 and np.all(g == g[0])
+    assert np.all(ids("coupons33") == -1)                                # 33 coupons: a chained trade
+    assert np.all(ids("semi") == ids("semi")[0]) and ids("semi")[0] >= 0
+    a, b = ids("spread"), ids("spread_other")
+    assert np.all(a == a[0]) and np.all(b == b[0]) and a[0] >= 0 and b[0] >= 0 and a[0] != b[0]
+    g = ids("mixed")
+    assert g[3] == -1 and g[4] == -1                                     # last payment alone zero; one payment 1 % off
+    assert g[0] >= 0 and g[0] == g[1] == g[2] == g[5]                    # the zero-coupon member joins
+    lo = marks["mixed"][0]
+    assert cX[lo + 2] == 0.0 and cF[lo + 2] != 0.0
+    g = ids("zero_first")
+    assert g[0] >= 0 and np.all(g == g[0]) and cX[marks["zero_first"][0]] == 0.0
+
+
+@pytest.mark.parametrize("what", ["payment", "spread", "time"])
+def test_a_different_trade_leaves_its_group(what):
+    batch = _concat_batches(S.group(5, 8.3, 9, 9, seed=1))
+    base, *_ = groups_of(batch)
+    assert np.all(base == 0)
+    odd = copy.deepcopy(batch)
+    if what == "payment":
+        odd.fix_pay = odd.fix_pay.copy()
+        odd.fix_pay[odd.fix_off[2] + 4] *= 1.01
+    elif what == "spread":
+        odd.spread = odd.spread.copy()
+        odd.spread[2] = 0.001
+    else:
+        odd.flt_ts = odd.flt_ts.copy()
+        odd.flt_ts[odd.flt_off[2] + 3] = np.nextafter(odd.flt_ts[odd.flt_off[2] + 3], np.inf)
+    got, *_ = groups_of(odd)
+    assert got[2] == -1 and np.all(np.delete(got, 2) == 0)
+
+
+def test_lagged_and_weighted_trades_are_never_grouped():
+    batch = _concat_batches(S.group(4, 8.3, 9, 9, seed=2))
+    lag = copy.deepcopy(batch)
+    lag.flt_tp = lag.flt_tp + 2.0 / 365.0                                # paid two days after the accrual end
+    assert np.all(groups_of(lag)[0] == -1)
+    w = copy.deepcopy(batch)
+    w.flt_weight = np.full(w.flt_tp.shape, 0.5)
+    assert np.all(groups_of(w)[0] == -1)
+
+
+@pytest.mark.parametrize("interp", S.SCHEMES)
+def test_recombined_basis_ladders_match_the_oracle(interp):
+    host = S.curve_arrays(interp)
+    edge, _ = S.edge_book(filler=0)
+    batch = _concat_batches([edge, synthetic.synthesize(S.VD, 4000, kind="offgrid", seed=5)])
+    group_of, cF, cX, basis = groups_of(batch)
+    used = group_of >= 0
+    assert used.sum() > 4000
+    ref = port.price(interp.value, host.times, host.dfs, host.jac, host.hess, batch)
+    got = S.recombined(interp.value, host, group_of, cF, cX, basis)
+    worst = assert_batch_parity({k: v[used] for k, v in got.items()}, {k: ref[k][used] for k in ("pv", "delta", "gamma")},
+                                batch.notional[used], tol=REL_TOL)
+    print(f"recombined basis ladders vs oracle, {interp.name}: {worst:.2e}")
