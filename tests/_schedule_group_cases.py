@@ -80,6 +80,49 @@ def edge_book(filler=3000):
     return book, marks
 
 
+def auto_book():
+    """A batch that takes the route under AUTO with only some of its groups in use: 34 000 ongrid trades on 30 schedules
+    (the groups of 64 trades and more), 3 000 offgrid trades on some 340 schedules (groups below 64, a few trades falling
+    into the large ones) and the edge book.  The large groups' numbers lie scattered among the small ones', so a group's
+    number among all groups and among those in use differ almost everywhere.  Returns ``(batch, marks)``, the marks those
+    of `edge_book` moved to their place in this batch."""
+    edge, marks = edge_book(filler=0)
+    head = [synthetic.synthesize(VD, 3000, kind="offgrid", seed=9), synthetic.synthesize(VD, 34000, kind="ongrid", seed=11)]
+    at = sum(b.n_trades for b in head)
+    return _concat_batches(head + [edge]), {k: (lo + at, hi + at) for k, (lo, hi) in marks.items()}
+
+
+def all_grouped_book():
+    """40 schedules of 3 trades each and nothing else: under FORCE no plain row is left outside the groups."""
+    return _concat_batches([t for k in range(40) for t in group(3, 5.37 + 0.5 * k, 5 + k % 7, 5 + k % 7, seed=400 + k)])
+
+
+def tiny_books():
+    """Batches of one or two blocks of the fast row launch (24 rows per block), by name: ``one_block_one_outside`` - 4
+    trades of one schedule and one of another; ``one_block_all_grouped`` - 3 trades of one schedule; ``two_blocks`` - 2
+    trades of one schedule and 46 on a schedule of their own each."""
+    singles = [group(1, 3.21 + 0.53 * k, 3 + k % 9, 3 + k % 9, seed=600 + k)[0] for k in range(46)]
+    return {"one_block_one_outside": _concat_batches(group(4, 6.37, 6, 6, seed=500) + group(1, 4.61, 5, 5, seed=501)),
+            "one_block_all_grouped": _concat_batches(group(3, 7.37, 7, 7, seed=502)),
+            "two_blocks": _concat_batches(group(2, 9.37, 9, 9, seed=503) + singles)}
+
+
+def many_groups_book(groups=4100):
+    """``groups`` groups of 2 on one schedule, told apart by their spreads."""
+    return _concat_batches([t for k in range(groups) for t in group(2, 8.37, 8, 8, seed=k, spread=1e-7 * k)])
+
+
+def no_group_book():
+    """5 trades on 5 schedules: nothing to group."""
+    return _concat_batches([group(1, 4.4 + k, 4 + k, 4 + k, seed=700 + k)[0] for k in range(5)])
+
+
+def short_curve_quotes(P):
+    """The README quotes at 1Y, 2Y, ..., 8Y (``P`` = 8) or 9Y (``P`` = 9): ``(px, tenors)``."""
+    idx = [14] + list(range(16, 15 + P))
+    return [F.GBP_PX[i] for i in idx], [F.TENORS[i] for i in idx]
+
+
 def flipped(b):
     out = copy.deepcopy(b)
     out.fix_sign, out.flt_sign = -b.fix_sign, -b.flt_sign

@@ -96,6 +96,69 @@ def test_a_different_trade_leaves_its_group(what):
     assert got[2] == -1 and np.all(np.delete(got, 2) == 0)
 
 
+def off_shape(batch, trade, k):
+    """``batch`` with ``k`` ulp of ``trade``'s last payment added to its coupon 4."""
+    odd = copy.deepcopy(batch)
+    odd.fix_pay = odd.fix_pay.copy()
+    last = odd.fix_pay[odd.fix_off[trade + 1] - 1]
+    odd.fix_pay[odd.fix_off[trade] + 4] += k * np.spacing(abs(last))
+    return odd
+
+
+def test_shape_tolerance_is_about_16_ulp_of_the_last_payment():
+    """8 ulp off the group's shape joins, 32 ulp leaves (the edge itself, 16 / 17 here, hangs on one rounding of
+    ``last * x^``)."""
+    batch = _concat_batches(S.group(5, 8.3, 9, 9, seed=1))
+    assert np.all(groups_of(off_shape(batch, 2, 8))[0] == 0)
+    got, *_ = groups_of(off_shape(batch, 2, 32))
+    assert got[2] == -1 and np.all(np.delete(got, 2) == 0)
+
+
+@pytest.mark.parametrize("k", [8, 16])
+def test_a_member_at_the_shape_tolerance_recombines_to_the_oracle(k):
+    """What the tolerance costs: the ladders of a trade ``k`` ulp off its group's shape, recombined from the group's basis
+    with the trade's own coefficients (whether or not the search keeps it at the edge), against the oracle's."""
+    batch = off_shape(_concat_batches(S.group(5, 8.3, 9, 9, seed=1)), 2, k)
+    group_of, _, _, basis = groups_of(batch)
+    assert basis["n_trades"] == 2 and np.all(np.delete(group_of, 2) == 0)
+    cF, cX = batch.flt_sign * batch.notional, batch.fix_sign * batch.fix_pay[batch.fix_off[1:] - 1]
+    worst = 0.0
+    for interp in S.SCHEMES:
+        host = S.curve_arrays(interp)
+        ref = port.price(interp.value, host.times, host.dfs, host.jac, host.hess, batch)
+        got = S.recombined(interp.value, host, np.zeros(5, dtype=np.int32), cF, cX, basis)
+        worst = max(worst, assert_batch_parity({key: v[2:3] for key, v in got.items()}, {key: ref[key][2:3] for key in got},
+                                               batch.notional[2:3], tol=REL_TOL))
+        moved = max(float(np.max(np.abs(got[key][2] - ref[key][2]))) for key in ("pv", "delta", "gamma")) / batch.notional[2]
+        print(f"{k} ulp off the shape, {interp.name}: parity {worst:.2e}, largest move {moved:.2e} of notional")
+
+
+def test_a_key_whose_lowest_trade_is_the_odd_one_out_is_not_grouped():
+    """The key's lowest trade sets the shape: when it is the one trade off the others' shape, no
+    second trade is proportional to it and the key gives no group at all."""
+    batch = _concat_batches(S.group(5, 8.3, 9, 9, seed=1))
+    odd = copy.deepcopy(batch)
+    odd.fix_pay = odd.fix_pay.copy()
+    odd.fix_pay[odd.fix_off[0] + 4] *= 1.01
+    group_of, _, _, basis = groups_of(odd)
+    assert np.all(group_of == -1) and basis["n_trades"] == 0
+
+
+def test_auto_book_reaches_auto_with_some_groups_unused():
+    """What tests/test_gpu_schedule_groups.py needs of `auto_book`: enough trades in groups of 64 and more for AUTO, many
+    smaller groups, and the large groups' numbers scattered among theirs."""
+    batch, marks = S.auto_book()
+    group_of, *_ = groups_of(batch)
+    sizes = np.bincount(group_of[group_of >= 0])
+    large = np.flatnonzero(sizes >= 64)
+    assert len(large) == 30 and sizes[large].sum() > 32768
+    assert np.sum(sizes < 64) > 300 and sizes.min() >= 2
+    assert large[0] > 0 and np.any(np.diff(large) > 1)                   # old and new numbers differ from the first one on
+    assert 0 < np.sum(group_of < 0) < 100
+    lo, hi = marks["coupons33"]
+    assert np.all(group_of[lo:hi] == -1)
+
+
 def test_lagged_and_weighted_trades_are_never_grouped():
     batch = _concat_batches(S.group(4, 8.3, 9, 9, seed=2))
     lag = copy.deepcopy(batch)
