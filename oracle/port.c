@@ -170,7 +170,24 @@ static double price_one(const curve_t* c, work_t* w, int mf, const double* ftp, 
         interpolate(c, ltp[j], &X[2]);
         X[3] = V;
         const double C = X[2].v, Vv = V.v, R = C / Vv;
-        if (al > 0.0) {
+        if (al > 0.0 && lte[j] == ltp[j]) {
+            /* paid on the accrual end: B and C are the same number, so (A / B - 1 + spread al) C = A + (spread al - 1) C,
+             * linear in A and C.  The general form below is the same function, but its second partials in B and C cancel
+             * only up to rounding (2 n A / B^3 C against 2 n A / B^2), which costs two digits of gamma. */
+            df_t Y[3];
+            interpolate(c, lts[j], &Y[0]);
+            Y[1] = X[2];
+            Y[2] = V;
+            const double A = Y[0].v, n = sl * N * (lw ? lw[j] : 1.0), m1 = n * (spread * al - 1.0);
+            const double num = n * A + m1 * C;
+            pv += num / Vv;
+            const double fX[3] = {n / Vv, m1 / Vv, -num / (Vv * Vv)};
+            double fXY[9] = {0};
+            fXY[0 * 3 + 2] = fXY[2 * 3 + 0] = -n / (Vv * Vv);
+            fXY[1 * 3 + 2] = fXY[2 * 3 + 1] = -m1 / (Vv * Vv);
+            fXY[2 * 3 + 2] = 2.0 * num / (Vv * Vv * Vv);
+            add_term(w, 3, Y, fX, fXY);
+        } else if (al > 0.0) {
             interpolate(c, lts[j], &X[0]);
             interpolate(c, lte[j], &X[1]);
             const double A = X[0].v, B = X[1].v, n = sl * N * (lw ? lw[j] : 1.0);

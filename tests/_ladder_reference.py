@@ -1,0 +1,459 @@
+"""The plain reference of the sub-book ladders (adr_subbook_ladders*, adr_credit_subbook_ladders*) and the bound the kernels,
+their host twins and the C oracle are held to, entry by entry (tests/test_ladder_edges_host.py, CPU, and
+tests/test_gpu_ladder_edges.py, GPU).  It shares no code with the kernels or with oracle/port.c.
+
+The operation.  The inputs are what `DeviceCurve` and the `_host` entries take, each an exact binary number: the scheme,
+the knot times x_k, the knot discount factors d_k, ``jac [K, P]`` = J, ``hess [K, P, P]`` = C, a `TradeBatch`, ``sub_off`` and,
+for credit, ``z``, ``bucket``, the spread times and ``G``.  A desk's PV is a sum of TERMS c D(t), one per cash flow and NOT
+folded into nodes (oracle/mp_oracle.py's value level):
+  fixed flow, counts when tp > 0:            c = fix_sign fix_pay at tp
+  float coupon, counts when tp >= 0:         N sign ((D(ts) / D(te) - 1 when alpha > 0) + spread alpha) D(tp); the ladders take
+                                             accruing coupons with te == tp only, so D(ts) / D(te) D(tp) = D(ts) and the coupon
+                                             is  +sn at ts,  -sn at tp  (both only when alpha > 0)  and  sn spread alpha at tp.
+Credit multiplies every term of a flow by f = exp(-z tau) of that flow.  D(t) is simple_interp.hpp's lookup rule, its float64
+decisions (snap within 1e-10 to the first of equal knots, else the segment and weight of t + 1e-12, clamped at the ends)
+taken from `oracle.mp_oracle._lookup_plan`; with L_k = ln d_k
+  FLAT_FWD_RATES     ln D = (1 - w) L_a + w L_b                            (a knot alone: L_k)
+  LINEAR_ZERO_RATES  ln D = t (1 - w) / max(x_a, 1e-15) L_a + t w / x_b L_b  (a knot held at an end: t / max(x_k, 1e-15) L_k)
+  LINEAR_FWD_RATES   D = (1 - w) d_a + w d_b.
+Everything that depends on d runs in mpmath at 60 digits.  The derivatives are analytic in the L_k: g_k = dPV/dL_k and the
+banded H_kl = d2PV/dL_k dL_l, then with LJ = J / d and LC_k = C_k / d_k - J_k J_k^T / d_k^2
+  delta = 1e-4 LJ^T g,      gamma = 1e-8 (LJ^T H LJ + sum_k g_k LC_k),
+and for credit cs01 = 1e-4 dPV/dz, spread_gamma = 1e-8 d2PV/dz2, cross = 1e-4 d delta/dz per (desk, bucket) cell, from the
+terms' amounts times -tau and tau^2.  The projection is done in exact integer arithmetic: g_k / d_k, g_k / d_k^2 and
+H_kl / (d_k d_l) are formed in mpmath and taken apart into integer mantissas on one exponent without any rounding, J and C
+are exact integers times a power of two, and the sums are Python integers (object arrays).  1e-4 and 1e-8 stay exact: a
+result is an integer V with value = V 2^E / 10^s.
+
+Gross.  Every element comes with ``gross``: the sum of the absolute values of its terms written in the inputs - |c| f D(t)
+through the absolute interpolation weights, and the tables as |J| / d, |C| / d and |J J^T| / d^2 separately, so the
+subtraction inside LC counts as cancellation against gross.  It is computed by the same exact integer arithmetic on the
+absolute values.  An element with gross == 0 must be +0.0.
+
+The bound |got - value| <= k 2^-53 gross, k = `bound_k`.  Each rounding below is counted as ONE unit 2^-53 of the absolute
+sum it acts on (twice the unit roundoff 2^-54, which pays for every second-order term), a library function with a documented
+error of one ulp as TWO units (an ulp is at most 2^-52 of the value).  As the code performs them
+(subbook_ladder_common.hpp, simple_interp.hpp, curve_tables.cpp):
+  amount    sn (spread alpha - 1): 3 roundings; the next coupon's start and the fixed flow joined: 2 more            5
+  weight    e_w roundings of a lookup weight formed from w (w itself is the plan's float64 number, the same expression
+            in the code): FLAT_FWD 1 - w: 1;  LINEAR_ZERO t (1 - w) / x_a: 3;  LINEAR_FWD 1 - w: 1
+  argument  (log schemes) s = wa L_a + wb L_b: L = log(d) from the table builder (2), the weight (e_w), a product (1), the
+            sum (1), all relative to |wa L_a| + |wb L_b| <= cond, and an absolute error of s is a relative one of exp(s):
+                                                                                                     cond (e_w + 4)
+            (LINEAR_FWD) exp(L_k) on L_k = log(d_k): the table's log (2) conditioned by |L_k| <= cond:      2 cond
+  exp       the device's and the host's exp, documented at one ulp or better                                          2
+  products  (log schemes) amount exp(s): 1; om wa, (om wa) wa or (om wa) wb: 2, each with the weight's error again: 2 e_w
+                                                                                                        1 + 2 + 2 e_w
+            (LINEAR_FWD) 1 - w (e_w), amount (1 - w), the product with exp(L)                                 e_w + 2
+  credit    f = exp(-(z tau)): the product conditioned by |z tau| <= zt, exp (2); x f (1); (-tau) xf (1) or
+            tau (tau xf) (2)                                                                                   zt + 5
+  sums      a knot's slot and the pv take the desk's nodes one after another inside a chunk, the chunk records go to 64
+            slots and down a halving tree of 6 levels: any order of n numbers costs n - 1 roundings, the nodes number at
+            most the desk's unfolded terms n_terms                                                        n_terms + 7
+            credit sums chunks to cells and cells to desks: the second reduction                                   + 7
+  tables    LJ = J / d: 1;  LC = C / d - LJ LJ: C / d (1), LJ LJ (2 + 1), the difference (1): at most 4 against
+            |C| / d + |J J| / d^2
+  project   the worst of the three terms of `gamma_step`: (D_k LJ) LJ: 2 (tables) + 2;  O_k (LJ LJ + LJ LJ): 2 + 1 + 1 + 1;
+            w_k LC: 4 + 1                                                                                            5
+            the adds: three per knot, a wave takes every eighth knot, then eight partial sums in order
+                                                                                              3 ceil(Kc / 8) + 7
+  scale     the constant 1e-4 or 1e-8 is not a binary number (1), the product (1)                                   2
+Kc is the compact grid's length, read off the knot times: the first and the last knot of every run of equal times
+(`compact_count`).  `bound_k` adds these and rounds the two conditioned terms up to an integer; the
+same k is used for every element of a desk (pv and delta have fewer roundings than gamma).  cond and zt are read off the
+inputs by the reference: the largest sum of |weight L_k| over the desk's terms and the largest |z tau|.
+"""
+import math
+
+import numpy as np
+from mpmath import mp, mpf
+
+from oracle.mp_oracle import _lookup_plan
+
+FLAT_FWD, LINEAR_FWD, LINEAR_ZERO = 1, 2, 4
+_WEIGHT_ROUNDINGS = {FLAT_FWD: 1, LINEAR_FWD: 1, LINEAR_ZERO: 3}
+
+
+def compact_count(times):
+    """Kc: the knots that are the first or the last of a run of equal times."""
+    x = np.asarray(times, dtype=np.float64)
+    first = np.concatenate([[True], x[1:] != x[:-1]])
+    last = np.concatenate([x[1:] != x[:-1], [True]])
+    return int(np.count_nonzero(first | last))
+
+
+def bound_k(method, n_terms, K, cond, zt=None):
+    """k of the module docstring: ``n_terms`` unfolded live terms of the desk, ``K`` = Kc knots, ``cond`` the largest
+    sum |weight L_k| of a term, ``zt`` the largest |z tau| (credit; None for the rates ladders)."""
+    e_w = _WEIGHT_ROUNDINGS[int(method)]
+    amount, exp_ulp, tables_project, scale = 5, 2, 5, 2
+    if int(method) == LINEAR_FWD:
+        node = amount + math.ceil(2 * cond) + exp_ulp + (e_w + 2)
+    else:
+        node = amount + math.ceil(cond * (e_w + 4)) + exp_ulp + (1 + 2 + 2 * e_w)
+    sums = n_terms + 7
+    if zt is not None:
+        node += math.ceil(zt) + 5
+        sums += 7
+    return node + sums + tables_project + 3 * ((K + 7) // 8) + 7 + scale
+
+
+# ------------------------------------------------------------------------------------------------ exact integer helpers
+def _mp(x):
+    return mpf(float(x))
+
+
+def _float_ints(a):
+    """``(ints, e)``: the float64 array as Python integers with ``a == ints * 2 ** e`` exactly."""
+    a = np.asarray(a, dtype=np.float64)
+    m, ex = np.frexp(a)
+    nz = a != 0.0
+    lo = (int(ex[nz].min()) if np.any(nz) else 0) - 53
+    m = (m * 2.0 ** 53).astype(np.int64)
+    out = np.array([int(mm) << (int(ee) - 53 - lo) if mm else 0 for mm, ee in zip(m.ravel(), ex.ravel())], dtype=object)
+    return out.reshape(a.shape), lo
+
+
+def _mp_ints(values):
+    """``(ints [n], e)``: mpf numbers as integers on one exponent, exactly (an mpf is mantissa * 2 ** exponent)."""
+    parts = []
+    for v in values:
+        sign, man, ex, _ = mpf(v)._mpf_
+        parts.append((-int(man) if sign else int(man), int(ex)))
+    live = [ex for man, ex in parts if man]
+    lo = min(live) if live else 0
+    return np.array([man << (ex - lo) if man else 0 for man, ex in parts], dtype=object), lo
+
+
+def _align(pieces):
+    """The sum of ``(ints, e)`` pieces on their lowest exponent."""
+    lo = min(e for _, e in pieces)
+    total = 0
+    for ints, e in pieces:
+        total = total + ints * (1 << (e - lo))
+    return total, lo
+
+
+class Block:
+    """Elements ``value = V 2^E / 10^s`` and ``gross = A 2^E / 10^s`` (``V``, ``A``: object arrays of Python integers)."""
+
+    def __init__(self, V, A, E, s):
+        self.V, self.A, self.E, self.s = np.asarray(V, dtype=object), np.asarray(A, dtype=object), E, s
+
+    @staticmethod
+    def of(value_piece, gross_piece, s):
+        (v, ev), (a, ea) = value_piece, gross_piece
+        lo = min(ev, ea)
+        return Block(v * (1 << (ev - lo)), a * (1 << (ea - lo)), lo, s)
+
+    def floats(self):
+        """The values rounded to float64 (for reading and for comparisons that need no exactness)."""
+        f = np.vectorize(lambda v: float(mpf(int(v)) * mpf(2) ** self.E / mpf(10) ** self.s), otypes=[np.float64])
+        return f(self.V)
+
+    def gross_floats(self):
+        f = np.vectorize(lambda v: float(mpf(int(v)) * mpf(2) ** self.E / mpf(10) ** self.s), otypes=[np.float64])
+        return f(self.A)
+
+    def share(self, got, k, what=""):
+        """The worst |got - value| / (k 2^-53 gross) over the elements, in exact integer arithmetic up to the final
+        quotient; asserts that an element with gross == 0 is +0.0."""
+        got = np.asarray(got, dtype=np.float64)
+        assert got.shape == self.V.shape, (what, got.shape, self.V.shape)
+        assert np.all(np.isfinite(got)), f"{what}: not finite"
+        m, ex = np.frexp(got)
+        m = (m * 2.0 ** 53).astype(np.int64)
+        worst = 0.0
+        ten = 10 ** self.s
+        for idx in np.ndindex(got.shape):
+            V, A = int(self.V[idx]), int(self.A[idx])
+            if A == 0:
+                assert got[idx] == 0.0 and not np.signbit(got[idx]), f"{what}{list(idx)}: gross is 0 but the entry is {got[idx]!r}"
+                continue
+            sh = int(ex[idx]) - 53 - self.E                 # got 10^s / 2^E = m ten 2^sh
+            g = int(m[idx]) * ten
+            if sh >= 0:
+                err, scale = abs((g << sh) - V), A
+            else:
+                err, scale = abs(g - (V << -sh)), A << -sh
+            worst = max(worst, ((err << 83) // (k * scale)) / 2.0 ** 30)      # err 2^53 / (k gross), 30 binary digits kept
+        return worst
+
+
+    def between(self, a, b, k):
+        """The worst |a - b| / (k 2^-53 gross) of two results, exactly; where gross is 0 both must be +0.0 (`share` says so
+        of each)."""
+        from fractions import Fraction
+        a, b = np.asarray(a, dtype=np.float64).reshape(self.V.shape), np.asarray(b, dtype=np.float64).reshape(self.V.shape)
+        unit = Fraction(k, 2 ** 53) * Fraction(2) ** self.E / 10 ** self.s
+        worst = 0.0
+        for idx in np.ndindex(a.shape):
+            if a[idx] != b[idx]:
+                assert int(self.A[idx]) != 0, idx
+                worst = max(worst, float(abs(Fraction(float(a[idx])) - Fraction(float(b[idx]))) / (unit * int(self.A[idx]))))
+        return worst
+
+
+# ------------------------------------------------------------------------------------------------------------ the curve
+class _Curve:
+    def __init__(self, method, times, dfs, jac, hess):
+        self.method = int(method)
+        self.x = np.ascontiguousarray(times, dtype=np.float64)
+        self.K = self.x.size
+        self.d = [_mp(v) for v in np.asarray(dfs, dtype=np.float64)]
+        self.L = [mp.log(v) for v in self.d]
+        self.J = np.ascontiguousarray(jac, dtype=np.float64).reshape(self.K, -1)
+        self.P = self.J.shape[1]
+        self.C = None if hess is None else np.ascontiguousarray(hess, dtype=np.float64).reshape(self.K, self.P, self.P)
+        self._dates = {}
+
+    def date(self, t):
+        """``(D, [(k, weight)], pieces)`` of one date: log schemes D = exp(sum weight L_k) and ``pieces`` is None;
+        LINEAR_FWD_RATES D = sum of the pieces ``(k, share d_k)``.  ``cond``: sum |weight L_k| (LINEAR_FWD: max |L_k|)."""
+        t = float(t)
+        if t in self._dates:
+            return self._dates[t]
+        plan = _lookup_plan(self.x, t, self.method)
+        x, m = self.x, self.method
+        if plan[0] == "snap":
+            knots = [(plan[1], mpf(1))]
+        elif plan[0] == "flat":
+            k = plan[1]
+            knots = [(k, _mp(t) / _mp(max(float(x[k]), 1e-15)) if m == LINEAR_ZERO else mpf(1))]
+        else:
+            _, a, b, w = plan
+            w = _mp(w)
+            if m == LINEAR_ZERO:
+                knots = [(a, _mp(t) * (1 - w) / _mp(max(float(x[a]), 1e-15))), (b, _mp(t) * w / _mp(max(float(x[b]), 1e-15)))]
+            else:
+                knots = [(a, 1 - w), (b, w)]
+            knots = [(k, wk) for k, wk in knots if wk != 0]
+        if m == LINEAR_FWD:
+            pieces = [(k, wk * self.d[k]) for k, wk in knots]
+            out = (sum((p for _, p in pieces), mpf(0)), knots, pieces, max(abs(self.L[k]) for k, _ in knots))
+        else:
+            s = sum((wk * self.L[k] for k, wk in knots), mpf(0))
+            out = (mp.exp(s), knots, None, sum((abs(wk * self.L[k]) for k, wk in knots), mpf(0)))
+        self._dates[t] = out
+        return out
+
+
+class _Sums:
+    """pv, g_k and H_kl of a set of terms, and the same of their absolute values."""
+
+    def __init__(self, curve, second):
+        self.cv, self.second = curve, second
+        self.pv, self.pv_abs = mpf(0), mpf(0)
+        self.g, self.g_abs, self.H, self.H_abs = {}, {}, {}, {}
+        self.n, self.cond = 0, mpf(0)
+
+    def add(self, t, c):
+        if c == 0:
+            return
+        D, knots, pieces, cond = self.cv.date(t)
+        self.n += 1
+        self.cond = max(self.cond, cond)
+        bump = lambda table, key, v: table.__setitem__(key, table.get(key, mpf(0)) + v)
+        if pieces is not None:                              # LINEAR_FWD_RATES: two single-knot amounts, weight 1
+            for k, p in pieces:
+                v = c * p
+                self.pv += v
+                self.pv_abs += abs(v)
+                bump(self.g, k, v)
+                bump(self.g_abs, k, abs(v))
+                if self.second:
+                    bump(self.H, (k, k), v)
+                    bump(self.H_abs, (k, k), abs(v))
+            return
+        om = c * D
+        self.pv += om
+        self.pv_abs += abs(om)
+        for k, wk in knots:
+            bump(self.g, k, om * wk)
+            bump(self.g_abs, k, abs(om * wk))
+            if self.second:
+                for l, wl in knots:
+                    bump(self.H, (k, l), om * wk * wl)
+                    bump(self.H_abs, (k, l), abs(om * wk * wl))
+
+    # -------------------------------------------------------------------------------------------------- projection
+    def _project(self, g, H, J, C, sign, second):
+        """``(delta piece, gamma piece or None)`` as ``(ints, e)`` before the powers of ten."""
+        cv = self.cv
+        ks = sorted(g)
+        P = cv.P
+        if not ks:
+            zero = np.array([0] * P, dtype=object)
+            return (zero, 0), ((np.array([0] * (P * P), dtype=object).reshape(P, P), 0) if second else None)
+        Jk, eJ = J
+        Jk = Jk[ks]
+        gt, eg = _mp_ints([g[k] / cv.d[k] for k in ks])
+        delta = (np.dot(gt, Jk), eg + eJ)
+        if not second:
+            return delta, None
+        pos = {k: i for i, k in enumerate(ks)}
+        g2, eg2 = _mp_ints([g[k] / (cv.d[k] * cv.d[k]) for k in ks])
+        keys = sorted(H)
+        ht, eH = _mp_ints([H[key] / (cv.d[key[0]] * cv.d[key[1]]) for key in keys])
+        M = np.array([[0] * P for _ in ks], dtype=object)                    # Ht J, Ht banded
+        for (k, l), v in zip(keys, ht):
+            M[pos[k]] = M[pos[k]] + v * Jk[pos[l]]
+        Ck, eC = C
+        Ck = Ck[ks].reshape(len(ks), P * P)
+        pieces = [(np.dot(Jk.T, M), eH + 2 * eJ), (np.dot(gt, Ck).reshape(P, P), eg + eC),
+                  (sign * np.dot(Jk.T, g2[:, None] * Jk), eg2 + 2 * eJ)]
+        return delta, _align(pieces)
+
+    def blocks(self, tables, delta_scale=4, gamma_scale=8):
+        """``(pv, delta, gamma)`` Blocks (gamma None without the second order)."""
+        J, Ja, C, Ca = tables
+        second = self.second and C is not None
+        dv, gv = self._project(self.g, self.H, J, C, -1, second)
+        da, ga = self._project(self.g_abs, self.H_abs, Ja, Ca, +1, second)
+        pv = Block.of(_mp_ints([self.pv]), _mp_ints([self.pv_abs]), 0)
+        return pv, Block.of(dv, da, delta_scale), (Block.of(gv, ga, gamma_scale) if second else None)
+
+
+def _tables(cv):
+    J = _float_ints(cv.J)
+    Ja = (abs(J[0]), J[1])
+    if cv.C is None:
+        return J, Ja, None, None
+    C = _float_ints(cv.C)
+    return J, Ja, C, (abs(C[0]), C[1])
+
+
+# ------------------------------------------------------------------------------------------------------------ the terms
+def trade_terms(batch, i, z=None, fix_tau=None, flt_tau=None):
+    """The unfolded terms ``(t, c, tau)`` of trade ``i`` (c an mpf, the spread factor not applied; tau None without
+    spreads).  Ratio-node trades are out of scope: an accruing coupon must be paid on its accrual end."""
+    assert batch.flt_weight is None
+    out = []
+    for j in range(int(batch.fix_off[i]), int(batch.fix_off[i + 1])):
+        tp = float(batch.fix_tp[j])
+        if tp > 0.0:
+            out.append((tp, _mp(batch.fix_sign[i]) * _mp(batch.fix_pay[j]), None if fix_tau is None else float(fix_tau[j])))
+    sn = _mp(batch.flt_sign[i]) * _mp(batch.notional[i])
+    for j in range(int(batch.flt_off[i]), int(batch.flt_off[i + 1])):
+        tp, ts, te, al = (float(getattr(batch, name)[j]) for name in ("flt_tp", "flt_ts", "flt_te", "flt_alpha"))
+        if al > 0.0:
+            assert te == tp, "a ratio node: out of scope"
+        if not tp >= 0.0:
+            continue
+        tau = None if flt_tau is None else float(flt_tau[j])
+        if al > 0.0:
+            out.append((ts, sn, tau))
+            out.append((tp, -sn, tau))
+        out.append((tp, sn * _mp(batch.spread[i]) * _mp(al), tau))
+    return [term for term in out if term[1] != 0]
+
+
+def _key(*arrays):
+    return tuple(None if a is None else (np.ascontiguousarray(a).tobytes(), np.asarray(a).shape) for a in arrays)
+
+
+_BATCH_FIELDS = ("fix_off", "flt_off", "fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional", "spread",
+                 "fix_sign", "flt_sign")
+_CACHE = {}
+
+
+def _cached(kind, method, host, batch, extra, build):
+    key = (kind, int(method)) + _key(host.times, host.dfs, host.jac, host.hess, *[getattr(batch, f) for f in _BATCH_FIELDS], *extra)
+    if key not in _CACHE:
+        _CACHE[key] = build()
+    return _CACHE[key]
+
+
+def rates_reference(method, host, batch, sub_off):
+    """Per desk ``{"pv", "delta", "gamma": Block, "k": int, "n_terms": int}``; ``host``: an object with times, dfs, jac,
+    hess.  Built once per process for the same inputs."""
+    sub_off = np.asarray(sub_off, dtype=np.int64)
+
+    def build():
+        mp.dps = 60
+        cv = _Curve(method, host.times, host.dfs, host.jac, host.hess)
+        tables = _tables(cv)
+        desks = []
+        for lo, hi in zip(sub_off[:-1], sub_off[1:]):
+            sums = _Sums(cv, True)
+            for i in range(int(lo), int(hi)):
+                for t, c, _ in trade_terms(batch, i):
+                    sums.add(t, c)
+            pv, delta, gamma = sums.blocks(tables)
+            desks.append({"pv": pv, "delta": delta, "gamma": gamma, "n_terms": sums.n,
+                          "k": bound_k(method, sums.n, compact_count(cv.x), float(sums.cond))})
+        return desks
+    return _cached("rates", method, host, batch, (sub_off,), build)
+
+
+def credit_reference(method, host, case, G, sub_off):
+    """Per desk the rates blocks AT THE SPREADS plus ``cs01``, ``spread_gamma`` ([G] Blocks) and ``cross_gamma`` ([G, P]);
+    ``case``: batch, z, bucket, fix_tau, flt_tau."""
+    sub_off = np.asarray(sub_off, dtype=np.int64)
+    batch = case.batch
+
+    def build():
+        mp.dps = 60
+        cv = _Curve(method, host.times, host.dfs, host.jac, host.hess)
+        tables = _tables(cv)
+        P = cv.P
+        desks = []
+        for lo, hi in zip(sub_off[:-1], sub_off[1:]):
+            at = _Sums(cv, True)
+            first = [_Sums(cv, False) for _ in range(G)]
+            second = [_Sums(cv, False) for _ in range(G)]
+            zt = mpf(0)
+            for i in range(int(lo), int(hi)):
+                z, g = _mp(case.z[i]), int(case.bucket[i])
+                for t, c, tau in trade_terms(batch, i, case.z, case.fix_tau, case.flt_tau):
+                    tau = _mp(tau)
+                    zt = max(zt, abs(z * tau))
+                    cf = c * mp.exp(-z * tau)
+                    at.add(t, cf)
+                    if g >= 0:
+                        first[g].add(t, -tau * cf)
+                        second[g].add(t, tau * tau * cf)
+            pv, delta, gamma = at.blocks(tables)
+            cs, csg, cross = [], [], []
+            for g in range(G):
+                pv1, d1, _ = first[g].blocks(tables, delta_scale=8)
+                pv2, _, _ = second[g].blocks(tables)
+                cs.append(Block(pv1.V, pv1.A, pv1.E, 4))
+                csg.append(Block(pv2.V, pv2.A, pv2.E, 8))
+                cross.append(d1)
+            stack = lambda blocks, shape: _stack(blocks, shape)
+            desks.append({"pv": pv, "delta": delta, "gamma": gamma, "cs01": stack(cs, (G,)), "spread_gamma": stack(csg, (G,)),
+                          "cross_gamma": stack(cross, (G, P)), "n_terms": at.n,
+                          "k": bound_k(method, at.n, compact_count(cv.x), float(at.cond), float(zt))})
+        return desks
+    return _cached("credit", method, host, batch, (case.z, case.bucket, case.fix_tau, case.flt_tau, np.array([G]), sub_off), build)
+
+
+def _stack(blocks, shape):
+    """Blocks of one scale stacked along a new first axis, on their lowest exponent."""
+    if not blocks:
+        empty = np.empty(shape, dtype=object)
+        return Block(empty, empty.copy(), 0, 0)
+    lo = min(b.E for b in blocks)
+    V = np.array([b.V * (1 << (b.E - lo)) for b in blocks], dtype=object).reshape(shape)
+    A = np.array([b.A * (1 << (b.E - lo)) for b in blocks], dtype=object).reshape(shape)
+    return Block(V, A, lo, blocks[0].s)
+
+
+def worst_between(a, b, ref, blocks):
+    """`Block.between` over every element of every desk."""
+    return max((desk[name].between(a[name][i], b[name][i], desk["k"]) for i, desk in enumerate(ref) for name in blocks), default=0.0)
+
+
+RATES_BLOCKS = ("pv", "delta", "gamma")
+CREDIT_BLOCKS = RATES_BLOCKS + ("cs01", "spread_gamma", "cross_gamma")
+
+
+def worst_share(got, ref, blocks=RATES_BLOCKS, what=""):
+    """The worst share of the bound over every element of every desk; ``got[block][desk]`` against ``ref[desk][block]``."""
+    worst = 0.0
+    for b, desk in enumerate(ref):
+        for name in blocks:
+            g = np.asarray(got[name][b])
+            worst = max(worst, desk[name].share(g.reshape(desk[name].V.shape), desk["k"], f"{what} desk {b} {name}"))
+    return worst

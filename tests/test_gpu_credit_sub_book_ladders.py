@@ -40,7 +40,9 @@ def check_book(ctx, method, host, dc, case, G, sub_off, what, key=None):
 def test_geometry(gpu_ctx, interp, G):
     """Desks of GEOMETRY_SIZES trades, bonds and lag-free FRNs mixed: one cell of 65 trades (two chunks), one desk of G + 1
     cells, one all unbucketed, one that lacks most buckets.  Observed on an MI355X, worst over the schemes and G (bound
-    1e-10): against the oracle desks 8.6e-12 (the one-trade desk's gamma), cells 1.3e-14; against the host twin 3.5e-15."""
+    1e-10): against the oracle desks 3.6e-13 (the one-trade desk's gamma, an FRN whose gamma nets far below its gross; 8.6e-12
+    before oracle/port.c priced coupons paid on their accrual end in linear form - the oracle's own error, see
+    tests/test_ladder_edges_host.py), cells 8.1e-15; against the host twin 3.5e-15."""
     curve = F.gbp_model(L.VD, interp).curves.GBP_OIS_SONIA
     host, dc = _device_curve(gpu_ctx, curve)
     case, sub_off = X.geometry_case(G)
