@@ -169,6 +169,13 @@ _SIGNATURES = {
                                                  C.c_int64, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "adr_credit_subbook_ladders_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64p, _i64p] +
                                         [_dp] * 11 + [_dp, _i32p, _dp, _dp, C.c_int, C.c_int64, _i64p, C.c_uint32, _dp]),
+    "adr_yoy_subbook_ladders_work": (C.c_int64, [_vp, C.c_int, C.c_int64, C.c_int64, C.c_uint32, _i64p]),
+    "adr_yoy_subbook_ladders": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int64, _i64p, _dp, _dp, C.c_int64,
+                                          _i64p, _dp, C.c_int64, _i64p, C.c_uint32, _dp]),
+    "adr_yoy_subbook_ladders_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64,
+                                              _vp, _vp, C.c_int64, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "adr_yoy_subbook_ladders_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int64,
+                                               C.c_int64, _i64p, _dp, _dp, C.c_int64, _i64p, _dp, C.c_int64, _i64p, C.c_uint32, _dp]),
     "adr_ladder_pnl": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "adr_ladder_pnl_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "adr_ladder_pnl_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
@@ -994,18 +1001,9 @@ def scenario_pv_dev(ctx: Context, method: int, K: int, times_ptr: int, S: int, d
                                       _dev(pv_ptr), _dev(book_ptr), _dev(work_ptr), _vp(stream or None)), "adr_scenario_pv_dev")
 
 
-def _yoy_scenario_inputs(times, dfs, T, b, fixed, book):
-    """The arrays of adr_yoy_scenario_pv from ``dfs`` [S, K] or [K], ``b`` [S, P] or [P], the fixed legs ``(fix_off,
-    fix_tp, fix_pay)`` (None: no fixed flows) and the coupon book (``cpn_off`` and YOY_FIELDS; None: no coupons)."""
-    times, dfs = _scenario_curves(times, dfs)
-    T = _f64(T).reshape(-1)
-    b = _f64(np.atleast_2d(b))
-    if b.ndim != 2 or b.shape[1] != T.size:
-        raise LibError(f"b must have shape [n_scenarios, {T.size}] or [{T.size}] (one column per pillar), not {list(b.shape)}")
-    S = max(dfs.shape[0], b.shape[0])
-    if dfs.shape[0] not in (1, S) or b.shape[0] not in (1, S):
-        raise LibError(f"{dfs.shape[0]} discount rows and {b.shape[0]} breakeven rows: each must be one shared row or "
-                       "one row per scenario")
+def _yoy_legs(fixed, book):
+    """``(fix_off, fix_tp, fix_pay, cpn_off, cpn)`` of a YoY book from the fixed legs ``(fix_off, fix_tp, fix_pay)`` (None: no
+    fixed flows) and the coupon book (``cpn_off`` and YOY_FIELDS; None: no coupons)."""
     if fixed is None and book is None:
         raise LibError("neither fixed legs nor YoY coupons")
     if book is not None:
@@ -1021,6 +1019,22 @@ def _yoy_scenario_inputs(times, dfs, T, b, fixed, book):
         cpn_off, cpn = np.zeros_like(fix_off), np.zeros((len(YOY_FIELDS), 0))
     if fix_off.shape != cpn_off.shape:
         raise LibError(f"fix_off describes {fix_off.size - 1} swaps, cpn_off {cpn_off.size - 1}")
+    return fix_off, fix_tp, fix_pay, cpn_off, cpn
+
+
+def _yoy_scenario_inputs(times, dfs, T, b, fixed, book):
+    """The arrays of adr_yoy_scenario_pv from ``dfs`` [S, K] or [K], ``b`` [S, P] or [P], the fixed legs ``(fix_off,
+    fix_tp, fix_pay)`` (None: no fixed flows) and the coupon book (``cpn_off`` and YOY_FIELDS; None: no coupons)."""
+    times, dfs = _scenario_curves(times, dfs)
+    T = _f64(T).reshape(-1)
+    b = _f64(np.atleast_2d(b))
+    if b.ndim != 2 or b.shape[1] != T.size:
+        raise LibError(f"b must have shape [n_scenarios, {T.size}] or [{T.size}] (one column per pillar), not {list(b.shape)}")
+    S = max(dfs.shape[0], b.shape[0])
+    if dfs.shape[0] not in (1, S) or b.shape[0] not in (1, S):
+        raise LibError(f"{dfs.shape[0]} discount rows and {b.shape[0]} breakeven rows: each must be one shared row or "
+                       "one row per scenario")
+    fix_off, fix_tp, fix_pay, cpn_off, cpn = _yoy_legs(fixed, book)
     return times, dfs, T, b, S, fix_off, fix_tp, fix_pay, cpn_off, cpn
 
 
@@ -1544,6 +1558,86 @@ def credit_subbook_ladders_dev(ctx: Context, curve: DeviceCurve, trades: DeviceT
                                                  int(n_flt), g("flt_tau"), int(G), int(B), int(n_cells), g("cell_plan"),
                                                  g("desk_cell_off"), g("cell_bucket"), int(mask), _dev(out_ptr), _dev(work_ptr),
                                                  _vp(stream or None)), "adr_credit_subbook_ladders_dev")
+
+
+# --------------------------------------------------------------------------------------- inflation sub-book Greeks
+def _yoy_ladder_rows(out, P, Pi):
+    """``out [B, 1 + Q + Q Q]`` (Q = P + Pi) as its blocks; ``ladders`` is ``out`` itself, what `ladder_pnl` takes beside
+    shock rows ``[x_bp (P), (b - b0) * 1e4 (Pi)]``."""
+    Q = P + Pi
+    g = out[:, 1 + Q:].reshape(-1, Q, Q)
+    return {"pv": out[:, 0].copy(), "delta": out[:, 1:1 + P].copy(), "gamma": g[:, :P, :P].copy(),
+            "infl_delta": out[:, 1 + P:1 + Q].copy(), "infl_gamma": g[:, P:, P:].copy(), "cross_gamma": g[:, P:, :P].copy(),
+            "ladders": out}
+
+
+def _yoy_ladder_inputs(T, b, fixed, book):
+    """The inflation curve and the book as the YoY ladder entries take them: one breakeven row, both legs' arrays."""
+    T, b = _f64(T).reshape(-1), _f64(b).reshape(-1)
+    if b.shape != T.shape:
+        raise LibError(f"b must hold one breakeven rate per pillar ({T.size}), not {list(b.shape)}")
+    return (T, b) + _yoy_legs(fixed, book)
+
+
+def yoy_subbook_ladders(ctx: Context, curve: DeviceCurve, infl_method: int, T, b, fixed, book, sub_off, want_delta=True,
+                        want_gamma=True):
+    """The augmented ladders of every sub-book of a YoY book from one launch chain (adr_yoy_subbook_ladders, blocking):
+    ``curve`` the uploaded discount curve, ``(infl_method, T [Pi], b [Pi])`` the inflation curve, ``fixed`` and ``book`` as
+    `yoy_scenario_subbook_pv` takes them.  Returns ``pv [B]``, ``delta [B, P]``, ``gamma [B, P, P]`` (discount), ``infl_delta
+    [B, Pi]``, ``infl_gamma [B, Pi, Pi]`` (breakeven), ``cross_gamma [B, Pi, P]`` and the augmented rows ``ladders
+    [B, 1 + Q + Q Q]``, Q = P + Pi; what was not requested is zeros."""
+    sub_off, B = _sub_offsets(sub_off)
+    T, b, fix_off, fix_tp, fix_pay, cpn_off, cpn = _yoy_ladder_inputs(T, b, fixed, book)
+    P, Pi = curve.n_pillars, T.size
+    Q = P + Pi
+    out = np.empty((B, 1 + Q + Q * Q))
+    _check(load().adr_yoy_subbook_ladders(ctx._h, curve._h, int(infl_method), Pi, _ptr(T), _ptr(b), fix_off.size - 1, fix_tp.size,
+                                          _ptr(fix_off, _i64p), _ptr(fix_tp), _ptr(fix_pay), cpn.shape[1], _ptr(cpn_off, _i64p),
+                                          _ptr(cpn), B, _ptr(sub_off, _i64p), _request_mask(want_delta, want_gamma), _ptr(out)),
+           "adr_yoy_subbook_ladders")
+    return _yoy_ladder_rows(out, P, Pi)
+
+
+def yoy_subbook_ladders_host(interp_method: int, times, dfs, jac, hess, infl_method: int, T, b, fixed, book, sub_off,
+                             want_delta=True, want_gamma=True):
+    """`yoy_subbook_ladders` on the CPU (adr_yoy_subbook_ladders_host) for the discount curve's arrays as `DeviceCurve` takes
+    them: the same node, sum and projection code, chunks and orders; no GPU needed."""
+    sub_off, B = _sub_offsets(sub_off)
+    times, dfs, jac, hess, K, P = _curve_arrays(times, dfs, jac, hess, shapes=True)
+    T, b, fix_off, fix_tp, fix_pay, cpn_off, cpn = _yoy_ladder_inputs(T, b, fixed, book)
+    Pi = T.size
+    Q = P + Pi
+    out = np.empty((B, 1 + Q + Q * Q))
+    _check(load().adr_yoy_subbook_ladders_host(int(interp_method), K, P, _ptr(times), _ptr(dfs), _ptr(jac), _ptr(hess),
+                                               int(infl_method), Pi, _ptr(T), _ptr(b), fix_off.size - 1, fix_tp.size,
+                                               _ptr(fix_off, _i64p), _ptr(fix_tp), _ptr(fix_pay), cpn.shape[1],
+                                               _ptr(cpn_off, _i64p), _ptr(cpn), B, _ptr(sub_off, _i64p),
+                                               _request_mask(want_delta, want_gamma), _ptr(out)), "adr_yoy_subbook_ladders_host")
+    return _yoy_ladder_rows(out, P, Pi)
+
+
+def yoy_subbook_ladders_work(curve: DeviceCurve, n_infl_pillars: int, n_swaps: int, n_sub_books: int, want_gamma=True):
+    """``(doubles of scratch, rows of chunk records it holds)`` of `yoy_subbook_ladders_dev` (adr_yoy_subbook_ladders_work)."""
+    chunks = C.c_int64(0)
+    work = load().adr_yoy_subbook_ladders_work(curve._h, int(n_infl_pillars), int(n_swaps), int(n_sub_books),
+                                               _request_mask(True, want_gamma), C.cast(C.byref(chunks), _i64p))
+    if work <= 0:
+        raise LibError("adr_yoy_subbook_ladders_work: a curve, 1 .. 64 inflation pillars and at least one swap and sub-book are "
+                       "needed")
+    return int(work), int(chunks.value)
+
+
+def yoy_subbook_ladders_dev(ctx: Context, curve: DeviceCurve, infl_method: int, P_i: int, n_swaps: int, n_fix: int, n_coupons: int,
+                            B: int, ptrs, mask: int, out_ptr: int, work_ptr: int, stream=0):
+    """Non-blocking form (adr_yoy_subbook_ladders_dev): ``ptrs`` maps ``T`` [P_i], ``b`` [P_i], ``fix_off``, ``fix_tp``,
+    ``fix_pay``, ``cpn_off``, ``cpn`` and ``plan`` (the uploaded `scenario_subbook_plan`) to device pointers (integers; the
+    value arrays of an empty leg may be 0); the output ``[B, 1 + Q + Q Q]`` and `yoy_subbook_ladders_work` doubles of
+    scratch."""
+    g = _dev_of(ptrs)
+    _check(load().adr_yoy_subbook_ladders_dev(ctx._h, curve._h, int(infl_method), int(P_i), g("T"), g("b"), int(n_swaps), int(n_fix),
+                                              g("fix_off"), g("fix_tp"), g("fix_pay"), int(n_coupons), g("cpn_off"), g("cpn"),
+                                              int(B), g("plan"), int(mask), _dev(out_ptr), _dev(work_ptr), _vp(stream or None)),
+           "adr_yoy_subbook_ladders_dev")
 
 
 # --------------------------------------------------------------------------------------- delta-gamma P&L of ladders

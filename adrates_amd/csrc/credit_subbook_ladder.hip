@@ -243,20 +243,8 @@ struct ProjectArgs {
 // The curve block of the augmented ladder from the desks' sums and +0.0 in every spread row and column.
 __global__ __launch_bounds__(kWave * kProjWaves) void credit_project_kernel(ProjectArgs a) { project_curve_block<true>(a); }
 
-// One pillar's cross term of a cell: sum_k wz_k LJ[k][p], the knots taken as the projection's waves take them.
-template <class LJ>
-__host__ __device__ inline double cross_sum(const double* wz, int Kc, const LJ& lj) {
-    double tot = 0.0;
-    for (int part = 0; part < kProjWaves; ++part) {
-        double s = 0.0;
-        for (int k = part; k < Kc; k += kProjWaves) s = delta_step(s, wz[k], lj(k));
-        tot = part == 0 ? s : tot + s;
-    }
-    return tot;
-}
-
 // The spread rows and columns from the cells' sums, one wave per cell; every value is computed once and written where it
-// belongs (twice for the cross terms).  Runs after credit_project_kernel on the same stream.
+// belongs (twice for the cross terms, sbl::cross_sum).  Runs after credit_project_kernel on the same stream.
 __global__ __launch_bounds__(kWave * kCellWaves) void credit_cell_kernel(ProjectArgs a) {
     const CurveDev& cv = a.cv;
     const int P = cv.P, Kc = cv.Kc, Q = P + a.G;

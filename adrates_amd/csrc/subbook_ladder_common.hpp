@@ -1,9 +1,10 @@
-// What the sub-book ladder sources (subbook_ladder.hip, credit_subbook_ladder.hip) have in common, once: the folding of a
-// trade's cash flows into knot-space nodes, a node's lookup and its numbers, the projection of the curve block on the device
-// and on the host, the owner search of the knot kernels, the knot launch, the checks of the handles and of the `_host`
-// entries' arrays, the host's trade walk and the request and refusal wording.  These are what the host twins and the device
-// are held to bit for bit and what decides a refusal's message, so a fix to any of them is made here.  A source keeps its
-// knot kernel, its record layout, its entries and the order in which an entry calls the checks.
+// What the sub-book ladder sources (subbook_ladder.hip, credit_subbook_ladder.hip and, for the curve block, the node's
+// numbers, the cross sum and the launch, yoy_subbook_ladder.hip) have in common, once: the folding of a trade's cash flows
+// into knot-space nodes, a node's lookup and its numbers, the projection of the curve block on the device and on the host,
+// the owner search of the knot kernels, the knot launch, the checks of the handles and of the `_host` entries' arrays, the
+// host's trade walk and the request and refusal wording.  These are what the host twins and the device are held to bit for
+// bit and what decides a refusal's message, so a fix to any of them is made here.  A source keeps its knot kernel, its
+// record layout, its entries and the order in which an entry calls the checks.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -175,6 +176,19 @@ __host__ __device__ inline double gamma_step(double s, double wk, double dk, dou
 }
 
 __host__ __device__ inline double delta_step(double s, double wk, double aq) { return s + wk * aq; }
+
+// One pillar's cross term of a second risk factor: sum_k wz_k LJ[k][p] over a knot-space table wz of mixed sums (the
+// credit cells' spread table, the YoY desks' rows of M), the knots taken as the projection's waves take them.
+template <class LJ>
+__host__ __device__ inline double cross_sum(const double* wz, int Kc, const LJ& lj) {
+    double tot = 0.0;
+    for (int part = 0; part < kProjWaves; ++part) {
+        double s = 0.0;
+        for (int k = part; k < Kc; k += kProjWaves) s = delta_step(s, wz[k], lj(k));
+        tot = part == 0 ? s : tot + s;
+    }
+    return tot;
+}
 
 // The curve block of out[b] = [pv, delta[Q], gamma[Q][Q]] from the desks' sums, the body of the two projection kernels.
 // blockIdx.y < Q: row y of the gamma matrices (lane = column); blockIdx.y == Q: pv and the delta ladders.  A block takes

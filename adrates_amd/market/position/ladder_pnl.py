@@ -12,6 +12,9 @@ inflation ladders of `YoYBook.compute` the breakeven shocks.
 and one P&L launch.  The gap to full revaluation - the unexplained P&L per desk and scenario - is
 `ScenarioGrid.explain_sub_books`.
 
+Inflation desks take it too: `price_yoy_sub_books`' rows on the discount and the inflation pillars beside
+`yoy_shock_matrix_bp`'s joint rows.
+
 Credit desks take the same kernel: `price_credit_sub_books`' augmented rows hold, beside the curve ladders at the spreads,
 CS01, spread gamma and the rate x spread cross gamma per bucket in the layout of a ladder over ``P + G`` "pillars", so
 `credit_delta_gamma_sub_books` is `ladder_pnl` on those rows and `credit_shock_matrix_bp`'s joint shocks.
@@ -123,6 +126,29 @@ def credit_shock_matrix_bp(shocks_bp, spread_shocks) -> np.ndarray:
         raise LibError(f"{x.shape[0]} curve-shock rows and {y.shape[0]} spread-shock rows: each must be one shared row or one "
                        "row per scenario")
     return np.ascontiguousarray(np.hstack([np.broadcast_to(x, (S, x.shape[1])), np.broadcast_to(y, (S, y.shape[1])) * 1e4]))
+
+
+def yoy_shock_matrix_bp(shocks_bp, breakevens=None, b0=None, infl_shocks_bp=None) -> np.ndarray:
+    """``[S, P_d + P_i]``: joint shock rows for the augmented ladders of `price_yoy_sub_books` - the discount curve's shocks
+    ``shocks_bp [S, P_d]`` in basis points as they are, then the breakeven moves in basis points: ``(breakevens - b0) * 1e4``
+    from breakeven rows ``[S, P_i]`` and the base rates ``b0 [P_i]``, or ``infl_shocks_bp [S, P_i]`` as they are (moves built
+    from the shocks themselves carry no rounding of a difference).  Either side may be one row, shared by all scenarios."""
+    if (breakevens is None) == (infl_shocks_bp is None):
+        raise LibError("give breakevens (with b0) or infl_shocks_bp")
+    x = np.atleast_2d(np.asarray(shocks_bp, dtype=np.float64))
+    if infl_shocks_bp is not None:
+        y = np.atleast_2d(np.asarray(infl_shocks_bp, dtype=np.float64))
+    else:
+        if b0 is None:
+            raise LibError("breakeven rows need the base rates b0")
+        y = (np.atleast_2d(np.asarray(breakevens, dtype=np.float64)) - np.asarray(b0, dtype=np.float64).reshape(1, -1)) * 1e4
+    if x.ndim != 2 or y.ndim != 2:
+        raise LibError(f"shocks_bp [S, P_d] and breakeven rows [S, P_i] are needed, not {list(x.shape)} and {list(y.shape)}")
+    S = max(x.shape[0], y.shape[0])
+    if x.shape[0] not in (1, S) or y.shape[0] not in (1, S):
+        raise LibError(f"{x.shape[0]} curve-shock rows and {y.shape[0]} breakeven rows: each must be one shared row or one row per "
+                       "scenario")
+    return np.ascontiguousarray(np.hstack([np.broadcast_to(x, (S, x.shape[1])), np.broadcast_to(y, (S, y.shape[1]))]))
 
 
 def augmented_ladder_pnl(ladders, shocks, parts=False, host=False, ctx=None):

@@ -12,6 +12,10 @@ and refuses such a book.
 Credit desks: `price_credit_sub_books` prices bonds at their z-spreads and FRNs at their discount margins and returns, beside
 the curve ladders AT THE SPREADS, every desk's CS01 and spread gamma per credit bucket and the rate x spread cross gamma
 (adr_credit_subbook_ladders).  It has no route for ratio nodes and refuses such a trade.
+
+Inflation desks: `price_yoy_sub_books` returns every desk's row on ``Q = P_d + P_i`` columns - the discount pillars, then the
+inflation curve's: the discount ladders, the breakeven ladders and the discount x breakeven cross gamma of a YoY book
+(adr_yoy_subbook_ladders), which no other route has.
 """
 from dataclasses import dataclass
 
@@ -24,7 +28,8 @@ from ...utils.global_types import CurveTypes, InstrumentTypes, RequestTypes
 from ...utils.helpers import to_tenor
 from ..curves.curve_tables import build_engine_curve
 from .engine import Engine, price_batch, price_frns
-from .scenarios import _permute_batch, compile_book, compile_credit_book, split_sub_books
+from .scenarios import (_permute_batch, compile_book, compile_credit_book, split_sub_books, split_yoy_sub_books,
+                        yoy_book_arrays)
 
 
 def has_ratio_node(batch: TradeBatch) -> np.ndarray:
@@ -187,3 +192,35 @@ def price_credit_sub_books(engine: Engine, ir_model, trades, spreads, keys, buck
                 out["ladders"][b, 0] = out["pv"][b]
     out["labels"], out["buckets"], out["tenors"] = cb.labels, cb.buckets, tenors
     return out
+
+
+def price_yoy_sub_books(engine: Engine, disc_curve, infl_curve, swaps_or_book, keys, reqs, host=False):
+    """The inflation desks' augmented ladders from one launch chain (adr_yoy_subbook_ladders).
+
+    ``swaps_or_book``: `YoYInflationSwap` objects or compiled arrays (`yoy_book_arrays`) on ``disc_curve`` and ``infl_curve``;
+    ``keys`` one hashable desk key per swap.  Returns ``{"labels", "pv" [B], "delta" [B, Q], "gamma" [B, Q, Q], "tenors",
+    "infl_tenors", "ladders" [B, 1 + Q + Q Q]}`` on ``Q = P_d + P_i`` columns, the discount pillars (``tenors``) first and then
+    the inflation curve's (``infl_tenors``): ``delta`` per bp of a par quote or of a breakeven rate, ``gamma`` per bp squared
+    with the discount block, the breakeven block and, in ``gamma[:, :P_d, P_d:]`` and its transpose, the cross block;
+    ``ladders`` the same rows as `ladder_pnl` takes them beside `yoy_shock_matrix_bp`'s.  What ``reqs`` does not ask for is
+    zeros.  ``host``: the CPU twin, no GPU needed."""
+    from .inflation_engine import inflation_inputs
+    reqs = set(reqs)
+    want_gamma = RequestTypes.GAMMA in reqs
+    want_delta = want_gamma or RequestTypes.DELTA in reqs
+    sb = split_yoy_sub_books(*yoy_book_arrays(swaps_or_book, engine.model.value_dt), list(keys))
+    im, T, b = inflation_inputs(infl_curve)
+    method = disc_curve._interp_type.value
+    if host:
+        curve, tenors = _host_curve(disc_curve)
+        out = _native.yoy_subbook_ladders_host(method, curve.times, curve.dfs, curve.jac, curve.hess if want_gamma else None, im,
+                                               T, b, sb.fixed, sb.coupons, sb.sub_off, want_delta, want_gamma)
+    else:
+        cur = engine._device_curve(disc_curve)
+        tenors = cur["tenors"]
+        out = _native.yoy_subbook_ladders(cur["ctx"], cur["dev"], im, T, b, sb.fixed, sb.coupons, sb.sub_off, want_delta,
+                                          want_gamma)
+    rows = out["ladders"]
+    Q = len(tenors) + T.size
+    return {"labels": sb.labels, "pv": out["pv"], "delta": rows[:, 1:1 + Q].copy(), "gamma": rows[:, 1 + Q:].reshape(-1, Q, Q).copy(),
+            "tenors": tenors, "infl_tenors": to_tenor(list(infl_curve.swap_times)), "ladders": rows}

@@ -14,10 +14,12 @@ from ... import _native
 from ...trades.rates.yoy_inflation_swap import YoYInflationSwap
 from ...utils.error import LibError
 from ...utils.global_types import RequestTypes
+from ...utils.helpers import to_tenor
 from .engine import Engine
 from .inflation_engine import inflation_inputs, price_yoy, yoy_curves
 from .scenarios import (revalue_yoy_on_curves, revalue_yoy_on_curves_sub_books, shocked_breakevens, split_yoy_sub_books,
                         tail_count, yoy_book_arrays, _finish_yoy_sub_books)
+from .sub_book_ladders import price_yoy_sub_books
 
 
 def tile_yoy_book(book: dict, reps: int) -> dict:
@@ -155,12 +157,16 @@ class YoYBook:
                                      self.model.value_dt, ctx=ctx)["book_pv"]
         return book[:-1] - book[-1]
 
-    def pnl_delta_gamma(self, grid=None, inflation_shocks=None, breakevens=None) -> np.ndarray:
+    def pnl_delta_gamma(self, grid=None, inflation_shocks=None, breakevens=None, cross: bool = False) -> np.ndarray:
         """``[S]``: `pnl` to second order from the book's ladders (`compute` with ``aggregate``), without a revaluation:
         the discount ladders under the grid's shocks plus the inflation ladders under the breakeven shocks in basis
         points (``inflation_shocks`` as they are, ``breakevens`` as ``(b - b0) * 1e4``) - two `ladder_pnl` calls.  There
         is no discount x inflation cross term, as in the engine's Greeks, so with both curves shocked the gap to `pnl`
-        is second order.  Scenarios and their checks: see `revalue`."""
+        is second order.  ``cross=True`` takes the ladders of `compute_sub_books` with one desk instead, which hold the
+        cross block: the gap to `pnl` is then third order under joint shocks too (`pnl_delta_gamma_sub_books`' row).
+        Scenarios and their checks: see `revalue`."""
+        if cross:
+            return self.pnl_delta_gamma_sub_books([0] * len(self.swaps), grid, inflation_shocks, breakevens)["pnl"][0]
         from .ladder_pnl import ladder_pnl, shock_matrix_bp
         b = self._breakeven_rows(grid, inflation_shocks, breakevens)
         res = self.compute({RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}, per_trade=False, aggregate=True)
@@ -251,15 +257,19 @@ class YoYBook:
         return revalue_yoy_on_curves_sub_books(self.curve._interp_type.value, cur["host"].times, cur["host"].dfs, im, T, b,
                                                self._arrays(), keys, self.model.value_dt, per_trade=per_trade, ctx=cur["ctx"])
 
-    def pnl_sub_books(self, keys, grid=None, inflation_shocks=None, breakevens=None) -> np.ndarray:
-        """``[B, S]``: `pnl` per sub-book (rows in the order of `revalue_sub_books`' labels).  The unshocked pair is priced
-        as one more column of the same launch, so a zero shock is exactly 0 in every row."""
+    def _pnl_sub_books(self, keys, grid, inflation_shocks, breakevens):
+        """``(labels, pnl [B, S])`` of `pnl_sub_books`."""
         b = self._breakeven_rows(grid, inflation_shocks, breakevens)
         im, T, _ = inflation_inputs(self.inflation_curve)
         times, dfs, rows, ctx = self._base_pair(grid, b)
         sub = revalue_yoy_on_curves_sub_books(self.curve._interp_type.value, times, dfs, im, T, rows, self._arrays(), keys,
-                                              self.model.value_dt, ctx=ctx)["sub_pv"]
-        return sub[:, :-1] - sub[:, -1:]
+                                              self.model.value_dt, ctx=ctx)
+        return sub["labels"], sub["sub_pv"][:, :-1] - sub["sub_pv"][:, -1:]
+
+    def pnl_sub_books(self, keys, grid=None, inflation_shocks=None, breakevens=None) -> np.ndarray:
+        """``[B, S]``: `pnl` per sub-book (rows in the order of `revalue_sub_books`' labels).  The unshocked pair is priced
+        as one more column of the same launch, so a zero shock is exactly 0 in every row."""
+        return self._pnl_sub_books(keys, grid, inflation_shocks, breakevens)[1]
 
     def sub_book_var_es(self, keys, level: float = 0.99, grid=None, inflation_shocks=None, breakevens=None) -> dict:
         """``{"labels": [...], "var": [B], "es": [B]}``: the sub-book launch and the tail kernel chained on one stream, so
@@ -276,3 +286,102 @@ class YoYBook:
         var, es = self._sub_books_on_device(ctx, sb, self.curve._interp_type.value, times, dfs, rows,
                                             tail=(S, tail_count(level, S)))
         return {"labels": sb.labels, "var": var, "es": es}
+
+    # ------------------------------------------------------------------------------------------- sub-book Greeks
+    def compute_sub_books(self, request_list, keys, host: bool = False) -> dict:
+        """`compute` per sub-book from ONE launch chain (`price_yoy_sub_books`, adr_yoy_subbook_ladders): ``keys`` holds one
+        hashable value per swap.  ``{"labels", "pv" [B], "delta" [B, Q], "gamma" [B, Q, Q], "tenors", "infl_tenors",
+        "ladders"}`` on ``Q = P_d + P_i`` columns, the discount pillars first; ``gamma`` holds the discount block, the
+        breakeven block and the discount x breakeven cross block, which `compute` does not have."""
+        reqs = set(request_list)
+        if not reqs & {RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}:
+            raise LibError("YoYBook.compute_sub_books needs VALUE, DELTA or GAMMA")
+        return price_yoy_sub_books(self._engine, self.curve, self.inflation_curve, self._arrays(), keys, reqs, host=host)
+
+    def _joint_shocks_bp(self, grid, inflation_shocks, breakevens):
+        """``[S, P_d + P_i]`` basis points (`yoy_shock_matrix_bp`); a curve that is not shocked has a row of zeros."""
+        from .ladder_pnl import shock_matrix_bp, yoy_shock_matrix_bp
+        b = self._breakeven_rows(grid, inflation_shocks, breakevens)
+        b0 = inflation_inputs(self.inflation_curve)[2]
+        x = np.zeros((1, len(self.curve.swap_times))) if grid is None else grid.shocks_bp()
+        if inflation_shocks is not None:
+            return yoy_shock_matrix_bp(x, infl_shocks_bp=shock_matrix_bp(to_tenor(list(self.inflation_curve.swap_times)),
+                                                                         inflation_shocks, 1.0))
+        return yoy_shock_matrix_bp(x, b0[None, :] if b is None else b, b0)
+
+    def pnl_delta_gamma_sub_books(self, keys, grid=None, inflation_shocks=None, breakevens=None, parts: bool = False,
+                                  cross: bool = True, host: bool = False) -> dict:
+        """`pnl_sub_books` to second order without a revaluation: `compute_sub_books`' ladders (one launch chain) times the
+        joint shocks (`ladder_pnl`, one kernel),
+
+            delta . x + x' Gamma x / 2 + delta_i . y + y' Gamma_i y / 2 + y' C x,
+
+        ``x`` the grid's par-quote shocks and ``y`` the breakeven moves in basis points, ``C`` the cross block.  Returns
+        `compute_sub_books`' dict plus ``"pnl" [B, S]`` and, with ``parts``, ``"delta_pnl"`` and ``"gamma_pnl"``.
+        ``cross=False`` leaves the cross block out: the engine's Greeks, second-order gap under joint shocks."""
+        from .ladder_pnl import augmented_ladder_pnl
+        shocks = self._joint_shocks_bp(grid, inflation_shocks, breakevens)
+        out = self.compute_sub_books({RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}, keys, host=host)
+        rows = out["ladders"]
+        if not cross:
+            P, Q = len(out["tenors"]), shocks.shape[1]
+            g = rows.copy()[:, 1 + Q:].reshape(-1, Q, Q)
+            g[:, :P, P:] = 0.0
+            g[:, P:, :P] = 0.0
+            rows = np.hstack([rows[:, :1 + Q], g.reshape(g.shape[0], Q * Q)])
+        ctx = None if host else self._engine._device_curve(self.curve)["ctx"]
+        pnl = augmented_ladder_pnl(rows, shocks, parts=parts, host=host, ctx=ctx)
+        out.update(pnl if parts else {"pnl": pnl})
+        return out
+
+    def explain_sub_books(self, keys, grid=None, inflation_shocks=None, breakevens=None, cross: bool = True) -> dict:
+        """P&L explain per inflation desk and scenario: ``{"labels", "full", "delta_pnl", "gamma_pnl", "unexplained"}``, all
+        ``[B, S]`` - ``full`` is `pnl_sub_books`' full revaluation under the joint scenarios, the parts are
+        `pnl_delta_gamma_sub_books`', and ``unexplained = full - (delta_pnl + gamma_pnl)``: third order in the shocks, second
+        order with ``cross=False``."""
+        keys = list(keys)
+        labels, full = self._pnl_sub_books(keys, grid, inflation_shocks, breakevens)
+        dg = self.pnl_delta_gamma_sub_books(keys, grid, inflation_shocks, breakevens, parts=True, cross=cross)
+        assert dg["labels"] == labels and full.shape == dg["pnl"].shape, "the two routes order the desks differently"
+        return {"labels": labels, "full": full, "delta_pnl": dg["delta_pnl"], "gamma_pnl": dg["gamma_pnl"],
+                "unexplained": full - (dg["delta_pnl"] + dg["gamma_pnl"])}
+
+    def sub_book_delta_gamma_var_es(self, keys, level: float = 0.99, grid=None, inflation_shocks=None, breakevens=None) -> dict:
+        """``{"labels": [...], "var": [B], "es": [B]}`` of the delta-gamma P&L straight from the book: the ladder chain
+        (adr_yoy_subbook_ladders_dev), the P&L kernel (adr_ladder_pnl_dev on the augmented rows) and the tail kernel
+        (adr_scenario_tail_dev) on one stream, so neither the ladders nor the ``[B, S]`` matrix leave the device.  ``var``
+        and ``es`` are `tail_measures`' of `pnl_delta_gamma_sub_books`' ``pnl``, bit for bit.  The buffers are torch tensors;
+        where torch brings a HIP runtime of its own, import torch before the first call into this library, as the tools do."""
+        import torch
+        shocks_bp = self._joint_shocks_bp(grid, inflation_shocks, breakevens)
+        S, Q = shocks_bp.shape
+        if S > _native.SCENARIO_TAIL_MAX:
+            raise LibError(f"{S} scenarios: at most {_native.SCENARIO_TAIL_MAX} fit the tail kernel; use "
+                           "pnl_delta_gamma_sub_books and tail_measures")
+        if Q > _native.LADDER_PNL_MAX_PILLARS:
+            raise LibError(f"{Q} columns: at most {_native.LADDER_PNL_MAX_PILLARS} fit the P&L kernel")
+        sb = self._split(keys)
+        cur = self._engine._device_curve(self.curve)
+        ctx, curve = cur["ctx"], cur["dev"]
+        im, T, b0 = inflation_inputs(self.inflation_curve)
+        cpn_off, cpn = _native.yoy_pack(sb.coupons)
+        n, B = cpn_off.size - 1, sb.sub_off.size - 1
+        dev = torch.device("cuda", ctx.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        bufs = dict(T=up(T), b=up(b0), fix_off=up(sb.fixed[0]), fix_tp=up(sb.fixed[1]), fix_pay=up(sb.fixed[2]), cpn_off=up(cpn_off),
+                    cpn=up(cpn), plan=up(_native.scenario_subbook_plan(n, sb.sub_off)))
+        shocks = up(shocks_bp)
+        ladders, work = new(B, 1 + Q + Q * Q), new(_native.yoy_subbook_ladders_work(curve, T.size, n, B)[0])
+        pnl, var_es = new(B, S), new(2, B)
+        torch.cuda.synchronize(dev)
+        _native.yoy_subbook_ladders_dev(ctx, curve, im, T.size, n, sb.fixed[1].size, cpn.shape[1], B,
+                                        {k: v.data_ptr() if v.numel() else 0 for k, v in bufs.items()},
+                                        _native.REQ_VALUE | _native.REQ_DELTA | _native.REQ_GAMMA, ladders.data_ptr(),
+                                        work.data_ptr())
+        _native.ladder_pnl_dev(ctx, B, Q, ladders.data_ptr(), S, shocks.data_ptr(), pnl.data_ptr())
+        _native.scenario_tail_dev(ctx, B, S, pnl.data_ptr(), tail_count(level, S), var_es[0].data_ptr(), var_es[1].data_ptr(),
+                                  base_col=-1)
+        ctx.sync()
+        out = var_es.cpu().numpy()
+        return {"labels": sb.labels, "var": out[0].copy(), "es": out[1].copy()}

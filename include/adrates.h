@@ -1008,6 +1008,67 @@ int adr_credit_subbook_ladders_host(int interp_method, int K, int P, const doubl
                                     const int32_t* bucket, const double* fix_tau, const double* flt_tau, int G, int64_t B,
                                     const int64_t* sub_off, uint32_t req_mask, double* out);
 
+/*
+ * Inflation sub-book Greeks: per-desk PV, discount ladders, breakeven ladders and the discount x breakeven cross gamma of
+ * one YoY book from ONE launch chain (csrc/yoy_subbook_ladder.hip), instead of one adr_yoy_risk plus one adr_price per desk.
+ *
+ * The discount curve is an uploaded adr_curve (adr_subbook_ladders' knot tables; the _host twin takes its raw arrays as
+ * adr_subbook_ladders_host does).  The inflation curve is (infl_method, P_i, T[P_i], b[P_i]) as adr_yoy_risk takes it and
+ * the book (n swaps; fix_off[n + 1], fix_tp, fix_pay [n_fix]; cpn_off[n + 1], cpn [ADR_YOY_FIELDS][m]) as
+ * adr_yoy_scenario_subbook_pv takes it.  Sub-book b holds the swaps sub_off[b] .. sub_off[b + 1].
+ *
+ * out[B][1 + Q + Q*Q], Q = P_d + P_i (the discount pillars first, then the inflation curve's), one augmented row per
+ * sub-book in adr_price's `agg` layout, out[b] = [pv, delta'[Q], gamma'[Q][Q]]:
+ *
+ *   pv                                      fixed legs plus YoY coupons (tp > 0)
+ *   delta'[p < P_d], gamma'[p][q]           the discount ladders of the desk's cash flows, per bp and bp^2: the fixed flows and
+ *                                           each coupon's projected amount as a fixed flow at tp (adr_subbook_ladders' nodes)
+ *   delta'[P_d + k], gamma'[P_d+k][P_d+l]   breakeven delta per bp and gamma per bp^2, adr_yoy_risk's closed form: per coupon,
+ *                                           g = scale E (1 + y), g u_k and g (u_k u_l + [k == l] v_k) over its live slots
+ *   gamma'[p][P_d + k] = gamma'[P_d + k][p] d2PV / dquote_p db_k per bp^2, 1e-8 sum_a M[a][k] LJ[a][p] with M the knot-space
+ *                                           mixed sum: ONE value stored twice.  adr_price and adr_yoy_risk do not have it.
+ *
+ * so adr_ladder_pnl* with P := Q and shock rows [x_bp[P_d], (b - b0) * 1e4 [P_i]] gives the joint second-order expansion.
+ * E is the discount factor at tp as the knot tables give it, with NO division by D(0); adr_yoy_risk divides by D(0), and the
+ * two agree where D(0) == 1.0, which holds on every curve the engine builds.  pv always, delta' with ADR_REQ_DELTA or
+ * ADR_REQ_GAMMA, gamma' with ADR_REQ_GAMMA; blocks not requested are +0.0.  The entries write and do not add.
+ *
+ * A chunk (at most ADR_SCENARIO_CHUNK swaps of ONE sub-book) gives the record [pv, w[Kc], D[Kc], O[Kc], di[P_i],
+ * gi[P_i][P_i], M[P_i][Kc]] (without GAMMA [pv, w[Kc], di[P_i]]); a sub-book's records are added in the plan's order by
+ * adr_subbook_ladders' rule and the row is projected from the sums.  Contract: a sub-book's row has exactly the bits of the
+ * same entry called with B = 1 on that sub-book's swaps alone - on the host twin and on the device -, does not depend on B
+ * or on the other sub-books, and repeats bit for bit from run to run; an empty sub-book's row is +0.0 throughout; gamma' is
+ * symmetric bit for bit in its cross rows and columns.  The device part rests on the same observed ordering of the LDS adds
+ * (ds_add_f64) as adr_subbook_ladders.  On the host twin the discount block has the bits of adr_subbook_ladders_host on the
+ * batch that holds, per swap, its fixed flows followed by its coupons' amounts as fixed flows.
+ *
+ * Refused: an inflation scheme other than LINEAR_ZERO_RATES / FLAT_FWD_RATES, P_i outside 1 .. ADR_YOY_MAX_PILLARS, a curve
+ * pair whose tables for one wave (8 (3 Kc + P_i + P_i^2 + Kc P_i) bytes with GAMMA, 8 (Kc + P_i) without) do not fit the
+ * LDS (all ADR_ERR_UNSUPPORTED); GAMMA on a curve uploaded without hess, null arrays, B < 1, n < 1 (ADR_ERR_INVALID); by the
+ * blocking entry and the host twin also what they can read: pillars, rates, offsets and flows as adr_yoy_scenario_pv checks
+ * them, sub_off as adr_scenario_subbook_plan does.  _dev checks scalars only; there a swap whose leg offsets leave
+ * 0 .. n_fix / 0 .. m makes its chunk read nothing and its sub-book's row NaN, and no other row.
+ *
+ * adr_yoy_subbook_ladders: host arrays, builds the plan itself, blocks (one allocation).  _dev: device arrays and
+ * plan_dev = adr_scenario_subbook_plan(n, B, sub_off), enqueues on `stream` (NULL: the ctx's own) without allocation,
+ * synchronisation or atomics to global memory.  adr_yoy_subbook_ladders_work is its scratch in doubles,
+ * (ceil(n / 64) + 2 B) records, and leaves the rows of chunk records in *chunks when that is not NULL.
+ */
+int64_t adr_yoy_subbook_ladders_work(const adr_curve* curve, int P_i, int64_t n, int64_t B, uint32_t req_mask, int64_t* chunks);
+int adr_yoy_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, int infl_method, int P_i, const double* T, const double* b, int64_t n,
+                            int64_t n_fix, const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                            const int64_t* cpn_off, const double* cpn, int64_t B, const int64_t* sub_off, uint32_t req_mask,
+                            double* out);
+int adr_yoy_subbook_ladders_dev(adr_ctx* ctx, const adr_curve* curve, int infl_method, int P_i, const double* T_dev, const double* b_dev,
+                                int64_t n, int64_t n_fix, const int64_t* fix_off_dev, const double* fix_tp_dev,
+                                const double* fix_pay_dev, int64_t m, const int64_t* cpn_off_dev, const double* cpn_dev, int64_t B,
+                                const int64_t* plan_dev, uint32_t req_mask, double* out_dev, double* work_dev, void* stream);
+int adr_yoy_subbook_ladders_host(int interp_method, int K, int P, const double* times, const double* dfs, const double* jac,
+                                 const double* hess, int infl_method, int P_i, const double* T, const double* b, int64_t n,
+                                 int64_t n_fix, const int64_t* fix_off, const double* fix_tp, const double* fix_pay, int64_t m,
+                                 const int64_t* cpn_off, const double* cpn, int64_t B, const int64_t* sub_off, uint32_t req_mask,
+                                 double* out);
+
 /* Wait for everything enqueued on the ctx's own stream. */
 int adr_sync(adr_ctx* ctx);
 
