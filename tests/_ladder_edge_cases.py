@@ -1,13 +1,15 @@
 """The hand-made books of the sub-book ladder edge tests (tests/test_ladder_edges_host.py, CPU, and
 tests/test_gpu_ladder_edges.py, GPU): the smallest shapes at which the lookup rule, the folding rules, the owner search and the
 projection's loops can still go wrong.  Every case is ``Case(name, host curve, batch, layouts)`` with ``layouts`` a dict
-name -> sub_off; a credit case adds the spread side and G."""
+name -> sub_off; a credit case adds the spread side and G; an inflation case (`YoYCase`) holds a raw YoY book, the
+inflation curve and the request."""
 import dataclasses
 from functools import lru_cache
 from types import SimpleNamespace
 
 import numpy as np
 
+from adrates_amd import _native
 from adrates_amd.market.curves.curve_tables import build_engine_curve
 from adrates_amd.market.position.scenarios import _concat_batches
 from adrates_amd.trades import synthetic
@@ -15,8 +17,11 @@ from adrates_amd.trades.compiler import TradeBatch
 
 from . import _credit_ladder_cases as CL
 from . import _fixtures as F
+from . import _ladder_reference as R
 from . import _scenario_cases as SC
 from . import _sub_book_ladder_cases as L
+from . import _yoy_cases as YC
+from . import _yoy_ladder_cases as Y
 
 VD = L.VD
 SCHEMES = L.SCHEMES
@@ -206,6 +211,110 @@ def rates_cases(interp):
     out.append(Case("long legs", gbp_curve(interp), legs, {"desks": sub_off}))
     out.append(Case(f"{WIDE_P} pillars", gbp_curve(interp, WIDE_P), wide_book(), {"nine desks": L.offsets(WIDE_DESKS)}))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------ inflation
+@dataclasses.dataclass
+class YoYCase:
+    name: str
+    host: object             # the discount curve: times, dfs, jac, hess
+    infl: tuple              # (inflation scheme, T, b)
+    book: object             # _yoy_ladder_cases.Book: fixed, coupons, names
+    layouts: dict            # name -> sub_off
+    want_gamma: bool = True
+
+
+YOY_LOOKUP_DATES = np.concatenate((SC.LOOKUP_DATES, [1.0 + 5e-11, -0.25, 0.0]))      # ... beside the repeated knot, negative, zero
+ONE_PILLAR = (np.array([3.0]), np.array([0.03]))
+
+
+def each_and_all(n):
+    return {"each": np.arange(n + 1, dtype=np.int64), "all": np.array([0, n], dtype=np.int64)}
+
+
+def yoy_knot_book():
+    """Every swap of `_yoy_cases.knot_swaps` (each coupon paid at ``te``) with a fixed flow on every second swap."""
+    return Y.Book([(name, N, cpns, [(1.25 + 0.5 * i, 0.02 * N)] if i % 2 else []) for i, (name, N, cpns) in enumerate(YC.knot_swaps())])
+
+
+def yoy_lookup_book():
+    """Per lookup date ``tp`` one four-knot coupon (ts, te) = (1.5, 12.0) on T5 and one fixed flow, both paid at ``tp``."""
+    return Y.Book([(f"tp = {tp!r}", 1e6, [(tp, 1.5, 12.0, 1e6 * (-1.0) ** i, 0.002)], [(tp, 2e4)]) for i, tp in enumerate(YOY_LOOKUP_DATES)])
+
+
+def twin_amounts(infl, coupons):
+    """The amounts as the twin's `describe` forms them (they do not depend on the discount curve)."""
+    return _native.yoy_risk_host((YC.LF, np.array([0.0, 1.0]), np.array([1.0, 1.0])), infl, YC.raw_book([coupons]), 0)["amount"]
+
+
+def yoy_amount_book(infl):
+    """The branches of a coupon's amount; the first two swaps depend on the inflation curve through the twin's amounts."""
+    c = YC._cpn
+    y = float(twin_amounts(infl, [c(2.5, 3.5, 1.0)])[0])                       # (1 + y) - 1 in float64
+    far = c(1.5, 12.0, 1e6, 0.002)
+    return Y.Book([
+        ("amount exactly 0.0, slots live", 1e6, [c(2.5, 3.5, 1e6, -y)], []),
+        ("a fixed flow cancels the coupon's amount", 1e6, [far], [(12.0, -float(twin_amounts(infl, [far])[0]))]),
+        ("scale == 0.0", 1e6, [c(2.5, 3.5, 0.0, 0.001)], [(3.5, 1e4)]),
+        ("pay == 0.0", 1e6, [c(1.5, 3.0, -1e6, 0.001)], [(2.0, 0.0)]),
+        ("tp == 0 on both legs", 1e6, [(0.0, -1.0, 0.0, 1e6, 0.001)], [(0.0, 5e5)]),
+        ("tp < 0 on both legs", 1e6, [(-0.6, -1.6, -0.6, 1e6, 0.002)], [(-0.25, 5e5)]),
+    ])
+
+
+YOY_CHUNK_SIZES = (64, 65, 0, 2, 1, 2, 0)
+
+
+def yoy_chunk_book():
+    """Desks of 64 and of 65 one-coupon swaps cycling the singles of `_yoy_cases.knot_swaps`, an empty desk, the two long
+    swaps of `_yoy_ladder_cases.edge_book` (70 coupons; 70 fixed flows), a swap of 129 coupons, the pair that cancels and
+    an empty desk last."""
+    singles = YC.knot_swaps()[:11]
+    cycle = lambda n, at: [(f"{at + i}: {singles[(at + i) % 11][0]}",) + tuple(singles[(at + i) % 11][1:]) + ([],) for i in range(n)]
+    edge, _ = Y.edge_book(1.0)
+    fix_off, fix_tp, fix_pay = edge.fixed
+
+    def pick(name):                                          # the swap of that name with its fixed flows
+        i = next(i for i in range(edge.n) if edge.names[i].startswith(name))
+        f = slice(int(fix_off[i]), int(fix_off[i + 1]))
+        return edge.names[i], edge.notional[i], edge.rows[i], list(zip(fix_tp[f], fix_pay[f]))
+    long_legs = [pick("70 monthly coupons"), pick("70 fixed flows")]
+    pair = [pick("a swap"), pick("and its opposite")]
+    return Y.Book(cycle(64, 0) + cycle(65, 64) + long_legs + [("129 coupons", 1e6, YC.leg(129, 0.31, 1e6 / 12.0, 0.001), [])] + pair)
+
+
+@lru_cache(maxsize=None)
+def yoy_cases(interp):
+    """The inflation cases of one discount scheme; the inflation scheme is both in the first case and alternates after."""
+    LZ, FF = YC.LZ, YC.FF
+    gbp = gbp_curve(interp)
+    knots = yoy_knot_book()
+    out = [YoYCase(f"inflation knots, {YC.NAMES[im]}", gbp, (im, YC.T5, YC.B5), knots, each_and_all(knots.n)) for im in (LZ, FF)]
+    one = Y.Book([s + ([],) for s in YC.single_pillar_swaps()])
+    out.append(YoYCase("one pillar", gbp, (FF,) + ONE_PILLAR, one, each_and_all(one.n)))
+    looks = yoy_lookup_book()
+    for name, times, im in (("discount lookups", SC.LOOKUP_TIMES, LZ), ("discount lookups, a knot three times", LOOKUP_TIMES_TRIPLE, FF)):
+        out.append(YoYCase(name, lookup_curve(times), (im, YC.T5, YC.B5), looks, lookup_layouts(looks.n)))
+    amounts = yoy_amount_book((LZ, YC.T5, YC.B5))
+    out.append(YoYCase("amount edges", gbp, (LZ, YC.T5, YC.B5), amounts, each_and_all(amounts.n)))
+    out.append(YoYCase("chunks", gbp, (FF, YC.T5, YC.B5), yoy_chunk_book(), {"desks": L.offsets(YOY_CHUNK_SIZES)}))
+    wide = Y.small_book()
+    for P_i, im in ((5, LZ), (64, FF)):
+        out.append(YoYCase(f"{WIDE_P} pillars, P_i = {P_i}", gbp_curve(interp, WIDE_P), Y.infl_curve(P_i, im), wide,
+                           {"nine desks": L.offsets(WIDE_DESKS)}))
+    out.append(YoYCase("delta only", gbp, (LZ, YC.T5, YC.B5), knots, each_and_all(knots.n), want_gamma=False))
+    return out
+
+
+def yoy_entry(interp, c, sub_off, ctx=None, dc=None):
+    """The host twin's (or, with a ctx and an uploaded curve, the device's) rows of an inflation case."""
+    return Y.Entries(interp.value, c.host, ctx, dc)(c.infl, c.book.fixed, c.book.coupons, sub_off, want_gamma=c.want_gamma)
+
+
+def check_yoy_rows(got, ref, c, what):
+    """The share of the bound over pv, delta and gamma, the layout, and +0.0 throughout a gamma that was not asked for."""
+    Y.check_layout(got, c.host.jac.shape[1], c.infl[1].size, want_gamma=c.want_gamma)
+    return R.worst_share(got, ref, R.RATES_BLOCKS if c.want_gamma else ("pv", "delta"), what=what)
 
 
 # --------------------------------------------------------------------------------------------------------------- credit

@@ -1,6 +1,6 @@
-"""The plain reference of the sub-book ladders (adr_subbook_ladders*, adr_credit_subbook_ladders*) and the bound the kernels,
-their host twins and the C oracle are held to, entry by entry (tests/test_ladder_edges_host.py, CPU, and
-tests/test_gpu_ladder_edges.py, GPU).  It shares no code with the kernels or with oracle/port.c.
+"""The plain reference of the sub-book ladders (adr_subbook_ladders*, adr_credit_subbook_ladders*, adr_yoy_subbook_ladders*)
+and the bound the kernels, their host twins and the C oracle are held to, entry by entry (tests/test_ladder_edges_host.py,
+CPU, and tests/test_gpu_ladder_edges.py, GPU).  It shares no code with the kernels or with oracle/port.c.
 
 The operation.  The inputs are what `DeviceCurve` and the `_host` entries take, each an exact binary number: the scheme,
 the knot times x_k, the knot discount factors d_k, ``jac [K, P]`` = J, ``hess [K, P, P]`` = C, a `TradeBatch`, ``sub_off`` and,
@@ -62,6 +62,41 @@ Kc is the compact grid's length, read off the knot times: the first and the last
 (`compact_count`).  `bound_k` adds these and rounds the two conditioned terms up to an integer; the
 same k is used for every element of a desk (pv and delta have fewer roundings than gamma).  cond and zt are read off the
 inputs by the reference: the largest sum of |weight L_k| over the desk's terms and the largest |z tau|.
+
+Inflation (adr_yoy_subbook_ladders*, `yoy_reference`).  The inputs add the inflation scheme, the pillar
+times T_k and the breakeven rates b_k, fixed flows (tp, pay) and coupons (tp, ts, te, scale, spread).  The inflation nodes are
+L_0 = 0 at x = 0 and L_k = T_k ln(1 + b_k); a coupon has ln(1 + y) = sum of w L_k over the slots of te (+w) and of ts (-w),
+with the weights of `si::log_weights` on `_lookup_plan`'s float64 decisions on x = [0, T]: a snap 1; FLAT_FWD 1 - w and w;
+LINEAR_ZERO t (1 - w) / max(x_a, 1e-15) and t w / x_b; a held end t / max(x_k, 1e-15) or 1; node 0 is left out.  It pays
+amount = scale ((1 + y) - 1 + spread) at tp and counts when tp > 0, a fixed flow when tp > 0.  On the discount side both are
+terms c D(tp) of the sums above (no division by D(0): the kernels have none), which gives pv, delta[:P_d] and
+gamma[:P_d, :P_d].  On the inflation side, with g = scale (1 + y) D(tp), u_k = (sum of the slots' w at k) T_k / (1 + b_k)
+and v_k = -(that sum) T_k / (1 + b_k)^2:
+  delta[P_d + k] = 1e-4 sum g u_k,      gamma[P_d + k][P_d + l] = 1e-8 sum g (u_k u_l + [k == l] v_k),
+and row k of the cross block is the projected delta, at 1e-8, of the first-order sums of the terms scale (1 + y) u_k D(tp)
+(as credit's cross_gamma); both mirror positions are compared.  Gross takes the terms as written: the amount counts as
+|scale| ((1 + y) + 1 + |spread|), a slot sum as sum |w| - before the merge of two slots on one knot, so where ts and te share a
+knot the difference we.w - ws.w is cancellation -, u_k u_l and v_k separately, D(tp) and the tables as above.
+The roundings the inflation side adds to a node's count above, as yoy_nodes.hpp and yoy_subbook_ladder.hip perform them
+(e_w of the INFLATION scheme, W_k = sum |w| at knot k):
+  make_node 1 + b_k (1): an ABSOLUTE error of one unit of ln(1 + b_k), so T_k units of L_k; log (2) and the product (1):
+            3 |L_k|.  L' = T / (1 + b): 2;  L'' = -(T / ((1 + b) (1 + b))): 4
+  describe  a coefficient: the weight (e_w) and the merge add (1), of W_k;  lnr = sum c_k L_k: the coefficient
+            (e_w + 1) W_k |L_k|, the node W_k (T_k + 3 |L_k|), the product (1) and at most three adds (3) of
+            sum W_k |L_k|: an absolute error of lnr, hence a relative one of 1 + y
+                                                           cond_i = max over the coupons of sum W_k (T_k + (e_w + 8) |L_k|)
+            exp                                                                                                        2
+            the amount: (1 + y) - 1, + spread, scale x: 3 roundings of |scale| ((1 + y) + 1 + |spread|); less than what
+            follows for a breakeven gamma entry, and one k serves the desk
+            g = (scale 1.0) (1 + y) on the unit grid (1), times E = D(tp) in `add_coupon` (1; E itself: the node above)     2
+            u = c L': e_w + 1, 2 and the product: e_w + 4;  v = c L'': e_w + 1, 4 and the product: e_w + 6
+  gamma_term  u_k u_l: 2 (e_w + 4) + 1 of its gross;  v_k: e_w + 6 of its;  the add (1)                        2 e_w + 10
+  add_coupon  g term (1); g u and (scale (1 + y)) u, s t.wa have fewer roundings than the line above                    1
+  sums, cross_sum / delta_step, the tables and 1e-4 / 1e-8: the lines above (a desk's coupons and fixed flows are its
+            n_terms; the breakeven blocks are scaled by one product each)
+so `bound_k(..., infl=(scheme, cond_i))` adds ceil(cond_i) + 2 e_w + 15.  cond_i is large beside the rest - a coupon far out
+on the curve has sum W_k T_k of 40 and more, because one rounding of 1 + b_k moves L_k by T_k units whatever ln(1 + b_k) is -
+and k runs from about 70 to 800 on the edge books.  Nothing in it was fitted: the host twin's worst share is 0.12.
 """
 import math
 
@@ -82,9 +117,11 @@ def compact_count(times):
     return int(np.count_nonzero(first | last))
 
 
-def bound_k(method, n_terms, K, cond, zt=None):
+def bound_k(method, n_terms, K, cond, zt=None, infl=None):
     """k of the module docstring: ``n_terms`` unfolded live terms of the desk, ``K`` = Kc knots, ``cond`` the largest
-    sum |weight L_k| of a term, ``zt`` the largest |z tau| (credit; None for the rates ladders)."""
+    sum |weight L_k| of a term, ``zt`` the largest |z tau| (credit; None for the rates ladders), ``infl`` =
+    (inflation scheme, cond_i) with cond_i the largest  sum |w| (T_k + (e_w + 8) |L_k|)  over a coupon's inflation slots
+    (inflation; None otherwise)."""
     e_w = _WEIGHT_ROUNDINGS[int(method)]
     amount, exp_ulp, tables_project, scale = 5, 2, 5, 2
     if int(method) == LINEAR_FWD:
@@ -95,6 +132,8 @@ def bound_k(method, n_terms, K, cond, zt=None):
     if zt is not None:
         node += math.ceil(zt) + 5
         sums += 7
+    if infl is not None:
+        node += math.ceil(infl[1]) + 2 + 2 + (2 * _WEIGHT_ROUNDINGS[int(infl[0])] + 10) + 1
     return node + sums + tables_project + 3 * ((K + 7) // 8) + 7 + scale
 
 
@@ -247,8 +286,10 @@ class _Sums:
         self.g, self.g_abs, self.H, self.H_abs = {}, {}, {}, {}
         self.n, self.cond = 0, mpf(0)
 
-    def add(self, t, c):
-        if c == 0:
+    def add(self, t, c, gross=None):
+        """The term ``c D(t)``; ``gross``: what |c| counts as where c was formed by subtractions (default |c|)."""
+        a = abs(c) if gross is None else gross
+        if c == 0 and a == 0:
             return
         D, knots, pieces, cond = self.cv.date(t)
         self.n += 1
@@ -256,25 +297,25 @@ class _Sums:
         bump = lambda table, key, v: table.__setitem__(key, table.get(key, mpf(0)) + v)
         if pieces is not None:                              # LINEAR_FWD_RATES: two single-knot amounts, weight 1
             for k, p in pieces:
-                v = c * p
+                v, va = c * p, a * abs(p)
                 self.pv += v
-                self.pv_abs += abs(v)
+                self.pv_abs += va
                 bump(self.g, k, v)
-                bump(self.g_abs, k, abs(v))
+                bump(self.g_abs, k, va)
                 if self.second:
                     bump(self.H, (k, k), v)
-                    bump(self.H_abs, (k, k), abs(v))
+                    bump(self.H_abs, (k, k), va)
             return
-        om = c * D
+        om, oa = c * D, a * D
         self.pv += om
-        self.pv_abs += abs(om)
+        self.pv_abs += oa
         for k, wk in knots:
             bump(self.g, k, om * wk)
-            bump(self.g_abs, k, abs(om * wk))
+            bump(self.g_abs, k, oa * abs(wk))
             if self.second:
                 for l, wl in knots:
                     bump(self.H, (k, l), om * wk * wl)
-                    bump(self.H_abs, (k, l), abs(om * wk * wl))
+                    bump(self.H_abs, (k, l), oa * abs(wk * wl))
 
     # -------------------------------------------------------------------------------------------------- projection
     def _project(self, g, H, J, C, sign, second):
@@ -427,6 +468,127 @@ def credit_reference(method, host, case, G, sub_off):
                           "k": bound_k(method, at.n, compact_count(cv.x), float(at.cond), float(zt))})
         return desks
     return _cached("credit", method, host, batch, (case.z, case.bucket, case.fix_tau, case.flt_tau, np.array([G]), sub_off), build)
+
+
+# ------------------------------------------------------------------------------------------------------------ inflation
+def _infl_slots(x, t, im):
+    """``[(k, weight)]`` of ln I(t) on the inflation nodes x = [0, T] (`si::log_weights` on `_lookup_plan`'s float64
+    decisions, the weights in mpmath); node 0 has L = 0 and is left out, as the code drops it."""
+    plan = _lookup_plan(x, t, im)
+    held = lambda k: _mp(t) / _mp(max(float(x[k]), 1e-15)) if im == LINEAR_ZERO else mpf(1)
+    if plan[0] == "snap":
+        slots = [(plan[1], mpf(1))]
+    elif plan[0] == "flat":
+        slots = [(plan[1], held(plan[1]))]
+    else:
+        _, a, b, w = plan
+        w = _mp(w)
+        if im == LINEAR_ZERO:
+            slots = [(a, _mp(t) * (1 - w) / _mp(max(float(x[a]), 1e-15))), (b, _mp(t) * w / _mp(float(x[b])))]
+        else:
+            slots = [(a, 1 - w), (b, w)]
+    return [(k, wk) for k, wk in slots if k > 0 and wk != 0]
+
+
+def _place(shape, parts, s):
+    """A Block of ``shape`` (zeros elsewhere) from ``(index, Block)`` parts of scale ``s`` on their lowest exponent."""
+    lo = min((b.E for _, b in parts), default=0)
+    V, A = np.empty(shape, dtype=object), np.empty(shape, dtype=object)
+    V.fill(0)
+    A.fill(0)
+    for idx, b in parts:
+        assert b.s == s
+        V[idx] = b.V * (1 << (b.E - lo))
+        A[idx] = b.A * (1 << (b.E - lo))
+    return Block(V, A, lo, s)
+
+
+def _mp_block(values, gross, shape, s):
+    """A Block of ``shape`` from mpf values and their gross, exactly."""
+    (v, ev), (a, ea) = _mp_ints(values), _mp_ints(gross)
+    return Block.of((v.reshape(shape), ev), (a.reshape(shape), ea), s)
+
+
+def yoy_reference(method, host, infl, book, sub_off):
+    """Per desk ``{"pv", "delta" [Q], "gamma" [Q, Q]: Block, "k", "n_terms"}`` on Q = P_d + P_i, the discount pillars first
+    (module docstring, "Inflation").  ``infl`` = (scheme, T, b); ``book``: ``fixed`` = (fix_off, fix_tp, fix_pay) and
+    ``coupons`` = cpn_off, tp, ts, te, scale, spread as the entries take them.  Built once per process for the same inputs."""
+    sub_off = np.asarray(sub_off, dtype=np.int64)
+    im, T, b = int(infl[0]), np.ascontiguousarray(infl[1], dtype=np.float64), np.ascontiguousarray(infl[2], dtype=np.float64)
+    fix_off, fix_tp, fix_pay = (np.asarray(a) for a in book.fixed)
+    cp = book.coupons
+
+    def build():
+        mp.dps = 60
+        cv = _Curve(method, host.times, host.dfs, host.jac, host.hess)
+        tables = _tables(cv)
+        P, Pi = cv.P, T.size
+        x = np.concatenate(([0.0], T))
+        Tk = [mpf(0)] + [_mp(t) for t in T]
+        ob = [mpf(1)] + [1 + _mp(v) for v in b]
+        L = [tk * mp.log(o) for tk, o in zip(Tk, ob)]
+        e_wi = _WEIGHT_ROUNDINGS[im]
+        desks = []
+        for lo, hi in zip(sub_off[:-1], sub_off[1:]):
+            disc = _Sums(cv, True)
+            cross = {}
+            bd, bd_abs, bg, bg_abs = {}, {}, {}, {}
+            bump = lambda table, key, v: table.__setitem__(key, table.get(key, mpf(0)) + v)
+            n_terms, cond, cond_i = 0, mpf(0), mpf(0)
+            for i in range(int(lo), int(hi)):
+                for j in range(int(fix_off[i]), int(fix_off[i + 1])):
+                    if float(fix_tp[j]) > 0.0 and float(fix_pay[j]) != 0.0:
+                        disc.add(float(fix_tp[j]), _mp(fix_pay[j]))
+                        n_terms += 1
+                for j in range(int(cp["cpn_off"][i]), int(cp["cpn_off"][i + 1])):
+                    tp, ts, te = float(cp["tp"][j]), float(cp["ts"][j]), float(cp["te"][j])
+                    if not tp > 0.0:
+                        continue
+                    n_terms += 1
+                    scale, spread = _mp(cp["scale"][j]), _mp(cp["spread"][j])
+                    coef, W = {}, {}
+                    for k, wk in _infl_slots(x, te, im) + [(k, -wk) for k, wk in _infl_slots(x, ts, im)]:
+                        bump(coef, k, wk)
+                        bump(W, k, abs(wk))
+                    one_y = mp.exp(sum((coef[k] * L[k] for k in coef), mpf(0)))
+                    cond_i = max(cond_i, sum((W[k] * (Tk[k] + (e_wi + 8) * abs(L[k])) for k in W), mpf(0)))
+                    disc.add(tp, scale * (one_y - 1 + spread), gross=abs(scale) * (one_y + 1 + abs(spread)))
+                    D, _, pieces, cd = cv.date(tp)
+                    cond = max(cond, cd)
+                    Da = D if pieces is None else sum((abs(p) for _, p in pieces), mpf(0))
+                    g, ga = scale * one_y * D, abs(scale) * one_y * Da
+                    u = {k: coef[k] * Tk[k] / ob[k] for k in coef}
+                    ua = {k: W[k] * Tk[k] / ob[k] for k in coef}
+                    for k in coef:
+                        bump(bd, k, g * u[k])
+                        bump(bd_abs, k, ga * ua[k])
+                        for l in coef:
+                            bump(bg, (k, l), g * u[k] * u[l])
+                            bump(bg_abs, (k, l), ga * ua[k] * ua[l])
+                        bump(bg, (k, k), -g * u[k] / ob[k])                 # v_k = -(sum w) T_k / (1 + b_k)^2
+                        bump(bg_abs, (k, k), ga * ua[k] / ob[k])
+                        if k not in cross:
+                            cross[k] = _Sums(cv, False)
+                        cross[k].add(tp, scale * one_y * u[k], gross=abs(scale) * one_y * ua[k])
+            pv, d_disc, g_disc = disc.blocks(tables)
+            cond = max([cond, disc.cond] + [c.cond for c in cross.values()])
+            Q = P + Pi
+            flat = lambda table, keys: [table.get(key, mpf(0)) for key in keys]
+            ks, kl = list(range(1, Pi + 1)), [(k, l) for k in range(1, Pi + 1) for l in range(1, Pi + 1)]
+            delta = _place((Q,), [(slice(0, P), d_disc), (slice(P, Q), _mp_block(flat(bd, ks), flat(bd_abs, ks), (Pi,), 4))], 4)
+            parts = [((slice(0, P), slice(0, P)), g_disc),
+                     ((slice(P, Q), slice(P, Q)), _mp_block(flat(bg, kl), flat(bg_abs, kl), (Pi, Pi), 8))]
+            for k, sums in cross.items():
+                row = sums.blocks(tables, delta_scale=8)[1]
+                parts += [((P + k - 1, slice(0, P)), row), ((slice(0, P), P + k - 1), row)]
+            desks.append({"pv": pv, "delta": delta, "gamma": _place((Q, Q), parts, 8), "n_terms": n_terms,
+                          "k": bound_k(method, n_terms, compact_count(cv.x), float(cond), infl=(im, float(cond_i)))})
+        return desks
+    key = ("yoy", int(method), im) + _key(host.times, host.dfs, host.jac, host.hess, T, b, fix_off, fix_tp, fix_pay,
+                                          *[cp[f] for f in ("cpn_off", "tp", "ts", "te", "scale", "spread")], sub_off)
+    if key not in _CACHE:
+        _CACHE[key] = build()
+    return _CACHE[key]
 
 
 def _stack(blocks, shape):
