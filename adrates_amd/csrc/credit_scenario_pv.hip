@@ -172,8 +172,9 @@ __host__ __device__ inline void apply_slot(const Slot& s, bool weighted, const T
     }
 }
 
+// + 0.0: as scenario_pv.hip's - the PV of a trade without a live flow is +0.0 whatever its signs.
 __host__ __device__ inline double trade_pv(const Acc& a, double fix_sign, double flt_sign, double notional) {
-    return fix_sign * a.fix + (flt_sign * notional) * a.flt;
+    return (fix_sign * a.fix + (flt_sign * notional) * a.flt) + 0.0;
 }
 
 // A leg's range against the length of its spread-time array; false: nothing of the trade is read.

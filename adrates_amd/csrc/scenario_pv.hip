@@ -134,8 +134,10 @@ __host__ __device__ inline void apply_slot(const Slot& s, bool weighted, const T
     }
 }
 
+// + 0.0: a trade without a live flow has two zero sums, and with fix_sign = -1 and flt_sign * notional < 0 both products are
+// -0.0; the PV of nothing is +0.0.  Every other value passes through the add unchanged.
 __host__ __device__ inline double trade_pv(const Acc& a, double fix_sign, double flt_sign, double notional) {
-    return fix_sign * a.fix + (flt_sign * notional) * a.flt;
+    return (fix_sign * a.fix + (flt_sign * notional) * a.flt) + 0.0;
 }
 
 // ------------------------------------------------------------------------------------------------------------ device
