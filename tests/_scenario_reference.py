@@ -63,13 +63,17 @@ _WEIGHT_ROUNDINGS = {FLAT_FWD: 1, LINEAR_FWD: 0, LINEAR_ZERO: 3}
 DPS = 60
 
 
+def date_roundings(method, cond):
+    """e_D of the module docstring: the units of one D(t) whose conditioning is ``cond``."""
+    if int(method) == LINEAR_FWD:
+        return math.ceil(2 * cond) + 1
+    return math.ceil(cond * (_WEIGHT_ROUNDINGS[int(method)] + 4)) + 2
+
+
 def bound_k(method, n_terms, cond, zt=None):
     """k of the module docstring: ``n_terms`` live terms of the trade, ``cond`` the largest conditioning of one of its dates
     on the scenario's row, ``zt`` the largest |x tau| (credit; None for the rates entries)."""
-    if int(method) == LINEAR_FWD:
-        e_d = math.ceil(2 * cond) + 1
-    else:
-        e_d = math.ceil(cond * (_WEIGHT_ROUNDINGS[int(method)] + 4)) + 2
+    e_d = date_roundings(method, cond)
     k = 3 * e_d + 6 + n_terms + 1
     if zt is not None:
         k += math.ceil(3 * zt + cond) + 3
