@@ -95,12 +95,17 @@ struct CurveLds {
 // compact tables.  LINEAR_FWD_RATES is linear in the knot DFs themselves, D = (1-w) d_a + w d_b: its log-gradient
 // is the convex combination rho_a LJ[ka] + rho_b LJ[kb] with rho_a = (1-w) d_a / D, so the same node machinery
 // applies with (ba, bb) = (rho_a, rho_b), plus a rank-one correction rho_a rho_b (LJ[ka] - LJ[kb])(...)^T in the
-// Hessian of ln D (`kappa` = rho_a rho_b; 0 for the log-linear schemes).
+// Hessian of ln D (`kappa` = rho_a rho_b; 0 for the log-linear schemes).  That form is for the RATIO nodes, which need
+// ln D.  A plain node a D(t) is the two single-knot amounts a (1 - w) d_a and a w d_b (`pa`, `pb`: the knots' parts of D),
+// each with weight 1 on its own knot, and is walked as such (`lindf_plain` in the kernel): in the rho form the cross
+// products rho_a rho_b LJ[ka] LJ[kb]^T of v v^T and of the correction cancel only up to rounding, which left rounding
+// dust on gamma entries no term reaches (a date between two short-end knots that move different pillars).
 struct Lookup {
     int ka, kb;
     double ba, bb;
     double ln_d;     // ln D(t)
     double kappa;
+    double pa, pb;   // LINEAR_FWD_RATES, two knots: (1 - w) d_a and w d_b (else unset: D = exp(ln_d) on knot ka)
 };
 
 // InterpolatorAd.simple_interpolate for one time (interpolator_ad.py:210-243) in weight form.
@@ -125,6 +130,7 @@ __device__ __forceinline__ Lookup curve_lookup(const CurveLds& c, double t) {
     }
     Lookup r;
     r.kappa = 0.0;
+    r.pa = r.pb = 0.0;
     if (best_dist < 1e-10) {            // exact grid point: that knot's DF, gradient to that knot only
         r.ka = c.compact_of[best]; r.kb = 0; r.ba = 1.0; r.bb = 0.0;
         r.ln_d = c.log_df[r.ka];
@@ -150,6 +156,8 @@ __device__ __forceinline__ Lookup curve_lookup(const CurveLds& c, double t) {
     if (c.method == 2) {                 // LINEAR_FWD_RATES (interpolator_ad.py:234-235)
         const double da = exp(c.log_df[r.ka]), db = exp(c.log_df[r.kb]);
         const double d = da + w * (db - da);
+        r.pa = (1.0 - w) * da;
+        r.pb = w * db;
         r.bb = w * db / d;
         r.ba = 1.0 - r.bb;
         r.kappa = r.ba * r.bb;
@@ -578,6 +586,22 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
     double* stage = s_stage + wave * kConvStage;
     // LDS path: the knot words handed to add_nodes carry the knot's class in their high half
     auto tag = [&](int k) { return LDSLC ? (k | (static_cast<int>(s_class[k]) << 16)) : k; };
+    // LINEAR_FWD_RATES, a plain node of amount a (see `Lookup`): the two knots' amounts ...
+    auto lindf_amounts = [&](const Lookup& q, double a, double (&om)[2]) {
+        const bool two = q.bb != 0.0;
+        om[0] = a * (two ? q.pa : exp(q.ln_d));
+        om[1] = two ? a * q.pb : 0.0;
+    };
+    // ... and their walk as two single-knot nodes (weight 1 on the knot; `cf`: the knots' convexity coefficients - the
+    // amounts, unless a ratio node has taken them over)
+    auto lindf_plain = [&](const int (&k)[2], const double (&om)[2], const double (&cf)[2], Ladders<GAMMA, WIDE>& acc) {
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const int k1[2] = {tag(k[side]), tag(0)};
+            const double b1[2] = {1.0, 0.0}, cf1[2] = {cf[side], 0.0};
+            add_nodes_any<2, DELTA, GAMMA, true, LDSLC, WIDE>(__ballot(om[side] != 0.0), k1, b1, om[side], c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf1, conv);
+        }
+    };
     // ... and the flat convexity sums are scattered to this lane's 4x4 block once per trade: position of each of
     // the block's 16 entries in a packed row (the row's trailing zero for pairs outside the core), two per register
     int conv_pos[(LDSLC && GAMMA) ? kGammaPerLane / 2 : 1];
@@ -646,36 +670,47 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
             const bool pay_on = in && a_pay != 0.0;
             kp[0] = kp[1] = 0; bp[0] = bp[1] = 0.0;
             Lookup qpay;
-            qpay.ka = qpay.kb = 0; qpay.ba = qpay.bb = 0.0; qpay.ln_d = 0.0; qpay.kappa = 0.0;
+            qpay.ka = qpay.kb = 0; qpay.ba = qpay.bb = 0.0; qpay.ln_d = 0.0; qpay.kappa = 0.0; qpay.pa = qpay.pb = 0.0;
             if (pay_on || (valid && ratio)) qpay = curve_lookup(c, tp);
+            double omp2[2] = {0.0, 0.0};           // LINEAR_FWD_RATES: the two knots' amounts
             if (pay_on) {
                 kp[0] = qpay.ka; kp[1] = qpay.kb; bp[0] = qpay.ba; bp[1] = qpay.bb;
-                omega_p = a_pay * exp(linear_df ? qpay.ln_d : fma(qpay.ba, c.log_df[qpay.ka], qpay.bb * c.log_df[qpay.kb]));
+                if constexpr (linear_df) {
+                    lindf_amounts(qpay, a_pay, omp2);
+                    omega_p = omp2[0] + omp2[1];
+                } else {
+                    omega_p = a_pay * exp(fma(qpay.ba, c.log_df[qpay.ka], qpay.bb * c.log_df[qpay.kb]));
+                }
                 acc.pv += omega_p;
             }
-            cfp[0] = omega_p * bp[0]; cfp[1] = omega_p * bp[1];
+            if constexpr (linear_df) { cfp[0] = omp2[0]; cfp[1] = omp2[1]; }
+            else { cfp[0] = omega_p * bp[0]; cfp[1] = omega_p * bp[1]; }
             // a node on the value-time knot alone (t = 0: D = 1, no sensitivity - build_curve_tables checks
             // that) adds to the PV only; the cross-currency assembly pays every weighted coupon there
             const bool pay_node = pay_on && !(kp[0] == knot0 && bp[1] == 0.0);
             {   // unmerged start nodes
                 int k[2]; double b[2]; double omega = 0.0;
                 k[0] = k[1] = 0; b[0] = b[1] = 0.0;
-                double kap = 0.0;
+                double om2[2] = {0.0, 0.0};
                 if (own_start) {
                     const Lookup q = curve_lookup(c, ts);
-                    k[0] = q.ka; k[1] = q.kb; b[0] = q.ba; b[1] = q.bb; kap = q.kappa;
-                    omega = sl * Nw * exp(linear_df ? q.ln_d : fma(q.ba, c.log_df[q.ka], q.bb * c.log_df[q.kb]));
+                    k[0] = q.ka; k[1] = q.kb; b[0] = q.ba; b[1] = q.bb;
+                    if constexpr (linear_df) {
+                        lindf_amounts(q, sl * Nw, om2);
+                        omega = om2[0] + om2[1];
+                    } else {
+                        omega = sl * Nw * exp(fma(q.ba, c.log_df[q.ka], q.bb * c.log_df[q.kb]));
+                    }
                     acc.pv += omega;
                 }
-                { int kt_[2];
+                if constexpr (linear_df) {
+                    lindf_plain(k, om2, om2, acc);
+                } else {
+                    int kt_[2];
 #pragma unroll
-                  for (int i_ = 0; i_ < 2; ++i_) kt_[i_] = tag(k[i_]);
-                  if constexpr (FUSE) {
-                      const double kw1[1] = {omega * kap};
-                      add_nodes<2, DELTA, GAMMA, false, LDSLC, 1>(__ballot(own_start), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, b, conv, kw1, stage);
-                  } else
-                  add_nodes_any<2, DELTA, GAMMA, false, LDSLC, WIDE>(__ballot(own_start), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, b, conv); }
-                if constexpr (linear_df && !FUSE) add_df_correction<GAMMA, LDSLC, WIDE>(own_start, k[0], k[1], omega * kap, c, lc_lanes, lc_block_mask, vbuf, lane, acc);
+                    for (int i_ = 0; i_ < 2; ++i_) kt_[i_] = tag(k[i_]);
+                    add_nodes_any<2, DELTA, GAMMA, false, LDSLC, WIDE>(__ballot(own_start), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, b, conv);
+                }
             }
             const bool own_ratio = RATIO && valid && ratio;
             if (RATIO && __ballot(own_ratio)) {   // payment lag: N D(ts) D(tp) / D(te) keeps all three lookups
@@ -777,15 +812,15 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
                         add_df_correction<GAMMA, LDSLC, WIDE>(own_ratio, kc[2 * q], kc[2 * q + 1], omega * kap[q], c, lc_lanes, lc_block_mask, vbuf, lane, acc);
                 }
             }
-            { int kt_[2];
+            if constexpr (linear_df) {
+                const double omn[2] = {pay_node ? omp2[0] : 0.0, pay_node ? omp2[1] : 0.0};
+                lindf_plain(kp, omn, cfp, acc);
+            } else {
+                int kt_[2];
 #pragma unroll
-              for (int i_ = 0; i_ < 2; ++i_) kt_[i_] = tag(kp[i_]);
-              if constexpr (FUSE) {
-                  const double kw1[1] = {omega_p * qpay.kappa};
-                  add_nodes<2, DELTA, GAMMA, true, LDSLC, 1>(__ballot(pay_node), kt_, bp, omega_p, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cfp, conv, kw1, stage);
-              } else
-              add_nodes_any<2, DELTA, GAMMA, true, LDSLC, WIDE>(__ballot(pay_node), kt_, bp, omega_p, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cfp, conv); }
-            if constexpr (linear_df && !FUSE) add_df_correction<GAMMA, LDSLC, WIDE>(pay_node, kp[0], kp[1], omega_p * qpay.kappa, c, lc_lanes, lc_block_mask, vbuf, lane, acc);
+                for (int i_ = 0; i_ < 2; ++i_) kt_[i_] = tag(kp[i_]);
+                add_nodes_any<2, DELTA, GAMMA, true, LDSLC, WIDE>(__ballot(pay_node), kt_, bp, omega_p, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cfp, conv);
+            }
         }
         // ---------------------------------------------------------------- fixed coupons not merged above
         for (int base = 0; base < n_fix; base += 64) {
@@ -801,22 +836,26 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
             }
             int k[2]; double b[2]; double omega = 0.0;
             k[0] = k[1] = 0; b[0] = b[1] = 0.0;
-            double kap = 0.0;
+            double om2[2] = {0.0, 0.0};
             if (on) {
                 const Lookup q = curve_lookup(c, tp);
-                k[0] = q.ka; k[1] = q.kb; b[0] = q.ba; b[1] = q.bb; kap = q.kappa;
-                omega = a * exp(linear_df ? q.ln_d : fma(q.ba, c.log_df[q.ka], q.bb * c.log_df[q.kb]));
+                k[0] = q.ka; k[1] = q.kb; b[0] = q.ba; b[1] = q.bb;
+                if constexpr (linear_df) {
+                    lindf_amounts(q, a, om2);
+                    omega = om2[0] + om2[1];
+                } else {
+                    omega = a * exp(fma(q.ba, c.log_df[q.ka], q.bb * c.log_df[q.kb]));
+                }
                 acc.pv += omega;
             }
-            { int kt_[2];
+            if constexpr (linear_df) {
+                lindf_plain(k, om2, om2, acc);
+            } else {
+                int kt_[2];
 #pragma unroll
-              for (int i_ = 0; i_ < 2; ++i_) kt_[i_] = tag(k[i_]);
-              if constexpr (FUSE) {
-                  const double kw1[1] = {omega * kap};
-                  add_nodes<2, DELTA, GAMMA, false, LDSLC, 1>(__ballot(on), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, b, conv, kw1, stage);
-              } else
-              add_nodes_any<2, DELTA, GAMMA, false, LDSLC, WIDE>(__ballot(on), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, b, conv); }
-            if constexpr (linear_df && !FUSE) add_df_correction<GAMMA, LDSLC, WIDE>(on, k[0], k[1], omega * kap, c, lc_lanes, lc_block_mask, vbuf, lane, acc);
+                for (int i_ = 0; i_ < 2; ++i_) kt_[i_] = tag(k[i_]);
+                add_nodes_any<2, DELTA, GAMMA, false, LDSLC, WIDE>(__ballot(on), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, b, conv);
+            }
         }
 
         // ---------------------------------------------------------------- results of this trade

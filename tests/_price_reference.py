@@ -1,0 +1,275 @@
+"""The bound the per-trade pricing kernels (`adr_price`: kernels_fast.hip, kernels_fast_lindf.hip, kernels_general.hip,
+kernels_lite.hip, kernels_knot.hip) are held to, element by element, on one pillar tile and on trades whose accruing coupons are
+paid on their accrual end (tests/test_price_edges_host.py, CPU, and tests/test_gpu_price_edges.py, GPU).
+
+The value and the gross of every element are `_ladder_reference.rates_reference`'s: per trade with ``sub_off = arange(n + 1)``,
+for the aggregate the one-desk row ``[0, n]``.  What is derived here is k of  |got - value| <= k 2^-53 gross  per kernel family,
+because the pricing kernels do other arithmetic than the ladder kernels `bound_k` counts.  The conventions are the same: one
+rounding is ONE unit 2^-53 of the absolute sum it acts on, a contracted FMA counts as its unfused pair, the device's exp and log
+(one ulp) as TWO units; one k serves every element of a trade (pv and delta have fewer roundings than gamma).  Three numbers are
+read off the inputs per trade (`trade_stats`), none off a result:
+  n      the trade's unfolded live terms (a kernel's nodes are sums of terms, so it has at most n nodes)
+  cond   the largest sum |weight L_k| of a term (LINEAR_FWD_RATES: the largest |L_k|), as in `bound_k`
+  wr     what an absolute error of w does to the lower knot's weight 1 - w, in units of the gross: over the trade's two-knot
+         lookups the largest of  w / (1 - w)  times the lower knot's share of an element's gross (`_amplification`: the share is
+         small where both knots move the same pillars, and 1 where the lower knot alone moves one); at least 1
+
+The weight e_w (curve_lookup.hpp, `curve_lookup_at`; w is the plan's float64 number, the same expression):
+  FLAT_FWD 1 - w: 1;  LINEAR_FWD 1 - w: 1;  LINEAR_ZERO t (1 - w) inv_x: inv_x = 1 / x is a rounded table entry (1), 1 - w,
+  two products: 4.
+  The lite kernel and the knot pass (INV_DX) form w as (tau - x_a) inv_dx, not by the division: inv_dx (1), the product (1) and
+  the reference's own quotient (1) part the two w by 3 units of w, and 1 - w turns them into 3 w / (1 - w) units of the lower
+  knot's weight, 3 wr of the gross:                                                                               e_w' = e_w + ceil(3 wr)
+
+The node (every family; kernels_fast.hip "fold the coupons into nodes", the same lines in kernels_lite.hip and
+kernels_general.hip):
+  amount    sl N (spread al - 1): 3; the next coupon's start joined: 1; the fixed flow by fma: 1                            5
+  argument  fma(ba, L_a, bb L_b): L from the table builder's log (2), the weight (e_w), a product, the sum: cond (e_w + 4)
+  exp       2;  omega = amount exp(): 1                                                                                   3
+  LINEAR_FWD_RATES (fast, lite, knot): the knot's amount qa ba exp(L_a): exp's argument is the table's log: 2 cond; exp 2; the
+  weight e_w and two products                                                                     5 + 2 cond + 4 + e_w
+                                                                               node = 8 + ceil(cond (e_w + 4))  [log schemes]
+
+fast, fast_chained (kernels_fast.hip, the walk; gamma is the worst element):
+  v = fma(wb, ub, wa ua): a Jacobian entry LJ = J / d (1), the weight (e_w), the product, the add: e_w + 3 of |wa ua| + |wb ub|
+  rank-one  fma(om u_i, v_q, acc): v twice, om u_i (1), the product (1)                                          2 e_w + 8
+  convexity fma(coa, LC, acc): coa = om wa (e_w + 1) [+ the carried right-knot weight: 1], a packed row entry is a copy of LC
+            (4, `bound_k`'s "tables"), the product: e_w + 7 of its own gross - less than the line above, as is a short-end
+            record's coef lc[j]
+  sums      an entry takes at most three adds per node (the rank-one term and two rows, or a row and a short-end number)    3 n
+  scale     acc 1e-8: the constant (1), the product (1)                                                                   2
+                                                                                       k = node + 2 e_w + 10 + 3 n
+  LINEAR_FWD_RATES (kernels_fast_lindf.hip): coa = amount + carry (1), coa u_i (LJ 1 + 1), times u_q (LJ 1 + 1): 5; coa LC: 6;
+  two knots per node, a rank-one term and a row each: 4 n                             k = 9 + e_w + ceil(2 cond) + 8 + 4 n
+
+general (kernels_general.hip, `add_nodes`; both variants - the LDS-resident rows add one final add per entry):
+  log schemes: v = fma(bb_i, lj_i, v): e_w + 3; vr = om v (1), fma(vr, vc): 2 e_w + 8; coef = om bb (e_w + 1), the tile (4), the
+  product; three adds per node, the merge of the flat convexity sums (1)               k = node + 2 e_w + 10 + 3 n + 1
+  LINEAR_FWD_RATES: a plain node is walked as two single-knot nodes of amounts a (1 - w) d_a and a w d_b (`lindf_plain`; the
+  node of the fast kernels above): v is the knot's Jacobian row itself (1), vr = om v (1), fma(vr, vc) (LJ 1 + 1): 4; the
+  amount times the tile: 5; a rank-one term and a row per knot: 4 n, the merge        k = 9 + e_w + ceil(2 cond) + 8 + 4 n + 1
+  (Until this bound was applied the kernel priced such a node in the form of its ratio nodes, om (v v^T + rho_a rho_b
+  (LJ_a - LJ_b)(LJ_a - LJ_b)^T) on the shares rho of D: the cross products rho_a rho_b LJ_a,p LJ_b,q of the two parts cancel
+  only up to rounding, and a date between two short-end knots that move different pillars left 1e-21 to 1e-24 on gamma
+  entries no term reaches.  tests/test_gpu_price_edges.py found it on the legs of 385, 400 and 450 coupons.)
+
+lite (kernels_lite.hip, `sweep`; PV and delta): ca = omega ba (e_w' + 1), fma(ca, LJ, d): LJ (1), the product (1); a node
+  leaves two entries: 2 n adds, d0 + e0 (1), 1e-4 (2)                                  k = node' + e_w' + 6 + 2 n
+  (node' = the node with e_w'; LINEAR_FWD_RATES likewise with its node)
+
+knot (kernels_lite.hip KNOT instantiations, kernels_knot.hip; the book's aggregate): a trade's part of the sums w_k += ca,
+  D_k += ca ba, O_k += ca bb holds a product more than its node (ca ba: 2 e_w' + 2); the projection: fma(dk ap, aq, s) - two
+  Jacobian entries (2), two products (2); the band term ok fma(ap, bq, bp aq): 2 + 2 + 1 against the same two-knot gross, one
+  more: 2 e_w' + 7; wk LC: e_w' + 1 + 4 + 1                                            k_t = node' + 2 e_w' + 7  per trade
+  and the sums: a wave's table takes at most N adds (N = the unfolded terms of all the pass's trades), the block sums its 8
+  waves (7), `knot_reduce_kernel` strides over the blocks and runs a butterfly (ceil(blocks / 64) - 1 + 6); three adds per knot
+  of a projection wave's share ceil(Kc / 16), fifteen adds of the waves' sums, agg += (1), 1e-8 (2)
+                             sums = N + 7 + ceil(blocks / 64) + 5 + 3 ceil(Kc / 16) + 18
+
+aggregate (the one-desk row): trade t arrives with an error of at most k_t units of ITS gross, so an element of the book is
+  held to  k = ceil(sum_t k_t gross_t / gross_book) + sums  of the book's gross (`book_k`; exact integer arithmetic) - one
+  trade with a large k_t (a date 1e-9 before a knot under INV_DX) then weighs on the book only by its own gross.  The block
+  partials (`reduce_partials_kernel`): a wave adds its trades (at most n_trades - 1 adds over all waves), its groups (1), the
+  block its waves in order (11: the fast kernel's 12 waves are the most), the reduction strides and runs its butterfly
+  (ceil(blocks / 64) - 1 + 6), the knot pass adds its projection to it (1)
+                             sums = n_trades + 18 + ceil(blocks / 64)  (+ the knot pass's sums where it runs)
+"""
+import math
+
+import numpy as np
+
+from oracle.mp_oracle import _lookup_plan
+
+from . import _ladder_reference as R
+
+FLAT_FWD, LINEAR_FWD, LINEAR_ZERO = R.FLAT_FWD, R.LINEAR_FWD, R.LINEAR_ZERO
+E_W = {FLAT_FWD: 1, LINEAR_FWD: 1, LINEAR_ZERO: 4}
+BLOCKS = R.RATES_BLOCKS
+
+
+def per_trade_reference(method, host, batch):
+    return R.rates_reference(method, host, batch, np.arange(batch.n_trades + 1, dtype=np.int64))
+
+
+def book_reference(method, host, batch):
+    return R.rates_reference(method, host, batch, np.array([0, batch.n_trades], dtype=np.int64))[0]
+
+
+def _amplification(s, wa, wb, A, B, GA, GB, La, Lb):
+    """What an ABSOLUTE error of the upper weight does to the lower one, in units of the reference's gross: the lower weight
+    wa moves by s = (upper / lower) times the upper weight's relative error, and the largest share of that in an element's
+    gross is taken over the argument (log schemes: |wa L_a| of |wa L_a| + |wb L_b|; LINEAR_FWD_RATES: wa of wa + wb), the delta
+    entries wa A_p of wa A_p + wb B_p, and the gamma entries - the convexity part wa GC_a and the second-order products
+    2 a_p a_q + a_p b_q + b_p a_q (a = wa A, b = wb B) of wa GC_a + wb GC_b + (a_p + b_p)(a_q + b_q).  A, B: |LJ| of the two
+    knots; GA, GB: their |C| / d + |J J^T| / d^2."""
+    a, b = wa * A, wb * B
+    worst = La / (La + Lb) if La + Lb > 0.0 else 0.0
+    live = a + b > 0.0
+    if np.any(live):
+        worst = max(worst, float(np.max(a[live] / (a + b)[live])))
+    if GA is not None:
+        num = wa * GA + 2.0 * np.outer(a, a) + np.outer(a, b) + np.outer(b, a)
+        den = wa * GA + wb * GB + np.outer(a + b, a + b)
+        live = den > 0.0
+        if np.any(live):
+            worst = max(worst, float(np.max(num[live] / den[live])))
+    return s * worst
+
+
+def trade_stats(method, host, batch):
+    """Per trade ``{"n", "cond", "wr"}`` (module docstring), from the inputs alone."""
+    def build():
+        R.mp.dps = 60
+        method_ = int(method)
+        cv = R._Curve(method_, host.times, host.dfs, host.jac, host.hess)
+        x, d = cv.x, np.asarray(host.dfs, dtype=np.float64)
+        A = np.abs(np.asarray(host.jac, dtype=np.float64)) / d[:, None]
+        L = np.abs(np.log(d))
+        hess = None if host.hess is None else np.abs(np.asarray(host.hess, dtype=np.float64))
+        gc = lambda k: None if hess is None else hess[k] / d[k] + np.outer(A[k], A[k])
+        seen = {}
+
+        def lookup(t):
+            if t not in seen:
+                plan = _lookup_plan(x, t, method_)
+                amp = 1.0
+                if plan[0] == "interp" and 0.0 < float(plan[3]) < 1.0:
+                    _, a, b, w = plan
+                    w = float(w)
+                    if method_ == LINEAR_FWD:
+                        wa, wb, La, Lb = (1.0 - w) * d[a], w * d[b], (1.0 - w) * d[a], w * d[b]
+                    elif method_ == LINEAR_ZERO:
+                        wa, wb = t * (1.0 - w) / max(x[a], 1e-15), t * w / max(x[b], 1e-15)
+                        La, Lb = abs(wa) * L[a], abs(wb) * L[b]
+                    else:
+                        wa, wb, La, Lb = 1.0 - w, w, (1.0 - w) * L[a], w * L[b]
+                    wa, wb = abs(wa), abs(wb)
+                    amp = max(1.0, _amplification(w / (1.0 - w), wa, wb, A[a], A[b], gc(a), gc(b), La, Lb))
+                seen[t] = amp
+            return seen[t]
+        out = []
+        for i in range(batch.n_trades):
+            st = dict(n=0, cond=0.0, wr=1.0)
+            for t, c, _ in R.trade_terms(batch, i):
+                st["n"] += 1
+                st["cond"] = max(st["cond"], float(cv.date(t)[3]))
+                st["wr"] = max(st["wr"], lookup(float(t)))
+            out.append(st)
+        return out
+    return R._cached("price stats", method, host, batch, (), build)
+
+
+def _node(method, cond, e_w):
+    if int(method) == LINEAR_FWD:
+        return 9 + e_w + math.ceil(2 * cond)
+    return 8 + math.ceil(cond * (e_w + 4))
+
+
+def trade_k(family, method, st):
+    """k of one trade priced by ``family`` ("fast", "fast_chained", "general", "lite")."""
+    method = int(method)
+    e_w, n, cond = E_W[method], st["n"], st["cond"]
+    if family in ("fast", "fast_chained", "general"):
+        merge = 1 if family == "general" else 0
+        if method == LINEAR_FWD:
+            return _node(method, cond, e_w) + 8 + 4 * n + merge
+        return _node(method, cond, e_w) + 2 * e_w + 10 + 3 * n + merge
+    if family == "lite":
+        e_w += math.ceil(3 * st["wr"])
+        return _node(method, cond, e_w) + e_w + 6 + 2 * n
+    raise ValueError(family)
+
+
+def knot_trade_k(method, st):
+    """k_t of one trade in the knot pass."""
+    e_w = E_W[int(method)] + math.ceil(3 * st["wr"])
+    return _node(method, st["cond"], e_w) + 2 * e_w + 7
+
+
+def knot_sums(stats, Kc, blocks):
+    return sum(s["n"] for s in stats) + 7 + -(-max(blocks, 1) // 64) + 5 + 3 * (-(-Kc // 16)) + 18
+
+
+def aggregate_sums(n_trades, blocks):
+    return n_trades + 18 + -(-max(blocks, 1) // 64)
+
+
+def book_k(ref, book, ks, name, sums):
+    """Per element of the book's block ``name``: ceil(sum_t k_t gross_t / gross_book) + sums, object array of int."""
+    lo = min([book[name].E] + [d[name].E for d in ref])
+    num = None
+    for k, d in zip(ks, ref):
+        part = d[name].A * (int(k) << (d[name].E - lo))
+        num = part if num is None else num + part
+    den = book[name].A * (1 << (book[name].E - lo))
+    out = np.empty(den.shape, dtype=object)
+    for idx in np.ndindex(den.shape):
+        out[idx] = (-(-int(num[idx]) // int(den[idx])) if den[idx] else 0) + sums
+    return out
+
+
+def share_elems(block, got, k, what=""):
+    """`Block.share` with k per element (object array of int)."""
+    got = np.asarray(got, dtype=np.float64).reshape(block.V.shape)
+    assert np.all(np.isfinite(got)), f"{what}: not finite"
+    m, ex = np.frexp(got)
+    m = (m * 2.0 ** 53).astype(np.int64)
+    worst, ten = 0.0, 10 ** block.s
+    for idx in np.ndindex(got.shape):
+        V, A = int(block.V[idx]), int(block.A[idx])
+        if A == 0:
+            assert got[idx] == 0.0 and not np.signbit(got[idx]), f"{what}{list(idx)}: gross is 0 but the entry is {got[idx]!r}"
+            continue
+        sh = int(ex[idx]) - 53 - block.E
+        g = int(m[idx]) * ten
+        if sh >= 0:
+            err, scale = abs((g << sh) - V), A
+        else:
+            err, scale = abs(g - (V << -sh)), A << -sh
+        worst = max(worst, ((err << 83) // (int(k[idx]) * scale)) / 2.0 ** 30)
+    return worst
+
+
+def case_ks(method, host, batch, ref, fams):
+    """k_t per trade for the families ``fams`` [n]."""
+    stats = trade_stats(method, host, batch)
+    out = []
+    for i, fam in enumerate(fams):
+        if fam == "knot":
+            out.append(knot_trade_k(method, stats[i]))
+            continue
+        out.append(trade_k(fam, method, stats[i]))
+    return out
+
+
+def rows_share(got, ref, ks, what, rows=None):
+    """The worst share over the per-trade blocks ``got`` holds (pv, delta, gamma), trade by trade on its own k; returns
+    ``(share, {family-less worst per block})``."""
+    worst = 0.0
+    for i in (range(len(ref)) if rows is None else rows):
+        for name in BLOCKS:
+            if name in got:
+                g = np.asarray(got[name][i])
+                worst = max(worst, ref[i][name].share(g.reshape(ref[i][name].V.shape), ks[i], f"{what} trade {i} {name}"))
+    return worst
+
+
+def book_share(got, ref, book, ks, sums, zero, what):
+    """The worst share of the aggregate ``agg_pv / agg_delta / agg_gamma`` against the one-desk row on `book_k`; the blocks
+    ``zero`` (not asked for) must be +0.0 throughout."""
+    worst = 0.0
+    for name in BLOCKS:
+        g = np.asarray(got["agg_" + name], dtype=np.float64)
+        if name in zero:
+            assert not np.any(g) and not np.any(np.signbit(g)), f"{what} agg_{name}: not asked for, not +0.0"
+            continue
+        worst = max(worst, share_elems(book[name], g, book_k(ref, book, ks, name, sums), f"{what} agg_{name}"))
+    return worst
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def same_bits(a, b, keys=None):
+    return all(np.array_equal(bits(a[k]), bits(b[k])) for k in (keys if keys is not None else a))

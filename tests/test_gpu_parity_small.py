@@ -53,8 +53,9 @@ def test_cashflows_next_to_gpu_requests(gpu_ctx):
 @pytest.mark.parametrize("shape", ["core21_epg12", "core16_epg7"])
 def test_other_curve_shapes_use_other_kernel_variants(gpu_ctx, shape):
     """32-pillar curves whose long end is longer / shorter than the README curve's: a different core size picks a
-    different instantiation of the fast kernel (12 or 7 packed entries per lane; hub layout with 10 or 5 core
-    slots).  Same parity bar."""
+    different instantiation of the fast kernel - 12 or 7 packed entries per lane, both "universal" (every slot reads a
+    convexity slice: 12 / 7 core slots, no hub layout), where the README curve takes the hub layout with 5 core slots of 7.
+    Same parity bar.  (An 8-entry instantiation: tests/test_gpu_price_edges.py, the 21-pillar curve.)"""
     from adrates_amd import _native
     from adrates_amd.market.curves.curve_tables import build_engine_curve
     vd = F.README_VALUE_DT
@@ -73,6 +74,7 @@ def test_other_curve_shapes_use_other_kernel_variants(gpu_ctx, shape):
     host = build_engine_curve(curve.swap_rates, curve.swap_times, curve.year_fracs)
     info = _native.curve_layout_host(host.times, host.dfs, host.jac, host.hess)
     assert info["packed_ok"] == 1 and (info["core_pillars"], info["entries_per_lane"]) == want
+    assert (info["core_slots_per_lane"], info["hub_layout"]) == (want[1], 0)
     assert info["lds_bytes"] <= 160 * 1024
     swaps = [F.make_swap(vd, "10Y", 0.045, 1e7), F.make_swap(vd, "87M", 0.04, 1e7, pay=False),
              F.make_swap(vd, "3M", 0.05, 2e6), F.make_swap(vd, "29Y", 0.039, 5e6),
