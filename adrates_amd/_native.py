@@ -179,6 +179,16 @@ _SIGNATURES = {
     "adr_ladder_pnl": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "adr_ladder_pnl_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "adr_ladder_pnl_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "adr_shock_normal": (C.c_int, [_vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp]),
+    "adr_shock_normal_dev": (C.c_int, [_vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "adr_shock_normal_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp]),
+    "adr_shock_words_host": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "adr_shock_uniforms": (C.c_int, [_vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp]),
+    "adr_shock_uniforms_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp]),
+    "adr_scenario_tail_select": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "adr_scenario_tail_select_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "adr_scenario_tail_select_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "adr_scenario_tail_select_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1677,6 +1687,88 @@ def ladder_pnl_dev(ctx: Context, B: int, P: int, ladders_ptr: int, S: int, shock
     the outputs [B, S] (0: not wanted, not touched)."""
     _check(load().adr_ladder_pnl_dev(ctx._h, int(B), int(P), _dev(ladders_ptr), int(S), _dev(shocks_ptr), _dev(pnl_ptr),
                                      _dev(delta_pnl_ptr), _dev(gamma_pnl_ptr), _vp(stream or None)), "adr_ladder_pnl_dev")
+
+
+# ------------------------------------------------------------------------- Monte Carlo shocks and the tail of wide rows
+def _shock_args(factor_bp, n_scenarios, seed, first_scenario):
+    factor = _f64(factor_bp)
+    if factor.ndim != 2:
+        raise LibError(f"factor_bp must have shape [n_pillars, n_factors], not {list(factor.shape)}")
+    seed, first = int(seed), int(first_scenario)
+    if not 0 <= seed < 2 ** 64 or not -2 ** 63 <= first < 2 ** 63:
+        raise LibError(f"seed must fit a uint64 and first_scenario an int64, not {seed}, {first}")
+    S = int(n_scenarios)
+    return factor, seed, first, S, np.empty((max(S, 0), factor.shape[0]))
+
+
+def shock_normal(ctx: Context, factor_bp, n_scenarios: int, seed: int, antithetic: bool = False, first_scenario: int = 0):
+    """``[S, P]``: correlated normal shocks ``factor_bp [P, F] @ z`` in basis points on the device (adr_shock_normal,
+    blocking): Philox4x32-10 and Box-Muller, row ``s`` a function of ``seed``, ``first_scenario + s``, the factor matrix
+    and ``antithetic`` alone."""
+    factor, seed, first, S, out = _shock_args(factor_bp, n_scenarios, seed, first_scenario)
+    _check(load().adr_shock_normal(ctx._h, seed, first, S, factor.shape[0], factor.shape[1], _ptr(factor), int(bool(antithetic)),
+                                   _ptr(out)), "adr_shock_normal")
+    return out
+
+
+def shock_normal_host(factor_bp, n_scenarios: int, seed: int, antithetic: bool = False, first_scenario: int = 0):
+    """`shock_normal` on the CPU (adr_shock_normal_host): the same code; the uniforms have the same bits, the normals each
+    side's ``log``, ``sqrt``, ``cos`` and ``sin``."""
+    factor, seed, first, S, out = _shock_args(factor_bp, n_scenarios, seed, first_scenario)
+    _check(load().adr_shock_normal_host(seed, first, S, factor.shape[0], factor.shape[1], _ptr(factor), int(bool(antithetic)),
+                                        _ptr(out)), "adr_shock_normal_host")
+    return out
+
+
+def shock_normal_dev(ctx: Context, seed: int, first_scenario: int, S: int, P: int, F: int, factor_ptr: int, antithetic: bool,
+                     out_ptr: int, stream=0):
+    """Non-blocking form (adr_shock_normal_dev): device pointers of ``factor`` [P, F] and ``out`` [S, P]."""
+    _check(load().adr_shock_normal_dev(ctx._h, int(seed), int(first_scenario), int(S), int(P), int(F), _dev(factor_ptr),
+                                       int(bool(antithetic)), _dev(out_ptr), _vp(stream or None)), "adr_shock_normal_dev")
+
+
+def shock_words_host(counter, key) -> np.ndarray:
+    """The Philox4x32-10 block of ``counter [4]`` and ``key [2]`` (uint32 words), as the generator computes it (a test hook)."""
+    c, k, w = (C.c_uint32 * 4)(*[int(v) for v in counter]), (C.c_uint32 * 2)(*[int(v) for v in key]), (C.c_uint32 * 4)()
+    load().adr_shock_words_host(c, k, w)
+    return np.array(list(w), dtype=np.uint32)
+
+
+def shock_uniforms(n_scenarios: int, n_factors: int, seed: int, antithetic: bool = False, first_scenario: int = 0, ctx=None):
+    """``[S, ceil(F / 2), 2]``: the uniforms ``(u1, u2)`` behind every pair of normals (a test hook); ``ctx=None``: the host
+    twin's, else the device's."""
+    S, F = int(n_scenarios), int(n_factors)
+    u = np.empty((max(S, 0), max((F + 1) // 2, 0), 2))
+    if ctx is None:
+        rc = load().adr_shock_uniforms_host(int(seed), int(first_scenario), S, F, int(bool(antithetic)), _ptr(u))
+    else:
+        rc = load().adr_shock_uniforms(ctx._h, int(seed), int(first_scenario), S, F, int(bool(antithetic)), _ptr(u))
+    _check(rc, "adr_shock_uniforms")
+    return u
+
+
+def scenario_tail_select(ctx: Context, rows, k: int, base_col: int = -1):
+    """`scenario_tail` for rows of any width (adr_scenario_tail_select, blocking): a radix select of the ``k``-th smallest
+    P&L, then the tail kernel on the ``k`` survivors; ``k <= SCENARIO_TAIL_MAX``."""
+    return _tail_call(load().adr_scenario_tail_select, (ctx._h,), rows, k, base_col)
+
+
+def scenario_tail_select_host(rows, k: int, base_col: int = -1):
+    """`scenario_tail_select` on the CPU (adr_scenario_tail_select_host): the same bits."""
+    return _tail_call(load().adr_scenario_tail_select_host, (), rows, k, base_col)
+
+
+def scenario_tail_select_work(B: int, S_tot: int, k: int) -> int:
+    """Bytes of scratch `scenario_tail_select_dev` needs (0 for sizes it refuses)."""
+    return int(load().adr_scenario_tail_select_work(int(B), int(S_tot), int(k)))
+
+
+def scenario_tail_select_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: int, var_ptr: int, es_ptr: int, work_ptr: int,
+                             base_col: int = -1, stream=0):
+    """Non-blocking form (adr_scenario_tail_select_dev): device pointers of ``rows`` [B, S_tot], ``var`` [B], ``es`` [B] and
+    ``work`` (`scenario_tail_select_work` bytes, 16-byte aligned)."""
+    _check(load().adr_scenario_tail_select_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), int(k), _dev(var_ptr),
+                                               _dev(es_ptr), _dev(work_ptr), _vp(stream or None)), "adr_scenario_tail_select_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

@@ -208,76 +208,7 @@ void reduce_subbooks(const double* work, const int64_t* chunk_off, int64_t B, in
 }
 
 // ------------------------------------------------------------------------------------------------------ tail measures
-// A double as an int64 whose signed order is the doubles' order, -0.0 before +0.0; the map is its own inverse.
-__host__ __device__ inline int64_t key_of(double v) {
-    int64_t b;
-    memcpy(&b, &v, sizeof b);
-    return b ^ ((b >> 63) & INT64_MAX);
-}
-__host__ __device__ inline double value_of(int64_t k) {
-    const int64_t b = k ^ ((k >> 63) & INT64_MAX);
-    double v;
-    memcpy(&v, &b, sizeof v);
-    return v;
-}
-
-// P&L value e of a row: column e, stepping over base_col, minus the base column's value.
-__host__ __device__ inline double pnl_at(const double* row, int base_col, int e) {
-    if (base_col < 0) return row[e];
-    return row[e >= base_col ? e + 1 : e] - row[base_col];
-}
-
-__host__ __device__ inline void tail_of_sorted(const int64_t* keys, int k, double* var, double* es) {
-    double sum = 0.0;
-    for (int i = 0; i < k; ++i) sum = sum + value_of(keys[i]);
-    *var = -value_of(keys[k - 1]);
-    *es = -sum / static_cast<double>(k);
-}
-
-// m P&L values per row, P = the power of two >= m (the LDS holds P keys).
-__global__ __launch_bounds__(1024) void tail_kernel(const double* rows, int64_t S_tot, int base_col, int m, int P, int k,
-                                                    double* var, double* es) {
-    extern __shared__ int64_t keys[];
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const double* row = rows + static_cast<int64_t>(blockIdx.x) * S_tot;
-    int nan = 0;
-    for (int e = tid; e < P; e += nt) {
-        double v = INFINITY;
-        if (e < m) {
-            v = pnl_at(row, base_col, e);
-            nan |= v != v;
-        }
-        keys[e] = key_of(v);
-    }
-    if (__syncthreads_or(nan)) {                    // uniform over the block
-        if (tid == 0) {
-            var[blockIdx.x] = NAN;
-            es[blockIdx.x] = NAN;
-        }
-        return;
-    }
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += nt) {
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                const int64_t a = keys[lo], b = keys[hi];
-                if ((a > b) == ((lo & size) == 0)) {
-                    keys[lo] = b;
-                    keys[hi] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) tail_of_sorted(keys, k, var + blockIdx.x, es + blockIdx.x);
-}
-
-inline int pow2_at_least(int m) {
-    int p = 1;
-    while (p < m) p <<= 1;
-    return p;
-}
-
+// key_of, value_of, pnl_at, tail_of_sorted, tail_kernel and enqueue_tail: subbook.hpp (adr_scenario_tail_select* runs them too).
 int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
     if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
     if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
@@ -292,19 +223,6 @@ int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k) 
         return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": " + std::to_string(m) + " P&L values per row; a row of at most "
                                                   "ADR_SCENARIO_TAIL_MAX (16384) fits the LDS");
     return ADR_OK;
-}
-
-hipError_t enqueue_tail(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var, double* es, hipStream_t stream) {
-    if (B > INT32_MAX) return hipErrorInvalidConfiguration;
-    const int m = base_col >= 0 ? S_tot - 1 : S_tot, P = pow2_at_least(m);
-    const int threads = std::min(1024, std::max(kWave, P / 2));
-    const size_t lds = static_cast<size_t>(P) * sizeof(int64_t);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(tail_kernel, dim3(static_cast<unsigned>(B)), dim3(threads), lds, stream, rows, static_cast<int64_t>(S_tot),
-                       base_col, m, P, k, var, es);
-    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------- tail allocation

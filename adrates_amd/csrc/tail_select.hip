@@ -1,0 +1,337 @@
+// VaR and ES of rows of any width (adr_scenario_tail_select*; the rule is adr_scenario_tail's, the contract:
+// include/adrates.h): a radix select on the 64-bit keys finds every row's k-th smallest P&L, the values below it are
+// gathered into tail[b][k], and subbook.hpp's tail_kernel sorts and adds those k - the kernel adr_scenario_tail runs on
+// the whole row, so for rows it takes the bits are its bits.
+//
+// The keys are key_of's int64 with the sign bit flipped: their UNSIGNED order is the total order of the doubles.  A
+// round fixes kDigitBits (11) more bits of the threshold key from the top, six rounds fix all 64 (the last holds nine):
+//   count   grid = (segments of a row) x (rows).  A block reads its segment once, forms the keys, and histograms the
+//           round's digit of those whose higher bits equal the row's prefix: 2048 bins of uint32 in LDS (8 KiB), integer
+//           LDS atomics, so a count does not depend on the order of arrival.  The first round takes every key, and its
+//           digit is sign and exponent - a handful of values over a whole wave -, so there a wave first adds up its
+//           lanes per distinct digit (ballots, as many steps as the wave holds digits) and one lane adds the sum; it also
+//           ORs the row's NaN flag.  The block writes its histogram to work.
+//   scan    one block per row adds the segments' histograms in segment order, eight neighbouring bins per thread, scans
+//           the 256 partial sums in LDS, and the one thread whose bins hold the k_rem-th key extends the prefix and
+//           reduces k_rem.
+//   gather  the count grid again: a value whose key is below the threshold key goes to tail[b][slot], slot from a per-row
+//           integer counter (any order: the tail is sorted next); the block of segment 0 fills the other k - c slots
+//           with the threshold value, c = k - k_rem being known from the scan.
+//   tail    tail_kernel on tail[B][k] with base_col = -1, then NaN rows are patched from the flag.
+// Every round re-reads the whole row (seven reads of the matrix in all): nothing is compacted, so the scratch is the
+// histograms and the tail alone and a round is a pure streaming read.  The kernel boundary is the only
+// synchronisation: no flags, no spin-waits, no float atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/adrates.h"
+#include "blocking_call.hpp"
+#include "host_pool.hpp"
+#include "subbook.hpp"
+
+namespace adr {
+namespace tsel {
+
+using sub::key_of;
+using sub::pnl_at;
+using sub::value_of;
+
+constexpr int kDigitBits = 11;
+constexpr int kBins = 1 << kDigitBits;          // 2048 uint32 = 8 KiB
+constexpr int kRounds = 6;                      // 5 x 11 + 9 bits
+constexpr int kThreads = 256;
+constexpr int kBinsPerThread = kBins / kThreads;
+constexpr int kSegMin = 8192;                   // P&L values per segment at least: its histogram is an eighth of its bytes
+constexpr int kBlocksWanted = 2048;             // segments x rows aimed at, 8 blocks per CU
+
+// The bits below round r's digit, and the digit's width.
+__host__ __device__ inline int shift_of(int r) { return r < kRounds - 1 ? 64 - kDigitBits * (r + 1) : 0; }
+__host__ __device__ inline int bits_of(int r) { return r < kRounds - 1 ? kDigitBits : 64 - kDigitBits * (kRounds - 1); }
+
+__host__ __device__ inline uint64_t ukey_of(double v) { return static_cast<uint64_t>(key_of(v)) ^ (uint64_t(1) << 63); }
+__host__ __device__ inline double value_of_ukey(uint64_t u) { return value_of(static_cast<int64_t>(u ^ (uint64_t(1) << 63))); }
+
+// A row's state in work: the threshold key's bits fixed so far (right-aligned), what is left of k below them, the NaN
+// flag and the gather's slot counter.
+struct RowState {
+    uint64_t prefix;
+    int32_t k_rem, nan, count, pad;
+};
+
+// Segments per row (from S_tot, so that adr_scenario_tail_select_work needs no base_col) and a segment's length.
+inline int segments(int64_t B, int S_tot) {
+    const int64_t by_len = (static_cast<int64_t>(S_tot) + kSegMin - 1) / kSegMin, by_rows = (kBlocksWanted + B - 1) / B;
+    return static_cast<int>(std::max<int64_t>(1, std::min(by_len, by_rows)));
+}
+inline int segment_len(int S_tot, int nseg) { return static_cast<int>((static_cast<int64_t>(S_tot) + nseg - 1) / nseg); }
+
+// work: state[B] | hist[B][nseg][kBins] uint32 | tail[B][k] doubles
+struct Layout {
+    size_t hist, tail, bytes;
+};
+inline Layout layout(int64_t B, int S_tot, int k) {
+    Layout l;
+    l.hist = static_cast<size_t>(B) * sizeof(RowState);
+    l.tail = l.hist + static_cast<size_t>(B) * segments(B, S_tot) * kBins * sizeof(uint32_t);
+    l.bytes = l.tail + static_cast<size_t>(B) * k * sizeof(double);
+    return l;
+}
+
+struct Args {
+    const double* rows;              // [B][S_tot]
+    RowState* state;                 // [B]
+    uint32_t* hist;                  // [B][nseg][kBins]
+    double* tail;                    // [B][k]
+    int64_t S_tot;
+    int base_col, m, k, nseg, seg_len;
+};
+
+// blockIdx.x = row * nseg + segment.
+template <bool kFirst>
+__global__ __launch_bounds__(kThreads) void select_count_kernel(Args a, int round) {
+    __shared__ uint32_t h[kBins];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x / a.nseg;
+    const int seg = static_cast<int>(blockIdx.x - b * a.nseg);
+    for (int i = tid; i < kBins; i += kThreads) h[i] = 0;
+    __syncthreads();
+    const double* row = a.rows + b * a.S_tot;
+    const int e0 = seg * a.seg_len, e1 = a.m - e0 < a.seg_len ? a.m : e0 + a.seg_len;
+    const int shift = shift_of(round);
+    const uint32_t mask = (1u << bits_of(round)) - 1u;
+    const uint64_t prefix = kFirst ? 0 : a.state[b].prefix;         // uniform: a scalar load
+    int nan = 0;
+    for (int64_t base = e0; base < e1; base += kThreads) {          // uniform bounds: whole waves stay in the loop
+        const bool in = base + tid < e1;
+        const double v = in ? pnl_at(row, a.base_col, static_cast<int>(base + tid)) : 0.0;
+        const uint64_t u = ukey_of(v);
+        const uint32_t d = static_cast<uint32_t>(u >> shift) & mask;
+        if (kFirst) {
+            nan |= v != v;
+            uint64_t todo = __ballot(in);
+            while (todo) {                                          // one step per distinct digit of the wave
+                const int lead = __ffsll(static_cast<long long>(todo)) - 1;
+                const uint32_t d0 = __shfl(d, lead);
+                const uint64_t same = __ballot(in && d == d0) & todo;
+                if ((tid & 63) == lead) atomicAdd(&h[d0], static_cast<uint32_t>(__popcll(same)));
+                todo &= ~same;
+            }
+        } else if (in && (u >> shift >> bits_of(round)) == prefix) {
+            atomicAdd(&h[d], 1u);
+        }
+    }
+    if (kFirst && nan) atomicOr(&a.state[b].nan, 1);
+    __syncthreads();
+    uint32_t* out = a.hist + static_cast<size_t>(blockIdx.x) * kBins;
+    for (int i = tid; i < kBins; i += kThreads) out[i] = h[i];
+}
+
+// blockIdx.x = row.  k_rem is k in the first round (the state has been zeroed).
+__global__ __launch_bounds__(kThreads) void select_scan_kernel(Args a, int round) {
+    __shared__ uint32_t part[kThreads];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const uint32_t* hist = a.hist + static_cast<size_t>(b) * a.nseg * kBins + tid * kBinsPerThread;
+    // the state is read here, before the barriers below, and written behind them by one thread
+    const uint32_t k_rem = static_cast<uint32_t>(round == 0 ? a.k : a.state[b].k_rem);
+    const uint64_t prefix = round == 0 ? 0 : a.state[b].prefix;
+    uint32_t c[kBinsPerThread];
+#pragma unroll
+    for (int i = 0; i < kBinsPerThread; ++i) c[i] = 0;
+    for (int seg = 0; seg < a.nseg; ++seg) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(hist + static_cast<size_t>(seg) * kBins);
+        const uint4 hi = *reinterpret_cast<const uint4*>(hist + static_cast<size_t>(seg) * kBins + 4);
+        c[0] += lo.x; c[1] += lo.y; c[2] += lo.z; c[3] += lo.w;
+        c[4] += hi.x; c[5] += hi.y; c[6] += hi.z; c[7] += hi.w;
+    }
+    uint32_t own = 0;
+#pragma unroll
+    for (int i = 0; i < kBinsPerThread; ++i) own += c[i];
+    part[tid] = own;
+    __syncthreads();
+    for (int step = 1; step < kThreads; step <<= 1) {               // inclusive scan of the 256 partial sums
+        const uint32_t add = tid >= step ? part[tid - step] : 0u;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    uint32_t below = part[tid] - own;                               // keys in the bins before this thread's
+    if (below < k_rem && k_rem <= below + own) {                    // exactly one thread: the counts add up to >= k_rem
+        int bin = kBinsPerThread - 1;
+        bool found = false;
+#pragma unroll
+        for (int i = 0; i < kBinsPerThread; ++i) {                  // unrolled: c[] stays in registers
+            if (!found && below + c[i] >= k_rem) {
+                bin = i;
+                found = true;
+            }
+            if (!found) below += c[i];
+        }
+        a.state[b].prefix = (prefix << bits_of(round)) | static_cast<uint64_t>(tid * kBinsPerThread + bin);
+        a.state[b].k_rem = static_cast<int32_t>(k_rem - below);
+    }
+}
+static_assert(kBinsPerThread == 8, "select_scan_kernel reads two uint4");
+
+// blockIdx.x = row * nseg + segment; the prefix is the whole threshold key now.
+__global__ __launch_bounds__(kThreads) void select_gather_kernel(Args a) {
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x / a.nseg;
+    const int seg = static_cast<int>(blockIdx.x - b * a.nseg);
+    const double* row = a.rows + b * a.S_tot;
+    const int e0 = seg * a.seg_len, e1 = a.m - e0 < a.seg_len ? a.m : e0 + a.seg_len;
+    const uint64_t thr = a.state[b].prefix;                         // uniform: scalar loads
+    const int below = a.k - a.state[b].k_rem;                       // the keys under the threshold: fewer than k
+    double* tail = a.tail + b * a.k;
+    for (int64_t e = static_cast<int64_t>(e0) + tid; e < e1; e += kThreads) {
+        const double v = pnl_at(row, a.base_col, static_cast<int>(e));
+        if (ukey_of(v) < thr) {
+            const int slot = atomicAdd(&a.state[b].count, 1);
+            if (slot < below) tail[slot] = v;                       // always, unless the counts were wrong: never out of bounds
+        }
+    }
+    if (seg == 0) {
+        const double t = value_of_ukey(thr);
+        for (int i = below + tid; i < a.k; i += kThreads) tail[i] = t;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void select_nan_kernel(const RowState* state, int64_t B, double* var, double* es) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    if (b < B && state[b].nan) {
+        var[b] = NAN;
+        es[b] = NAN;
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------- host
+int check(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
+    if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
+    if (base_col < -1 || base_col >= S_tot)
+        return adr_set_error(ADR_ERR_INVALID, w + ": base_col must be -1 (the rows are P&L) or a column, 0 .. " +
+                                                  std::to_string(S_tot - 1));
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    if (m < 1) return adr_set_error(ADR_ERR_INVALID, w + ": no P&L value is left beside the base column");
+    if (k < 1 || k > m)
+        return adr_set_error(ADR_ERR_INVALID, w + ": k must lie in 1 .. " + std::to_string(m) + " (the P&L values per row)");
+    if (k > ADR_SCENARIO_TAIL_MAX)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": a tail of " + std::to_string(k) + " P&L values; a tail of at most "
+                                                  "ADR_SCENARIO_TAIL_MAX (16384) fits the LDS");
+    return ADR_OK;
+}
+
+// The chain on `stream`; every pointer is device memory, `work` holds layout(B, S_tot, k).bytes.
+int enqueue(const std::string& w, const double* rows, int64_t B, int S_tot, int base_col, int k, double* var, double* es, void* work,
+            hipStream_t stream) {
+    const int nseg = segments(B, S_tot);
+    if (B * nseg > INT32_MAX) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 2^31 (row, segment) pairs in one launch");
+    const Layout l = layout(B, S_tot, k);
+    char* base = static_cast<char*>(work);
+    Args a{rows, reinterpret_cast<RowState*>(base), reinterpret_cast<uint32_t*>(base + l.hist), reinterpret_cast<double*>(base + l.tail),
+           S_tot, base_col, base_col >= 0 ? S_tot - 1 : S_tot, k, nseg, segment_len(S_tot, nseg)};
+    const dim3 grid(static_cast<unsigned>(B * nseg)), rows_grid(static_cast<unsigned>(B)), block(kThreads);
+    hipError_t e = hipMemsetAsync(a.state, 0, l.hist, stream);
+    for (int r = 0; r < kRounds && e == hipSuccess; ++r) {
+        if (r == 0) hipLaunchKernelGGL(select_count_kernel<true>, grid, block, 0, stream, a, r);
+        else hipLaunchKernelGGL(select_count_kernel<false>, grid, block, 0, stream, a, r);
+        hipLaunchKernelGGL(select_scan_kernel, rows_grid, block, 0, stream, a, r);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(select_gather_kernel, grid, block, 0, stream, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = sub::enqueue_tail(a.tail, B, k, -1, k, var, es, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(select_nan_kernel, dim3(static_cast<unsigned>((B + kThreads - 1) / kThreads)), block, 0, stream, a.state, B,
+                           var, es);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+}  // namespace tsel
+}  // namespace adr
+
+namespace TS = adr::tsel;
+
+extern "C" {
+
+int64_t adr_scenario_tail_select_work(int64_t B, int S_tot, int k) {
+    if (B < 1 || S_tot < 1 || k < 1 || k > ADR_SCENARIO_TAIL_MAX) return 0;
+    return static_cast<int64_t>(TS::layout(B, S_tot, k).bytes);
+}
+
+int adr_scenario_tail_select_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k, double* var_dev,
+                                 double* es_dev, void* work_dev, void* stream) {
+    const std::string w = "adr_scenario_tail_select_dev";
+    if (!ctx) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx");
+    int rc = TS::check(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows_dev || !var_dev || !es_dev) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    if (!work_dev) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_scenario_tail_select_work bytes are needed)");
+    hipStream_t st = nullptr;
+    rc = adr::call::target_stream(w, ctx, static_cast<hipStream_t>(stream), &st);
+    if (rc != ADR_OK) return rc;
+    return TS::enqueue(w, rows_dev, B, S_tot, base_col, k, var_dev, es_dev, work_dev, st);
+}
+
+int adr_scenario_tail_select(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es) {
+    const std::string w = "adr_scenario_tail_select";
+    if (!ctx) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx");
+    int rc = TS::check(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    hipStream_t stream = nullptr;
+    rc = adr::call::target_stream(w, ctx, nullptr, &stream);
+    if (rc != ADR_OK) return rc;
+    // one allocation: the rows, var and es, the scratch
+    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot, nb = static_cast<size_t>(B);
+    const size_t head = (R + 2 * nb) * d, work_at = (head + 15) / 16 * 16;
+    char* base = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), work_at + TS::layout(B, S_tot, k).bytes);
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double *drows = reinterpret_cast<double*>(base), *dvar = drows + R, *des = dvar + nb;
+    e = hipMemcpyAsync(drows, rows, R * d, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) rc = TS::enqueue(w, drows, B, S_tot, base_col, k, dvar, des, base + work_at, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(var, dvar, nb * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(es, des, nb * d, hipMemcpyDeviceToHost, stream);
+    return adr::call::finish_blocking(w, rc, e, stream, base);
+}
+
+int adr_scenario_tail_select_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es) {
+    const std::string w = "adr_scenario_tail_select_host";
+    const int rc = TS::check(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    adr::parallel_ranges(B, adr::pool_threads(B, 4), [&](int, int64_t lo, int64_t hi) {
+        std::vector<int64_t> keys(static_cast<size_t>(m));
+        for (int64_t b = lo; b < hi; ++b) {
+            const double* row = rows + b * S_tot;
+            bool nan = false;
+            for (int e = 0; e < m; ++e) {
+                const double v = adr::sub::pnl_at(row, base_col, e);
+                nan |= v != v;
+                keys[e] = adr::sub::key_of(v);
+            }
+            if (nan) {
+                var[b] = es[b] = NAN;
+                continue;
+            }
+            std::nth_element(keys.begin(), keys.begin() + (k - 1), keys.end());
+            std::sort(keys.begin(), keys.begin() + k);
+            adr::sub::tail_of_sorted(keys.data(), k, var + b, es + b);
+        }
+    });
+    return ADR_OK;
+}
+
+}  // extern "C"

@@ -941,6 +941,70 @@ int adr_ladder_pnl_host(int64_t B, int P, const double* ladders, int S, const do
                         double* pnl_gamma);
 
 /*
+ * Correlated normal shocks from a factor matrix: the scenario set of a Monte Carlo delta-gamma VaR, made where
+ * adr_ladder_pnl* reads it.  factor[P][F], row-major, 1 <= F <= P <= ADR_LADDER_PNL_MAX_PILLARS: a Cholesky factor of the
+ * covariance of the quote moves in bp^2, or fewer PCA columns.  out[S][P], adr_ladder_pnl's shocks_bp:
+ *
+ *   out[s][p] = sum_j factor[p][j] z[s][j]                                        (basis points)
+ *
+ * Row s is GLOBAL row first_scenario + s (first_scenario >= 0), so a set can be made in pieces.  Its normals belong to the
+ * generating scenario g: g = the global row, or with antithetic = 1 the global row >> 1, and then the odd global rows are
+ * the exact negation (sign bit flipped, zeros included) of the even rows before them.
+ *
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key
+ *              (seed lo, seed hi), counter (g lo, g hi, j / 2, 0); one call yields the words w0 .. w3
+ *   uniforms   u1 = (((w1 << 32 | w0) >> 11) + 0.5) * 2^-53, u2 the same from w3, w2: the 53-bit integer is exact, the sum
+ *              is rounded once to nearest even and the scaling is exact, so u lies in (0, 1] - 1.0 when all 53 bits are
+ *              set - and is never 0: there is no log(0)
+ *   normals    r = sqrt(-2 log(u1)); z[2 (j / 2)] = r cos(2 pi u2), z[2 (j / 2) + 1] = r sin(2 pi u2), 2 pi the nearest
+ *              double; an odd F drops the last sine
+ *   products   x = fma(factor[p][j], z_j, x) for j = 0 .. F - 1 ascending, from +0.0; the antithetic negation comes last
+ *
+ * A row depends on seed, its global index, factor and antithetic alone: not on S, on how first_scenario splits the set,
+ * on the launch geometry or on the run.  u has the same bits on the device and in the host twin; log, sqrt, cos and sin
+ * are each side's library, so z and out agree to a few ulp of their terms, not bit for bit.  Refused with
+ * ADR_ERR_INVALID: F > P, P > ADR_LADDER_PNL_MAX_PILLARS, S < 1, F < 1, first_scenario < 0 (or first_scenario + S beyond
+ * an int64), antithetic other than 0 / 1, NULL pointers.  adr_shock_normal: host arrays, blocks (one allocation); _dev:
+ * device arrays, one kernel on `stream` (NULL: the ctx's own), no allocation, no synchronisation, scalar checks only;
+ * _host: the CPU twin, the same code.
+ *
+ * Test hooks: adr_shock_words_host is the raw Philox4x32-10 block of a counter and a key; adr_shock_uniforms* write
+ * u[S][ceil(F / 2)][2], (u1, u2) of every pair of every row, from the host twin and from the device (host arrays, blocks).
+ */
+int adr_shock_normal(adr_ctx* ctx, uint64_t seed, int64_t first_scenario, int S, int P, int F, const double* factor, int antithetic,
+                     double* out);
+int adr_shock_normal_dev(adr_ctx* ctx, uint64_t seed, int64_t first_scenario, int S, int P, int F, const double* factor_dev,
+                         int antithetic, double* out_dev, void* stream);
+int adr_shock_normal_host(uint64_t seed, int64_t first_scenario, int S, int P, int F, const double* factor, int antithetic,
+                          double* out);
+void adr_shock_words_host(const uint32_t counter[4], const uint32_t key[2], uint32_t words[4]);
+int adr_shock_uniforms(adr_ctx* ctx, uint64_t seed, int64_t first_scenario, int S, int F, int antithetic, double* u);
+int adr_shock_uniforms_host(uint64_t seed, int64_t first_scenario, int S, int F, int antithetic, double* u);
+
+/*
+ * adr_scenario_tail for rows of any width: var[b] and es[b] of rows[B][S_tot] by adr_scenario_tail's definition, word for
+ * word - base_col, k, var[b] minus the k-th smallest P&L, es[b] minus the sum of the k smallest added in ascending order
+ * from 0.0 and divided by k, the total order of the doubles (-0.0 before +0.0), NaN in both for a row holding a NaN.  The
+ * limit is on the tail, not on the row: 1 <= k <= ADR_SCENARIO_TAIL_MAX (beyond: ADR_ERR_UNSUPPORTED); the P&L values per
+ * row are bounded by int alone.  k < 1, k beyond the P&L values per row, a bad base_col, B < 1, NULL arrays:
+ * ADR_ERR_INVALID.  For rows adr_scenario_tail takes the results have its bits.
+ *
+ * Device: a radix select on the 64-bit keys, 11 bits a round from the top (six rounds: a histogram kernel over
+ * (segment, row) blocks with integer LDS atomics and a scan kernel per row), a gather of the values below the k-th into
+ * tail[B][k], padded with the k-th value itself, then adr_scenario_tail's kernel on that matrix.  Only integer atomics,
+ * whose sums do not depend on the order of arrival; the kernel boundary is the only synchronisation; two runs give the
+ * same bits.  adr_scenario_tail_select: host arrays, blocks (one allocation); _dev: device arrays and work_dev -
+ * adr_scenario_tail_select_work(B, S_tot, k) bytes, 16-byte aligned, contents free - on `stream`, no allocation, no
+ * synchronisation; _host: the CPU twin - std::nth_element on the keys, a sort of the k smallest, the same sum - the same
+ * bits.  adr_scenario_tail_select_work returns 0 for sizes the entries refuse.
+ */
+int adr_scenario_tail_select(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es);
+int adr_scenario_tail_select_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k, double* var_dev,
+                                 double* es_dev, void* work_dev, void* stream);
+int adr_scenario_tail_select_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es);
+int64_t adr_scenario_tail_select_work(int64_t B, int S_tot, int k);
+
+/*
  * Credit sub-book Greeks: per sub-book the PV, the curve delta and gamma AT THE TRADES' SPREADS, CS01 and spread gamma
  * per credit bucket and the rate x spread cross gamma, from one launch chain.  The spread side is adr_credit_scenario_pv's:
  * z[n] (z-spread of a bond, discount margin of an FRN), bucket[n] in -1 .. G - 1 (-1: no bucket), 0 <= G <=
