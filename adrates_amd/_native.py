@@ -189,6 +189,20 @@ _SIGNATURES = {
     "adr_scenario_tail_select_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "adr_scenario_tail_select_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "adr_scenario_tail_select_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "adr_scenario_tail_order": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _i64p, _dp, _dp]),
+    "adr_scenario_tail_order_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "adr_scenario_tail_order_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _i64p, _dp, _dp]),
+    "adr_scenario_tail_order_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "adr_scenario_tail_alloc_select": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "adr_scenario_tail_alloc_select_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "adr_scenario_tail_alloc_select_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "adr_scenario_tail_alloc_select_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "adr_scenario_total_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "adr_scenario_total_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int, _dp]),
+    "adr_shock_gather_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "adr_shock_gather_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _i64p, _dp]),
+    "adr_tail_components_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
+    "adr_tail_components_host": (C.c_int, [C.c_int64, C.c_int, _dp, _dp, _dp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1769,6 +1783,115 @@ def scenario_tail_select_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k:
     ``work`` (`scenario_tail_select_work` bytes, 16-byte aligned)."""
     _check(load().adr_scenario_tail_select_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), int(k), _dev(var_ptr),
                                                _dev(es_ptr), _dev(work_ptr), _vp(stream or None)), "adr_scenario_tail_select_dev")
+
+
+# ------------------------------------------------------------------ the ordered tail select and the allocation around it
+def _order_call(fn, head, rows, k, base_col):
+    rows = _tail_rows(rows)
+    B = rows.shape[0]
+    order, var, es = np.empty((B, max(int(k), 0)), dtype=np.int64), np.empty(B), np.empty(B)
+    _check(fn(*head, B, rows.shape[1], _ptr(rows), int(base_col), int(k), _ptr(order, _i64p), _ptr(var), _ptr(es)), fn.__name__)
+    return order, var, es
+
+
+def scenario_tail_order(ctx: Context, rows, k: int, base_col: int = -1):
+    """``(order [B, k] int64, var [B], es [B])`` of ``rows [B, S]`` on the device (adr_scenario_tail_order, blocking): every
+    row's ``k`` worst P&L indices ordered by (value, index) - ties to the lower index - and `scenario_tail_select`'s ``var``
+    and ``es``; ``k <= SCENARIO_ALLOC_MAX``.  A row holding a NaN: -1 and NaN."""
+    return _order_call(load().adr_scenario_tail_order, (ctx._h,), rows, k, base_col)
+
+
+def scenario_tail_order_host(rows, k: int, base_col: int = -1):
+    """`scenario_tail_order` on the CPU (adr_scenario_tail_order_host): the same bits."""
+    return _order_call(load().adr_scenario_tail_order_host, (), rows, k, base_col)
+
+
+def scenario_tail_order_work(B: int, S_tot: int, k: int) -> int:
+    """Bytes of scratch `scenario_tail_order_dev` needs (0 for sizes it refuses)."""
+    return int(load().adr_scenario_tail_order_work(int(B), int(S_tot), int(k)))
+
+
+def scenario_tail_order_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: int, order_ptr: int, var_ptr: int, es_ptr: int,
+                            work_ptr: int, base_col: int = -1, stream=0):
+    """Non-blocking form (adr_scenario_tail_order_dev): device pointers of ``rows`` [B, S_tot], ``order`` [B, k] int64,
+    ``var`` [B], ``es`` [B] and ``work`` (`scenario_tail_order_work` bytes, 16-byte aligned)."""
+    _check(load().adr_scenario_tail_order_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), int(k), _dev(order_ptr),
+                                              _dev(var_ptr), _dev(es_ptr), _dev(work_ptr), _vp(stream or None)),
+           "adr_scenario_tail_order_dev")
+
+
+def scenario_tail_alloc_select(ctx: Context, rows, k: int, base_col: int = -1):
+    """`scenario_tail_alloc` for rows of any width (adr_scenario_tail_alloc_select, blocking): the limit is on the tail,
+    ``k <= SCENARIO_ALLOC_MAX``."""
+    return _alloc_call(load().adr_scenario_tail_alloc_select, (ctx._h,), rows, k, base_col)
+
+
+def scenario_tail_alloc_select_host(rows, k: int, base_col: int = -1):
+    """`scenario_tail_alloc_select` on the CPU (adr_scenario_tail_alloc_select_host): the same bits."""
+    return _alloc_call(load().adr_scenario_tail_alloc_select_host, (), rows, k, base_col)
+
+
+def scenario_tail_alloc_select_work(B: int, S_tot: int, k: int) -> int:
+    """Bytes of scratch `scenario_tail_alloc_select_dev` needs (0 for sizes it refuses)."""
+    return int(load().adr_scenario_tail_alloc_select_work(int(B), int(S_tot), int(k)))
+
+
+def scenario_tail_alloc_select_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, k: int, var_ptr: int, es_ptr: int,
+                                   comp_var_ptr: int, comp_es_ptr: int, work_ptr: int, base_col: int = -1, stream=0):
+    """Non-blocking form (adr_scenario_tail_alloc_select_dev): device pointers as `scenario_tail_alloc_dev` takes them, with
+    ``work`` of `scenario_tail_alloc_select_work` bytes, 16-byte aligned."""
+    _check(load().adr_scenario_tail_alloc_select_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), int(k),
+                                                     _dev(var_ptr), _dev(es_ptr), _dev(comp_var_ptr), _dev(comp_es_ptr),
+                                                     _dev(work_ptr), _vp(stream or None)), "adr_scenario_tail_alloc_select_dev")
+
+
+def scenario_total_host(rows, base_col: int = -1):
+    """``tot [m]``: the fixed-order column sums of ``rows [B, S]`` (adr_scenario_total_host), `scenario_tail_alloc`'s firm
+    totals; of ladder rows, the firm's ladder row."""
+    rows = _tail_rows(rows)
+    tot = np.empty(max(rows.shape[1] - (1 if base_col >= 0 else 0), 0))
+    _check(load().adr_scenario_total_host(rows.shape[0], rows.shape[1], _ptr(rows), int(base_col), _ptr(tot)), "adr_scenario_total_host")
+    return tot
+
+
+def scenario_total_dev(ctx: Context, B: int, S_tot: int, rows_ptr: int, tot_ptr: int, base_col: int = -1, stream=0):
+    """Non-blocking form (adr_scenario_total_dev): device pointers of ``rows`` [B, S_tot] and ``tot`` [m]."""
+    _check(load().adr_scenario_total_dev(ctx._h, int(B), int(S_tot), _dev(rows_ptr), int(base_col), _dev(tot_ptr),
+                                         _vp(stream or None)), "adr_scenario_total_dev")
+
+
+def shock_gather_host(shocks_bp, order):
+    """``[k, P]``: the rows ``order [k]`` of ``shocks_bp [S, P]`` (adr_shock_gather_host); NaN everywhere when ``order[0]``
+    is negative."""
+    shocks_bp, order = _f64(shocks_bp), np.ascontiguousarray(order, dtype=np.int64).reshape(-1)
+    if shocks_bp.ndim != 2:
+        raise LibError(f"shocks_bp must have shape [n_scenarios, n_pillars], not {list(shocks_bp.shape)}")
+    out = np.empty((order.size, shocks_bp.shape[1]))
+    _check(load().adr_shock_gather_host(order.size, shocks_bp.shape[1], _ptr(shocks_bp), shocks_bp.shape[0], _ptr(order, _i64p),
+                                        _ptr(out)), "adr_shock_gather_host")
+    return out
+
+
+def shock_gather_dev(ctx: Context, k: int, P: int, shocks_ptr: int, S: int, order_ptr: int, out_ptr: int, stream=0):
+    """Non-blocking form (adr_shock_gather_dev): device pointers of ``shocks`` [S, P], ``order`` [k] int64 and ``out`` [k, P]."""
+    _check(load().adr_shock_gather_dev(ctx._h, int(k), int(P), _dev(shocks_ptr), int(S), _dev(order_ptr), _dev(out_ptr),
+                                       _vp(stream or None)), "adr_shock_gather_dev")
+
+
+def tail_components_host(pnl):
+    """``(comp_var [B], comp_es [B])`` of ``pnl [B, k]``, every row's P&L at the firm's ``k`` worst scenarios in the firm's
+    order (adr_tail_components_host): minus the last column, and minus the sequential sum over ``k``."""
+    pnl = _tail_rows(pnl)
+    comp_var, comp_es = np.empty(pnl.shape[0]), np.empty(pnl.shape[0])
+    _check(load().adr_tail_components_host(pnl.shape[0], pnl.shape[1], _ptr(pnl), _ptr(comp_var), _ptr(comp_es)),
+           "adr_tail_components_host")
+    return comp_var, comp_es
+
+
+def tail_components_dev(ctx: Context, B: int, k: int, pnl_ptr: int, comp_var_ptr: int, comp_es_ptr: int, stream=0):
+    """Non-blocking form (adr_tail_components_dev): device pointers of ``pnl`` [B, k], ``comp_var`` [B] and ``comp_es`` [B]."""
+    _check(load().adr_tail_components_dev(ctx._h, int(B), int(k), _dev(pnl_ptr), _dev(comp_var_ptr), _dev(comp_es_ptr),
+                                          _vp(stream or None)), "adr_tail_components_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

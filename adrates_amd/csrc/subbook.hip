@@ -233,11 +233,7 @@ int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k) 
 //      the firm's tail and leaves the first k indices where tot was (the scratch is S_tot doubles, k <= S_tot);
 //   3. one thread per row adds the row's P&L over those k scenarios in that order.
 // A NaN total is passed on as index -1 in the first slot; every output is then NaN.
-struct KeyIdx {
-    int64_t key, idx;
-};
-__host__ __device__ inline bool after(const KeyIdx& a, const KeyIdx& b) { return a.key > b.key || (a.key == b.key && a.idx > b.idx); }
-
+// KeyIdx, after, total_of_sorted and components_of: subbook.hpp (tail_order.hip shares them).
 __global__ __launch_bounds__(scen::kRedLanes * scen::kRedEntries) void alloc_total_kernel(const double* rows, int64_t B, int64_t S_tot,
                                                                                           int base_col, int m, double* tot) {
     constexpr int kLanes = scen::kRedLanes, kEntries = scen::kRedEntries;
@@ -256,14 +252,6 @@ __global__ __launch_bounds__(scen::kRedLanes * scen::kRedEntries) void alloc_tot
         __syncthreads();
     }
     if (cl == 0 && e < m) tot[e] = sh[0][ei];
-}
-
-// The firm's measures from the ordered pairs; both sums run over the first k in order from 0.0.
-__host__ __device__ inline void total_of_sorted(const KeyIdx* pairs, int k, double* var_tot, double* es_tot) {
-    double sum = 0.0;
-    for (int i = 0; i < k; ++i) sum = sum + value_of(pairs[i].key);
-    *var_tot = -value_of(pairs[k - 1].key);
-    *es_tot = -sum / static_cast<double>(k);
 }
 
 // m totals, P = the power of two >= m (the LDS holds P pairs; the padding is +inf with indices m .. P - 1, behind
@@ -306,18 +294,6 @@ __global__ __launch_bounds__(1024) void alloc_order_kernel(double* tot, int m, i
     if (tid == 0) total_of_sorted(pairs, k, var_tot, es_tot);
 }
 
-// A row's components over the k ordered scenarios.
-__host__ __device__ inline void components_of(const double* row, int base_col, const int64_t* order, int k, double* comp_var,
-                                              double* comp_es) {
-    double sum = 0.0, last = 0.0;
-    for (int i = 0; i < k; ++i) {
-        last = pnl_at(row, base_col, static_cast<int>(order[i]));
-        sum = sum + last;
-    }
-    *comp_var = -last;
-    *comp_es = -sum / static_cast<double>(k);
-}
-
 __global__ __launch_bounds__(256) void alloc_rows_kernel(const double* rows, int64_t B, int64_t S_tot, int base_col, int m,
                                                          const int64_t* order, int k, double* comp_var, double* comp_es) {
     const int64_t b = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -347,14 +323,43 @@ int check_alloc(const std::string& w, int64_t B, int S_tot, int base_col, int k)
     return ADR_OK;
 }
 
+hipError_t enqueue_alloc_total(const double* rows, int64_t B, int S_tot, int base_col, double* tot, hipStream_t stream) {
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    hipLaunchKernelGGL(alloc_total_kernel, dim3(static_cast<unsigned>((m + scen::kRedEntries - 1) / scen::kRedEntries)),
+                       dim3(scen::kRedLanes * scen::kRedEntries), 0, stream, rows, B, static_cast<int64_t>(S_tot), base_col, m, tot);
+    return hipGetLastError();
+}
+
+hipError_t enqueue_alloc_rows(const double* rows, int64_t B, int S_tot, int base_col, const int64_t* order, int k, double* comp_var,
+                              double* comp_es, hipStream_t stream) {
+    const int64_t row_blocks = (B + 255) / 256;
+    if (row_blocks > INT32_MAX) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(alloc_rows_kernel, dim3(static_cast<unsigned>(row_blocks)), dim3(256), 0, stream, rows, B,
+                       static_cast<int64_t>(S_tot), base_col, base_col >= 0 ? S_tot - 1 : S_tot, order, k, comp_var, comp_es);
+    return hipGetLastError();
+}
+
+void alloc_total_host(const double* rows, int64_t B, int S_tot, int base_col, double* tot) {
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    adr::parallel_ranges(m, adr::pool_threads(m, 1024), [&](int, int64_t lo, int64_t hi) {
+        for (int64_t e = lo; e < hi; ++e) {
+            double p[kSlots];
+            for (int q = 0; q < kSlots; ++q) {
+                p[q] = 0.0;
+                for (int64_t b = q; b < B; b += kSlots) p[q] = p[q] + pnl_at(rows + b * S_tot, base_col, static_cast<int>(e));
+            }
+            for (int h = kSlots / 2; h >= 1; h >>= 1)
+                for (int q = 0; q < h; ++q) p[q] = p[q] + p[q + h];
+            tot[e] = p[0];
+        }
+    });
+}
+
 hipError_t enqueue_alloc(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var_tot, double* es_tot,
                          double* comp_var, double* comp_es, double* work, hipStream_t stream) {
     const int m = base_col >= 0 ? S_tot - 1 : S_tot, P = pow2_at_least(m);
-    const int64_t row_blocks = (B + 255) / 256;
-    if (row_blocks > INT32_MAX) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(alloc_total_kernel, dim3(static_cast<unsigned>((m + scen::kRedEntries - 1) / scen::kRedEntries)),
-                       dim3(scen::kRedLanes * scen::kRedEntries), 0, stream, rows, B, static_cast<int64_t>(S_tot), base_col, m, work);
-    hipError_t e = hipGetLastError();
+    if ((B + 255) / 256 > INT32_MAX) return hipErrorInvalidConfiguration;
+    hipError_t e = enqueue_alloc_total(rows, B, S_tot, base_col, work, stream);
     if (e != hipSuccess) return e;
     const int threads = std::min(1024, std::max(kWave, P / 2));
     const size_t lds = static_cast<size_t>(P) * sizeof(KeyIdx);
@@ -364,9 +369,7 @@ hipError_t enqueue_alloc(const double* rows, int64_t B, int S_tot, int base_col,
     hipLaunchKernelGGL(alloc_order_kernel, dim3(1), dim3(threads), lds, stream, work, m, P, k, var_tot, es_tot);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(alloc_rows_kernel, dim3(static_cast<unsigned>(row_blocks)), dim3(256), 0, stream, rows, B,
-                       static_cast<int64_t>(S_tot), base_col, m, reinterpret_cast<const int64_t*>(work), k, comp_var, comp_es);
-    return hipGetLastError();
+    return enqueue_alloc_rows(rows, B, S_tot, base_col, reinterpret_cast<const int64_t*>(work), k, comp_var, comp_es, stream);
 }
 
 }  // namespace sub

@@ -125,6 +125,42 @@ inline hipError_t enqueue_tail(const double* rows, int64_t B, int S_tot, int bas
 }
 int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k);
 
+// ---------------------------------------------------------------------------------------------------- tail allocation
+// What subbook.hip's allocation and tail_order.hip's ordered select share: the (key, index) pair and its order, the
+// firm's measures from the ordered pairs and a row's components over the ordered scenarios.
+struct KeyIdx {
+    int64_t key, idx;
+};
+__host__ __device__ inline bool after(const KeyIdx& a, const KeyIdx& b) { return a.key > b.key || (a.key == b.key && a.idx > b.idx); }
+
+// The firm's measures from the ordered pairs; both sums run over the first k in order from 0.0.
+__host__ __device__ inline void total_of_sorted(const KeyIdx* pairs, int k, double* var_tot, double* es_tot) {
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) sum = sum + value_of(pairs[i].key);
+    *var_tot = -value_of(pairs[k - 1].key);
+    *es_tot = -sum / static_cast<double>(k);
+}
+
+// A row's components over the k ordered scenarios.
+__host__ __device__ inline void components_of(const double* row, int base_col, const int64_t* order, int k, double* comp_var,
+                                              double* comp_es) {
+    double sum = 0.0, last = 0.0;
+    for (int i = 0; i < k; ++i) {
+        last = pnl_at(row, base_col, static_cast<int>(order[i]));
+        sum = sum + last;
+    }
+    *comp_var = -last;
+    *comp_es = -sum / static_cast<double>(k);
+}
+
+// The allocation's first and last kernel on their own (tail_order.hip puts its ordered select between them):
+// tot[e] = the fixed-order sum over the rows of pnl[b][e], m values; and every row's components over order[k], NaN in
+// both when order[0] is no scenario.  The host forms are the same sums in the same order.
+hipError_t enqueue_alloc_total(const double* rows, int64_t B, int S_tot, int base_col, double* tot, hipStream_t stream);
+hipError_t enqueue_alloc_rows(const double* rows, int64_t B, int S_tot, int base_col, const int64_t* order, int k, double* comp_var,
+                              double* comp_es, hipStream_t stream);
+void alloc_total_host(const double* rows, int64_t B, int S_tot, int base_col, double* tot);
+
 // The tail allocation of rows[b][S_tot] (adr_scenario_tail_alloc's rule): the firm's var and es and every row's
 // components; `work` holds S_tot doubles; k and the width have been checked.  Three kernels on `stream`.
 hipError_t enqueue_alloc(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var_tot, double* es_tot,

@@ -21,6 +21,19 @@
 // Every round re-reads the whole row (seven reads of the matrix in all): nothing is compacted, so the scratch is the
 // histograms and the tail alone and a round is a pure streaming read.  The kernel boundary is the only
 // synchronisation: no flags, no spin-waits, no float atomics.
+//
+// The ORDERED select (adr_scenario_tail_order*) keeps the scenario index: order[b][k], the first k P&L indices of a row by
+// (key, index) ascending - adr_scenario_tail_alloc's order, ties to the lower index.  The six rounds are the same; then
+//   gather  writes (key, index) pairs to pairs[b][k].  A pair below the threshold key takes a slot from the row's integer
+//           counter (any slot: all of them are taken and the sort places them).  Of the pairs EQUAL to the threshold key
+//           exactly the k_rem with the lowest indices are taken, by rank: the ties of the segments before the block's (the
+//           last round's histograms hold every segment's count of them), of the 256-element chunks before this one (a
+//           running count, uniform over the block) and of the lower lanes of the chunk (a ballot's popcount below the lane,
+//           the four waves' counts meeting in LDS).  A tie of rank r < k_rem goes to slot below + r.  What is selected
+//           depends on no atomic's return value; a block whose segment holds no tie, or whose ties all rank beyond k_rem,
+//           skips the ranking and its barriers.
+//   sort    one block per row: the k pairs in LDS, padded with +inf keys to a power of two, alloc_order_kernel's bitonic
+//           network; it writes order, var and es (thread 0 adds the k values in order), -1 and NaN for a NaN row.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +46,7 @@
 #include "blocking_call.hpp"
 #include "host_pool.hpp"
 #include "subbook.hpp"
+#include "tail_select.hpp"
 
 namespace adr {
 namespace tsel {
@@ -209,8 +223,99 @@ __global__ __launch_bounds__(kThreads) void select_nan_kernel(const RowState* st
     }
 }
 
+// ------------------------------------------------------------------------------------------------------ ordered select
+using sub::KeyIdx;
+constexpr int kWaves = kThreads / 64;
+
+// blockIdx.x = row * nseg + segment; the prefix is the whole threshold key and hist still holds the last round's counts.
+__global__ __launch_bounds__(kThreads) void order_gather_kernel(Args a, KeyIdx* pairs_all) {
+    __shared__ uint32_t wave_part[kWaves];
+    __shared__ uint32_t wave_ties[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t b = blockIdx.x / a.nseg;
+    const int seg = static_cast<int>(blockIdx.x - b * a.nseg);
+    const double* row = a.rows + b * a.S_tot;
+    const int e0 = seg * a.seg_len, e1 = a.m - e0 < a.seg_len ? a.m : e0 + a.seg_len;
+    const uint64_t thr = a.state[b].prefix;                         // uniform: scalar loads
+    const uint32_t k_rem = static_cast<uint32_t>(a.state[b].k_rem); // 1 .. the ties of the row
+    const int below = a.k - static_cast<int>(k_rem);                // the keys under the threshold: fewer than k
+    KeyIdx* pairs = pairs_all + b * a.k;
+    // the ties of the segments before this one, and this segment's own: the last round's bin of the threshold's digit
+    const uint32_t* ties_of = a.hist + static_cast<size_t>(b) * a.nseg * kBins + (static_cast<uint32_t>(thr) & ((1u << bits_of(kRounds - 1)) - 1u));
+    uint32_t part = 0;
+    for (int s = tid; s < seg; s += kThreads) part += ties_of[static_cast<size_t>(s) * kBins];
+    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
+    if (lane == 0) wave_part[wave] = part;
+    __syncthreads();
+    uint32_t run = 0;                                               // the ties before the chunk: uniform over the block
+    for (int w = 0; w < kWaves; ++w) run += wave_part[w];
+    const bool rank_ties = ties_of[static_cast<size_t>(seg) * kBins] != 0 && run < k_rem;   // uniform
+    for (int64_t base = e0; base < e1; base += kThreads) {          // uniform bounds: whole waves stay in the loop
+        const int64_t e = base + tid;
+        const bool in = e < e1;
+        const double v = in ? pnl_at(row, a.base_col, static_cast<int>(e)) : 0.0;
+        const uint64_t u = ukey_of(v);
+        if (in && u < thr) {
+            const int slot = atomicAdd(&a.state[b].count, 1);
+            if (slot < below) pairs[slot] = KeyIdx{key_of(v), e};   // always, unless the counts were wrong: never out of bounds
+        }
+        if (rank_ties && run < k_rem) {                             // uniform: the barriers are met by every wave
+            const bool tie = in && u == thr;
+            const uint64_t mates = __ballot(tie);
+            if (lane == 0) wave_ties[wave] = static_cast<uint32_t>(__popcll(mates));
+            __syncthreads();
+            uint32_t before = 0, chunk = 0;
+            for (int w = 0; w < kWaves; ++w) {
+                const uint32_t c = wave_ties[w];
+                before += w < wave ? c : 0u;
+                chunk += c;
+            }
+            const uint32_t r = run + before + static_cast<uint32_t>(__popcll(mates & ((uint64_t(1) << lane) - 1)));
+            if (tie && r < k_rem) pairs[below + r] = KeyIdx{key_of(v), e};          // below + r < k
+            run += chunk;
+            __syncthreads();                                        // wave_ties is written again in the next chunk
+        }
+    }
+}
+
+// blockIdx.x = row.  P = the power of two >= k (the LDS holds P pairs; the padding is +inf behind every index).
+__global__ __launch_bounds__(1024) void order_sort_kernel(const KeyIdx* pairs_all, const RowState* state, int k, int P, int64_t* order_all,
+                                                          double* var, double* es) {
+    extern __shared__ KeyIdx pairs[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int64_t b = blockIdx.x;
+    int64_t* order = order_all + b * k;
+    if (state[b].nan) {                                             // uniform: a scalar load
+        for (int i = tid; i < k; i += nt) order[i] = -1;
+        if (tid == 0) {
+            var[b] = NAN;
+            es[b] = NAN;
+        }
+        return;
+    }
+    const KeyIdx* in = pairs_all + b * k;
+    for (int e = tid; e < P; e += nt) pairs[e] = e < k ? in[e] : KeyIdx{key_of(INFINITY), INT64_MAX};
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += nt) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const KeyIdx x = pairs[lo], y = pairs[hi];
+                if (sub::after(x, y) == ((lo & size) == 0)) {
+                    pairs[lo] = y;
+                    pairs[hi] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < k; i += nt) order[i] = pairs[i].idx;
+    if (tid == 0) sub::total_of_sorted(pairs, k, var + b, es + b);
+}
+
 // -------------------------------------------------------------------------------------------------------------- host
-int check(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+// k_max pairs or values of a tail fit the LDS; `limit` names that bound in the refusal.
+static int check_sizes(const std::string& w, int64_t B, int S_tot, int base_col, int k, int k_max, const char* limit) {
     if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
     if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
     if (base_col < -1 || base_col >= S_tot)
@@ -220,10 +325,16 @@ int check(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
     if (m < 1) return adr_set_error(ADR_ERR_INVALID, w + ": no P&L value is left beside the base column");
     if (k < 1 || k > m)
         return adr_set_error(ADR_ERR_INVALID, w + ": k must lie in 1 .. " + std::to_string(m) + " (the P&L values per row)");
-    if (k > ADR_SCENARIO_TAIL_MAX)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": a tail of " + std::to_string(k) + " P&L values; a tail of at most "
-                                                  "ADR_SCENARIO_TAIL_MAX (16384) fits the LDS");
+    if (k > k_max)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": a tail of " + std::to_string(k) + " P&L values; a tail of at most " + limit +
+                                                  " fits the LDS");
     return ADR_OK;
+}
+int check(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+    return check_sizes(w, B, S_tot, base_col, k, ADR_SCENARIO_TAIL_MAX, "ADR_SCENARIO_TAIL_MAX (16384)");
+}
+int check_order(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+    return check_sizes(w, B, S_tot, base_col, k, ADR_SCENARIO_ALLOC_MAX, "ADR_SCENARIO_ALLOC_MAX (8192) (key, index) pairs");
 }
 
 // The chain on `stream`; every pointer is device memory, `work` holds layout(B, S_tot, k).bytes.
@@ -255,6 +366,80 @@ int enqueue(const std::string& w, const double* rows, int64_t B, int S_tot, int 
     }
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
+}
+
+// work of the ordered select: state[B] | hist[B][nseg][kBins] uint32 | (to a multiple of 16) pairs[B][k]
+struct OrderLayout {
+    size_t hist, pairs, bytes;
+};
+inline OrderLayout order_layout(int64_t B, int S_tot, int k) {
+    OrderLayout l;
+    l.hist = static_cast<size_t>(B) * sizeof(RowState);
+    l.pairs = (l.hist + static_cast<size_t>(B) * segments(B, S_tot) * kBins * sizeof(uint32_t) + 15) / 16 * 16;
+    l.bytes = l.pairs + static_cast<size_t>(B) * k * sizeof(KeyIdx);
+    return l;
+}
+size_t order_work_bytes(int64_t B, int S_tot, int k) { return order_layout(B, S_tot, k).bytes; }
+
+int enqueue_order(const std::string& w, const double* rows, int64_t B, int S_tot, int base_col, int k, int64_t* order, double* var,
+                  double* es, void* work, hipStream_t stream) {
+    const int nseg = segments(B, S_tot);
+    if (B * nseg > INT32_MAX) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 2^31 (row, segment) pairs in one launch");
+    const OrderLayout l = order_layout(B, S_tot, k);
+    char* base = static_cast<char*>(work);
+    Args a{rows, reinterpret_cast<RowState*>(base), reinterpret_cast<uint32_t*>(base + l.hist), nullptr,
+           S_tot, base_col, base_col >= 0 ? S_tot - 1 : S_tot, k, nseg, segment_len(S_tot, nseg)};
+    KeyIdx* pairs = reinterpret_cast<KeyIdx*>(base + l.pairs);
+    const dim3 grid(static_cast<unsigned>(B * nseg)), rows_grid(static_cast<unsigned>(B)), block(kThreads);
+    hipError_t e = hipMemsetAsync(a.state, 0, l.hist, stream);
+    for (int r = 0; r < kRounds && e == hipSuccess; ++r) {
+        if (r == 0) hipLaunchKernelGGL(select_count_kernel<true>, grid, block, 0, stream, a, r);
+        else hipLaunchKernelGGL(select_count_kernel<false>, grid, block, 0, stream, a, r);
+        hipLaunchKernelGGL(select_scan_kernel, rows_grid, block, 0, stream, a, r);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(order_gather_kernel, grid, block, 0, stream, a, pairs);
+        e = hipGetLastError();
+    }
+    const int P = sub::pow2_at_least(k);
+    const size_t lds = static_cast<size_t>(P) * sizeof(KeyIdx);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&order_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                static_cast<int>(lds));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(order_sort_kernel, rows_grid, dim3(std::min(1024, std::max(64, P / 2))), lds, stream, pairs, a.state, k, P, order,
+                           var, es);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
+    return ADR_OK;
+}
+
+void order_host(const double* rows, int64_t B, int S_tot, int base_col, int k, int64_t* order, double* var, double* es) {
+    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    const auto before = [](const KeyIdx& x, const KeyIdx& y) { return sub::after(y, x); };
+    adr::parallel_ranges(B, adr::pool_threads(B, 4), [&](int, int64_t lo, int64_t hi) {
+        std::vector<KeyIdx> pairs(static_cast<size_t>(m));
+        for (int64_t b = lo; b < hi; ++b) {
+            const double* row = rows + b * S_tot;
+            bool nan = false;
+            for (int e = 0; e < m; ++e) {
+                const double v = pnl_at(row, base_col, e);
+                nan |= v != v;
+                pairs[e] = KeyIdx{key_of(v), e};
+            }
+            if (nan) {
+                var[b] = es[b] = NAN;
+                std::fill(order + b * k, order + (b + 1) * k, int64_t(-1));
+                continue;
+            }
+            std::nth_element(pairs.begin(), pairs.begin() + (k - 1), pairs.end(), before);
+            std::sort(pairs.begin(), pairs.begin() + k, before);
+            for (int i = 0; i < k; ++i) order[b * k + i] = pairs[i].idx;
+            sub::total_of_sorted(pairs.data(), k, var + b, es + b);
+        }
+    });
 }
 
 }  // namespace tsel
@@ -304,6 +489,61 @@ int adr_scenario_tail_select(adr_ctx* ctx, int64_t B, int S_tot, const double* r
     if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(var, dvar, nb * d, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(es, des, nb * d, hipMemcpyDeviceToHost, stream);
     return adr::call::finish_blocking(w, rc, e, stream, base);
+}
+
+int64_t adr_scenario_tail_order_work(int64_t B, int S_tot, int k) {
+    if (B < 1 || S_tot < 1 || k < 1 || k > ADR_SCENARIO_ALLOC_MAX) return 0;
+    return static_cast<int64_t>(TS::order_work_bytes(B, S_tot, k));
+}
+
+int adr_scenario_tail_order_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k, int64_t* order_dev,
+                                double* var_dev, double* es_dev, void* work_dev, void* stream) {
+    const std::string w = "adr_scenario_tail_order_dev";
+    if (!ctx) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx");
+    int rc = TS::check_order(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows_dev || !order_dev || !var_dev || !es_dev) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    if (!work_dev) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_scenario_tail_order_work bytes are needed)");
+    hipStream_t st = nullptr;
+    rc = adr::call::target_stream(w, ctx, static_cast<hipStream_t>(stream), &st);
+    if (rc != ADR_OK) return rc;
+    return TS::enqueue_order(w, rows_dev, B, S_tot, base_col, k, order_dev, var_dev, es_dev, work_dev, st);
+}
+
+int adr_scenario_tail_order(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, int64_t* order, double* var,
+                            double* es) {
+    const std::string w = "adr_scenario_tail_order";
+    if (!ctx) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx");
+    int rc = TS::check_order(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !order || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    hipStream_t stream = nullptr;
+    rc = adr::call::target_stream(w, ctx, nullptr, &stream);
+    if (rc != ADR_OK) return rc;
+    // one allocation: the rows, the order, var and es, the scratch
+    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot, nb = static_cast<size_t>(B), nk = nb * k;
+    const size_t head = (R + nk + 2 * nb) * d, work_at = (head + 15) / 16 * 16;
+    char* base = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), work_at + TS::order_work_bytes(B, S_tot, k));
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
+    double* drows = reinterpret_cast<double*>(base);
+    int64_t* dorder = reinterpret_cast<int64_t*>(drows + R);
+    double *dvar = drows + R + nk, *des = dvar + nb;
+    e = hipMemcpyAsync(drows, rows, R * d, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) rc = TS::enqueue_order(w, drows, B, S_tot, base_col, k, dorder, dvar, des, base + work_at, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(order, dorder, nk * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(var, dvar, nb * d, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(es, des, nb * d, hipMemcpyDeviceToHost, stream);
+    return adr::call::finish_blocking(w, rc, e, stream, base);
+}
+
+int adr_scenario_tail_order_host(int64_t B, int S_tot, const double* rows, int base_col, int k, int64_t* order, double* var, double* es) {
+    const std::string w = "adr_scenario_tail_order_host";
+    const int rc = TS::check_order(w, B, S_tot, base_col, k);
+    if (rc != ADR_OK) return rc;
+    if (!rows || !order || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
+    TS::order_host(rows, B, S_tot, base_col, k, order, var, es);
+    return ADR_OK;
 }
 
 int adr_scenario_tail_select_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es) {

@@ -19,6 +19,15 @@ in the ladder's order and in basis points:
     >>> monte_carlo_var_es(None, None, factor_from_covariance(cov_Q_bp2), 262_144, ladders=out["ladders"])
     >>> out = price_yoy_sub_books(engine, disc_curve, infl_curve, swaps, desk_keys, reqs)
     >>> monte_carlo_var_es(out["delta"], out["gamma"], factor_from_covariance(cov_Q_bp2), 262_144)
+
+The firm's question - how much of the FIRM's VaR and expected shortfall each desk carries - is `monte_carlo_allocate_tail`:
+the firm's P&L is `ladder_pnl` of one row, the fixed-order sum of the desks' rows; adr_scenario_tail_order (an ordered radix
+select, ties to the lower scenario index) hands out the firm's ``k`` worst scenarios; every desk is priced at those ``k``
+shock rows alone.  No ``[B, S]`` matrix is made, and the components add up to the firm's figures:
+
+    >>> risk = sub_book_monte_carlo_allocate_tail(engine, curve, trades, desk_keys, L, 262_144, level=0.99, seed=7)
+    >>> risk["var"], risk["es"], risk["comp_es"]                 # the firm's, and [B] shares with sum(comp_es) = es
+    >>> monte_carlo_shocks(L, 1, 7, first_scenario=int(risk["scenarios"][0]))     # the firm's worst scenario, made again
 """
 from __future__ import annotations
 
@@ -87,10 +96,26 @@ def tail_measures_select(rows, level: float = 0.99, base_col: int = -1, host: bo
     return _native.scenario_tail_select(ctx or _native.default_context(), rows, k, base_col)
 
 
-def _check_tail_count(k, level, m):
-    if k > _native.SCENARIO_TAIL_MAX:
-        raise LibError(f"a tail of {k} P&L values (level {level}, {m} values per row): at most {_native.SCENARIO_TAIL_MAX} "
+def _check_tail_count(k, level, m, limit=None):
+    limit = _native.SCENARIO_TAIL_MAX if limit is None else limit
+    if k > limit:
+        raise LibError(f"a tail of {k} P&L values (level {level}, {m} values per row): at most {limit} "
                        "fit the tail kernel", status=_native.ADR_ERR_UNSUPPORTED)
+
+
+def allocate_tail_select(rows, level: float = 0.99, base_col: int = -1, host: bool = False, ctx=None):
+    """`allocate_tail` without the row limit, on the device for any width: ``{"var", "es", "comp_var" [B], "comp_es" [B]}`` of
+    ``rows [B, S]`` (adr_scenario_tail_alloc_select; ``host=True``: its CPU twin, the same bits).  The firm's ``k`` worst
+    scenarios come from the ordered tail select (adr_scenario_tail_order) on the fixed-order column sums, so the limit is on
+    the tail: a `LibError` with ``ADR_ERR_UNSUPPORTED`` when ``tail_count(level, S)`` exceeds ``_native.SCENARIO_ALLOC_MAX``.
+    Where `allocate_tail`'s kernel takes the rows the result has its bits; beyond, those of the rule as NumPy states it
+    (`scenarios._allocate_tail_numpy`)."""
+    rows, m, k = _tail_args(rows, base_col, level, 1)
+    _check_tail_count(k, level, m, _native.SCENARIO_ALLOC_MAX)
+    rows = np.ascontiguousarray(rows)
+    if host:
+        return _native.scenario_tail_alloc_select_host(rows, k, base_col)
+    return _native.scenario_tail_alloc_select(ctx or _native.default_context(), rows, k, base_col)
 
 
 def monte_carlo_var_es(delta, gamma, factor_bp, n_scenarios: int, level: float = 0.99, seed: int = 0, antithetic: bool = False,
@@ -107,16 +132,7 @@ def monte_carlo_var_es(delta, gamma, factor_bp, n_scenarios: int, level: float =
     and the result is `tail_measures_select` of `ladder_pnl` of `monte_carlo_shocks` (device shocks), bit for bit.
     ``host=True``: the three CPU twins, tile by tile; no GPU needed.  Where torch brings a HIP runtime of its own, import
     torch before the first call into this library, as the tools do."""
-    if ladders is None:
-        rows = ladder_rows(delta, gamma)
-    else:
-        if delta is not None or gamma is not None:
-            raise LibError("give delta and gamma, or ladders, not both")
-        rows = np.ascontiguousarray(ladders, dtype=np.float64)
-    factor = np.ascontiguousarray(factor_bp, dtype=np.float64)
-    if rows.ndim != 2 or factor.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] != 1 + factor.shape[0] * (1 + factor.shape[0]):
-        raise LibError(f"ladder rows [B, 1 + P + P P] and factor_bp [P, F] are needed, not {list(rows.shape)} and "
-                       f"{list(factor.shape)}")
+    rows, factor = _ladder_args(delta, gamma, factor_bp, ladders)
     (B, width), (P, F), S = rows.shape, factor.shape, int(n_scenarios)
     if S < 1:
         raise LibError("at least one scenario is needed")
@@ -148,6 +164,112 @@ def monte_carlo_var_es(delta, gamma, factor_bp, n_scenarios: int, level: float =
     ctx.sync()
     out = var_es.cpu().numpy()
     return {"var": out[0].copy(), "es": out[1].copy()}
+
+
+def _ladder_args(delta, gamma, factor_bp, ladders):
+    """``(rows [B, 1 + P + P P], factor [P, F])`` as `monte_carlo_var_es` and `monte_carlo_allocate_tail` take them."""
+    if ladders is None:
+        rows = ladder_rows(delta, gamma)
+    else:
+        if delta is not None or gamma is not None:
+            raise LibError("give delta and gamma, or ladders, not both")
+        rows = np.ascontiguousarray(ladders, dtype=np.float64)
+    factor = np.ascontiguousarray(factor_bp, dtype=np.float64)
+    if rows.ndim != 2 or factor.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] != 1 + factor.shape[0] * (1 + factor.shape[0]):
+        raise LibError(f"ladder rows [B, 1 + P + P P] and factor_bp [P, F] are needed, not {list(rows.shape)} and "
+                       f"{list(factor.shape)}")
+    return rows, factor
+
+
+def firm_ladder(ladders) -> np.ndarray:
+    """``[1 + P + P P]``: the firm's ladder row, the fixed-order sum of the desks' rows ``ladders [B, 1 + P + P P]`` -
+    `allocate_tail`'s column-sum rule (row ``b`` to slot ``b % 64`` in row order from 0.0, then the halving tree) on every
+    column (adr_scenario_total_host; the device's kernel gives the same bits).  Delta-gamma P&L is linear in the row, so
+    `ladder_pnl` of this row is the firm's P&L."""
+    return _native.scenario_total_host(ladders)
+
+
+def monte_carlo_allocate_tail(delta, gamma, factor_bp, n_scenarios: int, level: float = 0.99, seed: int = 0, antithetic: bool = False,
+                              host: bool = False, ctx=None, max_bytes: int = 2 ** 31, ladders=None) -> dict:
+    """``{"var", "es", "comp_var" [B], "comp_es" [B], "scenarios" [k]}``: the FIRM's Monte Carlo delta-gamma VaR and expected
+    shortfall and how much of each every desk carries - the Euler allocation that adds up to the firm's figure - under
+    ``n_scenarios`` normal shocks.  The arguments are `monte_carlo_var_es`'s, ``ladders=`` included.
+
+    No ``[B, S]`` matrix is made.  Delta-gamma P&L is linear in the ladder row, so the firm's P&L under every shock is
+    adr_ladder_pnl of ONE row, `firm_ladder` of the desks' rows (adr_scenario_total_dev); the ordered tail select
+    (adr_scenario_tail_order_dev) hands out the firm's ``k = tail_count(level, n_scenarios)`` worst scenarios as indices in
+    the firm's order - ties to the lower index - with the firm's ``var`` and ``es``; those shock rows are gathered
+    (adr_shock_gather_dev) and every desk is priced at them alone, ``[tile, k]`` at a time under ``max_bytes``
+    (adr_ladder_pnl_dev, then adr_tail_components_dev), all on one stream with torch tensors as buffers.  Only the results
+    leave the device; ``scenarios`` are the global scenario indices in the firm's order, and a row of the shock set can be
+    made again from ``seed`` and its index alone (`monte_carlo_shocks` with ``first_scenario``).
+
+    Bit for bit, whatever the tiling: every output is the CPU twins' chain on the device's shocks; ``var`` and ``es`` are
+    `monte_carlo_var_es` of the firm's row (``ladders=firm_ladder(rows)[None]``); ``comp_*`` are `allocate_tail`'s component
+    sums over the columns ``scenarios`` of the full ``ladder_pnl(rows, shocks)``.  The firm's P&L comes from the firm's
+    LADDER, not from column sums of desk P&Ls as in `allocate_tail_select` of that matrix: the two differ by rounding, at
+    most ``(P P + P + B + 8) eps A_s`` with ``A_s`` the sum of the absolute terms of scenario ``s``, so the two agree on
+    ``scenarios`` and ``comp_*`` wherever the firm's ``k + 1`` smallest totals lie further apart than that, and then on
+    ``var`` and ``es`` to that rounding.  ``sum(comp_es)`` is ``es`` and ``sum(comp_var)`` is ``var`` to rounding.
+
+    The ``k`` pairs are sorted in LDS: ``k > _native.SCENARIO_ALLOC_MAX`` is a `LibError` with ``ADR_ERR_UNSUPPORTED``
+    (1 048 576 scenarios at 99 %; 99.5 % fits, and so do 786 432 at 99 %).  A NaN in the firm's row gives NaN everywhere and
+    ``scenarios`` of -1.  ``host=True``: the CPU twins of every step on the host's shocks; no GPU needed."""
+    rows, factor = _ladder_args(delta, gamma, factor_bp, ladders)
+    (B, width), (P, F), S = rows.shape, factor.shape, int(n_scenarios)
+    if S < 1:
+        raise LibError("at least one scenario is needed")
+    k = tail_count(level, S)
+    _check_tail_count(k, level, S, _native.SCENARIO_ALLOC_MAX)
+    tile = int(max(1, min(B, int(max_bytes) // (8 * k))))
+    tiles = [(b0, min(tile, B - b0)) for b0 in range(0, B, tile)]
+    if host:
+        shocks = _native.shock_normal_host(factor, S, seed, antithetic, 0)
+        tot = _native.ladder_pnl_host(firm_ladder(rows)[None], shocks)["pnl"]
+        order, var, es = _native.scenario_tail_order_host(tot, k)
+        gathered = _native.shock_gather_host(shocks, order[0])
+        comp = np.empty((2, B))
+        for b0, nb in tiles:
+            comp[0, b0:b0 + nb], comp[1, b0:b0 + nb] = _native.tail_components_host(
+                _native.ladder_pnl_host(rows[b0:b0 + nb], gathered)["pnl"])
+        return {"var": float(var[0]), "es": float(es[0]), "comp_var": comp[0].copy(), "comp_es": comp[1].copy(), "scenarios": order[0].copy()}
+
+    import torch
+    ctx = ctx or _native.default_context()
+    dev = torch.device("cuda", ctx.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    d_rows, d_factor, firm, shocks, tot = up(rows), up(factor), new(width), new(S, P), new(S)
+    gathered, pnl, out = new(k, P), new(tile, k), new(2, B + 1)         # out: [comp_var | var], [comp_es | es]
+    order = torch.empty(k, dtype=torch.int64, device=dev)
+    work = torch.empty(_native.scenario_tail_order_work(1, S, k), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    _native.scenario_total_dev(ctx, B, width, d_rows.data_ptr(), firm.data_ptr())
+    _native.shock_normal_dev(ctx, seed, 0, S, P, F, d_factor.data_ptr(), antithetic, shocks.data_ptr())
+    _native.ladder_pnl_dev(ctx, 1, P, firm.data_ptr(), S, shocks.data_ptr(), tot.data_ptr())
+    _native.scenario_tail_order_dev(ctx, 1, S, tot.data_ptr(), k, order.data_ptr(), out.data_ptr() + 8 * B,
+                                    out.data_ptr() + 8 * (2 * B + 1), work.data_ptr())
+    _native.shock_gather_dev(ctx, k, P, shocks.data_ptr(), S, order.data_ptr(), gathered.data_ptr())
+    for b0, nb in tiles:
+        _native.ladder_pnl_dev(ctx, nb, P, d_rows.data_ptr() + 8 * width * b0, k, gathered.data_ptr(), pnl.data_ptr())
+        _native.tail_components_dev(ctx, nb, k, pnl.data_ptr(), out.data_ptr() + 8 * b0, out.data_ptr() + 8 * (B + 1 + b0))
+    ctx.sync()
+    res, scenarios = out.cpu().numpy(), order.cpu().numpy()
+    return {"var": float(res[0, B]), "es": float(res[1, B]), "comp_var": res[0, :B].copy(), "comp_es": res[1, :B].copy(),
+            "scenarios": scenarios}
+
+
+def sub_book_monte_carlo_allocate_tail(engine, ir_model, trades, keys, factor_bp, n_scenarios: int, level: float = 0.99, seed: int = 0,
+                                       antithetic: bool = False, host: bool = False) -> dict:
+    """`monte_carlo_allocate_tail` straight from the trades, with ``labels``: `price_sub_books` (one ladder launch) and then
+    the chain on ``ir_model``'s pillars, as `sub_book_monte_carlo_var_es` does for the desks' own figures."""
+    from .sub_book_ladders import price_sub_books
+    reqs = {RequestTypes.VALUE, RequestTypes.DELTA, RequestTypes.GAMMA}
+    out = price_sub_books(engine, ir_model, trades, keys, reqs, host=host)
+    ctx = None if host else engine._device_curve(ir_model)["ctx"]
+    risk = monte_carlo_allocate_tail(out["delta"], out["gamma"], factor_bp, n_scenarios, level=level, seed=seed, antithetic=antithetic,
+                                     host=host, ctx=ctx)
+    return {"labels": out["labels"], **risk}
 
 
 def sub_book_monte_carlo_var_es(engine, ir_model, trades, keys, factor_bp, n_scenarios: int, level: float = 0.99, seed: int = 0,

@@ -1005,6 +1005,86 @@ int adr_scenario_tail_select_host(int64_t B, int S_tot, const double* rows, int 
 int64_t adr_scenario_tail_select_work(int64_t B, int S_tot, int k);
 
 /*
+ * The ordered tail select: a row's k worst scenarios as INDICES, in the row's order - what the tail allocation needs of
+ * the firm's P&L.  rows[B][S_tot], base_col and k are read as adr_scenario_tail_select reads them; pnl[b][e] is P&L value
+ * e of row b.  The scenarios of a row are ordered by (key(pnl[b][e]), e) ascending: adr_scenario_tail's total order of
+ * the doubles (-0.0 before +0.0), ties to the lower scenario index - adr_scenario_tail_alloc's rule.  With e_1, e_2, ..
+ * that order:
+ *
+ *   order[b][0 .. k-1] = e_1 .. e_k   int64, P&L indices: the base column is not counted, as in adr_scenario_tail_alloc
+ *   var[b] = -pnl[b][e_k];   es[b] = -(pnl[b][e_1] + .. + pnl[b][e_k]) / k, added in that order from 0.0
+ *
+ * so var and es have adr_scenario_tail_select's bits.  A row holding a NaN gives var = es = NaN and order[b][.] = -1, and
+ * touches no other row.  1 <= k <= ADR_SCENARIO_ALLOC_MAX (k pairs of 16 bytes are sorted in LDS); a larger k is
+ * ADR_ERR_UNSUPPORTED, the other refusals are adr_scenario_tail_select's; the row may have any width.
+ *
+ * Device: adr_scenario_tail_select's six count / scan rounds find the k-th key; a gather then writes (key, index) pairs.
+ * Pairs below the k-th key take any slot.  Of the pairs EQUAL to it exactly the k_rem with the lowest indices are taken,
+ * by rank: the ties of earlier segments (the last round's histograms), of earlier 256-element chunks of the block (a
+ * running count) and of lower lanes (ballot and popcount); rank r < k_rem goes to slot below + r.  What is selected
+ * depends on no atomic's return value and not on the order in which blocks and waves arrive.  One block per row then
+ * sorts the k pairs (adr_scenario_tail_alloc's bitonic network, padded with +inf) and writes order, var and es.  Only
+ * integer atomics; the kernel boundary is the only synchronisation; two runs give the same bits.
+ * adr_scenario_tail_order: host arrays, blocks (one allocation); _dev: device arrays and work_dev -
+ * adr_scenario_tail_order_work(B, S_tot, k) bytes, 16-byte aligned, contents free - on `stream` (NULL: the ctx's own), no
+ * allocation, no synchronisation; _host: the CPU twin - std::nth_element on the pairs, a sort of the first k, the same
+ * sums - the same bits.  adr_scenario_tail_order_work returns 0 for sizes the entries refuse.
+ */
+int adr_scenario_tail_order(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, int64_t* order, double* var,
+                            double* es);
+int adr_scenario_tail_order_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k, int64_t* order_dev,
+                                double* var_dev, double* es_dev, void* work_dev, void* stream);
+int adr_scenario_tail_order_host(int64_t B, int S_tot, const double* rows, int base_col, int k, int64_t* order, double* var, double* es);
+int64_t adr_scenario_tail_order_work(int64_t B, int S_tot, int k);
+
+/*
+ * adr_scenario_tail_alloc for a matrix of any width: the same outputs, the same sums in the same order, NaN everywhere
+ * when a total is NaN.  The limit moves from the row to the tail: 1 <= k <= ADR_SCENARIO_ALLOC_MAX, beyond that
+ * ADR_ERR_UNSUPPORTED; the other refusals are adr_scenario_tail_alloc's.  Where adr_scenario_tail_alloc takes the rows the
+ * results have its bits.  Device: its column-sum kernel, adr_scenario_tail_order on the one-row tot, its components
+ * kernel.  adr_scenario_tail_alloc_select: host arrays, blocks (one allocation); _dev: device arrays and work_dev -
+ * adr_scenario_tail_alloc_select_work(B, S_tot, k) bytes, 16-byte aligned - on `stream`, no allocation, no
+ * synchronisation; _host: the CPU twin, the same bits.  _work returns 0 for sizes the entries refuse.
+ *
+ * adr_scenario_total*: tot[e] alone, m values (S_tot, or S_tot - 1 with a base column) - the fixed-order column sums of
+ * adr_scenario_tail_alloc.  On ladder rows [B][1 + P + P P] with base_col = -1 it is the firm's ladder row.
+ */
+int adr_scenario_tail_alloc_select(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, int base_col, int k, double* var_tot,
+                                   double* es_tot, double* comp_var, double* comp_es);
+int adr_scenario_tail_alloc_select_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, int k,
+                                       double* var_tot_dev, double* es_tot_dev, double* comp_var_dev, double* comp_es_dev,
+                                       void* work_dev, void* stream);
+int adr_scenario_tail_alloc_select_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var_tot, double* es_tot,
+                                        double* comp_var, double* comp_es);
+int64_t adr_scenario_tail_alloc_select_work(int64_t B, int S_tot, int k);
+int adr_scenario_total_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows_dev, int base_col, double* tot_dev, void* stream);
+int adr_scenario_total_host(int64_t B, int S_tot, const double* rows, int base_col, double* tot);
+
+/*
+ * The two steps between the firm's order and the desks' components in a Monte Carlo tail allocation (delta-gamma P&L is
+ * linear in the ladder row: the firm's P&L is adr_ladder_pnl of the sum of the desks' rows, and a desk is priced at the
+ * firm's k worst shocks alone).
+ *
+ * adr_shock_gather*: out[i][p] = shocks[order[i]][p] for i < k; shocks[S][P], order[k] as adr_scenario_tail_order writes
+ * it.  When order[0] is negative (the firm's row held a NaN) every out value is NaN, and so is row i when order[i] is
+ * no row of shocks: adr_ladder_pnl* then turns every desk's figures into NaN without a host round trip.  k >= 1, S >= 1,
+ * 1 <= P <= ADR_LADDER_PNL_MAX_PILLARS, else ADR_ERR_INVALID.
+ *
+ * adr_tail_components*: pnl[B][k] holds every row's P&L at the firm's k worst scenarios, in the firm's order:
+ *   comp_es[b] = -(pnl[b][0] + .. + pnl[b][k-1]) / k, added in that order from 0.0;   comp_var[b] = -pnl[b][k-1]
+ * - adr_scenario_tail_alloc's component sums, so on the gathered columns of a matrix they have its bits.  B >= 1, k >= 1.
+ *
+ * _dev: device arrays, one kernel on `stream` (NULL: the ctx's own), no allocation, no synchronisation, scalar checks
+ * only; _host: the CPU twin, the same bits.
+ */
+int adr_shock_gather_dev(adr_ctx* ctx, int k, int P, const double* shocks_dev, int S, const int64_t* order_dev, double* out_dev,
+                         void* stream);
+int adr_shock_gather_host(int k, int P, const double* shocks, int S, const int64_t* order, double* out);
+int adr_tail_components_dev(adr_ctx* ctx, int64_t B, int k, const double* pnl_dev, double* comp_var_dev, double* comp_es_dev,
+                            void* stream);
+int adr_tail_components_host(int64_t B, int k, const double* pnl, double* comp_var, double* comp_es);
+
+/*
  * Credit sub-book Greeks: per sub-book the PV, the curve delta and gamma AT THE TRADES' SPREADS, CS01 and spread gamma
  * per credit bucket and the rate x spread cross gamma, from one launch chain.  The spread side is adr_credit_scenario_pv's:
  * z[n] (z-spread of a bond, discount margin of an FRN), bucket[n] in -1 .. G - 1 (-1: no bucket), 0 <= G <=
