@@ -15,6 +15,7 @@
 
 #include "../../include/adrates.h"
 #include "curve_tables.hpp"
+#include "device_owner.hpp"
 #include "host_pool.hpp"
 #include "kernels.hpp"
 #include "route.hpp"
@@ -41,14 +42,17 @@ int fail_hip(hipError_t e, const char* what) {
         if (e__ != hipSuccess) return fail_hip(e__, #call); \
     } while (0)
 
-template <typename T>
-hipError_t upload(const std::vector<T>& host, T** dev) {
-    *dev = nullptr;
-    if (host.empty()) return hipSuccess;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dev), host.size() * sizeof(T));
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+// The interpolation schemes the kernels implement; `who`: the entry point, for the message.
+int check_interp(int method, const char* who) {
+    if (method == ADR_INTERP_FLAT_FWD_RATES || method == ADR_INTERP_LINEAR_ZERO_RATES || method == ADR_INTERP_LINEAR_FWD_RATES)
+        return ADR_OK;
+    return fail(ADR_ERR_UNSUPPORTED, std::string(who) + ": only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and "
+                                                        "LINEAR_ZERO_RATES (4) are implemented");
 }
+
+// Every array of a batch and of its schedule groups has this much room behind it: the kernels' neighbour reads (a header's
+// worth past the last element) never leave the buffer.  The curve arrays have none: the kernels read them by table sizes.
+constexpr size_t kBatchPad = 64;
 
 }  // namespace
 
@@ -71,13 +75,51 @@ struct adr_ctx {
 namespace {
 namespace R = adr::route;
 constexpr int kKnotStrideMax = std::max(1 + 3 * R::kKnotMaxKc, 1 + (2 + adr::kKnotBand) * R::kKnotLagMaxKc);
+
+// The structural half of a curve's device image - everything that follows from the knot grid and the sparsity of the
+// Jacobians, not from the curve's values: uploads those tables into `mem` and sets every such field of `c`.  An uploaded
+// curve (adr_curve_upload_ex) adds its value arrays, a curve plan (adr_curve_plan_create) shares this half among the curves
+// built from it, so a field set here is set for both.  `wide`: the wide layout's index tables are wanted (the callers decide
+// differently).  Returns with its copies done (they read vectors of this function); errors are left in `mem`.
+void fill_curve_structure(const adr::CurveTables& t, int method, const R::CurveClass& cls, bool wide, adr::DeviceOwner& mem,
+                          hipStream_t stream, adr::CurveDev& c) {
+    const std::vector<int16_t> first16(t.first_of.begin(), t.first_of.end()), comp16(t.compact_of.begin(), t.compact_of.end());
+    const std::vector<unsigned long long> mask(t.lc_block_mask.begin(), t.lc_block_mask.end());
+    c.K = t.K; c.Kc = t.Kc; c.P = t.P; c.method = method;
+    c.T = t.T; c.tile_i = c.tile_j = 0;
+    c.x = mem.put(t.x, stream); c.inv_x = mem.put(t.inv_x, stream);
+    c.first_of = mem.put(first16, stream); c.compact_of = mem.put(comp16, stream);
+    c.lut = mem.put(t.lut, stream); c.n_lut = static_cast<int>(t.lut.size() / 2);
+    c.lc_block_mask = mem.put(mask, stream);
+    // wide layout (33-64 pillars): the whole ladder in one launch when its LDS image fits, else one launch per tile pair
+    c.wide_nch = cls.wide_nch;
+    if (wide) {
+        c.wide_ent = mem.put(t.wide_ent, stream); c.wide_store_map = mem.put(t.wide_store_map, stream);
+        c.wide_pos = mem.put(t.wide_pos, stream); c.wide_order = mem.put(t.wide_order, stream);
+        if (t.has_hess) c.wide_knot_chunks = mem.put(t.wide_knot_chunks, stream);
+    }
+    // the fast kernels store the [P][P] matrices as 16-byte pairs of the flat array: P must be even
+    // LINEAR_FWD_RATES is linear in the knot DFs, not in their logs: only the general kernel carries the extra
+    // Hessian term (kernels_general.hip, `Lookup`)
+    c.packed_ok = cls.packed_ok;
+    c.odd_last = t.odd_last;
+    c.Pc = t.Pc; c.pc_pad = t.pc_pad; c.Ec = t.Ec; c.Eu = t.Eu; c.epg = t.epg; c.cpg = t.cpg; c.hub = t.hub ? 1 : 0;
+    c.Kcore = t.Kcore; c.n_mini = t.n_mini; c.fringe_start = t.fringe_start; c.n_fringe = t.n_fringe; c.fringe_own = t.fringe_own ? 1 : 0;
+    if (t.packed_ok) {
+        c.knot_class = mem.put(t.knot_class, stream); c.pillar_to_core = mem.put(t.pillar_to_core, stream);
+        c.out_map = mem.put(t.out_map, stream); c.store_map = mem.put(t.store_map, stream);
+        c.ent_pq = mem.put(t.ent_pq, stream);
+        c.core_pos = mem.put(t.core_pos, stream); c.lcc_pos = mem.put(t.lcc_pos, stream);
+    }
+    mem.note(hipStreamSynchronize(stream));       // (also on errors: the copies read this function's vectors)
+}
 }
 
 struct adr_curve {
     adr_ctx* ctx = nullptr;
     adr::CurveDev dev{};
     R::CurveClass cls{};                 // what the launch plan reads (route.hpp)
-    std::vector<void*> allocations;
+    adr::DeviceOwner mem;
 };
 
 // Rate-independent description of one knot grid: its bootstrap scan and the table layout of the base curve.
@@ -89,7 +131,7 @@ struct adr_curve_plan {
     adr::CurveBuildPlanDev dev{};
     adr::CurveDev shared{};              // the structural device arrays every built curve points at
     R::CurveClass cls{};                 // ... and the class of every built curve
-    std::vector<void*> allocations;
+    adr::DeviceOwner mem;
 };
 
 // Curves built together on the device; `curves` are views into the set's slabs.
@@ -99,7 +141,7 @@ struct adr_curve_set {
     int n = 0;
     double *dfs = nullptr, *jac = nullptr, *hess = nullptr;   // dense [n][K], [n][K][P], [n][K][P][P]
     std::vector<adr_curve> curves;
-    std::vector<void*> allocations;
+    adr::DeviceOwner mem;
 };
 
 struct adr_trades {
@@ -115,7 +157,7 @@ struct adr_trades {
     // per-wave stash of the payment-lag variant (kernels.hpp, OutputsDev::lag_scratch), sized for a grid of counts.lag_blocks
     // blocks.  It belongs to the BATCH (not to the ctx): two batches priced on two streams never share it.
     double* lag_scratch = nullptr;
-    std::vector<void*> allocations;
+    adr::DeviceOwner mem;
 
     // Schedule groups (schedule_groups.hpp).  The upload finds the groups and keeps them on the host;
     // the device tables of the groups in use under `mode` are (re)built by apply_schedule_groups - at upload and when
@@ -131,7 +173,17 @@ struct adr_trades {
         int64_t used_groups = 0, used_trades = 0;
         adr::CombineDev combine{};
         adr::TradesDev basis{}, ungrouped{}; // row tables: two pseudo-trades per group / the plain rows outside the groups
-        std::vector<void*> allocations;
+        // An empty array is a real buffer here (the batch's own are null): when no group in use has a fixed leg, or none a
+        // float leg, the basis batch has flow arrays of no elements, and its row builder and the fast kernel are handed
+        // those pointers whatever the counts; that neither ever forms a read from a null one has not been shown.
+        adr::DeviceOwner mem{true};
+        // Releases the device tables: no grouped route.  Returns the error the owner held.
+        hipError_t reset() {
+            active = false;
+            used_groups = used_trades = 0;
+            combine = adr::CombineDev{};
+            return mem.release();
+        }
     } grouping;
 
     // The plan of the last (curve class, request) this batch was priced with: built on first use, replayed afterwards.  A
@@ -226,34 +278,26 @@ int adr_init(int device_ordinal, adr_ctx** out) {
     ctx->n_cu = prop.multiProcessorCount;
     ctx->lds_limit = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor
                                                            : prop.sharedMemPerBlock;
+    // (every failure from here on releases what the ctx holds so far through adr_free_ctx, which tests each member)
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete ctx; return fail_hip(e, "hipStreamCreate"); }
+    if (e != hipSuccess) { adr_free_ctx(ctx); return fail_hip(e, "hipStreamCreate"); }
     const R::Grid grid = R::grid_for(ctx->n_cu);
     ctx->max_blocks = grid.max_blocks;
     e = hipMalloc(reinterpret_cast<void**>(&ctx->partials),
                   sizeof(double) * static_cast<size_t>(ctx->max_blocks) * adr::kAggStride);
-    if (e != hipSuccess) { hipStreamDestroy(ctx->stream); delete ctx; return fail_hip(e, "hipMalloc(partials)"); }
+    if (e != hipSuccess) { adr_free_ctx(ctx); return fail_hip(e, "hipMalloc(partials)"); }
     e = hipMalloc(reinterpret_cast<void**>(&ctx->dump), sizeof(double) * adr::kPillarPad * adr::kPillarPad);
-    if (e != hipSuccess) {
-        hipFree(ctx->partials); hipStreamDestroy(ctx->stream); delete ctx;
-        return fail_hip(e, "hipMalloc(dump)");
-    }
+    if (e != hipSuccess) { adr_free_ctx(ctx); return fail_hip(e, "hipMalloc(dump)"); }
     ctx->knot_blocks = grid.knot_blocks;
     e = hipMalloc(reinterpret_cast<void**>(&ctx->knot_partials),
                   sizeof(double) * (static_cast<size_t>(ctx->knot_blocks + 1) * kKnotStrideMax + static_cast<size_t>(R::kKnotLagMaxKc) * R::kKnotLagMaxKc + 1));
-    if (e != hipSuccess) {
-        hipFree(ctx->dump); hipFree(ctx->partials); hipStreamDestroy(ctx->stream); delete ctx;
-        return fail_hip(e, "hipMalloc(knot partials)");
-    }
+    if (e != hipSuccess) { adr_free_ctx(ctx); return fail_hip(e, "hipMalloc(knot partials)"); }
     ctx->knot_reduced = ctx->knot_partials + static_cast<size_t>(ctx->knot_blocks) * kKnotStrideMax;
     ctx->knot_overflow = ctx->knot_reduced + kKnotStrideMax;
     // Dynamic-LDS ceiling of every kernel instantiation, once per device: the whole 160 KiB of a CU.  (Setting it per
     // uploaded curve to that curve's need would LOWER it below what an earlier, larger curve's launches request.)
     e = adr::set_kernel_lds_limits(kLdsBudget, kLdsBudget);
-    if (e != hipSuccess) {
-        hipFree(ctx->knot_partials); hipFree(ctx->dump); hipFree(ctx->partials); hipStreamDestroy(ctx->stream); delete ctx;
-        return fail_hip(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
+    if (e != hipSuccess) { adr_free_ctx(ctx); return fail_hip(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)"); }
 #ifdef ADR_STAMPS
     hipMalloc(reinterpret_cast<void**>(&ctx->stamps), sizeof(unsigned long long) * ctx->max_blocks * 16 * 8);
     hipMemset(ctx->stamps, 0, sizeof(unsigned long long) * ctx->max_blocks * 16 * 8);
@@ -329,7 +373,7 @@ int adr_curve_layout_host(int K, int P, const double* times, const double* dfs, 
 void adr_free_curve(adr_curve* curve) {
     if (!curve) return;
     if (curve->ctx) hipSetDevice(curve->ctx->device);
-    for (void* p : curve->allocations) hipFree(p);
+    curve->mem.release();
     delete curve;
 }
 
@@ -346,10 +390,7 @@ int adr_curve_upload_ex(adr_ctx* ctx, int interp_method, int K, int P, const dou
     *out = nullptr;
     if (flags & ~static_cast<uint32_t>(ADR_CURVE_PILLAR_TILES))
         return fail(ADR_ERR_INVALID, "adr_curve_upload_ex: unknown flag bits");
-    if (interp_method != ADR_INTERP_FLAT_FWD_RATES && interp_method != ADR_INTERP_LINEAR_ZERO_RATES &&
-        interp_method != ADR_INTERP_LINEAR_FWD_RATES)
-        return fail(ADR_ERR_UNSUPPORTED, "adr_curve_upload: only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and "
-                                         "LINEAR_ZERO_RATES (4) are implemented");
+    if (const int rc = check_interp(interp_method, "adr_curve_upload")) return rc;
     if (P > ADR_MAX_PILLARS)
         return fail(ADR_ERR_UNSUPPORTED, "adr_curve_upload: more than ADR_MAX_PILLARS (256) pillars");
     adr::CurveTables t;
@@ -364,76 +405,25 @@ int adr_curve_upload_ex(adr_ctx* ctx, int interp_method, int K, int P, const dou
     adr_curve* c = new (std::nothrow) adr_curve();
     if (!c) return fail(ADR_ERR_NOMEM, "adr_curve_upload: out of memory");
     c->ctx = ctx;
-    std::vector<int16_t> first16(t.first_of.begin(), t.first_of.end());
-    std::vector<int16_t> comp16(t.compact_of.begin(), t.compact_of.end());
-    double *d_x = nullptr, *d_log = nullptr, *d_invx = nullptr, *d_lj = nullptr, *d_lc = nullptr;
-    double *d_ljc = nullptr, *d_lcc = nullptr;
-    int16_t *d_first = nullptr, *d_comp = nullptr, *d_class = nullptr, *d_p2c = nullptr, *d_omap = nullptr;
-    int16_t* d_smap = nullptr;
-    uint8_t* d_pq = nullptr;
-    int16_t *d_cpos = nullptr, *d_lpos = nullptr;
-    adr::MiniKnot* d_mini = nullptr;
-    hipError_t e = hipSuccess;
-    auto track = [&](hipError_t r, void* p) { if (p) c->allocations.push_back(p); if (e == hipSuccess) e = r; };
-    track(upload(t.x, &d_x), d_x);
-    track(upload(t.log_df, &d_log), d_log);
-    track(upload(t.inv_x, &d_invx), d_invx);
-    track(upload(t.lj, &d_lj), d_lj);
-    track(upload(t.lc_lanes, &d_lc), d_lc);
-    unsigned long long* d_lcmask = nullptr;
-    {
-        std::vector<unsigned long long> m(t.lc_block_mask.begin(), t.lc_block_mask.end());
-        track(upload(m, &d_lcmask), d_lcmask);
-    }
-    track(upload(first16, &d_first), d_first);
-    track(upload(comp16, &d_comp), d_comp);
-    int16_t* d_lut = nullptr;
-    track(upload(t.lut, &d_lut), d_lut);
-    // wide layout (33-64 pillars): the whole ladder in one launch when its LDS image fits, else one launch per tile pair
-    double *d_lj64 = nullptr, *d_lcflat = nullptr;
-    uint32_t *d_went = nullptr, *d_wchunks = nullptr, *d_wsmap = nullptr;
-    int32_t *d_wpos = nullptr, *d_worder = nullptr;
     c->cls = R::curve_class(t, interp_method, (flags & ADR_CURVE_PILLAR_TILES) != 0);
+    adr::DeviceOwner& mem = c->mem;
+    adr::CurveDev& d = c->dev;
+    hipStream_t stream = ctx->stream;
+    // The value arrays; the structural half last, because it waits for the stream: `t` outlives every copy, and the curve
+    // is returned only with its tables on the device.
+    d.log_df = mem.put(t.log_df, stream); d.lj = mem.put(t.lj, stream); d.lc_lanes = mem.put(t.lc_lanes, stream);
     const bool wide = c->cls.wide_nch > 0;
     if (wide) {
-        track(upload(t.lj64, &d_lj64), d_lj64);
-        track(upload(t.wide_ent, &d_went), d_went);
-        track(upload(t.wide_store_map, &d_wsmap), d_wsmap);
-        track(upload(t.wide_pos, &d_wpos), d_wpos);
-        track(upload(t.wide_order, &d_worder), d_worder);
-        if (t.has_hess) {
-            track(upload(t.lcflat, &d_lcflat), d_lcflat);
-            track(upload(t.wide_knot_chunks, &d_wchunks), d_wchunks);
-        }
+        d.lj64 = mem.put(t.lj64, stream);
+        if (t.has_hess) d.lcflat = mem.put(t.lcflat, stream);
     }
-    if (t.packed_ok) {
-        track(upload(t.ljc, &d_ljc), d_ljc);
-        track(upload(t.lcc, &d_lcc), d_lcc);
-        track(upload(t.knot_class, &d_class), d_class);
-        track(upload(t.pillar_to_core, &d_p2c), d_p2c);
-        track(upload(t.out_map, &d_omap), d_omap);
-        track(upload(t.store_map, &d_smap), d_smap);
-        track(upload(t.ent_pq, &d_pq), d_pq);
-        track(upload(t.core_pos, &d_cpos), d_cpos);
-        track(upload(t.lcc_pos, &d_lpos), d_lpos);
-        track(upload(t.mini, &d_mini), d_mini);
+    if (t.packed_ok) { d.ljc = mem.put(t.ljc, stream); d.lcc = mem.put(t.lcc, stream); d.mini = mem.put(t.mini, stream); }
+    fill_curve_structure(t, interp_method, c->cls, wide, mem, stream, d);
+    if (!mem.ok()) {
+        const hipError_t e = mem.error;
+        adr_free_curve(c);
+        return fail_hip(e, "adr_curve_upload: copying tables");
     }
-    if (e != hipSuccess) { adr_free_curve(c); return fail_hip(e, "adr_curve_upload: copying tables"); }
-    c->dev.K = t.K; c->dev.Kc = t.Kc; c->dev.P = t.P; c->dev.method = interp_method;
-    c->dev.T = t.T; c->dev.tile_i = c->dev.tile_j = 0;
-    c->dev.x = d_x; c->dev.log_df = d_log; c->dev.inv_x = d_invx; c->dev.lj = d_lj; c->dev.lc_lanes = d_lc; c->dev.lc_block_mask = d_lcmask;
-    c->dev.first_of = d_first; c->dev.compact_of = d_comp; c->dev.lut = d_lut; c->dev.n_lut = static_cast<int>(t.lut.size() / 2);
-    c->dev.wide_nch = c->cls.wide_nch;
-    c->dev.lj64 = d_lj64; c->dev.wide_ent = d_went; c->dev.lcflat = d_lcflat; c->dev.wide_knot_chunks = d_wchunks; c->dev.wide_store_map = d_wsmap; c->dev.wide_pos = d_wpos; c->dev.wide_order = d_worder;
-    // the fast kernels store the [P][P] matrices as 16-byte pairs of the flat array: P must be even
-    // LINEAR_FWD_RATES is linear in the knot DFs, not in their logs: only the general kernel carries the extra
-    // Hessian term (kernels_general.hip, `Lookup`)
-    c->dev.packed_ok = c->cls.packed_ok;
-    c->dev.odd_last = t.odd_last;
-    c->dev.Pc = t.Pc; c->dev.pc_pad = t.pc_pad; c->dev.Ec = t.Ec; c->dev.Eu = t.Eu; c->dev.epg = t.epg; c->dev.cpg = t.cpg; c->dev.hub = t.hub ? 1 : 0;
-    c->dev.Kcore = t.Kcore; c->dev.n_mini = t.n_mini; c->dev.fringe_start = t.fringe_start; c->dev.n_fringe = t.n_fringe; c->dev.fringe_own = t.fringe_own ? 1 : 0;
-    c->dev.ljc = d_ljc; c->dev.lcc = d_lcc; c->dev.mini = d_mini; c->dev.knot_class = d_class;
-    c->dev.pillar_to_core = d_p2c; c->dev.out_map = d_omap; c->dev.store_map = d_smap; c->dev.ent_pq = d_pq; c->dev.core_pos = d_cpos; c->dev.lcc_pos = d_lpos;
     *out = c;
     return ADR_OK;
 }
@@ -456,16 +446,15 @@ int adr_curve_df(adr_ctx* ctx, const adr_curve* curve, int64_t n, const double* 
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(t[i])) return fail(ADR_ERR_INVALID, "adr_curve_df: times must be finite");
     ADR_HIP(hipSetDevice(ctx->device));
-    double *d_t = nullptr, *d_df = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_t), sizeof(double) * static_cast<size_t>(n));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_df), sizeof(double) * static_cast<size_t>(n));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream);
+    adr::DeviceOwner tmp;                     // the call's two device arrays
+    double* d_t = tmp.put_n(t, static_cast<size_t>(n), ctx->stream);
+    double* d_df = tmp.array<double>(static_cast<size_t>(n));
     int rc = ADR_OK;
-    if (e == hipSuccess) rc = adr_curve_df_dev(ctx, curve, n, d_t, d_df, nullptr);
-    if (e == hipSuccess && rc == ADR_OK)
-        e = hipMemcpyAsync(df, d_df, sizeof(double) * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d_t); hipFree(d_df);
+    if (tmp.ok()) rc = adr_curve_df_dev(ctx, curve, n, d_t, d_df, nullptr);
+    if (tmp.ok() && rc == ADR_OK)
+        tmp.note(hipMemcpyAsync(df, d_df, sizeof(double) * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
+    if (tmp.ok() && rc == ADR_OK) tmp.note(hipStreamSynchronize(ctx->stream));
+    const hipError_t e = tmp.release();
     if (rc != ADR_OK) return rc;
     if (e != hipSuccess) return fail_hip(e, "adr_curve_df");
     return ADR_OK;
@@ -475,7 +464,7 @@ int adr_curve_df(adr_ctx* ctx, const adr_curve* curve, int64_t n, const double* 
 void adr_free_curve_plan(adr_curve_plan* plan) {
     if (!plan) return;
     if (plan->ctx) hipSetDevice(plan->ctx->device);
-    for (void* p : plan->allocations) hipFree(p);
+    plan->mem.release();
     delete plan;
 }
 
@@ -484,10 +473,7 @@ int adr_curve_plan_create(adr_ctx* ctx, int interp_method, int K, int P, const d
                           const double* base_jac, const double* base_hess, adr_curve_plan** out) {
     if (!ctx || !out) return fail(ADR_ERR_INVALID, "adr_curve_plan_create: null ctx/out");
     *out = nullptr;
-    if (interp_method != ADR_INTERP_FLAT_FWD_RATES && interp_method != ADR_INTERP_LINEAR_ZERO_RATES &&
-        interp_method != ADR_INTERP_LINEAR_FWD_RATES)
-        return fail(ADR_ERR_UNSUPPORTED, "adr_curve_plan_create: only FLAT_FWD_RATES (1), LINEAR_FWD_RATES (2) and "
-                                         "LINEAR_ZERO_RATES (4) are implemented");
+    if (const int rc = check_interp(interp_method, "adr_curve_plan_create")) return rc;
     if (P > ADR_MAX_PLAN_PILLARS)
         return fail(ADR_ERR_UNSUPPORTED, "adr_curve_plan_create: more than ADR_MAX_PLAN_PILLARS (64) pillars");
     if (!acc || !pillar || !prev_idx) return fail(ADR_ERR_INVALID, "adr_curve_plan_create: null scan arrays");
@@ -516,78 +502,32 @@ int adr_curve_plan_create(adr_ctx* ctx, int interp_method, int K, int P, const d
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) { delete plan; return fail_hip(e, "hipSetDevice"); }
 
-    std::vector<double> acc_v(acc, acc + K);
-    std::vector<int32_t> pil_v(pillar, pillar + K), prev_v(prev_idx, prev_idx + K);
-    std::vector<int16_t> first16(t.first_of.begin(), t.first_of.end()), comp16(t.compact_of.begin(), t.compact_of.end());
     std::vector<int32_t> core_pillars;
     for (int p = 0; p < P; ++p)
         if (t.packed_ok && t.pillar_to_core[p] < t.Pc) core_pillars.push_back(p);
-    double *d_acc = nullptr, *d_x = nullptr, *d_invx = nullptr;
-    int32_t *d_pil = nullptr, *d_prev = nullptr, *d_kidx = nullptr, *d_core = nullptr;
-    int16_t *d_first = nullptr, *d_comp = nullptr, *d_class = nullptr, *d_p2c = nullptr, *d_omap = nullptr;
-    int16_t* d_smap = nullptr;
-    uint8_t *d_pq = nullptr, *d_lccpq = nullptr;
-    int16_t *d_cpos = nullptr, *d_lpos = nullptr;
-    auto track = [&](hipError_t r, void* p) { if (p) plan->allocations.push_back(p); if (e == hipSuccess) e = r; };
-    track(upload(acc_v, &d_acc), d_acc);
-    track(upload(pil_v, &d_pil), d_pil);
-    track(upload(prev_v, &d_prev), d_prev);
-    track(upload(t.knot_index, &d_kidx), d_kidx);
-    unsigned long long* d_lcmask = nullptr;
-    {
-        std::vector<unsigned long long> m(t.lc_block_mask.begin(), t.lc_block_mask.end());
-        track(upload(m, &d_lcmask), d_lcmask);
-    }
-    track(upload(t.x, &d_x), d_x);
-    track(upload(t.inv_x, &d_invx), d_invx);
-    track(upload(first16, &d_first), d_first);
-    track(upload(comp16, &d_comp), d_comp);
-    int16_t* d_lut = nullptr;
-    track(upload(t.lut, &d_lut), d_lut);
-    uint32_t *d_went = nullptr, *d_wchunks = nullptr, *d_wsmap = nullptr;
-    int32_t *d_wpos = nullptr, *d_worder = nullptr;
-    uint8_t* d_wpq = nullptr;
-    if (wide) {
-        track(upload(t.wide_ent, &d_went), d_went);
-        track(upload(t.wide_store_map, &d_wsmap), d_wsmap);
-        track(upload(t.wide_pos, &d_wpos), d_wpos);
-        track(upload(t.wide_order, &d_worder), d_worder);
-        track(upload(t.wide_pq, &d_wpq), d_wpq);
-        if (plan->has_hess) track(upload(t.wide_knot_chunks, &d_wchunks), d_wchunks);
-    }
-    if (t.packed_ok) {
-        track(upload(core_pillars, &d_core), d_core);
-        track(upload(t.knot_class, &d_class), d_class);
-        track(upload(t.pillar_to_core, &d_p2c), d_p2c);
-        track(upload(t.out_map, &d_omap), d_omap);
-        track(upload(t.store_map, &d_smap), d_smap);
-        track(upload(t.ent_pq, &d_pq), d_pq);
-        track(upload(t.lcc_pq, &d_lccpq), d_lccpq);
-        track(upload(t.core_pos, &d_cpos), d_cpos);
-        track(upload(t.lcc_pos, &d_lpos), d_lpos);
-    }
-    if (e != hipSuccess) { adr_free_curve_plan(plan); return fail_hip(e, "adr_curve_plan_create: copying tables"); }
-
-    adr::CurveBuildPlanDev& d = plan->dev;
-    d.K = K; d.P = P; d.Kc = t.Kc; d.acc = d_acc; d.pillar = d_pil; d.prev_idx = d_prev; d.knot_index = d_kidx;
+    adr::DeviceOwner& mem = plan->mem;
+    hipStream_t stream = ctx->stream;
     R::CurveClass& cls = plan->cls;
     cls = R::curve_class(t, interp_method, false);
     if (!cls.packed_ok) cls.lds_rows = 0;   // (the built curves carry the convexity rows only with the packed layout)
+    // The scan arrays, read from the caller's; the structural half last, because it waits for the stream: the caller's
+    // arrays, `core_pillars` and the plan's tables outlive every copy.
+    adr::CurveBuildPlanDev& d = plan->dev;
+    d.K = K; d.P = P; d.Kc = t.Kc;
+    d.acc = mem.put_n(acc, static_cast<size_t>(K), stream); d.pillar = mem.put_n(pillar, static_cast<size_t>(K), stream);
+    d.prev_idx = mem.put_n(prev_idx, static_cast<size_t>(K), stream); d.knot_index = mem.put(t.knot_index, stream);
     d.packed_ok = cls.packed_ok;
     d.Pc = t.Pc; d.pc_pad = t.pc_pad; d.Ec = t.Ec; d.Kcore = t.Kcore; d.n_mini = t.n_mini;
-    d.knot_class = d_class; d.core_pillars = d_core; d.lcc_pq = d_lccpq;
-    d.wide_nch = cls.wide_nch; d.wide_pq = d_wpq; d.dpv_global = dpv_global ? 1 : 0;
-
-    adr::CurveDev& c = plan->shared;
-    c.K = t.K; c.Kc = t.Kc; c.P = t.P; c.method = interp_method; c.T = t.T; c.tile_i = c.tile_j = 0;
-    c.wide_nch = d.wide_nch; c.wide_ent = d_went; c.wide_store_map = d_wsmap; c.wide_pos = d_wpos; c.wide_order = d_worder;
-    c.wide_knot_chunks = d_wchunks;
-    c.x = d_x; c.inv_x = d_invx; c.first_of = d_first; c.compact_of = d_comp; c.lc_block_mask = d_lcmask;
-    c.lut = d_lut; c.n_lut = static_cast<int>(t.lut.size() / 2);
-    c.packed_ok = d.packed_ok;
-    c.odd_last = t.odd_last;
-    c.Pc = t.Pc; c.pc_pad = t.pc_pad; c.Ec = t.Ec; c.Eu = t.Eu; c.epg = t.epg; c.cpg = t.cpg; c.hub = t.hub ? 1 : 0; c.Kcore = t.Kcore; c.n_mini = t.n_mini; c.fringe_start = t.fringe_start; c.n_fringe = t.n_fringe; c.fringe_own = t.fringe_own ? 1 : 0;
-    c.knot_class = d_class; c.pillar_to_core = d_p2c; c.out_map = d_omap; c.store_map = d_smap; c.ent_pq = d_pq; c.core_pos = d_cpos; c.lcc_pos = d_lpos;
+    d.wide_nch = cls.wide_nch; d.dpv_global = dpv_global ? 1 : 0;
+    if (wide) d.wide_pq = mem.put(t.wide_pq, stream);
+    if (t.packed_ok) { d.core_pillars = mem.put(core_pillars, stream); d.lcc_pq = mem.put(t.lcc_pq, stream); }
+    fill_curve_structure(t, interp_method, cls, wide, mem, stream, plan->shared);
+    d.knot_class = plan->shared.knot_class;
+    if (!mem.ok()) {
+        e = mem.error;
+        adr_free_curve_plan(plan);
+        return fail_hip(e, "adr_curve_plan_create: copying tables");
+    }
     *out = plan;
     return ADR_OK;
 }
@@ -595,7 +535,7 @@ int adr_curve_plan_create(adr_ctx* ctx, int interp_method, int K, int P, const d
 void adr_free_curve_set(adr_curve_set* set) {
     if (!set) return;
     if (set->ctx) hipSetDevice(set->ctx->device);
-    for (void* p : set->allocations) hipFree(p);
+    set->mem.release();
     delete set;
 }
 
@@ -621,53 +561,50 @@ int adr_curve_set_build(adr_ctx* ctx, const adr_curve_plan* plan, int n_scen, co
     set->ctx = ctx; set->plan = plan; set->n = n_scen;
     if (n_scen == 0) { *out = set; return ADR_OK; }
 
-    hipError_t e = hipSuccess;
-    auto alloc = [&](size_t bytes, bool zero) -> void* {
-        if (bytes == 0 || e != hipSuccess) return nullptr;
-        void* p = nullptr;
-        e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return nullptr;
-        set->allocations.push_back(p);
-        if (zero) e = hipMemsetAsync(p, 0, bytes, ctx->stream);
-        return p;
-    };
+    // The set's slabs, one per table with a leading scenario axis (null for an absent table); those the build adds into
+    // or leaves partly unwritten are zeroed.
+    adr::DeviceOwner& mem = set->mem;
+    hipStream_t stream = ctx->stream;
     const bool hs = plan->has_hess, packed = plan->dev.packed_ok != 0;
-    double* d_rates = static_cast<double*>(alloc(sizeof(double) * S * P, false));
-    set->dfs = static_cast<double*>(alloc(sizeof(double) * S * K, false));
-    set->jac = static_cast<double*>(alloc(sizeof(double) * S * K * P, false));
-    set->hess = hs ? static_cast<double*>(alloc(sizeof(double) * S * K * P * P, false)) : nullptr;
+    double* d_rates = mem.put_n(rates, S * P, stream);
+    set->dfs = mem.array<double>(S * K);
+    set->jac = mem.array<double>(S * K * P);
+    set->hess = hs ? mem.array<double>(S * K * P * P) : nullptr;
     adr::CurvePackOut po{};
-    po.log_df = static_cast<double*>(alloc(sizeof(double) * S * Kc, false));
+    po.log_df = mem.array<double>(S * Kc);
     const bool wide = plan->dev.wide_nch > 0;
     const size_t wrow = static_cast<size_t>(plan->dev.wide_nch) * adr::kWideChunk;
     if (wide) {
-        po.lj64 = static_cast<double*>(alloc(sizeof(double) * S * Kc * adr::kWidePad, false));
-        po.lcflat = hs ? static_cast<double*>(alloc(sizeof(double) * S * Kc * wrow, true)) : nullptr;
+        po.lj64 = mem.array<double>(S * Kc * adr::kWidePad);
+        po.lcflat = hs ? static_cast<double*>(mem.alloc_zeroed(sizeof(double) * S * Kc * wrow, stream)) : nullptr;
     } else {
-        po.lj = static_cast<double*>(alloc(sizeof(double) * S * Kc * adr::kPillarPad, false));
-        po.lc_lanes = hs ? static_cast<double*>(alloc(sizeof(double) * S * Kc * 64 * adr::kGammaPerLane, false)) : nullptr;
+        po.lj = mem.array<double>(S * Kc * adr::kPillarPad);
+        po.lc_lanes = hs ? mem.array<double>(S * Kc * 64 * adr::kGammaPerLane) : nullptr;
     }
     const size_t ljc_n = static_cast<size_t>(t.Kcore + 1) * t.pc_pad, lcc_n = static_cast<size_t>(t.Kcore + 1) * (t.Ec + 1);
     if (packed) {
-        po.ljc = static_cast<double*>(alloc(sizeof(double) * S * ljc_n, true));
-        po.lcc = hs ? static_cast<double*>(alloc(sizeof(double) * S * lcc_n, true)) : nullptr;
-        po.mini = static_cast<adr::MiniKnot*>(alloc(sizeof(adr::MiniKnot) * S * std::max(1, t.n_mini), false));
+        po.ljc = static_cast<double*>(mem.alloc_zeroed(sizeof(double) * S * ljc_n, stream));
+        po.lcc = hs ? static_cast<double*>(mem.alloc_zeroed(sizeof(double) * S * lcc_n, stream)) : nullptr;
+        po.mini = mem.array<adr::MiniKnot>(S * std::max(1, t.n_mini));
     }
     // scratch of the scan's second-derivative state; released once the build has run
-    double *d_scratch = nullptr, *d_dpv = nullptr;
-    if (hs && e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_scratch), sizeof(double) * S * K * P * P);
-    if (plan->dev.dpv_global && e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_dpv), sizeof(double) * S * K * P);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rates, rates, sizeof(double) * S * P, hipMemcpyHostToDevice, ctx->stream);
+    adr::DeviceOwner tmp;
+    double* d_scratch = hs && mem.ok() ? tmp.array<double>(S * K * P * P) : nullptr;
+    double* d_dpv = plan->dev.dpv_global && mem.ok() ? tmp.array<double>(S * K * P) : nullptr;
+    mem.note(tmp.error);
     if (packed && t.n_mini > 0)
-        for (size_t s = 0; s < S && e == hipSuccess; ++s)   // pillar / entry fields of the short-end records
-            e = hipMemcpyAsync(po.mini + s * t.n_mini, t.mini.data(), sizeof(adr::MiniKnot) * t.n_mini,
-                               hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = adr::launch_curve_build(plan->dev, n_scen, d_rates, set->dfs, set->jac, set->hess, d_scratch, d_dpv, po, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (d_scratch) hipFree(d_scratch);
-    if (d_dpv) hipFree(d_dpv);
-    if (e != hipSuccess) { adr_free_curve_set(set); return fail_hip(e, "adr_curve_set_build"); }
+        for (size_t s = 0; s < S && mem.ok(); ++s)   // pillar / entry fields of the short-end records
+            mem.note(hipMemcpyAsync(po.mini + s * t.n_mini, t.mini.data(), sizeof(adr::MiniKnot) * t.n_mini,
+                                    hipMemcpyHostToDevice, stream));
+    if (mem.ok())
+        mem.note(adr::launch_curve_build(plan->dev, n_scen, d_rates, set->dfs, set->jac, set->hess, d_scratch, d_dpv, po, stream));
+    mem.note(hipStreamSynchronize(stream));      // (also on errors: the copies read the caller's rates)
+    tmp.release();
+    if (!mem.ok()) {
+        const hipError_t e = mem.error;
+        adr_free_curve_set(set);
+        return fail_hip(e, "adr_curve_set_build");
+    }
 
     set->curves.resize(S);
     for (size_t s = 0; s < S; ++s) {
@@ -710,8 +647,8 @@ int adr_curve_set_download(const adr_curve_set* set, int i, double* dfs, double*
 void adr_free_trades(adr_trades* t) {
     if (!t) return;
     if (t->ctx) hipSetDevice(t->ctx->device);
-    for (void* p : t->grouping.allocations) hipFree(p);
-    for (void* p : t->allocations) hipFree(p);
+    t->grouping.mem.release();
+    t->mem.release();
     delete t;
 }
 
@@ -728,164 +665,108 @@ constexpr int kScheduleMinGroup = 64;
 constexpr int64_t kScheduleMinGrouped = 32768;
 constexpr int kScheduleSegment = 16;         // records per wave of the store pass (kernels_combine.hip)
 
-// (Re)builds the device tables of the batch's schedule groups for its current knobs.  Allocates and synchronises: never
-// called from adr_price_dev, and not while a pricing call on the batch is in flight.
+// One row table of the fast kernel (kernels.hpp): 32 zero-padded slots per row and array, gathered on the device
+// (trades_build.hip) from the work list - `piece_trade`: the row's trade, or -1 for an empty row; a chained table also has
+// `piece_first` (first coupon of the piece) and `piece_more` ("the trade continues"), any other passes null for both.  Fills
+// the row fields of `dst` and nothing else of it; an empty list is a table of no rows and launches nothing.  The lists must
+// outlive the copies (DeviceOwner::put).
+void build_row_table(const adr::CsrDev& csr, const std::vector<int32_t>& piece_trade, const std::vector<int32_t>* piece_first,
+                     const std::vector<uint8_t>* piece_more, bool lagged, bool weighted, adr::DeviceOwner& mem, hipStream_t stream,
+                     adr::TradesDev& dst) {
+    dst.n_rows = 0;
+    if (piece_trade.empty()) return;
+    const size_t rows = piece_trade.size(), S = adr::kRowSlots;
+    adr::RowBuildDev rb{};
+    rb.rows = static_cast<int64_t>(rows);
+    rb.piece_trade = mem.put(piece_trade, stream, kBatchPad);
+    rb.piece_first = piece_first ? mem.put(*piece_first, stream, kBatchPad) : nullptr;
+    rb.piece_more = piece_more ? mem.put(*piece_more, stream, kBatchPad) : nullptr;
+    rb.row_tp = mem.array<double>(rows * S, kBatchPad);
+    rb.row_ts = mem.array<double>(rows * S, kBatchPad);
+    rb.row_alpha = mem.array<double>(rows * S, kBatchPad);
+    rb.row_xtp = mem.array<double>(rows * S, kBatchPad);
+    rb.row_xpay = mem.array<double>(rows * S, kBatchPad);
+    rb.row_te = lagged ? mem.array<double>(rows * S, kBatchPad) : nullptr;
+    rb.row_w = (lagged && weighted) ? mem.array<double>(rows * S, kBatchPad) : nullptr;
+    rb.row_notional = mem.array<double>(rows, kBatchPad);
+    rb.row_spread = mem.array<double>(rows, kBatchPad);
+    rb.row_meta = mem.array<int32_t>(rows, kBatchPad);
+    rb.row_trade = mem.array<int32_t>(rows, kBatchPad);
+    if (mem.ok()) mem.note(adr::launch_build_rows(csr, rb, stream));
+    dst.n_rows = static_cast<int64_t>(rows);
+    dst.row_tp = rb.row_tp; dst.row_ts = rb.row_ts; dst.row_alpha = rb.row_alpha; dst.row_xtp = rb.row_xtp; dst.row_xpay = rb.row_xpay;
+    dst.row_notional = rb.row_notional; dst.row_spread = rb.row_spread; dst.row_meta = rb.row_meta; dst.row_trade = rb.row_trade;
+    dst.rows_chained = piece_first ? 1 : 0;
+    dst.rows_lagged = lagged ? 1 : 0;
+    dst.row_te = rb.row_te; dst.row_w = rb.row_w;
+}
+
+// (Re)builds the device tables of the batch's schedule groups for its current knobs: the host image of the groups in use
+// (schedule_groups.hpp, build_group_tables), uploaded.  Allocates and synchronises: never called from adr_price_dev, and not
+// while a pricing call on the batch is in flight.
 hipError_t apply_schedule_groups(adr_trades* tr) {
     adr_trades::Grouping& G = tr->grouping;
+    adr::DeviceOwner& mem = G.mem;
     hipStream_t stream = tr->ctx->stream;
-    hipError_t e = hipStreamSynchronize(stream);
-    for (void* p : G.allocations) hipFree(p);
-    G.allocations.clear();
-    G.active = false;
-    G.used_groups = G.used_trades = 0;
-    G.combine = adr::CombineDev{};
-    if (e != hipSuccess) return e;
-    const adr::ScheduleGroups& F = G.found;
-    if (G.mode == ADR_SCHEDULE_GROUPS_OFF || F.n_groups == 0) return hipSuccess;
+    const hipError_t e0 = hipStreamSynchronize(stream);       // first: nothing on the stream reads the tables released next
+    G.reset();
+    if (e0 != hipSuccess) return e0;
+    if (G.mode == ADR_SCHEDULE_GROUPS_OFF || G.found.n_groups == 0) return hipSuccess;
+    const bool force = G.mode == ADR_SCHEDULE_GROUPS_FORCE;
+    const adr::GroupTables T = adr::build_group_tables(G.found, G.rows_order.data(), static_cast<int64_t>(G.rows_order.size()),
+                                                       force ? 2 : kScheduleMinGroup, force ? 0 : kScheduleMinGrouped,
+                                                       G.segment > 0 ? G.segment : kScheduleSegment);
+    if (T.used_groups == 0) return hipSuccess;             // route not taken
+    const size_t ng = static_cast<size_t>(T.used_groups);
 
-    // the groups in use, renumbered in order
-    const int min_group = G.mode == ADR_SCHEDULE_GROUPS_FORCE ? 2 : kScheduleMinGroup;
-    std::vector<int32_t> new_id(static_cast<size_t>(F.n_groups), -1);
-    std::vector<int64_t> first;              // first record of every group in use, then the total
-    for (int64_t g = 0; g < F.n_groups; ++g)
-        if (F.size[static_cast<size_t>(g)] >= min_group) {
-            new_id[static_cast<size_t>(g)] = static_cast<int32_t>(G.used_groups++);
-            first.push_back(G.used_trades);
-            G.used_trades += F.size[static_cast<size_t>(g)];
-        }
-    first.push_back(G.used_trades);
-    if (G.used_groups == 0 || (G.mode == ADR_SCHEDULE_GROUPS_AUTO && G.used_trades < kScheduleMinGrouped)) {
-        G.used_groups = G.used_trades = 0;
-        return hipSuccess;
-    }
-    const size_t ng = static_cast<size_t>(G.used_groups);
-
-    // records sorted by group, in trade order inside a group; the coefficient sums in trade order
-    std::vector<adr::GroupRecord> rec(static_cast<size_t>(G.used_trades));
-    std::vector<double> sum_f(ng, 0.0), sum_x(ng, 0.0);
-    {
-        std::vector<int64_t> at(first.begin(), first.end() - 1);
-        const int64_t n = static_cast<int64_t>(F.group_of.size());
-        for (int64_t t = 0; t < n; ++t) {
-            const int32_t old = F.group_of[static_cast<size_t>(t)];
-            const int32_t g = old >= 0 ? new_id[static_cast<size_t>(old)] : -1;
-            if (g < 0) continue;
-            rec[static_cast<size_t>(at[static_cast<size_t>(g)]++)] =
-                adr::GroupRecord{static_cast<int32_t>(t), g, F.cF[static_cast<size_t>(t)], F.cX[static_cast<size_t>(t)], 0};
-            sum_f[static_cast<size_t>(g)] += F.cF[static_cast<size_t>(t)];
-            sum_x[static_cast<size_t>(g)] += F.cX[static_cast<size_t>(t)];
-        }
-    }
-    // segments: no wave straddles two groups
-    const int R = G.segment > 0 ? G.segment : kScheduleSegment;
-    std::vector<adr::GroupSegment> seg;
-    for (size_t g = 0; g < ng; ++g)
-        for (int64_t at = first[g]; at < first[g + 1]; at += R)
-            seg.push_back(adr::GroupSegment{static_cast<int32_t>(g), static_cast<int32_t>(at),
-                                            static_cast<int32_t>(std::min<int64_t>(R, first[g + 1] - at)), 0});
-    // the plain rows outside the groups in use, in the table's order
-    std::vector<int32_t> rest;
-    for (int32_t t : G.rows_order) {
-        const int32_t old = F.group_of[static_cast<size_t>(t)];
-        if (old < 0 || new_id[static_cast<size_t>(old)] < 0) rest.push_back(t);
-    }
-    // the basis trades of the groups in use: a small CSR batch of their own
-    std::vector<int64_t> b_fix_off(1, 0), b_flt_off(1, 0);
-    std::vector<double> b_fix_tp, b_fix_pay, b_flt_tp, b_flt_ts, b_flt_te, b_flt_alpha, b_notional, b_spread;
-    for (int64_t g = 0; g < F.n_groups; ++g) {
-        if (new_id[static_cast<size_t>(g)] < 0) continue;
-        for (int64_t k = 2 * g; k < 2 * g + 2; ++k) {
-            const size_t f0 = static_cast<size_t>(F.fix_off[static_cast<size_t>(k)]), f1 = static_cast<size_t>(F.fix_off[static_cast<size_t>(k) + 1]);
-            const size_t l0 = static_cast<size_t>(F.flt_off[static_cast<size_t>(k)]), l1 = static_cast<size_t>(F.flt_off[static_cast<size_t>(k) + 1]);
-            b_fix_tp.insert(b_fix_tp.end(), F.fix_tp.begin() + f0, F.fix_tp.begin() + f1);
-            b_fix_pay.insert(b_fix_pay.end(), F.fix_pay.begin() + f0, F.fix_pay.begin() + f1);
-            b_flt_tp.insert(b_flt_tp.end(), F.flt_tp.begin() + l0, F.flt_tp.begin() + l1);
-            b_flt_ts.insert(b_flt_ts.end(), F.flt_ts.begin() + l0, F.flt_ts.begin() + l1);
-            b_flt_te.insert(b_flt_te.end(), F.flt_te.begin() + l0, F.flt_te.begin() + l1);
-            b_flt_alpha.insert(b_flt_alpha.end(), F.flt_alpha.begin() + l0, F.flt_alpha.begin() + l1);
-            b_fix_off.push_back(static_cast<int64_t>(b_fix_tp.size()));
-            b_flt_off.push_back(static_cast<int64_t>(b_flt_tp.size()));
-            b_notional.push_back(F.notional[static_cast<size_t>(k)]);
-            b_spread.push_back(F.spread[static_cast<size_t>(k)]);
-        }
-    }
-    const std::vector<double> b_sign(2 * ng, 1.0);
-    std::vector<int32_t> b_rows(2 * ng);
-    for (size_t k = 0; k < 2 * ng; ++k) b_rows[k] = static_cast<int32_t>(k);
-
-    auto alloc = [&](size_t bytes) -> void* {
-        if (e != hipSuccess) return nullptr;
-        void* p = nullptr;
-        e = hipMalloc(&p, bytes + 64);       // (as the upload: the kernels' neighbour reads never leave the buffer)
-        if (e != hipSuccess) return nullptr;
-        G.allocations.push_back(p);
-        return p;
-    };
-    auto put = [&](const void* src, size_t bytes) -> void* {
-        void* p = alloc(bytes);
-        if (p && bytes && e == hipSuccess) e = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream);
-        return p;
-    };
-    auto putd = [&](const std::vector<double>& v) { return static_cast<const double*>(put(v.data(), v.size() * sizeof(double))); };
-    auto put64 = [&](const std::vector<int64_t>& v) { return static_cast<const int64_t*>(put(v.data(), v.size() * sizeof(int64_t))); };
-    auto rows_of = [&](const adr::CsrDev& csr, const std::vector<int32_t>& trades, adr::TradesDev& dst) {
-        dst = tr->dev;
-        dst.n_rows = 0;
-        if (trades.empty()) return;
-        const size_t rows = trades.size(), S = adr::kRowSlots;
-        adr::RowBuildDev rb{};
-        rb.rows = static_cast<int64_t>(rows);
-        rb.piece_trade = static_cast<const int32_t*>(put(trades.data(), rows * sizeof(int32_t)));
-        rb.row_tp = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_ts = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_alpha = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_xtp = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_xpay = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_notional = static_cast<double*>(alloc(rows * sizeof(double)));
-        rb.row_spread = static_cast<double*>(alloc(rows * sizeof(double)));
-        rb.row_meta = static_cast<int32_t*>(alloc(rows * sizeof(int32_t)));
-        rb.row_trade = static_cast<int32_t*>(alloc(rows * sizeof(int32_t)));
-        if (e == hipSuccess) e = adr::launch_build_rows(csr, rb, stream);
-        dst.n_rows = static_cast<int64_t>(rows);
-        dst.row_tp = rb.row_tp; dst.row_ts = rb.row_ts; dst.row_alpha = rb.row_alpha; dst.row_xtp = rb.row_xtp; dst.row_xpay = rb.row_xpay;
-        dst.row_notional = rb.row_notional; dst.row_spread = rb.row_spread; dst.row_meta = rb.row_meta; dst.row_trade = rb.row_trade;
-        dst.rows_chained = 0; dst.rows_lagged = 0; dst.row_te = nullptr; dst.row_w = nullptr;
-    };
-    rows_of(G.csr, rest, G.ungrouped);
+    G.ungrouped = tr->dev;
+    build_row_table(G.csr, T.rest, nullptr, nullptr, false, false, mem, stream, G.ungrouped);
     adr::CsrDev bc{};
     bc.n = static_cast<int64_t>(2 * ng);
-    bc.fix_off = put64(b_fix_off); bc.flt_off = put64(b_flt_off);
-    bc.fix_tp = putd(b_fix_tp); bc.fix_pay = putd(b_fix_pay);
-    bc.flt_tp = putd(b_flt_tp); bc.flt_ts = putd(b_flt_ts); bc.flt_te = putd(b_flt_te); bc.flt_alpha = putd(b_flt_alpha);
-    bc.notional = putd(b_notional); bc.spread = putd(b_spread); bc.fix_sign = putd(b_sign); bc.flt_sign = putd(b_sign);
-    rows_of(bc, b_rows, G.basis);
+    bc.fix_off = mem.put(T.fix_off, stream, kBatchPad); bc.flt_off = mem.put(T.flt_off, stream, kBatchPad);
+    bc.fix_tp = mem.put(T.fix_tp, stream, kBatchPad); bc.fix_pay = mem.put(T.fix_pay, stream, kBatchPad);
+    bc.flt_tp = mem.put(T.flt_tp, stream, kBatchPad); bc.flt_ts = mem.put(T.flt_ts, stream, kBatchPad);
+    bc.flt_te = mem.put(T.flt_te, stream, kBatchPad); bc.flt_alpha = mem.put(T.flt_alpha, stream, kBatchPad);
+    bc.notional = mem.put(T.notional, stream, kBatchPad); bc.spread = mem.put(T.spread, stream, kBatchPad);
+    bc.fix_sign = mem.put(T.sign, stream, kBatchPad); bc.flt_sign = mem.put(T.sign, stream, kBatchPad);
+    G.basis = tr->dev;
+    build_row_table(bc, T.rows, nullptr, nullptr, false, false, mem, stream, G.basis);
     G.basis.n = bc.n;
 
     adr::CombineDev& cd = G.combine;
-    cd.rec = static_cast<const adr::GroupRecord*>(put(rec.data(), rec.size() * sizeof(adr::GroupRecord)));
-    cd.seg = static_cast<const adr::GroupSegment*>(put(seg.data(), seg.size() * sizeof(adr::GroupSegment)));
-    cd.n_seg = static_cast<int64_t>(seg.size());
+    cd.rec = mem.put(T.rec, stream, kBatchPad);
+    cd.seg = mem.put(T.seg, stream, kBatchPad);
+    cd.n_seg = static_cast<int64_t>(T.seg.size());
     cd.max_blocks = G.blocks;
-    cd.n_groups = G.used_groups;
-    cd.sum_f = putd(sum_f); cd.sum_x = putd(sum_x);
+    cd.n_groups = T.used_groups;
+    cd.sum_f = mem.put(T.sum_f, stream, kBatchPad); cd.sum_x = mem.put(T.sum_x, stream, kBatchPad);
     // the basis ladders of a pricing call, for any curve of up to 32 pillars
     constexpr size_t PM = adr::kPillarPad;
-    cd.b_pv = static_cast<double*>(alloc(2 * ng * sizeof(double)));
-    cd.b_delta = static_cast<double*>(alloc(2 * ng * PM * sizeof(double)));
-    cd.b_gamma = static_cast<double*>(alloc(2 * ng * PM * PM * sizeof(double)));
-    {
-        const hipError_t es = hipStreamSynchronize(stream);      // (also on errors: the copies read this function's vectors)
-        if (e == hipSuccess) e = es;
-    }
-    if (e != hipSuccess) {
-        for (void* p : G.allocations) hipFree(p);
-        G.allocations.clear();
-        G.combine = adr::CombineDev{};
-        G.used_groups = G.used_trades = 0;
-        return e;
-    }
+    cd.b_pv = mem.array<double>(2 * ng, kBatchPad);
+    cd.b_delta = mem.array<double>(2 * ng * PM, kBatchPad);
+    cd.b_gamma = mem.array<double>(2 * ng * PM * PM, kBatchPad);
+    mem.note(hipStreamSynchronize(stream));                    // (also on errors: the copies read `T`)
+    if (!mem.ok()) return G.reset();
+    G.used_groups = T.used_groups;
+    G.used_trades = T.used_trades;
     G.active = true;
     return hipSuccess;
+}
+
+// Which table or list every trade lands in, and the host side of those tables (route.cpp), with the one limit they have.
+// `flagged`: the caller has filled lagged_of (the upload does, in its parallel validation pass); else the trades with
+// payment lag or per-coupon notionals are flagged here (route.hpp, flag_lagged).  `who`: the entry point, for the message.
+int layout_trades(const char* who, int64_t n, const int64_t* fix_off, const int64_t* flt_off, const double* flt_tp,
+                  const double* flt_te, const double* flt_alpha, const double* flt_weight, int n_cu, bool flagged,
+                  std::vector<uint8_t>& lagged_of, R::TradeLayout& L) {
+    if (!flagged) {
+        lagged_of.assign(static_cast<size_t>(n), 0);
+        R::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, lagged_of.data());
+    }
+    L = R::trade_layout(n, fix_off, flt_off, lagged_of.data(), n_cu);
+    if (L.too_many_rows)
+        return fail(ADR_ERR_UNSUPPORTED, std::string(who) + ": more than 2^28 rows in the delta-only table; shard the portfolio");
+    return ADR_OK;
 }
 
 }  // namespace
@@ -1038,9 +919,9 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
 
     // which table or list every trade lands in, and the host side of those tables (route.cpp); they are gathered on the
     // device (trades_build.hip)
-    R::TradeLayout L = R::trade_layout(n, fix_off, flt_off, lagged_of.data(), ctx->n_cu);
-    if (L.too_many_rows)
-        return fail(ADR_ERR_UNSUPPORTED, "adr_trades_upload: more than 2^28 rows in the delta-only table; shard the portfolio");
+    R::TradeLayout L;
+    if (const int rc = layout_trades("adr_trades_upload", n, fix_off, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, ctx->n_cu, true, lagged_of, L))
+        return rc;
 
     ADR_HIP(hipSetDevice(ctx->device));
     adr_trades* tr = new (std::nothrow) adr_trades();
@@ -1053,49 +934,34 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
         const auto it = std::find(lagged_of.begin(), lagged_of.end(), uint8_t(1));
         if (it != lagged_of.end()) tr->first_ratio = it - lagged_of.begin();
     }
-    hipError_t e = hipSuccess;
+    adr::DeviceOwner& mem = tr->mem;
     hipStream_t stream = ctx->stream;
-    auto alloc = [&](size_t bytes) -> void* {
-        if (bytes == 0 || e != hipSuccess) return nullptr;
-        // over-allocate one header's worth so that the kernels' neighbour reads never leave the buffer
-        void* p = nullptr;
-        e = hipMalloc(&p, bytes + 64);
-        if (e != hipSuccess) return nullptr;
-        tr->allocations.push_back(p);
-        return p;
-    };
-    // (the host vectors handed to `put` - the caller's arrays and the layout - outlive the asynchronous copies: they are
-    // kept until the final synchronisation)
-    auto put = [&](const void* src, size_t bytes) -> void* {
-        void* p = alloc(bytes);
-        if (p && e == hipSuccess) e = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream);
-        return p;
-    };
-    auto put32 = [&](const std::vector<int32_t>& v) { return static_cast<const int32_t*>(put(v.data(), v.size() * sizeof(int32_t))); };
-    auto put8 = [&](const std::vector<uint8_t>& v) { return static_cast<const uint8_t*>(put(v.data(), v.size())); };
+    // (The host memory handed to `put` - the caller's arrays and the layout - outlives the asynchronous copies: it is kept
+    // until the final synchronisation.  An empty array is null here, unlike in the schedule groups' tables.)
+    const size_t nn = static_cast<size_t>(n), nf = static_cast<size_t>(n_fix), nl = static_cast<size_t>(n_flt);
 
     // the caller's arrays, once
     adr::CsrDev csr{};
     csr.n = n;
-    csr.fix_off = static_cast<const int64_t*>(put(fix_off, (n ? n + 1 : 0) * sizeof(int64_t)));
-    csr.flt_off = static_cast<const int64_t*>(put(flt_off, (n ? n + 1 : 0) * sizeof(int64_t)));
-    csr.fix_tp = static_cast<const double*>(put(fix_tp, n_fix * sizeof(double)));
-    csr.fix_pay = static_cast<const double*>(put(fix_pay, n_fix * sizeof(double)));
-    csr.flt_tp = static_cast<const double*>(put(flt_tp, n_flt * sizeof(double)));
-    csr.flt_ts = static_cast<const double*>(put(flt_ts, n_flt * sizeof(double)));
-    csr.flt_te = static_cast<const double*>(put(flt_te, n_flt * sizeof(double)));
-    csr.flt_alpha = static_cast<const double*>(put(flt_alpha, n_flt * sizeof(double)));
-    csr.flt_weight = flt_weight ? static_cast<const double*>(put(flt_weight, n_flt * sizeof(double))) : nullptr;
-    csr.notional = static_cast<const double*>(put(notional, n * sizeof(double)));
-    csr.spread = static_cast<const double*>(put(spread, n * sizeof(double)));
-    csr.fix_sign = static_cast<const double*>(put(fix_sign, n * sizeof(double)));
-    csr.flt_sign = static_cast<const double*>(put(flt_sign, n * sizeof(double)));
+    csr.fix_off = mem.put_n(fix_off, nn ? nn + 1 : 0, stream, kBatchPad);
+    csr.flt_off = mem.put_n(flt_off, nn ? nn + 1 : 0, stream, kBatchPad);
+    csr.fix_tp = mem.put_n(fix_tp, nf, stream, kBatchPad);
+    csr.fix_pay = mem.put_n(fix_pay, nf, stream, kBatchPad);
+    csr.flt_tp = mem.put_n(flt_tp, nl, stream, kBatchPad);
+    csr.flt_ts = mem.put_n(flt_ts, nl, stream, kBatchPad);
+    csr.flt_te = mem.put_n(flt_te, nl, stream, kBatchPad);
+    csr.flt_alpha = mem.put_n(flt_alpha, nl, stream, kBatchPad);
+    csr.flt_weight = flt_weight ? mem.put_n(flt_weight, nl, stream, kBatchPad) : nullptr;
+    csr.notional = mem.put_n(notional, nn, stream, kBatchPad);
+    csr.spread = mem.put_n(spread, nn, stream, kBatchPad);
+    csr.fix_sign = mem.put_n(fix_sign, nn, stream, kBatchPad);
+    csr.flt_sign = mem.put_n(flt_sign, nn, stream, kBatchPad);
 
     tr->dev.n = n;
     tr->dev.any_ratio = L.any_lagged ? 1 : 0;
     {
-        adr::TradeHeader* hdr = static_cast<adr::TradeHeader*>(alloc(static_cast<size_t>(n) * sizeof(adr::TradeHeader)));
-        if (e == hipSuccess && n > 0) e = adr::launch_build_headers(csr, hdr, stream);
+        adr::TradeHeader* hdr = mem.array<adr::TradeHeader>(nn, kBatchPad);
+        if (mem.ok() && n > 0) mem.note(adr::launch_build_headers(csr, hdr, stream));
         tr->dev.header = hdr;
     }
     tr->dev.fix_tp = csr.fix_tp; tr->dev.fix_pay = csr.fix_pay; tr->dev.flt_tp = csr.flt_tp; tr->dev.flt_ts = csr.flt_ts;
@@ -1103,56 +969,29 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
     tr->dev.list = nullptr;
     tr->dev.n_list = n;
 
-    // Row tables of the fast kernel (kernels.hpp): 32 zero-padded slots per row and array, gathered on the device from the
-    // work list (trade or -1 for an empty row; chained tables: first coupon of the piece, "the trade continues" flag).
-    auto build_rows = [&](int set, bool chained, bool lagged) {
-        const std::vector<int32_t>& piece_trade = chained ? L.chain_trade[set] : L.trades[set];
-        adr::TradesDev& dst = set == R::S_ROWS ? tr->dev : tr->set[set];
-        if (set != R::S_ROWS) { dst = tr->dev; dst.n_rows = 0; }
-        if (piece_trade.empty()) return;
-        const size_t rows = piece_trade.size(), S = adr::kRowSlots;
-        adr::RowBuildDev rb{};
-        rb.rows = static_cast<int64_t>(rows);
-        rb.piece_trade = put32(piece_trade);
-        rb.piece_first = chained ? put32(L.chain_first[set]) : nullptr;
-        rb.piece_more = chained ? put8(L.chain_more[set]) : nullptr;
-        rb.row_tp = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_ts = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_alpha = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_xtp = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_xpay = static_cast<double*>(alloc(rows * S * sizeof(double)));
-        rb.row_te = lagged ? static_cast<double*>(alloc(rows * S * sizeof(double))) : nullptr;
-        rb.row_w = (lagged && flt_weight) ? static_cast<double*>(alloc(rows * S * sizeof(double))) : nullptr;
-        rb.row_notional = static_cast<double*>(alloc(rows * sizeof(double)));
-        rb.row_spread = static_cast<double*>(alloc(rows * sizeof(double)));
-        rb.row_meta = static_cast<int32_t*>(alloc(rows * sizeof(int32_t)));
-        rb.row_trade = static_cast<int32_t*>(alloc(rows * sizeof(int32_t)));
-        if (e == hipSuccess) e = adr::launch_build_rows(csr, rb, stream);
-        dst.n_rows = static_cast<int64_t>(rows);
-        dst.row_tp = rb.row_tp; dst.row_ts = rb.row_ts; dst.row_alpha = rb.row_alpha; dst.row_xtp = rb.row_xtp; dst.row_xpay = rb.row_xpay;
-        dst.row_notional = rb.row_notional; dst.row_spread = rb.row_spread; dst.row_meta = rb.row_meta; dst.row_trade = rb.row_trade;
-        dst.rows_chained = chained ? 1 : 0;
-        dst.rows_lagged = lagged ? 1 : 0;
-        dst.row_te = rb.row_te; dst.row_w = rb.row_w;
+    // The row tables of the fast kernel (build_row_table).  The plain one lives in tr->dev itself; every other set starts
+    // from a copy of tr->dev as it stands.
+    const struct { int set; bool chained, lagged; } row_tables[] = {
+        {R::S_ROWS, false, false},                      // plain table: one row per trade, sorted by coupon count
+        {R::S_CHAINED, true, false},                    // longer trades as chains of 32-coupon rows
+        {R::S_LAGGED, false, true},                     // payment-lag rows, one per trade (GAMMA on the packed layout)
+        {R::S_LAGGED_CHAINED, true, true},              // ... chains of them (33-128 coupons)
     };
-    build_rows(R::S_ROWS, false, false);                // plain table: one row per trade, sorted by coupon count
-    build_rows(R::S_CHAINED, true, false);              // longer trades as chains of 32-coupon rows
-    build_rows(R::S_LAGGED, false, true);               // payment-lag rows, one per trade (GAMMA on the packed layout)
-    build_rows(R::S_LAGGED_CHAINED, true, true);        // ... chains of them (33-128 coupons)
+    for (const auto& rt : row_tables) {
+        adr::TradesDev& dst = rt.set == R::S_ROWS ? tr->dev : tr->set[rt.set];
+        if (rt.set != R::S_ROWS) dst = tr->dev;
+        build_row_table(csr, rt.chained ? L.chain_trade[rt.set] : L.trades[rt.set], rt.chained ? &L.chain_first[rt.set] : nullptr,
+                        rt.chained ? &L.chain_more[rt.set] : nullptr, rt.lagged, flt_weight != nullptr, mem, stream, dst);
+    }
     tr->set[R::S_ROWS] = tr->dev;
     // the trade lists of the general / wide / tiled kernels; S_ALL: the identity
     for (int s = R::S_GENERAL; s <= R::S_ALL; ++s) {
         tr->set[s] = tr->dev;
-        if (s != R::S_ALL) { tr->set[s].list = put32(L.trades[s]); tr->set[s].n_list = static_cast<int64_t>(L.trades[s].size()); }
+        if (s != R::S_ALL) { tr->set[s].list = mem.put(L.trades[s], stream, kBatchPad); tr->set[s].n_list = static_cast<int64_t>(L.trades[s].size()); }
     }
-    if (tr->counts.lag_scratch && e == hipSuccess) {
-        // per-wave scratch of the payment-lag variant: its special nodes' stash
-        void* p = nullptr;
-        const size_t bytes = adr::fast_kernel_lag_scratch_bytes(tr->counts.lag_blocks);
-        e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) { tr->allocations.push_back(p); tr->lag_scratch = static_cast<double*>(p); }
-        if (e == hipSuccess) e = hipMemsetAsync(p, 0, bytes, stream);
-    }
+    // per-wave scratch of the payment-lag variant: its special nodes' stash (read by the owning wave only: no pad)
+    if (tr->counts.lag_scratch)
+        tr->lag_scratch = static_cast<double*>(mem.alloc_zeroed(adr::fast_kernel_lag_scratch_bytes(tr->counts.lag_blocks), stream));
     // lite tables (kernels.hpp, LiteRowsDev): gathered on the device from their slots' trades and their rows' slot and piece
     for (int s : {R::S_LITE, R::S_LITE_LAG}) {
         constexpr int S = adr::kLiteSlots;
@@ -1162,36 +1001,37 @@ int adr_trades_upload_weighted(adr_ctx* ctx, int64_t n, const int64_t* fix_off, 
         adr::LiteBuildDev lb{};
         const size_t n_rows = L.lite_row_slot[s].size(), n_slots = L.trades[s].size();
         lb.rows = static_cast<int64_t>(n_rows); lb.n_slots = static_cast<int64_t>(n_slots);
-        lb.slot_trade = put32(L.trades[s]);
-        lb.row_slot = put32(L.lite_row_slot[s]);
-        lb.row_piece = put8(L.lite_row_piece[s]);
-        lb.tp_ts = static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double)));
-        lb.al_xtp = static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double)));
-        lb.xpay = static_cast<double*>(alloc(n_rows * S * sizeof(double)));
-        lb.te_w = s == R::S_LITE_LAG ? static_cast<double*>(alloc(n_rows * S * 2 * sizeof(double))) : nullptr;
-        lb.slot = static_cast<adr::LiteTrade*>(alloc(n_slots * sizeof(adr::LiteTrade)));
-        if (e == hipSuccess) e = adr::launch_build_lite(csr, lb, stream);
+        lb.slot_trade = mem.put(L.trades[s], stream, kBatchPad);
+        lb.row_slot = mem.put(L.lite_row_slot[s], stream, kBatchPad);
+        lb.row_piece = mem.put(L.lite_row_piece[s], stream, kBatchPad);
+        lb.tp_ts = mem.array<double>(n_rows * S * 2, kBatchPad);
+        lb.al_xtp = mem.array<double>(n_rows * S * 2, kBatchPad);
+        lb.xpay = mem.array<double>(n_rows * S, kBatchPad);
+        lb.te_w = s == R::S_LITE_LAG ? mem.array<double>(n_rows * S * 2, kBatchPad) : nullptr;
+        lb.slot = mem.array<adr::LiteTrade>(n_slots, kBatchPad);
+        if (mem.ok()) mem.note(adr::launch_build_lite(csr, lb, stream));
         lt.tp_ts = lb.tp_ts; lt.al_xtp = lb.al_xtp; lt.xpay = lb.xpay; lt.te_w = lb.te_w; lt.slot = lb.slot;
     }
     // schedule groups among the trades of the plain row table: the host search runs while the device gathers the tables above
     // (apply_schedule_groups synchronises the stream before it builds its own)
-    if (e == hipSuccess && !L.trades[R::S_ROWS].empty()) {
+    if (mem.ok() && !L.trades[R::S_ROWS].empty()) {
         const adr::CsrHost host{n, fix_off, flt_off, fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, notional, spread, fix_sign, flt_sign};
         adr::build_schedule_groups(host, L.trades[R::S_ROWS].data(), static_cast<int64_t>(L.trades[R::S_ROWS].size()), tr->grouping.found);
         if (tr->grouping.found.n_groups > 0) {
             tr->grouping.rows_order = L.trades[R::S_ROWS];
             tr->grouping.csr = csr;
-            e = apply_schedule_groups(tr);
+            mem.note(apply_schedule_groups(tr));
         } else {
             tr->grouping.found = adr::ScheduleGroups();
         }
     }
     // the copies and the table builders run on the ctx's stream: the batch is usable once they are done
-    {
-        const hipError_t es = hipStreamSynchronize(stream);        // (also on errors: the copies read this function's vectors)
-        if (e == hipSuccess) e = es;
+    mem.note(hipStreamSynchronize(stream));                  // (also on errors: the copies read the caller's arrays and `L`)
+    if (!mem.ok()) {
+        const hipError_t e = mem.error;
+        adr_free_trades(tr);
+        return fail_hip(e, "adr_trades_upload: copying trades");
     }
-    if (e != hipSuccess) { adr_free_trades(tr); return fail_hip(e, "adr_trades_upload: copying trades"); }
     *out = tr;
     return ADR_OK;
 }
@@ -1323,25 +1163,20 @@ int adr_price(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades, ui
     const size_t n = static_cast<size_t>(trades->dev.n);
     const size_t n_agg = 1 + P + static_cast<size_t>(P) * P;
     ADR_HIP(hipSetDevice(ctx->device));
-    double *d_pv = nullptr, *d_delta = nullptr, *d_gamma = nullptr, *d_agg = nullptr;
-    int rc = ADR_OK;
-    hipError_t e = hipSuccess;
-    auto cleanup = [&]() { hipFree(d_pv); hipFree(d_delta); hipFree(d_gamma); hipFree(d_agg); };
-    if (pv && (req_mask & ADR_REQ_VALUE) && n) e = hipMalloc(reinterpret_cast<void**>(&d_pv), n * sizeof(double));
-    if (e == hipSuccess && delta && (req_mask & ADR_REQ_DELTA) && n)
-        e = hipMalloc(reinterpret_cast<void**>(&d_delta), n * P * sizeof(double));
-    if (e == hipSuccess && gamma && (req_mask & ADR_REQ_GAMMA) && n)
-        e = hipMalloc(reinterpret_cast<void**>(&d_gamma), n * P * P * sizeof(double));
-    if (e == hipSuccess && agg) e = hipMalloc(reinterpret_cast<void**>(&d_agg), n_agg * sizeof(double));
-    if (e != hipSuccess) { cleanup(); return fail_hip(e, "adr_price: allocating outputs"); }
-    rc = adr_price_dev(ctx, curve, trades, req_mask, d_pv, d_delta, d_gamma, d_agg, nullptr);
-    if (rc != ADR_OK) { cleanup(); return rc; }
-    e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && d_pv) e = hipMemcpy(pv, d_pv, n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && d_delta) e = hipMemcpy(delta, d_delta, n * P * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && d_gamma) e = hipMemcpy(gamma, d_gamma, n * P * P * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && d_agg) e = hipMemcpy(agg, d_agg, n_agg * sizeof(double), hipMemcpyDeviceToHost);
-    cleanup();
+    adr::DeviceOwner tmp;                     // the call's output arrays on the device
+    double* d_pv = (pv && (req_mask & ADR_REQ_VALUE)) ? tmp.array<double>(n) : nullptr;
+    double* d_delta = (delta && (req_mask & ADR_REQ_DELTA)) ? tmp.array<double>(n * P) : nullptr;
+    double* d_gamma = (gamma && (req_mask & ADR_REQ_GAMMA)) ? tmp.array<double>(n * P * P) : nullptr;
+    double* d_agg = agg ? tmp.array<double>(n_agg) : nullptr;
+    if (!tmp.ok()) return fail_hip(tmp.release(), "adr_price: allocating outputs");
+    const int rc = adr_price_dev(ctx, curve, trades, req_mask, d_pv, d_delta, d_gamma, d_agg, nullptr);
+    if (rc != ADR_OK) { tmp.release(); return rc; }
+    tmp.note(hipStreamSynchronize(ctx->stream));
+    if (tmp.ok() && d_pv) tmp.note(hipMemcpy(pv, d_pv, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (tmp.ok() && d_delta) tmp.note(hipMemcpy(delta, d_delta, n * P * sizeof(double), hipMemcpyDeviceToHost));
+    if (tmp.ok() && d_gamma) tmp.note(hipMemcpy(gamma, d_gamma, n * P * P * sizeof(double), hipMemcpyDeviceToHost));
+    if (tmp.ok() && d_agg) tmp.note(hipMemcpy(agg, d_agg, n_agg * sizeof(double), hipMemcpyDeviceToHost));
+    const hipError_t e = tmp.release();
     if (e != hipSuccess) return fail_hip(e, "adr_price: running kernels / copying results");
     return ADR_OK;
 }
@@ -1397,23 +1232,20 @@ int adr_price_xccy_foreign(adr_ctx* ctx, const adr_curve* foreign_curve, const a
     if (!ctx || !foreign_curve || !xccy_curve || !legs) return fail(ADR_ERR_INVALID, "adr_price_xccy_foreign: null ctx/curve/legs");
     const size_t n = static_cast<size_t>(legs->dev.n), Pf = foreign_curve->dev.P, Px = xccy_curve->dev.P;
     ADR_HIP(hipSetDevice(ctx->device));
-    double *d_pv = nullptr, *d_f = nullptr, *d_x = nullptr, *d_af = nullptr, *d_ax = nullptr;
-    hipError_t e = hipSuccess;
-    auto cleanup = [&]() { hipFree(d_pv); hipFree(d_f); hipFree(d_x); hipFree(d_af); hipFree(d_ax); };
-    auto get = [&](double** p, size_t count) { if (e == hipSuccess && count) e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(double)); };
-    if (pv && (req_mask & ADR_REQ_VALUE)) get(&d_pv, n);
-    if (delta_foreign && (req_mask & ADR_REQ_DELTA)) get(&d_f, n * Pf);
-    if (delta_basis && (req_mask & ADR_REQ_DELTA)) get(&d_x, n * Px);
-    if (agg_foreign) get(&d_af, 1 + Pf + Pf * Pf);
-    if (agg_basis) get(&d_ax, 1 + Px + Px * Px);
-    if (e != hipSuccess) { cleanup(); return fail_hip(e, "adr_price_xccy_foreign: allocating outputs"); }
+    adr::DeviceOwner tmp;                     // the call's output arrays on the device
+    double* d_pv = (pv && (req_mask & ADR_REQ_VALUE)) ? tmp.array<double>(n) : nullptr;
+    double* d_f = (delta_foreign && (req_mask & ADR_REQ_DELTA)) ? tmp.array<double>(n * Pf) : nullptr;
+    double* d_x = (delta_basis && (req_mask & ADR_REQ_DELTA)) ? tmp.array<double>(n * Px) : nullptr;
+    double* d_af = agg_foreign ? tmp.array<double>(1 + Pf + Pf * Pf) : nullptr;
+    double* d_ax = agg_basis ? tmp.array<double>(1 + Px + Px * Px) : nullptr;
+    if (!tmp.ok()) return fail_hip(tmp.release(), "adr_price_xccy_foreign: allocating outputs");
     const int rc = adr_price_xccy_foreign_dev(ctx, foreign_curve, xccy_curve, legs, req_mask, d_pv, d_f, d_x, d_af, d_ax, nullptr);
-    if (rc != ADR_OK) { cleanup(); return rc; }
-    e = hipStreamSynchronize(ctx->stream);
-    auto back = [&](double* dst, double* src, size_t count) { if (e == hipSuccess && src) e = hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost); };
+    if (rc != ADR_OK) { tmp.release(); return rc; }
+    tmp.note(hipStreamSynchronize(ctx->stream));
+    auto back = [&](double* dst, double* src, size_t count) { if (tmp.ok() && src) tmp.note(hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost)); };
     back(pv, d_pv, n); back(delta_foreign, d_f, n * Pf); back(delta_basis, d_x, n * Px);
     back(agg_foreign, d_af, 1 + Pf + Pf * Pf); back(agg_basis, d_ax, 1 + Px + Px * Px);
-    cleanup();
+    const hipError_t e = tmp.release();
     if (e != hipSuccess) return fail_hip(e, "adr_price_xccy_foreign: running the kernel / copying results");
     return ADR_OK;
 }
@@ -1430,11 +1262,10 @@ int adr_route_host(int interp_method, int K, int P, const double* times, const d
     if (!err.empty()) return fail(ADR_ERR_INVALID, "adr_route_host: " + err);
     const R::CurveClass cls = R::curve_class(t, interp_method, (curve_flags & ADR_CURVE_PILLAR_TILES) != 0);
     if ((req_mask & ADR_REQ_GAMMA) && !t.has_hess) return fail(ADR_ERR_INVALID, "adr_route_host: GAMMA requested but hess is null");
-    std::vector<uint8_t> lagged_of(static_cast<size_t>(n), 0);
-    R::flag_lagged(0, n, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, lagged_of.data());
-    const R::TradeLayout L = R::trade_layout(n, fix_off, flt_off, lagged_of.data(), n_cu);
-    if (L.too_many_rows)
-        return fail(ADR_ERR_UNSUPPORTED, "adr_route_host: more than 2^28 rows in the delta-only table; shard the portfolio");
+    std::vector<uint8_t> lagged_of;
+    R::TradeLayout L;
+    if (const int rc = layout_trades("adr_route_host", n, fix_off, flt_off, flt_tp, flt_te, flt_alpha, flt_weight, n_cu, false, lagged_of, L))
+        return rc;
     const bool want_gamma = (req_mask & ADR_REQ_GAMMA) != 0, want_delta = want_gamma || (req_mask & ADR_REQ_DELTA) != 0;
     const R::Plan plan = R::make_plan(cls, L.counts, want_delta, want_gamma, per_trade != 0, aggregate != 0, n_cu);
     if (plan.error) return fail(ADR_ERR_INVALID, std::string("adr_route_host: ") + plan.error);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "curve_tables.hpp"
+#include "schedule_groups.hpp"
 
 #ifndef ADR_FAST_THREADS
 #define ADR_FAST_THREADS 768
@@ -298,16 +299,8 @@ hipError_t launch_knot_project(const CurveDev& cv, const double* partials, int n
 hipError_t launch_reduce_partials(const double* partials, int n_blocks, int P, bool has_gamma, double* agg,
                                   hipStream_t stream, int tile_i = 0, int tile_j = 0);
 
-// Schedule groups (schedule_groups.hpp, kernels_combine.hip): the members' ladders from their group's two basis ladders.
-struct GroupRecord {              // 32 bytes, read with scalar loads; sorted by group, trade order inside a group
-    int32_t trade, group;
-    double cF, cX;                // out[trade] = cF * BF[group] + cX * BX[group]
-    int64_t pad;
-};
-static_assert(sizeof(GroupRecord) == 32, "GroupRecord is read as 32-byte records");
-struct GroupSegment {             // the records one wave writes: all of one group
-    int32_t group, first, count, pad;
-};
+// Schedule groups (kernels_combine.hip): the members' ladders from their group's two basis ladders; GroupRecord and
+// GroupSegment: schedule_groups.hpp.
 struct CombineDev {
     const GroupRecord* rec;       // [grouped trades]
     const GroupSegment* seg;      // [n_seg]

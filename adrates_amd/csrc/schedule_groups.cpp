@@ -1,4 +1,5 @@
-// Schedule groups of a batch (schedule_groups.hpp): hash the key, confirm by comparison, test the fixed leg's shape.
+// Schedule groups of a batch (schedule_groups.hpp): hash the key, confirm by comparison, test the fixed leg's shape; and the
+// host image of the device tables of the groups in use.
 #include "schedule_groups.hpp"
 
 #include <algorithm>
@@ -186,6 +187,75 @@ void build_schedule_groups(const CsrHost& c, const int32_t* eligible, int64_t n_
         out.spread.push_back(0.0);
     }
     out.sign.assign(2 * order.size(), 1.0);
+}
+
+GroupTables build_group_tables(const ScheduleGroups& F, const int32_t* rows_order, int64_t n_rows, int min_group,
+                               int64_t min_grouped, int segment) {
+    GroupTables T;
+    // the groups in use, renumbered in order
+    std::vector<int32_t> new_id(static_cast<size_t>(F.n_groups), -1);
+    std::vector<int64_t> first;              // first record of every group in use, then the total
+    for (int64_t g = 0; g < F.n_groups; ++g)
+        if (F.size[static_cast<size_t>(g)] >= min_group) {
+            new_id[static_cast<size_t>(g)] = static_cast<int32_t>(T.used_groups++);
+            first.push_back(T.used_trades);
+            T.used_trades += F.size[static_cast<size_t>(g)];
+        }
+    first.push_back(T.used_trades);
+    if (T.used_groups == 0 || T.used_trades < min_grouped) return GroupTables();
+    const size_t ng = static_cast<size_t>(T.used_groups);
+
+    // records sorted by group, in trade order inside a group; the coefficient sums in trade order
+    T.rec.resize(static_cast<size_t>(T.used_trades));
+    T.sum_f.assign(ng, 0.0);
+    T.sum_x.assign(ng, 0.0);
+    {
+        std::vector<int64_t> at(first.begin(), first.end() - 1);
+        const int64_t n = static_cast<int64_t>(F.group_of.size());
+        for (int64_t t = 0; t < n; ++t) {
+            const int32_t old = F.group_of[static_cast<size_t>(t)];
+            const int32_t g = old >= 0 ? new_id[static_cast<size_t>(old)] : -1;
+            if (g < 0) continue;
+            T.rec[static_cast<size_t>(at[static_cast<size_t>(g)]++)] =
+                GroupRecord{static_cast<int32_t>(t), g, F.cF[static_cast<size_t>(t)], F.cX[static_cast<size_t>(t)], 0};
+            T.sum_f[static_cast<size_t>(g)] += F.cF[static_cast<size_t>(t)];
+            T.sum_x[static_cast<size_t>(g)] += F.cX[static_cast<size_t>(t)];
+        }
+    }
+    // segments: no wave straddles two groups
+    for (size_t g = 0; g < ng; ++g)
+        for (int64_t at = first[g]; at < first[g + 1]; at += segment)
+            T.seg.push_back(GroupSegment{static_cast<int32_t>(g), static_cast<int32_t>(at),
+                                         static_cast<int32_t>(std::min<int64_t>(segment, first[g + 1] - at)), 0});
+    // the plain rows outside the groups in use, in the table's order
+    for (int64_t i = 0; i < n_rows; ++i) {
+        const int32_t old = F.group_of[static_cast<size_t>(rows_order[i])];
+        if (old < 0 || new_id[static_cast<size_t>(old)] < 0) T.rest.push_back(rows_order[i]);
+    }
+    // the basis trades of the groups in use: a small CSR batch of their own
+    T.fix_off.assign(1, 0);
+    T.flt_off.assign(1, 0);
+    for (int64_t g = 0; g < F.n_groups; ++g) {
+        if (new_id[static_cast<size_t>(g)] < 0) continue;
+        for (int64_t k = 2 * g; k < 2 * g + 2; ++k) {
+            const size_t f0 = static_cast<size_t>(F.fix_off[static_cast<size_t>(k)]), f1 = static_cast<size_t>(F.fix_off[static_cast<size_t>(k) + 1]);
+            const size_t l0 = static_cast<size_t>(F.flt_off[static_cast<size_t>(k)]), l1 = static_cast<size_t>(F.flt_off[static_cast<size_t>(k) + 1]);
+            T.fix_tp.insert(T.fix_tp.end(), F.fix_tp.begin() + f0, F.fix_tp.begin() + f1);
+            T.fix_pay.insert(T.fix_pay.end(), F.fix_pay.begin() + f0, F.fix_pay.begin() + f1);
+            T.flt_tp.insert(T.flt_tp.end(), F.flt_tp.begin() + l0, F.flt_tp.begin() + l1);
+            T.flt_ts.insert(T.flt_ts.end(), F.flt_ts.begin() + l0, F.flt_ts.begin() + l1);
+            T.flt_te.insert(T.flt_te.end(), F.flt_te.begin() + l0, F.flt_te.begin() + l1);
+            T.flt_alpha.insert(T.flt_alpha.end(), F.flt_alpha.begin() + l0, F.flt_alpha.begin() + l1);
+            T.fix_off.push_back(static_cast<int64_t>(T.fix_tp.size()));
+            T.flt_off.push_back(static_cast<int64_t>(T.flt_tp.size()));
+            T.notional.push_back(F.notional[static_cast<size_t>(k)]);
+            T.spread.push_back(F.spread[static_cast<size_t>(k)]);
+        }
+    }
+    T.sign.assign(2 * ng, 1.0);
+    T.rows.resize(2 * ng);
+    for (size_t k = 0; k < 2 * ng; ++k) T.rows[k] = static_cast<int32_t>(k);
+    return T;
 }
 
 }  // namespace adr

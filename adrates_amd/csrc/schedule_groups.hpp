@@ -41,4 +41,37 @@ struct ScheduleGroups {
 // the times, accrual fractions and spread, the shape test is relative to the trade's own last payment.
 void build_schedule_groups(const CsrHost& csr, const int32_t* eligible, int64_t n_eligible, ScheduleGroups& out);
 
+// What the store pass reads (kernels.hpp, CombineDev; kernels_combine.hip): the members' ladders from their group's two basis
+// ladders.
+struct GroupRecord {              // 32 bytes, read with scalar loads; sorted by group, trade order inside a group
+    int32_t trade, group;
+    double cF, cX;                // out[trade] = cF * BF[group] + cX * BX[group]
+    int64_t pad;
+};
+static_assert(sizeof(GroupRecord) == 32, "GroupRecord is read as 32-byte records");
+struct GroupSegment {             // the records one wave writes: all of one group
+    int32_t group, first, count, pad;
+};
+
+// The host image of the device tables of the groups IN USE (renumbered in order): what the batch uploads for the grouped
+// route.  used_groups == 0: the route is not taken and every vector is empty.
+struct GroupTables {
+    int64_t used_groups = 0, used_trades = 0;
+    std::vector<GroupRecord> rec;        // [used_trades] sorted by group, in trade order inside a group
+    std::vector<GroupSegment> seg;       // they tile `rec`; no segment straddles two groups or exceeds the length asked for
+    std::vector<double> sum_f, sum_x;    // [used_groups] the members' coefficient sums, taken in TRADE order (the grouped
+                                         // aggregate must not depend on the segment length)
+    std::vector<int32_t> rest;           // the trades of the plain row table outside the groups in use, in the table's order
+    // the basis trades of the groups in use: the CSR batch of ScheduleGroups cut down to them, every sign +1, and its row list
+    std::vector<int64_t> fix_off, flt_off;
+    std::vector<double> fix_tp, fix_pay, flt_tp, flt_ts, flt_te, flt_alpha, notional, spread, sign;
+    std::vector<int32_t> rows;           // [2 used_groups] the identity
+};
+
+// A group is used from `min_group` trades on; the route is taken when the groups in use hold at least `min_grouped` trades
+// (0: whatever they hold).  rows_order[0 .. n_rows): the plain row table's trades in table order; `segment`: records per
+// segment (>= 1).  Host only.
+GroupTables build_group_tables(const ScheduleGroups& found, const int32_t* rows_order, int64_t n_rows, int min_group,
+                               int64_t min_grouped, int segment);
+
 }  // namespace adr
