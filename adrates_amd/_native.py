@@ -203,6 +203,11 @@ _SIGNATURES = {
     "adr_shock_gather_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _i64p, _dp]),
     "adr_tail_components_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "adr_tail_components_host": (C.c_int, [C.c_int64, C.c_int, _dp, _dp, _dp]),
+    "adr_curve_dfs_shocked": (C.c_int, [_vp, _vp, _dp, C.c_int, C.c_int, _dp, _dp, _i32p]),
+    "adr_curve_dfs_shocked_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "adr_curve_dfs_shocked_work": (C.c_int64, [_vp, C.c_int]),
+    "adr_curve_dfs_shocked_host": (C.c_int, [C.c_int, C.c_int, _dp, _i32p, _i32p, _dp, C.c_int, C.c_int, _dp, _dp, _i32p]),
+    "adr_scenario_rows_place_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1892,6 +1897,65 @@ def tail_components_dev(ctx: Context, B: int, k: int, pnl_ptr: int, comp_var_ptr
     """Non-blocking form (adr_tail_components_dev): device pointers of ``pnl`` [B, k], ``comp_var`` [B] and ``comp_es`` [B]."""
     _check(load().adr_tail_components_dev(ctx._h, int(B), int(k), _dev(pnl_ptr), _dev(comp_var_ptr), _dev(comp_es_ptr),
                                           _vp(stream or None)), "adr_tail_components_dev")
+
+
+# ------------------------------------------------------------ discount factors of shocked curves (csrc/curve_dfs.hip)
+def _dfs_shocked_args(base_rates, shocks_bp):
+    """``(base [P], shocks [S, ld])`` as the blocking and host entries take them."""
+    base, shocks = _f64(base_rates).reshape(-1), _f64(shocks_bp)
+    if shocks.ndim != 2:
+        raise LibError(f"shocks_bp must have shape [n_scenarios, ld], not {list(shocks.shape)}")
+    return base, shocks
+
+
+def curve_dfs_shocked(ctx: Context, plan: CurvePlan, base_rates, shocks_bp):
+    """``(dfs [S, K], bad [S] int32)``: the discount factors of ``plan``'s grid at the rates ``base_rates [P] +
+    shocks_bp[s, :P] * 1e-4`` on the device (adr_curve_dfs_shocked, blocking), with `CurvePlan.build`'s bits at those
+    rates; ``bad[s]``: a discount factor of row ``s`` is not finite or not positive.  Columns of ``shocks_bp`` beyond
+    ``P`` are not read."""
+    base, shocks = _dfs_shocked_args(base_rates, shocks_bp)
+    if base.size != plan.n_pillars:
+        raise LibError(f"base_rates needs one entry per pillar ({plan.n_pillars}), not {base.size}")
+    S, ld = shocks.shape
+    dfs, bad = np.empty((S, plan.n_knots)), np.empty(S, dtype=np.int32)
+    _check(load().adr_curve_dfs_shocked(ctx._h, plan._h, _ptr(base), S, ld, _ptr(shocks), _ptr(dfs), _ptr(bad, _i32p)),
+           "adr_curve_dfs_shocked")
+    return dfs, bad
+
+
+def curve_dfs_shocked_host(acc, pillar, prev_idx, base_rates, shocks_bp):
+    """`curve_dfs_shocked` on the CPU (adr_curve_dfs_shocked_host) from the scan arrays of an `EngineCurve`: the same
+    operations in the same order, the same bits; no GPU and no plan."""
+    base, shocks = _dfs_shocked_args(base_rates, shocks_bp)
+    acc = _f64(acc).reshape(-1)
+    pillar, prev_idx = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (pillar, prev_idx))
+    if pillar.size != acc.size or prev_idx.size != acc.size:
+        raise LibError("scan arrays must have one entry per knot")
+    S, ld = shocks.shape
+    dfs, bad = np.empty((S, acc.size)), np.empty(S, dtype=np.int32)
+    _check(load().adr_curve_dfs_shocked_host(acc.size, base.size, _ptr(acc), _ptr(pillar, _i32p), _ptr(prev_idx, _i32p), _ptr(base),
+                                             S, ld, _ptr(shocks), _ptr(dfs), _ptr(bad, _i32p)), "adr_curve_dfs_shocked_host")
+    return dfs, bad
+
+
+def curve_dfs_shocked_work(plan: CurvePlan, n_scenarios: int) -> int:
+    """Doubles of scratch `curve_dfs_shocked_dev` needs (0 for sizes it refuses)."""
+    return int(load().adr_curve_dfs_shocked_work(plan._h, int(n_scenarios)))
+
+
+def curve_dfs_shocked_dev(ctx: Context, plan: CurvePlan, base_ptr: int, S: int, ld: int, shocks_ptr: int, dfs_ptr: int,
+                          work_ptr: int, bad_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_curve_dfs_shocked_dev): device pointers of ``base_rates`` [P], ``shocks_bp`` [S, ld], ``dfs``
+    [S, K], ``bad`` [S] int32 (0: not wanted) and `curve_dfs_shocked_work` doubles of scratch."""
+    _check(load().adr_curve_dfs_shocked_dev(ctx._h, plan._h, _dev(base_ptr), int(S), int(ld), _dev(shocks_ptr), _dev(dfs_ptr),
+                                            _dev(bad_ptr), _dev(work_ptr), _vp(stream or None)), "adr_curve_dfs_shocked_dev")
+
+
+def scenario_rows_place_dev(ctx: Context, B: int, S_tile: int, tile_ptr: int, S_tot: int, s0: int, rows_ptr: int, stream=0):
+    """``rows[b, s0 + s] = tile[b, s]`` on the device (adr_scenario_rows_place_dev): device pointers of ``tile`` [B, S_tile]
+    and ``rows`` [B, S_tot]."""
+    _check(load().adr_scenario_rows_place_dev(ctx._h, int(B), int(S_tile), _dev(tile_ptr), int(S_tot), int(s0), _dev(rows_ptr),
+                                              _vp(stream or None)), "adr_scenario_rows_place_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

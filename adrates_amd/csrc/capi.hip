@@ -249,6 +249,19 @@ int adr_curve_set_device_view(const adr_curve_set* set, const adr_ctx** owner, i
     return ADR_OK;
 }
 
+// what curve_dfs.hip needs of a curve plan: its owner and the scan arrays on the device
+int adr_curve_plan_scan_view(const adr_curve_plan* plan, const adr_ctx** owner, int* K, int* P, const double** acc_dev,
+                             const int32_t** pillar_dev, const int32_t** prev_idx_dev) {
+    if (!plan) return fail(ADR_ERR_INVALID, "null curve plan");
+    *owner = plan->ctx;
+    *K = plan->dev.K;
+    *P = plan->dev.P;
+    *acc_dev = plan->dev.acc;
+    *pillar_dev = plan->dev.pillar;
+    *prev_idx_dev = plan->dev.prev_idx;
+    return ADR_OK;
+}
+
 extern "C" {
 
 int adr_version(void) { return 100; }

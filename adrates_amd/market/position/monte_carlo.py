@@ -28,6 +28,14 @@ shock rows alone.  No ``[B, S]`` matrix is made, and the components add up to th
     >>> risk = sub_book_monte_carlo_allocate_tail(engine, curve, trades, desk_keys, L, 262_144, level=0.99, seed=7)
     >>> risk["var"], risk["es"], risk["comp_es"]                 # the firm's, and [B] shares with sum(comp_es) = es
     >>> monte_carlo_shocks(L, 1, 7, first_scenario=int(risk["scenarios"][0]))     # the firm's worst scenario, made again
+
+Full revaluation on the same shocks: the scenario kernels read discount factors only, so the shock rows are turned into
+``dfs [S, K]`` where the generator wrote them (adr_curve_dfs_shocked, csrc/curve_dfs.hip: the bootstrap scan, values only,
+with the curve builder's bits) and priced per desk by the sub-book launch, a tile of scenarios at a time:
+
+    >>> curves = ShockedCurves(model, "GBP_OIS_SONIA")
+    >>> risk = monte_carlo_revalue_var_es(curves, trades, desk_keys, L, 262_144, level=0.99, seed=7)
+    >>> gap = monte_carlo_explain_var_es(engine, curves, curve, trades, desk_keys, L, 262_144, seed=7)["gap_var"]
 """
 from __future__ import annotations
 
@@ -35,9 +43,10 @@ import numpy as np
 
 from ... import _native
 from ...utils.error import LibError
-from ...utils.global_types import RequestTypes
+from ...utils.global_types import CurveTypes, RequestTypes
+from ..curves.curve_tables import build_engine_curve
 from .ladder_pnl import ladder_rows
-from .scenarios import _tail_args, tail_count
+from .scenarios import _interp_value, _tail_args, compile_book, split_sub_books, tail_count
 
 
 def factor_from_covariance(cov_bp2, n_factors=None) -> np.ndarray:
@@ -286,3 +295,244 @@ def sub_book_monte_carlo_var_es(engine, ir_model, trades, keys, factor_bp, n_sce
     risk = monte_carlo_var_es(out["delta"], out["gamma"], factor_bp, n_scenarios, level=level, seed=seed, antithetic=antithetic,
                               host=host, ctx=ctx)
     return {"labels": out["labels"], **risk}
+
+
+# --------------------------------------------------------------------------- full revaluation on Monte Carlo shock rows
+SCENARIO_LAUNCH_MAX = 65535 * 64         # scenarios of one sub-book launch (csrc/scenario_common.hpp, launch_grid)
+
+
+class ShockedCurves:
+    """What turns shock rows of ``model.curves[curve_name]``'s par quotes into discount factors: the base `EngineCurve`
+    (the host builder's, without derivatives), its par rates, the interpolation scheme and, on first use on the device, a
+    `_native.CurvePlan` on ``ctx`` (default: the default context).  No curve is built here - `ScenarioGrid` holds whole
+    curves with their Jacobians for a few thousand scenarios; this holds the recipe for any number of them."""
+
+    def __init__(self, model, curve_name: str, ctx=None):
+        if curve_name not in model._curve_params_dict:
+            raise ValueError(f"No stored parameters found for curve '{curve_name}'")
+        self.model, self.curve_name = model, curve_name
+        self.curve = getattr(model.curves, curve_name)
+        self.method = _interp_value(self.curve._interp_type)
+        self.base = build_engine_curve(self.curve.swap_rates, self.curve.swap_times, self.curve.year_fracs, with_hessian=False)
+        self.rates = self.base.rates
+        self._ctx, self._plan = ctx, None
+
+    @property
+    def n_pillars(self) -> int:
+        return int(self.rates.size)
+
+    @property
+    def n_knots(self) -> int:
+        return self.base.n_knots
+
+    def context(self):
+        if self._ctx is None:
+            self._ctx = _native.default_context()
+        return self._ctx
+
+    def plan(self):
+        if self._plan is None:
+            self._plan = _native.CurvePlan(self.context(), self.method, self.base)
+        return self._plan
+
+    def dfs(self, shocks_bp, host: bool = False):
+        """``(dfs [S, K], bad [S])`` of the shock rows ``shocks_bp [S, ld >= P]`` (adr_curve_dfs_shocked, or its CPU twin)."""
+        if host:
+            return _native.curve_dfs_shocked_host(self.base.acc, self.base.pillar, self.base.prev_idx, self.rates, shocks_bp)
+        return _native.curve_dfs_shocked(self.context(), self.plan(), self.rates, shocks_bp)
+
+    def _book(self, trades, keys):
+        return split_sub_books(*compile_book(trades, self.curve._value_dt, CurveTypes[self.curve_name]), keys)
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+
+def revalue_scenario_bytes(curves: ShockedCurves, n_trades: int, n_sub_books: int) -> int:
+    """Bytes of scratch ONE scenario of a revaluation tile takes: its row of ``dfs`` (K doubles), the bootstrap's scratch
+    (K + P), the sub-book launch's (adr_scenario_subbook_work: a double per chunk of 64 trades and desk) and its column of
+    the ``[B, tile]`` rows."""
+    return 8 * (2 * curves.n_knots + curves.n_pillars + _native.scenario_subbook_work(n_trades, n_sub_books, 1) + n_sub_books)
+
+
+def _scenario_tile(curves, n, B, S, max_bytes):
+    """Scenarios per tile: the ``[B, S + 1]`` rows and the tile's scratch stay under ``max_bytes``."""
+    per, rows = revalue_scenario_bytes(curves, n, B), 8 * B * (S + 1)
+    if int(max_bytes) - rows < per:
+        raise LibError(f"the [{B}, {S} + 1] P&L rows ({rows} bytes) and one scenario's scratch ({per} bytes) do not fit max_bytes = "
+                       f"{int(max_bytes)}: raise it, or revalue fewer scenarios or desks at a time")
+    return int(min(S, SCENARIO_LAUNCH_MAX, (int(max_bytes) - rows) // per))
+
+
+def _raise_bad(count, first):
+    raise LibError(f"{count} scenario(s) give a discount factor that is not finite or not positive, the first at index {first}: "
+                   "the shocks are too large for the curve")
+
+
+def _revalue_rows_host(curves, sb, shocks, tile):
+    """``[B, S + 1]`` on the CPU twins: the desks' PVs under the shock rows, tile by tile, and under the zero shock last."""
+    S, B = shocks.shape[0], len(sb.labels)
+    rows = np.empty((B, S + 1))
+    zero = np.zeros((1, shocks.shape[1]))
+    count, first = 0, -1
+    for s0, x in [(s0, shocks[s0:s0 + tile]) for s0 in range(0, S, tile)] + [(S, zero)]:
+        dfs, bad = curves.dfs(x, host=True)
+        if bad.any() and count == 0:
+            first = s0 + int(np.argmax(bad != 0))
+        count += int(np.count_nonzero(bad))
+        if count == 0:                  # (once a scenario is bad only the flags of the rest are wanted)
+            rows[:, s0:s0 + x.shape[0]] = _native.scenario_subbook_pv_host(curves.method, curves.base.times, dfs, sb.batch,
+                                                                           sb.sub_off)["sub_pv"]
+    if count:
+        _raise_bad(count, first)
+    return rows
+
+
+def _revalue_rows_dev(curves, sb, dev_trades, shocks_ptr, S, ld, tile, rows, bad, new, up):
+    """Enqueue on the context's stream: ``rows [B, S + 1]`` (a torch tensor) of the desks' PVs under the device shock rows
+    ``[S, ld]`` at ``shocks_ptr``, tile by tile, and under the zero shock as column ``S``; ``bad [S + 1]`` int32 beside
+    them.  Returns the buffers the stream still reads."""
+    ctx, plan, K, B, n = curves.context(), curves.plan(), curves.n_knots, len(sb.labels), sb.batch.n_trades
+    times, base, sub_plan = up(curves.base.times), up(curves.rates), up(_native.scenario_subbook_plan(n, sb.sub_off))
+    zero = up(np.zeros(curves.n_pillars))
+    dfs, work_b, part = new(tile, K), new(_native.curve_dfs_shocked_work(plan, tile)), new(B, tile)
+    work_s = new(_native.scenario_subbook_work(n, B, tile))
+    for s0, nt, x_ptr, x_ld in [(s0, min(tile, S - s0), shocks_ptr + 8 * ld * s0, ld) for s0 in range(0, S, tile)] + \
+            [(S, 1, zero.data_ptr(), curves.n_pillars)]:
+        _native.curve_dfs_shocked_dev(ctx, plan, base.data_ptr(), nt, x_ld, x_ptr, dfs.data_ptr(), work_b.data_ptr(),
+                                      bad_ptr=bad.data_ptr() + 4 * s0)
+        _native.scenario_subbook_pv_dev(ctx, curves.method, K, times.data_ptr(), nt, dfs.data_ptr(), dev_trades, B,
+                                        sub_plan.data_ptr(), part.data_ptr(), work_s.data_ptr())
+        _native.scenario_rows_place_dev(ctx, B, nt, part.data_ptr(), S + 1, s0, rows.data_ptr())
+    return times, base, sub_plan, zero, dfs, work_b, part, work_s
+
+
+def _check_bad_dev(bad):
+    """After the stream has drained: the `LibError` of the bad flags, counted on the device."""
+    count = int(bad.count_nonzero())
+    if count:
+        _raise_bad(count, int(bad.nonzero()[0]))
+
+
+def _torch_buffers(ctx):
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    return torch, dev, up, new
+
+
+def revalue_shocks_sub_books(curves: ShockedCurves, trades, keys, shocks_bp, host: bool = False, max_bytes: int = 2 ** 31) -> dict:
+    """``{"labels": [...], "pnl": [B, S]}``: every desk's full-revaluation P&L under the explicit shock rows ``shocks_bp
+    [S, P]`` (basis points on the par quotes; columns beyond ``P`` are not read).
+
+    ``trades`` and ``keys`` as `ScenarioGrid.revalue_sub_books` takes them (`compile_book`, `split_sub_books`).  The
+    scenarios are cut into tiles so that the tile's ``dfs``, the two scratch buffers, its ``[B, tile]`` rows and the ``[B, S
+    + 1]`` result stay under ``max_bytes`` (`revalue_scenario_bytes` per scenario; a `LibError` when not even one fits); per
+    tile the bootstrap (adr_curve_dfs_shocked_dev), the sub-book launch (adr_scenario_subbook_pv_dev) and the copy into the
+    rows (adr_scenario_rows_place_dev) run on one stream.  The base PV is one more launch, on a zero shock row, whose
+    ``dfs`` are the base curve's bits: a scenario's result does not depend on the launch it is priced in, so a zero shock
+    row gives exactly 0.0 in every desk, the tiling changes no bit, and the P&L is `revalue_on_curves_sub_books`' on the
+    same ``dfs`` with the base row appended, column minus last column.  What does not depend on the curve (an FRN coupon
+    fixed and paid at the value time) cancels and is not added.  A scenario with a discount factor that is not finite or
+    not positive is a `LibError` naming the count and the first index.  ``host=True``: the CPU twins; no GPU needed."""
+    shocks = np.ascontiguousarray(shocks_bp, dtype=np.float64)
+    if shocks.ndim != 2 or shocks.shape[0] < 1 or shocks.shape[1] < curves.n_pillars:
+        raise LibError(f"shocks_bp must have shape [S >= 1, {curves.n_pillars} or more], not {list(shocks.shape)}")
+    sb = curves._book(trades, keys)
+    S, B = shocks.shape[0], len(sb.labels)
+    tile = _scenario_tile(curves, sb.batch.n_trades, B, S, max_bytes)
+    if host:
+        rows = _revalue_rows_host(curves, sb, shocks, tile)
+    else:
+        ctx = curves.context()
+        torch, dev, up, new = _torch_buffers(ctx)
+        d_shocks, d_rows = up(shocks), new(B, S + 1)
+        bad = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        with _native.DeviceTrades(ctx, sb.batch) as dev_trades:
+            held = _revalue_rows_dev(curves, sb, dev_trades, d_shocks.data_ptr(), S, shocks.shape[1], tile, d_rows, bad, new, up)
+            ctx.sync()
+        del held
+        _check_bad_dev(bad)
+        rows = d_rows.cpu().numpy()
+    return {"labels": sb.labels, "pnl": rows[:, :-1] - rows[:, -1:]}
+
+
+def monte_carlo_revalue_var_es(curves: ShockedCurves, trades, keys, factor_bp, n_scenarios: int, level: float = 0.99, seed: int = 0,
+                               antithetic: bool = False, host: bool = False, max_bytes: int = 2 ** 31, allocate: bool = False) -> dict:
+    """``{"labels": [...], "var": [B], "es": [B]}``: every desk's Monte Carlo VaR and expected shortfall by FULL
+    revaluation under ``n_scenarios`` normal shocks with factor matrix ``factor_bp [P, F]`` - `monte_carlo_var_es`' shock
+    rows (the same seed gives the same bits), priced as `revalue_shocks_sub_books` prices them.
+
+    One stream, torch tensors as buffers: the shocks (adr_shock_normal_dev), the tiles of `revalue_shocks_sub_books` into
+    ``rows [B, S + 1]`` with the base PV as column ``S``, then adr_scenario_tail_select_dev with ``base_col = S``; only the
+    ``[B]`` vectors leave the device.  ``allocate=True`` adds adr_scenario_tail_alloc_select_dev on the same rows: the
+    result is then ``{"labels", "var", "es", "firm_var", "firm_es", "comp_var" [B], "comp_es" [B]}`` - the firm's figures
+    and every desk's share of them, which add up to them (`allocate_tail_select`).  The rows must fit the device: when
+    ``[B, S + 1]`` and one scenario's scratch exceed ``max_bytes`` a `LibError` says so.  Bit for bit the result is
+    `tail_measures_select` (and `allocate_tail_select`) of `revalue_shocks_sub_books`' rows on `monte_carlo_shocks`,
+    whatever the tiling.  ``host=True``: the CPU twins on the host's shocks; no GPU needed."""
+    factor = np.ascontiguousarray(factor_bp, dtype=np.float64)
+    if factor.ndim != 2 or factor.shape[0] != curves.n_pillars:
+        raise LibError(f"factor_bp [P, F] needs one row per par quote ({curves.n_pillars}), not {list(factor.shape)}")
+    (P, F), S = factor.shape, int(n_scenarios)
+    if S < 1:
+        raise LibError("at least one scenario is needed")
+    k = tail_count(level, S)
+    _check_tail_count(k, level, S, _native.SCENARIO_ALLOC_MAX if allocate else None)
+    sb = curves._book(trades, keys)
+    B = len(sb.labels)
+    tile = _scenario_tile(curves, sb.batch.n_trades, B, S, max_bytes)
+    if host:
+        rows = _revalue_rows_host(curves, sb, _native.shock_normal_host(factor, S, seed, antithetic, 0), tile)
+        var, es = _native.scenario_tail_select_host(rows, k, S)
+        out = {"labels": sb.labels, "var": var, "es": es}
+        if allocate:
+            firm = _native.scenario_tail_alloc_select_host(rows, k, S)
+            out.update(firm_var=firm["var"], firm_es=firm["es"], comp_var=firm["comp_var"], comp_es=firm["comp_es"])
+        return out
+
+    ctx = curves.context()
+    torch, dev, up, new = _torch_buffers(ctx)
+    d_factor, shocks, rows, res = up(factor), new(S, P), new(B, S + 1), new(4, B + 1)    # res: var, es, [comp_var | firm], [comp_es | firm]
+    bad = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    n_work = max(_native.scenario_tail_select_work(B, S + 1, k), _native.scenario_tail_alloc_select_work(B, S + 1, k) if allocate else 0)
+    work = torch.empty(n_work, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    with _native.DeviceTrades(ctx, sb.batch) as dev_trades:
+        _native.shock_normal_dev(ctx, seed, 0, S, P, F, d_factor.data_ptr(), antithetic, shocks.data_ptr())
+        held = _revalue_rows_dev(curves, sb, dev_trades, shocks.data_ptr(), S, P, tile, rows, bad, new, up)
+        at = lambda r, c=0: res.data_ptr() + 8 * (r * (B + 1) + c)
+        _native.scenario_tail_select_dev(ctx, B, S + 1, rows.data_ptr(), k, at(0), at(1), work.data_ptr(), base_col=S)
+        if allocate:
+            _native.scenario_tail_alloc_select_dev(ctx, B, S + 1, rows.data_ptr(), k, at(2, B), at(3, B), at(2), at(3), work.data_ptr(),
+                                                   base_col=S)
+        ctx.sync()
+    del held
+    _check_bad_dev(bad)
+    got = res.cpu().numpy()
+    out = {"labels": sb.labels, "var": got[0, :B].copy(), "es": got[1, :B].copy()}
+    if allocate:
+        out.update(firm_var=float(got[2, B]), firm_es=float(got[3, B]), comp_var=got[2, :B].copy(), comp_es=got[3, :B].copy())
+    return out
+
+
+def monte_carlo_explain_var_es(engine, curves: ShockedCurves, ir_model, trades, keys, factor_bp, n_scenarios: int, level: float = 0.99,
+                               seed: int = 0, antithetic: bool = False, host: bool = False, max_bytes: int = 2 ** 31) -> dict:
+    """The delta-gamma figures held against full revaluation on the SAME shock rows: ``{"labels", "full_var", "full_es",
+    "dg_var", "dg_es", "gap_var", "gap_es"}``, ``[B]`` each - `monte_carlo_revalue_var_es` beside
+    `sub_book_monte_carlo_var_es` on one seed (the generator gives both the same bits), ``gap = full - dg``: what the
+    second-order expansion misses in the tail, where it is weakest.  ``ir_model``: the curve ``curves`` was made from, as
+    `sub_book_monte_carlo_var_es` takes it."""
+    trades, keys = (trades if hasattr(trades, "n_trades") else list(trades)), list(keys)
+    full = monte_carlo_revalue_var_es(curves, trades, keys, factor_bp, n_scenarios, level=level, seed=seed, antithetic=antithetic,
+                                      host=host, max_bytes=max_bytes)
+    dg = sub_book_monte_carlo_var_es(engine, ir_model, trades, keys, factor_bp, n_scenarios, level=level, seed=seed,
+                                     antithetic=antithetic, host=host)
+    if dg["labels"] != full["labels"]:
+        raise LibError("the two routes order the desks differently")
+    return {"labels": full["labels"], "full_var": full["var"], "full_es": full["es"], "dg_var": dg["var"], "dg_es": dg["es"],
+            "gap_var": full["var"] - dg["var"], "gap_es": full["es"] - dg["es"]}

@@ -1085,6 +1085,42 @@ int adr_tail_components_dev(adr_ctx* ctx, int64_t B, int k, const double* pnl_de
 int adr_tail_components_host(int64_t B, int k, const double* pnl, double* comp_var, double* comp_es);
 
 /*
+ * Discount factors of shocked curves, values only: the link between the Monte Carlo shock rows and the scenario kernels,
+ * which read discount factors alone.  For shock row s of shocks_bp[S][ld] (basis points; the first P columns are read,
+ * ld >= P is the row stride, so augmented rows - spread or breakeven columns behind the quotes - go in without a copy):
+ *
+ *   r_p  = base_rates[p] + shocks_bp[s][p] * 1e-4           (one rounded product, one rounded sum)
+ *   v    = 1 + r a_i ;  Pp = 0 <= prev_idx[i] < i ? pv01[prev_idx[i]] : 0 ;  r = r_{pillar[i]}
+ *   d_i  = prev_idx[i] >= 0 ? (1 - r Pp) / v : 1 / v ;  pv01[i] = Pp + a_i d_i ;  dfs[s][i] = d_i       i = 0 .. K - 1
+ *
+ * - the scan of adr_curve_set_build without its Jacobian and Hessian: 8 K bytes per scenario instead of
+ * 8 K (1 + P + P P).  Every step is one IEEE operation in this order, nothing is fused and no library function is
+ * called: dfs[s] has the bits of adr_curve_set_build's discount factors at the rates r, on the device and on the host.
+ * bad[s] (NULL: not wanted) is 1 where any d_i of scenario s is not finite or not positive, else 0; the row is written
+ * all the same.
+ *
+ * adr_curve_dfs_shocked_dev: `plan`'s scan arrays (acc, pillar, prev_idx; K knots, P <= ADR_MAX_PLAN_PILLARS pillars),
+ * device arrays, and work_dev of adr_curve_dfs_shocked_work(plan, S) DOUBLES, (K + P) S: one kernel on `stream` (NULL:
+ * the ctx's own), no allocation, no synchronisation, scalar checks only.  adr_curve_dfs_shocked: host arrays, blocks (one
+ * allocation); it also refuses base rates that are not finite.  adr_curve_dfs_shocked_host: the CPU twin on the scan
+ * arrays themselves, no GPU and no plan; it also refuses a pillar outside 0 .. P - 1 and a prev_idx outside -1 .. K - 1.
+ * ADR_ERR_INVALID: NULL pointers (bad excepted), S < 1, ld < P, a plan of another ctx.  _work returns 0 for those.
+ *
+ * adr_scenario_rows_place_dev: rows[b][s0 + s] = tile[b][s] for b < B, s < S_tile; tile[B][S_tile], rows[B][S_tot].  The
+ * sub-book launch writes [B][S_tile] for a tile of scenarios, the tail entries read rows [B][S_tot].  One kernel on
+ * `stream`.  ADR_ERR_INVALID: B < 1, S_tile < 1, s0 < 0, s0 + S_tile > S_tot, NULL pointers.
+ */
+int adr_curve_dfs_shocked(adr_ctx* ctx, const adr_curve_plan* plan, const double* base_rates, int S, int ld, const double* shocks_bp,
+                          double* dfs, int32_t* bad);
+int adr_curve_dfs_shocked_dev(adr_ctx* ctx, const adr_curve_plan* plan, const double* base_rates_dev, int S, int ld,
+                              const double* shocks_bp_dev, double* dfs_dev, int32_t* bad_dev, double* work_dev, void* stream);
+int64_t adr_curve_dfs_shocked_work(const adr_curve_plan* plan, int S);
+int adr_curve_dfs_shocked_host(int K, int P, const double* acc, const int32_t* pillar, const int32_t* prev_idx, const double* base_rates,
+                               int S, int ld, const double* shocks_bp, double* dfs, int32_t* bad);
+int adr_scenario_rows_place_dev(adr_ctx* ctx, int64_t B, int S_tile, const double* tile_dev, int S_tot, int s0, double* rows_dev,
+                                void* stream);
+
+/*
  * Credit sub-book Greeks: per sub-book the PV, the curve delta and gamma AT THE TRADES' SPREADS, CS01 and spread gamma
  * per credit bucket and the rate x spread cross gamma, from one launch chain.  The spread side is adr_credit_scenario_pv's:
  * z[n] (z-spread of a bond, discount margin of an FRN), bucket[n] in -1 .. G - 1 (-1: no bucket), 0 <= G <=

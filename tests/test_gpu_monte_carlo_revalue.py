@@ -1,0 +1,276 @@
+"""Discount factors of shocked curves and Monte Carlo VaR by full revaluation on the GPU (adr_curve_dfs_shocked*,
+adr_scenario_rows_place_dev, csrc/curve_dfs.hip; market/position/monte_carlo.py), on the tables of the CPU suite
+(tests/_curve_dfs_cases.py): the device's discount factors with the twin's bits on every grid and scenario count and with
+the curve builder's own, the cut of a set, the device-array entries in guarded buffers; the chain against
+`revalue_on_curves_sub_books` on the twin's rows, whatever the tiling, its tail figures against the tail entries, the device
+against the host chain, and the third-order gap to delta-gamma."""
+import numpy as np
+import pytest
+import torch
+
+from adrates_amd import _native
+from adrates_amd.market.position.engine import Engine
+from adrates_amd.market.position.ladder_pnl import delta_gamma_sub_books
+from adrates_amd.market.position.monte_carlo import (ShockedCurves, allocate_tail_select, factor_from_covariance,
+                                                     monte_carlo_explain_var_es, monte_carlo_revalue_var_es, monte_carlo_shocks,
+                                                     revalue_scenario_bytes, revalue_shocks_sub_books,
+                                                     sub_book_monte_carlo_var_es, tail_measures_select)
+from adrates_amd.market.position.scenarios import revalue_on_curves_sub_books, tail_count
+from adrates_amd.utils.error import LibError
+
+from . import _curve_dfs_cases as C
+from . import _tail_alloc_cases as TA
+from ._parity import REL_TOL
+from .test_gpu_monte_carlo import GUARD
+
+pytestmark = pytest.mark.gpu
+TAIL = 16                                                           # guard words behind every buffer
+
+
+@pytest.fixture(scope="module")
+def plans(gpu_ctx):
+    """One `CurvePlan` per grid of the table, made once."""
+    made = {name: _native.CurvePlan(gpu_ctx, C.INTERP.value, C.grid(name)) for name in C.GRIDS}
+    yield made
+    for plan in made.values():
+        plan.close()
+
+
+def twin(g, x):
+    return _native.curve_dfs_shocked_host(g.acc, g.pillar, g.prev_idx, g.rates, x)
+
+
+# ---------------------------------------------------------------------------------------------------------- bootstrap
+@pytest.mark.parametrize("name", C.GRIDS)
+def test_device_has_the_twins_bits(gpu_ctx, plans, name):
+    """Every scenario count of the table as a launch of its own, and the same bits from a second run."""
+    g = C.grid(name)
+    for S in C.SCENARIOS:
+        x = C.rows(g.rates.size, S)
+        dfs, bad = _native.curve_dfs_shocked(gpu_ctx, plans[name], g.rates, x)
+        ref, ref_bad = twin(g, x)
+        assert np.array_equal(C.bits(dfs), C.bits(ref)) and np.array_equal(bad, ref_bad), S
+    again, _ = _native.curve_dfs_shocked(gpu_ctx, plans[name], g.rates, x)
+    assert np.array_equal(C.bits(again), C.bits(dfs)), "two runs"
+    x, flags = C.bad_rows(g)
+    dfs, bad = _native.curve_dfs_shocked(gpu_ctx, plans[name], g.rates, x)
+    assert np.array_equal(bad, flags) and C.same_bits(dfs, twin(g, x)[0]), "flagged rows are written, their neighbours keep their bits"
+    wide = np.hstack([x, np.full((5, 3), np.nan)])
+    assert C.same_bits(_native.curve_dfs_shocked(gpu_ctx, plans[name], g.rates, wide)[0], dfs), "ld > P"
+
+
+def test_device_has_the_curve_builders_bits(gpu_ctx, plans):
+    """adr_curve_set_build's discount factors at the same rates, downloaded, on the 32-pillar grid."""
+    g = C.grid("gbp32")
+    x = C.rows(32, max(C.SCENARIOS))
+    dfs, _ = _native.curve_dfs_shocked(gpu_ctx, plans["gbp32"], g.rates, x)
+    built = plans["gbp32"].build(g.rates[None, :] + x * 1e-4)
+    try:
+        for s in range(x.shape[0]):
+            assert np.array_equal(C.bits(dfs[s]), C.bits(built.download(s)[0])), s
+    finally:
+        built.close()
+
+
+def test_rows_do_not_depend_on_the_cut(gpu_ctx, plans):
+    g = C.grid("gbp32")
+    x = np.vstack([C.rows(32, 129), C.rows(32, 71)])
+    whole, _ = _native.curve_dfs_shocked(gpu_ctx, plans["gbp32"], g.rates, x)
+    at, pieces = 0, []
+    for n in (1, 63, 64, 72):
+        pieces.append(_native.curve_dfs_shocked(gpu_ctx, plans["gbp32"], g.rates, x[at:at + n])[0])
+        at += n
+    assert at == 200 and np.array_equal(C.bits(np.vstack(pieces)), C.bits(whole))
+
+
+def guarded(values, dtype=torch.float64):
+    """``values`` on the device with TAIL guard words behind them."""
+    t = torch.from_numpy(np.ascontiguousarray(values).ravel()).to(dtype)
+    return torch.cat([t, torch.full((TAIL,), GUARD, dtype=torch.float64).to(dtype)]).cuda()
+
+
+def guard_intact(t, n):
+    want = torch.full((TAIL,), GUARD, dtype=torch.float64).to(t.dtype).cuda()
+    return t.numel() == n + TAIL and bool((t[n:] == want).all())
+
+
+@pytest.mark.parametrize("name,S,extra", [("semi_annual3", 65, 0), ("gbp32", 129, 4), ("wide64", 63, 1)])
+def test_dev_entry_in_guarded_buffers(gpu_ctx, plans, name, S, extra):
+    """adr_curve_dfs_shocked_dev on a caller's stream: the blocking entry's bits, 16 guard words intact behind ``dfs``,
+    ``bad``, ``work`` and the shock matrix."""
+    g, plan = C.grid(name), plans[name]
+    K, P = g.n_knots, g.rates.size
+    x = np.hstack([C.rows(P, S), np.full((S, extra), 1e300)])
+    n_work = _native.curve_dfs_shocked_work(plan, S)
+    assert n_work == (K + P) * S and _native.curve_dfs_shocked_work(plan, 0) == 0
+    shocks, base = guarded(x), guarded(g.rates)
+    dfs, work = guarded(np.full(S * K, GUARD)), guarded(np.full(n_work, GUARD))
+    bad = guarded(np.full(S, 7), torch.int32)
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    _native.curve_dfs_shocked_dev(gpu_ctx, plan, base.data_ptr(), S, P + extra, shocks.data_ptr(), dfs.data_ptr(), work.data_ptr(),
+                                  bad_ptr=bad.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    assert guard_intact(dfs, S * K) and guard_intact(work, n_work) and guard_intact(bad, S)
+    assert guard_intact(shocks, x.size) and guard_intact(base, P)
+    ref, ref_bad = _native.curve_dfs_shocked(gpu_ctx, plan, g.rates, x)
+    assert np.array_equal(C.bits(dfs[:S * K].cpu().numpy().reshape(S, K)), C.bits(ref))
+    assert np.array_equal(bad[:S].cpu().numpy(), ref_bad) and not ref_bad.any()
+    assert np.array_equal(shocks[:x.size].cpu().numpy(), x.ravel())
+    # without the flags: the same rows
+    dfs2 = guarded(np.full(S * K, GUARD))
+    _native.curve_dfs_shocked_dev(gpu_ctx, plan, base.data_ptr(), S, P + extra, shocks.data_ptr(), dfs2.data_ptr(), work.data_ptr(),
+                                  stream=stream.cuda_stream)
+    stream.synchronize()
+    assert guard_intact(dfs2, S * K) and torch.equal(dfs2, dfs)
+
+
+def test_dev_entry_refusals(gpu_ctx, plans):
+    buf = torch.full((4096,), GUARD, dtype=torch.float64, device="cuda")
+    p, plan = buf.data_ptr(), plans["semi_annual3"]
+    other = _native.Context(0)
+    try:
+        for ctx, args in ((gpu_ctx, (p, 0, 3, p, p, p)), (gpu_ctx, (p, 4, 2, p, p, p)), (gpu_ctx, (0, 4, 3, p, p, p)),
+                          (gpu_ctx, (p, 4, 3, 0, p, p)), (gpu_ctx, (p, 4, 3, p, 0, p)), (gpu_ctx, (p, 4, 3, p, p, 0)),
+                          (other, (p, 4, 3, p, p, p))):
+            with pytest.raises(LibError) as e:
+                _native.curve_dfs_shocked_dev(ctx, plan, *args)
+            assert e.value.status == -1, args
+        g = C.grid("semi_annual3")
+        for base, x in ((np.array([0.03, np.nan, 0.04]), C.rows(3, 4)), (g.rates, C.rows(3, 4)[:, :2])):
+            with pytest.raises(LibError) as e:
+                _native.curve_dfs_shocked(gpu_ctx, plan, base, x)
+            assert e.value.status == -1
+        for args in ((0, 4, p, 8, 0, p), (2, 0, p, 8, 0, p), (2, 4, p, 8, 5, p), (2, 4, p, 8, -1, p), (2, 4, 0, 8, 0, p), (2, 4, p, 8, 0, 0)):
+            with pytest.raises(LibError) as e:
+                _native.scenario_rows_place_dev(gpu_ctx, *args)
+            assert e.value.status == -1, args
+    finally:
+        other.close()
+    gpu_ctx.sync()
+    assert bool((buf == GUARD).all())
+
+
+@pytest.mark.parametrize("B,S_tile,S_tot", [(1, 1, 1), (5, 64, 130), (3, 257, 700), (70000, 1, 3)])
+def test_rows_place_leaves_the_other_columns(gpu_ctx, B, S_tile, S_tot):
+    tile = np.random.default_rng([B, S_tile]).standard_normal((B, S_tile))
+    d_tile = guarded(tile)
+    stream = torch.cuda.Stream()
+    for s0 in sorted({0, min(1, S_tot - S_tile), S_tot - S_tile}):
+        rows = guarded(np.full(B * S_tot, GUARD))
+        torch.cuda.synchronize()
+        _native.scenario_rows_place_dev(gpu_ctx, B, S_tile, d_tile.data_ptr(), S_tot, s0, rows.data_ptr(), stream=stream.cuda_stream)
+        stream.synchronize()
+        want = np.full((B, S_tot), GUARD)
+        want[:, s0:s0 + S_tile] = tile
+        assert guard_intact(rows, B * S_tot) and np.array_equal(C.bits(rows[:B * S_tot].cpu().numpy().reshape(B, S_tot)), C.bits(want)), s0
+    assert guard_intact(d_tile, tile.size)
+
+
+# -------------------------------------------------------------------------------------------------------------- chain
+@pytest.fixture(scope="module")
+def chain(gpu_ctx):
+    """The model, its shocked-curve recipe, the factor, the DEVICE's shock rows and the device chain's P&L, made once."""
+    model, ir = C.LP.gbp(C.INTERP)
+    curves = ShockedCurves(model, "GBP_OIS_SONIA", ctx=gpu_ctx)
+    factor = factor_from_covariance(C.covariance(curves.n_pillars))
+    x = monte_carlo_shocks(factor, C.CHAIN_S, C.SEED, ctx=gpu_ctx)
+    pnl = revalue_shocks_sub_books(curves, C.chain_book(), C.chain_keys(), x)
+    yield dict(model=model, ir=ir, curves=curves, factor=factor, x=x, pnl=pnl)
+    curves.close()
+
+
+def test_chain_has_the_bits_of_revaluation_on_the_twins_rows(gpu_ctx, chain):
+    curves, x = chain["curves"], chain["x"]
+    assert chain["pnl"]["labels"] == [0, 1, 2, 3, 4] and chain["pnl"]["pnl"].shape == (5, C.CHAIN_S)
+    dfs, bad = curves.dfs(np.vstack([x, np.zeros((1, 32))]), host=True)
+    assert not bad.any()
+    sub = revalue_on_curves_sub_books(C.INTERP, curves.base.times, dfs, C.chain_book(), C.chain_keys(), C.VD, ctx=gpu_ctx)["sub_pv"]
+    assert np.array_equal(C.bits(chain["pnl"]["pnl"]), C.bits(sub[:, :-1] - sub[:, -1:]))
+
+
+def test_chain_does_not_depend_on_the_tiling(chain):
+    curves, book, keys = chain["curves"], C.chain_book(), C.chain_keys()
+    per, rows = revalue_scenario_bytes(curves, book.n_trades, 5), 8 * 5 * (C.CHAIN_S + 1)
+    for tile in C.TILES:
+        got = revalue_shocks_sub_books(curves, book, keys, chain["x"], max_bytes=rows + tile * per)
+        assert np.array_equal(C.bits(got["pnl"]), C.bits(chain["pnl"]["pnl"])), tile
+    x = chain["x"][:5].copy()
+    x[2] = 0.0
+    pnl = revalue_shocks_sub_books(curves, book, keys, x)["pnl"]
+    assert np.array_equal(C.bits(pnl[:, 2]), C.bits(np.zeros(5))) and np.all(pnl[:, [0, 1, 3, 4]] != 0.0), "a zero shock row"
+
+
+def test_var_es_and_allocation_are_the_tail_entries_of_the_rows(chain):
+    curves, book, keys, pnl = chain["curves"], C.chain_book(), C.chain_keys(), chain["pnl"]["pnl"]
+    per = revalue_scenario_bytes(curves, book.n_trades, 5)
+    for level in (0.99, 0.9):
+        var, es = tail_measures_select(pnl, level, host=True)
+        firm = allocate_tail_select(pnl, level, host=True)
+        for max_bytes in (2 ** 31, 8 * 5 * (C.CHAIN_S + 1) + 64 * per):
+            got = monte_carlo_revalue_var_es(curves, book, keys, chain["factor"], C.CHAIN_S, level=level, seed=C.SEED, max_bytes=max_bytes)
+            assert sorted(got) == ["es", "labels", "var"] and got["labels"] == [0, 1, 2, 3, 4]
+            assert np.array_equal(C.bits(got["var"]), C.bits(var)) and np.array_equal(C.bits(got["es"]), C.bits(es)), level
+        got = monte_carlo_revalue_var_es(curves, book, keys, chain["factor"], C.CHAIN_S, level=level, seed=C.SEED, allocate=True)
+        assert np.array_equal(C.bits(got["var"]), C.bits(var)) and np.array_equal(C.bits(got["es"]), C.bits(es))
+        assert got["firm_var"] == firm["var"] and got["firm_es"] == firm["es"]
+        assert np.array_equal(C.bits(got["comp_var"]), C.bits(firm["comp_var"])) and np.array_equal(C.bits(got["comp_es"]), C.bits(firm["comp_es"]))
+        TA.check(dict(var=got["firm_var"], es=got["firm_es"], comp_var=got["comp_var"], comp_es=got["comp_es"]), pnl, -1,
+                 tail_count(level, C.CHAIN_S))
+
+
+def test_device_chain_against_the_host_chain(chain):
+    """On the same shock rows the two chains differ by the pricing kernels' exp and log alone.  The project's metric,
+    |a - b| / max(1, |b|) per unit notional within REL_TOL, holds each desk PV to REL_TOL max(N, |PV|), N the desk's summed
+    notionals (the synthetic OIS carry amounts of their own, so a desk's PV can be far above N); a P&L is the difference
+    of two PVs, the scenario's and the base's, and is held to the sum of their two bounds."""
+    curves, book, keys = chain["curves"], C.chain_book(), C.chain_keys()
+    host = revalue_shocks_sub_books(curves, book, keys, chain["x"], host=True)
+    dfs, _ = curves.dfs(np.vstack([chain["x"], np.zeros((1, 32))]), host=True)
+    pv = np.abs(revalue_on_curves_sub_books(C.INTERP, curves.base.times, dfs, book, keys, C.VD, host=True)["sub_pv"])
+    N = C.desk_notionals()[:, None]
+    bound = REL_TOL * (np.maximum(N, pv[:, :-1]) + np.maximum(N, pv[:, -1:]))
+    err = np.abs(chain["pnl"]["pnl"] - host["pnl"])
+    print("device against host chain, worst share of the bound per desk:", np.max(err / bound, axis=1))
+    assert host["labels"] == chain["pnl"]["labels"] and np.all(err <= bound)
+
+
+def test_bad_scenarios_raise(chain):
+    curves, book, keys = chain["curves"], C.chain_book(), C.chain_keys()
+    with pytest.raises(LibError, match=r"scenario\(s\) give a discount factor .* first at index \d+"):
+        monte_carlo_revalue_var_es(curves, book, keys, chain["factor"] * 1e4, C.CHAIN_S, seed=C.SEED)
+    x = chain["x"][:4].copy()
+    x[1, 3], x[3, 0] = np.nan, np.nan
+    with pytest.raises(LibError, match=r"2 scenario\(s\) .* first at index 1"):
+        revalue_shocks_sub_books(curves, book, keys, x)
+    with pytest.raises(LibError, match="do not fit max_bytes"):
+        monte_carlo_revalue_var_es(curves, book, keys, chain["factor"], C.CHAIN_S, max_bytes=8 * 5 * (C.CHAIN_S + 1))
+
+
+# ------------------------------------------------------------------------------------------ the reason for the feature
+def test_gap_to_delta_gamma_is_third_order(gpu_ctx, chain):
+    """The same seed with the factor L and with L / 2: the rows are exact halves, and the worst |full - delta-gamma| over
+    the scenarios, per desk, falls by about 8 (the host twins: 8.229, 7.820, 7.893, 7.837, 7.844)."""
+    curves, book, keys, L = chain["curves"], C.chain_book(), C.chain_keys(), chain["factor"]
+    engine = Engine(chain["model"])
+    x, half = chain["x"], monte_carlo_shocks(0.5 * L, C.CHAIN_S, C.SEED, ctx=gpu_ctx)
+    assert np.array_equal(C.bits(half), C.bits(0.5 * x))
+    gap = []
+    for rows, full in ((x, chain["pnl"]["pnl"]), (half, revalue_shocks_sub_books(curves, book, keys, half)["pnl"])):
+        gap.append((full, delta_gamma_sub_books(engine, chain["ir"], book, keys, rows)["pnl"]))
+    ratios = C.gap_ratios(*gap[0], *gap[1])
+    print("device: gap ratios per desk", np.round(ratios, 3))
+    assert np.all((C.GAP_BAND[0] < ratios) & (ratios < C.GAP_BAND[1])), ratios
+
+
+def test_explain_sets_the_two_routes_side_by_side(chain):
+    curves, book, keys, L = chain["curves"], C.chain_book(), C.chain_keys(), chain["factor"]
+    engine = Engine(chain["model"])
+    got = monte_carlo_explain_var_es(engine, curves, chain["ir"], book, keys, L, C.CHAIN_S, level=0.9, seed=C.SEED)
+    full = monte_carlo_revalue_var_es(curves, book, keys, L, C.CHAIN_S, level=0.9, seed=C.SEED)
+    dg = sub_book_monte_carlo_var_es(engine, chain["ir"], book, keys, L, C.CHAIN_S, level=0.9, seed=C.SEED)
+    assert got["labels"] == full["labels"] == dg["labels"]
+    for key, ref in (("full_var", full["var"]), ("full_es", full["es"]), ("dg_var", dg["var"]), ("dg_es", dg["es"]),
+                     ("gap_var", full["var"] - dg["var"]), ("gap_es", full["es"] - dg["es"])):
+        assert np.array_equal(C.bits(got[key]), C.bits(ref)), key
+    assert np.all(np.abs(got["gap_var"]) < 0.05 * np.abs(got["full_var"]))
