@@ -208,6 +208,11 @@ _SIGNATURES = {
     "adr_curve_dfs_shocked_work": (C.c_int64, [_vp, C.c_int]),
     "adr_curve_dfs_shocked_host": (C.c_int, [C.c_int, C.c_int, _dp, _i32p, _i32p, _dp, C.c_int, C.c_int, _dp, _dp, _i32p]),
     "adr_scenario_rows_place_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "adr_shock_columns": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _i32p]),
+    "adr_shock_columns_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp]),
+    "adr_shock_columns_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _i32p]),
+    "adr_scenario_rows_merge_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "adr_scenario_rows_merge_host": (C.c_int, [C.c_int64, C.c_int, _dp, C.c_int64, C.c_int, C.c_int, _dp, _i64p, _i32p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1956,6 +1961,70 @@ def scenario_rows_place_dev(ctx: Context, B: int, S_tile: int, tile_ptr: int, S_
     and ``rows`` [B, S_tot]."""
     _check(load().adr_scenario_rows_place_dev(ctx._h, int(B), int(S_tile), _dev(tile_ptr), int(S_tot), int(s0), _dev(rows_ptr),
                                               _vp(stream or None)), "adr_scenario_rows_place_dev")
+
+
+# ------------------------------------------- shock columns and the merge of sub-book rows (csrc/shock_columns.hip)
+def _shock_columns_call(fn, head, shocks_bp, col0, n, base, floor, bad):
+    shocks = _f64(shocks_bp)
+    if shocks.ndim != 2:
+        raise LibError(f"shocks_bp must have shape [n_scenarios, ld], not {list(shocks.shape)}")
+    base = None if base is None else _f64(base).reshape(-1)
+    if base is not None and base.size != int(n):
+        raise LibError(f"base needs one entry per column ({int(n)}), not {base.size}")
+    S, ld = shocks.shape
+    bad = np.zeros(S, dtype=np.int32) if bad is None else np.ascontiguousarray(bad, dtype=np.int32).reshape(-1).copy()
+    if bad.size != S:
+        raise LibError(f"bad needs one flag per scenario ({S}), not {bad.size}")
+    out = np.empty((S, max(int(n), 0)))
+    _check(fn(*head, S, ld, _ptr(shocks), int(col0), int(n), _ptr(base), int(floor is not None), float(floor or 0.0), _ptr(out),
+              _ptr(bad, _i32p)), fn.__name__)
+    return out, bad
+
+
+def shock_columns(ctx: Context, shocks_bp, col0: int, n: int, base=None, floor=None, bad=None):
+    """``(out [S, n], bad [S] int32)``: ``base + shocks_bp[:, col0:col0 + n] * 1e-4`` (``base`` None: the product itself) on
+    the device (adr_shock_columns, blocking), a rounded product and a rounded sum - NumPy's bits.  ``bad[s]`` is 1 where an
+    entry of row ``s`` is not finite or, with ``floor``, is ``<= floor``; a flag of the ``bad`` passed in stays set."""
+    return _shock_columns_call(load().adr_shock_columns, (ctx._h,), shocks_bp, col0, n, base, floor, bad)
+
+
+def shock_columns_host(shocks_bp, col0: int, n: int, base=None, floor=None, bad=None):
+    """`shock_columns` on the CPU (adr_shock_columns_host): the same bits; no GPU needed."""
+    return _shock_columns_call(load().adr_shock_columns_host, (), shocks_bp, col0, n, base, floor, bad)
+
+
+def shock_columns_dev(ctx: Context, S: int, ld: int, shocks_ptr: int, col0: int, n: int, out_ptr: int, base_ptr: int = 0,
+                      floor=None, bad_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_shock_columns_dev): device pointers of ``shocks_bp`` [S, ld], ``base`` [n] (0: none), ``out``
+    [S, n] and ``bad`` [S] int32 (0: not wanted); ``floor`` None: no floor."""
+    _check(load().adr_shock_columns_dev(ctx._h, int(S), int(ld), _dev(shocks_ptr), int(col0), int(n), _dev(base_ptr),
+                                        int(floor is not None), float(floor or 0.0), _dev(out_ptr), _dev(bad_ptr),
+                                        _vp(stream or None)), "adr_shock_columns_dev")
+
+
+def scenario_rows_merge_host(tile, rows, s0: int, target, add=None):
+    """``rows[target[b], s0 + s] = tile[b, s]``, or ``+=`` where ``add[b]`` is not 0, IN PLACE on ``rows [B_tot, S_tot]``
+    (float64, C-contiguous) (adr_scenario_rows_merge_host); a target outside the rows skips its row, a repeated one is
+    refused.  Returns ``rows``."""
+    tile = _f64(np.atleast_2d(tile))
+    if not (isinstance(rows, np.ndarray) and rows.dtype == np.float64 and rows.ndim == 2 and rows.flags.c_contiguous):
+        raise LibError("rows must be a C-contiguous float64 array [B_tot, S_tot]: it is written in place")
+    target = np.ascontiguousarray(target, dtype=np.int64).reshape(-1)
+    add = None if add is None else np.ascontiguousarray(add, dtype=np.int32).reshape(-1)
+    if tile.ndim != 2 or target.size != tile.shape[0] or (add is not None and add.size != tile.shape[0]):
+        raise LibError(f"target and add need one entry per row of the tile ({tile.shape[0] if tile.ndim == 2 else '?'})")
+    _check(load().adr_scenario_rows_merge_host(tile.shape[0], tile.shape[1], _ptr(tile), rows.shape[0], rows.shape[1], int(s0),
+                                               _ptr(rows), _ptr(target, _i64p), _ptr(add, _i32p)), "adr_scenario_rows_merge_host")
+    return rows
+
+
+def scenario_rows_merge_dev(ctx: Context, B: int, S_tile: int, tile_ptr: int, B_tot: int, S_tot: int, s0: int, rows_ptr: int,
+                            target_ptr: int, add_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_scenario_rows_merge_dev): device pointers of ``tile`` [B, S_tile], ``rows`` [B_tot, S_tot],
+    ``target`` [B] int64 (distinct) and ``add`` [B] int32 (0: copy every row)."""
+    _check(load().adr_scenario_rows_merge_dev(ctx._h, int(B), int(S_tile), _dev(tile_ptr), int(B_tot), int(S_tot), int(s0),
+                                              _dev(rows_ptr), _dev(target_ptr), _dev(add_ptr), _vp(stream or None)),
+           "adr_scenario_rows_merge_dev")
 
 
 def set_default_context(ctx: Context, device: int | None = None) -> None:

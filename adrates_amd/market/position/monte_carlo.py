@@ -36,6 +36,9 @@ with the curve builder's bits) and priced per desk by the sub-book launch, a til
     >>> curves = ShockedCurves(model, "GBP_OIS_SONIA")
     >>> risk = monte_carlo_revalue_var_es(curves, trades, desk_keys, L, 262_144, level=0.99, seed=7)
     >>> gap = monte_carlo_explain_var_es(engine, curves, curve, trades, desk_keys, L, 262_144, seed=7)["gap_var"]
+
+Credit and inflation desks, and all three product lines in one matrix of the firm's desks, are revalued under joint shock
+rows by `monte_carlo_firm.FirmBook` and `monte_carlo_firm.monte_carlo_revalue_firm_var_es`.
 """
 from __future__ import annotations
 
@@ -359,15 +362,21 @@ def revalue_scenario_bytes(curves: ShockedCurves, n_trades: int, n_sub_books: in
 
 def _scenario_tile(curves, n, B, S, max_bytes):
     """Scenarios per tile: the ``[B, S + 1]`` rows and the tile's scratch stay under ``max_bytes``."""
-    per, rows = revalue_scenario_bytes(curves, n, B), 8 * B * (S + 1)
+    return _tile_of(revalue_scenario_bytes(curves, n, B), B, S, max_bytes)
+
+
+def _tile_of(per, B, S, max_bytes):
+    """The same from the bytes ``per`` scenario."""
+    rows = 8 * B * (S + 1)
     if int(max_bytes) - rows < per:
         raise LibError(f"the [{B}, {S} + 1] P&L rows ({rows} bytes) and one scenario's scratch ({per} bytes) do not fit max_bytes = "
                        f"{int(max_bytes)}: raise it, or revalue fewer scenarios or desks at a time")
     return int(min(S, SCENARIO_LAUNCH_MAX, (int(max_bytes) - rows) // per))
 
 
-def _raise_bad(count, first):
-    raise LibError(f"{count} scenario(s) give a discount factor that is not finite or not positive, the first at index {first}: "
+def _raise_bad(count, first, also=""):
+    """``also``: what else the flags of the caller stand for, beside a bad discount factor."""
+    raise LibError(f"{count} scenario(s) give a discount factor that is not finite or not positive{also}, the first at index {first}: "
                    "the shocks are too large for the curve")
 
 
@@ -409,11 +418,11 @@ def _revalue_rows_dev(curves, sb, dev_trades, shocks_ptr, S, ld, tile, rows, bad
     return times, base, sub_plan, zero, dfs, work_b, part, work_s
 
 
-def _check_bad_dev(bad):
+def _check_bad_dev(bad, also=""):
     """After the stream has drained: the `LibError` of the bad flags, counted on the device."""
     count = int(bad.count_nonzero())
     if count:
-        _raise_bad(count, int(bad.nonzero()[0]))
+        _raise_bad(count, int(bad.nonzero()[0]), also)
 
 
 def _torch_buffers(ctx):

@@ -1121,6 +1121,50 @@ int adr_scenario_rows_place_dev(adr_ctx* ctx, int64_t B, int S_tile, const doubl
                                 void* stream);
 
 /*
+ * Columns of the joint shock rows as the credit and inflation scenario kernels read them, and the three product lines'
+ * sub-book rows in one matrix: what full revaluation of a firm needs between adr_shock_normal_dev, the sub-book launches
+ * and the tail entries, on the device.
+ *
+ * adr_shock_columns*: shocks_bp[S][ld] in basis points, one joint row per scenario (quotes, then spread buckets, then
+ * breakevens); columns col0 .. col0 + n of every row become the dense out[S][n]:
+ *
+ *   out[s][j] = base[j] + shocks_bp[s][col0 + j] * 1e-4     (base NULL: the product itself, so -0.0 stays -0.0)
+ *
+ * - one rounded product, then one rounded sum, never fused: the bits of NumPy's b0 + x * 1e-4 (`shocked_breakevens`) and
+ * of x * 1e-4 (`shocked_spreads`), on the device and on the host.  base NULL gives dz[S][G] in decimals for
+ * adr_credit_scenario_subbook_pv_dev, base = the curve's breakeven rates gives b[S][P_i] for
+ * adr_yoy_scenario_subbook_pv_dev.  bad[s] (NULL: not wanted) is set to 1 where any out[s][j] is not finite or, with
+ * floor_on != 0, is <= floor (breakevens: floor = -1.0, where 1 + b <= 0 has no inflation factor), and is LEFT AS IT IS
+ * otherwise: the entry chains behind adr_curve_dfs_shocked_dev on one array of flags.  The row is written all the same.
+ * No atomics: every lane that finds a bad entry stores the constant 1.
+ *
+ * _dev: device arrays, one kernel on `stream` (NULL: the ctx's own), no allocation, no synchronisation, 64-bit indices,
+ * scalar checks only.  adr_shock_columns: host arrays, blocks (one allocation); bad goes in and comes back.  _host: the
+ * CPU twin, the same bits.  ADR_ERR_INVALID: S < 1, n < 1, col0 < 0, ld < col0 + n, NULL shocks_bp or out.
+ *
+ * adr_scenario_rows_merge*: tile[B][S_tile] into rows[B_tot][S_tot] through a row map,
+ *
+ *   rows[target[b]][s0 + s] = tile[b][s]                            where add == NULL or add[b] == 0
+ *   rows[target[b]][s0 + s] = rows[target[b]][s0 + s] + tile[b][s]  otherwise
+ *
+ * for b < B and s < S_tile; a target outside 0 .. B_tot - 1 skips its row; nothing else of rows is touched.  The targets
+ * of one call must be distinct: the caller's duty for _dev, refused by _host (ADR_ERR_INVALID naming the row).  Calls on
+ * one stream are ordered, so with one call per product line a desk's row is its first line's row with the later lines'
+ * rows added in line order.  _dev: one kernel on `stream`, no allocation, no synchronisation, no atomics.
+ * ADR_ERR_INVALID: B < 1, S_tile < 1, B_tot < 1, S_tot < 1, s0 < 0, s0 + S_tile > S_tot, NULL tile, rows or target.
+ */
+int adr_shock_columns(adr_ctx* ctx, int S, int ld, const double* shocks_bp, int col0, int n, const double* base, int floor_on, double floor,
+                      double* out, int32_t* bad);
+int adr_shock_columns_dev(adr_ctx* ctx, int S, int ld, const double* shocks_bp_dev, int col0, int n, const double* base_dev, int floor_on,
+                          double floor, double* out_dev, int32_t* bad_dev, void* stream);
+int adr_shock_columns_host(int S, int ld, const double* shocks_bp, int col0, int n, const double* base, int floor_on, double floor,
+                           double* out, int32_t* bad);
+int adr_scenario_rows_merge_dev(adr_ctx* ctx, int64_t B, int S_tile, const double* tile_dev, int64_t B_tot, int S_tot, int s0,
+                                double* rows_dev, const int64_t* target_dev, const int32_t* add_dev, void* stream);
+int adr_scenario_rows_merge_host(int64_t B, int S_tile, const double* tile, int64_t B_tot, int S_tot, int s0, double* rows,
+                                 const int64_t* target, const int32_t* add);
+
+/*
  * Credit sub-book Greeks: per sub-book the PV, the curve delta and gamma AT THE TRADES' SPREADS, CS01 and spread gamma
  * per credit bucket and the rate x spread cross gamma, from one launch chain.  The spread side is adr_credit_scenario_pv's:
  * z[n] (z-spread of a bond, discount margin of an FRN), bucket[n] in -1 .. G - 1 (-1: no bucket), 0 <= G <=
