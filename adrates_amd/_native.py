@@ -1957,8 +1957,8 @@ def curve_dfs_shocked_dev(ctx: Context, plan: CurvePlan, base_ptr: int, S: int, 
 
 
 def scenario_rows_place_dev(ctx: Context, B: int, S_tile: int, tile_ptr: int, S_tot: int, s0: int, rows_ptr: int, stream=0):
-    """``rows[b, s0 + s] = tile[b, s]`` on the device (adr_scenario_rows_place_dev): device pointers of ``tile`` [B, S_tile]
-    and ``rows`` [B, S_tot]."""
+    """``rows[b, s0 + s] = tile[b, s]`` on the device (adr_scenario_rows_place_dev, csrc/shock_columns.hip: the merge kernel
+    without a row map): device pointers of ``tile`` [B, S_tile] and ``rows`` [B, S_tot]."""
     _check(load().adr_scenario_rows_place_dev(ctx._h, int(B), int(S_tile), _dev(tile_ptr), int(S_tot), int(s0), _dev(rows_ptr),
                                               _vp(stream or None)), "adr_scenario_rows_place_dev")
 

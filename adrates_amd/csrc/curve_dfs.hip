@@ -114,13 +114,6 @@ __global__ __launch_bounds__(kWave * kWaves) void curve_dfs_kernel(Args a) {
     if (live && a.bad) a.bad[s] = bad ? 1 : 0;
 }
 
-// rows[b][s0 + s] = tile[b][s]; blockIdx.y strides over the rows.
-__global__ __launch_bounds__(256) void rows_place_kernel(int64_t B, int S_tile, const double* tile, int64_t S_tot, int64_t s0, double* rows) {
-    const int64_t s = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (s >= S_tile) return;
-    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) rows[b * S_tot + s0 + s] = tile[b * S_tile + s];
-}
-
 // -------------------------------------------------------------------------------------------------------------- host
 int check(const std::string& w, int P, int S, int ld, const void* base, const void* shocks, const void* dfs) {
     if (S < 1) return adr_set_error(ADR_ERR_INVALID, w + ": S >= 1 is needed");
@@ -243,26 +236,6 @@ int adr_curve_dfs_shocked_host(int K, int P, const double* acc, const int32_t* p
             if (bad) bad[s] = any ? 1 : 0;
         }
     });
-    return ADR_OK;
-}
-
-int adr_scenario_rows_place_dev(adr_ctx* ctx, int64_t B, int S_tile, const double* tile_dev, int S_tot, int s0, double* rows_dev,
-                                void* stream) {
-    const std::string w = "adr_scenario_rows_place_dev";
-    if (!ctx) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx");
-    if (B < 1 || S_tile < 1 || S_tot < 1 || s0 < 0) return adr_set_error(ADR_ERR_INVALID, w + ": B >= 1, S_tile >= 1, S_tot >= 1 and s0 >= 0 are needed");
-    if (static_cast<int64_t>(s0) + S_tile > S_tot)
-        return adr_set_error(ADR_ERR_INVALID, w + ": columns " + std::to_string(s0) + " .. " + std::to_string(static_cast<int64_t>(s0) + S_tile) +
-                                                  " do not fit rows of " + std::to_string(S_tot));
-    if (!tile_dev || !rows_dev) return adr_set_error(ADR_ERR_INVALID, w + ": tile / rows is NULL");
-    hipStream_t st = nullptr;
-    const int rc = adr::call::target_stream(w, ctx, static_cast<hipStream_t>(stream), &st);
-    if (rc != ADR_OK) return rc;
-    const dim3 grid(static_cast<unsigned>((S_tile + 255) / 256), static_cast<unsigned>(std::min<int64_t>(B, 65535)));
-    hipLaunchKernelGGL(CD::rows_place_kernel, grid, dim3(256), 0, st, B, S_tile, tile_dev, static_cast<int64_t>(S_tot),
-                       static_cast<int64_t>(s0), rows_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
 }
 

@@ -1,6 +1,6 @@
 // The two small steps between the Monte Carlo shock rows and the credit and inflation scenario kernels, and between their
-// sub-book rows and one [B][S] matrix of the firm (adr_shock_columns*, adr_scenario_rows_merge*; the contract:
-// include/adrates.h).
+// sub-book rows and one [B][S] matrix of the firm (adr_shock_columns*, adr_scenario_rows_merge*,
+// adr_scenario_rows_place_dev; the contract: include/adrates.h).
 //
 // adr_shock_columns: adr_shock_normal_dev writes one joint row per scenario, shocks[S][ld] in basis points; the credit
 // kernel reads a dense dz[S][G] in decimals, the YoY kernel a dense b[S][P_i] of breakeven rates:
@@ -10,8 +10,9 @@
 // doubles from rows that lie 8 ld bytes apart.  bad[s] gets the constant 1 from every lane that finds a bad entry, a plain
 // vector store of the same value to the same word, and is not touched otherwise.
 //
-// adr_scenario_rows_merge: rows[target[b]][s0 + s] = tile[b][s], or += where add[b] != 0: adr_scenario_rows_place_dev
-// with a row map, so the rates, credit and inflation launches of one tile land in the desks' rows one after another.
+// adr_scenario_rows_merge: rows[target[b]][s0 + s] = tile[b][s], or += where add[b] != 0, so the rates, credit and
+// inflation launches of one tile land in the desks' rows one after another.  adr_scenario_rows_place_dev is the same
+// kernel without a row map (target null: t = b) and without add.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -65,13 +66,13 @@ __global__ __launch_bounds__(kBlock) void shock_columns_kernel(Args a) {
     }
 }
 
-// blockIdx.y strides over the tile's rows
+// blockIdx.y strides over the tile's rows; target null: the identity map
 __global__ __launch_bounds__(kBlock) void rows_merge_kernel(int64_t B, int S_tile, const double* tile, int64_t B_tot, int64_t S_tot,
                                                             int64_t s0, double* rows, const int64_t* target, const int32_t* add) {
     const int64_t s = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (s >= S_tile) return;
     for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
-        const int64_t t = target[b];
+        const int64_t t = target ? target[b] : b;
         if (t < 0 || t >= B_tot) continue;
         double* at = rows + t * S_tot + s0 + s;
         const double v = tile[b * S_tile + s];
@@ -97,14 +98,32 @@ int enqueue_columns(const std::string& w, const Args& a, hipStream_t stream) {
     return ADR_OK;
 }
 
-int check_merge(const std::string& w, int64_t B, int S_tile, int64_t B_tot, int S_tot, int s0, const void* tile, const void* rows,
-                const void* target) {
+// mapped: the entry takes B_tot and a row map; the place entry has neither (B_tot = B, target null)
+int check_merge(const std::string& w, bool mapped, int64_t B, int S_tile, int64_t B_tot, int S_tot, int s0, const void* tile,
+                const void* rows, const void* target) {
     if (B < 1 || S_tile < 1 || B_tot < 1 || S_tot < 1 || s0 < 0)
-        return adr_set_error(ADR_ERR_INVALID, w + ": B >= 1, S_tile >= 1, B_tot >= 1, S_tot >= 1 and s0 >= 0 are needed");
+        return adr_set_error(ADR_ERR_INVALID, w + ": B >= 1, S_tile >= 1, " + (mapped ? "B_tot >= 1, " : "") + "S_tot >= 1 and s0 >= 0 are needed");
     if (static_cast<int64_t>(s0) + S_tile > S_tot)
         return adr_set_error(ADR_ERR_INVALID, w + ": columns " + std::to_string(s0) + " .. " + std::to_string(static_cast<int64_t>(s0) + S_tile) +
                                                   " do not fit rows of " + std::to_string(S_tot));
-    if (!tile || !rows || !target) return adr_set_error(ADR_ERR_INVALID, w + ": tile / rows / target is NULL");
+    if (!tile || !rows || (mapped && !target)) return adr_set_error(ADR_ERR_INVALID, w + ": tile / rows" + (mapped ? " / target" : "") + " is NULL");
+    return ADR_OK;
+}
+
+// The checks and the launch of both device entries.
+int enqueue_merge(const std::string& w, bool mapped, adr_ctx* ctx, int64_t B, int S_tile, const double* tile, int64_t B_tot, int S_tot,
+                  int s0, double* rows, const int64_t* target, const int32_t* add, void* stream) {
+    if (!ctx) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx");
+    int rc = check_merge(w, mapped, B, S_tile, B_tot, S_tot, s0, tile, rows, target);
+    if (rc != ADR_OK) return rc;
+    hipStream_t st = nullptr;
+    rc = adr::call::target_stream(w, ctx, static_cast<hipStream_t>(stream), &st);
+    if (rc != ADR_OK) return rc;
+    const dim3 grid(static_cast<unsigned>((S_tile + kBlock - 1) / kBlock), static_cast<unsigned>(std::min<int64_t>(B, 65535)));
+    hipLaunchKernelGGL(rows_merge_kernel, grid, dim3(kBlock), 0, st, B, S_tile, tile, B_tot, static_cast<int64_t>(S_tot),
+                       static_cast<int64_t>(s0), rows, target, add);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
 }
 
@@ -174,25 +193,18 @@ int adr_shock_columns_host(int S, int ld, const double* shocks_bp, int col0, int
 
 int adr_scenario_rows_merge_dev(adr_ctx* ctx, int64_t B, int S_tile, const double* tile_dev, int64_t B_tot, int S_tot, int s0,
                                 double* rows_dev, const int64_t* target_dev, const int32_t* add_dev, void* stream) {
-    const std::string w = "adr_scenario_rows_merge_dev";
-    if (!ctx) return adr_set_error(ADR_ERR_INVALID, w + ": null ctx");
-    int rc = SQ::check_merge(w, B, S_tile, B_tot, S_tot, s0, tile_dev, rows_dev, target_dev);
-    if (rc != ADR_OK) return rc;
-    hipStream_t st = nullptr;
-    rc = adr::call::target_stream(w, ctx, static_cast<hipStream_t>(stream), &st);
-    if (rc != ADR_OK) return rc;
-    const dim3 grid(static_cast<unsigned>((S_tile + SQ::kBlock - 1) / SQ::kBlock), static_cast<unsigned>(std::min<int64_t>(B, 65535)));
-    hipLaunchKernelGGL(SQ::rows_merge_kernel, grid, dim3(SQ::kBlock), 0, st, B, S_tile, tile_dev, B_tot, static_cast<int64_t>(S_tot),
-                       static_cast<int64_t>(s0), rows_dev, target_dev, add_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return ADR_OK;
+    return SQ::enqueue_merge("adr_scenario_rows_merge_dev", true, ctx, B, S_tile, tile_dev, B_tot, S_tot, s0, rows_dev, target_dev, add_dev, stream);
+}
+
+int adr_scenario_rows_place_dev(adr_ctx* ctx, int64_t B, int S_tile, const double* tile_dev, int S_tot, int s0, double* rows_dev,
+                                void* stream) {
+    return SQ::enqueue_merge("adr_scenario_rows_place_dev", false, ctx, B, S_tile, tile_dev, B, S_tot, s0, rows_dev, nullptr, nullptr, stream);
 }
 
 int adr_scenario_rows_merge_host(int64_t B, int S_tile, const double* tile, int64_t B_tot, int S_tot, int s0, double* rows,
                                  const int64_t* target, const int32_t* add) {
     const std::string w = "adr_scenario_rows_merge_host";
-    const int rc = SQ::check_merge(w, B, S_tile, B_tot, S_tot, s0, tile, rows, target);
+    const int rc = SQ::check_merge(w, true, B, S_tile, B_tot, S_tot, s0, tile, rows, target);
     if (rc != ADR_OK) return rc;
     std::vector<int64_t> seen;
     for (int64_t b = 0; b < B; ++b)

@@ -38,7 +38,9 @@ with the curve builder's bits) and priced per desk by the sub-book launch, a til
     >>> gap = monte_carlo_explain_var_es(engine, curves, curve, trades, desk_keys, L, 262_144, seed=7)["gap_var"]
 
 Credit and inflation desks, and all three product lines in one matrix of the firm's desks, are revalued under joint shock
-rows by `monte_carlo_firm.FirmBook` and `monte_carlo_firm.monte_carlo_revalue_firm_var_es`.
+rows by `monte_carlo_firm.FirmBook` and `monte_carlo_firm.monte_carlo_revalue_firm_var_es`.  That module holds the one
+revaluation chain: `revalue_shocks_sub_books` and `monte_carlo_revalue_var_es` here check their own arguments, wrap the
+trades in a `FirmBook` with a rates line alone and run it.
 """
 from __future__ import annotations
 
@@ -160,11 +162,8 @@ def monte_carlo_var_es(delta, gamma, factor_bp, n_scenarios: int, level: float =
             out[0, b0:b0 + nb], out[1, b0:b0 + nb] = _native.scenario_tail_select_host(pnl, k)
         return {"var": out[0].copy(), "es": out[1].copy()}
 
-    import torch
     ctx = ctx or _native.default_context()
-    dev = torch.device("cuda", ctx.device)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    torch, dev, up, new = _torch_buffers(ctx)
     d_rows, d_factor, shocks, pnl, var_es = up(rows), up(factor), new(S, P), new(tile, S), new(2, B)
     work = torch.empty(max(_native.scenario_tail_select_work(nb, S, k) for _, nb in tiles), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize(dev)
@@ -246,11 +245,8 @@ def monte_carlo_allocate_tail(delta, gamma, factor_bp, n_scenarios: int, level: 
                 _native.ladder_pnl_host(rows[b0:b0 + nb], gathered)["pnl"])
         return {"var": float(var[0]), "es": float(es[0]), "comp_var": comp[0].copy(), "comp_es": comp[1].copy(), "scenarios": order[0].copy()}
 
-    import torch
     ctx = ctx or _native.default_context()
-    dev = torch.device("cuda", ctx.device)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    torch, dev, up, new = _torch_buffers(ctx)
     d_rows, d_factor, firm, shocks, tot = up(rows), up(factor), new(width), new(S, P), new(S)
     gathered, pnl, out = new(k, P), new(tile, k), new(2, B + 1)         # out: [comp_var | var], [comp_es | es]
     order = torch.empty(k, dtype=torch.int64, device=dev)
@@ -357,16 +353,19 @@ def revalue_scenario_bytes(curves: ShockedCurves, n_trades: int, n_sub_books: in
     """Bytes of scratch ONE scenario of a revaluation tile takes: its row of ``dfs`` (K doubles), the bootstrap's scratch
     (K + P), the sub-book launch's (adr_scenario_subbook_work: a double per chunk of 64 trades and desk) and its column of
     the ``[B, tile]`` rows."""
-    return 8 * (2 * curves.n_knots + curves.n_pillars + _native.scenario_subbook_work(n_trades, n_sub_books, 1) + n_sub_books)
+    return _scenario_bytes(curves, [(n_trades, n_sub_books)], n_sub_books)
 
 
-def _scenario_tile(curves, n, B, S, max_bytes):
-    """Scenarios per tile: the ``[B, S + 1]`` rows and the tile's scratch stay under ``max_bytes``."""
-    return _tile_of(revalue_scenario_bytes(curves, n, B), B, S, max_bytes)
+def _scenario_bytes(curves, lines, n_desks, n_columns=0):
+    """The same for any product lines ``(trades, sub-books)`` on one curve whose rows go into ``n_desks`` rows, with
+    ``n_columns`` doubles of dense shock columns beside the ``dfs`` (`monte_carlo_firm.firm_scenario_bytes`)."""
+    work = sum(_native.scenario_subbook_work(n, B, 1) for n, B in lines)
+    return 8 * (2 * curves.n_knots + curves.n_pillars + n_columns + work + n_desks)
 
 
 def _tile_of(per, B, S, max_bytes):
-    """The same from the bytes ``per`` scenario."""
+    """Scenarios per tile from the bytes ``per`` scenario: the ``[B, S + 1]`` rows and the tile's scratch stay under
+    ``max_bytes``."""
     rows = 8 * B * (S + 1)
     if int(max_bytes) - rows < per:
         raise LibError(f"the [{B}, {S} + 1] P&L rows ({rows} bytes) and one scenario's scratch ({per} bytes) do not fit max_bytes = "
@@ -378,44 +377,6 @@ def _raise_bad(count, first, also=""):
     """``also``: what else the flags of the caller stand for, beside a bad discount factor."""
     raise LibError(f"{count} scenario(s) give a discount factor that is not finite or not positive{also}, the first at index {first}: "
                    "the shocks are too large for the curve")
-
-
-def _revalue_rows_host(curves, sb, shocks, tile):
-    """``[B, S + 1]`` on the CPU twins: the desks' PVs under the shock rows, tile by tile, and under the zero shock last."""
-    S, B = shocks.shape[0], len(sb.labels)
-    rows = np.empty((B, S + 1))
-    zero = np.zeros((1, shocks.shape[1]))
-    count, first = 0, -1
-    for s0, x in [(s0, shocks[s0:s0 + tile]) for s0 in range(0, S, tile)] + [(S, zero)]:
-        dfs, bad = curves.dfs(x, host=True)
-        if bad.any() and count == 0:
-            first = s0 + int(np.argmax(bad != 0))
-        count += int(np.count_nonzero(bad))
-        if count == 0:                  # (once a scenario is bad only the flags of the rest are wanted)
-            rows[:, s0:s0 + x.shape[0]] = _native.scenario_subbook_pv_host(curves.method, curves.base.times, dfs, sb.batch,
-                                                                           sb.sub_off)["sub_pv"]
-    if count:
-        _raise_bad(count, first)
-    return rows
-
-
-def _revalue_rows_dev(curves, sb, dev_trades, shocks_ptr, S, ld, tile, rows, bad, new, up):
-    """Enqueue on the context's stream: ``rows [B, S + 1]`` (a torch tensor) of the desks' PVs under the device shock rows
-    ``[S, ld]`` at ``shocks_ptr``, tile by tile, and under the zero shock as column ``S``; ``bad [S + 1]`` int32 beside
-    them.  Returns the buffers the stream still reads."""
-    ctx, plan, K, B, n = curves.context(), curves.plan(), curves.n_knots, len(sb.labels), sb.batch.n_trades
-    times, base, sub_plan = up(curves.base.times), up(curves.rates), up(_native.scenario_subbook_plan(n, sb.sub_off))
-    zero = up(np.zeros(curves.n_pillars))
-    dfs, work_b, part = new(tile, K), new(_native.curve_dfs_shocked_work(plan, tile)), new(B, tile)
-    work_s = new(_native.scenario_subbook_work(n, B, tile))
-    for s0, nt, x_ptr, x_ld in [(s0, min(tile, S - s0), shocks_ptr + 8 * ld * s0, ld) for s0 in range(0, S, tile)] + \
-            [(S, 1, zero.data_ptr(), curves.n_pillars)]:
-        _native.curve_dfs_shocked_dev(ctx, plan, base.data_ptr(), nt, x_ld, x_ptr, dfs.data_ptr(), work_b.data_ptr(),
-                                      bad_ptr=bad.data_ptr() + 4 * s0)
-        _native.scenario_subbook_pv_dev(ctx, curves.method, K, times.data_ptr(), nt, dfs.data_ptr(), dev_trades, B,
-                                        sub_plan.data_ptr(), part.data_ptr(), work_s.data_ptr())
-        _native.scenario_rows_place_dev(ctx, B, nt, part.data_ptr(), S + 1, s0, rows.data_ptr())
-    return times, base, sub_plan, zero, dfs, work_b, part, work_s
 
 
 def _check_bad_dev(bad, also=""):
@@ -441,33 +402,18 @@ def revalue_shocks_sub_books(curves: ShockedCurves, trades, keys, shocks_bp, hos
     scenarios are cut into tiles so that the tile's ``dfs``, the two scratch buffers, its ``[B, tile]`` rows and the ``[B, S
     + 1]`` result stay under ``max_bytes`` (`revalue_scenario_bytes` per scenario; a `LibError` when not even one fits); per
     tile the bootstrap (adr_curve_dfs_shocked_dev), the sub-book launch (adr_scenario_subbook_pv_dev) and the copy into the
-    rows (adr_scenario_rows_place_dev) run on one stream.  The base PV is one more launch, on a zero shock row, whose
+    rows (adr_scenario_rows_merge_dev) run on one stream: the chain of `monte_carlo_firm.revalue_shocks_firm` on a `FirmBook`
+    with a rates line alone, here with rows of any width.  The base PV is one more launch, on a zero shock row, whose
     ``dfs`` are the base curve's bits: a scenario's result does not depend on the launch it is priced in, so a zero shock
     row gives exactly 0.0 in every desk, the tiling changes no bit, and the P&L is `revalue_on_curves_sub_books`' on the
     same ``dfs`` with the base row appended, column minus last column.  What does not depend on the curve (an FRN coupon
     fixed and paid at the value time) cancels and is not added.  A scenario with a discount factor that is not finite or
     not positive is a `LibError` naming the count and the first index.  ``host=True``: the CPU twins; no GPU needed."""
+    from .monte_carlo_firm import FirmBook, _revalue_pnl
     shocks = np.ascontiguousarray(shocks_bp, dtype=np.float64)
     if shocks.ndim != 2 or shocks.shape[0] < 1 or shocks.shape[1] < curves.n_pillars:
         raise LibError(f"shocks_bp must have shape [S >= 1, {curves.n_pillars} or more], not {list(shocks.shape)}")
-    sb = curves._book(trades, keys)
-    S, B = shocks.shape[0], len(sb.labels)
-    tile = _scenario_tile(curves, sb.batch.n_trades, B, S, max_bytes)
-    if host:
-        rows = _revalue_rows_host(curves, sb, shocks, tile)
-    else:
-        ctx = curves.context()
-        torch, dev, up, new = _torch_buffers(ctx)
-        d_shocks, d_rows = up(shocks), new(B, S + 1)
-        bad = torch.zeros(S + 1, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        with _native.DeviceTrades(ctx, sb.batch) as dev_trades:
-            held = _revalue_rows_dev(curves, sb, dev_trades, d_shocks.data_ptr(), S, shocks.shape[1], tile, d_rows, bad, new, up)
-            ctx.sync()
-        del held
-        _check_bad_dev(bad)
-        rows = d_rows.cpu().numpy()
-    return {"labels": sb.labels, "pnl": rows[:, :-1] - rows[:, -1:]}
+    return _revalue_pnl(FirmBook(curves, rates=(trades, keys)), shocks, host, max_bytes, also="")
 
 
 def monte_carlo_revalue_var_es(curves: ShockedCurves, trades, keys, factor_bp, n_scenarios: int, level: float = 0.99, seed: int = 0,
@@ -484,49 +430,12 @@ def monte_carlo_revalue_var_es(curves: ShockedCurves, trades, keys, factor_bp, n
     ``[B, S + 1]`` and one scenario's scratch exceed ``max_bytes`` a `LibError` says so.  Bit for bit the result is
     `tail_measures_select` (and `allocate_tail_select`) of `revalue_shocks_sub_books`' rows on `monte_carlo_shocks`,
     whatever the tiling.  ``host=True``: the CPU twins on the host's shocks; no GPU needed."""
+    from .monte_carlo_firm import FirmBook, _revalue_var_es
     factor = np.ascontiguousarray(factor_bp, dtype=np.float64)
     if factor.ndim != 2 or factor.shape[0] != curves.n_pillars:
         raise LibError(f"factor_bp [P, F] needs one row per par quote ({curves.n_pillars}), not {list(factor.shape)}")
-    (P, F), S = factor.shape, int(n_scenarios)
-    if S < 1:
-        raise LibError("at least one scenario is needed")
-    k = tail_count(level, S)
-    _check_tail_count(k, level, S, _native.SCENARIO_ALLOC_MAX if allocate else None)
-    sb = curves._book(trades, keys)
-    B = len(sb.labels)
-    tile = _scenario_tile(curves, sb.batch.n_trades, B, S, max_bytes)
-    if host:
-        rows = _revalue_rows_host(curves, sb, _native.shock_normal_host(factor, S, seed, antithetic, 0), tile)
-        var, es = _native.scenario_tail_select_host(rows, k, S)
-        out = {"labels": sb.labels, "var": var, "es": es}
-        if allocate:
-            firm = _native.scenario_tail_alloc_select_host(rows, k, S)
-            out.update(firm_var=firm["var"], firm_es=firm["es"], comp_var=firm["comp_var"], comp_es=firm["comp_es"])
-        return out
-
-    ctx = curves.context()
-    torch, dev, up, new = _torch_buffers(ctx)
-    d_factor, shocks, rows, res = up(factor), new(S, P), new(B, S + 1), new(4, B + 1)    # res: var, es, [comp_var | firm], [comp_es | firm]
-    bad = torch.zeros(S + 1, dtype=torch.int32, device=dev)
-    n_work = max(_native.scenario_tail_select_work(B, S + 1, k), _native.scenario_tail_alloc_select_work(B, S + 1, k) if allocate else 0)
-    work = torch.empty(n_work, dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize(dev)
-    with _native.DeviceTrades(ctx, sb.batch) as dev_trades:
-        _native.shock_normal_dev(ctx, seed, 0, S, P, F, d_factor.data_ptr(), antithetic, shocks.data_ptr())
-        held = _revalue_rows_dev(curves, sb, dev_trades, shocks.data_ptr(), S, P, tile, rows, bad, new, up)
-        at = lambda r, c=0: res.data_ptr() + 8 * (r * (B + 1) + c)
-        _native.scenario_tail_select_dev(ctx, B, S + 1, rows.data_ptr(), k, at(0), at(1), work.data_ptr(), base_col=S)
-        if allocate:
-            _native.scenario_tail_alloc_select_dev(ctx, B, S + 1, rows.data_ptr(), k, at(2, B), at(3, B), at(2), at(3), work.data_ptr(),
-                                                   base_col=S)
-        ctx.sync()
-    del held
-    _check_bad_dev(bad)
-    got = res.cpu().numpy()
-    out = {"labels": sb.labels, "var": got[0, :B].copy(), "es": got[1, :B].copy()}
-    if allocate:
-        out.update(firm_var=float(got[2, B]), firm_es=float(got[3, B]), comp_var=got[2, :B].copy(), comp_es=got[3, :B].copy())
-    return out
+    return _revalue_var_es(FirmBook(curves, rates=(trades, keys)), factor, n_scenarios, level, seed, antithetic, host, max_bytes, allocate,
+                           also="")
 
 
 def monte_carlo_explain_var_es(engine, curves: ShockedCurves, ir_model, trades, keys, factor_bp, n_scenarios: int, level: float = 0.99,

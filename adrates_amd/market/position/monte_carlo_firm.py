@@ -13,6 +13,11 @@ on the device.
     >>> cols = firm.columns                                      # where each block of the [Q, Q] covariance goes
     >>> risk = monte_carlo_revalue_firm_var_es(firm, factor_from_covariance(cov_Q_bp2), 262_144, level=0.99, seed=7)
     >>> gap = monte_carlo_explain_firm_var_es(engine, firm, L, 262_144, seed=7)["gap_var"]      # against delta-gamma
+
+This is the library's one full-revaluation chain (`_firm_rows_host`, `_firm_rows_dev`, `_revalue_pnl`, `_revalue_var_es`).
+`monte_carlo.revalue_shocks_sub_books` and `monte_carlo.monte_carlo_revalue_var_es` run it on a `FirmBook` with a rates line
+alone; what they add is their own argument checks, shock rows wider than ``Q`` (the row stride goes in beside ``Q``) and a
+bad-scenario message without the clause on breakevens.
 """
 from __future__ import annotations
 
@@ -25,7 +30,8 @@ from ...utils.error import LibError
 from ...utils.global_types import CurveTypes, RequestTypes
 from ...utils.helpers import to_tenor
 from .inflation_engine import inflation_inputs
-from .monte_carlo import (ShockedCurves, _check_bad_dev, _check_tail_count, _raise_bad, _tile_of, _torch_buffers, monte_carlo_var_es)
+from .monte_carlo import (ShockedCurves, _check_bad_dev, _check_tail_count, _raise_bad, _scenario_bytes, _tile_of, _torch_buffers,
+                          monte_carlo_var_es)
 from .scenarios import (_first_appearance, compile_credit_book, split_sub_books, split_yoy_sub_books, tail_count)
 
 _ALSO_BAD = ", a breakeven rate at or below -100 % or a shock that is not finite"
@@ -137,9 +143,8 @@ def firm_scenario_bytes(firm: FirmBook) -> int:
     """Bytes of scratch ONE scenario of a firm's revaluation tile takes: `revalue_scenario_bytes`' row of ``dfs``, bootstrap
     scratch and column of the ``[B, tile]`` rows, the scenario's ``dz`` and ``b`` (``G + P_i`` doubles) and every line's
     sub-book scratch (adr_scenario_subbook_work)."""
-    c, cols = firm.curves, firm.columns
-    work = sum(_native.scenario_subbook_work(line.n, line.B, 1) for line in firm.lines)
-    return 8 * (2 * c.n_knots + c.n_pillars + len(cols["spread"]) + len(cols["breakeven"]) + work + firm.n_desks)
+    cols = firm.columns
+    return _scenario_bytes(firm.curves, [(line.n, line.B) for line in firm.lines], firm.n_desks, len(cols["spread"]) + len(cols["breakeven"]))
 
 
 def _tiles(S, tile):
@@ -147,13 +152,14 @@ def _tiles(S, tile):
     return [(s0, min(tile, S - s0)) for s0 in range(0, S, tile)] + [(S, 1)]
 
 
-def _firm_rows_host(firm, shocks, tile):
-    """``[B, S + 1]`` on the CPU twins: the desks' PVs under the joint shock rows, tile by tile, and under the zero row last."""
+def _firm_rows_host(firm, shocks, tile, also):
+    """``[B, S + 1]`` on the CPU twins: the desks' PVs under the joint shock rows ``[S, ld >= Q]``, tile by tile, and under
+    the zero row last.  ``also``: `_raise_bad`'s."""
     c, cols = firm.curves, firm.columns
-    S, Q = shocks.shape
+    S, ld = shocks.shape
     G, Pi = len(cols["spread"]), len(cols["breakeven"])
     rows = np.zeros((firm.n_desks, S + 1))
-    zero = np.zeros((1, Q))
+    zero = np.zeros((1, ld))
     count, first = 0, -1
     for s0, nt in _tiles(S, tile):
         x = zero if s0 == S else shocks[s0:s0 + nt]
@@ -179,19 +185,19 @@ def _firm_rows_host(firm, shocks, tile):
                                                            line.sub_off)
             _native.scenario_rows_merge_host(out["sub_pv"], rows, s0, line.target, line.add)
     if count:
-        _raise_bad(count, first, _ALSO_BAD)
+        _raise_bad(count, first, also)
     return rows
 
 
-def _firm_rows_dev(firm, stack, shocks_ptr, S, tile, rows, bad, new, up):
+def _firm_rows_dev(firm, stack, shocks_ptr, S, ld, tile, rows, bad, new, up):
     """Enqueue on the context's stream: ``rows [B, S + 1]`` (a torch tensor) of the desks' PVs under the device shock rows
-    ``[S, Q]`` at ``shocks_ptr``, tile by tile, and under the zero row as column ``S``; ``bad [S + 1]`` int32 beside them.
+    ``[S, ld >= Q]`` at ``shocks_ptr``, tile by tile, and under the zero row as column ``S``; ``bad [S + 1]`` int32 beside them.
     ``stack``: the `contextlib.ExitStack` that owns the uploaded batches.  Returns the buffers the stream still reads."""
     c, cols = firm.curves, firm.columns
     ctx, plan, K, P, B = c.context(), c.plan(), c.n_knots, c.n_pillars, firm.n_desks
-    G, Pi, Q = len(cols["spread"]), len(cols["breakeven"]), firm.n_columns
+    G, Pi = len(cols["spread"]), len(cols["breakeven"])
     ptr = lambda t: t.data_ptr() if t.numel() else 0
-    times, base, zero = up(c.base.times), up(c.rates), up(np.zeros(Q))
+    times, base, zero = up(c.base.times), up(c.rates), up(np.zeros(ld))
     dfs, work_b, part = new(tile, K), new(_native.curve_dfs_shocked_work(plan, tile)), new(B, tile)
     dz, b = new(tile, G), new(tile, Pi)
     held = [times, base, zero, dfs, work_b, part, dz, b]
@@ -224,13 +230,13 @@ def _firm_rows_dev(firm, stack, shocks_ptr, S, tile, rows, bad, new, up):
                 ctx, c.method, K, nt, line.im, Pi, nt, nt, line.n, sizes[0], sizes[1], line.B, p, part.data_ptr(), p["work"])
         launches.append((launch, line.B, ptrs["target"], ptrs["add"]))
     for s0, nt in _tiles(S, tile):
-        x_ptr = zero.data_ptr() if s0 == S else shocks_ptr + 8 * Q * s0
+        x_ptr = zero.data_ptr() if s0 == S else shocks_ptr + 8 * ld * s0
         flags = bad.data_ptr() + 4 * s0
-        _native.curve_dfs_shocked_dev(ctx, plan, base.data_ptr(), nt, Q, x_ptr, dfs.data_ptr(), work_b.data_ptr(), bad_ptr=flags)
+        _native.curve_dfs_shocked_dev(ctx, plan, base.data_ptr(), nt, ld, x_ptr, dfs.data_ptr(), work_b.data_ptr(), bad_ptr=flags)
         if G:
-            _native.shock_columns_dev(ctx, nt, Q, x_ptr, P, G, dz.data_ptr(), bad_ptr=flags)
+            _native.shock_columns_dev(ctx, nt, ld, x_ptr, P, G, dz.data_ptr(), bad_ptr=flags)
         if Pi:
-            _native.shock_columns_dev(ctx, nt, Q, x_ptr, P + G, Pi, b.data_ptr(), base_ptr=b0_ptr, floor=-1.0, bad_ptr=flags)
+            _native.shock_columns_dev(ctx, nt, ld, x_ptr, P + G, Pi, b.data_ptr(), base_ptr=b0_ptr, floor=-1.0, bad_ptr=flags)
         for launch, B_line, target, add in launches:
             launch(nt)
             _native.scenario_rows_merge_dev(ctx, B_line, nt, part.data_ptr(), B, S + 1, s0, rows.data_ptr(), target, add)
@@ -259,11 +265,16 @@ def revalue_shocks_firm(firm: FirmBook, shocks_bp, host: bool = False, max_bytes
     column.  What does not depend on the scenario (an FRN coupon fixed and paid at the value time) cancels and is not
     added.  A scenario with a bad discount factor, a breakeven at or below -100 % or a shock that is not finite is a
     `LibError` naming the count and the first index.  ``host=True``: the CPU twins end to end; no GPU needed."""
-    shocks = _shock_rows(firm, shocks_bp)
-    S, B = shocks.shape[0], firm.n_desks
+    return {**_revalue_pnl(firm, _shock_rows(firm, shocks_bp), host, max_bytes, _ALSO_BAD), "columns": firm.columns}
+
+
+def _revalue_pnl(firm, shocks, host, max_bytes, also):
+    """``{"labels", "pnl" [B, S]}`` under the checked shock rows ``shocks [S, ld >= Q]``: `revalue_shocks_firm`'s chain, and
+    `revalue_shocks_sub_books`' on a rates-only firm.  ``also``: `_raise_bad`'s."""
+    (S, ld), B = shocks.shape, firm.n_desks
     tile = _tile_of(firm_scenario_bytes(firm), B, S, max_bytes)
     if host:
-        rows = _firm_rows_host(firm, shocks, tile)
+        rows = _firm_rows_host(firm, shocks, tile, also)
     else:
         ctx = firm.curves.context()
         torch, dev, up, new = _torch_buffers(ctx)
@@ -272,12 +283,12 @@ def revalue_shocks_firm(firm: FirmBook, shocks_bp, host: bool = False, max_bytes
         bad = torch.zeros(S + 1, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
         with contextlib.ExitStack() as stack:
-            held = _firm_rows_dev(firm, stack, d_shocks.data_ptr(), S, tile, d_rows, bad, new, up)
+            held = _firm_rows_dev(firm, stack, d_shocks.data_ptr(), S, ld, tile, d_rows, bad, new, up)
             ctx.sync()
         del held
-        _check_bad_dev(bad, _ALSO_BAD)
+        _check_bad_dev(bad, also)
         rows = d_rows.cpu().numpy()
-    return {"labels": firm.labels, "pnl": rows[:, :-1] - rows[:, -1:], "columns": firm.columns}
+    return {"labels": firm.labels, "pnl": rows[:, :-1] - rows[:, -1:]}
 
 
 def monte_carlo_revalue_firm_var_es(firm: FirmBook, factor_bp, n_scenarios: int, level: float = 0.99, seed: int = 0,
@@ -296,7 +307,13 @@ def monte_carlo_revalue_firm_var_es(firm: FirmBook, factor_bp, n_scenarios: int,
     Q = firm.n_columns
     if factor.ndim != 2 or factor.shape[0] != Q:
         raise LibError(f"factor_bp [Q, F] needs one row per column of the firm's shock rows ({Q}), not {list(factor.shape)}")
-    F, S = factor.shape[1], int(n_scenarios)
+    return _revalue_var_es(firm, factor, n_scenarios, level, seed, antithetic, host, max_bytes, allocate, _ALSO_BAD)
+
+
+def _revalue_var_es(firm, factor, n_scenarios, level, seed, antithetic, host, max_bytes, allocate, also):
+    """`monte_carlo_revalue_firm_var_es`' chain under the checked ``factor [Q, F]``, and `monte_carlo_revalue_var_es`' on a
+    rates-only firm.  ``also``: `_raise_bad`'s."""
+    (Q, F), S = factor.shape, int(n_scenarios)
     if S < 1:
         raise LibError("at least one scenario is needed")
     k = tail_count(level, S)
@@ -304,7 +321,7 @@ def monte_carlo_revalue_firm_var_es(firm: FirmBook, factor_bp, n_scenarios: int,
     B = firm.n_desks
     tile = _tile_of(firm_scenario_bytes(firm), B, S, max_bytes)
     if host:
-        rows = _firm_rows_host(firm, _native.shock_normal_host(factor, S, seed, antithetic, 0), tile)
+        rows = _firm_rows_host(firm, _native.shock_normal_host(factor, S, seed, antithetic, 0), tile, also)
         var, es = _native.scenario_tail_select_host(rows, k, S)
         out = {"labels": firm.labels, "var": var, "es": es}
         if allocate:
@@ -322,7 +339,7 @@ def monte_carlo_revalue_firm_var_es(firm: FirmBook, factor_bp, n_scenarios: int,
     torch.cuda.synchronize(dev)
     with contextlib.ExitStack() as stack:
         _native.shock_normal_dev(ctx, seed, 0, S, Q, F, d_factor.data_ptr(), antithetic, shocks.data_ptr())
-        held = _firm_rows_dev(firm, stack, shocks.data_ptr(), S, tile, rows, bad, new, up)
+        held = _firm_rows_dev(firm, stack, shocks.data_ptr(), S, Q, tile, rows, bad, new, up)
         at = lambda r, c=0: res.data_ptr() + 8 * (r * (B + 1) + c)
         _native.scenario_tail_select_dev(ctx, B, S + 1, rows.data_ptr(), k, at(0), at(1), work.data_ptr(), base_col=S)
         if allocate:
@@ -330,7 +347,7 @@ def monte_carlo_revalue_firm_var_es(firm: FirmBook, factor_bp, n_scenarios: int,
                                                    base_col=S)
         ctx.sync()
     del held
-    _check_bad_dev(bad, _ALSO_BAD)
+    _check_bad_dev(bad, also)
     got = res.cpu().numpy()
     out = {"labels": firm.labels, "var": got[0, :B].copy(), "es": got[1, :B].copy()}
     if allocate:

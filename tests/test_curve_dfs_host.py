@@ -138,6 +138,14 @@ def test_zero_shock_row_is_exactly_zero(chain):
     assert np.array_equal(C.bits(pnl[:, 2]), C.bits(np.zeros(5))) and np.all(pnl[:, [0, 1, 3, 4]] != 0.0)
 
 
+def test_columns_beyond_the_quotes_are_not_read(chain):
+    """``shocks_bp [S, ld > P]``: three columns of NaN behind five of the chain's shock rows change no bit."""
+    curves, book, keys, x = chain["curves"], C.chain_book(), C.chain_keys(), chain["x"][:5]
+    want = revalue_shocks_sub_books(curves, book, keys, x, host=True)
+    got = revalue_shocks_sub_books(curves, book, keys, np.hstack([x, np.full((5, 3), np.nan)]), host=True)
+    assert got["labels"] == want["labels"] and np.all(want["pnl"] != 0.0) and np.array_equal(C.bits(got["pnl"]), C.bits(want["pnl"]))
+
+
 def test_var_es_and_allocation_are_the_tail_entries_of_the_rows(chain):
     curves, book, keys, pnl = chain["curves"], C.chain_book(), C.chain_keys(), chain["pnl"]["pnl"]
     per = revalue_scenario_bytes(curves, book.n_trades, 5)

@@ -79,7 +79,7 @@ def test_one_line_is_that_lines_own_call(chain, kind):
     got = revalue_shocks_firm(firm, x, host=True)
     (labels, rows), = FC.line_rows(curves, firm, x, kinds=(kind,))
     assert got["labels"] == labels and np.array_equal(FC.bits(got["pnl"]), FC.bits(rows[:, :-1] - rows[:, -1:]))
-    if kind == "rates":
+    if kind == "rates":             # `revalue_shocks_sub_books` wraps this very firm: the wrapper against what it wraps
         own = revalue_shocks_sub_books(curves, *FC.lines()["rates"], x, host=True)
         assert own["labels"] == labels and np.array_equal(FC.bits(got["pnl"]), FC.bits(own["pnl"]))
 

@@ -1,6 +1,6 @@
 """Discount factors of shocked curves and Monte Carlo VaR by full revaluation on the GPU (adr_curve_dfs_shocked*,
-adr_scenario_rows_place_dev, csrc/curve_dfs.hip; market/position/monte_carlo.py), on the tables of the CPU suite
-(tests/_curve_dfs_cases.py): the device's discount factors with the twin's bits on every grid and scenario count and with
+csrc/curve_dfs.hip; adr_scenario_rows_place_dev, csrc/shock_columns.hip; market/position/monte_carlo.py), on the tables of
+the CPU suite (tests/_curve_dfs_cases.py): the device's discount factors with the twin's bits on every grid and scenario count and with
 the curve builder's own, the cut of a set, the device-array entries in guarded buffers; the chain against
 `revalue_on_curves_sub_books` on the twin's rows, whatever the tiling, its tail figures against the tail entries, the device
 against the host chain, and the third-order gap to delta-gamma."""
@@ -199,6 +199,14 @@ def test_chain_does_not_depend_on_the_tiling(chain):
     x[2] = 0.0
     pnl = revalue_shocks_sub_books(curves, book, keys, x)["pnl"]
     assert np.array_equal(C.bits(pnl[:, 2]), C.bits(np.zeros(5))) and np.all(pnl[:, [0, 1, 3, 4]] != 0.0), "a zero shock row"
+
+
+def test_columns_beyond_the_quotes_are_not_read(chain):
+    """``shocks_bp [S, ld > P]``: three columns of NaN behind five of the chain's shock rows change no bit."""
+    curves, book, keys, x = chain["curves"], C.chain_book(), C.chain_keys(), chain["x"][:5]
+    want = revalue_shocks_sub_books(curves, book, keys, x)
+    got = revalue_shocks_sub_books(curves, book, keys, np.hstack([x, np.full((5, 3), np.nan)]))
+    assert got["labels"] == want["labels"] and np.all(want["pnl"] != 0.0) and np.array_equal(C.bits(got["pnl"]), C.bits(want["pnl"]))
 
 
 def test_var_es_and_allocation_are_the_tail_entries_of_the_rows(chain):

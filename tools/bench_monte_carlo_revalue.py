@@ -1,5 +1,5 @@
-"""Monte Carlo VaR by full revaluation benchmark (adr_curve_dfs_shocked_dev and adr_scenario_rows_place_dev,
-csrc/curve_dfs.hip; `monte_carlo_revalue_var_es`' chain): n synthetic off-grid OIS on the README GBP curve (K = 264 knots,
+"""Monte Carlo VaR by full revaluation benchmark (adr_curve_dfs_shocked_dev, csrc/curve_dfs.hip, and
+adr_scenario_rows_place_dev, csrc/shock_columns.hip; `monte_carlo_revalue_var_es`' chain): n synthetic off-grid OIS on the README GBP curve (K = 264 knots,
 P = F = 32), cut into B desks of equal size, under S normal scenarios, level 0.99.
 
 Timed on one device and one stream, inputs and buffers resident, medians of warm repetitions between HIP events:
@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from adrates_amd import _native
-from adrates_amd.market.position.monte_carlo import (ShockedCurves, _scenario_tile, factor_from_covariance, revalue_scenario_bytes,
+from adrates_amd.market.position.monte_carlo import (ShockedCurves, _tile_of, factor_from_covariance, revalue_scenario_bytes,
                                                      tail_measures_select)
 from adrates_amd.market.position.scenarios import ScenarioGrid, tail_count
 from adrates_amd.trades import synthetic
@@ -72,7 +72,7 @@ for n in TRADES:
             d_plan = up(_native.scenario_subbook_plan(n, sub_off))
             for S in SCENARIOS:
                 try:
-                    tile = _scenario_tile(curves, n, B, S, MAX_BYTES)
+                    tile = _tile_of(revalue_scenario_bytes(curves, n, B), B, S, MAX_BYTES)
                 except LibError as e:
                     result["not_measured"].append({"trades": n, "desks": B, "scenarios": S, "why": str(e)})
                     continue
