@@ -1,6 +1,7 @@
 """The bound the per-trade pricing kernels (`adr_price`: kernels_fast.hip, kernels_fast_lindf.hip, kernels_general.hip,
-kernels_lite.hip, kernels_knot.hip) are held to, element by element, on one pillar tile and on trades whose accruing coupons are
-paid on their accrual end (tests/test_price_edges_host.py, CPU, and tests/test_gpu_price_edges.py, GPU).
+kernels_lite.hip, kernels_knot.hip) are held to, element by element, on trades whose accruing coupons are paid on their accrual
+end: on one pillar tile (tests/test_price_edges_host.py, CPU, and tests/test_gpu_price_edges.py, GPU) and on the wide and tiled
+routes of 33 to 97 pillars (tests/test_price_wide_host.py and tests/test_gpu_price_wide.py; the families `wide` and `tiled`).
 
 The value and the gross of every element are `_ladder_reference.rates_reference`'s: per trade with ``sub_off = arange(n + 1)``,
 for the aggregate the one-desk row ``[0, n]``.  What is derived here is k of  |got - value| <= k 2^-53 gross  per kernel family,
@@ -53,6 +54,26 @@ general (kernels_general.hip, `add_nodes`; both variants - the LDS-resident rows
   only up to rounding, and a date between two short-end knots that move different pillars left 1e-21 to 1e-24 on gamma
   entries no term reaches.  tests/test_gpu_price_edges.py found it on the legs of 385, 400 and 450 coupons.)
 
+wide (kernels_general.hip, `add_nodes_wide`, the WIDE result block; 33-64 pillars, tests/test_gpu_price_wide.py): the node is
+  built by the lines the general kernel runs; gamma, the packed upper triangle, is the worst element:
+  v = fma(bb_i, lj64_i, v), lane p on pillar p: a Jacobian entry (1), the weight (e_w), the product, the add            e_w + 3
+  the hand-off holds v and om v (1); rank-one fma(wa.x, vb, acc): (om v_a) v_b - v twice, om v (1), the product (1)  2 e_w + 8
+  convexity fma(cc_0, la, fma(cc_1, lb, acc)): cc = om bb (e_w + 1), a packed row entry is a copy of LC (4), the product:
+            e_w + 6 of its own gross, less than the line above; a chunk the mask skips holds zeros for both knots (no rounding)
+  sums      the rank-one add and one add per knot's row                                                                    3 n
+  scale     g = acc 1e-8 (the constant, the product) on its way to the staging area; `flush_gamma` and `wide_store_map` copy  2
+  no merge: the rows are added straight into the packed registers               k = node + 2 e_w + 10 + 3 n  (`general` less 1)
+  LINEAR_FWD_RATES: `lindf_plain` walks the two single-knot nodes with b = (1, 0): v = fma(0, lj, fma(1, lj_k, 0)) is the
+  Jacobian entry itself (1), om v (1), the product with v_b (1 + 1): 4; cf LC: 5; a rank-one term and a row per knot: 4 n
+                                                                                     k = 9 + e_w + ceil(2 cond) + 8 + 4 n
+  pv (wave_sum: 6 adds and one per 64 coupons) and delta (fma(om, v, acc): e_w + 4, n adds, 1e-4: 2) stay below gamma's count.
+  The delta-only and PV-only instantiations (masks 3 and 1, the trades outside the lite table) run the same lines.
+
+tiled (more than 64 pillars or PILLAR_TILES: `price_general_kernel` without WIDE, rows streamed from L2, one launch per tile
+  pair): `add_nodes` with the row tile's v in lanes 0-31 and the column tile's in lanes 32-63 of the hand-off buffer - the
+  arithmetic of an element is that of `general`'s L2 variant, whichever launch writes it (pv: tile (0, 0); delta: the diagonal
+  launches; an off-diagonal tile and its mirror: one launch, one number)                                       k = `general`'s
+
 lite (kernels_lite.hip, `sweep`; PV and delta): ca = omega ba (e_w' + 1), fma(ca, LJ, d): LJ (1), the product (1); a node
   leaves two entries: 2 n adds, d0 + e0 (1), 1e-4 (2)                                  k = node' + e_w' + 6 + 2 n
   (node' = the node with e_w'; LINEAR_FWD_RATES likewise with its node)
@@ -73,6 +94,15 @@ aggregate (the one-desk row): trade t arrives with an error of at most k_t units
   block its waves in order (11: the fast kernel's 12 waves are the most), the reduction strides and runs its butterfly
   (ceil(blocks / 64) - 1 + 6), the knot pass adds its projection to it (1)
                              sums = n_trades + 18 + ceil(blocks / 64)  (+ the knot pass's sums where it runs)
+  wide (a plan whose launches with block partials are all wide-kernel launches): a wave adds its trades into `total` (at most
+  n_trades - 1 adds over all waves; a packed entry outside the triangle adds 0.0), the block adds its waves in order (7: eight
+  waves up to 10 chunks and without GAMMA, four beyond), `reduce_wide_kernel` strides over the blocks and runs its butterfly
+  (ceil(blocks / 64) - 1 + 6) and reads each element through the store map (a copy), the knot pass adds its projection (1)
+                             sums = n_trades + 12 + ceil(blocks / 64)  (+ the knot pass's sums where it runs)
+  tiled: every tile launch is followed by its own `reduce_partials_kernel` over the launch's blocks, which writes the tile
+  (and, off the diagonal, its mirror from the same number) - no element is summed over launches; four waves per block (3):
+  inside the count of the block partials above, which is used as it stands.  The knot pass's projection is one kernel for
+  every pillar count (`lj_at`, `lc_at`; columns in blocks of 64): `knot_sums` as it stands.
 """
 import math
 
@@ -166,11 +196,11 @@ def _node(method, cond, e_w):
 
 
 def trade_k(family, method, st):
-    """k of one trade priced by ``family`` ("fast", "fast_chained", "general", "lite")."""
+    """k of one trade priced by ``family`` ("fast", "fast_chained", "general", "wide", "tiled", "lite")."""
     method = int(method)
     e_w, n, cond = E_W[method], st["n"], st["cond"]
-    if family in ("fast", "fast_chained", "general"):
-        merge = 1 if family == "general" else 0
+    if family in ("fast", "fast_chained", "general", "wide", "tiled"):
+        merge = 1 if family in ("general", "tiled") else 0
         if method == LINEAR_FWD:
             return _node(method, cond, e_w) + 8 + 4 * n + merge
         return _node(method, cond, e_w) + 2 * e_w + 10 + 3 * n + merge
@@ -190,8 +220,9 @@ def knot_sums(stats, Kc, blocks):
     return sum(s["n"] for s in stats) + 7 + -(-max(blocks, 1) // 64) + 5 + 3 * (-(-Kc // 16)) + 18
 
 
-def aggregate_sums(n_trades, blocks):
-    return n_trades + 18 + -(-max(blocks, 1) // 64)
+def aggregate_sums(n_trades, blocks, wide=False):
+    """The adds of the block partials and their reduction; ``wide``: every launch with partials is a wide-kernel launch."""
+    return n_trades + (12 if wide else 18) + -(-max(blocks, 1) // 64)
 
 
 def book_k(ref, book, ks, name, sums):
