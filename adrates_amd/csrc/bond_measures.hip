@@ -276,31 +276,29 @@ int adr_bond_measures(adr_ctx* ctx, int interp_method, int n_nodes, const double
     rc = adr::meas::target_stream(who, ctx, n, nullptr, &stream);
     if (rc != ADR_OK || n == 0) return rc;
     const int64_t m = flow_off[n];
-    const size_t d = sizeof(double);
-    // one allocation: nodes, flows, bonds, outputs, then the offsets and the status words
-    const size_t n_dbl = 2 * static_cast<size_t>(n_nodes) + 4 * static_cast<size_t>(m) + 5 * static_cast<size_t>(n) +
-                         ADR_BOND_OUTPUTS * static_cast<size_t>(n);
-    const size_t bytes = n_dbl * d + static_cast<size_t>(n + 1) * sizeof(int64_t) + static_cast<size_t>(n) * sizeof(int32_t);
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_bond_measures: hipMalloc: ") + hipGetErrorString(e));
-    double *dt = reinterpret_cast<double*>(base), *dd = dt + n_nodes, *dT = dd + n_nodes, *dtau = dT + m, *dcpn = dtau + m;
-    double *dprin = dcpn + m, *dTs = dprin + m, *dtauM = dTs + n, *dface = dtauM + n, *dacc = dface + n, *dquote = dacc + n;
-    double* dout = dquote + n;
-    int64_t* doff = reinterpret_cast<int64_t*>(dout + ADR_BOND_OUTPUTS * n);
-    int32_t* dstatus = reinterpret_cast<int32_t*>(doff + n + 1);
-    const adr::call::Piece in[] = {{dt, node_t, n_nodes * d}, {dd, node_df, n_nodes * d}, {dT, flow_T, m * d},
-                                   {dtau, flow_tau, m * d},   {dcpn, flow_cpn, m * d},    {dprin, flow_prin, m * d},
-                                   {dTs, bond_Ts, n * d},     {dtauM, bond_tauM, n * d},  {dface, bond_face, n * d},
-                                   {dacc, bond_acc100, n * d}, {dquote, bond_quote, n * d},
-                                   {doff, flow_off, (n + 1) * sizeof(int64_t)}};
-    const adr::call::Piece res[] = {{out, dout, ADR_BOND_OUTPUTS * n * d}, {status, dstatus, n * sizeof(int32_t)}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
+    double *dt, *dd, *dT, *dtau, *dcpn, *dprin, *dTs, *dtauM, *dface, *dacc, *dquote, *dout;
+    int64_t* doff;
+    int32_t* dstatus;
+    adr::call::Staging mem;
+    mem.in(&dt, node_t, n_nodes);
+    mem.in(&dd, node_df, n_nodes);
+    mem.in(&dT, flow_T, m);
+    mem.in(&dtau, flow_tau, m);
+    mem.in(&dcpn, flow_cpn, m);
+    mem.in(&dprin, flow_prin, m);
+    mem.in(&dTs, bond_Ts, n);
+    mem.in(&dtauM, bond_tauM, n);
+    mem.in(&dface, bond_face, n);
+    mem.in(&dacc, bond_acc100, n);
+    mem.in(&dquote, bond_quote, n);
+    mem.in(&doff, flow_off, n + 1);
+    mem.out(&dout, out, ADR_BOND_OUTPUTS * static_cast<size_t>(n));
+    mem.out(&dstatus, status, n);
+    const hipError_t e = mem.begin(stream);
     if (e == hipSuccess)
         rc = adr_bond_measures_dev(ctx, interp_method, n_nodes, dt, dd, n, doff, dT, dtau, dcpn, dprin, dTs, dtauM, dface, dacc,
                                    dquote, quote_is_z, dout, dstatus, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = adr::call::copy_pieces(res, hipMemcpyDeviceToHost, stream);
-    return adr::call::finish_blocking(who, rc, e, stream, base);
+    return mem.finish(who, rc, e, stream);
 }
 
 int adr_bond_measures_host(int interp_method, int n_nodes, const double* node_t, const double* node_df, int64_t n,

@@ -375,7 +375,7 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Curves& c, const adr_trade
     if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
     if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
     hipStream_t stream = nullptr;
-    rc = target_stream(w, ctx, stream_or_null, &stream);
+    rc = call::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const int64_t chunks = subs ? sub::max_chunks(tr->n, B, kChunk) : (tr->n + kChunk - 1) / kChunk;
     dim3 grid;
@@ -413,46 +413,30 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Curves& c, bool curve
     }
     const size_t rows = B > 0 ? static_cast<size_t>(B) : 1;
     hipStream_t stream = nullptr;
-    rc = target_stream(w, ctx, nullptr, &stream);
+    rc = call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    const size_t d = sizeof(double), K = c.K, SK = static_cast<size_t>(c.S_disc) * K, SG = static_cast<size_t>(c.S_spr) * c.G;
-    const size_t W = static_cast<size_t>(B > 0 ? adr_scenario_subbook_work(n, B, c.S) : adr_credit_scenario_pv_work(n, c.S));
-    const size_t NS = static_cast<size_t>(n) * c.S;
-    const size_t nf = static_cast<size_t>(x.n_fix), nl = static_cast<size_t>(x.n_flt);
-    const size_t n_dbl = (curves_on_host ? K + SK : 0) + SG + n + nf + nl + (pv ? NS : 0) + rows * c.S + W + plan.size();
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + static_cast<size_t>(n) * sizeof(int32_t));
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double* p = reinterpret_cast<double*>(base);
-    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
+    double *ht, *hd, *ddz, *dzs, *dft, *dlt, *dpv, *dbook, *dwork;
+    int64_t* dplan;
+    int32_t* dbucket;
+    call::Staging mem;                              // `plan` is uploaded from where it stands: it outlives finish()
+    mem.in(&ht, c.times, c.K, curves_on_host);
+    mem.in(&hd, c.dfs, static_cast<size_t>(c.S_disc) * c.K, curves_on_host);
+    mem.in(&dplan, plan.data(), plan.size());
+    mem.in(&ddz, c.dz, static_cast<size_t>(c.S_spr) * c.G);        // null with G = 0
+    mem.in(&dzs, x.z, n);
+    mem.in(&dft, x.fix_tau, x.n_fix);
+    mem.in(&dlt, x.flt_tau, x.n_flt);
+    mem.in(&dbucket, x.bucket, n);
+    mem.out(&dpv, pv, static_cast<size_t>(n) * c.S, pv != nullptr);
+    mem.out(&dbook, book, rows * c.S);
+    mem.scratch(&dwork, static_cast<size_t>(B > 0 ? adr_scenario_subbook_work(n, B, c.S) : adr_credit_scenario_pv_work(n, c.S)));
+    const hipError_t e = mem.begin(stream);
     Curves dc = c;
-    struct Piece { void* dst; const void* src; size_t bytes; };
-    std::vector<Piece> in;
-    if (curves_on_host) {
-        double *ht = take(K), *hd = take(SK);
-        in.push_back({ht, c.times, K * d});
-        in.push_back({hd, c.dfs, SK * d});
-        dc.times = ht; dc.dfs = hd;
-    }
-    double *ddz = take(SG), *dzs = take(n), *dft = take(nf), *dlt = take(nl);
-    double* dpv = pv ? take(NS) : nullptr;
-    double *dbook = take(rows * c.S), *dwork = take(W);
-    int64_t* dplan = B > 0 ? reinterpret_cast<int64_t*>(take(plan.size())) : nullptr;
-    if (dplan) in.push_back({dplan, plan.data(), plan.size() * sizeof(int64_t)});
-    int32_t* dbucket = reinterpret_cast<int32_t*>(p);
-    in.push_back({ddz, c.dz, SG * d});
-    in.push_back({dzs, x.z, static_cast<size_t>(n) * d});
-    in.push_back({dft, x.fix_tau, nf * d});
-    in.push_back({dlt, x.flt_tau, nl * d});
-    in.push_back({dbucket, x.bucket, static_cast<size_t>(n) * sizeof(int32_t)});
-    for (const Piece& pc : in)
-        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
-    dc.dz = c.G > 0 ? ddz : nullptr;
+    if (curves_on_host) { dc.times = ht; dc.dfs = hd; }
+    dc.dz = ddz;
     const Extra dx{dzs, dbucket, x.n_fix, dft, x.n_flt, dlt};
     if (e == hipSuccess) rc = enqueue(w, ctx, dc, trades, dx, dpv, dbook, dwork, stream, B, dplan);
-    if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, rows * c.S * d, hipMemcpyDeviceToHost, stream);
-    return finish_blocking(w, rc, e, stream, base);
+    return mem.finish(w, rc, e, stream);
 }
 
 template <bool kLog>

@@ -375,7 +375,7 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Handles& h, int64_t B, con
     if (!out) return adr_set_error(ADR_ERR_INVALID, w + ": out is NULL");
     if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_credit_subbook_ladders_work doubles are needed)");
     hipStream_t stream = nullptr;
-    const int rc = scen::target_stream(w, ctx, stream_or_null, &stream);
+    const int rc = call::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const CurveDev& cv = *h.cv;
     const int S = record_doubles(cv.Kc, rq.gamma);
@@ -526,32 +526,26 @@ int adr_credit_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, const adr_t
     rc = adr::sub::build_plan(w, n, C, cells.cell_off.data(), plan);
     if (rc != ADR_OK) return rc;
     hipStream_t stream = nullptr;
-    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
+    rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the ladders, the scratch, the spread side, the plan and the cell tables (8-byte items first)
     const int Q = h.cv->P + G;
-    const size_t d = sizeof(double), n_out = static_cast<size_t>(B) * (1 + Q + static_cast<size_t>(Q) * Q);
-    const size_t W = static_cast<size_t>(CL::work_doubles(h.cv->Kc, n, B, C, rq.gamma, nullptr));
-    const size_t nf = static_cast<size_t>(n_fix), nl = static_cast<size_t>(n_flt), nn = static_cast<size_t>(n);
-    const size_t words = n_out + W + nn + nf + nl + plan.size() + static_cast<size_t>(B + 1);
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), words * d + (nn + static_cast<size_t>(C)) * sizeof(int32_t));
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double* p = reinterpret_cast<double*>(base);
-    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
-    double *dout = take(n_out), *dwork = take(W), *dz = take(nn), *dft = take(nf), *dlt = take(nl);
-    int64_t *dplan = reinterpret_cast<int64_t*>(take(plan.size())), *ddesk = reinterpret_cast<int64_t*>(take(static_cast<size_t>(B + 1)));
-    int32_t *dbucket = reinterpret_cast<int32_t*>(p), *dcellb = dbucket + nn;
-    const adr::call::Piece in[] = {{dz, z, nn * d}, {dft, fix_tau, nf * d}, {dlt, flt_tau, nl * d},
-                                   {dplan, plan.data(), plan.size() * sizeof(int64_t)},
-                                   {ddesk, cells.desk_cell_off.data(), static_cast<size_t>(B + 1) * sizeof(int64_t)},
-                                   {dbucket, bucket, nn * sizeof(int32_t)},
-                                   {dcellb, cells.cell_bucket.data(), static_cast<size_t>(C) * sizeof(int32_t)}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
+    double *dout, *dwork, *dz, *dft, *dlt;
+    int64_t *dplan, *ddesk;
+    int32_t *dbucket, *dcellb;
+    adr::call::Staging mem;                         // `plan` and `cells` are uploaded from where they stand: they outlive finish()
+    mem.out(&dout, out, static_cast<size_t>(B) * (1 + Q + static_cast<size_t>(Q) * Q));
+    mem.scratch(&dwork, static_cast<size_t>(CL::work_doubles(h.cv->Kc, n, B, C, rq.gamma, nullptr)));
+    mem.in(&dz, z, n);
+    mem.in(&dft, fix_tau, n_fix);
+    mem.in(&dlt, flt_tau, n_flt);
+    mem.in(&dplan, plan.data(), plan.size());
+    mem.in(&ddesk, cells.desk_cell_off.data(), B + 1);
+    mem.in(&dbucket, bucket, n);
+    mem.in(&dcellb, cells.cell_bucket.data(), C);
+    const hipError_t e = mem.begin(stream);
     const CL::DevArrays da{CL::Extra{dz, dbucket, n_fix, dft, n_flt, dlt, G}, C, dplan, ddesk, dcellb};
     if (e == hipSuccess) rc = CL::enqueue(w, ctx, h, B, da, rq, dout, dwork, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, n_out * d, hipMemcpyDeviceToHost, stream);
-    return adr::scen::finish_blocking(w, rc, e, stream, base);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_credit_subbook_ladders_host(int interp_method, int K, int P, const double* times, const double* dfs, const double* jac,

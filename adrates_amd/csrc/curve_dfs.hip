@@ -188,24 +188,20 @@ int adr_curve_dfs_shocked(adr_ctx* ctx, const adr_curve_plan* plan, const double
     hipStream_t stream = nullptr;
     rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the base rates, the shock rows, the discount factors, the scratch, the flags
-    const size_t d = sizeof(double), n_x = static_cast<size_t>(S) * ld, n_df = static_cast<size_t>(S) * a.K;
-    const size_t n_w = static_cast<size_t>(a.K + a.P) * S, n_bad = (static_cast<size_t>(S) + 1) / 2;
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (a.P + n_x + n_df + n_w + n_bad) * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *d_base = base, *d_x = d_base + a.P, *d_df = d_x + n_x, *d_w = d_df + n_df;
-    int32_t* d_bad = reinterpret_cast<int32_t*>(d_w + n_w);
-    const adr::call::Piece in[] = {{d_base, base_rates, a.P * d}, {d_x, shocks_bp, n_x * d}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
+    double *d_base, *d_x, *d_df, *d_w;
+    int32_t* d_bad;
+    adr::call::Staging mem;
+    mem.in(&d_base, base_rates, a.P);
+    mem.in(&d_x, shocks_bp, static_cast<size_t>(S) * ld);
+    mem.out(&d_df, dfs, static_cast<size_t>(S) * a.K);
+    mem.scratch(&d_w, static_cast<size_t>(a.K + a.P) * S);
+    if (bad) mem.out(&d_bad, bad, S);
+    else mem.scratch(&d_bad, S);                    // the kernel writes the flags whether or not they are asked for
+    const hipError_t e = mem.begin(stream);
     a.base = d_base; a.shocks = d_x; a.dfs = d_df; a.bad = d_bad; a.work = d_w;
     a.S = S; a.ld = ld;
     if (e == hipSuccess) rc = CD::enqueue(w, a, stream);
-    if (e == hipSuccess && rc == ADR_OK) {
-        const adr::call::Piece out[] = {{dfs, d_df, n_df * d}, {bad, d_bad, bad ? S * sizeof(int32_t) : 0}};
-        e = adr::call::copy_pieces(out, hipMemcpyDeviceToHost, stream);
-    }
-    return adr::call::finish_blocking(w, rc, e, stream, base);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_curve_dfs_shocked_host(int K, int P, const double* acc, const int32_t* pillar, const int32_t* prev_idx, const double* base_rates,

@@ -299,30 +299,24 @@ int adr_frn_measures(adr_ctx* ctx, int disc_method, int disc_n, const double* di
     hipStream_t stream = nullptr;
     rc = adr::meas::target_stream(who, ctx, n, nullptr, &stream);
     if (rc != ADR_OK || n == 0) return rc;
-    const size_t d = sizeof(double);
-    // one allocation: the two node tables, coupons, FRNs, outputs, then the offsets and the status words
-    const size_t n_dbl = 2 * static_cast<size_t>(disc_n) + 2 * static_cast<size_t>(index_n) +
-                         ADR_FRN_FLOW_FIELDS * static_cast<size_t>(m) + ADR_FRN_FIELDS * static_cast<size_t>(n) +
-                         ADR_FRN_OUTPUTS * static_cast<size_t>(n);
-    const size_t bytes = n_dbl * d + static_cast<size_t>(n + 1) * sizeof(int64_t) + static_cast<size_t>(n) * sizeof(int32_t);
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string("adr_frn_measures: hipMalloc: ") + hipGetErrorString(e));
-    double *ddt = reinterpret_cast<double*>(base), *ddd = ddt + disc_n, *dit = ddd + disc_n, *did = dit + index_n;
-    double *dcpn = did + index_n, *dfrn = dcpn + ADR_FRN_FLOW_FIELDS * m, *dout = dfrn + ADR_FRN_FIELDS * n;
-    int64_t* doff = reinterpret_cast<int64_t*>(dout + ADR_FRN_OUTPUTS * n);
-    int32_t* dstatus = reinterpret_cast<int32_t*>(doff + n + 1);
-    const adr::call::Piece in[] = {{ddt, disc_t, disc_n * d},   {ddd, disc_df, disc_n * d},
-                                   {dit, index_t, index_n * d}, {did, index_df, index_n * d},
-                                   {dcpn, cpn, ADR_FRN_FLOW_FIELDS * m * d}, {dfrn, frn, ADR_FRN_FIELDS * n * d},
-                                   {doff, cpn_off, (n + 1) * sizeof(int64_t)}};
-    const adr::call::Piece res[] = {{out, dout, ADR_FRN_OUTPUTS * n * d}, {status, dstatus, n * sizeof(int32_t)}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
+    double *ddt, *ddd, *dit, *did, *dcpn, *dfrn, *dout;
+    int64_t* doff;
+    int32_t* dstatus;
+    adr::call::Staging mem;
+    mem.in(&ddt, disc_t, disc_n);
+    mem.in(&ddd, disc_df, disc_n);
+    mem.in(&dit, index_t, index_n);
+    mem.in(&did, index_df, index_n);
+    mem.in(&dcpn, cpn, ADR_FRN_FLOW_FIELDS * static_cast<size_t>(m));
+    mem.in(&dfrn, frn, ADR_FRN_FIELDS * static_cast<size_t>(n));
+    mem.in(&doff, cpn_off, n + 1);
+    mem.out(&dout, out, ADR_FRN_OUTPUTS * static_cast<size_t>(n));
+    mem.out(&dstatus, status, n);
+    const hipError_t e = mem.begin(stream);
     if (e == hipSuccess)
         rc = adr_frn_measures_dev(ctx, disc_method, disc_n, ddt, ddd, index_method, index_n, dit, did, n, m, doff, dcpn, dfrn,
                                   quote_is_dm, dout, dstatus, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = adr::call::copy_pieces(res, hipMemcpyDeviceToHost, stream);
-    return adr::call::finish_blocking(who, rc, e, stream, base);
+    return mem.finish(who, rc, e, stream);
 }
 
 int adr_frn_measures_host(int disc_method, int disc_n, const double* disc_t, const double* disc_df, int index_method,

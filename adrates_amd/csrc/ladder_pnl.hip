@@ -212,32 +212,17 @@ int adr_ladder_pnl(adr_ctx* ctx, int64_t B, int P, const double* ladders, int S,
     hipStream_t stream = nullptr;
     rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the ladders, the shocks, the outputs asked for
-    const size_t d = sizeof(double), n_lad = static_cast<size_t>(B) * (1 + P + static_cast<size_t>(P) * P);
-    const size_t n_x = static_cast<size_t>(S) * P, n_out = static_cast<size_t>(B) * S;
-    double* host_out[3] = {pnl, pnl_delta, pnl_gamma};
-    double* dev_out[3] = {nullptr, nullptr, nullptr};
-    size_t wanted = 0;
-    for (double* o : host_out) wanted += o ? 1 : 0;
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (n_lad + n_x + wanted * n_out) * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *dlad = base, *dx = dlad + n_lad, *next = dx + n_x;
-    for (int i = 0; i < 3; ++i)
-        if (host_out[i]) {
-            dev_out[i] = next;
-            next += n_out;
-        }
-    const adr::call::Piece in[] = {{dlad, ladders, n_lad * d}, {dx, shocks_bp, n_x * d}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) rc = LP::enqueue(w, LP::Args{dlad, dx, dev_out[0], dev_out[1], dev_out[2], B, P, S}, stream);
-    if (e == hipSuccess && rc == ADR_OK) {
-        const adr::call::Piece out[] = {{pnl, dev_out[0], pnl ? n_out * d : 0},
-                                        {pnl_delta, dev_out[1], pnl_delta ? n_out * d : 0},
-                                        {pnl_gamma, dev_out[2], pnl_gamma ? n_out * d : 0}};
-        e = adr::call::copy_pieces(out, hipMemcpyDeviceToHost, stream);
-    }
-    return adr::call::finish_blocking(w, rc, e, stream, base);
+    const size_t n_out = static_cast<size_t>(B) * S;
+    double *dlad, *dx, *dpnl, *ddelta, *dgamma;
+    adr::call::Staging mem;
+    mem.in(&dlad, ladders, static_cast<size_t>(B) * (1 + P + static_cast<size_t>(P) * P));
+    mem.in(&dx, shocks_bp, static_cast<size_t>(S) * P);
+    mem.out(&dpnl, pnl, n_out, pnl != nullptr);                     // the outputs asked for
+    mem.out(&ddelta, pnl_delta, n_out, pnl_delta != nullptr);
+    mem.out(&dgamma, pnl_gamma, n_out, pnl_gamma != nullptr);
+    const hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) rc = LP::enqueue(w, LP::Args{dlad, dx, dpnl, ddelta, dgamma, B, P, S}, stream);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_ladder_pnl_host(int64_t B, int P, const double* ladders, int S, const double* shocks_bp, double* pnl, double* pnl_delta,

@@ -158,10 +158,6 @@ hipError_t launch_with_lds(Kernel kernel, const Args& a, size_t lds, dim3 grid, 
     return hipGetLastError();
 }
 
-// The stream of a call and the end of a blocking one: blocking_call.hpp's, under this namespace's names.
-using call::finish_blocking;
-using call::target_stream;
-
 // ------------------------------------------------------------------------------------------------------- host checks
 // The first failing check decides an entry's message, so each entry calls these in its own order.
 inline int check_scheme_knots(const std::string& w, int method, int K) {

@@ -258,7 +258,7 @@ int enqueue(const std::string& w, adr_ctx* ctx, int method, int K, const double*
     if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
     if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
     hipStream_t stream = nullptr;
-    rc = target_stream(w, ctx, stream_or_null, &stream);
+    rc = call::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const int64_t chunks = subs ? sub::max_chunks(tr->n, B, kChunk) : (tr->n + kChunk - 1) / kChunk;
     dim3 grid;
@@ -305,40 +305,26 @@ int run_blocking(const std::string& w, adr_ctx* ctx, int method, int K, const do
     }
     const size_t B = sub ? static_cast<size_t>(sub->B) : 0, rows = sub ? B : 1;
     hipStream_t stream = nullptr;
-    rc = target_stream(w, ctx, nullptr, &stream);
+    rc = call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    const size_t d = sizeof(double), SK = static_cast<size_t>(S) * K;
-    const size_t W = static_cast<size_t>(sub ? adr_scenario_subbook_work(n, sub->B, S) : adr_scenario_pv_work(n, S));
-    const size_t n_dbl = (curves_on_host ? K + SK : 0) + (pv ? static_cast<size_t>(n) * S : 0) + rows * S + W + plan.size() +
-                         (tail ? 2 * B : 0);
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double* p = base;
-    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
-    const double *dt = times, *ddf = dfs;
-    if (curves_on_host) {
-        double *ht = take(K), *hd = take(SK);
-        e = hipMemcpyAsync(ht, times, K * d, hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hd, dfs, SK * d, hipMemcpyHostToDevice, stream);
-        dt = ht; ddf = hd;
-    }
-    double* dpv = pv ? take(static_cast<size_t>(n) * S) : nullptr;
-    double *dbook = take(rows * S), *dwork = take(W);
-    int64_t* dplan = nullptr;
-    if (sub) {
-        dplan = reinterpret_cast<int64_t*>(take(plan.size()));
-        if (e == hipSuccess) e = hipMemcpyAsync(dplan, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream);
-    }
-    double *dvar = tail ? take(B) : nullptr, *des = tail ? take(B) : nullptr;
-    if (e == hipSuccess) rc = enqueue(w, ctx, method, K, dt, S, ddf, trades, dpv, dbook, dwork, stream, sub ? sub->B : 0, dplan);
-    if (e == hipSuccess && rc == ADR_OK && pv) e = hipMemcpyAsync(pv, dpv, static_cast<size_t>(n) * S * d, hipMemcpyDeviceToHost, stream);
-    if (tail) {
-        if (e == hipSuccess && rc == ADR_OK) e = sub::enqueue_tail(dbook, sub->B, S, sub->base_col, sub->k, dvar, des, stream);
-        if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(sub->var, dvar, B * d, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(sub->es, des, B * d, hipMemcpyDeviceToHost, stream);
-    } else if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(book, dbook, rows * S * d, hipMemcpyDeviceToHost, stream);
-    return finish_blocking(w, rc, e, stream, base);
+    double *ht, *hd, *dpv, *dbook, *dwork, *dvar, *des;
+    int64_t* dplan;
+    call::Staging mem;                              // `plan` is uploaded from where it stands: it outlives finish()
+    mem.in(&ht, times, K, curves_on_host);
+    mem.in(&hd, dfs, static_cast<size_t>(S) * K, curves_on_host);
+    mem.out(&dpv, pv, static_cast<size_t>(n) * S, pv != nullptr);
+    if (tail) mem.scratch(&dbook, rows * S);        // the rows stay on the device: var and es go back in their place
+    else mem.out(&dbook, book, rows * S);
+    mem.scratch(&dwork, static_cast<size_t>(sub ? adr_scenario_subbook_work(n, sub->B, S) : adr_scenario_pv_work(n, S)));
+    mem.in(&dplan, plan.data(), plan.size());
+    mem.out(&dvar, tail ? sub->var : nullptr, B, tail);
+    mem.out(&des, tail ? sub->es : nullptr, B, tail);
+    hipError_t e = mem.begin(stream);
+    if (e == hipSuccess)
+        rc = enqueue(w, ctx, method, K, curves_on_host ? ht : times, S, curves_on_host ? hd : dfs, trades, dpv, dbook, dwork, stream,
+                     sub ? sub->B : 0, dplan);
+    if (e == hipSuccess && rc == ADR_OK && tail) e = sub::enqueue_tail(dbook, sub->B, S, sub->base_col, sub->k, dvar, des, stream);
+    return mem.finish(w, rc, e, stream);
 }
 
 template <bool kLog>

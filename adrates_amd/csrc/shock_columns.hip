@@ -155,23 +155,16 @@ int adr_shock_columns(adr_ctx* ctx, int S, int ld, const double* shocks_bp, int 
     hipStream_t stream = nullptr;
     rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the shock rows, the base row, the columns, the flags
-    const size_t d = sizeof(double), n_x = static_cast<size_t>(S) * ld, n_out = static_cast<size_t>(S) * n;
-    const size_t n_base = base ? n : 0, n_bad = bad ? (static_cast<size_t>(S) + 1) / 2 : 0;
-    double* mem = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&mem), (n_x + n_base + n_out + n_bad) * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *d_x = mem, *d_base = d_x + n_x, *d_out = d_base + n_base;
-    int32_t* d_bad = reinterpret_cast<int32_t*>(d_out + n_out);
-    const adr::call::Piece in[] = {{d_x, shocks_bp, n_x * d}, {d_base, base, n_base * d}, {d_bad, bad, bad ? S * sizeof(int32_t) : 0}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess)
-        rc = SQ::enqueue_columns(w, SQ::Args{d_x, base ? d_base : nullptr, d_out, bad ? d_bad : nullptr, floor, S, ld, col0, n, floor_on}, stream);
-    if (e == hipSuccess && rc == ADR_OK) {
-        const adr::call::Piece back[] = {{out, d_out, n_out * d}, {bad, d_bad, bad ? S * sizeof(int32_t) : 0}};
-        e = adr::call::copy_pieces(back, hipMemcpyDeviceToHost, stream);
-    }
-    return adr::call::finish_blocking(w, rc, e, stream, mem);
+    double *d_x, *d_base, *d_out;
+    int32_t* d_bad;
+    adr::call::Staging mem;
+    mem.in(&d_x, shocks_bp, static_cast<size_t>(S) * ld);
+    mem.in(&d_base, base, n, base != nullptr);
+    mem.out(&d_out, out, static_cast<size_t>(S) * n);
+    mem.inout(&d_bad, bad, S, bad != nullptr);                      // the flags are only ever raised: the caller's come in first
+    const hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) rc = SQ::enqueue_columns(w, SQ::Args{d_x, d_base, d_out, d_bad, floor, S, ld, col0, n, floor_on}, stream);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_shock_columns_host(int S, int ld, const double* shocks_bp, int col0, int n, const double* base, int floor_on, double floor,

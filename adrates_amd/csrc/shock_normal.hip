@@ -269,16 +269,13 @@ int adr_shock_normal(adr_ctx* ctx, uint64_t seed, int64_t first_scenario, int S,
     hipStream_t stream = nullptr;
     rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the factor matrix, the shocks
-    const size_t d = sizeof(double), n_f = static_cast<size_t>(P) * F, n_x = static_cast<size_t>(S) * P;
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (n_f + n_x) * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *dfac = base, *dx = base + n_f;
-    e = hipMemcpyAsync(dfac, factor, n_f * d, hipMemcpyHostToDevice, stream);
+    double *dfac, *dx;
+    adr::call::Staging mem;
+    mem.in(&dfac, factor, static_cast<size_t>(P) * F);
+    mem.out(&dx, out, static_cast<size_t>(S) * P);
+    const hipError_t e = mem.begin(stream);
     if (e == hipSuccess) rc = SN::enqueue(w, SN::Args{seed, first_scenario, dfac, dx, S, P, F, antithetic}, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dx, n_x * d, hipMemcpyDeviceToHost, stream);
-    return adr::call::finish_blocking(w, rc, e, stream, base);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_shock_normal_host(uint64_t seed, int64_t first_scenario, int S, int P, int F, const double* factor, int antithetic,
@@ -338,14 +335,16 @@ int adr_shock_uniforms(adr_ctx* ctx, uint64_t seed, int64_t first_scenario, int 
     const int pairs = (F + 1) / 2;
     const int64_t n = static_cast<int64_t>(S) * pairs, blocks = (n + 255) / 256;
     if (blocks > INT32_MAX) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 2^31 blocks of pairs");
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), static_cast<size_t>(n) * 2 * sizeof(double));
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    hipLaunchKernelGGL(SN::shock_uniforms_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, seed, first_scenario,
-                       static_cast<int64_t>(S), pairs, antithetic, base);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(u, base, static_cast<size_t>(n) * 2 * sizeof(double), hipMemcpyDeviceToHost, stream);
-    return adr::call::finish_blocking(w, ADR_OK, e, stream, base);
+    double* du;
+    adr::call::Staging mem;
+    mem.out(&du, u, static_cast<size_t>(n) * 2);
+    hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(SN::shock_uniforms_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, seed, first_scenario,
+                           static_cast<int64_t>(S), pairs, antithetic, du);
+        e = hipGetLastError();
+    }
+    return mem.finish(w, ADR_OK, e, stream);
 }
 
 }  // extern "C"

@@ -209,7 +209,7 @@ void reduce_subbooks(const double* work, const int64_t* chunk_off, int64_t B, in
 
 // ------------------------------------------------------------------------------------------------------ tail measures
 // key_of, value_of, pnl_at, tail_of_sorted, tail_kernel and enqueue_tail: subbook.hpp (adr_scenario_tail_select* runs them too).
-int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+int check_sizes(const std::string& w, int64_t B, int S_tot, int base_col, int k, const TailLimit& limit) {
     if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
     if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
     if (base_col < -1 || base_col >= S_tot)
@@ -219,10 +219,14 @@ int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k) 
     if (m < 1) return adr_set_error(ADR_ERR_INVALID, w + ": no P&L value is left beside the base column");
     if (k < 1 || k > m)
         return adr_set_error(ADR_ERR_INVALID, w + ": k must lie in 1 .. " + std::to_string(m) + " (the P&L values per row)");
-    if (m > ADR_SCENARIO_TAIL_MAX)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": " + std::to_string(m) + " P&L values per row; a row of at most "
-                                                  "ADR_SCENARIO_TAIL_MAX (16384) fits the LDS");
+    const int limited = limit.on_tail ? k : m;
+    if (limited > limit.max)
+        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": " + limit.before + std::to_string(limited) + limit.after);
     return ADR_OK;
+}
+int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
+    return check_sizes(w, B, S_tot, base_col, k,
+                       TailLimit{false, ADR_SCENARIO_TAIL_MAX, "", " P&L values per row; a row of at most ADR_SCENARIO_TAIL_MAX (16384) fits the LDS"});
 }
 
 // ---------------------------------------------------------------------------------------------------- tail allocation
@@ -308,19 +312,8 @@ __global__ __launch_bounds__(256) void alloc_rows_kernel(const double* rows, int
 }
 
 int check_alloc(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
-    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
-    if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
-    if (base_col < -1 || base_col >= S_tot)
-        return adr_set_error(ADR_ERR_INVALID, w + ": base_col must be -1 (the rows are P&L) or a column, 0 .. " +
-                                                  std::to_string(S_tot - 1));
-    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
-    if (m < 1) return adr_set_error(ADR_ERR_INVALID, w + ": no P&L value is left beside the base column");
-    if (k < 1 || k > m)
-        return adr_set_error(ADR_ERR_INVALID, w + ": k must lie in 1 .. " + std::to_string(m) + " (the P&L values per row)");
-    if (m > ADR_SCENARIO_ALLOC_MAX)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": " + std::to_string(m) + " P&L values per row; at most "
-                                                  "ADR_SCENARIO_ALLOC_MAX (8192) (key, index) pairs fit the LDS");
-    return ADR_OK;
+    return check_sizes(w, B, S_tot, base_col, k,
+                       TailLimit{false, ADR_SCENARIO_ALLOC_MAX, "", " P&L values per row; at most ADR_SCENARIO_ALLOC_MAX (8192) (key, index) pairs fit the LDS"});
 }
 
 hipError_t enqueue_alloc_total(const double* rows, int64_t B, int S_tot, int base_col, double* tot, hipStream_t stream) {
@@ -410,12 +403,10 @@ int adr_scenario_tail_dev(adr_ctx* ctx, int64_t B, int S_tot, const double* rows
     int rc = SB::check_tail(w, B, S_tot, base_col, k);
     if (rc != ADR_OK) return rc;
     if (!rows_dev || !var_dev || !es_dev) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
-    int device = 0;
-    hipStream_t own = nullptr;
-    rc = adr_ctx_target(ctx, &device, &own);
+    hipStream_t s = nullptr;
+    rc = adr::call::target_stream(w, ctx, static_cast<hipStream_t>(stream), &s);
     if (rc != ADR_OK) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = SB::enqueue_tail(rows_dev, B, S_tot, base_col, k, var_dev, es_dev, stream ? static_cast<hipStream_t>(stream) : own);
+    const hipError_t e = SB::enqueue_tail(rows_dev, B, S_tot, base_col, k, var_dev, es_dev, s);
     if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": " + hipGetErrorString(e));
     return ADR_OK;
 }
@@ -426,18 +417,16 @@ int adr_scenario_tail(adr_ctx* ctx, int64_t B, int S_tot, const double* rows, in
     if (rc != ADR_OK) return rc;
     if (!rows || !var || !es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
     hipStream_t stream = nullptr;
-    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
+    rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot;
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (R + 2 * static_cast<size_t>(B)) * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *dvar = base + R, *des = dvar + B;
-    e = hipMemcpyAsync(base, rows, R * d, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = SB::enqueue_tail(base, B, S_tot, base_col, k, dvar, des, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(var, dvar, B * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(es, des, B * d, hipMemcpyDeviceToHost, stream);
-    return adr::scen::finish_blocking(w, ADR_OK, e, stream, base);
+    double *drows, *dvar, *des;
+    adr::call::Staging mem;
+    mem.in(&drows, rows, static_cast<size_t>(B) * S_tot);
+    mem.out(&dvar, var, B);
+    mem.out(&des, es, B);
+    hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) e = SB::enqueue_tail(drows, B, S_tot, base_col, k, dvar, des, stream);
+    return mem.finish(w, ADR_OK, e, stream);
 }
 
 int adr_scenario_tail_host(int64_t B, int S_tot, const double* rows, int base_col, int k, double* var, double* es) {
@@ -476,7 +465,7 @@ int adr_scenario_tail_alloc_dev(adr_ctx* ctx, int64_t B, int S_tot, const double
     if (!rows_dev || !var_tot_dev || !es_tot_dev || !comp_var_dev || !comp_es_dev) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
     if (!work_dev) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (S_tot doubles are needed)");
     hipStream_t s = nullptr;
-    rc = adr::scen::target_stream(w, ctx, static_cast<hipStream_t>(stream), &s);
+    rc = adr::call::target_stream(w, ctx, static_cast<hipStream_t>(stream), &s);
     if (rc != ADR_OK) return rc;
     const hipError_t e = SB::enqueue_alloc(rows_dev, B, S_tot, base_col, k, var_tot_dev, es_tot_dev, comp_var_dev, comp_es_dev,
                                            work_dev, s);
@@ -491,21 +480,19 @@ int adr_scenario_tail_alloc(adr_ctx* ctx, int64_t B, int S_tot, const double* ro
     if (rc != ADR_OK) return rc;
     if (!rows || !var_tot || !es_tot || !comp_var || !comp_es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
     hipStream_t stream = nullptr;
-    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
+    rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the rows, the scratch, the two totals, the two component vectors
-    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot, nb = static_cast<size_t>(B);
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (R + S_tot + 2 + 2 * nb) * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *dwork = base + R, *dtot = dwork + S_tot, *dcv = dtot + 2, *dce = dcv + nb;
-    e = hipMemcpyAsync(base, rows, R * d, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = SB::enqueue_alloc(base, B, S_tot, base_col, k, dtot, dtot + 1, dcv, dce, dwork, stream);
-    double totals[2] = {0.0, 0.0};
-    if (e == hipSuccess) e = hipMemcpyAsync(totals, dtot, 2 * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(comp_var, dcv, nb * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(comp_es, dce, nb * d, hipMemcpyDeviceToHost, stream);
-    rc = adr::scen::finish_blocking(w, ADR_OK, e, stream, base);
+    double totals[2] = {0.0, 0.0};                  // the caller's two are written only by a call that succeeds
+    double *drows, *dwork, *dtot, *dcv, *dce;
+    adr::call::Staging mem;
+    mem.in(&drows, rows, static_cast<size_t>(B) * S_tot);
+    mem.scratch(&dwork, S_tot);
+    mem.out(&dtot, totals, 2);
+    mem.out(&dcv, comp_var, B);
+    mem.out(&dce, comp_es, B);
+    hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) e = SB::enqueue_alloc(drows, B, S_tot, base_col, k, dtot, dtot + 1, dcv, dce, dwork, stream);
+    rc = mem.finish(w, ADR_OK, e, stream);
     if (rc == ADR_OK) {
         *var_tot = totals[0];
         *es_tot = totals[1];
@@ -520,18 +507,13 @@ int adr_scenario_tail_alloc_host(int64_t B, int S_tot, const double* rows, int b
     if (rc != ADR_OK) return rc;
     if (!rows || !var_tot || !es_tot || !comp_var || !comp_es) return adr_set_error(ADR_ERR_INVALID, w + ": null array");
     const int m = base_col >= 0 ? S_tot - 1 : S_tot;
+    std::vector<double> tot(static_cast<size_t>(m));
+    SB::alloc_total_host(rows, B, S_tot, base_col, tot.data());
     std::vector<SB::KeyIdx> pairs(static_cast<size_t>(m));
     bool nan = false;
     for (int e = 0; e < m; ++e) {
-        double p[SB::kSlots];
-        for (int q = 0; q < SB::kSlots; ++q) {
-            p[q] = 0.0;
-            for (int64_t b = q; b < B; b += SB::kSlots) p[q] = p[q] + SB::pnl_at(rows + b * S_tot, base_col, e);
-        }
-        for (int h = SB::kSlots / 2; h >= 1; h >>= 1)
-            for (int q = 0; q < h; ++q) p[q] = p[q] + p[q + h];
-        nan |= p[0] != p[0];
-        pairs[e] = SB::KeyIdx{SB::key_of(p[0]), e};
+        nan |= tot[e] != tot[e];
+        pairs[e] = SB::KeyIdx{SB::key_of(tot[e]), e};
     }
     if (nan) {
         *var_tot = *es_tot = NAN;

@@ -123,7 +123,17 @@ inline hipError_t enqueue_tail(const double* rows, int64_t B, int S_tot, int bas
                        base_col, m, P, k, var, es);
     return hipGetLastError();
 }
-int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k);
+
+// The size checks of every tail entry (adr_scenario_tail*, _tail_alloc*, _tail_select*, _tail_order*): the rows, the
+// columns, base_col and k, then the entry's own limit - on the tail count k, or else on the row's width m - refused as
+// w + ": " + before + the count + after.
+struct TailLimit {
+    bool on_tail;
+    int max;
+    const char *before, *after;
+};
+int check_sizes(const std::string& w, int64_t B, int S_tot, int base_col, int k, const TailLimit& limit);
+int check_tail(const std::string& w, int64_t B, int S_tot, int base_col, int k);      // a row of ADR_SCENARIO_TAIL_MAX
 
 // ---------------------------------------------------------------------------------------------------- tail allocation
 // What subbook.hip's allocation and tail_order.hip's ordered select share: the (key, index) pair and its order, the
@@ -165,7 +175,7 @@ void alloc_total_host(const double* rows, int64_t B, int S_tot, int base_col, do
 // components; `work` holds S_tot doubles; k and the width have been checked.  Three kernels on `stream`.
 hipError_t enqueue_alloc(const double* rows, int64_t B, int S_tot, int base_col, int k, double* var_tot, double* es_tot,
                          double* comp_var, double* comp_es, double* work, hipStream_t stream);
-int check_alloc(const std::string& w, int64_t B, int S_tot, int base_col, int k);
+int check_alloc(const std::string& w, int64_t B, int S_tot, int base_col, int k);     // a row of ADR_SCENARIO_ALLOC_MAX
 
 }  // namespace sub
 }  // namespace adr

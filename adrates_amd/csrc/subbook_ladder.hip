@@ -155,7 +155,7 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Handles& h, int64_t B, con
     if (!out) return adr_set_error(ADR_ERR_INVALID, w + ": out is NULL");
     if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_subbook_ladders_work doubles are needed)");
     hipStream_t stream = nullptr;
-    const int rc = scen::target_stream(w, ctx, stream_or_null, &stream);
+    const int rc = call::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const CurveDev& cv = *h.cv;
     const int S = record_doubles(cv.Kc, rq.gamma);
@@ -270,21 +270,18 @@ int adr_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, const adr_trades* 
     rc = adr::sub::build_plan(w, h.tr->n, B, sub_off, plan);
     if (rc != ADR_OK) return rc;
     hipStream_t stream = nullptr;
-    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
+    rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the ladders, the scratch, the plan
     const int P = h.cv->P;
-    const size_t d = sizeof(double), n_out = static_cast<size_t>(B) * (1 + P + static_cast<size_t>(P) * P);
-    const size_t W = static_cast<size_t>(adr_subbook_ladders_work(curve, h.tr->n, B, req_mask, nullptr));
-    double* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (n_out + W + plan.size()) * d);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *dout = base, *dwork = dout + n_out;
-    int64_t* dplan = reinterpret_cast<int64_t*>(dwork + W);
-    e = hipMemcpyAsync(dplan, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+    double *dout, *dwork;
+    int64_t* dplan;
+    adr::call::Staging mem;                         // `plan` is uploaded from where it stands: it outlives finish()
+    mem.out(&dout, out, static_cast<size_t>(B) * (1 + P + static_cast<size_t>(P) * P));
+    mem.scratch(&dwork, static_cast<size_t>(adr_subbook_ladders_work(curve, h.tr->n, B, req_mask, nullptr)));
+    mem.in(&dplan, plan.data(), plan.size());
+    const hipError_t e = mem.begin(stream);
     if (e == hipSuccess) rc = SL::enqueue(w, ctx, h, B, dplan, rq, dout, dwork, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, n_out * d, hipMemcpyDeviceToHost, stream);
-    return adr::scen::finish_blocking(w, rc, e, stream, base);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_subbook_ladders_host(int interp_method, int K, int P, const double* times, const double* dfs, const double* jac,

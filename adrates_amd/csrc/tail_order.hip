@@ -147,20 +147,18 @@ int adr_scenario_tail_alloc_select(adr_ctx* ctx, int64_t B, int S_tot, const dou
     hipStream_t stream = nullptr;
     rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the rows, the two totals and the two component vectors, the scratch
-    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot, nb = static_cast<size_t>(B);
-    const size_t work_at = ((R + 2 + 2 * nb) * d + 15) / 16 * 16;
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), work_at + TO::alloc_layout(S_tot, k).bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *drows = reinterpret_cast<double*>(base), *dtot = drows + R, *dcv = dtot + 2, *dce = dcv + nb;
-    e = hipMemcpyAsync(drows, rows, R * d, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) rc = TO::enqueue_alloc_select(w, drows, B, S_tot, base_col, k, dtot, dtot + 1, dcv, dce, base + work_at, stream);
-    double totals[2] = {0.0, 0.0};
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(totals, dtot, 2 * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(comp_var, dcv, nb * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(comp_es, dce, nb * d, hipMemcpyDeviceToHost, stream);
-    rc = adr::call::finish_blocking(w, rc, e, stream, base);
+    double totals[2] = {0.0, 0.0};                  // the caller's two are written only by a call that succeeds
+    double *drows, *dtot, *dcv, *dce;
+    void* dwork;
+    adr::call::Staging mem;
+    mem.in(&drows, rows, static_cast<size_t>(B) * S_tot);
+    mem.out(&dtot, totals, 2);
+    mem.out(&dcv, comp_var, B);
+    mem.out(&dce, comp_es, B);
+    mem.scratch_bytes(&dwork, TO::alloc_layout(S_tot, k).bytes);
+    const hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) rc = TO::enqueue_alloc_select(w, drows, B, S_tot, base_col, k, dtot, dtot + 1, dcv, dce, dwork, stream);
+    rc = mem.finish(w, rc, e, stream);
     if (rc == ADR_OK) {
         *var_tot = totals[0];
         *es_tot = totals[1];

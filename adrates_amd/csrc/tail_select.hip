@@ -314,48 +314,54 @@ __global__ __launch_bounds__(1024) void order_sort_kernel(const KeyIdx* pairs_al
 }
 
 // -------------------------------------------------------------------------------------------------------------- host
-// k_max pairs or values of a tail fit the LDS; `limit` names that bound in the refusal.
-static int check_sizes(const std::string& w, int64_t B, int S_tot, int base_col, int k, int k_max, const char* limit) {
-    if (B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one row is needed");
-    if (S_tot < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one column is needed");
-    if (base_col < -1 || base_col >= S_tot)
-        return adr_set_error(ADR_ERR_INVALID, w + ": base_col must be -1 (the rows are P&L) or a column, 0 .. " +
-                                                  std::to_string(S_tot - 1));
-    const int m = base_col >= 0 ? S_tot - 1 : S_tot;
-    if (m < 1) return adr_set_error(ADR_ERR_INVALID, w + ": no P&L value is left beside the base column");
-    if (k < 1 || k > m)
-        return adr_set_error(ADR_ERR_INVALID, w + ": k must lie in 1 .. " + std::to_string(m) + " (the P&L values per row)");
-    if (k > k_max)
-        return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": a tail of " + std::to_string(k) + " P&L values; a tail of at most " + limit +
-                                                  " fits the LDS");
-    return ADR_OK;
-}
+// The limit of both is on the tail: its k values, or its k (key, index) pairs, are sorted in LDS.
 int check(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
-    return check_sizes(w, B, S_tot, base_col, k, ADR_SCENARIO_TAIL_MAX, "ADR_SCENARIO_TAIL_MAX (16384)");
+    return sub::check_sizes(w, B, S_tot, base_col, k,
+                            sub::TailLimit{true, ADR_SCENARIO_TAIL_MAX, "a tail of ",
+                                           " P&L values; a tail of at most ADR_SCENARIO_TAIL_MAX (16384) fits the LDS"});
 }
 int check_order(const std::string& w, int64_t B, int S_tot, int base_col, int k) {
-    return check_sizes(w, B, S_tot, base_col, k, ADR_SCENARIO_ALLOC_MAX, "ADR_SCENARIO_ALLOC_MAX (8192) (key, index) pairs");
+    return sub::check_sizes(w, B, S_tot, base_col, k,
+                            sub::TailLimit{true, ADR_SCENARIO_ALLOC_MAX, "a tail of ",
+                                           " P&L values; a tail of at most ADR_SCENARIO_ALLOC_MAX (8192) (key, index) pairs fits the LDS"});
 }
 
-// The chain on `stream`; every pointer is device memory, `work` holds layout(B, S_tot, k).bytes.
-int enqueue(const std::string& w, const double* rows, int64_t B, int S_tot, int base_col, int k, double* var, double* es, void* work,
-            hipStream_t stream) {
+// What both selects start with: the refusal of a grid past 2^31, the kernels' arguments over `work` (the histograms at
+// `hist_at`; `tail` is null for the ordered select) and the six rounds that leave every row's threshold key in its state.
+int check_grid(const std::string& w, int64_t B, int S_tot) {
+    if (B * segments(B, S_tot) > INT32_MAX) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 2^31 (row, segment) pairs in one launch");
+    return ADR_OK;
+}
+inline Args args_over(const double* rows, int64_t B, int S_tot, int base_col, int k, char* work, size_t hist_at, double* tail) {
     const int nseg = segments(B, S_tot);
-    if (B * nseg > INT32_MAX) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 2^31 (row, segment) pairs in one launch");
-    const Layout l = layout(B, S_tot, k);
-    char* base = static_cast<char*>(work);
-    Args a{rows, reinterpret_cast<RowState*>(base), reinterpret_cast<uint32_t*>(base + l.hist), reinterpret_cast<double*>(base + l.tail),
-           S_tot, base_col, base_col >= 0 ? S_tot - 1 : S_tot, k, nseg, segment_len(S_tot, nseg)};
-    const dim3 grid(static_cast<unsigned>(B * nseg)), rows_grid(static_cast<unsigned>(B)), block(kThreads);
-    hipError_t e = hipMemsetAsync(a.state, 0, l.hist, stream);
+    return Args{rows, reinterpret_cast<RowState*>(work), reinterpret_cast<uint32_t*>(work + hist_at), tail,
+                S_tot, base_col, base_col >= 0 ? S_tot - 1 : S_tot, k, nseg, segment_len(S_tot, nseg)};
+}
+inline dim3 pairs_grid(int64_t B, const Args& a) { return dim3(static_cast<unsigned>(B * a.nseg)); }
+hipError_t enqueue_rounds(const Args& a, int64_t B, hipStream_t stream) {
+    const dim3 grid = pairs_grid(B, a), rows_grid(static_cast<unsigned>(B)), block(kThreads);
+    hipError_t e = hipMemsetAsync(a.state, 0, static_cast<size_t>(B) * sizeof(RowState), stream);
     for (int r = 0; r < kRounds && e == hipSuccess; ++r) {
         if (r == 0) hipLaunchKernelGGL(select_count_kernel<true>, grid, block, 0, stream, a, r);
         else hipLaunchKernelGGL(select_count_kernel<false>, grid, block, 0, stream, a, r);
         hipLaunchKernelGGL(select_scan_kernel, rows_grid, block, 0, stream, a, r);
         e = hipGetLastError();
     }
+    return e;
+}
+
+// The chain on `stream`; every pointer is device memory, `work` holds layout(B, S_tot, k).bytes.
+int enqueue(const std::string& w, const double* rows, int64_t B, int S_tot, int base_col, int k, double* var, double* es, void* work,
+            hipStream_t stream) {
+    const int rc = check_grid(w, B, S_tot);
+    if (rc != ADR_OK) return rc;
+    const Layout l = layout(B, S_tot, k);
+    char* base = static_cast<char*>(work);
+    const Args a = args_over(rows, B, S_tot, base_col, k, base, l.hist, reinterpret_cast<double*>(base + l.tail));
+    const dim3 block(kThreads);
+    hipError_t e = enqueue_rounds(a, B, stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(select_gather_kernel, grid, block, 0, stream, a);
+        hipLaunchKernelGGL(select_gather_kernel, pairs_grid(B, a), block, 0, stream, a);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = sub::enqueue_tail(a.tail, B, k, -1, k, var, es, stream);
@@ -368,38 +374,28 @@ int enqueue(const std::string& w, const double* rows, int64_t B, int S_tot, int 
     return ADR_OK;
 }
 
-// work of the ordered select: state[B] | hist[B][nseg][kBins] uint32 | (to a multiple of 16) pairs[B][k]
-struct OrderLayout {
-    size_t hist, pairs, bytes;
-};
-inline OrderLayout order_layout(int64_t B, int S_tot, int k) {
-    OrderLayout l;
-    l.hist = static_cast<size_t>(B) * sizeof(RowState);
-    l.pairs = (l.hist + static_cast<size_t>(B) * segments(B, S_tot) * kBins * sizeof(uint32_t) + 15) / 16 * 16;
-    l.bytes = l.pairs + static_cast<size_t>(B) * k * sizeof(KeyIdx);
+// work of the ordered select: state[B] | hist[B][nseg][kBins] uint32 | (to a multiple of 16) pairs[B][k].  Layout's
+// `tail` is where the pairs start.
+inline Layout order_layout(int64_t B, int S_tot, int k) {
+    Layout l = layout(B, S_tot, 0);
+    l.tail = (l.tail + 15) / 16 * 16;
+    l.bytes = l.tail + static_cast<size_t>(B) * k * sizeof(KeyIdx);
     return l;
 }
 size_t order_work_bytes(int64_t B, int S_tot, int k) { return order_layout(B, S_tot, k).bytes; }
 
 int enqueue_order(const std::string& w, const double* rows, int64_t B, int S_tot, int base_col, int k, int64_t* order, double* var,
                   double* es, void* work, hipStream_t stream) {
-    const int nseg = segments(B, S_tot);
-    if (B * nseg > INT32_MAX) return adr_set_error(ADR_ERR_UNSUPPORTED, w + ": more than 2^31 (row, segment) pairs in one launch");
-    const OrderLayout l = order_layout(B, S_tot, k);
+    const int rc = check_grid(w, B, S_tot);
+    if (rc != ADR_OK) return rc;
+    const Layout l = order_layout(B, S_tot, k);
     char* base = static_cast<char*>(work);
-    Args a{rows, reinterpret_cast<RowState*>(base), reinterpret_cast<uint32_t*>(base + l.hist), nullptr,
-           S_tot, base_col, base_col >= 0 ? S_tot - 1 : S_tot, k, nseg, segment_len(S_tot, nseg)};
-    KeyIdx* pairs = reinterpret_cast<KeyIdx*>(base + l.pairs);
-    const dim3 grid(static_cast<unsigned>(B * nseg)), rows_grid(static_cast<unsigned>(B)), block(kThreads);
-    hipError_t e = hipMemsetAsync(a.state, 0, l.hist, stream);
-    for (int r = 0; r < kRounds && e == hipSuccess; ++r) {
-        if (r == 0) hipLaunchKernelGGL(select_count_kernel<true>, grid, block, 0, stream, a, r);
-        else hipLaunchKernelGGL(select_count_kernel<false>, grid, block, 0, stream, a, r);
-        hipLaunchKernelGGL(select_scan_kernel, rows_grid, block, 0, stream, a, r);
-        e = hipGetLastError();
-    }
+    const Args a = args_over(rows, B, S_tot, base_col, k, base, l.hist, nullptr);
+    const dim3 rows_grid(static_cast<unsigned>(B)), block(kThreads);
+    KeyIdx* pairs = reinterpret_cast<KeyIdx*>(base + l.tail);
+    hipError_t e = enqueue_rounds(a, B, stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(order_gather_kernel, grid, block, 0, stream, a, pairs);
+        hipLaunchKernelGGL(order_gather_kernel, pairs_grid(B, a), block, 0, stream, a, pairs);
         e = hipGetLastError();
     }
     const int P = sub::pow2_at_least(k);
@@ -477,18 +473,16 @@ int adr_scenario_tail_select(adr_ctx* ctx, int64_t B, int S_tot, const double* r
     hipStream_t stream = nullptr;
     rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the rows, var and es, the scratch
-    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot, nb = static_cast<size_t>(B);
-    const size_t head = (R + 2 * nb) * d, work_at = (head + 15) / 16 * 16;
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), work_at + TS::layout(B, S_tot, k).bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double *drows = reinterpret_cast<double*>(base), *dvar = drows + R, *des = dvar + nb;
-    e = hipMemcpyAsync(drows, rows, R * d, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) rc = TS::enqueue(w, drows, B, S_tot, base_col, k, dvar, des, base + work_at, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(var, dvar, nb * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(es, des, nb * d, hipMemcpyDeviceToHost, stream);
-    return adr::call::finish_blocking(w, rc, e, stream, base);
+    double *drows, *dvar, *des;
+    void* dwork;
+    adr::call::Staging mem;
+    mem.in(&drows, rows, static_cast<size_t>(B) * S_tot);
+    mem.out(&dvar, var, B);
+    mem.out(&des, es, B);
+    mem.scratch_bytes(&dwork, TS::layout(B, S_tot, k).bytes);
+    const hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) rc = TS::enqueue(w, drows, B, S_tot, base_col, k, dvar, des, dwork, stream);
+    return mem.finish(w, rc, e, stream);
 }
 
 int64_t adr_scenario_tail_order_work(int64_t B, int S_tot, int k) {
@@ -520,21 +514,18 @@ int adr_scenario_tail_order(adr_ctx* ctx, int64_t B, int S_tot, const double* ro
     hipStream_t stream = nullptr;
     rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the rows, the order, var and es, the scratch
-    const size_t d = sizeof(double), R = static_cast<size_t>(B) * S_tot, nb = static_cast<size_t>(B), nk = nb * k;
-    const size_t head = (R + nk + 2 * nb) * d, work_at = (head + 15) / 16 * 16;
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), work_at + TS::order_work_bytes(B, S_tot, k));
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double* drows = reinterpret_cast<double*>(base);
-    int64_t* dorder = reinterpret_cast<int64_t*>(drows + R);
-    double *dvar = drows + R + nk, *des = dvar + nb;
-    e = hipMemcpyAsync(drows, rows, R * d, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) rc = TS::enqueue_order(w, drows, B, S_tot, base_col, k, dorder, dvar, des, base + work_at, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(order, dorder, nk * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(var, dvar, nb * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(es, des, nb * d, hipMemcpyDeviceToHost, stream);
-    return adr::call::finish_blocking(w, rc, e, stream, base);
+    double *drows, *dvar, *des;
+    int64_t* dorder;
+    void* dwork;
+    adr::call::Staging mem;
+    mem.in(&drows, rows, static_cast<size_t>(B) * S_tot);
+    mem.out(&dorder, order, static_cast<size_t>(B) * k);
+    mem.out(&dvar, var, B);
+    mem.out(&des, es, B);
+    mem.scratch_bytes(&dwork, TS::order_work_bytes(B, S_tot, k));
+    const hipError_t e = mem.begin(stream);
+    if (e == hipSuccess) rc = TS::enqueue_order(w, drows, B, S_tot, base_col, k, dorder, dvar, des, dwork, stream);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_scenario_tail_order_host(int64_t B, int S_tot, const double* rows, int base_col, int k, int64_t* order, double* var, double* es) {

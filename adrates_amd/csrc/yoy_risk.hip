@@ -319,34 +319,27 @@ int adr_yoy_risk(adr_ctx* ctx, int disc_method, int K, const double* times, cons
     const bool per = req_mask & ADR_YOY_PER_SWAP, agg_on = req_mask & ADR_YOY_AGG;
     const bool wv = per && (req_mask & ADR_REQ_VALUE), wd = per && (req_mask & ADR_REQ_DELTA);
     const bool wg = per && (req_mask & ADR_REQ_GAMMA);
-    const int64_t PP = static_cast<int64_t>(P) * P, R = Y::row_len(P), W = adr_yoy_risk_work(n, P);
-    const size_t d = sizeof(double);
-    // one allocation: curves, coupons, outputs, scratch, then the offsets
-    const size_t n_dbl = 2 * static_cast<size_t>(K) + 2 * static_cast<size_t>(P) + ADR_YOY_FIELDS * static_cast<size_t>(m) +
-                         (amount ? m : 0) + (wv ? n : 0) + (wd ? n * P : 0) + (wg ? n * PP : 0) + (agg_on ? R + W : 0);
-    const size_t bytes = n_dbl * d + static_cast<size_t>(n + 1) * sizeof(int64_t);
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
-    double* p = reinterpret_cast<double*>(base);
-    auto take = [&p](int64_t count, bool on) { double* q = on ? p : nullptr; if (on) p += count; return q; };
-    double *dt = take(K, true), *ddf = take(K, true), *dT = take(P, true), *db = take(P, true);
-    double* dcpn = take(ADR_YOY_FIELDS * m, true);
-    double *damt = take(m, amount != nullptr), *dpv = take(n, wv), *ddl = take(n * P, wd), *dg = take(n * PP, wg);
-    double *dagg = take(R, agg_on), *dwork = take(W, agg_on);
-    int64_t* doff = reinterpret_cast<int64_t*>(p);
-    const adr::call::Piece in[] = {{dt, times, K * d}, {ddf, dfs, K * d}, {dT, T, P * d}, {db, b, P * d},
-                                   {dcpn, cpn, ADR_YOY_FIELDS * m * d},
-                                   {doff, cpn_off, n > 0 ? (n + 1) * sizeof(int64_t) : 0}};
-    const adr::call::Piece res[] = {{amount, damt, amount ? m * d : 0}, {pv, dpv, wv ? n * d : 0},
-                                    {delta, ddl, wd ? n * P * d : 0}, {gamma, dg, wg ? n * PP * d : 0},
-                                    {agg, dagg, agg_on ? R * d : 0}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
+    const size_t PP = static_cast<size_t>(P) * P;
+    double *dt, *ddf, *dT, *db, *dcpn, *damt, *dpv, *ddl, *dg, *dagg, *dwork;
+    int64_t* doff;
+    adr::call::Staging mem;
+    mem.in(&dt, times, K);
+    mem.in(&ddf, dfs, K);
+    mem.in(&dT, T, P);
+    mem.in(&db, b, P);
+    mem.in(&dcpn, cpn, ADR_YOY_FIELDS * static_cast<size_t>(m));
+    mem.in(&doff, cpn_off, n + 1, n > 0);           // null for an empty book
+    mem.out(&damt, amount, m, amount != nullptr);
+    mem.out(&dpv, pv, n, wv);
+    mem.out(&ddl, delta, n * P, wd);
+    mem.out(&dg, gamma, n * PP, wg);
+    mem.out(&dagg, agg, Y::row_len(P), agg_on);
+    mem.scratch(&dwork, adr_yoy_risk_work(n, P), agg_on);
+    const hipError_t e = mem.begin(stream);
     if (e == hipSuccess)
-        rc = adr_yoy_risk_dev(ctx, disc_method, K, dt, ddf, infl_method, P, dT, db, n, m, n > 0 ? doff : nullptr, dcpn,
-                              req_mask, damt, dpv, ddl, dg, dagg, dwork, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = adr::call::copy_pieces(res, hipMemcpyDeviceToHost, stream);
-    return adr::call::finish_blocking(who, rc, e, stream, base);
+        rc = adr_yoy_risk_dev(ctx, disc_method, K, dt, ddf, infl_method, P, dT, db, n, m, doff, dcpn, req_mask, damt, dpv, ddl, dg,
+                              dagg, dwork, stream);
+    return mem.finish(who, rc, e, stream);
 }
 
 int adr_yoy_risk_host(int disc_method, int K, const double* times, const double* dfs, int infl_method, int P,

@@ -354,7 +354,7 @@ int enqueue(const std::string& w, adr_ctx* ctx, const Call& c, double* work, hip
     if (subs && B < 1) return adr_set_error(ADR_ERR_INVALID, w + ": at least one sub-book is needed");
     if (subs && !plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
     hipStream_t stream = nullptr;
-    rc = target_stream(w, ctx, stream_or_null, &stream);
+    rc = call::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const int64_t chunks = subs ? sub::max_chunks(c.n, B, kChunk) : (c.n + kChunk - 1) / kChunk;
     dim3 grid;
@@ -417,42 +417,33 @@ int run_blocking(const std::string& w, adr_ctx* ctx, const Call& h, int64_t B = 
         if (rc != ADR_OK) return rc;
     }
     hipStream_t stream = nullptr;
-    rc = target_stream(w, ctx, nullptr, &stream);
+    rc = call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: curves, flows, outputs, scratch, then the plan and the two offset arrays
     const int K = h.K, P = h.P, S = h.S;
     const int64_t n = h.n;
     const size_t rows = B > 0 ? static_cast<size_t>(B) : 1;
-    const size_t d = sizeof(double), SK = static_cast<size_t>(h.S_disc) * K, SP = static_cast<size_t>(h.S_infl) * P;
-    const size_t W = static_cast<size_t>(B > 0 ? adr_scenario_subbook_work(n, B, S) : adr_yoy_scenario_pv_work(n, S));
-    const size_t NS = static_cast<size_t>(n) * S, mf = static_cast<size_t>(h.mf), mc = ADR_YOY_FIELDS * static_cast<size_t>(h.m);
-    const size_t n_dbl = K + SK + P + SP + 2 * mf + mc + (h.pv ? NS : 0) + rows * S + W;
-    const size_t off_bytes = static_cast<size_t>(n + 1) * sizeof(int64_t), plan_bytes = plan.size() * sizeof(int64_t);
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), n_dbl * d + plan_bytes + 2 * off_bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double* p = reinterpret_cast<double*>(base);
-    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
-    double *dt = take(K), *ddf = take(SK), *dT = take(P), *db = take(SP);
-    double *dftp = take(mf), *dfpay = take(mf), *dcpn = take(mc);
-    double* dpv = h.pv ? take(NS) : nullptr;
-    double *dbook = take(rows * S), *dwork = take(W);
-    int64_t* dplan = reinterpret_cast<int64_t*>(p);
-    int64_t* dfo = dplan + plan.size();
-    int64_t* dco = dfo + (n + 1);
-    struct Piece { void* dst; const void* src; size_t bytes; };
-    const Piece in[] = {{dt, h.times, K * d}, {ddf, h.dfs, SK * d}, {dT, h.T, P * d}, {db, h.b, SP * d},
-                        {dftp, h.fix_tp, mf * d}, {dfpay, h.fix_pay, mf * d}, {dcpn, h.cpn, mc * d},
-                        {dplan, plan.data(), plan_bytes}, {dfo, h.fix_off, off_bytes}, {dco, h.cpn_off, off_bytes}};
-    for (const Piece& pc : in)
-        if (e == hipSuccess && pc.bytes) e = hipMemcpyAsync(pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice, stream);
+    double *dt, *ddf, *dT, *db, *dftp, *dfpay, *dcpn, *dpv, *dbook, *dwork;
+    int64_t *dplan, *dfo, *dco;
+    call::Staging mem;                              // `plan` is uploaded from where it stands: it outlives finish()
+    mem.in(&dt, h.times, K);
+    mem.in(&ddf, h.dfs, static_cast<size_t>(h.S_disc) * K);
+    mem.in(&dT, h.T, P);
+    mem.in(&db, h.b, static_cast<size_t>(h.S_infl) * P);
+    mem.in(&dftp, h.fix_tp, h.mf);
+    mem.in(&dfpay, h.fix_pay, h.mf);
+    mem.in(&dcpn, h.cpn, ADR_YOY_FIELDS * static_cast<size_t>(h.m));
+    mem.in(&dplan, plan.data(), plan.size());
+    mem.in(&dfo, h.fix_off, n + 1);
+    mem.in(&dco, h.cpn_off, n + 1);
+    mem.out(&dpv, h.pv, static_cast<size_t>(n) * S, h.pv != nullptr);
+    mem.out(&dbook, h.book, rows * S);
+    mem.scratch(&dwork, static_cast<size_t>(B > 0 ? adr_scenario_subbook_work(n, B, S) : adr_yoy_scenario_pv_work(n, S)));
+    const hipError_t e = mem.begin(stream);
     if (e == hipSuccess) {
         const Call c{h.dm, K, dt, h.S_disc, ddf, h.im, P, dT, h.S_infl, db, S, n, h.mf, dfo, dftp, dfpay, h.m, dco, dcpn, dpv, dbook};
-        rc = enqueue(w, ctx, c, dwork, stream, B, B > 0 ? dplan : nullptr);
+        rc = enqueue(w, ctx, c, dwork, stream, B, dplan);
     }
-    if (e == hipSuccess && rc == ADR_OK && h.pv) e = hipMemcpyAsync(h.pv, dpv, NS * d, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(h.book, dbook, rows * S * d, hipMemcpyDeviceToHost, stream);
-    return finish_blocking(w, rc, e, stream, base);
+    return mem.finish(w, rc, e, stream);
 }
 
 // The host entries' body; B > 0: c.book is sub_pv[B][S] of the sub-books sub_off.

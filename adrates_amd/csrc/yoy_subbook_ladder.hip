@@ -349,7 +349,7 @@ int enqueue(const std::string& w, adr_ctx* ctx, const CurveDev& cv, const InflCu
     if (!plan) return adr_set_error(ADR_ERR_INVALID, w + ": the sub-book plan is NULL (adr_scenario_subbook_plan fills it)");
     if (!work) return adr_set_error(ADR_ERR_INVALID, w + ": work is NULL (adr_yoy_subbook_ladders_work doubles are needed)");
     hipStream_t stream = nullptr;
-    const int rc = scen::target_stream(w, ctx, stream_or_null, &stream);
+    const int rc = call::target_stream(w, ctx, stream_or_null, &stream);
     if (rc != ADR_OK) return rc;
     const int S = record_doubles(cv.Kc, ic.P, rq.gamma);
     const int64_t cap = sub::max_chunks(bk.n, B, kChunk);
@@ -444,31 +444,27 @@ int adr_yoy_subbook_ladders(adr_ctx* ctx, const adr_curve* curve, int infl_metho
     rc = adr::sub::build_plan(w, n, B, sub_off, plan);
     if (rc != ADR_OK) return rc;
     hipStream_t stream = nullptr;
-    rc = adr::scen::target_stream(w, ctx, nullptr, &stream);
+    rc = adr::call::target_stream(w, ctx, nullptr, &stream);
     if (rc != ADR_OK) return rc;
-    // one allocation: the ladders, the scratch, the inflation curve, the flows, then the plan and the two offset arrays
     const int Q = cv->P + P_i;
-    const size_t d = sizeof(double), n_out = static_cast<size_t>(B) * (1 + Q + static_cast<size_t>(Q) * Q);
-    const size_t W = static_cast<size_t>(YL::work_doubles(cv->Kc, P_i, n, B, rq.gamma, nullptr));
-    const size_t Pi = static_cast<size_t>(P_i), nf = static_cast<size_t>(n_fix), mc = ADR_YOY_FIELDS * static_cast<size_t>(m);
-    const size_t off_bytes = static_cast<size_t>(n + 1) * sizeof(int64_t), plan_bytes = plan.size() * sizeof(int64_t);
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), (n_out + W + 2 * Pi + 2 * nf + mc) * d + plan_bytes + 2 * off_bytes);
-    if (e != hipSuccess) return adr_set_error(ADR_ERR_HIP, w + ": hipMalloc: " + hipGetErrorString(e));
-    double* p = reinterpret_cast<double*>(base);
-    auto take = [&p](size_t count) { double* q = p; p += count; return q; };
-    double *dout = take(n_out), *dwork = take(W), *dT = take(Pi), *db = take(Pi), *dftp = take(nf), *dfpay = take(nf), *dcpn = take(mc);
-    int64_t* dplan = reinterpret_cast<int64_t*>(p);
-    int64_t *dfo = dplan + plan.size(), *dco = dfo + (n + 1);
-    const adr::call::Piece in[] = {{dT, T, Pi * d}, {db, b, Pi * d}, {dftp, fix_tp, nf * d}, {dfpay, fix_pay, nf * d},
-                                   {dcpn, cpn, mc * d}, {dplan, plan.data(), plan_bytes}, {dfo, fix_off, off_bytes},
-                                   {dco, cpn_off, off_bytes}};
-    e = adr::call::copy_pieces(in, hipMemcpyHostToDevice, stream);
+    double *dout, *dwork, *dT, *db, *dftp, *dfpay, *dcpn;
+    int64_t *dplan, *dfo, *dco;
+    adr::call::Staging mem;                         // `plan` is uploaded from where it stands: it outlives finish()
+    mem.out(&dout, out, static_cast<size_t>(B) * (1 + Q + static_cast<size_t>(Q) * Q));
+    mem.scratch(&dwork, static_cast<size_t>(YL::work_doubles(cv->Kc, P_i, n, B, rq.gamma, nullptr)));
+    mem.in(&dT, T, P_i);
+    mem.in(&db, b, P_i);
+    mem.in(&dftp, fix_tp, n_fix);
+    mem.in(&dfpay, fix_pay, n_fix);
+    mem.in(&dcpn, cpn, ADR_YOY_FIELDS * static_cast<size_t>(m));
+    mem.in(&dplan, plan.data(), plan.size());
+    mem.in(&dfo, fix_off, n + 1);
+    mem.in(&dco, cpn_off, n + 1);
+    const hipError_t e = mem.begin(stream);
     if (e == hipSuccess)
         rc = YL::enqueue(w, ctx, *cv, YL::InflCurve{infl_method, P_i, dT, db}, YL::Book{n, n_fix, m, dfo, dftp, dfpay, dco, dcpn}, B,
                          dplan, rq, dout, dwork, stream);
-    if (e == hipSuccess && rc == ADR_OK) e = hipMemcpyAsync(out, dout, n_out * d, hipMemcpyDeviceToHost, stream);
-    return adr::scen::finish_blocking(w, rc, e, stream, base);
+    return mem.finish(w, rc, e, stream);
 }
 
 int adr_yoy_subbook_ladders_host(int interp_method, int K, int P, const double* times, const double* dfs, const double* jac,

@@ -65,6 +65,17 @@ def test_geometry_bit_for_bit(gpu_ctx, P):
         assert_same(*both(gpu_ctx, ladders[:9], shocks[:65], want), f"P = {P}, outputs {want}")
 
 
+def test_every_subset_of_the_outputs_on_two_desks(gpu_ctx):
+    """B = 2, P = 3, S = 5: the blocking entry stages only the outputs asked for, so every subset of the three is a device
+    allocation of its own shape.  Each against the twin, bit for bit."""
+    ladders, shocks = C.table(3, 5, 2)
+    for bits in range(1, 8):
+        want = (bool(bits & 1), bool(bits & 2), bool(bits & 4))
+        dev, twin = both(gpu_ctx, ladders, shocks, want)
+        assert len(dev) == sum(want), want
+        assert_same(dev, twin, f"outputs {want}")
+
+
 def test_exact_cases_on_the_device(gpu_ctx):
     P, S, B = 33, 65, 9
     ladders, shocks = C.table(P, S, B, seed=1)

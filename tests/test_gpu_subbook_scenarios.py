@@ -5,7 +5,8 @@ import pytest
 import torch
 
 from adrates_amd import _native
-from adrates_amd.market.position.scenarios import ScenarioGrid, expected_shortfall, historical_var, tail_count, tail_measures
+from adrates_amd.market.position.scenarios import (ScenarioGrid, expected_shortfall, historical_var,
+                                                   revalue_credit_on_curves_sub_books, tail_count, tail_measures)
 from adrates_amd.utils.error import LibError
 
 from . import _credit_scenario_cases as CC
@@ -239,6 +240,66 @@ def test_tail_kernel(gpu_ctx):
         _native.scenario_tail(gpu_ctx, wide, 3)
     var, es = tail_measures(wide, 0.99, ctx=gpu_ctx)                      # falls back to NumPy per row
     assert var[1] == historical_var(wide[1], 0.99) and es[1] == expected_shortfall(wide[1], 0.99)
+
+
+def test_var_es_entry_is_the_tail_of_the_sub_book_rows(gpu_ctx, curves):
+    """adr_scenario_subbook_var_es, whose rows stay on the device, against adr_scenario_tail on the rows that
+    adr_scenario_subbook_pv downloads: the same kernels on the same bits.  One sub-book and three, the rows as P&L and
+    against a base column."""
+    times, dfs = curves
+    batch = SB.take(SB.sized_book(), 0, 130)
+    dev = _native.DeviceTrades(gpu_ctx, batch)
+    try:
+        for sub_off in ([0, 130], [0, 1, 64, 130]):
+            rows = _native.scenario_subbook_pv(gpu_ctx, 4, times, dfs, dev, sub_off)["sub_pv"]
+            for base_col, k in ((-1, 1), (-1, 3), (0, 2), (dfs.shape[0] - 1, dfs.shape[0] - 1)):
+                var, es = _native.scenario_subbook_var_es(gpu_ctx, 4, times, dfs, dev, sub_off, k, base_col)
+                tv, te = _native.scenario_tail(gpu_ctx, rows, k, base_col)
+                assert var.shape == (len(sub_off) - 1,), (sub_off, base_col, k)
+                assert np.array_equal(var.view(np.int64), tv.view(np.int64)), (sub_off, base_col, k)
+                assert np.array_equal(es.view(np.int64), te.view(np.int64)), (sub_off, base_col, k)
+    finally:
+        dev.close()
+
+
+def test_grid_revalue_credit_sub_books_reads_the_set_in_place(gpu_ctx):
+    """`ScenarioGrid.revalue_credit_sub_books` (adr_credit_scenario_subbook_pv_set: the grid's curves read where the device
+    builder left them) against adr_credit_scenario_subbook_pv on the same rows uploaded from the host - the same bits - and
+    against the host twin within REL_TOL of the sub-book's gross notional.  One sub-book and three, with and without the
+    per-trade rows; one sub-book is `revalue_credit`'s book."""
+    model = F.gbp_model(VD)
+    mixed, _ = _mixed_list()
+    swaps = {id(t) for t in [t for t in mixed if type(t).__name__ == "OIS"][:16]}
+    trades = [t for t in mixed if type(t).__name__ != "OIS" or id(t) in swaps]               # 24 bonds and FRNs among 16 swaps
+    n = len(trades)
+    spreads = [0.0 if type(t).__name__ == "OIS" else 0.004 + 0.0001 * (i % 7) for i, t in enumerate(trades)]
+    buckets = [None if type(t).__name__ == "OIS" else ("AA", "B")[i % 2] for i, t in enumerate(trades)]
+    assert any(b is not None for b in buckets)
+    shocks = [0.0, 0.01, -0.5, 2.0, {"5Y": 0.25}]
+    dz = np.linspace(0.0, 0.002, 10).reshape(5, 2)
+    grid = ScenarioGrid(model, "GBP_OIS_SONIA", shocks, with_gamma=False, ctx=gpu_ctx)
+    try:
+        method, times, dfs = grid.curve._interp_type.value, grid.base.times, grid._dfs()
+        for keys in (["all"] * n, [f"desk {3 * i // n}" for i in range(n)]):
+            B = len(set(keys))
+            for per_trade in (False, True):
+                got = grid.revalue_credit_sub_books(trades, spreads, keys, buckets, dz, per_trade=per_trade)
+                up = revalue_credit_on_curves_sub_books(method, times, dfs, dz, trades, spreads, buckets, keys, VD,
+                                                        per_trade=per_trade, ctx=gpu_ctx)
+                assert got["labels"] == up["labels"] and got["sub_pv"].shape == (B, 5) and ("pv" in got) == per_trade
+                assert np.array_equal(got["sub_pv"].view(np.int64), up["sub_pv"].view(np.int64)), (B, per_trade)
+                if per_trade:
+                    assert got["pv"].shape == (5, n) and np.array_equal(got["pv"].view(np.int64), up["pv"].view(np.int64)), B
+            host = revalue_credit_on_curves_sub_books(method, times, dfs, dz, trades, spreads, buckets, keys, VD, host=True)
+            notional = np.array([abs(float(getattr(t, "_face_value", None) or t._notional)) for t in trades])
+            gross = np.array([notional[[k == lab for k in keys]].sum() for lab in got["labels"]])
+            err = np.max(np.abs(got["sub_pv"] - host["sub_pv"]) / gross[:, None])
+            print(f"revalue_credit_sub_books against the host twin, B = {B}: {err:.2e}")
+            assert err <= REL_TOL
+        one = grid.revalue_credit_sub_books(trades, spreads, ["all"] * n, buckets, dz)["sub_pv"][0]
+        assert np.array_equal(one, grid.revalue_credit(trades, spreads, buckets, dz)["book_pv"])
+    finally:
+        grid.close()
 
 
 def test_grid_methods(gpu_ctx):

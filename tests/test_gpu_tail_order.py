@@ -220,6 +220,22 @@ def test_alloc_select_on_tied_totals(gpu_ctx):
         assert T.same_alloc(_native.scenario_tail_alloc_select(gpu_ctx, rows, k), _allocate_tail_numpy(rows, k, -1)), k
 
 
+# ------------------------------------------------------------------------------------------------ the blocking entries
+@pytest.mark.parametrize("base_col", (-1, 0, 129))
+def test_blocking_tail_entries_on_three_rows(gpu_ctx, base_col):
+    """The five blocking tail entries on three rows of 130 columns with k = 2: an odd row count, so var, es and the
+    components do not fill whole 16-byte units of the call's one device allocation.  Each against its host twin, bit for
+    bit."""
+    rows, k = T.alloc_matrix(3, 130), 2
+    for name in ("scenario_tail", "scenario_tail_select"):
+        dev, twin = getattr(_native, name)(gpu_ctx, rows, k, base_col), getattr(_native, name + "_host")(rows, k, base_col)
+        assert C.same_bits(dev[0], twin[0]) and C.same_bits(dev[1], twin[1]), name
+    assert T.same_order(_native.scenario_tail_order(gpu_ctx, rows, k, base_col), _native.scenario_tail_order_host(rows, k, base_col))
+    for name in ("scenario_tail_alloc", "scenario_tail_alloc_select"):
+        dev, twin = getattr(_native, name)(gpu_ctx, rows, k, base_col), getattr(_native, name + "_host")(rows, k, base_col)
+        assert T.same_alloc(dev, twin), name
+
+
 # -------------------------------------------------------------------------------------------------------------- chain
 @pytest.mark.parametrize("P", [9, 32])
 def test_chain_contracts(gpu_ctx, P):
