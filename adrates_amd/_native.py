@@ -113,6 +113,17 @@ _SIGNATURES = {
                                           C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "adr_yoy_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int,
                                            C.c_int64, C.c_int64, _i64p, _dp, _dp, C.c_int64, _i64p, _dp, _dp, _dp, C.c_int]),
+    "adr_xccy_scenario_pv": (C.c_int, [_vp] + [C.c_int, C.c_int, _dp, C.c_int, _dp] * 2 + [C.c_int, _vp, _dp, _dp]),
+    "adr_xccy_scenario_pv_work": (C.c_int64, [C.c_int64, C.c_int]),
+    "adr_xccy_scenario_pv_dev": (C.c_int, [_vp] + [C.c_int, C.c_int, _vp, C.c_int, _vp] * 2 + [C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "adr_xccy_scenario_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp] * 2 + [C.c_int, C.c_int64, _i64p, _i64p] +
+                                  [_dp] * 11 + [_dp, _dp, C.c_int]),
+    "adr_xccy_scenario_subbook_pv": (C.c_int, [_vp] + [C.c_int, C.c_int, _dp, C.c_int, _dp] * 2 +
+                                     [C.c_int, _vp, C.c_int64, _i64p, _dp, _dp]),
+    "adr_xccy_scenario_subbook_pv_dev": (C.c_int, [_vp] + [C.c_int, C.c_int, _vp, C.c_int, _vp] * 2 +
+                                         [C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "adr_xccy_scenario_subbook_pv_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp] * 2 + [C.c_int, C.c_int64, _i64p, _i64p] +
+                                          [_dp] * 11 + [C.c_int64, _i64p, _dp, _dp, C.c_int]),
     "adr_credit_scenario_pv": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _vp, _dp,
                                          _i32p, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp]),
     "adr_credit_scenario_pv_set": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _vp, _dp, _i32p, C.c_int64, _dp, C.c_int64, _dp,
@@ -1118,6 +1129,65 @@ def yoy_scenario_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: int, inf
                                           _dev(book_ptr), _dev(work_ptr), _vp(stream or None)), "adr_yoy_scenario_pv_dev")
 
 
+def _xccy_scenario_curves(times_f, dfs_f, times_x, dfs_x):
+    """The two curve groups of adr_xccy_scenario_pv from ``dfs_f`` [S, K_f] or [K_f] and ``dfs_x`` [S, K_x] or [K_x], and S."""
+    times_f, dfs_f = _scenario_curves(times_f, dfs_f)
+    times_x, dfs_x = _scenario_curves(times_x, dfs_x)
+    S = max(dfs_f.shape[0], dfs_x.shape[0])
+    if dfs_f.shape[0] not in (1, S) or dfs_x.shape[0] not in (1, S):
+        raise LibError(f"{dfs_f.shape[0]} foreign rows and {dfs_x.shape[0]} XCCY rows: each must be one shared row or one row per "
+                       "scenario")
+    return times_f, dfs_f, times_x, dfs_x, S
+
+
+def _xccy_scenario_call(fn, head, trades, tail, for_method, times_f, dfs_f, x_method, times_x, dfs_x, n, per_trade, *sub_off):
+    """The four blocking and host XCCY entries: ``head`` the context or nothing, ``trades`` the handle or the host arrays,
+    ``tail`` ``n_threads`` or nothing, ``sub_off`` given for the sub-book entries."""
+    times_f, dfs_f, times_x, dfs_x, S = _xccy_scenario_curves(times_f, dfs_f, times_x, dfs_x)
+    sub = _sub_offsets(*sub_off) if sub_off else None
+    args = [*head, *_curve_args(for_method, times_f, dfs_f), *_curve_args(x_method, times_x, dfs_x), S, *trades]
+    return _scenario_call(fn, args, n, S, per_trade, sub, tail)
+
+
+def xccy_scenario_pv(ctx: Context, for_method: int, times_f, dfs_f, x_method: int, times_x, dfs_x, legs: DeviceTrades,
+                     per_trade=False):
+    """PVs of the foreign legs of a cross-currency book under scenario PAIRS (adr_xccy_scenario_pv, blocking): foreign OIS
+    rows ``dfs_f`` [S, K_f] or one shared row on the knots ``times_f`` (the forwards), XCCY rows ``dfs_x`` [S, K_x] or one
+    shared row on ``times_x`` (the discount factors); ``legs``: the uploaded foreign-leg batch (`compile_xccy_legs`).
+    Returns ``book_pv`` [S] and, with ``per_trade``, ``pv`` [S, n], in FOREIGN currency."""
+    return _xccy_scenario_call(load().adr_xccy_scenario_pv, (ctx._h,), (legs._h,), (), for_method, times_f, dfs_f, x_method,
+                               times_x, dfs_x, legs.n_trades, per_trade)
+
+
+def xccy_scenario_pv_host(for_method: int, times_f, dfs_f, x_method: int, times_x, dfs_x, batch, per_trade=False, n_threads=0):
+    """`xccy_scenario_pv` on the CPU (adr_xccy_scenario_pv_host) for a `TradeBatch`: the same per-coupon arithmetic and the
+    same order of the book sum; no GPU needed."""
+    arrays = _batch_arrays(batch)
+    return _xccy_scenario_call(load().adr_xccy_scenario_pv_host, (), _batch_args(*arrays), (int(n_threads),), for_method, times_f,
+                               dfs_f, x_method, times_x, dfs_x, arrays[0], per_trade)
+
+
+def xccy_scenario_pv_work(n_trades: int, n_scenarios: int) -> int:
+    """Doubles of scratch `xccy_scenario_pv_dev` needs."""
+    return int(load().adr_xccy_scenario_pv_work(int(n_trades), int(n_scenarios)))
+
+
+def _xccy_dev_curves(for_method, K_f, S_f, x_method, K_x, S_x, ptrs):
+    g = _dev_of(ptrs)
+    return [int(for_method), int(K_f), g("times_f"), int(S_f), g("dfs_f"), int(x_method), int(K_x), g("times_x"), int(S_x),
+            g("dfs_x")]
+
+
+def xccy_scenario_pv_dev(ctx: Context, for_method: int, K_f: int, S_f: int, x_method: int, K_x: int, S_x: int, S: int,
+                         legs: DeviceTrades, ptrs, book_ptr: int, work_ptr: int, pv_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_xccy_scenario_pv_dev): ``ptrs`` maps ``times_f`` [K_f], ``dfs_f`` [S_f, K_f], ``times_x`` [K_x]
+    and ``dfs_x`` [S_x, K_x] to device pointers (integers); outputs ``book_pv`` [S] and ``pv`` [n, S] (trade-major; 0: not
+    wanted); `xccy_scenario_pv_work` doubles of scratch."""
+    _check(load().adr_xccy_scenario_pv_dev(ctx._h, *_xccy_dev_curves(for_method, K_f, S_f, x_method, K_x, S_x, ptrs), int(S),
+                                           legs._h, _dev(pv_ptr), _dev(book_ptr), _dev(work_ptr), _vp(stream or None)),
+           "adr_xccy_scenario_pv_dev")
+
+
 CREDIT_MAX_BUCKETS = 32                                     # ADR_CREDIT_MAX_BUCKETS
 
 
@@ -1398,6 +1468,32 @@ def yoy_scenario_subbook_pv_dev(ctx: Context, disc_method: int, K: int, S_disc: 
 
 
 SCENARIO_ALLOC_MAX = 8192                                   # ADR_SCENARIO_ALLOC_MAX
+
+
+def xccy_scenario_subbook_pv(ctx: Context, for_method: int, times_f, dfs_f, x_method: int, times_x, dfs_x, legs: DeviceTrades,
+                             sub_off, per_trade=False):
+    """`xccy_scenario_pv` per sub-book in one launch (adr_xccy_scenario_subbook_pv, blocking): sub-book ``b`` holds the
+    trades ``sub_off[b] .. sub_off[b + 1]``.  Returns ``sub_pv`` [B, S] and, with ``per_trade``, ``pv`` [S, n]."""
+    return _xccy_scenario_call(load().adr_xccy_scenario_subbook_pv, (ctx._h,), (legs._h,), (), for_method, times_f, dfs_f,
+                               x_method, times_x, dfs_x, legs.n_trades, per_trade, sub_off)
+
+
+def xccy_scenario_subbook_pv_host(for_method: int, times_f, dfs_f, x_method: int, times_x, dfs_x, batch, sub_off,
+                                  per_trade=False, n_threads=0):
+    """`xccy_scenario_subbook_pv` on the CPU (adr_xccy_scenario_subbook_pv_host): the same arithmetic and the same order of
+    every sum; no GPU needed."""
+    arrays = _batch_arrays(batch)
+    return _xccy_scenario_call(load().adr_xccy_scenario_subbook_pv_host, (), _batch_args(*arrays), (int(n_threads),), for_method,
+                               times_f, dfs_f, x_method, times_x, dfs_x, arrays[0], per_trade, sub_off)
+
+
+def xccy_scenario_subbook_pv_dev(ctx: Context, for_method: int, K_f: int, S_f: int, x_method: int, K_x: int, S_x: int, S: int,
+                                 legs: DeviceTrades, B: int, ptrs, sub_pv_ptr: int, work_ptr: int, pv_ptr: int = 0, stream=0):
+    """Non-blocking form (adr_xccy_scenario_subbook_pv_dev): ``ptrs`` as `xccy_scenario_pv_dev` takes them plus ``plan``, the
+    uploaded `scenario_subbook_plan`; output ``sub_pv`` [B, S]; `scenario_subbook_work` doubles of scratch."""
+    _check(load().adr_xccy_scenario_subbook_pv_dev(ctx._h, *_xccy_dev_curves(for_method, K_f, S_f, x_method, K_x, S_x, ptrs),
+                                                   int(S), legs._h, int(B), _dev_of(ptrs)("plan"), _dev(pv_ptr), _dev(sub_pv_ptr),
+                                                   _dev(work_ptr), _vp(stream or None)), "adr_xccy_scenario_subbook_pv_dev")
 
 
 def _alloc_call(fn, head, rows, k, base_col):

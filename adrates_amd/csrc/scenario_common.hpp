@@ -1,8 +1,9 @@
-// What the scenario revaluation sources (scenario_pv.hip, credit_scenario_pv.hip, yoy_scenario_pv.hip) have in common,
+// What the scenario revaluation sources (scenario_pv.hip, credit_scenario_pv.hip, yoy_scenario_pv.hip, xccy_scenario_pv.hip) have in common,
 // once: the launch shape, the lookup of a discount factor in weight form, the lane broadcast of a coupon description,
 // the order of the book sum, and the host checks of a TradeBatch.  These are what the host twins and the device are
 // held to bit for bit, so a fix to any of them is made here.  The pricing kernels, their slots and their coupon code stay
-// in their sources.
+// in their sources; the slots of an ordinary TradeBatch, which scenario_pv.hip and xccy_scenario_pv.hip share, are in
+// scenario_trade_slots.hpp.
 //
 // Layout they share: one lane = one scenario, one wave = 64 scenarios (a "group"); a block is kWaves waves of ONE
 // group, which share the group's knot table in LDS as tab[k][lane].  The trades are cut into chunks of kChunk

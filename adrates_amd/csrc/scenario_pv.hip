@@ -5,9 +5,10 @@
 // fix_sign * pay * D_s(tp) and the float coupons flt_sign * N * w * ((D_s(ts) / D_s(te) - 1) + spread * alpha) * D_s(tp),
 // D_s(t) being InterpolatorAd.simple_interpolate (simple_interp.hpp).  No rates and no Jacobians are involved.
 //
-// Layout, lookup form, lane broadcast and book sum: scenario_common.hpp.  The group's table tab[k][lane] holds ln d under
-// the log-linear schemes and d under LINEAR_FWD_RATES; a lane reads consecutive doubles, so a knot costs one
-// conflict-free ds_read_b64.
+// Layout, lookup form, lane broadcast and book sum: scenario_common.hpp; the coupon description (Slot), make_slot,
+// apply_slot, lane_slot and trade_pv: scenario_trade_slots.hpp, shared with xccy_scenario_pv.hip.  The group's table
+// tab[k][lane] holds ln d under the log-linear schemes and d under LINEAR_FWD_RATES; a lane reads consecutive doubles, so a
+// knot costs one conflict-free ds_read_b64.
 //
 // Everything about a date that does not depend on the scenario is computed once per wave.  The knot search is not
 // done by a scalar loop per date (nine dependent LDS reads each) but lane-parallel: lane l describes coupon l of the
@@ -31,114 +32,13 @@
 #include "../../include/adrates.h"
 #include "host_pool.hpp"
 #include "scenario_common.hpp"
+#include "scenario_trade_slots.hpp"
 #include "subbook.hpp"
 
 #pragma clang fp contract(off)      // as scenario_common.hpp: the host and the device evaluate the same expressions
 
 namespace adr {
 namespace scen {
-
-// Coupon index c of a trade: its float coupon (c < n_flt) and its fixed flow (c < n_fix).  The masks are adr_price's
-// (the reference engine's): a float coupon counts when tp >= 0 and has no forward when alpha <= 0, a fixed flow counts
-// when tp > 0.
-enum : int {
-    kHasFlt = 1, kHasFix = 2,
-    kTsIsPrevTe = 4,     // accrual start == the previous coupon's accrual end: D(ts) is the D(te) just computed
-    kTpIsTe = 8,         // no payment lag: D(tp) is D(te)
-    kFixIsFltTp = 16,    // the fixed flow is paid with the float coupon: D is D(tp)
-    kNoAccrual = 32      // alpha <= 0: the coupon is spread * alpha * D(tp)
-};
-
-struct Slot {
-    int flags;
-    DateW ws, we, wp, wx;
-    double sa, w, pay;   // spread * alpha, the coupon's notional multiplier, the fixed amount
-};
-
-struct Legs {            // one trade's cash flows
-    const double *fix_tp, *fix_pay, *flt_tp, *flt_ts, *flt_te, *flt_alpha, *flt_weight;
-    int64_t f0, l0;
-    int n_fix, n_flt;
-    double spread;
-};
-
-template <bool kLog>
-__host__ __device__ inline Slot make_slot(const Legs& g, int c, const double* x, int K, int method) {
-    Slot s;
-    s.flags = 0;
-    s.ws = s.we = s.wp = s.wx = DateW{0, 0, 0.0, 0.0};
-    s.sa = 0.0; s.w = 1.0; s.pay = 0.0;
-    double tp = 0.0;
-    bool flt = false;
-    if (c < g.n_flt) {
-        const int64_t i = g.l0 + c;
-        tp = g.flt_tp[i];
-        flt = tp >= 0.0;
-    }
-    if (flt) {
-        const int64_t i = g.l0 + c;
-        const double ts = g.flt_ts[i], te = g.flt_te[i], al = g.flt_alpha[i];
-        s.flags |= kHasFlt;
-        s.sa = g.spread * al;
-        if (g.flt_weight) s.w = g.flt_weight[i];
-        if (al > 0.0) {
-            // the previous coupon left its D(te) behind when it counted and accrued
-            if (c > 0 && ts == g.flt_te[i - 1] && g.flt_tp[i - 1] >= 0.0 && g.flt_alpha[i - 1] > 0.0) s.flags |= kTsIsPrevTe;
-            else s.ws = date_weights<kLog>(ts, x, K, method);
-            s.we = date_weights<kLog>(te, x, K, method);
-            if (tp == te) s.flags |= kTpIsTe;
-            else s.wp = date_weights<kLog>(tp, x, K, method);
-        } else {
-            s.flags |= kNoAccrual;
-            s.wp = date_weights<kLog>(tp, x, K, method);
-        }
-    }
-    if (c < g.n_fix) {
-        const int64_t i = g.f0 + c;
-        const double xt = g.fix_tp[i];
-        if (xt > 0.0) {
-            s.flags |= kHasFix;
-            s.pay = g.fix_pay[i];
-            if (flt && xt == tp) s.flags |= kFixIsFltTp;
-            else s.wx = date_weights<kLog>(xt, x, K, method);
-        }
-    }
-    return s;
-}
-
-struct Acc {             // one scenario's running state inside a trade
-    double de, flt, fix; // D(te) of the previous coupon; the legs' sums before sign and notional
-};
-
-template <bool kLog, class Tab>
-__host__ __device__ inline void apply_slot(const Slot& s, bool weighted, const Tab& tab, Acc& a) {
-    double dp = 0.0;
-    if (s.flags & kHasFlt) {
-        double term;
-        if (s.flags & kNoAccrual) {
-            dp = eval_df<kLog>(s.wp, tab);
-            term = s.sa * dp;
-        } else {
-            const double ds = (s.flags & kTsIsPrevTe) ? a.de : eval_df<kLog>(s.ws, tab);
-            const double de = eval_df<kLog>(s.we, tab);
-            dp = (s.flags & kTpIsTe) ? de : eval_df<kLog>(s.wp, tab);
-            term = ((ds / de - 1.0) + s.sa) * dp;
-            a.de = de;
-        }
-        if (weighted) term = s.w * term;
-        a.flt = a.flt + term;
-    }
-    if (s.flags & kHasFix) {
-        const double dx = (s.flags & kFixIsFltTp) ? dp : eval_df<kLog>(s.wx, tab);
-        a.fix = a.fix + s.pay * dx;
-    }
-}
-
-// + 0.0: a trade without a live flow has two zero sums, and with fix_sign = -1 and flt_sign * notional < 0 both products are
-// -0.0; the PV of nothing is +0.0.  Every other value passes through the add unchanged.
-__host__ __device__ inline double trade_pv(const Acc& a, double fix_sign, double flt_sign, double notional) {
-    return (fix_sign * a.fix + (flt_sign * notional) * a.flt) + 0.0;
-}
 
 // ------------------------------------------------------------------------------------------------------------ device
 struct Args {
@@ -149,28 +49,6 @@ struct Args {
     double *pv, *work;               // [n][S] or null; [n_chunks][S]
     const int64_t *sub_chunks, *sub_bounds;      // kSub: the plan's chunk count and its [chunks][2] trade bounds (subbook.hpp)
 };
-
-// Lane j's slot in scalar registers; only the parts its flags say will be read.
-__device__ inline Slot lane_slot(const Slot& m, int j, bool weighted) {
-    Slot u;
-    u.flags = lane_int(m.flags, j);
-    u.ws = u.we = u.wp = u.wx = DateW{0, 0, 0.0, 0.0};
-    u.sa = 0.0; u.w = 1.0; u.pay = 0.0;
-    if (u.flags & kHasFlt) {
-        if (!(u.flags & kNoAccrual)) {
-            if (!(u.flags & kTsIsPrevTe)) u.ws = lane_date(m.ws, j);
-            u.we = lane_date(m.we, j);
-        }
-        if (!(u.flags & kTpIsTe)) u.wp = lane_date(m.wp, j);
-        u.sa = lane_dbl(m.sa, j);
-        if (weighted) u.w = lane_dbl(m.w, j);
-    }
-    if (u.flags & kHasFix) {
-        if (!(u.flags & kFixIsFltTp)) u.wx = lane_date(m.wx, j);
-        u.pay = lane_dbl(m.pay, j);
-    }
-    return u;
-}
 
 // kSub: the chunks are those of a sub-book plan (their trade bounds come from a table) instead of ch * kChunk.
 template <bool kLog, bool kLds, bool kSub>
@@ -190,6 +68,7 @@ __global__ __launch_bounds__(kThreads) void scenario_pv_kernel(Args a) {
     __syncthreads();
     const DevTab<kLog, kLds> tab{kLds ? s_tab + lane : row};
     const bool weighted = a.tr.flt_weight != nullptr;
+    const Grid grid{s_x, K, a.method};
     int64_t n_chunks = a.n_chunks;
     if (kSub) {
         const int64_t planned = *a.sub_chunks;              // uniform: a scalar load
@@ -211,8 +90,8 @@ __global__ __launch_bounds__(kThreads) void scenario_pv_kernel(Args a) {
                 mine.flags = 0;
                 mine.ws = mine.we = mine.wp = mine.wx = DateW{0, 0, 0.0, 0.0};
                 mine.sa = 0.0; mine.w = 1.0; mine.pay = 0.0;
-                if (lane < cnt) mine = make_slot<kLog>(g, base + lane, s_x, K, a.method);
-                for (int j = 0; j < cnt; ++j) apply_slot<kLog>(lane_slot(mine, j, weighted), weighted, tab, acc);
+                if (lane < cnt) mine = make_slot<kLog, false>(g, base + lane, grid, grid);
+                for (int j = 0; j < cnt; ++j) apply_slot<kLog>(lane_slot(mine, j, weighted), weighted, tab, tab, acc);
             }
             const double pv = trade_pv(acc, static_cast<double>(h.fix_sign), static_cast<double>(h.flt_sign), h.notional);
             if (a.pv && live) a.pv[i * S + s] = pv;
@@ -327,36 +206,6 @@ int run_blocking(const std::string& w, adr_ctx* ctx, int method, int K, const do
     return mem.finish(w, rc, e, stream);
 }
 
-template <bool kLog>
-void host_chunks(int method, int K, const double* times, int S, const double* tab, const HostBatch& t, const Legs& arrays,
-                 double* pv, double* work, int64_t lo, int64_t hi, const int64_t* bounds = nullptr) {
-    std::vector<Acc> acc(static_cast<size_t>(S));
-    std::vector<double> book(static_cast<size_t>(S));
-    const bool weighted = arrays.flt_weight != nullptr;
-    for (int64_t ch = lo; ch < hi; ++ch) {
-        std::fill(book.begin(), book.end(), 0.0);
-        const ChunkRange r = host_chunk_range(ch, bounds, t.n);
-        for (int64_t i = r.i0; i < r.i1; ++i) {
-            Legs g = arrays;
-            g.f0 = t.fix_off[i]; g.l0 = t.flt_off[i];
-            g.n_fix = static_cast<int>(t.fix_off[i + 1] - t.fix_off[i]);
-            g.n_flt = static_cast<int>(t.flt_off[i + 1] - t.flt_off[i]);
-            g.spread = t.spread[i];
-            std::fill(acc.begin(), acc.end(), Acc{0.0, 0.0, 0.0});
-            for (int c = 0; c < std::max(g.n_fix, g.n_flt); ++c) {
-                const Slot slot = make_slot<kLog>(g, c, times, K, method);
-                for (int s = 0; s < S; ++s) apply_slot<kLog>(slot, weighted, HostTab{tab + static_cast<size_t>(s) * K}, acc[s]);
-            }
-            for (int s = 0; s < S; ++s) {
-                const double v = trade_pv(acc[s], t.fix_sign[i], t.flt_sign[i], t.notional[i]);
-                if (pv) pv[i * S + s] = v;
-                book[s] = book[s] + v;
-            }
-        }
-        std::copy(book.begin(), book.end(), work + ch * S);
-    }
-}
-
 }  // namespace scen
 }  // namespace adr
 
@@ -410,35 +259,10 @@ static int scenario_host_run(const std::string& w, int interp_method, int K, con
     int rc = SC::validate(w, interp_method, K, S, n, times, dfs, book_pv);
     if (rc == ADR_OK) rc = SC::check_curves(w, K, times, S, dfs, "scenario");
     if (rc != ADR_OK) return rc;
-    if (!t.fix_off || !t.flt_off || !t.notional || !t.spread || !t.fix_sign || !t.flt_sign)
-        return adr_set_error(ADR_ERR_INVALID, w + ": null per-trade array");
-    for (int64_t i = 0; rc == ADR_OK && i < n; ++i) {      // trade by trade: the first trade at fault decides the message
-        rc = SC::check_leg_offsets(w, t, i, i + 1);
-        if (rc == ADR_OK) rc = SC::check_trade_values(w, t, i, i + 1);
-    }
-    if (rc == ADR_OK) rc = SC::check_flows(w, t);
+    rc = SC::check_host_batch(w, t);
     if (rc != ADR_OK) return rc;
-    const bool lin = interp_method == ADR_INTERP_LINEAR_FWD_RATES;
-    std::vector<double> tab(dfs, dfs + static_cast<size_t>(S) * K);
-    if (!lin)
-        for (double& v : tab) v = std::log(v);
-    std::vector<int64_t> plan;
-    if (B > 0) {
-        rc = adr::sub::build_plan(w, n, B, sub_off, plan);
-        if (rc != ADR_OK) return rc;
-    }
-    const int64_t* bounds = B > 0 ? plan.data() + B + 1 : nullptr;
-    const int64_t chunks = B > 0 ? plan[B] : (n + SC::kChunk - 1) / SC::kChunk;
-    std::vector<double> work(static_cast<size_t>(chunks) * S);
-    const SC::Legs arrays{t.fix_tp, t.fix_pay, t.flt_tp, t.flt_ts, t.flt_te, t.flt_alpha, t.flt_weight, 0, 0, 0, 0, 0.0};
-    const int threads = std::max(1, n_threads > 0 ? static_cast<int>(std::min<int64_t>(n_threads, chunks)) : adr::pool_threads(chunks, 4));
-    adr::parallel_ranges(chunks, threads, [&](int, int64_t lo, int64_t hi) {
-        if (lin) SC::host_chunks<false>(interp_method, K, times, S, tab.data(), t, arrays, pv, work.data(), lo, hi, bounds);
-        else SC::host_chunks<true>(interp_method, K, times, S, tab.data(), t, arrays, pv, work.data(), lo, hi, bounds);
-    });
-    if (B > 0) adr::sub::reduce_subbooks(work.data(), plan.data(), B, S, book_pv);
-    else SC::reduce_chunks(work.data(), chunks, S, book_pv);
-    return ADR_OK;
+    const SC::Grid grid{times, K, interp_method};
+    return SC::host_book_run<false>(w, grid, S, dfs, grid, S, dfs, S, t, pv, book_pv, n_threads, B, sub_off);
 }
 
 int adr_scenario_pv_host(int interp_method, int K, const double* times, int S, const double* dfs, int64_t n,

@@ -95,6 +95,7 @@ class XccyCurve(DiscountCurve):
                     spread_sens=0.0 if is_exchange else fracs[j] * notionals[j],
                     t_start=times_from_dates(start[j], self._value_dt, fc._dc_type),
                     t_end=times_from_dates(end[j], self._value_dt, fc._dc_type),
+                    t_ois=times_from_dates(dt, self._value_dt, fc._dc_type),       # where df_ois is read (scenario rows)
                     df_ois=fc.df(dt, fc._dc_type)))
         points.sort(key=lambda p: (p["time"], p["swap"]))
         return points

@@ -659,6 +659,82 @@ int adr_yoy_scenario_pv_host(int disc_method, int K, const double* times, int S_
                              const int64_t* cpn_off, const double* cpn, double* pv, double* book_pv, int n_threads);
 
 /*
+ * Cross-currency scenario revaluation: the PV of the FOREIGN leg of every cross-currency swap of an uploaded batch under
+ * S scenarios, each a PAIR of a foreign OIS row (the forwards) and an XCCY row (the discount factors) - the launch that
+ * replaces, per scenario, two curve uploads and one adr_price_xccy_foreign.  The domestic legs are an ordinary batch on one
+ * curve: adr_scenario_pv.
+ *
+ *     pv[i][s] = fix_sign_i * sum_j pay_j Dx_s(tp_j)                                                          [tp_j > 0]
+ *              + flt_sign_i * N_i * sum_j w_j ((Df_s(ts_j) / Df_s(te_j) - 1) [alpha_j > 0] + spread_i alpha_j) Dx_s(tp_j)
+ *                                                                                                             [tp_j >= 0]
+ *     book_pv[s] = sum_i pv[i][s]
+ *
+ * Df_s(t): InterpolatorAd.simple_interpolate on (times_f[K_f], dfs_f[s][K_f]) with for_method; Dx_s(t): the same rule on
+ * (times_x[K_x], dfs_x[s][K_x]) with x_method; each grid as adr_scenario_pv reads it (the first knot is t = 0 with discount
+ * factor 1; no division by D(0); 2 .. ADR_SCENARIO_MAX_KNOTS knots, non-decreasing, repeats allowed).  `legs` is the batch
+ * adr_price_xccy_foreign takes (adr_trades_upload_weighted): flt_ts / flt_te / flt_alpha in the foreign leg's day count,
+ * flt_tp and the notional exchanges (fixed flows) in the XCCY curve's, amounts in FOREIGN currency; the caller converts
+ * with 1 / spot.  The masks, flt_weight, the per-trade sum order (coupon c and fixed flow c at index c, each sum from
+ * 0.0) and the final fix_sign * fixed + (flt_sign * N) * float + 0.0 are adr_scenario_pv's: with one table and one scheme
+ * passed as both curves, adr_xccy_scenario_pv_host returns adr_scenario_pv_host's bits.
+ *
+ * Scheme pairs: both curves on ADR_INTERP_LINEAR_FWD_RATES, or each on ADR_INTERP_FLAT_FWD_RATES or
+ * ADR_INTERP_LINEAR_ZERO_RATES (four pairs).  LINEAR_FWD_RATES beside a log-linear scheme is ADR_ERR_UNSUPPORTED, as in
+ * adr_price_xccy_foreign.
+ *
+ * Broadcasting: S_f and S_x are each 1 or S.  One shared row means "this curve is not shocked" and is read with stride
+ * 0: foreign-only, basis-only and joint scenarios from one entry.
+ *
+ * Outputs: book_pv[S] always; pv[n][S] (trade-major, the layout of adr_scenario_pv) when given.  book_pv follows
+ * adr_scenario_pv's rule: the trades in chunks of ADR_SCENARIO_CHUNK summed in order from 0.0, chunk j added to slot
+ * j % 64 in order, then slots 0-31 += 32-63, ..., 0 += 1; no atomics.  A scenario's results do not depend on S, on the
+ * other scenarios, on broadcasting, on which tables sit in LDS or on the launch shape, and are bit-identical from run to
+ * run.
+ *
+ * adr_xccy_scenario_pv: host curves in, host outputs, blocks; refuses knot times that are not finite and non-decreasing
+ * and discount factors that are not positive and finite.  adr_xccy_scenario_pv_dev: device arrays, enqueued on `stream`
+ * (NULL: the ctx's own), no allocation and no synchronisation (two kernels in one chain); work_dev holds
+ * adr_xccy_scenario_pv_work(n, S) doubles; only the scalars are checked.  adr_xccy_scenario_pv_host: the legs as the arrays
+ * of adr_trades_upload_weighted (flt_weight may be NULL), checked as adr_scenario_pv_host checks them; the same per-date
+ * and per-coupon code in the same order on CPU threads (no GPU; n_threads <= 0: as many as the machine suggests, at most
+ * 16); it differs from the device by exp / log only.
+ *
+ * Sub-books: the _subbook entries take in addition B >= 1, sub_off[B + 1] (the _dev form: the uploaded plan of
+ * adr_scenario_subbook_plan and adr_scenario_subbook_work(n, B, S) doubles of scratch; three kernels) and return
+ * sub_pv[B][S] under the contract of adr_scenario_subbook_pv, word for word: sub_pv[b][s] has exactly the bits of
+ * adr_xccy_scenario_pv's book_pv[s] on a batch holding sub-book b's trades alone; an empty sub-book gives +0.0; pv[n][S],
+ * when given, has the parent's bits.
+ */
+int adr_xccy_scenario_pv(adr_ctx* ctx, int for_method, int K_f, const double* times_f, int S_f, const double* dfs_f, int x_method,
+                         int K_x, const double* times_x, int S_x, const double* dfs_x, int S, const adr_trades* legs, double* pv,
+                         double* book_pv);
+/* Doubles of scratch adr_xccy_scenario_pv_dev needs: ceil(n / ADR_SCENARIO_CHUNK) * S. */
+int64_t adr_xccy_scenario_pv_work(int64_t n, int S);
+int adr_xccy_scenario_pv_dev(adr_ctx* ctx, int for_method, int K_f, const double* times_f_dev, int S_f, const double* dfs_f_dev,
+                             int x_method, int K_x, const double* times_x_dev, int S_x, const double* dfs_x_dev, int S,
+                             const adr_trades* legs, double* pv_dev, double* book_pv_dev, double* work_dev, void* stream);
+int adr_xccy_scenario_pv_host(int for_method, int K_f, const double* times_f, int S_f, const double* dfs_f, int x_method, int K_x,
+                              const double* times_x, int S_x, const double* dfs_x, int S, int64_t n, const int64_t* fix_off,
+                              const int64_t* flt_off, const double* fix_tp, const double* fix_pay, const double* flt_tp,
+                              const double* flt_ts, const double* flt_te, const double* flt_alpha, const double* flt_weight,
+                              const double* notional, const double* spread, const double* fix_sign, const double* flt_sign,
+                              double* pv, double* book_pv, int n_threads);
+int adr_xccy_scenario_subbook_pv(adr_ctx* ctx, int for_method, int K_f, const double* times_f, int S_f, const double* dfs_f,
+                                 int x_method, int K_x, const double* times_x, int S_x, const double* dfs_x, int S,
+                                 const adr_trades* legs, int64_t B, const int64_t* sub_off, double* pv, double* sub_pv);
+int adr_xccy_scenario_subbook_pv_dev(adr_ctx* ctx, int for_method, int K_f, const double* times_f_dev, int S_f,
+                                     const double* dfs_f_dev, int x_method, int K_x, const double* times_x_dev, int S_x,
+                                     const double* dfs_x_dev, int S, const adr_trades* legs, int64_t B, const int64_t* plan_dev,
+                                     double* pv_dev, double* sub_pv_dev, double* work_dev, void* stream);
+int adr_xccy_scenario_subbook_pv_host(int for_method, int K_f, const double* times_f, int S_f, const double* dfs_f, int x_method,
+                                      int K_x, const double* times_x, int S_x, const double* dfs_x, int S, int64_t n,
+                                      const int64_t* fix_off, const int64_t* flt_off, const double* fix_tp, const double* fix_pay,
+                                      const double* flt_tp, const double* flt_ts, const double* flt_te, const double* flt_alpha,
+                                      const double* flt_weight, const double* notional, const double* spread,
+                                      const double* fix_sign, const double* flt_sign, int64_t B, const int64_t* sub_off,
+                                      double* pv, double* sub_pv, int n_threads);
+
+/*
  * Credit scenario revaluation: the PV of every trade of an uploaded batch under S scenarios, each a PAIR of a discount
  * curve row and a row of spread shocks per credit bucket - bonds at their z-spreads and FRNs at their discount margins
  * under rate-only, spread-only and joint shocks in one launch, instead of one rescaled upload and one adr_price per
