@@ -1,5 +1,6 @@
 """Edge books and curves for the bond and FRN measures kernels (csrc/bond_measures.hip, csrc/frn_measures.hip), shared
-by the host and GPU tests: inputs and a small numpy restatement of the kernels' documented formulas, no expected values.
+by the host and GPU tests: inputs and a small numpy restatement of the kernels' documented formulas, no expected values
+(the solver edges name the status each of their rows is built for).
 
 The books sit around the kernels' launch geometry: 16 lanes per instrument, and 8 flows per lane (128 per bond) or 24
 coupons per lane (384 per FRN) held in registers, later ones re-read from global memory on every pass.  The curves
@@ -227,6 +228,59 @@ def frns_on_nodes():
     for c in _native.FRN_FIELDS:
         book[c] = np.full(2, one[c], dtype=np.float64)
     return (dt, dd), (it, idf), book
+
+
+# ------------------------------------------------------------------------------------------------ solver edges
+# Rows for the exact reference (tests/_measures_reference.py): quotes at the ends of the solvers' brackets, quotes the
+# brackets do not hold (status 1) or no spread reprices (status 2) on instruments past the register windows, and flows
+# the edge books do not have.  Quotes only; what they give is the reference's to say.
+def matured_bond_rows(Ts=0.05):
+    """A raw book of two bonds whose principal was paid before settlement (tau_M = 0 and tau_M < 0, so the yield prices
+    no face): three lagged coupons of 5 remain.  ``bond_quote`` is left to the caller."""
+    T = Ts + np.array([0.1, 0.2, 0.3])
+    two = lambda v: np.concatenate((v, v))
+    return {"flow_off": np.array([0, 3, 6], dtype=np.int64), "flow_T": two(T), "flow_tau": two(T - Ts),
+            "flow_cpn": np.full(6, 5.0), "flow_prin": np.zeros(6), "bond_Ts": np.full(2, Ts),
+            "bond_tauM": np.array([0.0, -0.01]), "bond_face": np.full(2, 100.0), "bond_acc100": np.array([0.1, 0.0])}
+
+
+BOND_EXTRA_Z = np.array([-0.1, 0.5, 0.01, 0.02])              # the z bracket's ends on the 600-flow bond; the matured bonds
+BOND_EXTRA_CLEAN = np.array([400.0, -50.0, 14.8, 14.7])       # the 129-flow bond beyond the bracket (1), no root (2)
+BOND_EXTRA_STATUS = [1, 2, 0, 0]
+
+
+def extra_bond_book(curve, is_z):
+    """``(method, node_t, node_df, book)``: in z mode the 600-flow bond at both ends of the z bracket, in price mode the
+    129-flow bond at a clean price whose z lies below the bracket and at one no z reprices; then the matured bonds."""
+    bonds = dict((k, b) for k, b, _ in edge_bonds())
+    pair = [bonds["600_50y_monthly"]] * 2 if is_z else [bonds["129_seasoned"]] * 2
+    method, nt, nd, book = bond_arrays(pair, curve, 0.0)
+    tail = matured_bond_rows()
+    tail["bond_quote"] = np.zeros(2)
+    book = concat(book, tail, BOND_KEYS)
+    book["bond_quote"] = (BOND_EXTRA_Z if is_z else BOND_EXTRA_CLEAN).copy()
+    return method, nt, nd, book
+
+
+FRN_EXTRA_DM = np.array([-0.10, 0.20, 0.004, 0.004])          # the DM bracket's ends on the 600-coupon FRN; the clipped FRNs
+FRN_EXTRA_CLEAN = np.array([5.0, -50.0, 99.0, 90.0])          # a 385-coupon FRN beyond the bracket (1), no root (2)
+FRN_EXTRA_STATUS = [1, 2, 0, 0]
+
+
+def extra_frns(is_dm):
+    """In DM mode the 600-coupon FRN twice, in price mode twice a 385-coupon FRN floored at 0 (its coupons have one sign
+    whatever the index curve's forwards do); then an FRN whose cap equals its floor and one whose floored rate is
+    negative (margin -7%, floor -2%: negative coupons under a positive face)."""
+    mk = lambda issue, tenor, margin, **kw: FRN(issue, tenor, margin, M, ACT365, GBP, SONIA, **kw)
+    head = [dict((k, f) for k, f, _ in edge_frns())["600_50y_monthly"]] * 2 if is_dm else \
+        [mk(FRN_SETTLE, "385M", -0.003, face_value=1000.0, payment_lag=2, floor_rate=0.0)] * 2
+    return head + [mk(FRN_SETTLE, "24M", 0.002, cap_rate=0.04, floor_rate=0.04),
+                   mk(FRN_SETTLE, "24M", -0.07, floor_rate=-0.02)]
+
+
+def extra_frn_book(disc, index, is_dm):
+    """``(disc nodes, index nodes, book)`` of `extra_frns` at FRN_EXTRA_DM or FRN_EXTRA_CLEAN."""
+    return frn_arrays(extra_frns(is_dm), disc, index, FRN_EXTRA_DM if is_dm else FRN_EXTRA_CLEAN)
 
 
 # ------------------------------------------------------------------------------------------------ numpy restatement
