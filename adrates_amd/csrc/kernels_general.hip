@@ -93,18 +93,19 @@ struct CurveLds {
 
 // One discount-factor lookup.  FLAT_FWD / LINEAR_ZERO: D(t) = exp(ba*L[ka] + bb*L[kb]); ka/kb are rows of the
 // compact tables.  LINEAR_FWD_RATES is linear in the knot DFs themselves, D = (1-w) d_a + w d_b: its log-gradient
-// is the convex combination rho_a LJ[ka] + rho_b LJ[kb] with rho_a = (1-w) d_a / D, so the same node machinery
-// applies with (ba, bb) = (rho_a, rho_b), plus a rank-one correction rho_a rho_b (LJ[ka] - LJ[kb])(...)^T in the
-// Hessian of ln D (`kappa` = rho_a rho_b; 0 for the log-linear schemes).  That form is for the RATIO nodes, which need
-// ln D.  A plain node a D(t) is the two single-knot amounts a (1 - w) d_a and a w d_b (`pa`, `pb`: the knots' parts of D),
-// each with weight 1 on its own knot, and is walked as such (`lindf_plain` in the kernel): in the rho form the cross
-// products rho_a rho_b LJ[ka] LJ[kb]^T of v v^T and of the correction cancel only up to rounding, which left rounding
-// dust on gamma entries no term reaches (a date between two short-end knots that move different pillars).
+// is the convex combination rho_a LJ[ka] + rho_b LJ[kb] with rho_a = (1-w) d_a / D, which is what (ba, bb) hold.
+// A plain node a D(t) is the two single-knot amounts a (1 - w) d_a and a w d_b (`pa`, `pb`: the knots' parts of D),
+// each with weight 1 on its own knot, and is walked as such (`lindf_plain` in the kernel).  A RATIO node
+// f = c D(ts) D(tp) / D(te) is walked in the same spirit (`lindf_ratio`): its knots as single-knot nodes of amounts
+// f rho_k (- for te's), and the second-order products of two DIFFERENT dates' gradients pair by pair (`add_cross`).
+// Writing either as f (v v^T + sum over the dates of +-rho_a rho_b (LJ[ka] - LJ[kb])(...)^T), v the gradient of ln f,
+// puts the products rho_a rho_b LJ[ka] LJ[kb]^T of ONE date into v v^T and into that date's correction with opposite
+// signs: they cancel only up to rounding, which left rounding dust on gamma entries no term reaches (a date between two
+// short-end knots that move different pillars) and an error no term of the node accounts for on the others.
 struct Lookup {
     int ka, kb;
     double ba, bb;
     double ln_d;     // ln D(t)
-    double kappa;
     double pa, pb;   // LINEAR_FWD_RATES, two knots: (1 - w) d_a and w d_b (else unset: D = exp(ln_d) on knot ka)
 };
 
@@ -129,7 +130,6 @@ __device__ __forceinline__ Lookup curve_lookup(const CurveLds& c, double t) {
         if (dh < best_dist) { best_dist = dh; best = j; }
     }
     Lookup r;
-    r.kappa = 0.0;
     r.pa = r.pb = 0.0;
     if (best_dist < 1e-10) {            // exact grid point: that knot's DF, gradient to that knot only
         r.ka = c.compact_of[best]; r.kb = 0; r.ba = 1.0; r.bb = 0.0;
@@ -160,7 +160,6 @@ __device__ __forceinline__ Lookup curve_lookup(const CurveLds& c, double t) {
         r.pb = w * db;
         r.bb = w * db / d;
         r.ba = 1.0 - r.bb;
-        r.kappa = r.ba * r.bb;
         r.ln_d = log(d);
         return r;
     }
@@ -211,19 +210,12 @@ struct ConvLds {
 // CF: the convexity coefficients of the entries come from `cf` (final values: the caller has summed the weights
 // of the nodes that share a knot) instead of omega * b; without CF the argument is ignored.
 // LDSLC: the knot words carry the knot's class (curve_tables.hpp, knot_class) in their high half, `conv` is used.
-// NCORR (LINEAR_FWD_RATES, LDS-resident convexity rows): the rank-one corrections of the node's NCORR = NK / 2 lookups
-// (`add_df_correction`), weight kw[q] on the vector LJ[k[2q]] - LJ[k[2q+1]], ride in the node's own walk - their vectors are
-// differences of the Jacobian entries the walk has just read, and they reach the lanes through the idle halves of the
-// hand-off buffers (one tile: lanes 32-63 of `vbuf` hold a copy; `stage2` is the wave's trade-end staging area): one walk
-// per node instead of one per node and lookup (a payment-lag coupon: two walks instead of six).
-template <int NK, bool DELTA, bool GAMMA, bool CF = false, bool LDSLC = false, int NCORR = 0>
+template <int NK, bool DELTA, bool GAMMA, bool CF = false, bool LDSLC = false>
 __device__ __forceinline__ void add_nodes(unsigned long long mask, const int (&k)[NK], const double (&b)[NK],
                                           double omega, const CurveLds& c, const double* __restrict__ lc_lanes,
                                           const unsigned long long* lc_block_mask,
                                           double* vbuf, int lane, Ladders<GAMMA>& acc, const double (&cf)[NK],
-                                          const ConvLds& conv = ConvLds{},
-                                          const double (&kw)[NCORR > 0 ? NCORR : 1] = {0.0}, double* stage2 = nullptr) {
-    static_assert(NCORR == 0 || (NCORR == NK / 2 && LDSLC && GAMMA), "fused corrections: one per lookup, LDS rows, gamma");
+                                          const ConvLds& conv = ConvLds{}) {
     const int p = lane & 31;
     const int bi = lane >> 3, bj = lane & 7;
     while (mask) {
@@ -242,30 +234,15 @@ __device__ __forceinline__ void add_nodes(unsigned long long mask, const int (&k
         double cc[NK];
 #pragma unroll
         for (int i = 0; i < NK; ++i) cc[i] = (CF && GAMMA) ? readlane_d(cf[i], n) : om * bb[i];
-        double v = 0.0, ljv[NK];
+        double v = 0.0;
 #pragma unroll
-        for (int i = 0; i < NK; ++i) { ljv[i] = c.lj[c.lj_off + kk[i] * kPillarPad + p]; v = fma(bb[i], ljv[i], v); }
+        for (int i = 0; i < NK; ++i) v = fma(bb[i], c.lj[c.lj_off + kk[i] * kPillarPad + p], v);
         if (DELTA) acc.delta = fma(om, v, acc.delta);
-        double wq[NCORR > 0 ? NCORR : 1];
-        if constexpr (NCORR > 0) {
-#pragma unroll
-            for (int q = 0; q < NCORR; ++q) wq[q] = readlane_d(kw[q], n);
-        }
         if (GAMMA) {
             // hand v[0..31] to every lane through the wave's LDS slot (same-wave LDS ops are ordered)
             // (the DS instructions of one wavefront execute in issue order: a compiler barrier is all the
             // hand-off needs, no wait for the write to retire)
             __builtin_amdgcn_wave_barrier();
-            if constexpr (NCORR > 0) {
-                const double d0 = ljv[0] - ljv[1];
-                vbuf[lane] = lane < 32 ? v : d0;
-                if constexpr (NCORR > 1) {
-                    const double d1 = ljv[2] - ljv[3];
-                    double d2 = 0.0;
-                    if constexpr (NCORR > 2) d2 = ljv[4] - ljv[5];
-                    stage2[lane] = lane < 32 ? d1 : d2;
-                }
-            } else
             vbuf[lane] = v;                       // lanes 32-63: the column tile's v (a copy on diagonal tile pairs)
             asm volatile("" ::: "memory");
             __builtin_amdgcn_wave_barrier();
@@ -306,19 +283,6 @@ __device__ __forceinline__ void add_nodes(unsigned long long mask, const int (&k
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int jx = 0; jx < 4; ++jx) acc.gamma[i * 4 + jx] = fma(vr[i], vc[jx], acc.gamma[i * 4 + jx]);
-            if constexpr (NCORR > 0) {
-#pragma unroll
-                for (int q = 0; q < NCORR; ++q) {
-                    const double* src = (q == 0 ? vbuf + 32 : (q == 1 ? stage2 : stage2 + 32));
-                    double dr[4], dc_[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { dr[i] = wq[q] * src[4 * bi + i]; dc_[i] = src[4 * bj + i]; }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int jx = 0; jx < 4; ++jx) acc.gamma[i * 4 + jx] = fma(dr[i], dc_[jx], acc.gamma[i * 4 + jx]);
-                }
-            }
             // curve-convexity part: sum_i om*b_i * LC[k_i]
             if constexpr (!LDSLC)
 #pragma unroll
@@ -434,21 +398,92 @@ __device__ __forceinline__ void add_nodes_any(unsigned long long mask, const int
     else add_nodes<NK, DELTA, GAMMA, CF, LDSLC>(mask, k, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf, conv);
 }
 
-// LINEAR_FWD_RATES: the rank-one term a discount factor that is linear in its two knot DFs adds to the Hessian,
-// weight * (LJ[ka] - LJ[kb]) (LJ[ka] - LJ[kb])^T with weight = (term value) * (+1 numerator / -1 denominator) * kappa
-// (see `Lookup`).  It has no first-order and no convexity part, so it runs as a node without DELTA and with zero
-// convexity coefficients.
-template <bool GAMMA, bool LDSLC = false, int WIDE = 0>
-__device__ __forceinline__ void add_df_correction(bool on, int ka, int kb, double weight, const CurveLds& c,
-                                                  const double* __restrict__ lc_lanes,
-                                                  const unsigned long long* lc_block_mask, double* vbuf, int lane,
-                                                  Ladders<GAMMA, WIDE>& acc) {
+// LINEAR_FWD_RATES, ratio nodes: the second-order term of two DIFFERENT dates of a node, omega (x y^T + y x^T) with
+// x = sum_i bx_i LJ[k_i] and y = sum_i by_i LJ[k_i] the two dates' log-gradients on the node's knots (weights 0 where a knot
+// is not the date's).  Each product goes through the hand-off buffer on its own - rows x against columns y, then rows y
+// against columns x - so an entry holds nothing but products of the two dates: there is no x x^T to cancel afterwards.
+// Lanes 0-31 build the row tile's vectors and lanes 32-63 the column tile's (copies on diagonal tile pairs), so the columns
+// are read from the upper half of the buffer on every tile pair.  No first-order and no convexity part.
+template <int NK, bool GAMMA>
+__device__ __forceinline__ void add_cross(unsigned long long mask, const int (&k)[NK], const double (&bx)[NK], const double (&by)[NK],
+                                          double omega, const CurveLds& c, double* vbuf, int lane, Ladders<GAMMA>& acc) {
     if constexpr (GAMMA) {
-        const int k2[2] = {ka, kb};     // untagged is fine: the convexity coefficients are zero
-        const double b2[2] = {1.0, -1.0}, none[2] = {0.0, 0.0};
-        const double om = on ? weight : 0.0;
-        add_nodes_any<2, false, true, true, LDSLC, WIDE>(__ballot(om != 0.0), k2, b2, om, c, lc_lanes, lc_block_mask, vbuf, lane, acc, none, ConvLds{});
+        const int p = lane & 31;
+        const int bi = lane >> 3, bj = lane & 7;
+        while (mask) {
+            const int n = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const double om = readlane_d(omega, n);
+            double x = 0.0, y = 0.0;
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                const double lj = c.lj[c.lj_off + readlane_i(k[i], n) * kPillarPad + p];
+                x = fma(readlane_d(bx[i], n), lj, x);
+                y = fma(readlane_d(by[i], n), lj, y);
+            }
+#pragma unroll
+            for (int pass = 0; pass < 2; ++pass) {
+                __builtin_amdgcn_wave_barrier();
+                vbuf[lane] = ((lane < 32) == (pass == 0)) ? x : y;
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                asm volatile("" ::: "memory");
+                if (c.diag && bi > bj) continue;          // blocks below the diagonal are mirrors (`add_nodes`)
+                double vr[4], vc[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { vr[i] = om * vbuf[4 * bi + i]; vc[i] = vbuf[32 + 4 * bj + i]; }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int jx = 0; jx < 4; ++jx) acc.gamma[i * 4 + jx] = fma(vr[i], vc[jx], acc.gamma[i * 4 + jx]);
+            }
+        }
     }
+}
+
+// ... on the wide layout: the packed upper triangle takes omega x at the entry's rows against y at its column, then omega y
+// against x (`add_nodes_wide`'s rank-one update, once per product)
+template <int NK, bool GAMMA, int NCH>
+__device__ __forceinline__ void add_cross_wide(unsigned long long mask, const int (&k)[NK], const double (&bx)[NK], const double (&by)[NK],
+                                               double omega, const CurveLds& c, double* vbuf, int lane, Ladders<GAMMA, NCH>& acc) {
+    if constexpr (GAMMA) {
+        while (mask) {
+            const int n = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const double om = readlane_d(omega, n);
+            double x = 0.0, y = 0.0;
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                const double lj = c.lj[readlane_i(k[i], n) * kWidePad + lane];
+                x = fma(readlane_d(bx[i], n), lj, x);
+                y = fma(readlane_d(by[i], n), lj, y);
+            }
+#pragma unroll
+            for (int pass = 0; pass < 2; ++pass) {
+                __builtin_amdgcn_wave_barrier();
+                vbuf[c.wpos] = pass == 0 ? y : x;
+                vbuf[kWidePad + c.wpos] = om * (pass == 0 ? x : y);
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    const unsigned w = c.went[ch];
+                    const double2 wa = *reinterpret_cast<const double2*>(vbuf + kWidePad + (w & 0xff));
+                    const double vb = vbuf[(w >> 8) & 0xff];
+                    acc.gamma[2 * ch] = fma(wa.x, vb, acc.gamma[2 * ch]);
+                    acc.gamma[2 * ch + 1] = fma(wa.y, vb, acc.gamma[2 * ch + 1]);
+                }
+            }
+        }
+    }
+}
+
+template <int NK, bool GAMMA, int WIDE>
+__device__ __forceinline__ void add_cross_any(unsigned long long mask, const int (&k)[NK], const double (&bx)[NK], const double (&by)[NK],
+                                              double omega, const CurveLds& c, double* vbuf, int lane, Ladders<GAMMA, WIDE>& acc) {
+    if constexpr (WIDE > 0) add_cross_wide<NK, GAMMA, WIDE>(mask, k, bx, by, omega, c, vbuf, lane, acc);
+    else add_cross<NK, GAMMA>(mask, k, bx, by, omega, c, vbuf, lane, acc);
 }
 
 // LINDF: the curve interpolates with LINEAR_FWD_RATES (a compile-time switch: the state of the corrections would
@@ -533,8 +568,6 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform -> scalar loads of the header
     const int knot0 = c.compact_of[0];                                    // the value-time knot (t = 0)
     constexpr bool linear_df = LINDF;                                     // LINEAR_FWD_RATES: see `Lookup`
-    // ... with LDS-resident convexity rows the corrections of a node's lookups ride in the node's walk (`add_nodes`, NCORR)
-    constexpr bool FUSE = LINDF && LDSLC && GAMMA && WIDE == 0;
     double* vbuf = s_vbuf + wave * kVbuf;
     const int P = cv.P;
     c.lj_off = (lane >= 32 && !diag) ? n_lj : 0;
@@ -600,6 +633,16 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
             const int k1[2] = {tag(k[side]), tag(0)};
             const double b1[2] = {1.0, 0.0}, cf1[2] = {cf[side], 0.0};
             add_nodes_any<2, DELTA, GAMMA, true, LDSLC, WIDE>(__ballot(om[side] != 0.0), k1, b1, om[side], c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf1, conv);
+        }
+    };
+    // ... and a ratio node's knots (`Lookup`): the same walk, but a knot stays in it for its convexity coefficient alone - the
+    // coefficients of a date move between the nodes that share it (below), the amounts do not
+    auto lindf_knots = [&](const int (&k)[2], const double (&om)[2], const double (&cf)[2], Ladders<GAMMA, WIDE>& acc) {
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const int k1[2] = {tag(k[side]), tag(0)};
+            const double b1[2] = {1.0, 0.0}, cf1[2] = {cf[side], 0.0};
+            add_nodes_any<2, DELTA, GAMMA, true, LDSLC, WIDE>(__ballot(om[side] != 0.0 || cf[side] != 0.0), k1, b1, om[side], c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf1, conv);
         }
     };
     // ... and the flat convexity sums are scattered to this lane's 4x4 block once per trade: position of each of
@@ -670,7 +713,7 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
             const bool pay_on = in && a_pay != 0.0;
             kp[0] = kp[1] = 0; bp[0] = bp[1] = 0.0;
             Lookup qpay;
-            qpay.ka = qpay.kb = 0; qpay.ba = qpay.bb = 0.0; qpay.ln_d = 0.0; qpay.kappa = 0.0; qpay.pa = qpay.pb = 0.0;
+            qpay.ka = qpay.kb = 0; qpay.ba = qpay.bb = 0.0; qpay.ln_d = 0.0; qpay.pa = qpay.pb = 0.0;
             if (pay_on || (valid && ratio)) qpay = curve_lookup(c, tp);
             double omp2[2] = {0.0, 0.0};           // LINEAR_FWD_RATES: the two knots' amounts
             if (pay_on) {
@@ -715,9 +758,9 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
             const bool own_ratio = RATIO && valid && ratio;
             if (RATIO && __ballot(own_ratio)) {   // payment lag: N D(ts) D(tp) / D(te) keeps all three lookups
                 int k[6]; double b[6]; double omega = 0.0;
-                int kc[6]; double kap[3] = {0.0, 0.0, 0.0};    // LINEAR_FWD: the lookups' own knots and correction weights
+                double b0[6];                                  // LINEAR_FWD: the dates' own weights, before te's are folded into tp's
 #pragma unroll
-                for (int i = 0; i < 6; ++i) { k[i] = 0; b[i] = 0.0; kc[i] = 0; }
+                for (int i = 0; i < 6; ++i) { k[i] = 0; b[i] = 0.0; b0[i] = 0.0; }
                 if (own_ratio) {
                     const Lookup qs = curve_lookup(c, ts), qe = curve_lookup(c, te), qp = qpay;
                     k[0] = qs.ka; k[1] = qs.kb; b[0] = qs.ba; b[1] = qs.bb;
@@ -726,9 +769,8 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
                     double l = 0.0;
                     if constexpr (linear_df) {
                         l = qs.ln_d - qe.ln_d + qp.ln_d;
-                        kap[0] = qs.kappa; kap[1] = -qe.kappa; kap[2] = qp.kappa;
 #pragma unroll
-                        for (int i = 0; i < 6; ++i) kc[i] = k[i];
+                        for (int i = 0; i < 6; ++i) b0[i] = b[i];
                     } else {
 #pragma unroll
                         for (int i = 0; i < 6; ++i) l = fma(b[i], c.log_df[k[i]], l);
@@ -784,13 +826,27 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
                 // paid on the value-time knot alone (the cross-currency assembly): the payment entries carry no
                 // sensitivity, the node is its four accrual entries
                 const bool pay_flat = k[4] == knot0 && b[5] == 0.0;
+                if constexpr (linear_df && GAMMA) {
+                    // LINEAR_FWD_RATES (`Lookup`): the node's knots as single-knot nodes of amounts omega b_k, which carry the
+                    // first order, the knots' own second order and the convexity; then the products of two different dates'
+                    // gradients: with S(x, y) = x y^T + y x^T and v = v_s - v_e + v_p the whole gradient,
+                    //   omega (S(v_s, v_p) - S(v_s, v_e) - S(v_p, v_e) + S(v_e, v_e)) = omega (S(v_s, v_p) - S(v, v_e))
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        const bool on = own_ratio && (q < 2 || !pay_flat);
+                        const int k2[2] = {k[2 * q], k[2 * q + 1]};
+                        const double om2[2] = {on ? omega * b[2 * q] : 0.0, on ? omega * b[2 * q + 1] : 0.0};
+                        const double cf2[2] = {on ? cf[2 * q] : 0.0, on ? cf[2 * q + 1] : 0.0};
+                        lindf_knots(k2, om2, cf2, acc);
+                    }
+                    const double xs[6] = {b0[0], b0[1], 0.0, 0.0, 0.0, 0.0}, xp[6] = {0.0, 0.0, 0.0, 0.0, b0[4], b0[5]};
+                    const double xe[6] = {0.0, 0.0, b0[2], b0[3], 0.0, 0.0};        // (-v_e: te's weights carry their sign)
+                    add_cross_any<6, GAMMA, WIDE>(__ballot(own_ratio && !pay_flat), k, xs, xp, omega, c, vbuf, lane, acc);
+                    add_cross_any<6, GAMMA, WIDE>(__ballot(own_ratio), k, b, xe, omega, c, vbuf, lane, acc);
+                } else {
                 { int kt_[6];
 #pragma unroll
                   for (int i_ = 0; i_ < 6; ++i_) kt_[i_] = tag(k[i_]);
-                  if constexpr (FUSE) {
-                      const double kw3[3] = {omega * kap[0], omega * kap[1], omega * kap[2]};
-                      add_nodes<6, DELTA, GAMMA, true, LDSLC, 3>(__ballot(own_ratio && !pay_flat), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf, conv, kw3, stage);
-                  } else
                   add_nodes_any<6, DELTA, GAMMA, true, LDSLC, WIDE>(__ballot(own_ratio && !pay_flat), kt_, b, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf, conv); }
                 const unsigned long long flat_mask = __ballot(own_ratio && pay_flat);
                 if (flat_mask) {
@@ -800,16 +856,8 @@ __global__ __launch_bounds__(general_block_threads(LDSLC, WIDE), (WIDE > 10) ? 1
                     { int kt_[4];
 #pragma unroll
                       for (int i_ = 0; i_ < 4; ++i_) kt_[i_] = tag(k4[i_]);
-                      if constexpr (FUSE) {
-                          const double kw2[2] = {omega * kap[0], omega * kap[1]};      // (the payment lookup sits on the value-time knot: no correction)
-                          add_nodes<4, DELTA, GAMMA, true, LDSLC, 2>(flat_mask, kt_, b4, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf4, conv, kw2, stage);
-                      } else
                       add_nodes_any<4, DELTA, GAMMA, true, LDSLC, WIDE>(flat_mask, kt_, b4, omega, c, lc_lanes, lc_block_mask, vbuf, lane, acc, cf4, conv); }
                 }
-                if constexpr (linear_df && !FUSE) {
-#pragma unroll
-                    for (int q = 0; q < 3; ++q)
-                        add_df_correction<GAMMA, LDSLC, WIDE>(own_ratio, kc[2 * q], kc[2 * q + 1], omega * kap[q], c, lc_lanes, lc_block_mask, vbuf, lane, acc);
                 }
             }
             if constexpr (linear_df) {

@@ -571,36 +571,57 @@ void price_lite_kernel(CurveDev cv, LiteRowsDev tr,
                     const double pba = row_prev(qe.ba), pbb = row_prev(qe.bb);
                     int kk[6] = {chained ? pka : qs.ka, chained ? pkb : qs.kb, qe.ka, qe.kb, qp.ka, qp.kb};
                     double cc[6] = {chained ? pba : qs.ba, chained ? pbb : qs.bb, -qe.ba, -qe.bb, qp.ba, qp.bb};
-                    // a payment time a few days behind the accrual end sits on the same two knots: its weights join the end's
-                    // (four terms instead of six: ten sums instead of twenty-one)
-                    // LINEAR_FWD_RATES: a factor F = ba D_a + bb D_b is not an exponential of a linear form; its logarithm has the
-                    // Hessian g_a g_b (e_a - e_b)(e_a - e_b)^T (g: the effective weights), so every factor of a node of value omega
-                    // adds +- omega g_a g_b of that matrix (-: the accrual end, which divides)
-                    auto factor_curvature = [&](int ka, int kb, double ga, double gb, double om) {
-                        const double w = om * ga * gb;
-                        if (ka != 0 && w != 0.0) __hip_atomic_fetch_add(knot_d + ka, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        if (kb != 0 && w != 0.0) __hip_atomic_fetch_add(knot_d + kb, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        pair_add(ka, 1.0, kb, -1.0, w);
-                    };
                     if constexpr (LINDF) {
-                        factor_curvature(kk[0], kk[1], cc[0], cc[1], om_r);
-                        factor_curvature(qe.ka, qe.kb, qe.ba, qe.bb, -om_r);
-                        factor_curvature(qp.ka, qp.kb, qp.ba, qp.bb, om_r + om_p);        // the ratio node's and the payment node's
-                    }
-                    if (qp.ka == qe.ka && qp.kb == qe.kb) { cc[2] += cc[4]; cc[3] += cc[5]; cc[4] = 0.0; cc[5] = 0.0; }
-                    if (ratio) {
+                        // LINEAR_FWD_RATES: a factor F = ba D_a + bb D_b is not an exponential of a linear form.  With g the factors'
+                        // effective weights, the node f = omega_r F(ts) F(tp) / F(te) has, in the log discount factors,
+                        //   H_kl = f ((s_k p_l + p_k s_l) - (s_k e_l + e_k s_l) - (p_k e_l + e_k p_l) + 2 e_k e_l) + [k == l] f (s_k - e_k + p_k):
+                        // a knot's own amount on the diagonal, and products of two DIFFERENT factors' weights (te's with itself: it
+                        // divides).  Written as f (u u^T + sum over the factors of +-g_a g_b (e_a - e_b)(e_a - e_b)^T), the product
+                        // g_a g_b of ONE factor lands on its pair of knots twice with opposite signs, and the sums cancel only up
+                        // to rounding: dust on gamma entries no term reaches (kernels_general.hip, `Lookup`).
+                        auto diag_add = [&](int k_, double v) {
+                            if (k_ != 0 && v != 0.0) __hip_atomic_fetch_add(knot_d + k_, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        };
+                        const int ks[2] = {kk[0], kk[1]}, ke[2] = {qe.ka, qe.kb}, kp[2] = {qp.ka, qp.kb};
+                        const double gs[2] = {cc[0], cc[1]}, ge[2] = {qe.ba, qe.bb}, gp[2] = {qp.ba, qp.bb};
 #pragma unroll
-                        for (int i = 0; i < 6; ++i) {
-                            if (kk[i] != 0 && cc[i] != 0.0)
-                                __hip_atomic_fetch_add(knot_d + kk[i], om_r * cc[i] * cc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#pragma unroll
-                            for (int j = i + 1; j < 6; ++j) pair_add(kk[i], cc[i], kk[j], cc[j], om_r);
+                        for (int i = 0; i < 2; ++i) {
+                            if (ratio) {
+                                diag_add(ks[i], om_r * gs[i]);
+                                diag_add(ke[i], -om_r * ge[i]);
+                                diag_add(ke[i], 2.0 * om_r * ge[i] * ge[i]);
+                            }
+                            if (paid_later) diag_add(kp[i], (om_r + om_p) * gp[i]);      // the ratio node's and the payment node's
                         }
-                    }
-                    if (paid_later) {
-                        if (qp.ka != 0) __hip_atomic_fetch_add(knot_d + qp.ka, om_p * qp.ba * qp.ba, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        if (qp.kb != 0 && qp.bb != 0.0) __hip_atomic_fetch_add(knot_d + qp.kb, om_p * qp.bb * qp.bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        pair_add(qp.ka, qp.ba, qp.kb, qp.bb, om_p);
+                        if (ratio) {
+#pragma unroll
+                            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                                for (int j = 0; j < 2; ++j) {
+                                    pair_add(ks[i], gs[i], kp[j], gp[j], om_r);
+                                    pair_add(ks[i], gs[i], ke[j], ge[j], -om_r);
+                                    pair_add(kp[i], gp[i], ke[j], ge[j], -om_r);
+                                }
+                            pair_add(ke[0], ge[0], ke[1], ge[1], 2.0 * om_r);
+                        }
+                    } else {
+                        // a payment time a few days behind the accrual end sits on the same two knots: its weights join the end's
+                        // (four terms instead of six: ten sums instead of twenty-one)
+                        if (qp.ka == qe.ka && qp.kb == qe.kb) { cc[2] += cc[4]; cc[3] += cc[5]; cc[4] = 0.0; cc[5] = 0.0; }
+                        if (ratio) {
+#pragma unroll
+                            for (int i = 0; i < 6; ++i) {
+                                if (kk[i] != 0 && cc[i] != 0.0)
+                                    __hip_atomic_fetch_add(knot_d + kk[i], om_r * cc[i] * cc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#pragma unroll
+                                for (int j = i + 1; j < 6; ++j) pair_add(kk[i], cc[i], kk[j], cc[j], om_r);
+                            }
+                        }
+                        if (paid_later) {
+                            if (qp.ka != 0) __hip_atomic_fetch_add(knot_d + qp.ka, om_p * qp.ba * qp.ba, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                            if (qp.kb != 0 && qp.bb != 0.0) __hip_atomic_fetch_add(knot_d + qp.kb, om_p * qp.bb * qp.bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                            pair_add(qp.ka, qp.ba, qp.kb, qp.bb, om_p);
+                        }
                     }
                 }
                 if (DELTA) {

@@ -7,9 +7,12 @@ the knot times x_k, the knot discount factors d_k, ``jac [K, P]`` = J, ``hess [K
 for credit, ``z``, ``bucket``, the spread times and ``G``.  A desk's PV is a sum of TERMS c D(t), one per cash flow and NOT
 folded into nodes (oracle/mp_oracle.py's value level):
   fixed flow, counts when tp > 0:            c = fix_sign fix_pay at tp
-  float coupon, counts when tp >= 0:         N sign ((D(ts) / D(te) - 1 when alpha > 0) + spread alpha) D(tp); the ladders take
-                                             accruing coupons with te == tp only, so D(ts) / D(te) D(tp) = D(ts) and the coupon
-                                             is  +sn at ts,  -sn at tp  (both only when alpha > 0)  and  sn spread alpha at tp.
+  float coupon, counts when tp >= 0:         N w sign ((D(ts) / D(te) - 1 when alpha > 0) + spread alpha) D(tp), w the coupon's
+                                             weight (1 without weights).  With te == tp (all the ladders take)
+                                             D(ts) / D(te) D(tp) = D(ts) and the coupon is  +c at ts,  -c at tp  (both only when
+                                             alpha > 0)  and  c spread alpha at tp, c = sn w.  With te != tp (payment lag; the
+                                             pricing kernels only, tests/_price_reference.py) the first term is the RATIO term
+                                             c D(ts) D(tp) / D(te)  (below, "Ratio terms").
 Credit multiplies every term of a flow by f = exp(-z tau) of that flow.  D(t) is simple_interp.hpp's lookup rule, its float64
 decisions (snap within 1e-10 to the first of equal knots, else the segment and weight of t + 1e-12, clamped at the ends)
 taken from `oracle.mp_oracle._lookup_plan`; with L_k = ln d_k
@@ -24,6 +27,18 @@ terms' amounts times -tau and tau^2.  The projection is done in exact integer ar
 H_kl / (d_k d_l) are formed in mpmath and taken apart into integer mantissas on one exponent without any rounding, J and C
 are exact integers times a power of two, and the sums are Python integers (object arrays).  1e-4 and 1e-8 stay exact: a
 result is an integer V with value = V 2^E / 10^s.
+
+Ratio terms.  Log schemes: om = c exp(sum_k u_k L_k) with u the sum of the knot weights of ts (+), te (-) and tp (+) - up to six
+knots, so H is not banded -, g_k += om u_k and H_kl += om u_k u_l.  Its gross takes the weights as written, before the merge:
+|om| W_k and |om| W_k W_l with W_k the sum of the three dates' absolute weights at knot k (a two-day lag that puts te and tp in
+one interval counts -b(te) + b(tp) as cancellation against gross, as the inflation side does for ts and te on one knot).
+LINEAR_FWD_RATES: f = c S P / E with S, E, P linear in the d_k (weights s, e, p); the reduced form, which has no product of
+two weights of one date but e's,
+  df/dd_k = f (s_k / S - e_k / E + p_k / P)
+  d2f/dd_k dd_l = f [(s_k p_l + p_k s_l) / (S P) - (s_k e_l + e_k s_l) / (S E) - (p_k e_l + e_k p_l) / (P E) + 2 e_k e_l / E^2]
+brought into the L_k as the plain term is: g_k = d_k df/dd_k, H_kl = d_k d_l d2f/dd_k dd_l + [k == l] g_k.  Its gross is the sum
+of the absolute values of exactly these terms, so an entry reached only through s_k s_l of one date has gross 0 and must be
++0.0.  ``cond`` of a ratio term: the sum of |weight L_k| over its three dates (LINEAR_FWD_RATES: the largest |L_k|).
 
 Gross.  Every element comes with ``gross``: the sum of the absolute values of its terms written in the inputs - |c| f D(t)
 through the absolute interpolation weights, and the tables as |J| / d, |C| / d and |J J^T| / d^2 separately, so the
@@ -317,6 +332,63 @@ class _Sums:
                     bump(self.H, (k, l), om * wk * wl)
                     bump(self.H_abs, (k, l), oa * abs(wk * wl))
 
+    def add_ratio(self, ts, te, tp, c):
+        """The ratio term ``c D(ts) D(tp) / D(te)`` (module docstring, "Ratio terms")."""
+        if c == 0:
+            return
+        dates = [self.cv.date(t) for t in (ts, te, tp)]
+        signs = (1, -1, 1)
+        (Ds, _, ps, _), (De, _, pe, _), (Dp, _, pp, _) = dates
+        om = c * Ds * Dp / De
+        oa = abs(om)
+        self.n += 1
+        self.pv += om
+        self.pv_abs += oa
+        bump = lambda table, key, v: table.__setitem__(key, table.get(key, mpf(0)) + v)
+        if ps is not None:                                  # LINEAR_FWD_RATES: the reduced form on the shares of S, E, P
+            self.cond = max(self.cond, max(d[3] for d in dates))
+            sh = [{k: p / D for k, p in pieces} for (D, _, pieces, _) in dates]          # s_k d_k / S, e_k d_k / E, p_k d_k / P
+            for sg, part in zip(signs, sh):
+                for k, v in part.items():
+                    bump(self.g, k, sg * om * v)
+                    bump(self.g_abs, k, oa * v)
+                    if self.second:
+                        bump(self.H, (k, k), sg * om * v)
+                        bump(self.H_abs, (k, k), oa * v)
+            if self.second:
+                s_, e_, p_ = sh
+                for a, b, coef in ((s_, p_, 1), (s_, e_, -1), (p_, e_, -1)):
+                    for k, vk in a.items():
+                        for l, vl in b.items():
+                            for key in ((k, l), (l, k)):
+                                bump(self.H, key, coef * om * vk * vl)
+                                bump(self.H_abs, key, oa * vk * vl)
+                for k, vk in e_.items():
+                    for l, vl in e_.items():
+                        bump(self.H, (k, l), 2 * om * vk * vl)
+                        bump(self.H_abs, (k, l), 2 * oa * vk * vl)
+            return
+        self.cond = max(self.cond, sum((d[3] for d in dates), mpf(0)))
+        u, W = {}, {}
+        for sg, (_, knots, _, _) in zip(signs, dates):
+            for k, wk in knots:
+                bump(u, k, sg * wk)
+                bump(W, k, abs(wk))
+        for k in u:
+            bump(self.g, k, om * u[k])
+            bump(self.g_abs, k, oa * W[k])
+            if self.second:
+                for l in u:
+                    bump(self.H, (k, l), om * u[k] * u[l])
+                    bump(self.H_abs, (k, l), oa * W[k] * W[l])
+
+    def add_term(self, t, c):
+        """A term of `trade_terms`: a date, or the three dates of a ratio term."""
+        if isinstance(t, tuple):
+            self.add_ratio(*t, c)
+        else:
+            self.add(t, c)
+
     # -------------------------------------------------------------------------------------------------- projection
     def _project(self, g, H, J, C, sign, second):
         """``(delta piece, gamma piece or None)`` as ``(ints, e)`` before the powers of ten."""
@@ -367,8 +439,9 @@ def _tables(cv):
 # ------------------------------------------------------------------------------------------------------------ the terms
 def trade_terms(batch, i, z=None, fix_tau=None, flt_tau=None):
     """The unfolded terms ``(t, c, tau)`` of trade ``i`` (c an mpf, the spread factor not applied; tau None without
-    spreads).  Ratio-node trades are out of scope: an accruing coupon must be paid on its accrual end."""
-    assert batch.flt_weight is None
+    spreads).  ``t`` is a date, or - an accruing coupon paid on another date than its accrual end - the tuple (ts, te, tp)
+    of the ratio term c D(ts) D(tp) / D(te) (`_Sums.add_term`); with spreads (the credit ladders) such a coupon is out of
+    scope.  A coupon's weight multiplies its c."""
     out = []
     for j in range(int(batch.fix_off[i]), int(batch.fix_off[i + 1])):
         tp = float(batch.fix_tp[j])
@@ -377,15 +450,16 @@ def trade_terms(batch, i, z=None, fix_tau=None, flt_tau=None):
     sn = _mp(batch.flt_sign[i]) * _mp(batch.notional[i])
     for j in range(int(batch.flt_off[i]), int(batch.flt_off[i + 1])):
         tp, ts, te, al = (float(getattr(batch, name)[j]) for name in ("flt_tp", "flt_ts", "flt_te", "flt_alpha"))
-        if al > 0.0:
+        if al > 0.0 and z is not None:
             assert te == tp, "a ratio node: out of scope"
         if not tp >= 0.0:
             continue
         tau = None if flt_tau is None else float(flt_tau[j])
+        c = sn if batch.flt_weight is None else sn * _mp(batch.flt_weight[j])
         if al > 0.0:
-            out.append((ts, sn, tau))
-            out.append((tp, -sn, tau))
-        out.append((tp, sn * _mp(batch.spread[i]) * _mp(al), tau))
+            out.append((ts if te == tp else (ts, te, tp), c, tau))
+            out.append((tp, -c, tau))
+        out.append((tp, c * _mp(batch.spread[i]) * _mp(al), tau))
     return [term for term in out if term[1] != 0]
 
 
@@ -394,7 +468,7 @@ def _key(*arrays):
 
 
 _BATCH_FIELDS = ("fix_off", "flt_off", "fix_tp", "fix_pay", "flt_tp", "flt_ts", "flt_te", "flt_alpha", "notional", "spread",
-                 "fix_sign", "flt_sign")
+                 "fix_sign", "flt_sign", "flt_weight")
 _CACHE = {}
 
 
@@ -419,7 +493,7 @@ def rates_reference(method, host, batch, sub_off):
             sums = _Sums(cv, True)
             for i in range(int(lo), int(hi)):
                 for t, c, _ in trade_terms(batch, i):
-                    sums.add(t, c)
+                    sums.add_term(t, c)
             pv, delta, gamma = sums.blocks(tables)
             desks.append({"pv": pv, "delta": delta, "gamma": gamma, "n_terms": sums.n,
                           "k": bound_k(method, sums.n, compact_count(cv.x), float(sums.cond))})

@@ -174,25 +174,43 @@ def cases():
     return out
 
 
+def lagged(batch):
+    """Per trade: a coupon accrues to another date than it is paid on, or carries a weight != 1 (route.hpp, flag_lagged)."""
+    out = np.zeros(batch.n_trades, dtype=bool)
+    for t in range(batch.n_trades):
+        j = slice(int(batch.flt_off[t]), int(batch.flt_off[t + 1]))
+        out[t] = np.any((batch.flt_alpha[j] > 0.0) & (batch.flt_te[j] != batch.flt_tp[j])) or (
+            batch.flt_weight is not None and np.any(batch.flt_weight[j] != 1.0))
+    return out
+
+
 def row_class(batch):
-    """Per trade "fast" (one row of 32 slots), "fast_chained" (2 to 12 rows) or "general" (route.cpp, trade_layout; no trade
-    here has a payment lag or weights)."""
+    """Per trade "fast" (one row of 32 slots), "fast_chained" (2 to 12 rows) or "general" (route.cpp, trade_layout); a trade
+    with payment lag or weights: "fast_lag" (one row), "fast_lag_chained" (2 to 4 rows: 128 coupons) or "lag_rest"."""
     m = np.maximum(np.diff(batch.flt_off), np.diff(batch.fix_off))
     rows = np.maximum(1, -(-m // 32))
-    return np.where(rows == 1, "fast", np.where(rows <= 12, "fast_chained", "general"))
+    plain = np.where(rows == 1, "fast", np.where(rows <= 12, "fast_chained", "general"))
+    return np.where(lagged(batch), np.where(rows == 1, "fast_lag", np.where(rows <= 4, "fast_lag_chained", "lag_rest")), plain)
 
 
 def families(case, mask, per_trade, aggregate):
     """The kernel family that prices each trade of ``case`` under a request (route.hpp, make_plan, up to 32 pillars), [n] of
     str: with GAMMA per trade the fast kernels by row class where the curve has the packed layout, else the general kernel;
     PV / PV + delta per trade the lite kernel up to 384 coupons per leg; an aggregate-only request with DELTA or GAMMA the
-    knot pass for those; the general kernel for what is left."""
-    cls = row_class(case.batch)
+    knot pass for those; the general kernel for what is left.  A trade with payment lag or weights: with GAMMA per trade the
+    fast kernel's payment-lag variant up to 128 coupons where the curve has the packed layout, an even pillar count and a
+    log-linear scheme; without GAMMA `lite_lag` up to 390 coupons per leg (26 rows of 15), aggregate-only `knot_lag` for those
+    (every curve here has at most 256 reachable knots); the general kernel for what is left."""
+    batch = case.batch
+    cls = row_class(batch)
+    lag = lagged(batch)
     packed = LAYOUTS[case.curve][0][0]
+    m = np.maximum(np.diff(batch.flt_off), np.diff(batch.fix_off))
+    in_table = np.where(lag, m <= 390, cls != "general")
     if not per_trade and mask & 6:
-        short = "knot"
-    elif mask & 4:
-        return cls if packed else np.full(cls.shape, "general")
-    else:
-        short = "lite"
-    return np.where(cls == "general", "general", short)
+        return np.where(in_table, np.where(lag, "knot_lag", "knot"), "general")
+    if mask & 4:
+        use_lag = packed and case.interp != LF and case.host.jac.shape[1] % 2 == 0
+        plain = cls if packed else np.full(cls.shape, "general")
+        return np.where(lag, np.where(use_lag & (cls != "lag_rest"), cls, "general"), plain)
+    return np.where(in_table, np.where(lag, "lite_lag", "lite"), "general")

@@ -1,7 +1,9 @@
 """The bound the per-trade pricing kernels (`adr_price`: kernels_fast.hip, kernels_fast_lindf.hip, kernels_general.hip,
 kernels_lite.hip, kernels_knot.hip) are held to, element by element, on trades whose accruing coupons are paid on their accrual
 end: on one pillar tile (tests/test_price_edges_host.py, CPU, and tests/test_gpu_price_edges.py, GPU) and on the wide and tiled
-routes of 33 to 97 pillars (tests/test_price_wide_host.py and tests/test_gpu_price_wide.py; the families `wide` and `tiled`).
+routes of 33 to 97 pillars (tests/test_price_wide_host.py and tests/test_gpu_price_wide.py; the families `wide` and `tiled`);
+and, on one pillar tile, on trades with payment lag and per-coupon weights (tests/test_price_lag_host.py and
+tests/test_gpu_price_lag.py; "Payment lag and weights" below).
 
 The value and the gross of every element are `_ladder_reference.rates_reference`'s: per trade with ``sub_off = arange(n + 1)``,
 for the aggregate the one-desk row ``[0, n]``.  What is derived here is k of  |got - value| <= k 2^-53 gross  per kernel family,
@@ -86,6 +88,92 @@ knot (kernels_lite.hip KNOT instantiations, kernels_knot.hip; the book's aggrega
   waves (7), `knot_reduce_kernel` strides over the blocks and runs a butterfly (ceil(blocks / 64) - 1 + 6); three adds per knot
   of a projection wave's share ceil(Kc / 16), fifteen adds of the waves' sums, agg += (1), 1e-8 (2)
                              sums = N + 7 + ceil(blocks / 64) + 5 + 3 ceil(Kc / 16) + 18
+
+Payment lag and weights (tests/_price_lag_cases.py, tests/test_price_lag_host.py and tests/test_gpu_price_lag.py; one pillar tile).
+A coupon paid on another date than its accrual end is the RATIO node c D(ts) D(tp) / D(te), c = sl N w, plus the payment node
+-c (1 - spread al) D(tp); the reference has its terms (tests/_ladder_reference.py, "Ratio terms").  `trade_stats` reads two
+more numbers off the inputs: ``ratio``, the trade's ratio terms, and ``cond_lag``, the largest |L(ts)| + |L(te)| + |L(tp)| in
+weighted-knot form over the trade's accruing coupons, te == tp included - the payment-lag variants of the fast and lite
+kernels and the knot pass form exp(L(ts) - L(te) + L(tp)) for every accruing coupon of their rows (where te == tp the folded
+weights -b(te) + b(tp) are exactly 0: the same two numbers).  ``cond`` of a ratio term is that sum too (LINEAR_FWD_RATES: the
+largest |L_k|).  The node of a payment-lag family under a log scheme:
+  amount    c = sl N w: 2; the payment node's c (spread al - 1): 3 more, the fixed flow by fma: 1                          6
+  argument  three lookups fma(ba, L_a, bb L_b), each (e_w + 4) of its own |weight L|; their signed sum: 2 adds (fast, lite,
+            knot: ls - le + lp) or the one fma chain over the six knots, 5 adds and no separate lookups (general: e_w + 3
+            per product and 5) of the whole sum cond                                    cond (e_w + 6)  /  cond (e_w + 8)
+  exp       2;  omega = c exp(): 1                                                                                        3
+                                                                         node_lag = 9 + ceil(cond (e_w + 6 or 8))
+
+fast_lag, fast_lag_chained (kernels_fast.hip, LAG: the chunk passes and the date record):
+  v         a record's fma(wb, ub, wa ua): LJ (1), the weight (e_w) - the date record's has the accrual end's folded in,
+            ba -= e_ba (1) -, the product, the add: e_w + 4; vacc takes the start's and the end's (2), v1 = vacc + vr (1)
+                                                                                                                  e_w + 7
+  rank-one  fma(om u_i, v_q, acc): v twice, om u_i (1), the product (1)                                        2 e_w + 16
+  convexity coef = fma(om, wa, fma(om_p, wpa, om_s wsa)): the weight (e_w + 1), three products and two adds, the carried
+            weight (1), a packed row entry (4), the product: e_w + 12 of its own gross - less than the line above
+  special   a node without a packed entry for (r, c) leaves {v, om}; the output phase adds (om 1e-8) v_r v_c: v twice
+            (2 e_w + 14), the constant and three products (4) - the rank-one line with its scale, no more
+  sums      per coupon an entry takes the date record's rank-one term and the payment node's (2) and one row or short-end
+            number per record and knot (6): 8 adds for at least two terms (the ratio term and -c D(tp))               4 n
+  scale     acc 1e-8                                                                                                      2
+                                                                          k = node_lag(e_w + 6) + 2 e_w + 18 + 4 n
+
+general, a trade with ratio terms (kernels_general.hip, `add_nodes<6, ...>`; `general_lag` in `trade_k`; both variants):
+  v         fma(bb_i, lj_i, v) over six knots: LJ (1), the weight (e_w), te's folded into tp's entry b[jx] += b[i] (1), the
+            product, five adds                                                                                    e_w + 8
+  rank-one  vr = om v (1), fma(vr, vc): v twice, two products                                                  2 e_w + 18
+  convexity cf = om b (e_w + 2), the start weights handed to the previous coupon's entries (1), the payment node's joined
+            (1), the tile (4), the product: e_w + 9 of its own gross, less
+  sums      per coupon the rank-one term, six tiles, and the payment node's rank-one term and two tiles: 10 adds for at
+            least two terms                                                                                             5 n
+  scale 2, the merge of the flat convexity sums 1                     k = node_lag(e_w + 8) + 2 e_w + 20 + 5 n + 1
+  LINEAR_FWD_RATES (`lindf_knots` and `add_cross`: the weights rho = d ln D / d ln d_k of each date): a lookup's
+  d = da + w (db - da) on da = exp(L_a): 2 cond + 2 each, the difference, the product, the sum: 2 cond + 5; ln d = log(d): 2
+  units of |ln d| <= cond and d's own: 4 cond + 5 per date, 12 cond + 15 for three, the two adds of l (of at most 3 cond): 6
+  cond; exp (2), c (2), the product (1)                                                     node = ceil(18 cond) + 20
+  rho_b = w db / d: 4 cond + 9; rho_a = 1 - rho_b takes rho_b's ABSOLUTE error, which `wr` brings into units of the gross
+                                                                                     e_rho = ceil((4 cond + 9) wr)
+  a knot's single-knot node: the amount om rho_k (e_rho + 1; te's folded into tp's: 1), v the Jacobian entry itself (1),
+  vr = om v (1), fma(vr, vc) (LJ 1 + 1): e_rho + 6; the cross term om (x y^T + y x^T): x and y are fma chains over the node's
+  knots (LJ, e_rho, the product, at most five adds: e_rho + 7), om x (1), the product (1): 2 e_rho + 16 - the line that counts
+  sums      per coupon six single-knot nodes (a rank-one term and a row each: 12), two cross terms of two products (4) and
+            the payment node's two knots (4): 20 adds for at least two terms, the merge 1; scale 2
+                                                          k = ceil(18 cond) + 20 + 2 e_rho + 18 + 10 n + 1
+  (Until this bound was applied the kernel walked such a node in the rho form of ln f, om (v v^T + sum over the dates of
+  +-rho_a rho_b (LJ_a - LJ_b)(LJ_a - LJ_b)^T): the products rho_a rho_b LJ_a,p LJ_b,q of ONE date stand in v v^T and in the
+  date's correction with opposite signs and cancel only up to rounding - 2e-23 to 4e-19 on gamma entries no term reaches, and
+  on the others an error the reference's gross does not hold.  tests/test_gpu_price_lag.py found it on four books; DESIGN.md
+  section 33.)
+
+lite_lag (kernels_lite.hip, LAG; PV and delta; INV_DX, so e_w' = e_w + ceil(3 wr)):
+  node_lag with e_w' and (e_w' + 6); a chained start takes the previous lane's L(te): the same number
+  entries   om_r b(ts): e_w' + 1; the end's (next_om - om_r) b(te): the difference (1), e_w' + 1; the date's (om_r + om_p)
+            b(tp) likewise: e_w' + 2;  fma(c, LJ, d): LJ (1), the product (1)                                     e_w' + 4
+  sums      three sweeps of two entries per coupon: 6 adds for at least two terms: 3 n; d0 + e0 (1), 1e-4 (2)
+                                                                          k = node_lag' + e_w' + 7 + 3 n
+  LINEAR_FWD_RATES ("effective log weights"): a factor F = ba D_a + bb D_b: a part ba exp(L_a) is e_w' + 2 cond + 3, F one
+  more, g = part (1 / F): 2 e_w' + 4 cond + 9; om_r = c ls lp / le: three factors (e_w' + 2 cond + 4), c (2), three
+  operations; the entry om g (1 + 1), LJ and the product (2); the sums as above
+                                                          k = 5 e_w' + ceil(10 cond) + 33 + 3 n
+
+knot_lag (kernels_lite.hip KNOT + LAG, kernels_knot.hip): a trade's part of W += om_r u_k u_l holds the merge of the date's
+  weights into the end's cc[2] += cc[4] (1) and two weights and two products: 2 e_w' + 5; the projection's two Jacobian
+  entries and two products, the band term one more: 2 e_w' + 8 with the node           k_t = node_lag' + 2 e_w' + 8
+  LINEAR_FWD_RATES: om_r (3 (e_w' + 2 cond + 4) + 5), two effective weights (2 (2 e_w' + 4 cond + 9)), two products, the
+  projection (5)                                                          k_t = 7 e_w' + ceil(14 cond) + 42
+  (the sums are the general kernel's reduced form in knot space: a knot's own amount on the diagonal, products of two
+  different factors' weights on the pairs.  Until this bound was applied they were u u^T plus `factor_curvature`, the rho
+  form: -w and +w on one pair of knots from every coupon of an interval, 1.6e-22 on a structural zero of agg_gamma.)
+  sums      a table entry takes at most 7 adds per coupon (log schemes: three squares or pairs of the ratio node on one slot
+            and the payment node's; LINEAR_FWD_RATES: four diagonal amounts and three pairs at distance 0): 4 N for at least
+            two terms each; the block's 8 waves (7) and
+            `knot_reduce_kernel` as for `knot`; the projection adds D_k and w_k LC per knot of a wave's share (2 ceil(Kc /
+            16)) and one term per non-zero pair entry, band or overflow matrix - at most 15 per ratio node and one per
+            payment node (15 R + N); the waves' sums (15), agg += (1), 1e-8 (2)
+                             sums = 4 N + 7 + ceil(blocks / 64) + 5 + 2 ceil(Kc / 16) + 15 R + N + 18  (`knot_lag_sums`)
+  The overflow matrix (pairs of knots more than 16 apart) is filled with atomic adds from every wave: the order of those
+  adds, and so the last bits of an aggregate-only gamma, depend on scheduling - any order of m numbers costs m - 1 roundings,
+  which the 4 N above holds.
 
 aggregate (the one-desk row): trade t arrives with an error of at most k_t units of ITS gross, so an element of the book is
   held to  k = ceil(sum_t k_t gross_t / gross_book) + sums  of the book's gross (`book_k`; exact integer arithmetic) - one
@@ -179,11 +267,23 @@ def trade_stats(method, host, batch):
             return seen[t]
         out = []
         for i in range(batch.n_trades):
-            st = dict(n=0, cond=0.0, wr=1.0)
+            st = dict(n=0, cond=0.0, wr=1.0, ratio=0)
             for t, c, _ in R.trade_terms(batch, i):
                 st["n"] += 1
-                st["cond"] = max(st["cond"], float(cv.date(t)[3]))
-                st["wr"] = max(st["wr"], lookup(float(t)))
+                dates = t if isinstance(t, tuple) else (t,)
+                conds = [float(cv.date(d)[3]) for d in dates]
+                if isinstance(t, tuple):
+                    st["ratio"] += 1
+                st["cond"] = max(st["cond"], max(conds) if method_ == LINEAR_FWD else sum(conds))
+                st["wr"] = max(st["wr"], max(lookup(float(d)) for d in dates))
+            # the payment-lag variants form exp(L(ts) - L(te) + L(tp)) for EVERY accruing coupon, te == tp included
+            st["cond_lag"] = st["cond"]
+            st["weighted"] = batch.flt_weight is not None and bool(np.any(batch.flt_weight[int(batch.flt_off[i]):int(batch.flt_off[i + 1])] != 1.0))
+            for j in range(int(batch.flt_off[i]), int(batch.flt_off[i + 1])):
+                live = float(batch.flt_alpha[j]) > 0.0 and float(batch.flt_tp[j]) >= 0.0
+                if live and method_ != LINEAR_FWD and (batch.flt_weight is None or float(batch.flt_weight[j]) != 0.0):
+                    three = sum(float(cv.date(float(getattr(batch, f)[j]))[3]) for f in ("flt_ts", "flt_te", "flt_tp"))
+                    st["cond_lag"] = max(st["cond_lag"], three)
             out.append(st)
         return out
     return R._cached("price stats", method, host, batch, (), build)
@@ -196,7 +296,8 @@ def _node(method, cond, e_w):
 
 
 def trade_k(family, method, st):
-    """k of one trade priced by ``family`` ("fast", "fast_chained", "general", "wide", "tiled", "lite")."""
+    """k of one trade priced by ``family`` ("fast", "fast_chained", "general", "wide", "tiled", "lite"; with payment lag or
+    weights "fast_lag", "fast_lag_chained", "lite_lag" and "general_lag", the general kernel on a trade with ratio terms)."""
     method = int(method)
     e_w, n, cond = E_W[method], st["n"], st["cond"]
     if family in ("fast", "fast_chained", "general", "wide", "tiled"):
@@ -207,17 +308,45 @@ def trade_k(family, method, st):
     if family == "lite":
         e_w += math.ceil(3 * st["wr"])
         return _node(method, cond, e_w) + e_w + 6 + 2 * n
+    if family in ("fast_lag", "fast_lag_chained"):
+        assert method != LINEAR_FWD, "the payment-lag variant of the fast kernel serves the log-linear schemes"
+        return _node_lag(st["cond_lag"], e_w, 6) + 2 * e_w + 18 + 4 * n
+    if family == "general_lag":
+        if method == LINEAR_FWD:
+            e_rho = math.ceil((4 * cond + 9) * st["wr"])
+            return math.ceil(18 * cond) + 20 + 2 * e_rho + 18 + 10 * n + 1
+        return _node_lag(cond, e_w, 8) + 2 * e_w + 20 + 5 * n + 1
+    if family == "lite_lag":
+        e_w += math.ceil(3 * st["wr"])
+        if method == LINEAR_FWD:
+            return 5 * e_w + math.ceil(10 * cond) + 33 + 3 * n
+        return _node_lag(st["cond_lag"], e_w, 6) + e_w + 7 + 3 * n
     raise ValueError(family)
 
 
-def knot_trade_k(method, st):
-    """k_t of one trade in the knot pass."""
+def _node_lag(cond, e_w, adds):
+    """The node of a payment-lag family under a log scheme: 9 + ceil(cond (e_w + adds)) (module docstring)."""
+    return 9 + math.ceil(cond * (e_w + adds))
+
+
+def knot_trade_k(method, st, lag=False):
+    """k_t of one trade in the knot pass (``lag``: the pass over the payment-lag rows)."""
     e_w = E_W[int(method)] + math.ceil(3 * st["wr"])
+    if lag and int(method) == LINEAR_FWD:
+        return 7 * e_w + math.ceil(14 * st["cond"]) + 42
+    if lag:
+        return _node_lag(st["cond_lag"], e_w, 6) + 2 * e_w + 8
     return _node(method, st["cond"], e_w) + 2 * e_w + 7
 
 
 def knot_sums(stats, Kc, blocks):
     return sum(s["n"] for s in stats) + 7 + -(-max(blocks, 1) // 64) + 5 + 3 * (-(-Kc // 16)) + 18
+
+
+def knot_lag_sums(stats, Kc, blocks):
+    """The adds of the pass over the payment-lag rows and its share of the projection (module docstring, `knot_lag`)."""
+    N, ratios = sum(s["n"] for s in stats), sum(s["ratio"] for s in stats)
+    return 4 * N + 7 + -(-max(blocks, 1) // 64) + 5 + 2 * (-(-Kc // 16)) + 15 * ratios + N + 18
 
 
 def aggregate_sums(n_trades, blocks, wide=False):
@@ -266,10 +395,13 @@ def case_ks(method, host, batch, ref, fams):
     stats = trade_stats(method, host, batch)
     out = []
     for i, fam in enumerate(fams):
-        if fam == "knot":
-            out.append(knot_trade_k(method, stats[i]))
+        if fam in ("knot", "knot_lag"):
+            out.append(knot_trade_k(method, stats[i], lag=fam == "knot_lag"))
             continue
-        out.append(trade_k(fam, method, stats[i]))
+        # the general kernel walks a trade with ratio terms through `add_nodes<6, ...>`: its own count
+        # (a weighted coupon paid on its accrual end is a plain node of amount N w: one product more)
+        plain_weighted = fam == "general" and not stats[i]["ratio"] and stats[i]["weighted"]
+        out.append(trade_k("general_lag" if fam == "general" and stats[i]["ratio"] else fam, method, stats[i]) + int(plain_weighted))
     return out
 
 
