@@ -1234,8 +1234,11 @@ int adr_price_xccy_foreign_dev(adr_ctx* ctx, const adr_curve* foreign_curve, con
     o.block_partials = want_agg ? ctx->partials : nullptr;
     o.block_partials2 = want_agg ? ctx->partials + static_cast<size_t>(blocks) * adr::kAggStride : nullptr;
     ADR_HIP(adr::launch_price_lite_xc(cf, cx, rows, o, blocks, stream));
-    if (agg_foreign_dev) ADR_HIP(adr::launch_reduce_partials(o.block_partials, blocks, Pf, false, agg_foreign_dev, stream));
-    if (agg_basis_dev) ADR_HIP(adr::launch_reduce_partials(o.block_partials2, blocks, Px, false, agg_basis_dev, stream));
+    // (the kernel is built with DELTA only, so its block records always carry the delta sums: a request without DELTA drops
+    // them in the reduction, which writes +0.0 there as adr_price does for a block that is not asked for)
+    const bool has_delta = (req_mask & ADR_REQ_DELTA) != 0;
+    if (agg_foreign_dev) ADR_HIP(adr::launch_reduce_partials(o.block_partials, blocks, Pf, false, agg_foreign_dev, stream, 0, 0, has_delta));
+    if (agg_basis_dev) ADR_HIP(adr::launch_reduce_partials(o.block_partials2, blocks, Px, false, agg_basis_dev, stream, 0, 0, has_delta));
     return ADR_OK;
 }
 

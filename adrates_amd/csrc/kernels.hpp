@@ -296,8 +296,10 @@ hipError_t launch_knot_project(const CurveDev& cv, const double* partials, int n
 // has_gamma == false: the gamma part of the partials was not written (no gamma requested); agg's gamma part is zeroed
 // (tile_i, tile_j): the pillar tile pair the partials belong to (0, 0 for P <= 32); off-diagonal tiles are also written
 // transposed; pv comes from tile (0, 0), delta from the diagonal tiles
+// has_delta == false: the request has no DELTA but the records carry delta sums (the two-curve launch is built with DELTA
+// only); agg's delta part is zeroed as well, in the same pass
 hipError_t launch_reduce_partials(const double* partials, int n_blocks, int P, bool has_gamma, double* agg,
-                                  hipStream_t stream, int tile_i = 0, int tile_j = 0);
+                                  hipStream_t stream, int tile_i = 0, int tile_j = 0, bool has_delta = true);
 
 // Schedule groups (kernels_combine.hip): the members' ladders from their group's two basis ladders; GroupRecord and
 // GroupSegment: schedule_groups.hpp.

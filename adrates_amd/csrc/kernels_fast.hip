@@ -1214,7 +1214,8 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const double* part
         }
     }
     if (at < 0) return;
-    if (!has_gamma && i >= 1 + kPillarPad) {      // nothing was accumulated there: the launches ran without GAMMA
+    // has_gamma bit 0: the gamma part was accumulated; bit 1: the delta part is NOT asked for (its sums are dropped)
+    if ((!(has_gamma & 1) && i >= 1 + kPillarPad) || ((has_gamma & 2) && i >= 1)) {      // nothing was accumulated there, or nothing is wanted
         if (lane == 0) { agg[at] = 0.0; if (mirror >= 0) agg[mirror] = 0.0; }
         return;
     }
@@ -1341,9 +1342,9 @@ hipError_t launch_price_fast(const CurveDev& cv, const TradesDev& tr, const Outp
 }
 
 hipError_t launch_reduce_partials(const double* partials, int n_blocks, int P, bool has_gamma, double* agg,
-                                  hipStream_t stream, int tile_i, int tile_j) {
+                                  hipStream_t stream, int tile_i, int tile_j, bool has_delta) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((kAggStride + 3) / 4), dim3(256), 0, stream, partials, n_blocks, P,
-                       has_gamma ? 1 : 0, agg, tile_i, tile_j);
+                       (has_gamma ? 1 : 0) | (has_delta ? 0 : 2), agg, tile_i, tile_j);
     return hipGetLastError();
 }
 

@@ -362,7 +362,8 @@ int adr_price_dev(adr_ctx* ctx, const adr_curve* curve, const adr_trades* trades
  * FOREIGN currency (the caller converts the results with 1 / spot, as the reference does at :1713, :1733).  A coupon is
  * N ((D_f(ts) / D_f(te) - 1) + spread alpha) D_x(tp): pv [n]; delta_foreign [n * P_f] = d pv / d (foreign par rates) with the
  * XCCY curve held fixed (:1702-1712); delta_basis [n * P_x] = d pv / d (basis spreads); per bp.  agg_foreign / agg_basis: the
- * book sums in adr_price's layout ([pv, delta[P], zeros]; the PV total sits in agg_foreign[0]).  VALUE / DELTA only
+ * book sums in adr_price's layout ([pv, delta[P], zeros]; the PV total sits in agg_foreign[0], agg_basis[0] is +0.0; without
+ * ADR_REQ_DELTA in req_mask words 1 .. P of both are +0.0, as adr_price returns a block that is not asked for).  VALUE / DELTA only
  * (ADR_ERR_UNSUPPORTED with GAMMA: use three batches - adr_trades_upload_weighted - and adr_price); both curves up to 32
  * pillars, both on LINEAR_FWD_RATES or both on a log-linear scheme; every leg at most 390 coupons with some accrual end != payment time.
  * The _dev form enqueues on `stream` and neither allocates nor synchronises.

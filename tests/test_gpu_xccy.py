@@ -1,5 +1,10 @@
 """XCCY basis swap analytics through the HIP kernels against the torch-autodiff restatement of
-Engine._compute_xccy (oracle/xccy_oracle.py::xccy_analytics; cavour/market/position/engine.py:1411-1988)."""
+Engine._compute_xccy (oracle/xccy_oracle.py::xccy_analytics; cavour/market/position/engine.py:1411-1988).
+
+The two-curve foreign-leg launch (`adr_price_xccy_foreign`) is checked here on market swaps and a drawn book at 1e-10 of a
+ladder's largest entry; tests/test_gpu_xccy_foreign.py holds every element of it to the plain 60-digit reference on a counted
+bound, at the shapes these books miss (dates on and beside knots, curves of different K and P, row boundaries, weights, partly
+filled units, every XC instantiation, the aggregates' records)."""
 import numpy as np
 import pytest
 

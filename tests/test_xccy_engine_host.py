@@ -52,7 +52,7 @@ def _host_no_two_curve_launch(ctx, *a, **k):
     """The two-curve foreign-leg launch (adr_price_xccy_foreign) has no C restatement: the stand-in answers as the library
     does for a book the launch does not take (ADR_ERR_UNSUPPORTED), so these tests run the three-batch assembly - the
     fallback of the product path.  The one-launch path is compared with it and with the oracle on the GPU
-    (tests/test_gpu_xccy.py)."""
+    (tests/test_gpu_xccy.py), and held element by element to a plain 60-digit reference in tests/test_gpu_xccy_foreign.py."""
     from adrates_amd.utils.error import LibError
     raise LibError("adr_price_xccy_foreign failed (-2): no two-curve launch on the host stand-in",
                    status=_native.ADR_ERR_UNSUPPORTED)
